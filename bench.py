@@ -8,6 +8,13 @@ A step = one search batch of --nq queries (default 16, the HBM-bound headline
 batch of SURVEY.md 8d) against the whole index, inputs resident in HBM.  With N
 GPUs the 1M rows are row-sharded (strong scaling) and a step also contains the
 one all-gather + merge.  Prints ONE JSON line (rank 0).
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed
+steps, the result line.  --full adds the rest: roofline and per-kernel
+figures, batch latency, board power, the CPU baseline and the parity gate
+against the CPU oracle.  --dump-outputs DIR writes the distances and ids of
+the last timed step (DIR/distances.npy float32, DIR/ids.npy float64) so that
+two builds can be compared output for output.
 """
 import argparse
 import json
@@ -189,6 +196,26 @@ def cpu_baseline(xb, xq, k, budget_s=12.0):
     }
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, D, I):
+    """What the caller of the timed path receives for one batch: D (nq, k) float32 distances, I (nq, k) int64 ids,
+    the ids stored as float64 (exact below 2**53).  Above DUMP_MAX_BYTES a fixed, seeded sample of query rows is
+    written instead, and its row numbers go to query_rows.npy."""
+    nq, k = D.shape
+    budget = DUMP_MAX_BYTES - 4096  # room for the .npy headers
+    rows = None
+    if nq * k * (4 + 8) > budget:
+        rows = np.sort(np.random.default_rng(0).choice(nq, budget // (k * (4 + 8) + 8), replace=False))
+        D, I = D[rows], I[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "distances.npy"), np.ascontiguousarray(D, dtype=np.float32))
+    np.save(os.path.join(out_dir, "ids.npy"), np.ascontiguousarray(I, dtype=np.float64))
+    if rows is not None:
+        np.save(os.path.join(out_dir, "query_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     # stdout carries exactly one line, the JSON result: whatever libraries print there on the way
     # (RCCL writes a version banner to stdout when a communicator is created) goes to stderr instead
@@ -204,9 +231,15 @@ def main():
     ap.add_argument("--d", type=int, default=512)
     ap.add_argument("--nq", type=int, default=16)
     ap.add_argument("--k", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline, no parity gate")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, latency, board power, CPU baseline and parity gate figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's distances and ids to DIR/*.npy")
     args = ap.parse_args()
 
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if not 1 <= args.k <= 32:
         raise SystemExit("bench.py times one scan pass per batch: 1 <= k <= 32 (larger k is covered by the tests)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -325,64 +358,69 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
 
-    # roofline of the dominant kernel (the shard-local scan), timed with HIP events on
-    # the stream it runs on, inside the library
-    n_local = hi - lo
-    _, _, scan_ms, merge_ms = local.search_timed_torch(xq, k, 50 if nq <= 64 else 10)
-    alg_bytes = 4.0 * n_local * d + 4.0 * nq * d + 12.0 * nq * k
-    achieved = alg_bytes / (scan_ms * 1e-3) / 1e9
-    # batches of >= 256 queries take the GEMM-shaped pass (csrc/ise_gemm_scan.hpp): MFMA-bound, priced in flops
-    gemm_batch = local.exact_stats().get("gemm_chunks", 0) > 0
-    alg_flops = 2.0 * nq * n_local * d
-    # which kernel scanned the rows (the dominant kernel of the step)
-    if gemm_batch:
-        kernel_name = "gemm_scan_kernel (threshold sample + main pass)"
-    elif local.host_stats()["direct_queries"] > 0:
-        kernel_name = "exact_scan_kernel<1, nt> (one-query batches: the direct-difference scan is the whole search)"
-    elif local.short_stats()["short_batches"] > 0:
-        kernel_name = "short_scan_kernel (short index: scores dumped to LDS, one selection per block)"
-    else:
-        kernel_name = "scan_kernel"
-
-    # per-batch latency (median + p10/p90): one batch at a time on one stream, an
-    # event pair around scan + merge.  Single-GPU runs only; the timed region above is the metric.
-    latency = None
-    if not sharded:
-        s0 = streams[0]
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(100)]
-        for e0, e1 in evs:
-            e0.record(s0)
-            index.search_into(xq, k, outs[0][0], outs[0][1], s0.cuda_stream)
-            e1.record(s0)
-        torch.cuda.synchronize()
-        us = np.sort(np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in evs]))
-        latency = {"p10": float(us[10]), "median": float(us[50]), "p90": float(us[90]),
-                   "what": "one batch at a time on one stream: scan + merge, HIP event pair per batch, 100 batches"}
-    # board power under the same steps, sustained (untimed, after everything that is timed): the hwmon figure is
-    # a moving average that needs about a second of load to settle, the K timed steps are over in milliseconds
-    board_power = None
-    if not sharded and nq <= 64:
-        power = BoardPower(dev.index if dev.index is not None else 0)
-        t_seg = time.perf_counter()
-        while time.perf_counter() - t_seg < 2.0:
-            run(200)
-            torch.cuda.synchronize()
-        board_power = power.stop(t_seg + 1.2)
-
-    # N > 1: what a SCALE record needs to describe itself -- every rank's own shard roofline, the collective in
-    # use and the ranks it reached, and the check that all ranks issued the same sequence of all-gathers.
-    # Then the communicator and the process group go away BEFORE rank 0 regenerates the index and runs the
-    # CPU oracle pass (15-20 s): the other ranks are not parked in a barrier meanwhile.
-    multi = None
+    # what the caller of the timed path received for the last timed step, before anything else touches the
+    # output buffers
     D_host, I_host = D.cpu(), I.cpu()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, D_host.numpy(), I_host.numpy())
+
+    n_local = hi - lo
+    latency = board_power = multi = None
+    if args.full:
+        # roofline of the dominant kernel (the shard-local scan), timed with HIP events on
+        # the stream it runs on, inside the library
+        _, _, scan_ms, merge_ms = local.search_timed_torch(xq, k, 50 if nq <= 64 else 10)
+        alg_bytes = 4.0 * n_local * d + 4.0 * nq * d + 12.0 * nq * k
+        achieved = alg_bytes / (scan_ms * 1e-3) / 1e9
+        # batches of >= 256 queries take the GEMM-shaped pass (csrc/ise_gemm_scan.hpp): MFMA-bound, priced in flops
+        gemm_batch = local.exact_stats().get("gemm_chunks", 0) > 0
+        alg_flops = 2.0 * nq * n_local * d
+        # which kernel scanned the rows (the dominant kernel of the step)
+        if gemm_batch:
+            kernel_name = "gemm_scan_kernel (threshold sample + main pass)"
+        elif local.host_stats()["direct_queries"] > 0:
+            kernel_name = "exact_scan_kernel<1, nt> (one-query batches: the direct-difference scan is the whole search)"
+        elif local.short_stats()["short_batches"] > 0:
+            kernel_name = "short_scan_kernel (short index: scores dumped to LDS, one selection per block)"
+        else:
+            kernel_name = "scan_kernel"
+
+        # per-batch latency (median + p10/p90): one batch at a time on one stream, an
+        # event pair around scan + merge.  Single-GPU runs only; the timed region above is the metric.
+        if not sharded:
+            s0 = streams[0]
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(100)]
+            for e0, e1 in evs:
+                e0.record(s0)
+                index.search_into(xq, k, outs[0][0], outs[0][1], s0.cuda_stream)
+                e1.record(s0)
+            torch.cuda.synchronize()
+            us = np.sort(np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in evs]))
+            latency = {"p10": float(us[10]), "median": float(us[50]), "p90": float(us[90]),
+                       "what": "one batch at a time on one stream: scan + merge, HIP event pair per batch, 100 batches"}
+        # board power under the same steps, sustained (untimed, after everything that is timed): the hwmon figure is
+        # a moving average that needs about a second of load to settle, the K timed steps are over in milliseconds
+        if not sharded and nq <= 64:
+            power = BoardPower(dev.index if dev.index is not None else 0)
+            t_seg = time.perf_counter()
+            while time.perf_counter() - t_seg < 2.0:
+                run(200)
+                torch.cuda.synchronize()
+            board_power = power.stop(t_seg + 1.2)
+
+    # N > 1: what a SCALE record needs to describe itself (--full) -- every rank's own shard roofline, the
+    # collective in use and the ranks it reached, and the check that all ranks issued the same sequence of
+    # all-gathers.  Then the communicator and the process group go away BEFORE rank 0 regenerates the index and
+    # runs the CPU oracle pass (15-20 s): the other ranks are not parked in a barrier meanwhile.
     if sharded:
-        mine = {"rank": rank, "rows": n_local, "kernel_ms": scan_ms, "achieved_gbs": achieved,
-                "frac": achieved / HBM_PEAK_GBS}
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
-        order = index.check_collective_order()   # raises on every rank if the sequences differ
-        multi = {"per_rank_roofline": per_rank, "collective": index.collective, "ranks_seen": index.ranks_seen,
-                 "collective_order": order}
+        if args.full:
+            mine = {"rank": rank, "rows": n_local, "kernel_ms": scan_ms, "achieved_gbs": achieved,
+                    "frac": achieved / HBM_PEAK_GBS}
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine)
+            order = index.check_collective_order()   # raises on every rank if the sequences differ
+            multi = {"per_rank_roofline": per_rank, "collective": index.collective, "ranks_seen": index.ranks_seen,
+                     "collective_order": order}
         if index.comm is not None:  # the library's communicator goes before the process group that bootstrapped it
             torch.cuda.synchronize()
             barrier()
@@ -411,31 +449,33 @@ def main():
                                    + f"; {CLOCK_WARMUP_STEPS} untimed steps ahead of the warm-up bring the GPU out of "
                                      f"its idle power state",
                        "n": n, "d": d, "k": k, "nq": nq},
-            "roofline": {"bound": "mfma" if gemm_batch else "hbm",
-                         "achieved": alg_flops / (scan_ms * 1e-3) / 1e12 if gemm_batch else achieved,
-                         "peak": MFMA_F32_PEAK_TF if gemm_batch else HBM_PEAK_GBS,
-                         "unit": "TFLOP/s" if gemm_batch else "GB/s",
-                         "frac": (alg_flops / (scan_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TF) if gemm_batch
-                         else achieved / HBM_PEAK_GBS,
-                         "traffic": pmc_traffic(n, d, nq, k, world),
-                         "kernel": kernel_name,
-                         "kernel_overlap": committed_overlap(n, d, nq, k, world),
-                         "kernel_ms": scan_ms, "merge_kernel_ms": merge_ms, "board_power": board_power,
-                         "algorithmic_bytes": alg_bytes, "algorithmic_flops": alg_flops,
-                         # the same bytes over the measured step time (batches overlapped on the GPU):
-                         # what the whole step sustains, beside the isolated kernel's figure above
-                         "step_effective": {"achieved": alg_bytes / (el / args.steps) / 1e9,
-                                            "frac": alg_bytes / (el / args.steps) / 1e9 / HBM_PEAK_GBS},
-                         "kernel_ms_source": "50 back-to-back launches on one stream, HIP events around the kernel "
-                                             "(ise_index_search_timed_device); merge_kernel_ms = everything behind "
-                                             "the scan (merge + exact re-rank + the gated exact-scan launches); "
-                                             f"rocprofv3 agreement: profiles/{PROFILE_ROUND}/ (kernel_stats CSVs, README.md)"},
         }
+        if args.full:
+            res["roofline"] = {"bound": "mfma" if gemm_batch else "hbm",
+                               "achieved": alg_flops / (scan_ms * 1e-3) / 1e12 if gemm_batch else achieved,
+                               "peak": MFMA_F32_PEAK_TF if gemm_batch else HBM_PEAK_GBS,
+                               "unit": "TFLOP/s" if gemm_batch else "GB/s",
+                               "frac": (alg_flops / (scan_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TF) if gemm_batch
+                               else achieved / HBM_PEAK_GBS,
+                               "traffic": pmc_traffic(n, d, nq, k, world),
+                               "kernel": kernel_name,
+                               "kernel_overlap": committed_overlap(n, d, nq, k, world),
+                               "kernel_ms": scan_ms, "merge_kernel_ms": merge_ms, "board_power": board_power,
+                               "algorithmic_bytes": alg_bytes, "algorithmic_flops": alg_flops,
+                               # the same bytes over the measured step time (batches overlapped on the GPU):
+                               # what the whole step sustains, beside the isolated kernel's figure above
+                               "step_effective": {"achieved": alg_bytes / (el / args.steps) / 1e9,
+                                                  "frac": alg_bytes / (el / args.steps) / 1e9 / HBM_PEAK_GBS},
+                               "kernel_ms_source": "50 back-to-back launches on one stream, HIP events around the "
+                                                   "kernel (ise_index_search_timed_device); merge_kernel_ms = "
+                                                   "everything behind the scan (merge + exact re-rank + the gated "
+                                                   "exact-scan launches); rocprofv3 agreement: "
+                                                   f"profiles/{PROFILE_ROUND}/ (kernel_stats CSVs, README.md)"}
         if latency is not None:
             res["batch_latency_us"] = latency
         if multi is not None:
             res["multi_gpu"] = multi
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             from oracle import flat_oracle as fo
 
             fo.build()

@@ -38,7 +38,7 @@ write = raw[scan[0]]["WRITE_SIZE"]["mean_KB"] * 1024.0
 alg = 4.0 * n * d + 4.0 * nq * d + 12.0 * nq * k
 rec = {
     "command": "ISE_BENCH_STREAMS=1 scripts/profile_bench.sh <tag> [bench args]: rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE "
-               "(separate passes) -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline [bench args]",
+               "(separate passes) -- python3 bench.py --steps 50 --warmup 5 --full --no-cpu-baseline [bench args]",
     "workload": f"{n}x{d} fp32, L2, k={k}, nq={nq}, 1 GPU",
     "kernel": scan[0],
     "kernel_source_hash": kernel_source_hash(),

@@ -12,7 +12,7 @@ OUT=$REPO/gpurun_out/prof_$TAG
 DST=$REPO/gpurun_out/profiles_r03
 mkdir -p "$OUT" "$DST"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--n $N --nq $NQ --no-cpu-baseline $*"
+ARGS="--n $N --nq $NQ --full --no-cpu-baseline $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace16" -- python3 "$REPO/bench.py" $ARGS --steps 2000 --warmup 50 > "$OUT/trace16.log" 2>&1
 python3 "$REPO/scripts/overlap_from_trace.py" "$(find "$OUT/trace16" -name '*kernel_trace.csv' | head -1)" --kernel "$KPREFIX" --last 1500 \
     --json "$DST/bench_n${N}_nq${NQ}_streams16_overlap.json" > /dev/null

@@ -7,8 +7,8 @@ mkdir -p "$DST"
 cd "$REPO"
 scripts/profile_r03.sh n1m_nq1 1000000 1 "void exact_scan_kernel<1" > "$DST/profile_n1m_nq1.log" 2>&1
 scripts/profile_r03.sh n125k_nq16 125000 16 "void short_scan_kernel" > "$DST/profile_n125k_nq16.log" 2>&1
-python bench.py --nq 1 --steps 200 --warmup 20 --no-cpu-baseline > "$DST/bench_nq1.json" 2> "$DST/bench_nq1.err"
-python bench.py --nq 1024 --steps 20 --warmup 5 --no-cpu-baseline > "$DST/bench_nq1024.json" 2> "$DST/bench_nq1024.err"
+python bench.py --full --nq 1 --steps 200 --warmup 20 --no-cpu-baseline > "$DST/bench_nq1.json" 2> "$DST/bench_nq1.err"
+python bench.py --full --nq 1024 --steps 20 --warmup 5 --no-cpu-baseline > "$DST/bench_nq1024.json" 2> "$DST/bench_nq1024.err"
 ISE_BENCH_FORCE_SHARDED=1 scripts/profile_trace.sh r03_sh125k --n 125000 --steps 400 --warmup 40 > /dev/null 2>&1
 cp "$(find gpurun_out/prof_r03_sh125k -name '*kernel_stats.csv' | head -1)" "$DST/sharded_rehearsal_world1_125k_kernel_stats.csv"
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # chunk size x ring depth of the short-index kernel (dev build), 16-wave blocks; and the crossover against the
 # streaming kernel for indexes between 131k and 262k rows (two 8-wave blocks per CU there)
 export ISE_KNN_LIB=$PWD/image-search-engine_amd/csrc/libise_knn_ablate.so
-run() { python bench.py $2 --steps 2000 --warmup 50 --no-cpu-baseline 2>/dev/null | python -c "
+run() { python bench.py --full $2 --steps 2000 --warmup 50 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read()); rf=r['roofline']
 print('$1 $2: us/step %.1f kernel_us %.1f behind %.1f lat %.1f'%(r['ms_per_step']*1e3, rf['kernel_ms']*1e3, rf['merge_kernel_ms']*1e3, r['batch_latency_us']['median']))"; }

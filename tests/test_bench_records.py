@@ -133,3 +133,31 @@ def test_pmc_reduction_calibrates_reads_on_the_known_copy(tmp_path):
     import bench
 
     assert rec["kernel"] == kname and rec["kernel_source_hash"] == bench.kernel_source_hash()
+
+
+def test_dump_outputs_formats_and_size_cap(tmp_path, monkeypatch):
+    """--dump-outputs: distances as float32 and ids as float64, bit for bit; above the size cap a seeded sample of
+    query rows (the same on every run, its row numbers beside it) that keeps the files under the cap."""
+    import numpy as np
+
+    import bench
+
+    rng = np.random.default_rng(3)
+    D = rng.random((16, 10), dtype=np.float32)
+    I = rng.integers(-1, 1_000_000, (16, 10))
+    bench.dump_outputs(str(tmp_path / "small"), D, I)
+    assert sorted(os.listdir(tmp_path / "small")) == ["distances.npy", "ids.npy"]
+    d, i = np.load(tmp_path / "small" / "distances.npy"), np.load(tmp_path / "small" / "ids.npy")
+    assert d.dtype == np.float32 and i.dtype == np.float64
+    assert np.array_equal(d, D) and np.array_equal(i.astype(np.int64), I)
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 20)
+    D = rng.random((20000, 10), dtype=np.float32)
+    I = rng.integers(0, 1_000_000, (20000, 10))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), D, I)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= 1 << 20
+    rows = np.load(tmp_path / "a" / "query_rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "query_rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "distances.npy"), D[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "ids.npy"), I[rows].astype(np.float64))

@@ -268,15 +268,15 @@ def test_query_index_both_branches_match_reference_formulas():
 
 
 def test_bench_contract_small():
-    """bench.py keeps its JSON contract (one line, required keys, roofline + cpu_baseline)."""
+    """bench.py --full keeps its JSON contract (one line, required keys, roofline + cpu_baseline)."""
     import json
     import os
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n", "60000", "--steps", "5", "--warmup", "2"],
-                         capture_output=True, text=True, timeout=600, cwd=root)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n", "60000", "--steps", "5", "--warmup", "2",
+                          "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
     r = json.loads(lines[0])
@@ -289,6 +289,34 @@ def test_bench_contract_small():
     assert r["ids_identical"] and r["recall_at_k"] == 1.0
     lat = r["batch_latency_us"]
     assert 0 < lat["p10"] <= lat["median"] <= lat["p90"]
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain bench.py run prints the headline line only, and --dump-outputs writes what the last timed step
+    returned: the neighbours of the benchmark's own queries, checked against the CPU oracle."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from bench import make_inputs
+    from oracle import knn_oracle as ko
+    from tests.knn_checks import assert_knn_matches
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n", "60000", "--steps", "7", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 7 and r["ms_per_step"] > 0 and r["dtype"] == "f32" and r["higher_is_better"]
+    assert abs(r["value"] - 16 * 1e3 / r["ms_per_step"]) <= 1e-6 * r["value"]
+    assert not {"roofline", "cpu_baseline", "batch_latency_us", "ids_identical"} & set(r)
+    D, I = np.load(tmp_path / "distances.npy"), np.load(tmp_path / "ids.npy")
+    assert D.dtype == np.float32 and I.dtype == np.float64 and D.shape == I.shape == (16, 10)
+    xb, xq = make_inputs(60000, 512, 16, 0, 60000)
+    D_ref, I_ref = ko.knn_exact(xb, xq, 10, ko.METRIC_L2)
+    assert_knn_matches(D, I.astype(np.int64), D_ref, I_ref, xb, xq, ko.METRIC_L2, atol=1e-4)
 
 
 # ---- visual-word histograms (SURVEY.md f-3): one batched assignment + one histogram kernel
