@@ -119,8 +119,10 @@ class IndexFlat:
         first search of that shape allocates nothing (serving loops, bench.py)."""
         _n.check(_n.lib.ise_index_reserve_workspaces(self._h, int(nq), int(k)))
 
-    # float32 L2 indexes filter around a shift vector (see include/ise_knn.h); results do not depend
-    # on it
+    # float32 L2 indexes filter around a shift vector (see include/ise_knn.h); search results do not
+    # depend on it.  The k = 1 assignment kernel (assign_torch, search with nq >= ASSIGN_MIN_NQ) scores in
+    # the expanded form around it, so there its rounding can reorder near-ties and even exact ties between
+    # distinct centroids (tests/test_tie_order_gpu.py::test_assignment_kernel_tie_order)
     def get_shift(self) -> np.ndarray:
         mu = np.zeros(self.d, dtype=np.float32)
         _n.check(_n.lib.ise_index_get_shift(self._h, mu.ctypes.data))

@@ -104,10 +104,14 @@ def knn_exact(xb, xq, k: int, metric: int = METRIC_L2, id_offset: int = 0):
     ids = np.arange(n, dtype=np.int64) + id_offset
     # block over queries so the (nq, N) float64 matrix stays bounded
     qstep = max(1, int(2**27 // max(1, n)))
+    bmax = float(np.abs(xb).max()) ** 2 * xb.shape[1] if metric == METRIC_L2 else 0.0
     for q0 in range(0, nq, qstep):
         S = _pairwise_blocked(xq[q0 : q0 + qstep], xb, metric)
         for i in range(S.shape[0]):
-            key, sel = _select_sorted(S[i], ids, k, metric)
+            if metric == METRIC_L2 and _expanded(xq[q0 : q0 + qstep], xb):
+                key, sel = _select_rescored(S[i], xq[q0 + i], xb, ids, k, bmax)
+            else:
+                key, sel = _select_sorted(S[i], ids, k, metric)
             m = len(sel)
             val = key if metric == METRIC_L2 else -key
             D[q0 + i, :m] = val.astype(np.float32)
@@ -115,10 +119,33 @@ def knn_exact(xb, xq, k: int, metric: int = METRIC_L2, id_offset: int = 0):
     return D, I
 
 
+def _expanded(xq, xb) -> bool:
+    return xb.shape[0] * xq.shape[0] * xb.shape[1] > 2**26
+
+
+def _select_rescored(approx: np.ndarray, x: np.ndarray, xb: np.ndarray, ids: np.ndarray, k: int, bmax: float):
+    """L2 selection behind the expanded form: its float64 rounding (~1e-16 of the squared norms) is far
+    below float32 resolution but still splits EXACT ties -- two rows at the same true distance would come
+    out in the order of their rounding errors, not of their ids.  So every row within a generous margin
+    of the k-th approximate score is scored again by the direct difference (exact on data whose squared
+    differences are integers, as in tests/knn_checks.py), and the order is taken from those scores.
+    ``bmax`` bounds every row's squared norm (d * max |x_ij|^2)."""
+    ok = approx < float(FLT_MAX)
+    if ok.sum() > k:
+        kth = np.partition(approx[ok], k - 1)[k - 1]
+        x64 = x.astype(np.float64)
+        margin = 1e-9 * (1.0 + kth + float(x64 @ x64) + bmax)
+        if np.isfinite(margin):  # (a non-finite bound, from inf / NaN rows: every finite-scored row is)
+            ok &= approx <= kth + margin
+    cand = np.flatnonzero(ok)
+    diff = xb[cand].astype(np.float64) - x.astype(np.float64)
+    return _select_sorted(np.einsum("ij,ij->i", diff, diff), ids[cand], k, METRIC_L2)
+
+
 def _pairwise_blocked(xq, xb, metric):
     """float64 scores; for big N use the expanded form in float64 (error ~1e-13,
     far below float32 resolution) so the oracle finishes in seconds."""
-    if xb.shape[0] * xq.shape[0] * xb.shape[1] <= 2**26:
+    if not _expanded(xq, xb):
         return pairwise_f64(xq, xb, metric)
     q = xq.astype(np.float64)
     out = np.empty((q.shape[0], xb.shape[0]), dtype=np.float64)

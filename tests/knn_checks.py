@@ -82,3 +82,73 @@ def load_fixture(path):
         out["xb"], out["xq"] = seeded_inputs(str(out["kind"]), int(out["seed"]), int(out["n"]), int(out["d"]),
                                              int(out["nq"]))
     return out
+
+
+# ------------------------------------------------------------------ integer data: exact arithmetic, strict order
+# Small integers make every product and every partial sum of a dot product, a squared norm or sum (x - y)^2 an
+# integer below 2^24: float32 arithmetic is then exact in ANY summation order, and bf16 holds every integer up
+# to 256 exactly.  On such data a kernel's D must equal the exact score bit for bit, and the only correct I is
+# the (score, id) order with ties by ascending id.
+EXACT_LIMIT = 1 << 24
+
+INT_KINDS = {"binary": (0, 1),    # dense ties: hundreds to thousands of rows per distance at small d
+             "small": (0, 15),    # sparse, scattered tie groups
+             "signed": (-2, 2)}   # many exact-zero inner products (a +0 / -0 key mismatch shows up here)
+
+
+def int_data(kind: str, rng, n: int, d: int) -> np.ndarray:
+    """(n, d) float32 of integers drawn uniformly from the kind's range (INT_KINDS)."""
+    lo, hi = INT_KINDS[kind]
+    return rng.integers(lo, hi + 1, (n, d)).astype(np.float32)
+
+
+def plant_ties(xb: np.ndarray, src: int, ids) -> np.ndarray:
+    """Copy row ``src`` onto every row in ``ids`` (in place; returns xb): one tie group {src} | ids for every
+    query -- a consecutive run, a run straddling a block or shard boundary, or ids far apart."""
+    xb[np.asarray(ids, dtype=np.int64)] = xb[src]
+    return xb
+
+
+def level_rows(rng, sizes, d: int, far: int, n: int) -> np.ndarray:
+    """(n, d) binary rows in tie groups of the given sizes -- group j is ``sizes[j]`` copies of the row whose
+    first j + 1 entries are 1 -- at random ids; every other row has ``far`` or more ones at random places.
+    Against the all-zero query (L2: distance = number of ones) and the all-minus-one query (inner product:
+    score = -number of ones) group j occupies ranks sum(sizes[:j]) .. sum(sizes[:j + 1]) - 1."""
+    assert sum(sizes) <= n and len(sizes) < far <= d
+    filler = n - sum(sizes)
+    rest = (np.arange(d)[None, :] < rng.integers(far, d + 1, filler)[:, None]).astype(np.float32)
+    groups = [np.repeat((np.arange(d) <= j).astype(np.float32)[None, :], s, axis=0) for j, s in enumerate(sizes)]
+    xb = np.concatenate(groups + [rng.permuted(rest, axis=1)])
+    return np.ascontiguousarray(xb[rng.permutation(n)])
+
+
+def assert_exact_range(xb: np.ndarray, xq: np.ndarray):
+    """The inputs are integers and every |partial sum| of x.y, sum (x - y)^2, |x|^2 + |y|^2 and the expanded
+    form |x|^2 + |y|^2 - 2 x.y stays below 2^24 (bounded by (|x| + |y|)^2 over the largest norms)."""
+    for a in (xb, xq):
+        assert a.dtype == np.float32 and np.array_equal(a, np.rint(a)), "integer-valued float32 expected"
+    A = float(np.einsum("ij,ij->i", xb.astype(np.float64), xb.astype(np.float64)).max(initial=0.0))
+    B = float(np.einsum("ij,ij->i", xq.astype(np.float64), xq.astype(np.float64)).max(initial=0.0))
+    bound = (np.sqrt(A) + np.sqrt(B)) ** 2
+    assert bound < EXACT_LIMIT, f"inputs leave float32's exact integer range: bound {bound:.0f}"
+    return bound
+
+
+def assert_knn_identical(D, I, D_ref, I_ref, what=""):
+    """Bit-for-bit equality with the exact answer: dtypes, shapes, padding positions, every id and every
+    distance's float32 bits (so the sign of a zero too).  No tolerance and no near-tie escape: for integer data
+    (assert_exact_range) nothing else is correct."""
+    D, I = np.asarray(D), np.asarray(I)
+    assert D.dtype == np.float32 and I.dtype == np.int64, (D.dtype, I.dtype, what)
+    assert D.shape == D_ref.shape and I.shape == I_ref.shape, (D.shape, D_ref.shape, what)
+    assert np.array_equal(I < 0, I_ref < 0), f"padding (-1) positions differ {what}"
+    if not np.array_equal(I, I_ref):
+        q, r = np.argwhere(I != I_ref)[0]
+        raise AssertionError(f"ids differ {what}: {int((I != I_ref).sum())} slots, first at query {q} rank {r}: "
+                             f"got {I[q, max(0, r - 2):r + 3].tolist()} want {I_ref[q, max(0, r - 2):r + 3].tolist()}"
+                             f" at D {D_ref[q, max(0, r - 2):r + 3].tolist()}")
+    bits, bits_ref = D.view(np.uint32), np.asarray(D_ref, np.float32).view(np.uint32)
+    if not np.array_equal(bits, bits_ref):
+        q, r = np.argwhere(bits != bits_ref)[0]
+        raise AssertionError(f"distances differ {what}: {int((bits != bits_ref).sum())} slots, first at query {q} "
+                             f"rank {r}: got {D[q, r]!r} want {D_ref[q, r]!r}")

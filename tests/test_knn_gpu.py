@@ -368,6 +368,14 @@ def test_assignment_kernel_matches_oracle(faiss, metric, n, K, d):
     dup.add(np.concatenate([cent[:5], cent[:5]]))
     Dd, Id = dup.assign_torch(torch.from_numpy(X[:300]).cuda())
     assert (Id.cpu().numpy() < 5).all()
+    # ... and exactly the oracle's choice; the copies change no distance: the same bits as the five alone
+    D_dup, I_dup = ko.knn_exact(np.concatenate([cent[:5], cent[:5]]), X[:300], 1, metric)
+    assert np.array_equal(Id.cpu().numpy(), I_dup)
+    assert_knn_matches(Dd.cpu().numpy(), Id.cpu().numpy(), D_dup, I_dup, cent[:5], X[:300], metric, rtol=2e-4)
+    five = make_index(faiss, metric, d)
+    five.add(cent[:5])
+    D5, I5 = five.assign_torch(torch.from_numpy(X[:300]).cuda())
+    assert torch.equal(I5, Id) and torch.equal(D5, Dd)
 
 
 def test_l2_on_offset_data_like_cnn_embeddings(faiss):

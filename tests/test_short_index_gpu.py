@@ -102,6 +102,8 @@ def test_what_does_not_take_the_short_kernel(faiss):
     assert index.short_stats()["short_batches"] == 0
     D, I = index.search(xq[:16], 32)                       # k = 32 + 4 spare candidates: still one pass
     assert index.short_stats()["short_batches"] == 1
+    D_ref, I_ref = ko.knn_exact(xb, xq[:16], 32, L2)
+    assert_knn_matches(D, I, D_ref, I_ref, xb, xq[:16], L2, gap=ko.kth_gap(xb, xq[:16], 32, L2), atol=ATOL_UNIFORM)
     big = faiss.IndexFlatL2(16)
     big.add(rng.random((300_000, 16), dtype=np.float32))   # 18750 row tiles: 37 per block even with 512 blocks
     big.search(xq[:4, :16].copy(), 5)
