@@ -35,6 +35,23 @@ __device__ __forceinline__ float unord_f32(uint32_t o) {
     uint32_t u = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
     return __uint_as_float(u);
 }
+// float32 L2 with non-finite inputs (Faiss's gate: an L2 score enters only if it is < FLT_MAX).
+// nonfinite_mark(x) is 0 for a finite x and NaN for +-inf or NaN.  Added to a partial squared norm (never -0,
+// so a finite sum keeps its bits) it makes the shifted norm of a row or query with a non-finite entry NaN:
+// every L2 score of such a row is inf or NaN, and a NaN norm keeps its lower bound NaN, so it never becomes a
+// candidate.  A non-finite bound from a norm that is not NaN is then an OVERFLOW of finite entries (|y - mu|^2,
+// |x - mu|^2 or their sum above FLT_MAX): it bounds nothing, and such a row may still be at a finite direct
+// distance, so l2_lower_bound keys it -FLT_MAX -- always a candidate, decided by the direct re-rank (or, when
+// every row is keyed so, by the certificate's fallback to the exact scan; ise_exact.hpp).
+__device__ __forceinline__ float nonfinite_mark(float x) { return x - x; }
+__device__ __forceinline__ float nonfinite_mark(f32x4 x) {
+    const f32x4 z = x - x;
+    return (z[0] + z[1]) + (z[2] + z[3]);
+}
+__device__ __forceinline__ float l2_lower_bound(float beta, float tt, float sc) {
+    const float lo = fmaf(-beta, tt, sc);
+    return (fabsf(lo) <= FLT_MAX || tt != tt) ? lo : -FLT_MAX;
+}
 __device__ __forceinline__ u64 readlane_u64(u64 v, int src) {
     uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
     lo = (uint32_t)__builtin_amdgcn_readlane((int)lo, src);

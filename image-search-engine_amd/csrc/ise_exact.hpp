@@ -181,7 +181,10 @@ __device__ __forceinline__ void rerank_block(const ExactParams& p, int q, unsign
 #pragma unroll
             for (int r = 0; r < R; r++)
                 if (c0 + r < n2)
-                    kex[c0 + r] = kc_[r] != KEY_PAD ? (((u64)ord_f32(dd[r]) << 32) | (uint32_t)kc_[r]) : KEY_PAD;
+                    // Faiss's gate: a distance >= FLT_MAX (a candidate keyed -FLT_MAX for an overflowing norm, or
+                    // one whose bound lay just below FLT_MAX) is not a result
+                    kex[c0 + r] = (kc_[r] != KEY_PAD && dd[r] < FLT_MAX) ? (((u64)ord_f32(dd[r]) << 32) | (uint32_t)kc_[r])
+                                                                       : KEY_PAD;
         }
     }
     DBG_STAMP(p.stats ? p.stats + 8 : nullptr, 5);
@@ -203,7 +206,11 @@ __device__ __forceinline__ void rerank_block(const ExactParams& p, int q, unsign
     }
     DBG_STAMP(p.stats ? p.stats + 8 : nullptr, 6);
     // certificate: lo of the last candidate strictly above the k-th direct distance.  A list that is
-    // not full holds every admissible row of the index.
+    // not full holds every row whose lo is not NaN: every row of finite entries, since an overflowing
+    // norm is keyed lo = -FLT_MAX (ise_common.hpp, l2_lower_bound); NaN-normed rows hold a NaN or inf
+    // entry and are never admissible.  A full list whose k-th slot is empty after the gate above (too
+    // few candidates below FLT_MAX), or whose last lo is -FLT_MAX (every row overflowed, as for a query
+    // with an overflowing |x - mu|^2), fails: d_k is NaN, or lo_last is not above it.
     bool ok = true;
     if (count == p.kc && p.n > p.kc) {
         const float lo_last = unord_f32((uint32_t)(kin[p.kc - 1] >> 32));

@@ -91,10 +91,14 @@ __global__ __launch_bounds__(256) void qprep_kernel(const float* __restrict__ q,
     if (i >= nq_pad) return;
     float s = 0.f;
     for (int j = lane; j < S; j += 64) {
-        float v = 0.f;
-        if (i < nq && j < d) v = q[(size_t)i * d + j] - (mu ? mu[j] : 0.f);  // mu = null: inner product, no shift
+        float x = 0.f, v = 0.f;
+        if (i < nq && j < d) {
+            x = q[(size_t)i * d + j];
+            v = x - (mu ? mu[j] : 0.f);  // mu = null: inner product, no shift
+        }
         qprep[(size_t)i * S + j] = v;
         s = fmaf(v, v, s);
+        if (mu) s += nonfinite_mark(x);  // a non-finite entry: |x - mu|^2 = NaN (ise_common.hpp)
     }
     s = wave_sum_f32(s);
     if (lane == 0) xn[i] = s;
@@ -303,7 +307,7 @@ __global__ __launch_bounds__(512, 2) void gemm_scan_kernel(const GemmScanParams 
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const float tt = xq_n + yn[j];
-                    lo[j] = IPM ? -dot[j] : fmaf(-p.beta, tt, tt - 2.f * dot[j]);
+                    lo[j] = IPM ? -dot[j] : l2_lower_bound(p.beta, tt, tt - 2.f * dot[j]);
                     pass[j] = lo[j] <= tq && j < nv;
                     any |= pass[j];
                 }

@@ -4,7 +4,8 @@
 
 // ---------------------------------------------------------------- row helpers
 // |y|^2 per row, wave per row, fixed summation order (lanes stride float4, then
-// an xor butterfly): deterministic for a given dp.
+// an xor butterfly): deterministic for a given dp.  Shifted (float32 L2): NaN for a row with a
+// NaN or inf entry, even where |y - mu|^2 would be inf (ise_common.hpp, nonfinite_mark).
 __global__ __launch_bounds__(256) void norms_kernel(const float* __restrict__ x, long long row0,
                                                     long long n, int dp, const float* __restrict__ mu,
                                                     float* __restrict__ out) {
@@ -14,12 +15,14 @@ __global__ __launch_bounds__(256) void norms_kernel(const float* __restrict__ x,
     const float* xr = x + (size_t)r * dp;
     float s = 0.f;
     for (int j = lane * 4; j < dp; j += 256) {
-        f32x4 v = *reinterpret_cast<const f32x4*>(xr + j);
+        const f32x4 x = *reinterpret_cast<const f32x4*>(xr + j);
+        f32x4 v = x;
         if (mu) v = v - *reinterpret_cast<const f32x4*>(mu + j);  // |y - mu|^2 (padding columns: 0 - 0)
         s = fmaf(v[0], v[0], s);
         s = fmaf(v[1], v[1], s);
         s = fmaf(v[2], v[2], s);
         s = fmaf(v[3], v[3], s);
+        if (mu) s += nonfinite_mark(x);  // a non-finite entry: |y - mu|^2 = NaN (ise_common.hpp)
     }
     s = wave_sum_f32(s);
     if (lane == 0) out[r] = s;

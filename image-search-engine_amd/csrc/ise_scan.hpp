@@ -220,6 +220,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                         sn = fmaf(v[1], v[1], sn);
                         sn = fmaf(v[2], v[2], sn);
                         sn = fmaf(v[3], v[3], sn);
+                        if (SHIFT) sn += nonfinite_mark(qv[tq][i]);  // a non-finite entry: |x - mu|^2 = NaN
                     }
                 }
             }
@@ -258,6 +259,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                             qs[cc * S + j] = v;
                             if (SHIFT && cc == 0) mus[j] = m[b];
                             sn = fmaf(v, v, sn);
+                            if (SHIFT) sn += nonfinite_mark(lo[b]);
                         }
                     }
                 }
@@ -363,13 +365,16 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     //     The scan selects the K' = k + extra rows of smallest lo; the merge stage re-evaluates
     //     them as sum (x-y)^2 and proves (or sends to the exact fallback scan) that no other
     //     row can enter the top k (ise_exact.hpp).  Not clamped: the order is what matters.
+    //     Non-finite inputs (ise_common.hpp, l2_lower_bound): a row or query with a NaN or inf entry
+    //     has a NaN norm, so lo = NaN and it never enters; finite entries whose shifted norms overflow
+    //     give no bound and are keyed -FLT_MAX, so they stay candidates for the direct re-rank.
     //   bf16 rows, L2: the expanded form clamped at 0 (NaN kept), approximate by construction.
     //   inner product: minus the dot product.
     auto score = [&](int t, float dotj, float ynj) -> float {
         if (l2) {
             const float tt = xq_n[t] + ynj;
             const float sc = tt - 2.f * dotj;
-            if (SHIFT) return fmaf(-p.beta, tt, sc);
+            if (SHIFT) return l2_lower_bound(p.beta, tt, sc);
             return sc < 0.f ? 0.f : sc;  // keeps NaN (Faiss: if (dis < 0) dis = 0)
         }
         return -dotj;

@@ -206,6 +206,7 @@ __global__ __launch_bounds__(W * 64, WPS) void short_scan_kernel(const ScanParam
                         sn = fmaf(v[1], v[1], sn);
                         sn = fmaf(v[2], v[2], sn);
                         sn = fmaf(v[3], v[3], sn);
+                        if (SHIFT) sn += nonfinite_mark(qv[i]);  // a non-finite entry: |x - mu|^2 = NaN
                     }
                 }
             }
@@ -222,10 +223,12 @@ __global__ __launch_bounds__(W * 64, WPS) void short_scan_kernel(const ScanParam
                     sn = fmaf(r1, r1, sn);
                 } else {
                     const float m = (SHIFT && j < p.d) ? p.mu[j] : 0.f;
-                    const float v = (rowok && j < p.d) ? src[j] - m : 0.f;
+                    const float x = (rowok && j < p.d) ? src[j] : 0.f;
+                    const float v = (rowok && j < p.d) ? x - m : 0.f;
                     qs[cc * S + j] = v;
                     if (SHIFT && cc == 0) mus[j] = m;
                     sn = fmaf(v, v, sn);
+                    if (SHIFT) sn += nonfinite_mark(x);
                 }
             }
         }
@@ -257,7 +260,7 @@ __global__ __launch_bounds__(W * 64, WPS) void short_scan_kernel(const ScanParam
         if (l2) {
             const float tt = xqn + ynj;
             const float sc = tt - 2.f * dotj;
-            if (SHIFT) return fmaf(-p.beta, tt, sc);
+            if (SHIFT) return l2_lower_bound(p.beta, tt, sc);
             return sc < 0.f ? 0.f : sc;  // keeps NaN (Faiss: if (dis < 0) dis = 0)
         }
         return -dotj;

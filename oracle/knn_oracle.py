@@ -104,7 +104,8 @@ def knn_exact(xb, xq, k: int, metric: int = METRIC_L2, id_offset: int = 0):
     ids = np.arange(n, dtype=np.int64) + id_offset
     # block over queries so the (nq, N) float64 matrix stays bounded
     qstep = max(1, int(2**27 // max(1, n)))
-    bmax = float(np.abs(xb).max()) ** 2 * xb.shape[1] if metric == METRIC_L2 else 0.0
+    # (over the finite entries: rows with a NaN or inf entry never enter L2, and _pairwise_blocked scores them so)
+    bmax = float(np.abs(xb[np.isfinite(xb)]).max(initial=0.0)) ** 2 * xb.shape[1] if metric == METRIC_L2 else 0.0
     for q0 in range(0, nq, qstep):
         S = _pairwise_blocked(xq[q0 : q0 + qstep], xb, metric)
         for i in range(S.shape[0]):
@@ -152,11 +153,13 @@ def _pairwise_blocked(xq, xb, metric):
     step = 1 << 17
     # L2 is translation invariant: taking it around the column mean keeps the expanded form's
     # float64 error (~1e-16 of the squared norms) far below float32 resolution of the distances even
-    # when the rows sit far from the origin or in far-apart clusters
+    # when the rows sit far from the origin or in far-apart clusters.  The mean is taken over the finite
+    # entries only: one NaN or inf entry must not make every score NaN
     centre = np.zeros(q.shape[1])
     if metric != METRIC_INNER_PRODUCT:
         for s in range(0, xb.shape[0], step):
-            centre += xb[s : s + step].astype(np.float64).sum(0)
+            b = xb[s : s + step].astype(np.float64)
+            centre += np.where(np.isfinite(b), b, 0.0).sum(0)
         centre /= xb.shape[0]
         q = q - centre
     qn = np.einsum("ij,ij->i", q, q)
@@ -168,6 +171,15 @@ def _pairwise_blocked(xq, xb, metric):
         else:
             bn = np.einsum("ij,ij->i", b, b)
             out[:, s : s + step] = np.maximum(qn[:, None] + bn[None, :] - 2.0 * ip, 0.0)
+    if metric != METRIC_INNER_PRODUCT:
+        # rows and queries with a NaN or inf entry: the direct form's inf or NaN, not the expanded form's
+        # (inf - inf = NaN where the direct difference gives inf; the gate keeps both out either way)
+        bad_b = np.flatnonzero(~np.isfinite(xb).all(1))
+        if len(bad_b):
+            out[:, bad_b] = pairwise_f64(xq, xb[bad_b], metric)
+        bad_q = np.flatnonzero(~np.isfinite(xq).all(1))
+        if len(bad_q):
+            out[bad_q] = pairwise_f64(xq[bad_q], xb, metric)
     return out
 
 
@@ -192,12 +204,14 @@ def normalize_rows(x: np.ndarray) -> np.ndarray:
     as called at backend/utils.py:303, backend/engine.py:53,
     backend/siamese/test_index.py:53.  float32 in, float32 out; the squared
     norm is accumulated in float64 here (the oracle is the exact value), the
-    scale is (float)(1.0 / sqrt(nr)); zero rows are left untouched."""
+    scale is (float)(1.0 / sqrt(nr)) with nr rounded to float32 first; rows whose float32 nr is not > 0
+    (zero, so tiny that nr underflows, a NaN entry) are left untouched, as Faiss's float32 test leaves them."""
     x = _as_f32_2d(x).copy()
-    nr = np.einsum("ij,ij->i", x.astype(np.float64), x.astype(np.float64))
+    with np.errstate(over="ignore", invalid="ignore"):
+        nr = np.einsum("ij,ij->i", x.astype(np.float64), x.astype(np.float64)).astype(np.float32)
     nz = nr > 0
-    inv = np.ones_like(nr)
-    inv[nz] = 1.0 / np.sqrt(nr[nz].astype(np.float32).astype(np.float64))
+    inv = np.ones(nr.shape, np.float64)
+    inv[nz] = 1.0 / np.sqrt(nr[nz].astype(np.float64))
     x[nz] = (x[nz] * inv[nz, None].astype(np.float32)).astype(np.float32)
     return x
 

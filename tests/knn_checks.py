@@ -152,3 +152,89 @@ def assert_knn_identical(D, I, D_ref, I_ref, what=""):
         q, r = np.argwhere(bits != bits_ref)[0]
         raise AssertionError(f"distances differ {what}: {int((bits != bits_ref).sum())} slots, first at query {q} "
                              f"rank {r}: got {D[q, r]!r} want {D_ref[q, r]!r}")
+
+
+# ------------------------------------------------------------- non-finite and overflowing rows and queries
+# Faiss's gate decides what enters: an L2 score enters only if it is < FLT_MAX (NaN and inf never do), an inner
+# product only if it is > -FLT_MAX (+inf does, with D = +inf; NaN and -inf never do).  The data stay integers, so
+# every finite score is still exact in any order; the non-finite entries give inf or NaN whatever the order.
+POISONS = {"nan": np.nan, "inf": np.inf, "-inf": -np.inf, "all_nan": np.nan}
+HUGE = np.float32(2.0 ** 64)  # an exact power of two whose square (2^128) already overflows float32
+
+
+def poison(x: np.ndarray, ids, kind: str, col: int = 0) -> np.ndarray:
+    """In place (returns x): rows ``ids`` get a NaN, +inf or -inf at column ``col``, or (all_nan) NaN everywhere."""
+    ids = np.asarray(ids, dtype=np.int64)
+    if kind == "all_nan":
+        x[ids] = np.nan
+    else:
+        x[ids, col] = POISONS[kind]
+    return x
+
+
+def plant_decoys(xb: np.ndarray, xq: np.ndarray, ids, kind: str, col: int = 0) -> np.ndarray:
+    """Rows ``ids`` become copies of the queries (row ids[i] <- query i mod nq) and are then poisoned: a gate that
+    lets one of them through puts a wrong id at rank 0 of that query, not in the tail.  In place; returns xb."""
+    ids = np.asarray(ids, dtype=np.int64)
+    xb[ids] = xq[np.arange(len(ids)) % xq.shape[0]]
+    return poison(xb, ids, kind, col)
+
+
+def decoy_ids(n: int, extra=()) -> list:
+    """Ids where a poisoned row sits: the first and last row, both sides of the 16-row tile edges next to them and
+    in the middle, and the given block or shard boundaries (and their left neighbours)."""
+    ids = {0, 15, 16, n // 2 - 1, n // 2, n - 17, n - 16, n - 1}
+    for b in extra:
+        ids |= {b - 1, b}
+    return sorted(i for i in ids if 0 <= i < n)
+
+
+def assert_nonfinite_range(xb: np.ndarray, xq: np.ndarray, metric: int):
+    """The guard of assert_exact_range for poisoned data.  Non-finite entries are ignored; every finite entry is an
+    integer, and an entry of magnitude 2^24 or more is +-HUGE (float32 L2 only).  Rows and queries without a HUGE
+    entry keep every sum below 2^24 (assert_exact_range), and every float32 L2 distance of a pair with a HUGE entry
+    is either at most FLT_MAX / 4 -- no partial sum overflows, and the HUGE parts cancel exactly -- or at least
+    2 FLT_MAX, so every summation order overflows to inf: no score depends on the order it was summed in."""
+    for a in (xb, xq):
+        assert a.dtype == np.float32
+        f = a[np.isfinite(a)]
+        assert np.array_equal(f, np.rint(f)), "integer-valued float32 expected"
+        big = np.abs(f) >= EXACT_LIMIT
+        assert (np.abs(f[big]) == HUGE).all(), "large entries must be +-HUGE"
+    hb = (np.abs(np.nan_to_num(xb, posinf=0, neginf=0)) >= EXACT_LIMIT).any(1)
+    hq = (np.abs(np.nan_to_num(xq, posinf=0, neginf=0)) >= EXACT_LIMIT).any(1)
+    assert_exact_range(np.nan_to_num(xb[~hb], nan=0, posinf=0, neginf=0),
+                       np.nan_to_num(xq[~hq], nan=0, posinf=0, neginf=0))
+    if hb.any() or hq.any():
+        assert metric == ko.METRIC_L2, "HUGE entries are for float32 L2 only"
+        fin_b, fin_q = np.isfinite(xb).all(1), np.isfinite(xq).all(1)
+        for rows, qs in ((hb & fin_b, fin_q), (fin_b, hq & fin_q)):
+            if rows.any() and qs.any():
+                dd = ko.pairwise_f64(xq[qs], xb[rows], ko.METRIC_L2)
+                lim = float(ko.FLT_MAX)
+                assert ((dd <= lim / 4) | (dd >= 2 * lim)).all(), "a HUGE pair lies between FLT_MAX / 4 and 2 FLT_MAX"
+
+
+def brute_knn(xb: np.ndarray, xq: np.ndarray, k: int, metric: int, id_offset: int = 0):
+    """Per-query float64 brute force with Faiss's gate written out, independent of knn_oracle's blocking, centring
+    and re-scoring: L2 = sum (x - y)^2 entry by entry, IP = sum x * y entry by entry (no BLAS)."""
+    nq = xq.shape[0]
+    D = np.full((nq, k), ko.FLT_MAX if metric == ko.METRIC_L2 else -ko.FLT_MAX, np.float32)
+    I = np.full((nq, k), -1, np.int64)
+    b = xb.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q in range(nq):
+            x = xq[q].astype(np.float64)
+            if metric == ko.METRIC_L2:
+                s = ((b - x) ** 2).sum(1)
+                ok = s < float(ko.FLT_MAX)  # NaN, inf and >= FLT_MAX never enter
+                key = s
+            else:
+                s = (b * x).sum(1)
+                ok = s > -float(ko.FLT_MAX)  # NaN and -inf never enter; +inf does
+                key = -s
+            ids = np.flatnonzero(ok)
+            order = ids[np.lexsort((ids, key[ids]))][:k]
+            D[q, :len(order)] = s[order].astype(np.float32)
+            I[q, :len(order)] = order + id_offset
+    return D, I
