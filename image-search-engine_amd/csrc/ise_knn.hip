@@ -19,6 +19,7 @@
 //   assign_kernel  ise_assign.hpp  k = 1 against a small index (centroids); MFMA-bound
 //   merge_kernel   ise_merge.hpp   k-way merge of sorted per-block / per-rank lists
 //   row helpers    ise_rows.hpp    norms, padding / bf16 conversion, normalize_L2, shift
+//   range search   ise_range.hpp   every row within a radius: one pass per 16 queries + offset / compaction kernels
 //
 // Candidate order: a 64-bit key = ord(score) << 32 | row id, where ord() is the
 // order-preserving map float -> uint32 and score = squared L2 (or -inner product).
@@ -38,6 +39,7 @@
 #include "ise_gemm_bf16.hpp"
 #include "ise_rows.hpp"
 #include "ise_short_scan.hpp"
+#include "ise_range.hpp"
 
 // ---------------------------------------------------------------- host side
 static thread_local std::string g_err;
@@ -146,6 +148,31 @@ struct ise_index {
     unsigned long long short_batches = 0;   // batches whose scan was the short-index kernel (under mu_)
     int num_cu = 256;
     std::mutex mu_;
+    // range search (ise_range.hpp): a workspace of its own, grown lazily and held by one call at a time (rg_mu,
+    // taken before mu_); the WorkSlot rotation of search is never touched
+    template <class T>
+    struct Buf {  // grown lazily, contents not kept (ise_knn.hip, range_grow)
+        T* p = nullptr;
+        size_t n = 0;
+    };
+    struct RangeWs {
+        Buf<float> q;                        // [m][dp] padded queries
+        Buf<unsigned> cnt;                   // [m][nseg] hits per segment
+        Buf<long long> segoff;               // [m][nseg] offset of a segment within its query
+        Buf<float> sD;                       // [m][nseg][cap] staged distances
+        Buf<uint32_t> sI;                    // [m][nseg][cap] staged row ids
+        Buf<long long> tot, lims;            // [m], [m + 1]
+        Buf<unsigned> flag;                  // overflow flag
+        Buf<float> D;                        // [total]
+        Buf<long long> I;                    // [total]
+        Buf<float> q_pin;                    // page-locked staging
+        Buf<long long> lims_pin;             // [m + 1] lims, then the overflow flag
+        Buf<float> D_pin;
+        Buf<long long> I_pin;
+    };
+    RangeWs rg;
+    std::mutex rg_mu;
+    unsigned long long range_batches = 0, range_overflows = 0;  // under rg_mu
 };
 
 // rows are padded to whole k-steps of 64 bytes (16 floats / 32 bf16); rows longer than
@@ -268,6 +295,15 @@ static void free_all(ise_index* h) {
         if (c.I_pin) (void)hipHostFree(c.I_pin);
         if (c.stream) (void)hipStreamDestroy(c.stream);
         c = ise_index::HostCtx();
+    }
+    {
+        auto& r = h->rg;
+        for (void* p : {(void*)r.q.p, (void*)r.cnt.p, (void*)r.segoff.p, (void*)r.sD.p, (void*)r.sI.p, (void*)r.tot.p,
+                        (void*)r.lims.p, (void*)r.flag.p, (void*)r.D.p, (void*)r.I.p})
+            if (p) (void)hipFree(p);
+        for (void* p : {(void*)r.q_pin.p, (void*)r.lims_pin.p, (void*)r.D_pin.p, (void*)r.I_pin.p})
+            if (p) (void)hipHostFree(p);
+        r = ise_index::RangeWs();
     }
     h->xb = h->norms = nullptr;
     h->n = h->cap = 0;
@@ -581,6 +617,7 @@ struct EnvKnobs {
     std::atomic<int> no_short{0};       // ISE_NO_SHORT=1: short indexes take the streaming kernel + merge launches
     std::atomic<int> short_tpb_max{0};  // ISE_SHORT_TPB_MAX: most row tiles per block the short-index kernel takes
     std::atomic<int> direct_short_max_tiles{0};  // ISE_DIRECT_SHORT_MAX_TILES: longest SHORT index (16-row tiles) whose one-query batches take the direct scan
+    std::atomic<int> range_stage_cap{0};  // ISE_RANGE_STAGE_CAP: staging entries per range-search segment (tests: force the overflow pass)
     void refresh() {
         auto flag = [](const char* name) { const char* e = getenv(name); return (e && e[0] == '1') ? 1 : 0; };
         auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
@@ -589,6 +626,7 @@ struct EnvKnobs {
         no_short.store(flag("ISE_NO_SHORT"));
         short_tpb_max.store(num("ISE_SHORT_TPB_MAX"));
         direct_short_max_tiles.store(num("ISE_DIRECT_SHORT_MAX_TILES"));
+        range_stage_cap.store(num("ISE_RANGE_STAGE_CAP"));
     }
 };
 static EnvKnobs& knobs() {
@@ -1728,6 +1766,244 @@ extern "C" int ise_index_search_host(ise_index_t* h, const float* q, int64_t nq,
     }
     lk.unlock();
     if (r.rc) return fail(r.rc, r.err);  // the message travels to the caller's own thread
+    return ISE_OK;
+}
+
+// ---- range search (ise_range.hpp): index.range_search(x, radius) -> (lims, D, I)
+struct ise_range_result {
+    std::vector<int64_t> lims;
+    std::vector<float> D;
+    std::vector<int64_t> I;
+};
+
+#define RANGE_NQ_CHUNK 256          /* queries per batch: one host synchronisation (and 16 passes over the index) each */
+#define RANGE_STAGE_CAP 16          /* default staging entries per (query, wave segment) */
+#define RANGE_STAGE_MAX (1ll << 23) /* most staged entries per batch (64 MiB): a smaller capacity beyond that */
+
+// grow a device (or, pinned, page-locked host) buffer to at least `need` elements; contents are not kept
+template <class T>
+static int range_grow(ise_index::Buf<T>& b, size_t need, bool pinned = false) {
+    if (b.p && need <= b.n) return ISE_OK;
+    if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
+    b.p = nullptr;
+    b.n = 0;
+    const size_t want = std::max<size_t>(need, 1);
+    if (pinned) HIP_TRY(hipHostMalloc((void**)&b.p, want * sizeof(T), hipHostMallocDefault));
+    else HIP_TRY(hipMalloc((void**)&b.p, want * sizeof(T)));
+    b.n = want;
+    return ISE_OK;
+}
+
+template <bool BF16, bool SHIFT>
+static void launch_range_v(int ch, dim3 grid, size_t lds, hipStream_t st, const RangeParams& rp) {
+    static LdsAttrOnce attr[3];
+    auto go = [&](auto kern, LdsAttrOnce& a) {
+        a.ensure(reinterpret_cast<const void*>(kern), LDS_LIMIT);
+        hipLaunchKernelGGL(kern, grid, dim3(RANGE_W * 64), lds, st, rp);
+    };
+    if (ch >= 4) go(range_scan_kernel<4, BF16, SHIFT>, attr[0]);
+    else if (ch == 2) go(range_scan_kernel<2, BF16, SHIFT>, attr[1]);
+    else go(range_scan_kernel<1, BF16, SHIFT>, attr[2]);
+}
+static void launch_range(const ise_index* h, int ch, dim3 grid, size_t lds, hipStream_t st, const RangeParams& rp) {
+    if (h->storage == ISE_STORE_BF16) launch_range_v<true, false>(ch, grid, lds, st, rp);
+    else if (uses_shift(h)) launch_range_v<false, true>(ch, grid, lds, st, rp);
+    else launch_range_v<false, false>(ch, grid, lds, st, rp);
+}
+
+// the index as the range kernels read it (mu_ held, shift prepared)
+static void range_params_index(const ise_index* h, RangeParams* rp) {
+    rp->xb = h->xb;
+    rp->norms = h->norms;
+    rp->mu = h->mu;
+    rp->d = h->d;
+    rp->dp = h->dp;
+    rp->qs_stride = qs_stride_for(h);
+    rp->row_slots = (int)(row_bytes(h) / 16);
+    rp->metric = h->metric;
+    rp->beta = uses_shift(h) ? exact_beta(h) : 0.f;
+}
+
+// one batch of m <= RANGE_NQ_CHUNK queries, appended to r (rg_mu held)
+static int range_batch(ise_index* h, hipStream_t st, const float* q, long long m, float radius, ise_range_result* r) {
+    auto& ws = h->rg;
+    const int dp = h->dp, d = h->d;
+    // queries zero padded to dp: the staging reads them per row, the direct difference as exact_l2_rows does
+    int rc = range_grow(ws.q_pin, (size_t)m * dp, true);
+    if (!rc) rc = range_grow(ws.q, (size_t)m * dp);
+    if (rc) return rc;
+    for (long long i = 0; i < m; i++) {
+        memcpy(ws.q_pin.p + (size_t)i * dp, q + (size_t)i * d, (size_t)d * sizeof(float));
+        memset(ws.q_pin.p + (size_t)i * dp + d, 0, (size_t)(dp - d) * sizeof(float));
+    }
+    HIP_TRY(hipMemcpyAsync(ws.q.p, ws.q_pin.p, (size_t)m * dp * sizeof(float), hipMemcpyHostToDevice, st));
+
+    RangeParams rp{};
+    dim3 grid;
+    size_t lds = 0;
+    int ch = 1;
+    long long n0 = 0;
+    {
+        std::lock_guard<std::mutex> lk(h->mu_);
+        rc = prepare_shift_locked(h, st);
+        if (rc) return rc;
+        n0 = h->n;
+        if (n0 == 0) {  // an empty index (a reset since the caller looked): every list is empty
+            r->lims.resize(r->lims.size() + (size_t)m, r->lims.back());
+            return ISE_OK;
+        }
+        range_params_index(h, &rp);
+        // the streaming kernel's query staging for this index (the bits of |x|^2 for bf16 L2): threads per query
+        // row from the waves of its one-tile plan, the vector path where the rows allow it (its host queries are
+        // 16-byte aligned)
+        ScanPlan pl;
+        rc = make_plan(h, 16, 1, &pl, false);
+        if (rc) return rc;
+        const bool bf16 = h->storage == ISE_STORE_BF16;
+        rp.tpr = pl.waves >= 8 ? 32 : 16;
+        rp.vec_q = (d & (bf16 ? 7 : 3)) == 0 && (rp.qs_stride >> 2) <= rp.tpr * (bf16 ? 4 : 8);
+        ch = std::min(chunk_steps(h), 4);
+        // blocks own contiguous slabs of row tiles, up to 4 blocks per CU
+        rp.tiles_total = (int)((n0 + 15) / 16);
+        int nb = std::max(1, std::min(rp.tiles_total, 4 * h->num_cu));
+        rp.tiles_per_block = (rp.tiles_total + nb - 1) / nb;
+        nb = (rp.tiles_total + rp.tiles_per_block - 1) / rp.tiles_per_block;
+        rp.nseg = nb * RANGE_W;
+        rp.n = n0;
+        rp.nq = (int)m;
+        rp.radius = radius;
+        int cap = knobs().range_stage_cap.load(std::memory_order_relaxed);
+        if (cap <= 0) cap = RANGE_STAGE_CAP;
+        rp.cap = (int)std::max<long long>(1, std::min<long long>(cap, RANGE_STAGE_MAX / (m * rp.nseg)));
+        const size_t segs = (size_t)m * rp.nseg;
+        rc = range_grow(ws.cnt, segs);
+        if (!rc) rc = range_grow(ws.segoff, segs);
+        if (!rc) rc = range_grow(ws.sD, segs * rp.cap);
+        if (!rc) rc = range_grow(ws.sI, segs * rp.cap);
+        if (!rc) rc = range_grow(ws.tot, (size_t)m);
+        if (!rc) rc = range_grow(ws.lims, (size_t)m + 1);
+        if (!rc) rc = range_grow(ws.flag, 1);
+        if (!rc) rc = range_grow(ws.lims_pin, (size_t)m + 2, true);
+        if (rc) return rc;
+        rp.q = ws.q.p;
+        rp.cnt = ws.cnt.p;
+        rp.sD = ws.sD.p;
+        rp.sI = ws.sI.p;
+        rp.mode = 0;
+        rp.g0 = 0;
+        grid = dim3((unsigned)nb, (unsigned)((m + 15) / 16));
+        lds = range_lds_bytes(rp.qs_stride);
+        HIP_TRY(hipMemsetAsync(ws.flag.p, 0, sizeof(unsigned), st));
+        launch_range(h, ch, grid, lds, st, rp);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(range_offsets_kernel, dim3((unsigned)m), dim3(256), 0, st, ws.cnt.p, rp.nseg, rp.cap,
+                       ws.segoff.p, ws.tot.p, ws.flag.p);
+    hipLaunchKernelGGL(range_lims_kernel, dim3(1), dim3(1024), 0, st, ws.tot.p, (int)m, ws.lims.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ws.lims_pin.p, ws.lims.p, (size_t)(m + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ws.lims_pin.p + m + 1, ws.flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the one synchronisation: the total sizes the output
+    const long long total = ws.lims_pin.p[m];
+    const bool overflow = *reinterpret_cast<const unsigned*>(ws.lims_pin.p + m + 1) != 0;
+    if (total > 0) {
+        rc = range_grow(ws.D, (size_t)total);
+        if (!rc) rc = range_grow(ws.I, (size_t)total);
+        if (!rc) rc = range_grow(ws.D_pin, (size_t)total, true);
+        if (!rc) rc = range_grow(ws.I_pin, (size_t)total, true);
+        if (rc) return rc;
+        if (overflow) {  // a segment overflowed: read the index once more, every hit straight to its exact offset
+            std::lock_guard<std::mutex> lk(h->mu_);
+            rc = prepare_shift_locked(h, st);
+            if (rc) return rc;
+            if (h->n < n0 || !h->xb) return fail(ISE_E_INVALID, "the index was reset during range_search");
+            range_params_index(h, &rp);
+            rp.mode = 1;
+            rp.lims = ws.lims.p;
+            rp.segoff = ws.segoff.p;
+            rp.D = ws.D.p;
+            rp.I = ws.I.p;
+            launch_range(h, ch, grid, lds, st, rp);
+            HIP_TRY(hipGetLastError());
+        } else {
+            hipLaunchKernelGGL(range_compact_kernel, dim3((unsigned)((rp.nseg + 3) / 4), (unsigned)m), dim3(256), 0,
+                               st, ws.cnt.p, ws.sD.p, ws.sI.p, ws.lims.p, ws.segoff.p, rp.nseg, rp.cap, ws.D.p, ws.I.p);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(ws.D_pin.p, ws.D.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ws.I_pin.p, ws.I.p, (size_t)total * sizeof(long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        r->D.insert(r->D.end(), ws.D_pin.p, ws.D_pin.p + total);
+        r->I.insert(r->I.end(), ws.I_pin.p, ws.I_pin.p + total);
+    }
+    const int64_t base = r->lims.back();
+    for (long long i = 1; i <= m; i++) r->lims.push_back(base + ws.lims_pin.p[i]);
+    h->range_batches++;
+    if (overflow) h->range_overflows++;
+    return ISE_OK;
+}
+
+extern "C" int ise_index_range_search_host(ise_index_t* h, const float* q, int64_t nq, float radius,
+                                           ise_range_result_t** out) {
+    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
+    if (!out) return fail(ISE_E_INVALID, "output pointer is NULL");
+    *out = nullptr;
+    if (nq < 0 || (nq > 0 && !q)) return fail(ISE_E_INVALID, "bad query argument");
+    ise_range_result* r = new (std::nothrow) ise_range_result;
+    if (!r) return fail(ISE_E_NOMEM, "range result");
+    try {
+        r->lims.reserve((size_t)nq + 1);
+        r->lims.push_back(0);
+        if (nq > 0 && h->n > 0) {
+            DeviceGuard gd(h->device);
+            ise_index::HostCtx* c = acquire_ctx(h);
+            struct Rel { ise_index* h; ise_index::HostCtx* c; ~Rel() { release_ctx(h, c); } } rel{h, c};
+            if (!c->stream) {
+                const hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+                if (e != hipSuccess) {
+                    delete r;
+                    return fail(ISE_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+                }
+            }
+            std::lock_guard<std::mutex> lk(h->rg_mu);
+            for (long long i0 = 0; i0 < nq; i0 += RANGE_NQ_CHUNK) {
+                const long long m = std::min<long long>(RANGE_NQ_CHUNK, nq - i0);
+                const int rc = range_batch(h, c->stream, q + (size_t)i0 * h->d, m, radius, r);
+                if (rc) {
+                    delete r;
+                    return rc;
+                }
+            }
+        }
+        r->lims.resize((size_t)nq + 1, r->lims.back());  // an empty index: every list is empty
+    } catch (const std::bad_alloc&) {
+        delete r;
+        return fail(ISE_E_NOMEM, "range result: host allocation failed");
+    }
+    *out = r;
+    return ISE_OK;
+}
+
+extern "C" int ise_range_result_get(const ise_range_result_t* r, int64_t* nq, const int64_t** lims, const float** D,
+                                    const int64_t** I) {
+    if (!r) return fail(ISE_E_INVALID, "result is NULL");
+    if (nq) *nq = (int64_t)r->lims.size() - 1;
+    if (lims) *lims = r->lims.data();
+    if (D) *D = r->D.data();
+    if (I) *I = r->I.data();
+    return ISE_OK;
+}
+
+extern "C" int ise_range_result_destroy(ise_range_result_t* r) {
+    delete r;
+    return ISE_OK;
+}
+
+extern "C" int ise_index_range_stats(ise_index_t* h, uint64_t* out2) {
+    if (!h || !out2) return fail(ISE_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->rg_mu);
+    out2[0] = h->range_batches;
+    out2[1] = h->range_overflows;
     return ISE_OK;
 }
 

@@ -9,6 +9,8 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
     IndexFlatL2(d) / IndexFlatIP(d)      backend/utils.py:302,306
     index.add(x) / .ntotal / .d          backend/utils.py:327-328, backend/engine.py:117
     index.search(x, k) -> (D, I)         backend/engine.py:55, backend/kmeans_faiss.py:49
+    index.range_search(x, radius)        Faiss's (lims, D, I); not called by the reference (its DHASH
+                                         method's "every match" request, backend/engine.py:82-91)
     normalize_L2(x)                      backend/utils.py:303, backend/engine.py:53
     write_index / read_index             backend/indexer.py:59, backend/engine.py:116
     Kmeans(...).index / .centroids       backend/kmeans_faiss.py:29-44 (assignment only)
@@ -114,6 +116,12 @@ class IndexFlat:
         _n.check(_n.lib.ise_index_short_stats(self._h, out))
         return {"short_batches": int(out[0])}
 
+    def range_stats(self) -> dict:
+        """Range-search batches and those that needed the overflow pass (include/ise_knn.h, ise_index_range_stats)."""
+        out = (ctypes.c_uint64 * 2)()
+        _n.check(_n.lib.ise_index_range_stats(self._h, out))
+        return {"range_batches": int(out[0]), "range_overflow_batches": int(out[1])}
+
     def reserve(self, nq: int, k: int) -> None:
         """Size every internal workspace for batches of ``nq`` queries / ``k`` results now, so that the
         first search of that shape allocates nothing (serving loops, bench.py)."""
@@ -200,6 +208,32 @@ class IndexFlat:
         I = np.empty((nq, k), dtype=np.int64)
         _n.check(_n.lib.ise_index_search_host(self._h, x.ctypes.data, nq, k, D.ctypes.data, I.ctypes.data))
         return D, I
+
+    def range_search(self, x, radius: float):
+        """(lims uint64 (nq+1,), D float32, I int64), fresh arrays, as Faiss returns them: query i's rows are
+        ``I[lims[i]:lims[i+1]]`` in ascending id order, every row with D < radius (L2) or D > radius (inner
+        product), D as ``search`` reports it."""
+        x = _as_rows(x, self.d)
+        nq = x.shape[0]
+        res = ctypes.c_void_p()
+        _n.check(_n.lib.ise_index_range_search_host(self._h, x.ctypes.data, nq, ctypes.c_float(float(radius)),
+                                                    ctypes.byref(res)))
+        try:
+            n = ctypes.c_int64()
+            lp, dp_, ip = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+            _n.check(_n.lib.ise_range_result_get(res, ctypes.byref(n), ctypes.byref(lp), ctypes.byref(dp_),
+                                                 ctypes.byref(ip)))
+            lims = np.ctypeslib.as_array(ctypes.cast(lp, ctypes.POINTER(ctypes.c_int64)), (n.value + 1,))
+            lims = lims.astype(np.uint64)
+            total = int(lims[-1])
+            D = np.empty(total, dtype=np.float32)
+            I = np.empty(total, dtype=np.int64)
+            if total:
+                ctypes.memmove(D.ctypes.data, dp_.value, total * 4)
+                ctypes.memmove(I.ctypes.data, ip.value, total * 8)
+        finally:
+            _n.lib.ise_range_result_destroy(res)
+        return lims, D, I
 
     def search_torch(self, xq, k: int):
         """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out, enqueued on

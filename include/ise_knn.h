@@ -103,7 +103,7 @@ int ise_index_stats(ise_index_t* h, uint64_t* out4);
 int ise_index_short_stats(ise_index_t* h, uint64_t* out1);
 
 /* Test / rehearsal knobs ($ISE_FORCE_EXACT, $ISE_NO_DIRECT, $ISE_NO_SHORT, $ISE_SHORT_TPB_MAX,
- * $ISE_DIRECT_SHORT_MAX_TILES) are read from the environment when the library is first used and again when
+ * $ISE_DIRECT_SHORT_MAX_TILES, $ISE_RANGE_STAGE_CAP) are read from the environment when the library is first used and again when
  * this is called -- never inside a search. */
 int ise_refresh_env_knobs(void);
 
@@ -131,6 +131,25 @@ int ise_index_search_host(ise_index_t* h, const float* q, int64_t nq, int k,
  * up to 4 queries with k <= 32 run Faiss's nq < 20 algorithm as it stands -- one direct-difference scan with
  * a k-best list, no filter in front ($ISE_NO_DIRECT=1 sends them through the filtered path; same bits). */
 int ise_index_host_stats(ise_index_t* h, uint64_t* out3);
+
+/* index.range_search(x, radius) -> (lims, D, I) (Faiss IndexFlat; not called by the reference, whose DHASH
+ * method returns every image with the query's hash, backend/engine.py:82-91: this is that request on the
+ * descriptors).  q: nq x d float32 on the host.  Every row with D < radius (L2) or D > radius (inner
+ * product) -- plain float comparisons: a NaN distance or radius keeps nothing, no +-FLT_MAX gate -- with D
+ * the bits ise_index_search_host reports for the same (query, row) pair on the streaming path.  Query i's
+ * results are [lims[i], lims[i+1]) in ascending id order; lims has nq + 1 entries, lims[0] = 0; no cap on
+ * the count.  One pass over the index per 16 queries (csrc/ise_range.hpp), a second one only when a wave's
+ * staging segment overflowed; one host synchronisation per 256 queries.  Thread-safe (range calls on one
+ * handle run one at a time; searches run beside them).  *out is NULL on error. */
+typedef struct ise_range_result ise_range_result_t;
+int ise_index_range_search_host(ise_index_t* h, const float* q, int64_t nq, float radius, ise_range_result_t** out);
+/* pointers valid until ise_range_result_destroy; any output pointer may be NULL */
+int ise_range_result_get(const ise_range_result_t* r, int64_t* nq, const int64_t** lims, const float** D,
+                         const int64_t** I);
+int ise_range_result_destroy(ise_range_result_t* r); /* NULL is a no-op */
+/* out2[0] = range batches (<= 256 queries of a call against a non-empty index), out2[1] = batches that needed
+ * the overflow pass ($ISE_RANGE_STAGE_CAP: staging entries per segment, default 16; tests set it small) */
+int ise_index_range_stats(ise_index_t* h, uint64_t* out2);
 int ise_index_search_device(ise_index_t* h, const float* q_dev, int64_t nq, int k,
                             float* D_dev, int64_t* I_dev, void* stream);
 
