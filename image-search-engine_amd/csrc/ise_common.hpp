@@ -20,6 +20,7 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
@@ -51,6 +52,21 @@ __device__ __forceinline__ float nonfinite_mark(f32x4 x) {
 __device__ __forceinline__ float l2_lower_bound(float beta, float tt, float sc) {
     const float lo = fmaf(-beta, tt, sc);
     return (fabsf(lo) <= FLT_MAX || tt != tt) ? lo : -FLT_MAX;
+}
+// The fp16 shadow-row filter's key (ise_scan.hpp, HALF).  tt = |u~|^2 + |v~|^2 and dot = u~.v~ as
+// the kernel has them (dot already scaled back by 2^-(s_r + sh)); e = e_r + e_q.  beta covers every rounding
+// between the exact |u~ - v~|^2 and tt - 2 dot relative to tt, 2^-140 the underflow of the scaled terms;
+// sqrt(.) (1 - 2^-21) - E is then <= |u~ - v~| - e_r - e_q <= |(x - mu) - (y - mu)|, and shrink takes the
+// square below the float32 direct-difference value the verifier computes.  NaN norms (a non-finite entry)
+// stay NaN: never a candidate; a bound that overflowed (tt = +inf: |u~|^2 or |v~|^2 beyond FLT_MAX, or a lo that
+// did) is keyed -FLT_MAX, as l2_lower_bound does.
+__device__ __forceinline__ float half_lower_bound(float beta, float shrink, float tt, float dot, float e) {
+    const float dd = fmaf(-beta, tt, tt - 2.f * dot) - 0x1p-140f;
+    const float E = fmaf(e, 1.f + 0x1p-20f, 0x1p-126f);
+    const float r = sqrtf(fmaxf(dd, 0.f)) * (1.f - 0x1p-21f) - E;
+    const float lo = r > 0.f ? fmaxf(r * r * shrink - 0x1p-126f, 0.f) : 0.f;
+    if (tt != tt) return tt;
+    return (tt <= FLT_MAX && lo <= FLT_MAX) ? lo : -FLT_MAX;
 }
 __device__ __forceinline__ u64 readlane_u64(u64 v, int src) {
     uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);

@@ -10,6 +10,8 @@
 //                     k-steps of 64 bytes; cap is a multiple of 16 rows
 //   norms  [cap]      float32 |y - mu|^2 per row (mu = 0 for inner product / bf16)
 //   mu     [dp]       float32 shift vector of float32 L2 indexes (column mean of the rows)
+//   xh     [cap][dph] fp16 shadow rows of LONG float32 L2 indexes: 2^-s_r fp16(2^s_r (y - mu)), what the
+//   hmeta  [3][cap]   scan's filter reads instead of xb; |u~|^2, e_r, s_r per row (ise_rows.hpp)
 //   part   [nqt][nb][16 T][k] u64  per-block sorted candidate lists (workspace slot)
 //
 // Kernels
@@ -83,6 +85,14 @@ struct ise_index {
     bool shift_pinned = false;
     long long mu_rows = 0;     // rows mu was computed from (0 = not yet)
     long long norms_rows = 0;  // rows whose norm is valid
+    // fp16 shadow of the centred rows (float32 L2 indexes of more than SHADOW_MIN_ROWS rows): the scan's filter
+    // streams it instead of xb (ise_scan.hpp HALF).  Built at the first search past the threshold, then kept
+    // with the norms: valid for rows [0, norms_rows) whenever xh is set (launch_norms writes both)
+    void* xh = nullptr;        // [cap][dph] fp16
+    float* hmeta = nullptr;    // [3][cap]: |u~|^2, e_r, s_r
+    int dph = 0;               // padded shadow row length (whole 64-byte k-steps)
+    bool shadow_off = false;   // its allocation failed: the float32 filter serves (no retry until reset)
+    unsigned long long half_batches = 0;  // batches whose filter read the shadow rows (under mu_)
     unsigned long long* stats_dev = nullptr;  // [4]: reranked queries, exact-scan queries
     unsigned long long mu_updates = 0;
     unsigned long long gemm_chunks = 0;  // query chunks that took the large-batch path
@@ -184,19 +194,23 @@ static int pad_dim(int d, int storage) {
     return (steps > 4 ? (steps + 3) / 4 * 4 : steps) * per_step;
 }
 static size_t row_bytes(const ise_index* h) { return (size_t)h->dp * elem_size(h->storage); }
-static int chunk_steps(const ise_index* h) {
-    const int steps = (int)(row_bytes(h) / 64);
+static size_t shadow_row_bytes(const ise_index* h) { return (size_t)h->dph * 2; }
+static int chunk_steps_rb(size_t rb) {
+    const int steps = (int)(rb / 64);
     for (int ch = 8; ch > 1; ch >>= 1)
         if (steps % ch == 0) return ch;
     return 1;
 }
+static int chunk_steps(const ise_index* h) { return chunk_steps_rb(row_bytes(h)); }
 // LDS query row stride in 4-byte units: (stride/4) % 16 == 2 makes the 16 rows x 4 k-groups
 // ds_read_b128 pattern bank-conflict-free
-static int qs_stride_for(const ise_index* h) {
-    const int units = (int)(row_bytes(h) / 4);
+static int qs_stride_units(int units) {
     const int pad = ((2 - (units / 4)) % 16 + 16) % 16 * 4;
     return units + pad;
 }
+static int qs_stride_for(const ise_index* h) { return qs_stride_units((int)(row_bytes(h) / 4)); }
+// the shadow-row kernel's query row: fp16 hi halves | lo halves, dph each
+static int qs_stride_half(const ise_index* h) { return qs_stride_units(h->dph); }
 #define KPASS_MAX 36 /* most keys per query one scan pass selects: k = 32 with the exact path's 4 spare candidates still is
                         ONE pass (k = 29..32 took two: 730 us instead of 355 at 1M x 512); more: floor-keyed passes */
 #define XPASS_MAX 32 /* most results per query of one exact-scan pass, of the direct scan and of the large-batch paths */
@@ -253,6 +267,7 @@ extern "C" int ise_index_create_ex(ise_index_t** out, int d, int metric, int dev
     h->d = d;
     h->storage = storage;
     h->dp = pad_dim(d, storage);
+    h->dph = pad_dim(d, ISE_STORE_BF16);
     h->metric = metric;
     h->device = device;
     h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -273,9 +288,17 @@ extern "C" int ise_index_create_ex(ise_index_t** out, int d, int metric, int dev
     return ISE_OK;
 }
 
+static void free_shadow(ise_index* h) {
+    if (h->xh) (void)hipFree(h->xh);
+    if (h->hmeta) (void)hipFree(h->hmeta);
+    h->xh = nullptr;
+    h->hmeta = nullptr;
+}
+
 static void free_all(ise_index* h) {
     if (h->xb) (void)hipFree(h->xb);
     if (h->norms) (void)hipFree(h->norms);
+    free_shadow(h);
     for (auto& w : h->ws) {
         if (w.part) (void)hipFree(w.part);
         if (w.keys_tmp) (void)hipFree(w.keys_tmp);
@@ -330,6 +353,8 @@ extern "C" int ise_index_reset(ise_index_t* h) {
     HIP_TRY(hipDeviceSynchronize());
     if (h->xb) (void)hipFree(h->xb);
     if (h->norms) (void)hipFree(h->norms);
+    free_shadow(h);
+    h->shadow_off = false;
     h->xb = h->norms = nullptr;
     h->n = h->cap = 0;
     h->shift_pinned = false;
@@ -370,10 +395,34 @@ static int reserve_rows(ise_index* h, long long need, hipStream_t st) {
     }
     HIP_TRY(hipMemsetAsync(nx + (size_t)h->n * rb, 0, (size_t)(want - h->n) * rb, st));
     HIP_TRY(hipMemsetAsync(nn + h->n, 0, (size_t)(want - h->n) * sizeof(float), st));
+    // the shadow rows grow with the rows (pad rows zero; their metadata zero too)
+    char* nxh = nullptr;
+    float* nmeta = nullptr;
+    if (h->xh) {
+        const size_t hb = shadow_row_bytes(h);
+        if (hipMalloc(&nxh, (size_t)want * hb) != hipSuccess || hipMalloc(&nmeta, (size_t)want * 3 * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (nxh) (void)hipFree(nxh);
+            nxh = nullptr;  // no room: the shadow is dropped and the float32 filter serves
+        } else {
+            HIP_TRY(hipMemcpyAsync(nxh, h->xh, (size_t)h->n * hb, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemsetAsync(nxh + (size_t)h->n * hb, 0, (size_t)(want - h->n) * hb, st));
+            HIP_TRY(hipMemsetAsync(nmeta, 0, (size_t)want * 3 * sizeof(float), st));
+            for (int i = 0; i < 3; i++)
+                HIP_TRY(hipMemcpyAsync(nmeta + (size_t)i * want, h->hmeta + (size_t)i * h->cap, (size_t)h->n * sizeof(float),
+                                       hipMemcpyDeviceToDevice, st));
+        }
+    }
     HIP_TRY(hipStreamSynchronize(st));
     if (h->xb) HIP_TRY(hipDeviceSynchronize());  // searches in flight on other streams still read the old storage
     if (h->xb) (void)hipFree(h->xb);
     if (h->norms) (void)hipFree(h->norms);
+    if (h->xh) {
+        free_shadow(h);
+        h->shadow_off = nxh == nullptr;
+        h->xh = nxh;
+        h->hmeta = nmeta;
+    }
     h->xb = nx;
     h->norms = nn;
     h->cap = want;
@@ -391,6 +440,14 @@ static bool uses_shift(const ise_index* h) { return h->storage == ISE_STORE_F32 
 // means new norms for every row.  Rare and blocking: other streams' searches read mu and norms.
 static int prepare_shift_locked(ise_index* h, hipStream_t st);
 
+static void launch_shadow(ise_index* h, long long row0, long long n, hipStream_t st) {
+    const long long nblk = (n + 3) / 4;
+    if (nblk > 0)
+        hipLaunchKernelGGL(shadow_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)h->xb, row0, n, h->d,
+                           h->dp, (const float*)h->mu, (_Float16*)h->xh, h->dph, h->hmeta, h->hmeta + h->cap,
+                           h->hmeta + 2 * h->cap);
+}
+
 static void launch_norms(ise_index* h, long long row0, long long n, hipStream_t st) {
     const long long nblk = (n + 3) / 4;  // n < 2^32 so nblk fits the 32-bit grid
     if (h->storage == ISE_STORE_BF16)
@@ -399,12 +456,42 @@ static void launch_norms(ise_index* h, long long row0, long long n, hipStream_t 
     else
         hipLaunchKernelGGL(norms_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)h->xb, row0, n, h->dp,
                            uses_shift(h) ? h->mu : (const float*)nullptr, h->norms);
+    if (h->xh) launch_shadow(h, row0, n, st);  // the shadow follows the norms (same rows, same mu)
+}
+
+// Long float32 L2 indexes get the fp16 shadow rows: past the reach of the short-index kernel (<= 262k rows on
+// an MI355X), where the scan streams the whole index per pass and the stream is the cost (1M x 512: 344 ->
+// see DESIGN.md 5.0).  Shorter indexes keep the float32 filter and pay no memory.
+#define SHADOW_MIN_ROWS 262144
+// Where the shadow's looser bound still certifies (measured): shadow rows of at most 2 KB (d <= 1024)
+// and batches whose kc = k + 4 fits the 16-slot block lists (k <= 12).  Past 2 KB its beta, which grows with dph,
+// sent 3 of 16 uniform queries at d = 2048 and 5 of 64 CNN-like ones to the exact scan (the float32 filter: none),
+// and the shadow kernel's LDS image stops fitting where the float32 one still does (d = 2177 .. 2240); at k = 32
+// and 100 four spare candidates no longer cover its width on uniform rows.  Other batches keep the float32 filter.
+#define SHADOW_MAX_ROW_BYTES 2048
+#define SHADOW_MAX_KC 16
+static bool shadow_wanted(const ise_index* h) {
+    return uses_shift(h) && !h->xh && !h->shadow_off && h->n > SHADOW_MIN_ROWS &&
+           shadow_row_bytes(h) <= SHADOW_MAX_ROW_BYTES;
+}
+static int alloc_shadow(ise_index* h) {
+    hipError_t e = hipMalloc(&h->xh, (size_t)h->cap * shadow_row_bytes(h));
+    if (e == hipSuccess) e = hipMalloc(&h->hmeta, (size_t)h->cap * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(h->xh, 0, (size_t)h->cap * shadow_row_bytes(h));  // pad rows read zeros
+    if (e == hipSuccess) e = hipMemset(h->hmeta, 0, (size_t)h->cap * 3 * sizeof(float));
+    if (e == hipSuccess) return ISE_OK;
+    (void)hipGetLastError();
+    free_shadow(h);
+    if (e != hipErrorOutOfMemory) return fail(ISE_E_HIP, std::string("shadow rows: ") + hipGetErrorString(e));
+    h->shadow_off = true;  // no room for it: the float32 filter serves
+    return ISE_OK;
 }
 
 static int prepare_shift_locked(ise_index* h, hipStream_t st) {
     if (!uses_shift(h) || h->n == 0) return ISE_OK;
     const bool need_mu = !h->shift_pinned && (h->mu_rows == 0 || h->n >= h->mu_rows + h->mu_rows / 4 + 1);
-    if (!need_mu && h->norms_rows == h->n) return ISE_OK;
+    const bool need_shadow = shadow_wanted(h);
+    if (!need_mu && h->norms_rows == h->n && !need_shadow) return ISE_OK;
     HIP_TRY(hipDeviceSynchronize());  // nothing in flight reads mu / norms while they change
     if (need_mu) {
         const int groups = (int)std::max<long long>(1, std::min<long long>(COLMEAN_GROUPS_MAX, h->n / 64));
@@ -422,7 +509,12 @@ static int prepare_shift_locked(ise_index* h, hipStream_t st) {
         h->norms_rows = 0;
         h->mu_updates++;
     }
-    launch_norms(h, h->norms_rows, h->n - h->norms_rows, st);
+    if (need_shadow) {  // built for the rows whose norms are current; launch_norms below takes the rest
+        int rc = alloc_shadow(h);
+        if (rc) return rc;
+        if (h->xh) launch_shadow(h, 0, h->norms_rows, st);
+    }
+    if (h->n > h->norms_rows) launch_norms(h, h->norms_rows, h->n - h->norms_rows, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     h->norms_rows = h->n;
@@ -571,9 +663,10 @@ extern "C" int ise_index_reconstruct_host(ise_index_t* h, int64_t i0, int64_t n,
 }
 
 // ---- search
-static void launch_scan(const ise_index* h, int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st,
+static void launch_scan(const ise_index* h, bool half, int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st,
                         const ScanParams& sp) {
-    if (h->storage == ISE_STORE_BF16) ise_launch_scan_bf16(ch, waves, T, grid, lds, st, sp);
+    if (half) ise_launch_scan_f16_shadow(ch, waves, T, grid, lds, st, sp);
+    else if (h->storage == ISE_STORE_BF16) ise_launch_scan_bf16(ch, waves, T, grid, lds, st, sp);
     else if (uses_shift(h)) ise_launch_scan_f32_shift(ch, waves, T, grid, lds, st, sp);
     else ise_launch_scan_f32_plain(ch, waves, T, grid, lds, st, sp);
 }
@@ -592,6 +685,7 @@ struct ScanPlan {
     int kc;      // keys per query the scan + merge stage selects: k, or k + extra candidates when exact
     bool gemm;   // the batch takes the large-batch path (ise_gemm_scan.hpp): the slot also holds its buffers
     size_t gemm_bytes;
+    bool half;    // float32 L2: the scan filters through the fp16 shadow rows (ise_scan.hpp HALF)
     bool short_;  // the batch's scan is the short-index kernel (ise_short_scan.hpp)
     int short_bpc;  // ... with this many blocks per CU
 };
@@ -608,6 +702,12 @@ static int exact_extra(int k) {
 // relative width of the scan's lower bound: every rounding between the stored floats and the keyed
 // value, in units of u = 2^-24 times (|x-mu|^2 + |y-mu|^2) (derivation: DESIGN.md section 4.1)
 static float exact_beta(const ise_index* h) { return (0.5625f * h->dp + 256.f) * 5.9604645e-8f * 1.02f; }
+// the shadow-row filter's beta: the f16 MFMA dot of 2 dph exact products in any accumulation order, twice the
+// worst-case n u, plus the roundings of |u~|^2, |v~|^2 and the expanded form, relative to |u~|^2 + |v~|^2 (DESIGN.md
+// 4.1); and the factor that takes its square below the float32 direct-difference value (fmaf chains of dp / 64
+// terms, an xor butterfly, the differences' own rounding) with room to spare
+static float half_beta(const ise_index* h) { return (5.f * h->dph + 128.f) * 5.9604645e-8f * 1.02f; }
+static float half_lo_shrink(const ise_index* h) { return 1.f - ((float)h->dp / 16.f + 96.f) * 5.9604645e-8f; }
 // Test / rehearsal knobs that may change while the process runs: read from the environment when the library
 // is first used and again whenever ise_refresh_env_knobs() is called (the tests call it after changing the
 // environment) -- never inside a search, where another thread's setenv would race with getenv.
@@ -618,6 +718,7 @@ struct EnvKnobs {
     std::atomic<int> short_tpb_max{0};  // ISE_SHORT_TPB_MAX: most row tiles per block the short-index kernel takes
     std::atomic<int> direct_short_max_tiles{0};  // ISE_DIRECT_SHORT_MAX_TILES: longest SHORT index (16-row tiles) whose one-query batches take the direct scan
     std::atomic<int> range_stage_cap{0};  // ISE_RANGE_STAGE_CAP: staging entries per range-search segment (tests: force the overflow pass)
+    std::atomic<int> no_half{0};        // ISE_NO_HALF_FILTER=1: long float32 L2 indexes keep the float32 filter (A/B, tests)
     void refresh() {
         auto flag = [](const char* name) { const char* e = getenv(name); return (e && e[0] == '1') ? 1 : 0; };
         auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
@@ -627,6 +728,7 @@ struct EnvKnobs {
         short_tpb_max.store(num("ISE_SHORT_TPB_MAX"));
         direct_short_max_tiles.store(num("ISE_DIRECT_SHORT_MAX_TILES"));
         range_stage_cap.store(num("ISE_RANGE_STAGE_CAP"));
+        no_half.store(flag("ISE_NO_HALF_FILTER"));
     }
 };
 static EnvKnobs& knobs() {
@@ -648,24 +750,33 @@ static bool xchg_enabled() {  // dev knob: ISE_NO_XCHG=1 switches the threshold 
 
 // pick (query tiles per pass T, waves per block) for nq queries: the largest T <= 3
 // that the batch can use and whose LDS image fits, preferring 8 waves
-static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool allow_short = true) {
+static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool allow_short = true,
+                     bool allow_half = true) {
     pl->exact = uses_shift(h);
     pl->kc = pl->exact ? k + exact_extra(k) : k;
     pl->kpass = pl->kc < KPASS_MAX ? pl->kc : KPASS_MAX;
     pl->kb = pl->kpass <= 16 ? 16 : (pl->kpass <= 32 ? 32 : KB_MAX);
-    pl->ch = chunk_steps(h);
+    // the streamed rows: the fp16 shadow of a long float32 L2 index, else the index's own rows
+    pl->half = allow_half && pl->exact && h->xh != nullptr && !knobs().no_half.load(std::memory_order_relaxed) &&
+               pl->kc <= SHADOW_MAX_KC;
+    const size_t rb = pl->half ? shadow_row_bytes(h) : row_bytes(h);
+    auto lds_bytes = [&](int waves, int T) {
+        return pl->half ? scan_lds_layout(qs_stride_half(h), waves, T, pl->kb, true) : scan_lds_bytes(h, waves, T, pl->kb);
+    };
+    pl->ch = chunk_steps_rb(rb);
 #ifdef ISE_ABLATE
     if (const char* e = getenv("ISE_CH")) {  // dev: force a smaller chunk (must divide dp/16)
         const int ch = atoi(e);
-        if ((ch == 1 || ch == 2 || ch == 4 || ch == 8) && (int)(row_bytes(h) / 64) % ch == 0) pl->ch = ch;
+        if ((ch == 1 || ch == 2 || ch == 4 || ch == 8) && (int)(rb / 64) % ch == 0) pl->ch = ch;
     }
 #endif
     // relative time of one pass over the index with T query tiles (measured, 1M x 512)
-    // (fp32: T = 3 is MFMA-bound; bf16 rows stay HBM-bound, the growth is top-k bookkeeping)
+    // (fp32: T = 3 is MFMA-bound; bf16 rows stay HBM-bound, the growth is top-k bookkeeping; fp16 shadow rows
+    // run the 2-byte stream with two MFMAs per k-step, no more than the bf16 kernel's T = 3 is built for them)
     static const double pass_cost_f32[5] = {0.0, 1.0, 1.11, 1.45, 0.0};
     static const double pass_cost_bf16[5] = {0.0, 1.0, 1.07, 1.16, 1.25};
     const bool bf16 = h->storage == ISE_STORE_BF16;
-    const double* pass_cost = bf16 ? pass_cost_bf16 : pass_cost_f32;
+    const double* pass_cost = (bf16 || pl->half) ? pass_cost_bf16 : pass_cost_f32;
     int tmax = bf16 ? 4 : 3;
 #ifdef ISE_ABLATE
     if (const char* e = getenv("ISE_TMAX")) tmax = std::min(tmax, std::max(1, atoi(e)));
@@ -680,12 +791,12 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
         // extra waves hide the bookkeeping instead (71 vs 85 us at 125k rows)
         // (fp32 rows only: bf16 rows stay HBM-bound and run 208 vs 217 us with the 16-wave block)
         const bool xchg_pays = !bf16 && xchg_enabled() && (h->n + 15) / 16 >= 6ll * 8 * h->num_cu;
-        if (t == 2 && !xchg_pays && scan_lds_bytes(h, 16, 2, pl->kb) <= LDS_LIMIT) {
+        if (t == 2 && !xchg_pays && lds_bytes(16, 2) <= LDS_LIMIT) {
             wv = 16;
-            lds = scan_lds_bytes(h, 16, 2, pl->kb);
+            lds = lds_bytes(16, 2);
         }
         for (int cand_w = 8; cand_w >= (t == 1 ? 4 : 8) && !wv; cand_w -= 4) {  // 4 waves: one tile only
-            lds = scan_lds_bytes(h, cand_w, t, pl->kb);
+            lds = lds_bytes(cand_w, t);
             if (lds <= LDS_LIMIT) wv = cand_w;
         }
         if (!wv) break;
@@ -709,7 +820,7 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
         int wv = 8, bpc = 2;
         if (pl->T == 1 && sscanf(e, "%d,%d", &wv, &bpc) == 2 && (wv == 4 || wv == 8) && bpc >= 1) {
             pl->waves = wv;
-            pl->lds = scan_lds_bytes(h, wv, 1, pl->kb);
+            pl->lds = lds_bytes(wv, 1);
             blocks_per_cu = bpc;
         }
     }
@@ -720,9 +831,9 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
     // 8 CUs streamed 33 us where 63 CUs take 8 (the reference's own index size and default metric: 59 -> 34 us
     // per one-query batch; 1000 x 512, 32 queries: 56 -> 45 us).  More blocks than CUs x blocks_per_cu would run
     // in rounds: batches of several query tiles (grid.y) divide the budget.
-    const bool long_rows = row_bytes(h) > 2048;
+    const bool long_rows = rb > 2048;
     const int nqt_plan = (int)((nq + 16 * pl->T - 1) / (16 * pl->T));
-    const int min_tiles = (int)std::max<size_t>(1, 65536 / (16 * row_bytes(h)));
+    const int min_tiles = (int)std::max<size_t>(1, 65536 / (16 * rb));
     const int slots = h->num_cu * blocks_per_cu;
     const int nb_packed = std::min(slots, (pl->tiles_total + pl->waves - 1) / pl->waves);
     const int nb_spread = std::min(std::max(1, slots / nqt_plan), (pl->tiles_total + min_tiles - 1) / min_tiles);
@@ -735,7 +846,8 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
     if (pl->nblocks < 1) pl->nblocks = 1;
     // ... and a wave that owns ONE tile of long rows is latency-bound on its own loads: 8-step chunks (2 x 8 KB in
     // flight) where the register budget has them (8-wave blocks)
-    if (long_rows && pl->T == 1 && pl->waves <= 8 && pl->tiles_per_block <= pl->waves && chunk_steps(h) == 8) pl->ch = 8;
+    // (never shadow rows: they are at most 2 KB)
+    if (long_rows && pl->T == 1 && pl->waves <= 8 && pl->tiles_per_block <= pl->waves && chunk_steps_rb(rb) == 8) pl->ch = 8;
     pl->nqt = (int)((nq + 16 * pl->T - 1) / (16 * pl->T));
     pl->gemm = false;
     pl->gemm_bytes = 0;
@@ -786,6 +898,7 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
                 pl->T = short_T;
                 pl->nqt = short_nqt;
                 pl->ch = std::min(chunk_steps(h), 4);
+                pl->half = false;  // (never with a shadow: it exists past the short kernel's reach)
             }
         }
     }
@@ -1195,6 +1308,12 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
     sp.row_slots = (int)(row_bytes(h) / 16);
     sp.nq = (int)nq; sp.k = pl.kpass; sp.kb = pl.kb; sp.metric = h->metric; sp.id_base = id_base;
     sp.beta = pl.exact ? exact_beta(h) : 0.f;
+    if (pl.half) {  // the filter streams the fp16 shadow rows (ise_scan.hpp HALF)
+        sp.xb = h->xh; sp.norms = h->hmeta; sp.herr = h->hmeta + h->cap; sp.hexp = h->hmeta + 2 * h->cap;
+        sp.qs_stride = qs_stride_half(h); sp.row_slots = (int)(shadow_row_bytes(h) / 16);
+        sp.beta = half_beta(h); sp.lo_shrink = half_lo_shrink(h);
+        h->half_batches++;
+    }
     sp.tiles_total = pl.tiles_total; sp.tiles_per_block = pl.tiles_per_block;
     sp.xchg = xchg_enabled() ? w->xchg : nullptr;
     sp.xchg_seq = 0;
@@ -1251,7 +1370,7 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
     if (pl.kc <= pl.kpass) {  // one scan pass selects everything the merge stage needs
         if ((rc = next_xchg_seq(w, st, &sp.xchg_seq))) return rc;
         if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e0, st));
-        launch_scan(h, pl.ch, pl.waves, pl.T, grid, pl.lds, st, sp);
+        launch_scan(h, pl.half, pl.ch, pl.waves, pl.T, grid, pl.lds, st, sp);
         HIP_TRY(hipGetLastError());
         if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e1, st));
         if (pl.exact) {  // merge the kc lower-bound keys, re-rank them exactly, certify or list for the exact scan
@@ -1279,7 +1398,7 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
         sp.floor_keys = off ? floor_dev : nullptr;
         mp.D = nullptr; mp.I = nullptr; mp.keys_out = pass_keys;
         if ((rc = next_xchg_seq(w, st, &sp.xchg_seq))) return rc;
-        launch_scan(h, pl.ch, pl.waves, pl.T, grid, pl.lds, st, sp);
+        launch_scan(h, pl.half, pl.ch, pl.waves, pl.T, grid, pl.lds, st, sp);
         HIP_TRY(hipGetLastError());
         launch_merge<false>((unsigned)nq, 0, st, mp, xp);
         HIP_TRY(hipGetLastError());
@@ -1857,7 +1976,7 @@ static int range_batch(ise_index* h, hipStream_t st, const float* q, long long m
         // row from the waves of its one-tile plan, the vector path where the rows allow it (its host queries are
         // 16-byte aligned)
         ScanPlan pl;
-        rc = make_plan(h, 16, 1, &pl, false);
+        rc = make_plan(h, 16, 1, &pl, false, false);
         if (rc) return rc;
         const bool bf16 = h->storage == ISE_STORE_BF16;
         rp.tpr = pl.waves >= 8 ? 32 : 16;
@@ -2011,6 +2130,27 @@ extern "C" int ise_index_short_stats(ise_index_t* h, uint64_t* out1) {
     if (!h || !out1) return fail(ISE_E_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu_);
     out1[0] = h->short_batches;
+    return ISE_OK;
+}
+
+extern "C" int ise_index_half_stats(ise_index_t* h, uint64_t* out1) {
+    if (!h || !out1) return fail(ISE_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    out1[0] = h->half_batches;
+    return ISE_OK;
+}
+
+extern "C" int ise_index_shadow_row(ise_index_t* h, int64_t i, float* out3) {
+    if (!h || !out3) return fail(ISE_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    if (i < 0 || i >= h->n) return fail(ISE_E_INVALID, "row out of range");
+    DeviceGuard gd(h->device);
+    int rc = prepare_shift_locked(h, h->stream);
+    if (rc) return rc;
+    if (!h->xh) return fail(ISE_E_INVALID, "this index has no shadow rows");
+    HIP_TRY(hipDeviceSynchronize());
+    for (int j = 0; j < 3; j++)
+        HIP_TRY(hipMemcpy(out3 + j, h->hmeta + (size_t)j * h->cap + i, sizeof(float), hipMemcpyDeviceToHost));
     return ISE_OK;
 }
 

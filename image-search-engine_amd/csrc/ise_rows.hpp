@@ -28,6 +28,58 @@ __global__ __launch_bounds__(256) void norms_kernel(const float* __restrict__ x,
     if (lane == 0) out[r] = s;
 }
 
+// fp16 shadow rows of a float32 L2 index (the scan's filter reads them; ise_scan.hpp HALF), wave per
+// row, in float64 from the exact a = y - mu:  s_r puts max |a| in [2^14, 2^15) (no fp16 overflow), the row holds
+// fp16(2^s_r a) (zero padded to dph), and hn = |u~|^2, he = e_r >= |a - u~| (rounded up; a margin for a - mu not
+// being exact in float64 when the exponents are far apart), hs = s_r, with u~ = 2^-s_r fp16(2^s_r a).  A row
+// with a NaN or inf entry gets hn = NaN and a zero shadow (never a candidate, as its norm does).
+__global__ __launch_bounds__(256) void shadow_rows_kernel(const float* __restrict__ x, long long row0, long long n,
+                                                          int d, int dp, const float* __restrict__ mu,
+                                                          _Float16* __restrict__ xh, int dph, float* __restrict__ hn,
+                                                          float* __restrict__ he, float* __restrict__ hs) {
+    const int lane = threadIdx.x & 63;
+    const long long r = row0 + (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= row0 + n) return;
+    const float* xr = x + (size_t)r * dp;
+    double amax = 0.0;
+    float mark = 0.f;
+    for (int j = lane; j < d; j += 64) {
+        const float v = xr[j];
+        mark += v - v;
+        amax = fmax(amax, fabs((double)v - (double)mu[j]));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        amax = fmax(amax, __shfl_xor(amax, o));
+        mark += __shfl_xor(mark, o);
+    }
+    const bool bad = mark != 0.f;
+    const int s = (amax > 0.0 && !bad) ? 14 - ilogb(amax) : 0;
+    _Float16* hr = xh + (size_t)r * dph;
+    double nu = 0.0, e2 = 0.0;
+    for (int j = lane; j < dph; j += 64) {
+        const double a = (j < d && !bad) ? (double)xr[j] - (double)mu[j] : 0.0;
+        const _Float16 u = (_Float16)(float)ldexp(a, s);
+        hr[j] = u;
+        const double ut = ldexp((double)(float)u, -s);
+        nu = fma(ut, ut, nu);
+        e2 = fma(a - ut, a - ut, e2);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        nu += __shfl_xor(nu, o);
+        e2 += __shfl_xor(e2, o);
+    }
+    if (lane == 0) {
+        const double e = sqrt(e2) * (1.0 + 0x1p-40) + sqrt(nu) * 0x1p-49;
+        float ef = (float)e;
+        if ((double)ef < e) ef = nextafterf(ef, INFINITY);
+        hn[r] = bad ? __int_as_float(0x7fc00000) : (float)nu;
+        he[r] = ef;
+        hs[r] = (float)s;
+    }
+}
+
 // column mean of `rows` rows (d columns of a padded row).  Two levels, both in a fixed order
 // (`groups` row groups summed in row order, then the groups in group order): deterministic for a
 // given row count.  NaN / inf entries are skipped (they must not poison every distance).

@@ -56,9 +56,18 @@
 // stored unshifted (reconstruct / write_index are exact).  What the expanded form still
 // loses is bounded rigorously (beta) and the rows are keyed by that lower bound: this
 // kernel is the FILTER of the exact search, ise_exact.hpp holds the verifier.
-template <int CH, int W, int T, bool BF16, bool SHIFT>
+//
+// HALF (with SHIFT; long float32 L2 indexes): the same filter read through the index's fp16 SHADOW rows
+// u~ = 2^-s_r fp16(2^s_r (y - mu)) instead of the float32 rows -- half the bytes, 16x16x32 f16 MFMAs.  The
+// query v = x - mu is staged exactly as fp16 hi + lo halves scaled by 2^sh (two MFMAs per k-step, one per
+// accumulator chain), and a row is keyed by lo = (max(0, sqrt(max(0, d~ - beta tt)) - e_r - e_q))^2
+// with d~ = |u~|^2 + |v~|^2 - 2 u~.v~, tt = |u~|^2 + |v~|^2: a rigorous lower bound of the float32
+// direct-difference distance the verifier computes (tests/half_filter_ref.py restates it).
+template <int CH, int W, int T, bool BF16, bool SHIFT, bool HALF = false>
 __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) void scan_kernel(const ScanParams p) {
     static_assert(!(BF16 && SHIFT), "the shift is applied to fp32 rows only");
+    static_assert(!HALF || SHIFT, "shadow rows belong to float32 L2 indexes");
+    constexpr bool F32S = SHIFT && !HALF;  // float32 rows shifted in registers
     if (p.gate && *p.gate == 0u) return;  // a queued rerun that is not needed
     constexpr int BLOCK_THREADS = W * 64;
     // threshold exchange: compiled into the 8-wave kernels with two or more query tiles, where the candidate
@@ -80,7 +89,9 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     float* mus = reinterpret_cast<float*>(smem);                // [S] shift vector (SHIFT only)
     float* qs = mus + S;                                        // [NQ][S]
     float* xn = qs + NQ * S;                                    // [NQ]
-    u64* tauS = reinterpret_cast<u64*>(xn + NQ);                // [NQ]
+    float* xe = xn + NQ;                                        // [NQ] HALF: e_q
+    int* xsh = reinterpret_cast<int*>(xe + NQ);                 // [NQ] HALF: the query's scale exponent sh
+    u64* tauS = reinterpret_cast<u64*>(xn + (HALF ? 3 : 1) * NQ);  // [NQ]
     int* bwc = reinterpret_cast<int*>(tauS + NQ);               // [NQ]
     int* lockS = bwc + NQ;                                      // [NQ]
     int* cntS = lockS + NQ;                                     // [W][NQ]
@@ -113,6 +124,10 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     auto load_norms = [&](int tile) -> f32x4 {
         return *reinterpret_cast<const f32x4*>(p.norms + (size_t)tile * 16 + 4 * g);
     };
+    auto load_meta = [&](const float* m, int tile) -> f32x4 {  // HALF: e_r or s_r of the tile's rows
+        if constexpr (!HALF) return (f32x4){0.f, 0.f, 0.f, 0.f};
+        return *reinterpret_cast<const f32x4*>(m + (size_t)tile * 16 + 4 * g);
+    };
 
     // ---- query staging, step 1: REQUEST the query tiles first (small, L2-resident after
     // the first block): issued behind the index prefetch they would queue for microseconds.
@@ -124,12 +139,12 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     constexpr int QVS = QV / FPS;      // slots per thread and tile
     const int S4 = S >> 2;             // 16-byte slots per LDS query row
     const int dslots = BF16 ? (p.d >> 3) : (p.d >> 2);  // slots that carry data (vector path only)
-    const bool vec_q = (p.d & (BF16 ? 7 : 3)) == 0 && ((reinterpret_cast<uintptr_t>(p.q) & 15) == 0) &&
+    const bool vec_q = !HALF && (p.d & (BF16 ? 7 : 3)) == 0 && ((reinterpret_cast<uintptr_t>(p.q) & 15) == 0) &&
                        S4 <= TPR * QVS;
     f32x4 qv[T][QV];
-    f32x4 muv[SHIFT ? QVS : 1];
+    f32x4 muv[F32S ? QVS : 1];
     const bool stager = tid < 16 * TPR;  // whole waves
-    if (SHIFT && vec_q && stager) {
+    if (F32S && vec_q && stager) {
 #pragma unroll
         for (int i = 0; i < QVS; i++) {
             const int j4 = tid % TPR + i * TPR;
@@ -211,7 +226,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                         }
                     } else {
                         f32x4 v = qv[tq][i];
-                        if (SHIFT) {
+                        if (F32S) {
                             if (cc < nqt) v = v - muv[i];  // padding rows stay zero
                             if (cc == 0) *reinterpret_cast<f32x4*>(mus + 4 * j4) = muv[i];
                         }
@@ -220,9 +235,66 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                         sn = fmaf(v[1], v[1], sn);
                         sn = fmaf(v[2], v[2], sn);
                         sn = fmaf(v[3], v[3], sn);
-                        if (SHIFT) sn += nonfinite_mark(qv[tq][i]);  // a non-finite entry: |x - mu|^2 = NaN
+                        if (F32S) sn += nonfinite_mark(qv[tq][i]);  // a non-finite entry: |x - mu|^2 = NaN
                     }
                 }
+            }
+        } else if (HALF) {
+            // fp16 shadow rows: v = x - mu exactly as the float pair (v_hi, v_lo) (TwoSum), scaled by 2^sh so that
+            // max |v| lands in [2^14, 2^15), split into fp16 hi | lo halves (two MFMA operands); e_q bounds what the
+            // split misses.  Two passes over the query (L2-resident): the scale needs max |v| first.
+            const bool rowok = cc < nqt && !ABL(1);
+            const float* src = p.q + (size_t)(q0 + (rowok ? cc : 0)) * p.d;
+            float amax = 0.f, mark = 0.f;
+            if (rowok)
+                for (int j = t; j < p.d; j += TPR) {
+                    const float y = src[j];
+                    amax = fmaxf(amax, fabsf(y - p.mu[j]));
+                    mark += y - y;  // NaN for a non-finite entry (ise_common.hpp, nonfinite_mark)
+                }
+#pragma unroll
+            for (int o = TPR / 2; o > 0; o >>= 1) {
+                amax = fmaxf(amax, __shfl_xor(amax, o));
+                mark += __shfl_xor(mark, o);
+            }
+            const bool ovf = !(amax <= FLT_MAX);  // x - mu overflowed: no bound (keyed -FLT_MAX below)
+            const bool skip = ovf || mark != 0.f;
+            const int sh = (amax > 0.f && !ovf) ? 14 - ilogbf(amax) : 0;
+            _Float16* hi = reinterpret_cast<_Float16*>(qs + cc * S);
+            _Float16* lo = reinterpret_cast<_Float16*>(qs + cc * S + 4 * p.row_slots);
+            float e2 = 0.f;
+            const int dph = p.row_slots * 8;
+            for (int j = t; j < dph; j += TPR) {
+                float vh = 0.f, vl = 0.f;
+                if (rowok && j < p.d && !skip) {
+                    const float y = src[j], m = p.mu[j];
+                    vh = y - m;
+                    const float bb = vh - y;
+                    vl = (y - (vh - bb)) + (-m - bb);  // v = vh + vl exactly
+                }
+                const float V = ldexpf(vh, sh), VL = ldexpf(vl, sh);
+                const _Float16 h1 = (_Float16)V;
+                const float r1 = V - (float)h1;  // exact
+                const _Float16 h2 = (_Float16)(r1 + VL);
+                const float res = (r1 - (float)h2) + VL;
+                hi[j] = h1;
+                lo[j] = h2;
+                const float wv = (float)h1 + (float)h2;
+                sn = fmaf(wv, wv, sn);
+                e2 = fmaf(res, res, e2);
+            }
+#pragma unroll
+            for (int o = TPR / 2; o > 0; o >>= 1) {
+                sn += __shfl_xor(sn, o);
+                e2 += __shfl_xor(e2, o);
+            }
+            if (t == 0) {
+                // scaled units: |v - v~| <= sqrt(e2) up to the rounding of e2 (the margins) and 2^-46 |V| (res)
+                const float es = sqrtf(e2 * (1.f + 0x1p-9f)) * (1.f + 0x1p-20f) + 0x1p-44f * sqrtf(sn);
+                xe[cc] = ldexpf(es, -sh);
+                xsh[cc] = sh;
+                // |v~|^2: NaN for a non-finite entry (never enters), +inf when x - mu overflowed (keyed -FLT_MAX)
+                xn[cc] = mark != 0.f ? mark : (ovf ? INFINITY : ldexpf(sn, -2 * sh));
             }
         } else {  // odd d, unaligned queries or very long rows: scalar path, one 4-byte unit at a time
             // (the loads of SB units are requested together, then consumed in the same ascending order as a
@@ -265,9 +337,11 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                 }
             }
         }
+        if (!HALF) {
 #pragma unroll
-        for (int o = TPR / 2; o > 0; o >>= 1) sn += __shfl_xor(sn, o);
-        if (t == 0) xn[cc] = sn;
+            for (int o = TPR / 2; o > 0; o >>= 1) sn += __shfl_xor(sn, o);
+            if (t == 0) xn[cc] = sn;
+        }
     }
     for (int i = tid; i < NQ; i += BLOCK_THREADS) {
         tauS[i] = TAU0;
@@ -281,13 +355,16 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     const float* qrow = qs + c * S + 4 * g;
     const bool use_floor = p.floor_keys != nullptr;
 
-    float xq_n[T];
+    float xq_n[T], xq_e[T];
+    int xq_sh[T];
     u64 tau[T];
     int cnt[T];
     f32x4 acc0[T], acc1[T];
 #pragma unroll
     for (int t = 0; t < T; t++) {
         xq_n[t] = xn[t * 16 + c];
+        xq_e[t] = HALF ? xe[t * 16 + c] : 0.f;
+        xq_sh[t] = HALF ? xsh[t * 16 + c] : 0;
         tau[t] = TAU0;
         cnt[t] = 0;
         acc0[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -370,7 +447,9 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     //     give no bound and are keyed -FLT_MAX, so they stay candidates for the direct re-rank.
     //   bf16 rows, L2: the expanded form clamped at 0 (NaN kept), approximate by construction.
     //   inner product: minus the dot product.
-    auto score = [&](int t, float dotj, float ynj) -> float {
+    auto score = [&](int t, float dotj, float ynj, float yej, float ysj) -> float {
+        if constexpr (HALF) return half_lower_bound(p.beta, p.lo_shrink, xq_n[t] + ynj,
+                                                    ldexpf(dotj, -((int)ysj + xq_sh[t])), yej + xq_e[t]);
         if (l2) {
             const float tt = xq_n[t] + ynj;
             const float sc = tt - 2.f * dotj;
@@ -396,7 +475,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
 #pragma unroll
     for (int t = 0; t < T; t++) tau_sc[t] = FLT_MAX;
 
-    auto epilogue = [&](int etile, f32x4 yn) {
+    auto epilogue = [&](int etile, f32x4 yn, f32x4 ye, f32x4 ys) {
         f32x4 sc[T];
 #pragma unroll
         for (int t = 0; t < T; t++) {
@@ -404,7 +483,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
             acc0[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
             acc1[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int j = 0; j < 4; j++) sc[t][j] = score(t, dot[j], yn[j]);
+            for (int j = 0; j < 4; j++) sc[t][j] = score(t, dot[j], yn[j], ye[j], ys[j]);
         }
         if (!booted) {
             u64 key[T][4];
@@ -514,27 +593,35 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     // B operand (queries, from LDS) is software-pipelined one k-step ahead of the MFMAs
     // that consume it, across chunk boundaries too: bcur holds the B fragments of the
     // next step to be computed.
-    f32x4 bcur[T];
-    auto load_b = [&](f32x4(&b)[T], int step) {
+    // HALF: bcur_lo the lo halves of the same step (4 row_slots floats behind the hi halves of a query row)
+    f32x4 bcur[T], bcur_lo[HALF ? T : 1];
+    auto load_b = [&](f32x4(&b)[T], f32x4(&blo)[HALF ? T : 1], int step) {
         if (ABL(512)) return;  // dev: no LDS reads of the query operand (registers keep whatever they hold)
 #pragma unroll
-        for (int t = 0; t < T; t++) b[t] = *reinterpret_cast<const f32x4*>(qrow + (size_t)t * 16 * S + 16 * step);
+        for (int t = 0; t < T; t++) {
+            b[t] = *reinterpret_cast<const f32x4*>(qrow + (size_t)t * 16 * S + 16 * step);
+            if constexpr (HALF) blo[t] = *reinterpret_cast<const f32x4*>(qrow + (size_t)t * 16 * S + 4 * p.row_slots + 16 * step);
+        }
     };
     auto compute_chunk = [&](const f32x4(&a)[CH], int s0, int next_first_step) {
 #pragma unroll
         for (int s = 0; s < CH; s++) {
-            f32x4 bnext[T];
+            f32x4 bnext[T], bnext_lo[HALF ? T : 1];
             if (ABL(64)) {  // dev: no LDS reads, no MFMA -- the loaded data is only summed
 #pragma unroll
                 for (int t = 0; t < T; t++) acc0[t] += a[s];
                 continue;
             }
-            load_b(bnext, s + 1 < CH ? s0 + s + 1 : next_first_step);
+            load_b(bnext, bnext_lo, s + 1 < CH ? s0 + s + 1 : next_first_step);
             f32x4 as = a[s];
-            if (SHIFT && !ABL(1024)) as = as - *reinterpret_cast<const f32x4*>(mus + 4 * g + 16 * (s0 + s));
+            if (F32S && !ABL(1024)) as = as - *reinterpret_cast<const f32x4*>(mus + 4 * g + 16 * (s0 + s));
 #pragma unroll
             for (int t = 0; t < T; t++) {
-                if (BF16) {  // one 16x16x32 bf16 MFMA per k-step (8 bf16 per lane and operand)
+                if (HALF) {  // two 16x16x32 f16 MFMAs per k-step: the query's hi halves, then its lo halves
+                    const f16x8 av = __builtin_bit_cast(f16x8, a[s]);
+                    acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, __builtin_bit_cast(f16x8, bcur[t]), acc0[t], 0, 0, 0);
+                    acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, __builtin_bit_cast(f16x8, bcur_lo[t]), acc1[t], 0, 0, 0);
+                } else if (BF16) {  // one 16x16x32 bf16 MFMA per k-step (8 bf16 per lane and operand)
                     const bf16x8 av = __builtin_bit_cast(bf16x8, a[s]), bv = __builtin_bit_cast(bf16x8, bcur[t]);
                     if (s & 1) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc1[t], 0, 0, 0);
                     else acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc0[t], 0, 0, 0);
@@ -546,7 +633,10 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                 }
             }
 #pragma unroll
-            for (int t = 0; t < T; t++) bcur[t] = bnext[t];
+            for (int t = 0; t < T; t++) {
+                bcur[t] = bnext[t];
+                if constexpr (HALF) bcur_lo[t] = bnext_lo[t];
+            }
         }
     };
 
@@ -559,20 +649,21 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
         int tile = t0 + w, s0 = 0;  // position of the chunk being COMPUTED
         int tiles_done = 0;
         bool exchanged = !XCHG || p.xchg == nullptr || ABL(256);
-        load_b(bcur, 0);
+        load_b(bcur, bcur_lo, 0);
         bool done = false;
         while (!done) {
 #pragma unroll
             for (int j = 0; j < R; j++) {
                 if (!done) {
                     const f32x4 yn = load_norms(tile);
+                    const f32x4 ye = load_meta(p.herr, tile), ys = load_meta(p.hexp, tile);
                     load_chunk(A[(j + R - 1) % R], ltile, ls0);
                     advance_load();
                     __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of the MFMAs
                     int ns0 = s0 + CH, ntile = tile;
                     if (ns0 >= nsteps) { ns0 = 0; ntile = tile + W; }
                     compute_chunk(A[j], s0, ns0);
-                    if (ns0 == 0 && !ABL(8)) epilogue(tile, yn);
+                    if (ns0 == 0 && !ABL(8)) epilogue(tile, yn, ye, ys);
                     if (ns0 == 0) tiles_done++;
                     done = ntile >= t1;
                     tile = ntile; s0 = ns0;

@@ -7,8 +7,10 @@
 
 // ---------------------------------------------------------------- scan kernel
 struct ScanParams {
-    const void* xb;      // [cap][dp] float32 or bf16 rows; 16-byte "slots": row_slots per row
-    const float* norms;  // [cap]
+    const void* xb;      // [cap][dp] float32 or bf16 rows, or the fp16 shadow rows [cap][dph]; 16-byte "slots": row_slots per row
+    const float* norms;  // [cap]; shadow rows: |u~|^2
+    const float* herr = nullptr;  // shadow rows only: [cap] e_r >= |(y - mu) - u~|
+    const float* hexp = nullptr;  // shadow rows only: [cap] s_r (u~ = 2^-s_r fp16(2^s_r (y - mu)))
     const float* q;      // [nq][d]
     const float* mu;     // [dp] shift vector (zero padded), used by SHIFT kernels
     const u64* floor_keys;  // optional [nq]: only keys > floor enter (k > 64 passes)
@@ -19,6 +21,7 @@ struct ScanParams {
     int nq, k, kb, metric;  // kb: block-list slots per query (16 or 32, >= k)
     uint32_t id_base;
     float beta;  // SHIFT kernels: relative width of the lower bound the rows are keyed by (0 = none)
+    float lo_shrink = 1.f;  // shadow rows: factor that takes the bound below the float32 direct-difference value
     int tiles_total, tiles_per_block;
     // one-shot threshold exchange: [nqt][16 T][nblocks] entries (launch seq << 32 | ord(score) of the
     // block's best boot row); null = off.  See scan_kernel.
@@ -36,9 +39,11 @@ struct ScanParams {
 #define LDS_LIMIT (160 * 1024)
 
 // LDS bytes of one scan block (host and device agree through this function)
-__host__ __device__ constexpr size_t scan_lds_layout(int S, int waves, int T, int kb) {
+// (half: the fp16 shadow-row kernel, whose query rows hold hi | lo halves and which keeps e_q and the
+// query's scale exponent beside |x|^2)
+__host__ __device__ constexpr size_t scan_lds_layout(int S, int waves, int T, int kb, bool half = false) {
     return (size_t)S * 4 /* mus: the shift vector, laid out like one query row */ +
-           (size_t)(16 * T) * ((size_t)S * 4 + 4 /* qs, xn */ + 8 /* tauS */ + 8 /* bwc, lockS */ +
+           (size_t)(16 * T) * ((size_t)S * 4 + 4 /* qs, xn */ + (half ? 8 : 0) /* xe, xsh */ + 8 /* tauS */ + 8 /* bwc, lockS */ +
                                (size_t)waves * 4 /* cntS */ + (size_t)kb * 8 /* bootw */ +
                                (size_t)waves * CAP * 8 /* cand; boot staging aliases it */);
 }
@@ -48,3 +53,5 @@ __host__ __device__ constexpr size_t scan_lds_layout(int S, int waves, int T, in
 void ise_launch_scan_f32_shift(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp);
 void ise_launch_scan_f32_plain(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp);
 void ise_launch_scan_bf16(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp);
+// float32 L2 through the fp16 shadow rows (the filter of long indexes; ise_scan.hpp, HALF)
+void ise_launch_scan_f16_shadow(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp);

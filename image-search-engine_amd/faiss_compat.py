@@ -116,6 +116,18 @@ class IndexFlat:
         _n.check(_n.lib.ise_index_short_stats(self._h, out))
         return {"short_batches": int(out[0])}
 
+    def half_stats(self) -> dict:
+        """Batches whose filter read the fp16 shadow rows (include/ise_knn.h, ise_index_half_stats)."""
+        out = (ctypes.c_uint64 * 1)()
+        _n.check(_n.lib.ise_index_half_stats(self._h, out))
+        return {"half_batches": int(out[0])}
+
+    def shadow_row(self, i: int) -> tuple:
+        """(|u~|^2, e_r, s_r) of shadow row i (include/ise_knn.h, ise_index_shadow_row)."""
+        out = (ctypes.c_float * 3)()
+        _n.check(_n.lib.ise_index_shadow_row(self._h, int(i), out))
+        return float(out[0]), float(out[1]), int(out[2])
+
     def range_stats(self) -> dict:
         """Range-search batches and those that needed the overflow pass (include/ise_knn.h, ise_index_range_stats)."""
         out = (ctypes.c_uint64 * 2)()

@@ -102,8 +102,17 @@ int ise_index_stats(ise_index_t* h, uint64_t* out4);
  * backend/engine.py:50-55).  out1[0] = batches scanned that way ($ISE_NO_SHORT=1: none; same bits). */
 int ise_index_short_stats(ise_index_t* h, uint64_t* out1);
 
+/* Long float32 L2 indexes (more than 262144 rows, d <= 1024) keep an fp16 SHADOW of their centred rows,
+ * u~ = 2^-s_r fp16(2^s_r (y - mu)) (+2 bytes per element), which the streaming scan's filter reads instead of
+ * the float32 rows for batches with k <= 12; the re-rank, the certificate and the exact scan still read the float32 rows, so results do
+ * not change ($ISE_NO_HALF_FILTER=1 keeps the float32 filter).  ise_index_half_stats: out1[0] = batches whose
+ * filter read the shadow rows.  ise_index_shadow_row: out3 = (|u~|^2, e_r, s_r) of row i, e_r >= |(y - mu) - u~|
+ * (ISE_E_INVALID when the index has no shadow). */
+int ise_index_half_stats(ise_index_t* h, uint64_t* out1);
+int ise_index_shadow_row(ise_index_t* h, int64_t i, float* out3);
+
 /* Test / rehearsal knobs ($ISE_FORCE_EXACT, $ISE_NO_DIRECT, $ISE_NO_SHORT, $ISE_SHORT_TPB_MAX,
- * $ISE_DIRECT_SHORT_MAX_TILES, $ISE_RANGE_STAGE_CAP) are read from the environment when the library is first used and again when
+ * $ISE_DIRECT_SHORT_MAX_TILES, $ISE_RANGE_STAGE_CAP, $ISE_NO_HALF_FILTER) are read from the environment when the library is first used and again when
  * this is called -- never inside a search. */
 int ise_refresh_env_knobs(void);
 
