@@ -22,6 +22,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
 #define KEY_PAD (~0ull)
@@ -67,6 +68,24 @@ __device__ __forceinline__ float half_lower_bound(float beta, float shrink, floa
     const float lo = r > 0.f ? fmaxf(r * r * shrink - 0x1p-126f, 0.f) : 0.f;
     if (tt != tt) return tt;
     return (tt <= FLT_MAX && lo <= FLT_MAX) ? lo : -FLT_MAX;
+}
+// The byte shadow-row filter's key (ise_scan.hpp, BYTE), the expanded form
+//   lo = |v|^2 + |y - mu|^2 - 2 v~.u~ - 2 (|v| e_r + |y - mu| e_q + e_r e_q) - beta tt,
+// v = x - mu, u~ = c_r q the row's int8 image, v~ the query's two int8 limbs: |v.(y - mu) - v~.u~| <= |v| e_r +
+// |u~| e_q and |u~| <= |y - mu| + e_r.  xn, yn are |v|^2 and the row's float32 norm, tt = xn + yn, dot = v~.u~ as
+// the kernel has it (scaled back), rv and ry the square roots of xn and yn (raised by 2^-60 against their
+// underflow).  beta covers the roundings of xn, yn, dot and of the expression relative to tt, 1 + 2^-10 those of the
+// cross terms, 2^-140 the underflow of the scaled terms; shrink takes a positive bound below the float32
+// direct-difference value the verifier computes.  Non-finite values as half_lower_bound: a NaN norm stays NaN
+// (never a candidate), an overflow (tt or the bound) is keyed -FLT_MAX.
+__device__ __forceinline__ float byte_lower_bound(float beta, float shrink, float xn, float yn, float dot, float rv,
+                                                  float ry, float er, float eq) {
+    const float tt = xn + yn;
+    const float E = fmaf(fmaf(rv, er, fmaf(ry, eq, er * eq)), 1.f + 0x1p-10f, 0x1p-126f);
+    const float dd = fmaf(-beta, tt, (tt - 2.f * dot) - 2.f * E) - 0x1p-140f;
+    const float lo = dd > 0.f ? fmaxf(dd * shrink - 0x1p-126f, 0.f) : dd;
+    if (tt != tt) return tt;
+    return (tt <= FLT_MAX && fabsf(lo) <= FLT_MAX) ? lo : -FLT_MAX;
 }
 __device__ __forceinline__ u64 readlane_u64(u64 v, int src) {
     uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);

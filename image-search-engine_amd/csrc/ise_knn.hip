@@ -12,6 +12,8 @@
 //   mu     [dp]       float32 shift vector of float32 L2 indexes (column mean of the rows)
 //   xh     [cap][dph] fp16 shadow rows of LONG float32 L2 indexes: 2^-s_r fp16(2^s_r (y - mu)), what the
 //   hmeta  [3][cap]   scan's filter reads instead of xb; |u~|^2, e_r, s_r per row (ise_rows.hpp)
+//   xq8    [cap][dpb] int8 shadow rows beside xh: rint((y - mu) / c_r), what the filter of batches with k <= 10 reads;
+//   bmeta  [cap]      c_r (bf16) | e_r / c_r (fp16) per row (ise_rows.hpp, byte_rows_kernel)
 //   part   [nqt][nb][16 T][k] u64  per-block sorted candidate lists (workspace slot)
 //
 // Kernels
@@ -92,7 +94,15 @@ struct ise_index {
     float* hmeta = nullptr;    // [3][cap]: |u~|^2, e_r, s_r
     int dph = 0;               // padded shadow row length (whole 64-byte k-steps)
     bool shadow_off = false;   // its allocation failed: the float32 filter serves (no retry until reset)
-    unsigned long long half_batches = 0;  // batches whose filter read the shadow rows (under mu_)
+    // ... and its byte image (ise_scan.hpp BYTE), kept with the fp16 shadow: set only while xh is
+    void* xq8 = nullptr;       // [cap][dpb] int8
+    uint32_t* bmeta = nullptr; // [cap]: c_r | e_r / c_r
+    int dpb = 0;               // padded byte row length (whole 64-byte k-steps)
+    bool byte_off = false;     // its allocation failed: the fp16 shadow serves (no retry until reset)
+    double byte_rel = 0.0;     // mean e_r / |y - mu| when the byte shadow was last built over all rows (byte_rel_ok)
+    double byte_rho = 1.0;     // ... and the sample rows' mean nearest-neighbour over mean pair distance (byte_rel_ok)
+    unsigned long long half_batches = 0;  // batches whose filter read shadow rows, fp16 or byte (under mu_)
+    unsigned long long byte_batches = 0;  // ... of them, those that read the byte shadow rows (under mu_)
     unsigned long long* stats_dev = nullptr;  // [4]: reranked queries, exact-scan queries
     unsigned long long mu_updates = 0;
     unsigned long long gemm_chunks = 0;  // query chunks that took the large-batch path
@@ -193,8 +203,14 @@ static int pad_dim(int d, int storage) {
     const int steps = (d + per_step - 1) / per_step;
     return (steps > 4 ? (steps + 3) / 4 * 4 : steps) * per_step;
 }
+// byte rows (the int8 shadow): 64 values per k-step, padded as above
+static int pad_bytes(int d) {
+    const int steps = (d + 63) / 64;
+    return (steps > 4 ? (steps + 3) / 4 * 4 : steps) * 64;
+}
 static size_t row_bytes(const ise_index* h) { return (size_t)h->dp * elem_size(h->storage); }
 static size_t shadow_row_bytes(const ise_index* h) { return (size_t)h->dph * 2; }
+static size_t byte_row_bytes(const ise_index* h) { return (size_t)h->dpb; }
 static int chunk_steps_rb(size_t rb) {
     const int steps = (int)(rb / 64);
     for (int ch = 8; ch > 1; ch >>= 1)
@@ -211,6 +227,8 @@ static int qs_stride_units(int units) {
 static int qs_stride_for(const ise_index* h) { return qs_stride_units((int)(row_bytes(h) / 4)); }
 // the shadow-row kernel's query row: fp16 hi halves | lo halves, dph each
 static int qs_stride_half(const ise_index* h) { return qs_stride_units(h->dph); }
+// the byte shadow-row kernel's query row: int8 hi limbs | lo limbs, dpb each
+static int qs_stride_byte(const ise_index* h) { return qs_stride_units(h->dpb / 2); }
 #define KPASS_MAX 36 /* most keys per query one scan pass selects: k = 32 with the exact path's 4 spare candidates still is
                         ONE pass (k = 29..32 took two: 730 us instead of 355 at 1M x 512); more: floor-keyed passes */
 #define XPASS_MAX 32 /* most results per query of one exact-scan pass, of the direct scan and of the large-batch paths */
@@ -268,6 +286,7 @@ extern "C" int ise_index_create_ex(ise_index_t** out, int d, int metric, int dev
     h->storage = storage;
     h->dp = pad_dim(d, storage);
     h->dph = pad_dim(d, ISE_STORE_BF16);
+    h->dpb = pad_bytes(d);
     h->metric = metric;
     h->device = device;
     h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -288,11 +307,18 @@ extern "C" int ise_index_create_ex(ise_index_t** out, int d, int metric, int dev
     return ISE_OK;
 }
 
+static void free_byte_shadow(ise_index* h) {
+    if (h->xq8) (void)hipFree(h->xq8);
+    if (h->bmeta) (void)hipFree(h->bmeta);
+    h->xq8 = nullptr;
+    h->bmeta = nullptr;
+}
 static void free_shadow(ise_index* h) {
     if (h->xh) (void)hipFree(h->xh);
     if (h->hmeta) (void)hipFree(h->hmeta);
     h->xh = nullptr;
     h->hmeta = nullptr;
+    free_byte_shadow(h);
 }
 
 static void free_all(ise_index* h) {
@@ -355,6 +381,7 @@ extern "C" int ise_index_reset(ise_index_t* h) {
     if (h->norms) (void)hipFree(h->norms);
     free_shadow(h);
     h->shadow_off = false;
+    h->byte_off = false;
     h->xb = h->norms = nullptr;
     h->n = h->cap = 0;
     h->shift_pinned = false;
@@ -413,15 +440,35 @@ static int reserve_rows(ise_index* h, long long need, hipStream_t st) {
                                        hipMemcpyDeviceToDevice, st));
         }
     }
+    // ... and so does their byte image (dropped with them; alone when there is no room for it: the fp16 shadow serves)
+    char* nxq = nullptr;
+    uint32_t* nbm = nullptr;
+    if (h->xq8 && nxh) {
+        const size_t qb = byte_row_bytes(h);
+        if (hipMalloc(&nxq, (size_t)want * qb) != hipSuccess || hipMalloc(&nbm, (size_t)want * sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (nxq) (void)hipFree(nxq);
+            nxq = nullptr;
+        } else {
+            HIP_TRY(hipMemcpyAsync(nxq, h->xq8, (size_t)h->n * qb, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemsetAsync(nxq + (size_t)h->n * qb, 0, (size_t)(want - h->n) * qb, st));
+            HIP_TRY(hipMemsetAsync(nbm, 0, (size_t)want * sizeof(uint32_t), st));
+            HIP_TRY(hipMemcpyAsync(nbm, h->bmeta, (size_t)h->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        }
+    }
     HIP_TRY(hipStreamSynchronize(st));
     if (h->xb) HIP_TRY(hipDeviceSynchronize());  // searches in flight on other streams still read the old storage
     if (h->xb) (void)hipFree(h->xb);
     if (h->norms) (void)hipFree(h->norms);
     if (h->xh) {
+        const bool had_byte = h->xq8 != nullptr;
         free_shadow(h);
         h->shadow_off = nxh == nullptr;
+        h->byte_off = h->byte_off || (had_byte && nxh && !nxq);
         h->xh = nxh;
         h->hmeta = nmeta;
+        h->xq8 = nxq;
+        h->bmeta = nbm;
     }
     h->xb = nx;
     h->norms = nn;
@@ -446,6 +493,9 @@ static void launch_shadow(ise_index* h, long long row0, long long n, hipStream_t
         hipLaunchKernelGGL(shadow_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)h->xb, row0, n, h->d,
                            h->dp, (const float*)h->mu, (_Float16*)h->xh, h->dph, h->hmeta, h->hmeta + h->cap,
                            h->hmeta + 2 * h->cap);
+    if (nblk > 0 && h->xq8)
+        hipLaunchKernelGGL(byte_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)h->xb, row0, n, h->d,
+                           h->dp, (const float*)h->mu, (int8_t*)h->xq8, h->dpb, h->bmeta);
 }
 
 static void launch_norms(ise_index* h, long long row0, long long n, hipStream_t st) {
@@ -456,7 +506,7 @@ static void launch_norms(ise_index* h, long long row0, long long n, hipStream_t 
     else
         hipLaunchKernelGGL(norms_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)h->xb, row0, n, h->dp,
                            uses_shift(h) ? h->mu : (const float*)nullptr, h->norms);
-    if (h->xh) launch_shadow(h, row0, n, st);  // the shadow follows the norms (same rows, same mu)
+    if (h->xh) launch_shadow(h, row0, n, st);  // the shadows follow the norms (same rows, same mu)
 }
 
 // Long float32 L2 indexes get the fp16 shadow rows: past the reach of the short-index kernel (<= 262k rows on
@@ -470,20 +520,83 @@ static void launch_norms(ise_index* h, long long row0, long long n, hipStream_t 
 // and 100 four spare candidates no longer cover its width on uniform rows.  Other batches keep the float32 filter.
 #define SHADOW_MAX_ROW_BYTES 2048
 #define SHADOW_MAX_KC 16
+// The byte shadow's bound is wider still (e_r is ~2^-8 of the row's spread instead of ~2^-11): it certifies with
+// kc = 32 filter candidates where the fp16 one needs k + 4, so it takes batches with k <= 10 and
+// runs them at kc = 32 (kb = 32, within the merge's 8-round fast path); k = 11, 12 keep the fp16 shadow.  Only
+// batches of one query tile (nq <= 16, T = 1: the plan measured) take it; larger batches keep the
+// fp16 shadow, whose k + 4 lists still send tie-heavy data (binary rows) to the exact scan as before.
+#define BYTE_MAX_K 10
+#define BYTE_MAX_NQ 16
+#define BYTE_KC 32
+// ... and only on indexes where the byte bound stays narrow beside the neighbour distances, by two statistics taken
+// when the byte shadow is built over all rows (first search past the threshold, a new or pinned mu; rows added
+// behind a fixed mu do not re-evaluate them).  (1) Per-row int8 steps are max |y - mu| / 127, so heavy-tailed rows
+// quantise coarsely: mean e_r / |y - mu| must be at most BYTE_MAX_REL_ERR.  (2) The bound's cross terms scale with
+// |x - mu|, not with the distance to the neighbours, so clustered rows defeat it: over BYTE_SAMPLE rows, the mean
+// nearest-neighbour distance over the mean pair distance must be at least BYTE_MIN_RHO.  In the float64 restatement
+// (scripts/byte_hard_probe.py, profiles/byte/hard_data.jsonl, 60k x 512) uniform rows (0.0040, 0.85) certified every
+// query at kc = 32, while sparse ReLU-like rows (0.024), Gaussian rows (0.0074) and clusters with bounded (0.0045,
+// rho 0.009) or Gaussian (0.0074, 0.079) spreads sent queries to the exact scan that the fp16 route certified, or
+// sit where the issue's 1M-row restatement saw one (Gaussian).  Those indexes keep the fp16 shadow.
+#define BYTE_MAX_REL_ERR 0.005
+#define BYTE_MIN_RHO 0.5
+#define BYTE_SAMPLE 512
+static bool byte_rel_ok(const ise_index* h) { return h->byte_rel <= BYTE_MAX_REL_ERR && h->byte_rho >= BYTE_MIN_RHO; }
+static int measure_byte_rel(ise_index* h, hipStream_t st) {
+    const int m = (int)std::min<long long>(BYTE_SAMPLE, h->n);
+    double* dv = nullptr;
+    float* dist = nullptr;
+    HIP_TRY(hipMalloc(&dv, 2 * sizeof(double)));
+    hipError_t e = hipMalloc(&dist, (size_t)m * m * sizeof(float));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(byte_rel_kernel, dim3(1), dim3(1024), 0, st, (const float*)h->norms, (const uint32_t*)h->bmeta,
+                           h->n, dv);
+        hipLaunchKernelGGL(sample_dist_kernel, dim3((unsigned)(((long long)m * m + 255) / 256)), dim3(256), 0, st,
+                           (const float*)h->xb, h->dp, h->d, h->n / m, m, dist);
+        hipLaunchKernelGGL(rho_kernel, dim3(1), dim3(1024), 0, st, (const float*)dist, m, dv + 1);
+        e = hipGetLastError();
+    }
+    double v[2] = {INFINITY, 0.0};
+    if (e == hipSuccess) e = hipMemcpyAsync(v, dv, 2 * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(dv);
+    if (dist) (void)hipFree(dist);
+    if (e != hipSuccess) return fail(ISE_E_HIP, std::string("byte shadow statistics: ") + hipGetErrorString(e));
+    h->byte_rel = v[0];
+    h->byte_rho = v[1];
+    return ISE_OK;
+}
 static bool shadow_wanted(const ise_index* h) {
     return uses_shift(h) && !h->xh && !h->shadow_off && h->n > SHADOW_MIN_ROWS &&
            shadow_row_bytes(h) <= SHADOW_MAX_ROW_BYTES;
 }
+static bool byte_alloc_refused();  // test knob ISE_FAIL_BYTE_ALLOC (below, with the other knobs)
 static int alloc_shadow(ise_index* h) {
     hipError_t e = hipMalloc(&h->xh, (size_t)h->cap * shadow_row_bytes(h));
     if (e == hipSuccess) e = hipMalloc(&h->hmeta, (size_t)h->cap * 3 * sizeof(float));
     if (e == hipSuccess) e = hipMemset(h->xh, 0, (size_t)h->cap * shadow_row_bytes(h));  // pad rows read zeros
     if (e == hipSuccess) e = hipMemset(h->hmeta, 0, (size_t)h->cap * 3 * sizeof(float));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        free_shadow(h);
+        if (e != hipErrorOutOfMemory) return fail(ISE_E_HIP, std::string("shadow rows: ") + hipGetErrorString(e));
+        h->shadow_off = true;  // no room for it: the float32 filter serves
+        return ISE_OK;
+    }
+    // the byte image (+1 byte per element): no room for it leaves the fp16 shadow serving every batch
+    if (h->byte_off) return ISE_OK;
+    e = byte_alloc_refused() ? hipErrorOutOfMemory : hipMalloc(&h->xq8, (size_t)h->cap * byte_row_bytes(h));
+    if (e == hipSuccess) e = hipMalloc(&h->bmeta, (size_t)h->cap * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(h->xq8, 0, (size_t)h->cap * byte_row_bytes(h));
+    if (e == hipSuccess) e = hipMemset(h->bmeta, 0, (size_t)h->cap * sizeof(uint32_t));
     if (e == hipSuccess) return ISE_OK;
     (void)hipGetLastError();
-    free_shadow(h);
-    if (e != hipErrorOutOfMemory) return fail(ISE_E_HIP, std::string("shadow rows: ") + hipGetErrorString(e));
-    h->shadow_off = true;  // no room for it: the float32 filter serves
+    if (e != hipErrorOutOfMemory) {  // both shadows go: the fp16 one is allocated but not yet filled
+        free_shadow(h);
+        return fail(ISE_E_HIP, std::string("byte shadow rows: ") + hipGetErrorString(e));
+    }
+    free_byte_shadow(h);
+    h->byte_off = true;
     return ISE_OK;
 }
 
@@ -514,10 +627,12 @@ static int prepare_shift_locked(ise_index* h, hipStream_t st) {
         if (rc) return rc;
         if (h->xh) launch_shadow(h, 0, h->norms_rows, st);
     }
+    const bool full = h->norms_rows == 0 || need_shadow;  // every row's shadow is (re)taken now
     if (h->n > h->norms_rows) launch_norms(h, h->norms_rows, h->n - h->norms_rows, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     h->norms_rows = h->n;
+    if (full && h->xq8) return measure_byte_rel(h, st);
     return ISE_OK;
 }
 
@@ -663,13 +778,6 @@ extern "C" int ise_index_reconstruct_host(ise_index_t* h, int64_t i0, int64_t n,
 }
 
 // ---- search
-static void launch_scan(const ise_index* h, bool half, int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st,
-                        const ScanParams& sp) {
-    if (half) ise_launch_scan_f16_shadow(ch, waves, T, grid, lds, st, sp);
-    else if (h->storage == ISE_STORE_BF16) ise_launch_scan_bf16(ch, waves, T, grid, lds, st, sp);
-    else if (uses_shift(h)) ise_launch_scan_f32_shift(ch, waves, T, grid, lds, st, sp);
-    else ise_launch_scan_f32_plain(ch, waves, T, grid, lds, st, sp);
-}
 
 static void launch_short(const ise_index* h, int ch, int waves, int bpc, int grid, size_t lds, hipStream_t st,
                          const ScanParams& sp, const ShortParams& tp) {
@@ -685,10 +793,21 @@ struct ScanPlan {
     int kc;      // keys per query the scan + merge stage selects: k, or k + extra candidates when exact
     bool gemm;   // the batch takes the large-batch path (ise_gemm_scan.hpp): the slot also holds its buffers
     size_t gemm_bytes;
-    bool half;    // float32 L2: the scan filters through the fp16 shadow rows (ise_scan.hpp HALF)
+    bool half;    // float32 L2: the scan filters through shadow rows (ise_scan.hpp HALF, or BYTE when byte is set)
+    bool byte;    // ... through the byte shadow rows (ise_scan.hpp BYTE)
     bool short_;  // the batch's scan is the short-index kernel (ise_short_scan.hpp)
     int short_bpc;  // ... with this many blocks per CU
 };
+
+static void launch_scan(const ise_index* h, const ScanPlan& pl, dim3 grid, hipStream_t st, const ScanParams& sp) {
+    const int ch = pl.ch, waves = pl.waves, T = pl.T;
+    const size_t lds = pl.lds;
+    if (pl.byte) ise_launch_scan_i8_shadow(ch, waves, T, grid, lds, st, sp);
+    else if (pl.half) ise_launch_scan_f16_shadow(ch, waves, T, grid, lds, st, sp);
+    else if (h->storage == ISE_STORE_BF16) ise_launch_scan_bf16(ch, waves, T, grid, lds, st, sp);
+    else if (uses_shift(h)) ise_launch_scan_f32_shift(ch, waves, T, grid, lds, st, sp);
+    else ise_launch_scan_f32_plain(ch, waves, T, grid, lds, st, sp);
+}
 
 // candidates kept beyond k on the exact path: enough that the certificate holds on data whose
 // neighbour spacing exceeds the bound's width.  4 keeps k + extra below the 16-slot block lists at
@@ -708,6 +827,10 @@ static float exact_beta(const ise_index* h) { return (0.5625f * h->dp + 256.f) *
 // terms, an xor butterfly, the differences' own rounding) with room to spare
 static float half_beta(const ise_index* h) { return (5.f * h->dph + 128.f) * 5.9604645e-8f * 1.02f; }
 static float half_lo_shrink(const ise_index* h) { return 1.f - ((float)h->dp / 16.f + 96.f) * 5.9604645e-8f; }
+// the byte shadow-row filter's beta: the roundings of |x - mu|^2 (dpb / 32 fmaf steps, a butterfly,
+// the difference), of the float32 norm (dp / 64 + 9), of the dot (two: 256 A_hi + A_lo, times c_r; the integer
+// sums are exact) and of the expression, relative to tt, with a wide margin: none of them matters beside e_r
+static float byte_beta(const ise_index* h) { return ((float)h->dp / 8.f + 64.f) * 5.9604645e-8f * 1.02f; }
 // Test / rehearsal knobs that may change while the process runs: read from the environment when the library
 // is first used and again whenever ise_refresh_env_knobs() is called (the tests call it after changing the
 // environment) -- never inside a search, where another thread's setenv would race with getenv.
@@ -719,6 +842,8 @@ struct EnvKnobs {
     std::atomic<int> direct_short_max_tiles{0};  // ISE_DIRECT_SHORT_MAX_TILES: longest SHORT index (16-row tiles) whose one-query batches take the direct scan
     std::atomic<int> range_stage_cap{0};  // ISE_RANGE_STAGE_CAP: staging entries per range-search segment (tests: force the overflow pass)
     std::atomic<int> no_half{0};        // ISE_NO_HALF_FILTER=1: long float32 L2 indexes keep the float32 filter (A/B, tests)
+    std::atomic<int> no_byte{0};        // ISE_NO_BYTE_FILTER=1: ... filter through the fp16 shadow, never the byte one
+    std::atomic<int> fail_byte_alloc{0};  // ISE_FAIL_BYTE_ALLOC=1: the byte shadow's allocation fails as out of memory (tests)
     void refresh() {
         auto flag = [](const char* name) { const char* e = getenv(name); return (e && e[0] == '1') ? 1 : 0; };
         auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
@@ -729,6 +854,8 @@ struct EnvKnobs {
         direct_short_max_tiles.store(num("ISE_DIRECT_SHORT_MAX_TILES"));
         range_stage_cap.store(num("ISE_RANGE_STAGE_CAP"));
         no_half.store(flag("ISE_NO_HALF_FILTER"));
+        no_byte.store(flag("ISE_NO_BYTE_FILTER"));
+        fail_byte_alloc.store(flag("ISE_FAIL_BYTE_ALLOC"));
     }
 };
 static EnvKnobs& knobs() {
@@ -742,6 +869,7 @@ extern "C" int ise_refresh_env_knobs(void) {
     return ISE_OK;
 }
 static bool force_exact() { return knobs().force_exact.load(std::memory_order_relaxed) != 0; }
+static bool byte_alloc_refused() { return knobs().fail_byte_alloc.load(std::memory_order_relaxed) != 0; }
 
 static bool xchg_enabled() {  // dev knob: ISE_NO_XCHG=1 switches the threshold exchange off
     static const bool on = [] { const char* e = getenv("ISE_NO_XCHG"); return !(e && e[0] == '1'); }();
@@ -753,14 +881,17 @@ static bool xchg_enabled() {  // dev knob: ISE_NO_XCHG=1 switches the threshold 
 static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool allow_short = true,
                      bool allow_half = true) {
     pl->exact = uses_shift(h);
-    pl->kc = pl->exact ? k + exact_extra(k) : k;
+    // the streamed rows: the byte or the fp16 shadow of a long float32 L2 index, else the index's own rows
+    const bool shadow_ok = allow_half && pl->exact && h->xh != nullptr && !knobs().no_half.load(std::memory_order_relaxed);
+    pl->byte = shadow_ok && h->xq8 != nullptr && byte_rel_ok(h) && !knobs().no_byte.load(std::memory_order_relaxed) &&
+               k <= BYTE_MAX_K && nq <= BYTE_MAX_NQ;
+    pl->kc = pl->exact ? (pl->byte ? BYTE_KC : k + exact_extra(k)) : k;
     pl->kpass = pl->kc < KPASS_MAX ? pl->kc : KPASS_MAX;
     pl->kb = pl->kpass <= 16 ? 16 : (pl->kpass <= 32 ? 32 : KB_MAX);
-    // the streamed rows: the fp16 shadow of a long float32 L2 index, else the index's own rows
-    pl->half = allow_half && pl->exact && h->xh != nullptr && !knobs().no_half.load(std::memory_order_relaxed) &&
-               pl->kc <= SHADOW_MAX_KC;
-    const size_t rb = pl->half ? shadow_row_bytes(h) : row_bytes(h);
+    pl->half = shadow_ok && (pl->byte || pl->kc <= SHADOW_MAX_KC);
+    const size_t rb = pl->byte ? byte_row_bytes(h) : (pl->half ? shadow_row_bytes(h) : row_bytes(h));
     auto lds_bytes = [&](int waves, int T) {
+        if (pl->byte) return scan_lds_layout(qs_stride_byte(h), waves, T, pl->kb, true);
         return pl->half ? scan_lds_layout(qs_stride_half(h), waves, T, pl->kb, true) : scan_lds_bytes(h, waves, T, pl->kb);
     };
     pl->ch = chunk_steps_rb(rb);
@@ -860,7 +991,7 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
     // the row stream for float32 at d = 512), 33 .. 64 as two such passes side by side (grid.y)
     static const bool short_t2 = [] { const char* e = getenv("ISE_SHORT_T2"); return !(e && e[0] == '0'); }();
     const int short_T = nq <= 16 ? 1 : 2;
-    if (allow_short && (nq <= 16 || (short_t2 && nq <= 64)) && pl->kc <= pl->kpass && h->n > 0 &&
+    if (allow_short && !pl->byte && (nq <= 16 || (short_t2 && nq <= 64)) && pl->kc <= pl->kpass && h->n > 0 &&
         !knobs().no_short.load(std::memory_order_relaxed)) {
         int tpb_max = knobs().short_tpb_max.load(std::memory_order_relaxed);
         if (tpb_max <= 0 || tpb_max > SHORT_TPB_MAX) tpb_max = SHORT_TPB_MAX;
@@ -899,6 +1030,7 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
                 pl->nqt = short_nqt;
                 pl->ch = std::min(chunk_steps(h), 4);
                 pl->half = false;  // (never with a shadow: it exists past the short kernel's reach)
+                pl->byte = false;
             }
         }
     }
@@ -1308,7 +1440,13 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
     sp.row_slots = (int)(row_bytes(h) / 16);
     sp.nq = (int)nq; sp.k = pl.kpass; sp.kb = pl.kb; sp.metric = h->metric; sp.id_base = id_base;
     sp.beta = pl.exact ? exact_beta(h) : 0.f;
-    if (pl.half) {  // the filter streams the fp16 shadow rows (ise_scan.hpp HALF)
+    if (pl.byte) {  // the filter streams the byte shadow rows (ise_scan.hpp BYTE) beside the float32 norms
+        sp.xb = h->xq8; sp.bmeta = h->bmeta;
+        sp.qs_stride = qs_stride_byte(h); sp.row_slots = (int)(byte_row_bytes(h) / 16);
+        sp.beta = byte_beta(h); sp.lo_shrink = half_lo_shrink(h);
+        h->half_batches++;
+        h->byte_batches++;
+    } else if (pl.half) {  // the filter streams the fp16 shadow rows (ise_scan.hpp HALF)
         sp.xb = h->xh; sp.norms = h->hmeta; sp.herr = h->hmeta + h->cap; sp.hexp = h->hmeta + 2 * h->cap;
         sp.qs_stride = qs_stride_half(h); sp.row_slots = (int)(shadow_row_bytes(h) / 16);
         sp.beta = half_beta(h); sp.lo_shrink = half_lo_shrink(h);
@@ -1370,7 +1508,7 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
     if (pl.kc <= pl.kpass) {  // one scan pass selects everything the merge stage needs
         if ((rc = next_xchg_seq(w, st, &sp.xchg_seq))) return rc;
         if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e0, st));
-        launch_scan(h, pl.half, pl.ch, pl.waves, pl.T, grid, pl.lds, st, sp);
+        launch_scan(h, pl, grid, st, sp);
         HIP_TRY(hipGetLastError());
         if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e1, st));
         if (pl.exact) {  // merge the kc lower-bound keys, re-rank them exactly, certify or list for the exact scan
@@ -1398,7 +1536,7 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
         sp.floor_keys = off ? floor_dev : nullptr;
         mp.D = nullptr; mp.I = nullptr; mp.keys_out = pass_keys;
         if ((rc = next_xchg_seq(w, st, &sp.xchg_seq))) return rc;
-        launch_scan(h, pl.half, pl.ch, pl.waves, pl.T, grid, pl.lds, st, sp);
+        launch_scan(h, pl, grid, st, sp);
         HIP_TRY(hipGetLastError());
         launch_merge<false>((unsigned)nq, 0, st, mp, xp);
         HIP_TRY(hipGetLastError());
@@ -2137,6 +2275,34 @@ extern "C" int ise_index_half_stats(ise_index_t* h, uint64_t* out1) {
     if (!h || !out1) return fail(ISE_E_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu_);
     out1[0] = h->half_batches;
+    return ISE_OK;
+}
+
+extern "C" int ise_index_byte_stats(ise_index_t* h, uint64_t* out2) {
+    if (!h || !out2) return fail(ISE_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    out2[0] = h->byte_batches;
+    out2[1] = (h->xq8 && byte_rel_ok(h)) ? 1 : 0;
+    return ISE_OK;
+}
+
+extern "C" int ise_index_byte_row(ise_index_t* h, int64_t i, float* out2) {
+    if (!h || !out2) return fail(ISE_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    if (i < 0 || i >= h->n) return fail(ISE_E_INVALID, "row out of range");
+    DeviceGuard gd(h->device);
+    int rc = prepare_shift_locked(h, h->stream);
+    if (rc) return rc;
+    if (!h->xq8) return fail(ISE_E_INVALID, "this index has no byte shadow rows");
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t m = 0;
+    HIP_TRY(hipMemcpy(&m, h->bmeta + i, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint32_t cb = m << 16, eb = m >> 16;
+    float cr;
+    memcpy(&cr, &cb, sizeof(float));
+    const _Float16 eh = __builtin_bit_cast(_Float16, (unsigned short)eb);
+    out2[0] = cr;
+    out2[1] = cr * (float)eh;  // exact: 8 x 11 significant bits
     return ISE_OK;
 }
 

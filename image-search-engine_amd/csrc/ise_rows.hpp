@@ -80,6 +80,137 @@ __global__ __launch_bounds__(256) void shadow_rows_kernel(const float* __restric
     }
 }
 
+// byte shadow rows of a float32 L2 index (ise_scan.hpp BYTE), wave per row, in float64 from the
+// exact a = y - mu:  c_r = max |a| / 127 rounded UP to bf16, the row holds q = rint(a / c_r) in [-127, 127] (zero
+// padded to dpb), and bm packs c_r (bf16, low half) with e_r / c_r (fp16, rounded up, high half), where
+// e_r >= |a - c_r q| (rounded up; the margins of shadow_rows_kernel).  Their product (8 x 11 significant bits) is
+// exact in float32, so the scan recovers e_r with one multiply and a tile's c_r, e_r are one 16-byte load per lane.
+// A row with a NaN or inf entry gets a zero shadow and c_r = 0 (its float32 norm is NaN: never a candidate).
+__global__ __launch_bounds__(256) void byte_rows_kernel(const float* __restrict__ x, long long row0, long long n,
+                                                        int d, int dp, const float* __restrict__ mu,
+                                                        int8_t* __restrict__ xq, int dpb, uint32_t* __restrict__ bm) {
+    const int lane = threadIdx.x & 63;
+    const long long r = row0 + (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= row0 + n) return;
+    const float* xr = x + (size_t)r * dp;
+    double amax = 0.0;
+    float mark = 0.f;
+    for (int j = lane; j < d; j += 64) {
+        const float v = xr[j];
+        mark += v - v;
+        amax = fmax(amax, fabs((double)v - (double)mu[j]));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        amax = fmax(amax, __shfl_xor(amax, o));
+        mark += __shfl_xor(mark, o);
+    }
+    const bool bad = mark != 0.f;
+    const double c = bad ? 0.0 : amax / 127.0;
+    float cf = (float)c;
+    if ((double)cf < c) cf = nextafterf(cf, INFINITY);
+    uint32_t cb = __float_as_uint(cf);
+    if (cb & 0xFFFFu) cb = (cb + 0x10000u) & 0xFFFF0000u;  // bf16, rounded up: |a| / c_r <= 127
+    const double cr = (double)__uint_as_float(cb);
+    int8_t* qr = xq + (size_t)r * dpb;
+    double nu = 0.0, e2 = 0.0;
+    for (int j = lane; j < dpb; j += 64) {
+        const double a = (j < d && !bad) ? (double)xr[j] - (double)mu[j] : 0.0;
+        const double q = cr > 0.0 ? fmin(fmax(rint(a / cr), -127.0), 127.0) : 0.0;
+        qr[j] = (int8_t)q;
+        const double res = a - cr * q;  // cr q is exact (8 + 7 significant bits)
+        nu = fma(a, a, nu);
+        e2 = fma(res, res, e2);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        nu += __shfl_xor(nu, o);
+        e2 += __shfl_xor(e2, o);
+    }
+    if (lane == 0) {
+        const double e = sqrt(e2) * (1.0 + 0x1p-40) + sqrt(nu) * 0x1p-49;
+        const double eps = cr > 0.0 ? e / cr * (1.0 + 0x1p-40) : 0.0;
+        float ef = (float)eps;
+        if ((double)ef < eps) ef = nextafterf(ef, INFINITY);
+        unsigned short hb = __builtin_bit_cast(unsigned short, (_Float16)ef);
+        if ((float)__builtin_bit_cast(_Float16, hb) < ef) hb++;  // fp16, rounded up (eps <= sqrt(d) / 2 + margins)
+        bm[r] = (cb >> 16) | ((uint32_t)hb << 16);
+    }
+}
+
+// The byte route's index statistic (ise_knn.hip, byte_rel_ok): mean e_r / |y - mu| over the rows with a finite,
+// positive norm.  One block, a fixed summation order: deterministic for given rows.
+__global__ __launch_bounds__(1024) void byte_rel_kernel(const float* __restrict__ norms, const uint32_t* __restrict__ bm,
+                                                        long long n, double* __restrict__ out) {
+    __shared__ double ss[1024], sc[1024];
+    double s = 0.0, cnt = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 1024) {
+        const float nn = norms[i];
+        if (nn > 0.f && nn <= FLT_MAX) {  // NaN (a non-finite row), 0 and overflowed norms are left out
+            const uint32_t m = bm[i];
+            const float er = __uint_as_float(m << 16) * (float)__builtin_bit_cast(_Float16, (unsigned short)(m >> 16));
+            s += (double)er / sqrt((double)nn);
+            cnt += 1.0;
+        }
+    }
+    ss[threadIdx.x] = s;
+    sc[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            ss[threadIdx.x] += ss[threadIdx.x + o];
+            sc[threadIdx.x] += sc[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = sc[0] > 0.0 ? ss[0] / sc[0] : 0.0;
+}
+
+// ... and its neighbourhood statistic: squared distances between m sample rows (rows i * stride, float32, fixed order),
+// out[i * m + j], +inf on the diagonal; rho_kernel then takes mean_i min_j d_ij / mean_{i != j} d_ij (one block, m <=
+// 1024, non-finite distances left out).  Small on clustered rows, whose neighbours sit far closer than typical pairs.
+__global__ __launch_bounds__(256) void sample_dist_kernel(const float* __restrict__ x, int dp, int d, long long stride, int m,
+                                                          float* __restrict__ out) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)m * m) return;
+    const int i = (int)(t / m), j = (int)(t % m);
+    const float* a = x + (size_t)i * stride * dp;
+    const float* b = x + (size_t)j * stride * dp;
+    float s = 0.f;
+    for (int c = 0; c < d; c++) s = fmaf(a[c] - b[c], a[c] - b[c], s);
+    out[t] = i == j ? INFINITY : s;
+}
+__global__ __launch_bounds__(1024) void rho_kernel(const float* __restrict__ dist, int m, double* __restrict__ out) {
+    __shared__ double sn[1024], sp[1024], cn[1024], cp[1024];
+    const int i = threadIdx.x;
+    double mn = INFINITY, sum = 0.0, cnt = 0.0;
+    if (i < m)
+        for (int j = 0; j < m; j++) {
+            const float v = dist[(size_t)i * m + j];
+            if (v <= FLT_MAX) {  // finite (the diagonal and non-finite rows are left out)
+                mn = fmin(mn, (double)v);
+                sum += v;
+                cnt += 1.0;
+            }
+        }
+    const bool ok = mn <= 1e300;
+    sn[i] = ok ? mn : 0.0;
+    cn[i] = ok ? 1.0 : 0.0;
+    sp[i] = sum;
+    cp[i] = cnt;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if (i < o) {
+            sn[i] += sn[i + o];
+            cn[i] += cn[i + o];
+            sp[i] += sp[i + o];
+            cp[i] += cp[i + o];
+        }
+        __syncthreads();
+    }
+    if (i == 0) out[0] = (cn[0] > 0.0 && sp[0] > 0.0) ? (sn[0] / cn[0]) / (sp[0] / cp[0]) : 0.0;
+}
+
 // column mean of `rows` rows (d columns of a padded row).  Two levels, both in a fixed order
 // (`groups` row groups summed in row order, then the groups in group order): deterministic for a
 // given row count.  NaN / inf entries are skipped (they must not poison every distance).

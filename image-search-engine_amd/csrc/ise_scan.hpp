@@ -63,18 +63,27 @@
 // accumulator chain), and a row is keyed by lo = (max(0, sqrt(max(0, d~ - beta tt)) - e_r - e_q))^2
 // with d~ = |u~|^2 + |v~|^2 - 2 u~.v~, tt = |u~|^2 + |v~|^2: a rigorous lower bound of the float32
 // direct-difference distance the verifier computes (tests/half_filter_ref.py restates it).
-template <int CH, int W, int T, bool BF16, bool SHIFT, bool HALF = false>
+//
+// BYTE (with SHIFT; long float32 L2 indexes, k <= 10): the same filter read through the BYTE shadow rows
+// q = rint((y - mu) / c_r) in [-127, 127], u~ = c_r q -- a quarter of the float32 bytes, 16x16x64 i8 MFMAs.  The
+// query v = x - mu is staged as two int8 limbs of V = 2^sh v (V ~ 256 hi + lo, one exact i32 accumulator chain
+// per limb), and a row is keyed by the expanded-form bound byte_lower_bound (ise_common.hpp), which uses the
+// float32 norm |y - mu|^2 and bounds only the cross terms by e_r and e_q (tests/byte_filter_ref.py).
+template <int CH, int W, int T, bool BF16, bool SHIFT, int RM = ROWS_OWN>
 __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) void scan_kernel(const ScanParams p) {
+    constexpr bool HALF = RM == ROWS_F16, BYTE = RM == ROWS_I8, SHADOW = HALF || BYTE;
     static_assert(!(BF16 && SHIFT), "the shift is applied to fp32 rows only");
-    static_assert(!HALF || SHIFT, "shadow rows belong to float32 L2 indexes");
-    constexpr bool F32S = SHIFT && !HALF;  // float32 rows shifted in registers
+    static_assert(!SHADOW || SHIFT, "shadow rows belong to float32 L2 indexes");
+    constexpr bool F32S = SHIFT && !SHADOW;  // float32 rows shifted in registers
     if (p.gate && *p.gate == 0u) return;  // a queued rerun that is not needed
     constexpr int BLOCK_THREADS = W * 64;
     // threshold exchange: compiled into the 8-wave kernels with two or more query tiles, where the candidate
     // bookkeeping is what it saves (nq = 48: 560 -> 508 us; nq = 32: 399 (16 waves) -> 383 us).  Not into the
     // 16-wave two-tile kernel (the read costs more than it saves there: 399 -> 406 us; the host picks it
     // for short indexes, where the exchange would not run anyway) nor at T = 1 (neutral).
-    constexpr bool XCHG = T >= 3 || (T == 2 && W == 8);
+    // The byte shadow kernel takes it at T = 1 as well: its kc = 32 lists over ~2000-row blocks admit twice the
+    // candidates of the k + 4 lists, and a grid-wide threshold after the first tile cuts that bookkeeping.
+    constexpr bool XCHG = T >= 3 || (T == 2 && W == 8) || (RM == ROWS_I8 && T == 1 && W == 8);
     constexpr int NQ = 16 * T;                        // queries per block pass
     // threads staging one query row (per tile).  16-wave blocks stage with their first 8 waves: |x|^2 then has the
     // summation order of the 8-wave kernels (and of short_scan_kernel), and the bf16 L2 distances, which carry it,
@@ -89,9 +98,9 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     float* mus = reinterpret_cast<float*>(smem);                // [S] shift vector (SHIFT only)
     float* qs = mus + S;                                        // [NQ][S]
     float* xn = qs + NQ * S;                                    // [NQ]
-    float* xe = xn + NQ;                                        // [NQ] HALF: e_q
-    int* xsh = reinterpret_cast<int*>(xe + NQ);                 // [NQ] HALF: the query's scale exponent sh
-    u64* tauS = reinterpret_cast<u64*>(xn + (HALF ? 3 : 1) * NQ);  // [NQ]
+    float* xe = xn + NQ;                                        // [NQ] SHADOW: e_q
+    int* xsh = reinterpret_cast<int*>(xe + NQ);                 // [NQ] SHADOW: the query's scale exponent sh
+    u64* tauS = reinterpret_cast<u64*>(xn + (SHADOW ? 3 : 1) * NQ);  // [NQ]
     int* bwc = reinterpret_cast<int*>(tauS + NQ);               // [NQ]
     int* lockS = bwc + NQ;                                      // [NQ]
     int* cntS = lockS + NQ;                                     // [W][NQ]
@@ -124,9 +133,9 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     auto load_norms = [&](int tile) -> f32x4 {
         return *reinterpret_cast<const f32x4*>(p.norms + (size_t)tile * 16 + 4 * g);
     };
-    auto load_meta = [&](const float* m, int tile) -> f32x4 {  // HALF: e_r or s_r of the tile's rows
-        if constexpr (!HALF) return (f32x4){0.f, 0.f, 0.f, 0.f};
-        return *reinterpret_cast<const f32x4*>(m + (size_t)tile * 16 + 4 * g);
+    auto load_meta = [&](const void* m, int tile) -> f32x4 {  // HALF: e_r or s_r, BYTE: packed c_r | e_r / c_r
+        if constexpr (!SHADOW) return (f32x4){0.f, 0.f, 0.f, 0.f};
+        return *reinterpret_cast<const f32x4*>(static_cast<const float*>(m) + (size_t)tile * 16 + 4 * g);
     };
 
     // ---- query staging, step 1: REQUEST the query tiles first (small, L2-resident after
@@ -139,7 +148,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     constexpr int QVS = QV / FPS;      // slots per thread and tile
     const int S4 = S >> 2;             // 16-byte slots per LDS query row
     const int dslots = BF16 ? (p.d >> 3) : (p.d >> 2);  // slots that carry data (vector path only)
-    const bool vec_q = !HALF && (p.d & (BF16 ? 7 : 3)) == 0 && ((reinterpret_cast<uintptr_t>(p.q) & 15) == 0) &&
+    const bool vec_q = !SHADOW && (p.d & (BF16 ? 7 : 3)) == 0 && ((reinterpret_cast<uintptr_t>(p.q) & 15) == 0) &&
                        S4 <= TPR * QVS;
     f32x4 qv[T][QV];
     f32x4 muv[F32S ? QVS : 1];
@@ -296,6 +305,63 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                 // |v~|^2: NaN for a non-finite entry (never enters), +inf when x - mu overflowed (keyed -FLT_MAX)
                 xn[cc] = mark != 0.f ? mark : (ovf ? INFINITY : ldexpf(sn, -2 * sh));
             }
+        } else if (BYTE) {
+            // byte shadow rows: V = 2^sh fl(x - mu) with max |V| in [2^13, 2^14), split into int8 limbs hi = rint(V / 256)
+            // and lo = rint(V - 256 hi + 2^sh v_lo) (v_lo the TwoSum remainder of x - mu), so that 256 hi + lo misses
+            // 2^sh v by res per entry; e_q bounds |v - v~| from the residuals.  |v|^2 is taken of fl(x - mu).
+            const bool rowok = cc < nqt && !ABL(1);
+            const float* src = p.q + (size_t)(q0 + (rowok ? cc : 0)) * p.d;
+            float amax = 0.f, mark = 0.f;
+            if (rowok)
+                for (int j = t; j < p.d; j += TPR) {
+                    const float y = src[j];
+                    amax = fmaxf(amax, fabsf(y - p.mu[j]));
+                    mark += y - y;  // NaN for a non-finite entry (ise_common.hpp, nonfinite_mark)
+                }
+#pragma unroll
+            for (int o = TPR / 2; o > 0; o >>= 1) {
+                amax = fmaxf(amax, __shfl_xor(amax, o));
+                mark += __shfl_xor(mark, o);
+            }
+            const bool ovf = !(amax <= FLT_MAX);  // x - mu overflowed: no bound (keyed -FLT_MAX below)
+            const bool skip = ovf || mark != 0.f;
+            const int sh = (amax > 0.f && !ovf) ? 13 - ilogbf(amax) : 0;
+            int8_t* hi = reinterpret_cast<int8_t*>(qs + cc * S);
+            int8_t* lo = reinterpret_cast<int8_t*>(qs + cc * S + 4 * p.row_slots);
+            float e2 = 0.f;
+            const int dpb = p.row_slots * 16;
+            for (int j = t; j < dpb; j += TPR) {
+                float vh = 0.f, vl = 0.f;
+                if (rowok && j < p.d && !skip) {
+                    const float y = src[j], m = p.mu[j];
+                    vh = y - m;
+                    const float bb = vh - y;
+                    vl = (y - (vh - bb)) + (-m - bb);  // v = vh + vl exactly
+                }
+                const float V = ldexpf(vh, sh), VL = ldexpf(vl, sh);
+                float h1 = rintf(V * (1.f / 256.f));  // |h1| <= 64
+                const float r1 = fmaf(-256.f, h1, V);  // exact
+                float l1 = rintf(r1 + VL);              // |l1| <= 128
+                const float res = (r1 - l1) + VL;       // r1 - l1 exact
+                if (l1 > 127.f) { h1 += 1.f; l1 -= 256.f; }  // the same 256 hi + lo, lo in int8
+                hi[j] = (int8_t)h1;
+                lo[j] = (int8_t)l1;
+                sn = fmaf(V, V, sn);
+                e2 = fmaf(res, res, e2);
+            }
+#pragma unroll
+            for (int o = TPR / 2; o > 0; o >>= 1) {
+                sn += __shfl_xor(sn, o);
+                e2 += __shfl_xor(e2, o);
+            }
+            if (t == 0) {
+                // scaled units: |V - V~| <= sqrt(e2) up to the rounding of e2 (the margins) and 2^-44 |V| (res)
+                const float es = sqrtf(e2 * (1.f + 0x1p-9f)) * (1.f + 0x1p-20f) + 0x1p-44f * sqrtf(sn);
+                xe[cc] = ldexpf(es, -sh);
+                xsh[cc] = sh;
+                // |v|^2: NaN for a non-finite entry (never enters), +inf when x - mu overflowed (keyed -FLT_MAX)
+                xn[cc] = mark != 0.f ? mark : (ovf ? INFINITY : ldexpf(sn, -2 * sh));
+            }
         } else {  // odd d, unaligned queries or very long rows: scalar path, one 4-byte unit at a time
             // (the loads of SB units are requested together, then consumed in the same ascending order as a
             // plain loop would: |x|^2 keeps its summation order, the staging of a 2048-float row its round trips
@@ -337,7 +403,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                 }
             }
         }
-        if (!HALF) {
+        if (!SHADOW) {
 #pragma unroll
             for (int o = TPR / 2; o > 0; o >>= 1) sn += __shfl_xor(sn, o);
             if (t == 0) xn[cc] = sn;
@@ -355,16 +421,17 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     const float* qrow = qs + c * S + 4 * g;
     const bool use_floor = p.floor_keys != nullptr;
 
-    float xq_n[T], xq_e[T];
+    float xq_n[T], xq_e[T], xq_r[T];
     int xq_sh[T];
     u64 tau[T];
     int cnt[T];
-    f32x4 acc0[T], acc1[T];
+    f32x4 acc0[T], acc1[T];  // BYTE: i32 accumulators (bit casts)
 #pragma unroll
     for (int t = 0; t < T; t++) {
         xq_n[t] = xn[t * 16 + c];
-        xq_e[t] = HALF ? xe[t * 16 + c] : 0.f;
-        xq_sh[t] = HALF ? xsh[t * 16 + c] : 0;
+        xq_e[t] = SHADOW ? xe[t * 16 + c] : 0.f;
+        xq_sh[t] = SHADOW ? xsh[t * 16 + c] : 0;
+        xq_r[t] = BYTE ? sqrtf(xq_n[t]) + 0x1p-60f : 0.f;
         tau[t] = TAU0;
         cnt[t] = 0;
         acc0[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -450,6 +517,13 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     auto score = [&](int t, float dotj, float ynj, float yej, float ysj) -> float {
         if constexpr (HALF) return half_lower_bound(p.beta, p.lo_shrink, xq_n[t] + ynj,
                                                     ldexpf(dotj, -((int)ysj + xq_sh[t])), yej + xq_e[t]);
+        if constexpr (BYTE) {  // dotj = 256 A_hi + A_lo; yej the packed c_r | e_r / c_r
+            const uint32_t m = __float_as_uint(yej);
+            const float cr = __uint_as_float(m << 16);
+            const float er = cr * (float)__builtin_bit_cast(_Float16, (unsigned short)(m >> 16));  // exact
+            return byte_lower_bound(p.beta, p.lo_shrink, xq_n[t], ynj, ldexpf(dotj * cr, -xq_sh[t]), xq_r[t],
+                                    sqrtf(ynj) + 0x1p-60f, er, xq_e[t]);
+        }
         if (l2) {
             const float tt = xq_n[t] + ynj;
             const float sc = tt - 2.f * dotj;
@@ -479,7 +553,12 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
         f32x4 sc[T];
 #pragma unroll
         for (int t = 0; t < T; t++) {
-            const f32x4 dot = acc0[t] + acc1[t];
+            f32x4 dot = acc0[t] + acc1[t];
+            if constexpr (BYTE) {  // the exact integer dot products of the hi and lo limbs (|A| < 2^24 for dpb <= 1024)
+                const i32x4 ah = __builtin_bit_cast(i32x4, acc0[t]), al = __builtin_bit_cast(i32x4, acc1[t]);
+#pragma unroll
+                for (int j = 0; j < 4; j++) dot[j] = fmaf(256.f, (float)ah[j], (float)al[j]);
+            }
             acc0[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
             acc1[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -593,20 +672,20 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     // B operand (queries, from LDS) is software-pipelined one k-step ahead of the MFMAs
     // that consume it, across chunk boundaries too: bcur holds the B fragments of the
     // next step to be computed.
-    // HALF: bcur_lo the lo halves of the same step (4 row_slots floats behind the hi halves of a query row)
-    f32x4 bcur[T], bcur_lo[HALF ? T : 1];
-    auto load_b = [&](f32x4(&b)[T], f32x4(&blo)[HALF ? T : 1], int step) {
+    // SHADOW: bcur_lo the lo limbs of the same step (4 row_slots floats behind the hi limbs of a query row)
+    f32x4 bcur[T], bcur_lo[SHADOW ? T : 1];
+    auto load_b = [&](f32x4(&b)[T], f32x4(&blo)[SHADOW ? T : 1], int step) {
         if (ABL(512)) return;  // dev: no LDS reads of the query operand (registers keep whatever they hold)
 #pragma unroll
         for (int t = 0; t < T; t++) {
             b[t] = *reinterpret_cast<const f32x4*>(qrow + (size_t)t * 16 * S + 16 * step);
-            if constexpr (HALF) blo[t] = *reinterpret_cast<const f32x4*>(qrow + (size_t)t * 16 * S + 4 * p.row_slots + 16 * step);
+            if constexpr (SHADOW) blo[t] = *reinterpret_cast<const f32x4*>(qrow + (size_t)t * 16 * S + 4 * p.row_slots + 16 * step);
         }
     };
     auto compute_chunk = [&](const f32x4(&a)[CH], int s0, int next_first_step) {
 #pragma unroll
         for (int s = 0; s < CH; s++) {
-            f32x4 bnext[T], bnext_lo[HALF ? T : 1];
+            f32x4 bnext[T], bnext_lo[SHADOW ? T : 1];
             if (ABL(64)) {  // dev: no LDS reads, no MFMA -- the loaded data is only summed
 #pragma unroll
                 for (int t = 0; t < T; t++) acc0[t] += a[s];
@@ -617,7 +696,15 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
             if (F32S && !ABL(1024)) as = as - *reinterpret_cast<const f32x4*>(mus + 4 * g + 16 * (s0 + s));
 #pragma unroll
             for (int t = 0; t < T; t++) {
-                if (HALF) {  // two 16x16x32 f16 MFMAs per k-step: the query's hi halves, then its lo halves
+                if (BYTE) {  // two 16x16x64 i8 MFMAs per k-step: the query's hi limbs, then its lo limbs
+                    const i32x4 av = __builtin_bit_cast(i32x4, a[s]);
+                    acc0[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(
+                                                            av, __builtin_bit_cast(i32x4, bcur[t]),
+                                                            __builtin_bit_cast(i32x4, acc0[t]), 0, 0, 0));
+                    acc1[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(
+                                                            av, __builtin_bit_cast(i32x4, bcur_lo[t]),
+                                                            __builtin_bit_cast(i32x4, acc1[t]), 0, 0, 0));
+                } else if (HALF) {  // two 16x16x32 f16 MFMAs per k-step: the query's hi halves, then its lo halves
                     const f16x8 av = __builtin_bit_cast(f16x8, a[s]);
                     acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, __builtin_bit_cast(f16x8, bcur[t]), acc0[t], 0, 0, 0);
                     acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, __builtin_bit_cast(f16x8, bcur_lo[t]), acc1[t], 0, 0, 0);
@@ -635,7 +722,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
 #pragma unroll
             for (int t = 0; t < T; t++) {
                 bcur[t] = bnext[t];
-                if constexpr (HALF) bcur_lo[t] = bnext_lo[t];
+                if constexpr (SHADOW) bcur_lo[t] = bnext_lo[t];
             }
         }
     };
@@ -656,7 +743,8 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
             for (int j = 0; j < R; j++) {
                 if (!done) {
                     const f32x4 yn = load_norms(tile);
-                    const f32x4 ye = load_meta(p.herr, tile), ys = load_meta(p.hexp, tile);
+                    const f32x4 ye = load_meta(BYTE ? (const void*)p.bmeta : p.herr, tile);
+                    const f32x4 ys = HALF ? load_meta(p.hexp, tile) : (f32x4){0.f, 0.f, 0.f, 0.f};
                     load_chunk(A[(j + R - 1) % R], ltile, ls0);
                     advance_load();
                     __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of the MFMAs

@@ -3,5 +3,5 @@
 #include "ise_scan_launch.hpp"
 
 void ise_launch_scan_f16_shadow(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp) {
-    launch_scan_v<false, true, true>(ch, waves, T, grid, lds, st, sp);
+    launch_scan_v<false, true, ROWS_F16>(ch, waves, T, grid, lds, st, sp);
 }

@@ -6,11 +6,15 @@
 #include "ise_common.hpp"
 
 // ---------------------------------------------------------------- scan kernel
+// what scan_kernel streams (its RM parameter): the index's own rows, or a shadow of float32 L2 rows
+enum RowMode : int { ROWS_OWN = 0, ROWS_F16 = 1, ROWS_I8 = 2 };
+
 struct ScanParams {
-    const void* xb;      // [cap][dp] float32 or bf16 rows, or the fp16 shadow rows [cap][dph]; 16-byte "slots": row_slots per row
-    const float* norms;  // [cap]; shadow rows: |u~|^2
+    const void* xb;      // [cap][dp] float32 or bf16 rows, or the fp16 / byte shadow rows [cap][dph] / [cap][dpb]; 16-byte "slots": row_slots per row
+    const float* norms;  // [cap]; fp16 shadow rows: |u~|^2 (byte shadow rows: the float32 |y - mu|^2)
     const float* herr = nullptr;  // shadow rows only: [cap] e_r >= |(y - mu) - u~|
     const float* hexp = nullptr;  // shadow rows only: [cap] s_r (u~ = 2^-s_r fp16(2^s_r (y - mu)))
+    const uint32_t* bmeta = nullptr;  // byte shadow rows only: [cap] c_r (bf16) | e_r / c_r (fp16) << 16
     const float* q;      // [nq][d]
     const float* mu;     // [dp] shift vector (zero padded), used by SHIFT kernels
     const u64* floor_keys;  // optional [nq]: only keys > floor enter (k > 64 passes)
@@ -39,11 +43,11 @@ struct ScanParams {
 #define LDS_LIMIT (160 * 1024)
 
 // LDS bytes of one scan block (host and device agree through this function)
-// (half: the fp16 shadow-row kernel, whose query rows hold hi | lo halves and which keeps e_q and the
+// (shadow: the fp16 or byte shadow-row kernel, whose query rows hold hi | lo limbs and which keeps e_q and the
 // query's scale exponent beside |x|^2)
-__host__ __device__ constexpr size_t scan_lds_layout(int S, int waves, int T, int kb, bool half = false) {
+__host__ __device__ constexpr size_t scan_lds_layout(int S, int waves, int T, int kb, bool shadow = false) {
     return (size_t)S * 4 /* mus: the shift vector, laid out like one query row */ +
-           (size_t)(16 * T) * ((size_t)S * 4 + 4 /* qs, xn */ + (half ? 8 : 0) /* xe, xsh */ + 8 /* tauS */ + 8 /* bwc, lockS */ +
+           (size_t)(16 * T) * ((size_t)S * 4 + 4 /* qs, xn */ + (shadow ? 8 : 0) /* xe, xsh */ + 8 /* tauS */ + 8 /* bwc, lockS */ +
                                (size_t)waves * 4 /* cntS */ + (size_t)kb * 8 /* bootw */ +
                                (size_t)waves * CAP * 8 /* cand; boot staging aliases it */);
 }
@@ -53,5 +57,6 @@ __host__ __device__ constexpr size_t scan_lds_layout(int S, int waves, int T, in
 void ise_launch_scan_f32_shift(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp);
 void ise_launch_scan_f32_plain(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp);
 void ise_launch_scan_bf16(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp);
-// float32 L2 through the fp16 shadow rows (the filter of long indexes; ise_scan.hpp, HALF)
+// float32 L2 through the fp16 or the byte shadow rows (the filter of long indexes; ise_scan.hpp, HALF / BYTE)
 void ise_launch_scan_f16_shadow(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp);
+void ise_launch_scan_i8_shadow(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp);

@@ -117,10 +117,23 @@ class IndexFlat:
         return {"short_batches": int(out[0])}
 
     def half_stats(self) -> dict:
-        """Batches whose filter read the fp16 shadow rows (include/ise_knn.h, ise_index_half_stats)."""
+        """Batches whose filter read shadow rows, fp16 or byte (include/ise_knn.h, ise_index_half_stats)."""
         out = (ctypes.c_uint64 * 1)()
         _n.check(_n.lib.ise_index_half_stats(self._h, out))
         return {"half_batches": int(out[0])}
+
+    def byte_stats(self) -> dict:
+        """Batches whose filter read the byte shadow rows, and whether the index's byte route is open (include/ise_knn.h,
+        ise_index_byte_stats)."""
+        out = (ctypes.c_uint64 * 2)()
+        _n.check(_n.lib.ise_index_byte_stats(self._h, out))
+        return {"byte_batches": int(out[0]), "byte_route": bool(out[1])}
+
+    def byte_row(self, i: int) -> tuple:
+        """(c_r, e_r) of byte shadow row i (include/ise_knn.h, ise_index_byte_row)."""
+        out = (ctypes.c_float * 2)()
+        _n.check(_n.lib.ise_index_byte_row(self._h, int(i), out))
+        return float(out[0]), float(out[1])
 
     def shadow_row(self, i: int) -> tuple:
         """(|u~|^2, e_r, s_r) of shadow row i (include/ise_knn.h, ise_index_shadow_row)."""

@@ -103,16 +103,23 @@ int ise_index_stats(ise_index_t* h, uint64_t* out4);
 int ise_index_short_stats(ise_index_t* h, uint64_t* out1);
 
 /* Long float32 L2 indexes (more than 262144 rows, d <= 1024) keep an fp16 SHADOW of their centred rows,
- * u~ = 2^-s_r fp16(2^s_r (y - mu)) (+2 bytes per element), which the streaming scan's filter reads instead of
- * the float32 rows for batches with k <= 12; the re-rank, the certificate and the exact scan still read the float32 rows, so results do
- * not change ($ISE_NO_HALF_FILTER=1 keeps the float32 filter).  ise_index_half_stats: out1[0] = batches whose
- * filter read the shadow rows.  ise_index_shadow_row: out3 = (|u~|^2, e_r, s_r) of row i, e_r >= |(y - mu) - u~|
- * (ISE_E_INVALID when the index has no shadow). */
+ * u~ = 2^-s_r fp16(2^s_r (y - mu)) (+2 bytes per element), and a BYTE shadow beside it, q = rint((y - mu) / c_r)
+ * in [-127, 127] (+1 byte per element).  The streaming scan's filter reads the byte shadow for batches with k <= 10
+ * and nq <= 16, and the fp16 one for the other batches with k <= 12, instead of the float32 rows; the re-rank, the certificate and the exact scan
+ * still read the float32 rows, so results do not change ($ISE_NO_BYTE_FILTER=1 keeps the fp16 shadow for k <= 10,
+ * $ISE_NO_HALF_FILTER=1 the float32 filter for every batch).  ise_index_half_stats: out1[0] = batches whose filter
+ * read shadow rows of either kind.  ise_index_byte_stats: out2[0] = those of them that read the byte shadow, out2[1] = 1
+ * when the index's byte route is open (the byte shadow exists and its build-time statistics admit it).
+ * ise_index_shadow_row: out3 = (|u~|^2, e_r, s_r) of fp16 shadow row i, e_r >= |(y - mu) - u~|.
+ * ise_index_byte_row: out2 = (c_r, e_r) of byte shadow row i, e_r >= |(y - mu) - c_r q|.  Both ISE_E_INVALID when the
+ * index has no such shadow. */
 int ise_index_half_stats(ise_index_t* h, uint64_t* out1);
+int ise_index_byte_stats(ise_index_t* h, uint64_t* out2);
 int ise_index_shadow_row(ise_index_t* h, int64_t i, float* out3);
+int ise_index_byte_row(ise_index_t* h, int64_t i, float* out2);
 
 /* Test / rehearsal knobs ($ISE_FORCE_EXACT, $ISE_NO_DIRECT, $ISE_NO_SHORT, $ISE_SHORT_TPB_MAX,
- * $ISE_DIRECT_SHORT_MAX_TILES, $ISE_RANGE_STAGE_CAP, $ISE_NO_HALF_FILTER) are read from the environment when the library is first used and again when
+ * $ISE_DIRECT_SHORT_MAX_TILES, $ISE_RANGE_STAGE_CAP, $ISE_NO_HALF_FILTER, $ISE_NO_BYTE_FILTER, $ISE_FAIL_BYTE_ALLOC) are read from the environment when the library is first used and again when
  * this is called -- never inside a search. */
 int ise_refresh_env_knobs(void);
 
