@@ -44,6 +44,7 @@
 #include "ise_rows.hpp"
 #include "ise_short_scan.hpp"
 #include "ise_range.hpp"
+#include "ise_stage.hpp"
 
 // ---------------------------------------------------------------- host side
 static thread_local std::string g_err;
@@ -2317,6 +2318,40 @@ extern "C" int ise_index_shadow_row(ise_index_t* h, int64_t i, float* out3) {
     HIP_TRY(hipDeviceSynchronize());
     for (int j = 0; j < 3; j++)
         HIP_TRY(hipMemcpy(out3 + j, h->hmeta + (size_t)j * h->cap + i, sizeof(float), hipMemcpyDeviceToHost));
+    return ISE_OK;
+}
+
+// Tests only: one query row through the shadow filters' staging (ise_stage.hpp) in a one-block kernel.
+extern "C" int ise_index_stage_query_debug(ise_index_t* h, const void* q_dev, int route, void* limbs, int64_t limbs_bytes,
+                                           float* out2, int32_t* info3) {
+    if (!h || !q_dev || !limbs || !out2 || !info3) return fail(ISE_E_INVALID, "NULL argument");
+    if (route != 0 && route != 1) return fail(ISE_E_INVALID, "route: 0 = fp16 shadow, 1 = byte shadow");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    DeviceGuard gd(h->device);
+    int rc = prepare_shift_locked(h, h->stream);
+    if (rc) return rc;
+    if (route == 1 ? !h->xq8 : !h->xh) return fail(ISE_E_INVALID, "this index has no such shadow rows");
+    const int P = route == 1 ? h->dpb : h->dph, es = route == 1 ? 1 : 2;
+    const size_t need = (size_t)2 * P * es;
+    if (P > 1024 || limbs_bytes < (int64_t)need) return fail(ISE_E_INVALID, "limbs: room for hi and lo of the padded row needed");
+    unsigned char* dev = nullptr;
+    HIP_TRY(hipMalloc(&dev, need + 16));
+    float* out_f = reinterpret_cast<float*>(dev + need);  // need is a multiple of 4
+    int* out_i = reinterpret_cast<int*>(dev + need + 8);
+    if (route == 1)
+        hipLaunchKernelGGL(stage_debug_kernel<true>, dim3(1), dim3(32), 0, h->stream, (const float*)q_dev, h->mu, h->d, P, dev, out_f, out_i);
+    else
+        hipLaunchKernelGGL(stage_debug_kernel<false>, dim3(1), dim3(32), 0, h->stream, (const float*)q_dev, h->mu, h->d, P, dev, out_f, out_i);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    std::vector<unsigned char> host(need + 16);
+    if (e == hipSuccess) e = hipMemcpy(host.data(), dev, need + 16, hipMemcpyDeviceToHost);
+    (void)hipFree(dev);
+    HIP_TRY(e);
+    memcpy(limbs, host.data(), need);
+    memcpy(out2, host.data() + need, 8);
+    memcpy(info3, host.data() + need + 8, 8);
+    info3[2] = P;
     return ISE_OK;
 }
 

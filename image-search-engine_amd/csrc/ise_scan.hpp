@@ -3,6 +3,7 @@
 #include "ise_common.hpp"
 #include "ise_scan_params.hpp"
 #include "ise_select.hpp"
+#include "ise_stage.hpp"
 
 #ifdef ISE_ABLATE
 #define ABL(bit) (p.ablate & (bit))
@@ -179,6 +180,23 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
             }
         }
     }
+    // shadow rows: the same request, through ise_stage.hpp (mu once, then the rows of every query tile)
+    const int PS = p.row_slots * (BYTE ? 16 : 8);  // SHADOW: padded row length in elements (dpb / dph)
+    // (not in 16-wave blocks: at their 128 VGPRs two tiles' rows would spill, and the plan sends shadow rows to them
+    // only when the threshold exchange is switched off)
+    const bool vec_s = SHADOW && W < 16 && shadow_vec_ok(p.d, PS, p.q, TPR);
+    f32x4 sqv[SHADOW ? T : 1][SHADOW_QV], smuv[SHADOW_QV];
+    auto shadow_src = [&](int tq) -> const float* {
+        const int cc = tq * 16 + tid / TPR;
+        return p.q + (size_t)(q0 + ((cc < nqt && !ABL(1)) ? cc : 0)) * p.d;
+    };
+    if constexpr (SHADOW) {
+        if (vec_s && stager) {
+            stage_request_row(smuv, p.mu, tid % TPR, TPR, p.d >> 2);
+#pragma unroll
+            for (int tq = 0; tq < T; tq++) stage_request_row(sqv[tq], shadow_src(tq), tid % TPR, TPR, p.d >> 2);
+        }
+    }
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- register ring of R index chunks (CH k-steps x 16 rows each).  Chunk positions
@@ -248,119 +266,24 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                     }
                 }
             }
-        } else if (HALF) {
-            // fp16 shadow rows: v = x - mu exactly as the float pair (v_hi, v_lo) (TwoSum), scaled by 2^sh so that
-            // max |v| lands in [2^14, 2^15), split into fp16 hi | lo halves (two MFMA operands); e_q bounds what the
-            // split misses.  Two passes over the query (L2-resident): the scale needs max |v| first.
-            const bool rowok = cc < nqt && !ABL(1);
-            const float* src = p.q + (size_t)(q0 + (rowok ? cc : 0)) * p.d;
-            float amax = 0.f, mark = 0.f;
-            if (rowok)
-                for (int j = t; j < p.d; j += TPR) {
-                    const float y = src[j];
-                    amax = fmaxf(amax, fabsf(y - p.mu[j]));
-                    mark += y - y;  // NaN for a non-finite entry (ise_common.hpp, nonfinite_mark)
+        } else if (SHADOW) {
+            // shadow rows (ise_stage.hpp): v = x - mu exactly as a float pair, scaled by 2^sh, split into fp16 hi | lo
+            // halves (HALF) or int8 limbs (BYTE); e_q bounds what the split misses.  From the registers requested in
+            // step 1 when the shape allows, else two scalar passes over the query.
+            if constexpr (SHADOW) {
+                const bool rowok = cc < nqt && !ABL(1);
+                unsigned char* hi = reinterpret_cast<unsigned char*>(qs + cc * S);
+                unsigned char* lo = hi + 16 * p.row_slots;
+                if (vec_s) {
+                    float amax, mark;
+                    stage_shadow_vec_scale<TPR>(sqv[tq], smuv, shadow_src(tq), p.mu, p.d >> 2, rowok, t, PS >> 2, tq > 0,
+                                                amax, mark);
+                    stage_shadow_vec_limbs<BYTE, TPR>(sqv[tq], smuv, shadow_src(tq), p.mu, p.d >> 2, rowok, t, PS >> 2,
+                                                      amax, mark, hi, lo, xn + cc, xe + cc, xsh + cc);
+                } else {
+                    stage_shadow_scalar<BYTE, TPR>(shadow_src(tq), p.mu, p.d, PS, rowok, t, hi, lo, xn + cc, xe + cc,
+                                                   xsh + cc);
                 }
-#pragma unroll
-            for (int o = TPR / 2; o > 0; o >>= 1) {
-                amax = fmaxf(amax, __shfl_xor(amax, o));
-                mark += __shfl_xor(mark, o);
-            }
-            const bool ovf = !(amax <= FLT_MAX);  // x - mu overflowed: no bound (keyed -FLT_MAX below)
-            const bool skip = ovf || mark != 0.f;
-            const int sh = (amax > 0.f && !ovf) ? 14 - ilogbf(amax) : 0;
-            _Float16* hi = reinterpret_cast<_Float16*>(qs + cc * S);
-            _Float16* lo = reinterpret_cast<_Float16*>(qs + cc * S + 4 * p.row_slots);
-            float e2 = 0.f;
-            const int dph = p.row_slots * 8;
-            for (int j = t; j < dph; j += TPR) {
-                float vh = 0.f, vl = 0.f;
-                if (rowok && j < p.d && !skip) {
-                    const float y = src[j], m = p.mu[j];
-                    vh = y - m;
-                    const float bb = vh - y;
-                    vl = (y - (vh - bb)) + (-m - bb);  // v = vh + vl exactly
-                }
-                const float V = ldexpf(vh, sh), VL = ldexpf(vl, sh);
-                const _Float16 h1 = (_Float16)V;
-                const float r1 = V - (float)h1;  // exact
-                const _Float16 h2 = (_Float16)(r1 + VL);
-                const float res = (r1 - (float)h2) + VL;
-                hi[j] = h1;
-                lo[j] = h2;
-                const float wv = (float)h1 + (float)h2;
-                sn = fmaf(wv, wv, sn);
-                e2 = fmaf(res, res, e2);
-            }
-#pragma unroll
-            for (int o = TPR / 2; o > 0; o >>= 1) {
-                sn += __shfl_xor(sn, o);
-                e2 += __shfl_xor(e2, o);
-            }
-            if (t == 0) {
-                // scaled units: |v - v~| <= sqrt(e2) up to the rounding of e2 (the margins) and 2^-46 |V| (res)
-                const float es = sqrtf(e2 * (1.f + 0x1p-9f)) * (1.f + 0x1p-20f) + 0x1p-44f * sqrtf(sn);
-                xe[cc] = ldexpf(es, -sh);
-                xsh[cc] = sh;
-                // |v~|^2: NaN for a non-finite entry (never enters), +inf when x - mu overflowed (keyed -FLT_MAX)
-                xn[cc] = mark != 0.f ? mark : (ovf ? INFINITY : ldexpf(sn, -2 * sh));
-            }
-        } else if (BYTE) {
-            // byte shadow rows: V = 2^sh fl(x - mu) with max |V| in [2^13, 2^14), split into int8 limbs hi = rint(V / 256)
-            // and lo = rint(V - 256 hi + 2^sh v_lo) (v_lo the TwoSum remainder of x - mu), so that 256 hi + lo misses
-            // 2^sh v by res per entry; e_q bounds |v - v~| from the residuals.  |v|^2 is taken of fl(x - mu).
-            const bool rowok = cc < nqt && !ABL(1);
-            const float* src = p.q + (size_t)(q0 + (rowok ? cc : 0)) * p.d;
-            float amax = 0.f, mark = 0.f;
-            if (rowok)
-                for (int j = t; j < p.d; j += TPR) {
-                    const float y = src[j];
-                    amax = fmaxf(amax, fabsf(y - p.mu[j]));
-                    mark += y - y;  // NaN for a non-finite entry (ise_common.hpp, nonfinite_mark)
-                }
-#pragma unroll
-            for (int o = TPR / 2; o > 0; o >>= 1) {
-                amax = fmaxf(amax, __shfl_xor(amax, o));
-                mark += __shfl_xor(mark, o);
-            }
-            const bool ovf = !(amax <= FLT_MAX);  // x - mu overflowed: no bound (keyed -FLT_MAX below)
-            const bool skip = ovf || mark != 0.f;
-            const int sh = (amax > 0.f && !ovf) ? 13 - ilogbf(amax) : 0;
-            int8_t* hi = reinterpret_cast<int8_t*>(qs + cc * S);
-            int8_t* lo = reinterpret_cast<int8_t*>(qs + cc * S + 4 * p.row_slots);
-            float e2 = 0.f;
-            const int dpb = p.row_slots * 16;
-            for (int j = t; j < dpb; j += TPR) {
-                float vh = 0.f, vl = 0.f;
-                if (rowok && j < p.d && !skip) {
-                    const float y = src[j], m = p.mu[j];
-                    vh = y - m;
-                    const float bb = vh - y;
-                    vl = (y - (vh - bb)) + (-m - bb);  // v = vh + vl exactly
-                }
-                const float V = ldexpf(vh, sh), VL = ldexpf(vl, sh);
-                float h1 = rintf(V * (1.f / 256.f));  // |h1| <= 64
-                const float r1 = fmaf(-256.f, h1, V);  // exact
-                float l1 = rintf(r1 + VL);              // |l1| <= 128
-                const float res = (r1 - l1) + VL;       // r1 - l1 exact
-                if (l1 > 127.f) { h1 += 1.f; l1 -= 256.f; }  // the same 256 hi + lo, lo in int8
-                hi[j] = (int8_t)h1;
-                lo[j] = (int8_t)l1;
-                sn = fmaf(V, V, sn);
-                e2 = fmaf(res, res, e2);
-            }
-#pragma unroll
-            for (int o = TPR / 2; o > 0; o >>= 1) {
-                sn += __shfl_xor(sn, o);
-                e2 += __shfl_xor(e2, o);
-            }
-            if (t == 0) {
-                // scaled units: |V - V~| <= sqrt(e2) up to the rounding of e2 (the margins) and 2^-44 |V| (res)
-                const float es = sqrtf(e2 * (1.f + 0x1p-9f)) * (1.f + 0x1p-20f) + 0x1p-44f * sqrtf(sn);
-                xe[cc] = ldexpf(es, -sh);
-                xsh[cc] = sh;
-                // |v|^2: NaN for a non-finite entry (never enters), +inf when x - mu overflowed (keyed -FLT_MAX)
-                xn[cc] = mark != 0.f ? mark : (ovf ? INFINITY : ldexpf(sn, -2 * sh));
             }
         } else {  // odd d, unaligned queries or very long rows: scalar path, one 4-byte unit at a time
             // (the loads of SB units are requested together, then consumed in the same ascending order as a

@@ -31,9 +31,7 @@ static void launch_scan_v(int ch, int waves, int T, dim3 grid, size_t lds, hipSt
     if constexpr (RM == ROWS_I8) {  // byte shadow rows: one query tile only (the plan routes nothing else to them)
         if (waves == 4) launch_scan_ch<4, 1, BF16, SHIFT, RM>(ch, grid, lds, st, sp);
         else launch_scan_ch<8, 1, BF16, SHIFT, RM>(ch, grid, lds, st, sp);
-        return;
-    }
-    if (T == 1 && waves == 4) launch_scan_ch<4, 1, BF16, SHIFT, RM>(ch, grid, lds, st, sp);
+    } else if (T == 1 && waves == 4) launch_scan_ch<4, 1, BF16, SHIFT, RM>(ch, grid, lds, st, sp);
     else if (T == 1) launch_scan_ch<8, 1, BF16, SHIFT, RM>(ch, grid, lds, st, sp);
     else if (T == 2 && waves == 16) launch_scan_ch<16, 2, BF16, SHIFT, RM>(ch, grid, lds, st, sp);
     else if (T == 2) launch_scan_ch<8, 2, BF16, SHIFT, RM>(ch, grid, lds, st, sp);

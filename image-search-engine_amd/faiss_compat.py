@@ -141,6 +141,22 @@ class IndexFlat:
         _n.check(_n.lib.ise_index_shadow_row(self._h, int(i), out))
         return float(out[0]), float(out[1]), int(out[2])
 
+    def stage_query_debug(self, q: "torch.Tensor", route: str) -> dict:
+        """One float32 device query through the staging of the "half" or "byte" shadow filter, on its own (tests only;
+        include/ise_knn.h, ise_index_stage_query_debug): hi / lo limbs of the padded row (int8, or fp16), sh, |v|^2,
+        e_q and whether the vector path ran.  The tensor's own pointer is used, so a slice keeps its alignment."""
+        import torch
+        assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 1 and q.is_contiguous() and q.numel() == self.d
+        es = {"half": 2, "byte": 1}[route]
+        buf = np.zeros(2 * 1024 * es, dtype=np.uint8)
+        out, info = (ctypes.c_float * 2)(), (ctypes.c_int32 * 3)()
+        torch.cuda.synchronize()
+        _n.check(_n.lib.ise_index_stage_query_debug(self._h, q.data_ptr(), es == 1, buf.ctypes.data, buf.nbytes, out, info))
+        P = int(info[2])
+        limbs = buf[: 2 * P * es].view(np.int8 if es == 1 else np.float16).reshape(2, P)
+        return {"hi": limbs[0].copy(), "lo": limbs[1].copy(), "sh": int(info[0]), "vec": bool(info[1]),
+                "vn2": float(out[0]), "eq": float(out[1])}
+
     def range_stats(self) -> dict:
         """Range-search batches and those that needed the overflow pass (include/ise_knn.h, ise_index_range_stats)."""
         out = (ctypes.c_uint64 * 2)()

@@ -118,6 +118,14 @@ int ise_index_byte_stats(ise_index_t* h, uint64_t* out2);
 int ise_index_shadow_row(ise_index_t* h, int64_t i, float* out3);
 int ise_index_byte_row(ise_index_t* h, int64_t i, float* out2);
 
+/* Tests only (nothing on the search path calls it): one float32 query (device pointer, d floats) through the query
+ * staging of a shadow filter (csrc/ise_stage.hpp, the device functions the scan kernel runs) in a one-block kernel.
+ * route: 0 = fp16 shadow, 1 = byte shadow; ISE_E_INVALID when the index has no such shadow.  limbs (host,
+ * limbs_bytes >= 2 * P * element size): the hi limbs of the padded row (P elements: int8, or fp16 bits), then the
+ * lo limbs.  out2 = (|v|^2, e_q) as the kernel keeps them, info3 = (sh, 1 if the vector path ran, P). */
+int ise_index_stage_query_debug(ise_index_t* h, const void* q_dev, int route, void* limbs, int64_t limbs_bytes,
+                                float* out2, int32_t* info3);
+
 /* Test / rehearsal knobs ($ISE_FORCE_EXACT, $ISE_NO_DIRECT, $ISE_NO_SHORT, $ISE_SHORT_TPB_MAX,
  * $ISE_DIRECT_SHORT_MAX_TILES, $ISE_RANGE_STAGE_CAP, $ISE_NO_HALF_FILTER, $ISE_NO_BYTE_FILTER, $ISE_FAIL_BYTE_ALLOC) are read from the environment when the library is first used and again when
  * this is called -- never inside a search. */

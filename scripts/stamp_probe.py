@@ -1,17 +1,22 @@
-"""In-kernel phase stamps of the scan kernel (dev aid; ablate build + ISE_STAMPS)."""
+"""In-kernel phase stamps of the scan kernel (dev aid; ablate build + ISE_STAMPS).
+usage: ISE_KNN_LIB=.../libise_knn_ablate.so python scripts/stamp_probe.py [n:nq ...]"""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import image_search_engine_amd.faiss_compat as faiss
 d, k = 512, 10
-for n, nq in ((125_000, 16), (1_000_000, 16), (1_000_000, 32), (1_000_000, 48)):
+shapes = [tuple(int(v) for v in a.split(":")) for a in sys.argv[1:]] or [(125_000, 16), (1_000_000, 16), (1_000_000, 32), (1_000_000, 48)]
+for n, nq in shapes:
     xb = torch.rand((n, d), device="cuda"); xq = torch.rand((nq, d), device="cuda")
     index = faiss.IndexFlatL2(d); index.add_torch(xb)
     for _ in range(5): index.search_torch(xq, k)
     st = torch.zeros((1024 * 8 * 16,), dtype=torch.int64, device="cuda")
+    b0, h0 = index.byte_stats()["byte_batches"], index.half_stats()["half_batches"]
     os.environ["ISE_STAMPS"] = str(st.data_ptr())
     index.search_torch(xq, k); torch.cuda.synchronize()
     os.environ.pop("ISE_STAMPS")
+    b1, h1 = index.byte_stats()["byte_batches"], index.half_stats()["half_batches"]
+    route = "byte shadow" if b1 > b0 else ("fp16 shadow" if h1 > h0 else "own rows")  # half_batches counts both shadows
     s = st.cpu().numpy().reshape(1024, 8, 16).astype(np.float64)
     used = s[:, :, 0].max(axis=1) > 0
     s = s[used]                      # [blocks][waves][stamps]
@@ -19,7 +24,7 @@ for n, nq in ((125_000, 16), (1_000_000, 16), (1_000_000, 32), (1_000_000, 48)):
     us = (s - t0) / 100.0            # 100 MHz -> us
     names = ["entry", "staged", "boot in", "boot out", "loop end", "final barrier", "exit"]
     clk = (s[:, :, 9] - s[:, :, 8]) / np.maximum(s[:, :, 4] - s[:, :, 1], 1) * 100.0  # MHz
-    print(f"n={n} nq={nq}: blocks={s.shape[0]}  in-kernel clock over the main loop: median {np.median(clk):.0f} MHz (min {clk.min():.0f}, max {clk.max():.0f})")
+    print(f"n={n} nq={nq}: route of the stamped search: {route};  blocks={s.shape[0]}  in-kernel clock over the main loop: median {np.median(clk):.0f} MHz (min {clk.min():.0f}, max {clk.max():.0f})")
     for i, nm in enumerate(names):
         v = us[:, :, i]
         print(f"  {nm:14s} min {v.min():8.2f}  median {np.median(v):8.2f}  max {v.max():8.2f} us")
