@@ -5,6 +5,12 @@
 #include "ise_select.hpp"
 #include "ise_stage.hpp"
 
+// build-time switch of the filtered final phase of the exchange kernels (on in every shipped build; a dev build
+// with -DISE_FINAL_FILTER=0 is what an A/B of it runs against)
+#ifndef ISE_FINAL_FILTER
+#define ISE_FINAL_FILTER 1
+#endif
+
 #ifdef ISE_ABLATE
 #define ABL(bit) (p.ablate & (bit))
 #define STAMP(i)                                                                                   \
@@ -39,14 +45,20 @@
 //          into bootw (exact top-k of the union, sorted) and publishes the new k-th
 //          key, so tauS tracks the block's running k-th best.
 //   final  one wave selects the exact sorted top-k of bootw + what is left in the W
-//          private lists and writes the block's list to HBM.
+//          private lists and writes the block's list to HBM.  In the exchange kernels a wave that
+//          obtained the grid-wide bound of a query first drops every key above it: of the ~k keys a
+//          block holds (k of its first W*16 rows seeded the list) one or two lie below a bound as
+//          tight as the k-th best of a 65k-row sample, and only they are ranked and written, KEY_PAD
+//          behind them (the merge reads short lists).  No dropped key can be among the k smallest of
+//          the launch (see the final phase), so the merged keys are unchanged.
 //   exchange (8-wave kernels with T >= 2, once per block): at boot a block publishes, per query, the score of its best boot
 //          row (one 8-byte store: launch seq << 32 | ord(score)).  After its first row tile a
 //          wave reads the entries of all blocks for its queries: the k-th smallest of those scores
 //          is the k-th best of nblocks DISTINCT rows, hence an upper bound of the final k-th
 //          distance -- as tight as the k-th best of a W*16*nblocks-row sample (32k-64k rows)
-//          instead of the block's own W*16.  It only lowers tauS; entries not yet written (or of
-//          an older launch: seq mismatch) just count as absent.  No polling, no ordering needed.
+//          instead of the block's own W*16.  It lowers tauS, and the wave keeps it for the final
+//          phase of its queries (xbound); entries not yet written (or of an older launch: seq
+//          mismatch) just count as absent.  No polling, no ordering needed.
 //
 // SHIFT (fp32 L2 only): distances are translation invariant, and the expanded form
 // |x|^2 + |y|^2 - 2 x.y loses digits when the rows share a large common component
@@ -85,6 +97,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     // The byte shadow kernel takes it at T = 1 as well: its kc = 32 lists over ~2000-row blocks admit twice the
     // candidates of the k + 4 lists, and a grid-wide threshold after the first tile cuts that bookkeeping.
     constexpr bool XCHG = T >= 3 || (T == 2 && W == 8) || (RM == ROWS_I8 && T == 1 && W == 8);
+    constexpr bool FFILT = XCHG && ISE_FINAL_FILTER;    // final phase filtered by the exchange bound (below)
     constexpr int NQ = 16 * T;                        // queries per block pass
     // threads staging one query row (per tile).  16-wave blocks stage with their first 8 waves: |x|^2 then has the
     // summation order of the 8-wave kernels (and of short_scan_kernel), and the bf16 L2 distances, which carry it,
@@ -360,6 +373,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
         acc0[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         acc1[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
+    u64 xbound = KEY_PAD;  // FFILT: lane i keeps the exchange bound of the wave's i-th query (w + i W), KEY_PAD = none
     bool booted = false;
 
     // fold the wave's private list of query qq = 16 t + cq into the block list bootw[qq]
@@ -581,6 +595,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
             }
             if (prefix != 0xFFFFFFFFu) {  // at least k entries of this launch were there
                 const u64 bound = ((u64)prefix << 32) | 0xFFFFFFFFull;  // every id at that score stays admissible
+                if (FFILT && lane == (qq - w) / W) xbound = bound;  // for the final phase of this query, below
                 if (lane == 0) {
                     while (atomicCAS(&lockS[qq], 0, 1) != 0) __builtin_amdgcn_s_sleep(1);
                 }
@@ -674,7 +689,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                     int ns0 = s0 + CH, ntile = tile;
                     if (ns0 >= nsteps) { ns0 = 0; ntile = tile + W; }
                     compute_chunk(A[j], s0, ns0);
-                    if (ns0 == 0 && !ABL(8)) epilogue(tile, yn, ye, ys);
+                    if (ns0 == 0 && !ABL(8) && !(ABL(2048) && booted)) epilogue(tile, yn, ye, ys);  // 2048: boot only
                     if (ns0 == 0) tiles_done++;
                     done = ntile >= t1;
                     tile = ntile; s0 = ns0;
@@ -714,6 +729,16 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
 #pragma unroll
         for (int i = 0; i < W; i++) P[i + 2] = P[i + 1] + cntS[i * NQ + qq];
         const int n = P[W + 1];
+        // FFILT: where this wave obtained the exchange bound of the query, every key above it is dropped BEFORE the
+        // selection.  The bound is the k-th smallest score of k DISTINCT rows of this launch (one per block), so the
+        // final k-th key over all blocks is <= xbound = (that score << 32) | 0xFFFFFFFF and no dropped key can be among the k
+        // smallest: the merged list is unchanged, and of the block's ~k keys the one or two survivors are all that is
+        // ranked.  No bound (too few published entries, a block too short to read the exchange, ISE_NO_XCHG, or the
+        // floor keys of a multi-pass k): xbound is KEY_PAD and nothing is dropped.
+        u64 bnd = KEY_PAD;
+        if constexpr (FFILT) {
+            if (!use_floor && !ABL(8192)) bnd = readlane_u64(xbound, (qq - w) / W);
+        }
         u64 kk[KPLF];
 #pragma unroll
         for (int e = 0; e < KPLF; e++) {
@@ -725,6 +750,7 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                 for (int i = 0; i < W; i++)
                     if (idx >= P[i + 1] && idx < P[i + 2])
                         kk[e] = cand[(size_t)(i * NQ + qq) * CAP + idx - P[i + 1]];
+                if (FFILT && kk[e] > bnd) kk[e] = KEY_PAD;
             }
         }
         u64* out = p.part + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NQ + qq) * k;
