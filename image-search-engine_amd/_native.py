@@ -68,6 +68,10 @@ PROTOTYPES = [
     ("ise_range_result_get", _int, [_vp, _i64p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     ("ise_range_result_destroy", _int, [_vp]),
     ("ise_index_range_stats", _int, [_vp, _u64p]),
+    ("ise_index_remove_ids_host", _int, [_vp, _vp, _i64, _i64p]),
+    ("ise_index_remove_range", _int, [_vp, _i64, _i64, _i64p]),
+    ("ise_index_remove_stats", _int, [_vp, _u64p]),
+    ("ise_index_remove_last_timing", _int, [_vp, _f32p, _u64p]),
     ("ise_refresh_env_knobs", _int, []),
     ("ise_comm_precheck", _int, [_int]),
     ("ise_comm_unique_id", _int, [_vp]),

@@ -24,6 +24,7 @@
 //   merge_kernel   ise_merge.hpp   k-way merge of sorted per-block / per-rank lists
 //   row helpers    ise_rows.hpp    norms, padding / bf16 conversion, normalize_L2, shift
 //   range search   ise_range.hpp   every row within a radius: one pass per 16 queries + offset / compaction kernels
+//   remove_ids     ise_remove.hpp  stable in-place compaction of the rows and of everything kept per row
 //
 // Candidate order: a 64-bit key = ord(score) << 32 | row id, where ord() is the
 // order-preserving map float -> uint32 and score = squared L2 (or -inner product).
@@ -45,6 +46,7 @@
 #include "ise_short_scan.hpp"
 #include "ise_range.hpp"
 #include "ise_stage.hpp"
+#include "ise_remove.hpp"
 
 // ---------------------------------------------------------------- host side
 static thread_local std::string g_err;
@@ -194,6 +196,11 @@ struct ise_index {
     RangeWs rg;
     std::mutex rg_mu;
     unsigned long long range_batches = 0, range_overflows = 0;  // under rg_mu
+    // remove_ids (ise_remove.hpp): calls that removed something, rows removed, rows moved (under mu_); and the last
+    // such call's slab launches as HIP events timed them, with the bytes they moved (each counted once)
+    unsigned long long remove_calls = 0, remove_rows = 0, remove_moved = 0;
+    float remove_last_ms = 0.f;
+    unsigned long long remove_last_bytes = 0;
 };
 
 // rows are padded to whole k-steps of 64 bytes (16 floats / 32 bf16); rows longer than
@@ -845,6 +852,7 @@ struct EnvKnobs {
     std::atomic<int> no_half{0};        // ISE_NO_HALF_FILTER=1: long float32 L2 indexes keep the float32 filter (A/B, tests)
     std::atomic<int> no_byte{0};        // ISE_NO_BYTE_FILTER=1: ... filter through the fp16 shadow, never the byte one
     std::atomic<int> fail_byte_alloc{0};  // ISE_FAIL_BYTE_ALLOC=1: the byte shadow's allocation fails as out of memory (tests)
+    std::atomic<int> remove_slab_rows{0};  // ISE_REMOVE_SLAB_ROWS: destination rows per slab of a removal (tests: cross many slabs)
     void refresh() {
         auto flag = [](const char* name) { const char* e = getenv(name); return (e && e[0] == '1') ? 1 : 0; };
         auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
@@ -857,6 +865,7 @@ struct EnvKnobs {
         no_half.store(flag("ISE_NO_HALF_FILTER"));
         no_byte.store(flag("ISE_NO_BYTE_FILTER"));
         fail_byte_alloc.store(flag("ISE_FAIL_BYTE_ALLOC"));
+        remove_slab_rows.store(num("ISE_REMOVE_SLAB_ROWS"));
     }
 };
 static EnvKnobs& knobs() {
@@ -2254,6 +2263,212 @@ extern "C" int ise_range_result_get(const ise_range_result_t* r, int64_t* nq, co
 
 extern "C" int ise_range_result_destroy(ise_range_result_t* r) {
     delete r;
+    return ISE_OK;
+}
+
+// ---- remove_ids: stable in-place compaction (ise_remove.hpp)
+struct RemoveRun {
+    long long start, len;
+};
+
+// everything a removal allocates for the duration of the call
+struct RemoveScratch {
+    uint32_t* g = nullptr;        // [T] destination row at which run t bites
+    uint32_t* cend = nullptr;     // [T] rows removed up to and including run t
+    uint32_t* src_idx = nullptr;  // [slab] source rows of the current slab
+    char* bounce = nullptr;       // one slab of the widest array
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ~RemoveScratch() {
+        for (void* p : {(void*)g, (void*)cend, (void*)src_idx, (void*)bounce})
+            if (p) (void)hipFree(p);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+
+// one wide array's slab: rows src_idx[0 .. m) -> bounce -> rows [a, a + m)
+static void remove_move_rows(const ise_index* h, void* base, size_t stride, long long a, long long m, const RemoveScratch& sc,
+                             hipStream_t st) {
+    const uint32_t upr = (uint32_t)(stride / 16);
+    const uint32_t total = (uint32_t)(m * upr);
+    const uint32_t pieces = (total + 64 * REMOVE_UNROLL - 1) / (64 * REMOVE_UNROLL);
+    const unsigned grid = std::max(1u, std::min((pieces + 3) / 4, (unsigned)h->num_cu * 4u));  // 16 waves per CU
+    hipLaunchKernelGGL(remove_rows_kernel<true>, dim3(grid), dim3(256), 0, st, (const u32x4*)base,
+                       (const uint32_t*)sc.src_idx, (u32x4*)sc.bounce, total, upr);
+    hipLaunchKernelGGL(remove_rows_kernel<false>, dim3(grid), dim3(256), 0, st, (const u32x4*)sc.bounce,
+                       (const uint32_t*)nullptr, (u32x4*)(static_cast<char*>(base) + (size_t)a * stride), total, upr);
+}
+
+// runs: sorted, disjoint, non-adjacent, non-empty, inside [0, h->n).  rg_mu and mu_ held.
+static int remove_runs_locked(ise_index* h, const std::vector<RemoveRun>& runs, long long removed) {
+    const long long n_old = h->n, n_new = n_old - removed, first = runs[0].start;
+    const long long moved = n_new - first;  // destination rows [first, n_new) get a new row
+    hipStream_t st = h->stream;
+    HIP_TRY(hipDeviceSynchronize());  // nothing in flight reads the rows while they move
+    if (n_new <= SHADOW_MIN_ROWS) free_shadow(h);  // a fresh index of that size has none
+    // norms, shadows and their metadata are functions of the row and mu: they move with the rows when every row has
+    // them (always, unless a float32 L2 index still waits for its shift); otherwise only xb moves and the next
+    // search retakes them
+    const bool meta = h->norms_rows == n_old;
+    const size_t rb = row_bytes(h), hb = shadow_row_bytes(h), qb = byte_row_bytes(h);
+    const bool mv_h = meta && h->xh, mv_q = meta && h->xq8;
+    RemoveScratch sc;
+    if (moved > 0) {
+        const long long T = (long long)runs.size();
+        std::vector<uint32_t> g((size_t)T), cend((size_t)T);
+        long long c = 0;
+        for (long long t = 0; t < T; t++) {
+            g[(size_t)t] = (uint32_t)(runs[(size_t)t].start - c);
+            c += runs[(size_t)t].len;
+            cend[(size_t)t] = (uint32_t)c;
+        }
+        // slab: at most 256 MiB of the widest array (xb), as the upload slab of ise_index_add_host; a slab's 16-byte
+        // units stay below 2^31 whatever $ISE_REMOVE_SLAB_ROWS says
+        long long slab = knobs().remove_slab_rows.load(std::memory_order_relaxed);
+        if (slab <= 0) slab = std::max<long long>(1, (256ll << 20) / (long long)rb);
+        slab = std::min(slab, std::max<long long>(1, (1ll << 31) / (long long)(rb / 16)));
+        slab = std::min(slab, moved);
+        HIP_TRY(hipMalloc(&sc.g, (size_t)T * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&sc.cend, (size_t)T * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&sc.src_idx, (size_t)slab * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&sc.bounce, (size_t)slab * rb));
+        HIP_TRY(hipEventCreate(&sc.ev0));
+        HIP_TRY(hipEventCreate(&sc.ev1));
+        HIP_TRY(hipMemcpyAsync(sc.g, g.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(sc.cend, cend.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));  // g and cend are pageable host vectors
+        HIP_TRY(hipEventRecord(sc.ev0, st));
+        for (long long a = first; a < n_new; a += slab) {
+            const long long m = std::min(slab, n_new - a);
+            const unsigned gw = (unsigned)std::min<long long>((m + 255) / 256, (long long)h->num_cu * 8);
+            hipLaunchKernelGGL(remove_src_kernel, dim3(gw), dim3(256), 0, st, (const uint32_t*)sc.g,
+                               (const uint32_t*)sc.cend, (int)T, (uint32_t)a, (uint32_t)m, sc.src_idx);
+            remove_move_rows(h, h->xb, rb, a, m, sc, st);
+            if (mv_h) remove_move_rows(h, h->xh, hb, a, m, sc, st);
+            if (mv_q) remove_move_rows(h, h->xq8, qb, a, m, sc, st);
+            if (meta) {  // the 4-byte arrays: plane p of the bounce buffer is [p * m, (p + 1) * m)
+                RemovePlanes gp{}, cp{};
+                int np = 0;
+                auto plane = [&](void* arr) {
+                    uint32_t* w = static_cast<uint32_t*>(arr);
+                    uint32_t* b = reinterpret_cast<uint32_t*>(sc.bounce) + (size_t)np * m;
+                    gp.src[np] = w;
+                    gp.dst[np] = b;
+                    cp.src[np] = b;
+                    cp.dst[np] = w + a;
+                    np++;
+                };
+                plane(h->norms);
+                if (mv_h)
+                    for (int i = 0; i < 3; i++) plane(h->hmeta + (size_t)i * h->cap);
+                if (mv_q) plane(h->bmeta);
+                hipLaunchKernelGGL(remove_words_kernel<true>, dim3(gw, np), dim3(256), 0, st, gp,
+                                   (const uint32_t*)sc.src_idx, (uint32_t)m);
+                hipLaunchKernelGGL(remove_words_kernel<false>, dim3(gw, np), dim3(256), 0, st, cp,
+                                   (const uint32_t*)nullptr, (uint32_t)m);
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(sc.ev1, st));
+    }
+    // the tail [n_new, n_old) of every array reads zeros again (reserve_rows' invariant: pad rows zero, their norms
+    // and metadata zero; partial last tiles rely on it)
+    HIP_TRY(hipMemsetAsync(static_cast<char*>(h->xb) + (size_t)n_new * rb, 0, (size_t)removed * rb, st));
+    HIP_TRY(hipMemsetAsync(h->norms + n_new, 0, (size_t)removed * sizeof(float), st));
+    if (h->xh) {
+        HIP_TRY(hipMemsetAsync(static_cast<char*>(h->xh) + (size_t)n_new * hb, 0, (size_t)removed * hb, st));
+        for (int i = 0; i < 3; i++)
+            HIP_TRY(hipMemsetAsync(h->hmeta + (size_t)i * h->cap + n_new, 0, (size_t)removed * sizeof(float), st));
+    }
+    if (h->xq8) {
+        HIP_TRY(hipMemsetAsync(static_cast<char*>(h->xq8) + (size_t)n_new * qb, 0, (size_t)removed * qb, st));
+        HIP_TRY(hipMemsetAsync(h->bmeta + n_new, 0, (size_t)removed * sizeof(uint32_t), st));
+    }
+    h->n = n_new;
+    h->norms_rows = meta ? n_new : 0;  // 0: retaken with the shadows at the next search (prepare_shift_locked)
+    // mu stays: results never depend on it.  An unpinned index that has shrunk below three quarters of the rows mu
+    // was taken from refreshes it at the next search (the mirror of "grown by a quarter"); a pinned one stays pinned
+    const long long mu_rows_old = h->mu_rows;
+    h->mu_rows = std::min(h->mu_rows, n_new);
+    if (uses_shift(h) && !h->shift_pinned && n_new * 4 < mu_rows_old * 3) h->mu_rows = 0;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    h->remove_last_ms = 0.f;
+    h->remove_last_bytes = 0;
+    if (moved > 0) {
+        (void)hipEventElapsedTime(&h->remove_last_ms, sc.ev0, sc.ev1);
+        const size_t per_row = rb + (mv_h ? hb + 12 : 0) + (mv_q ? qb + 4 : 0) + (meta ? 4 : 0);
+        h->remove_last_bytes = (unsigned long long)moved * per_row;
+    }
+    h->remove_calls++;
+    h->remove_rows += (unsigned long long)removed;
+    h->remove_moved += (unsigned long long)moved;
+    return ISE_OK;
+}
+
+extern "C" int ise_index_remove_range(ise_index_t* h, int64_t i0, int64_t i1, int64_t* n_removed) {
+    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
+    if (n_removed) *n_removed = 0;
+    std::lock_guard<std::mutex> lr(h->rg_mu);
+    std::lock_guard<std::mutex> lk(h->mu_);
+    const long long a = std::max<long long>(i0, 0), b = std::min<long long>(i1, h->n);
+    if (a >= b) return ISE_OK;  // nothing to remove: no synchronisation, no counters
+    DeviceGuard gd(h->device);
+    const int rc = remove_runs_locked(h, {RemoveRun{a, b - a}}, b - a);
+    if (rc == ISE_OK && n_removed) *n_removed = b - a;
+    return rc;
+}
+
+extern "C" int ise_index_remove_ids_host(ise_index_t* h, const int64_t* ids, int64_t n_ids, int64_t* n_removed) {
+    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
+    if (n_removed) *n_removed = 0;
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(ISE_E_INVALID, "ids is NULL");
+    if (n_ids == 0) return ISE_OK;
+    std::vector<long long> v;
+    std::vector<RemoveRun> runs;
+    try {
+        v.reserve((size_t)n_ids);
+        for (int64_t i = 0; i < n_ids; i++)
+            if (ids[i] >= 0) v.push_back(ids[i]);
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+    } catch (const std::bad_alloc&) {
+        return fail(ISE_E_NOMEM, "remove_ids: host allocation failed");
+    }
+    std::lock_guard<std::mutex> lr(h->rg_mu);
+    std::lock_guard<std::mutex> lk(h->mu_);
+    long long removed = 0;
+    try {
+        for (long long id : v) {
+            if (id >= h->n) break;  // sorted: the rest does not exist either
+            if (!runs.empty() && runs.back().start + runs.back().len == id) runs.back().len++;
+            else runs.push_back(RemoveRun{id, 1});
+            removed++;
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(ISE_E_NOMEM, "remove_ids: host allocation failed");
+    }
+    if (removed == 0) return ISE_OK;  // nothing to remove: no synchronisation, no counters
+    DeviceGuard gd(h->device);
+    const int rc = remove_runs_locked(h, runs, removed);
+    if (rc == ISE_OK && n_removed) *n_removed = removed;
+    return rc;
+}
+
+extern "C" int ise_index_remove_stats(ise_index_t* h, uint64_t* out3) {
+    if (!h || !out3) return fail(ISE_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    out3[0] = h->remove_calls;
+    out3[1] = h->remove_rows;
+    out3[2] = h->remove_moved;
+    return ISE_OK;
+}
+
+extern "C" int ise_index_remove_last_timing(ise_index_t* h, float* ms, uint64_t* bytes) {
+    if (!h || !ms || !bytes) return fail(ISE_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    *ms = h->remove_last_ms;
+    *bytes = h->remove_last_bytes;
     return ISE_OK;
 }
 

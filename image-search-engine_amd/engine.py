@@ -19,6 +19,7 @@ config = Config()
 index = None
 images_paths = None
 descriptor = None
+index_file = None   # the file ``load`` read ``index`` from (None: bound some other way); remove_images rewrites it
 
 
 def paths_file_for(index_path):
@@ -72,9 +73,10 @@ def load(index_path=None, paths=None, desc=None):
     shifts every later id.  ``indexer.main`` here persists the paths of
     the rows it actually indexed beside the index; that list is used when present, the reference's
     glob otherwise."""
-    global index, images_paths, descriptor
+    global index, images_paths, descriptor, index_file
     index_path = index_path or config.DNN_INDEX_PATH
     index = faiss.read_index(str(index_path))
+    index_file = index_path
     listed = read_paths_file(index_path, index.ntotal) if paths is None else None
     if paths is not None:
         images_paths = paths
@@ -90,6 +92,28 @@ def load(index_path=None, paths=None, desc=None):
         if hasattr(desc, "warm_up") and getattr(desc, "device", None) is not None and desc.device.type == "cuda":
             desc.warm_up()   # the batch shapes combined request threads will produce (descriptors.CNNDescriptor.describe)
     return index
+
+
+def remove_images(paths) -> int:
+    """Delete images from the served index (new capability; the reference rebuilds its index file with
+    backend/indexer.py): the rows of the given paths leave ``index`` (``index.remove_ids``: in place on the device,
+    the other rows keep their order), ``images_paths`` stays in step, and when the index came from a file
+    (``load``) that file and its paths file are rewritten with the new row count and checksum.  Unknown paths are
+    ignored; returns how many rows went."""
+    global images_paths
+    want = {str(p) for p in paths}
+    rows = [i for i, p in enumerate(images_paths) if str(p) in want]
+    if not rows:
+        return 0
+    n = int(index.remove_ids(np.asarray(rows, dtype=np.int64)))
+    gone = set(rows)
+    images_paths = [p for i, p in enumerate(images_paths) if i not in gone]
+    if index_file is not None:
+        faiss.write_index(index, str(index_file))
+        with open(paths_file_for(index_file), "w") as f:
+            json.dump({"ntotal": int(index.ntotal), "index_crc32": file_crc32(index_file),
+                       "paths": [str(p) for p in images_paths]}, f)
+    return n
 
 
 def run_image_query(image_features, n_images, normalize=False):

@@ -11,8 +11,12 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
     index.search(x, k) -> (D, I)         backend/engine.py:55, backend/kmeans_faiss.py:49
     index.range_search(x, radius)        Faiss's (lims, D, I); not called by the reference (its DHASH
                                          method's "every match" request, backend/engine.py:82-91)
+    index.remove_ids(sel or ids) -> int  Faiss IndexFlatCodes::remove_ids with IDSelectorRange / Batch / Array /
+                                         Not: the other rows keep their order and are renumbered (in-place
+                                         compaction on the device, csrc/ise_remove.hpp); never called by the reference
+    IndexIDMap(index).add_with_ids       Faiss's id-mapping wrapper, so that ids handed out earlier survive a removal
     normalize_L2(x)                      backend/utils.py:303, backend/engine.py:53
-    write_index / read_index             backend/indexer.py:59, backend/engine.py:116
+    write_index / read_index             backend/indexer.py:59, backend/engine.py:116 (IndexFlat and IndexIDMap)
     Kmeans(...).index / .centroids       backend/kmeans_faiss.py:29-44 (assignment only)
 
 All arithmetic runs on the MI355X through ``include/ise_knn.h``; there is no
@@ -49,6 +53,101 @@ def _default_device() -> int:
     import torch
 
     return torch.cuda.current_device() if torch.cuda.is_available() else 0
+
+
+# ---------------------------------------------------------------- id selectors (faiss.IDSelector*)
+def _ids_array(ids) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+
+
+def _runs_of_sorted(ids: np.ndarray) -> np.ndarray:
+    """Sorted unique ids -> (T, 2) int64 runs (start, len), maximal (no two runs adjacent)."""
+    if ids.size == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    brk = np.flatnonzero(np.diff(ids) != 1) + 1
+    starts = np.concatenate(([0], brk))
+    ends = np.concatenate((brk, [ids.size]))
+    return np.stack([ids[starts], ends - starts], axis=1).astype(np.int64)
+
+
+class IDSelector:
+    """What ``remove_ids`` takes: ``is_member(i)``; ``runs(n)`` -- the selected ids inside [0, n) as sorted, disjoint,
+    non-adjacent (start, len) runs, (T, 2) int64; ``members(ids)`` -- ``is_member`` over an int64 array."""
+
+    def is_member(self, i: int) -> bool:
+        raise NotImplementedError
+
+    def runs(self, n: int) -> np.ndarray:
+        raise NotImplementedError
+
+    def members(self, ids) -> np.ndarray:
+        return np.fromiter((self.is_member(int(i)) for i in _ids_array(ids)), dtype=bool, count=len(_ids_array(ids)))
+
+
+class IDSelectorRange(IDSelector):
+    """ids in [imin, imax); never materialised."""
+
+    def __init__(self, imin: int, imax: int):
+        self.imin, self.imax = int(imin), int(imax)
+
+    def is_member(self, i: int) -> bool:
+        return self.imin <= int(i) < self.imax
+
+    def runs(self, n: int) -> np.ndarray:
+        a, b = max(self.imin, 0), min(self.imax, int(n))
+        return np.array([[a, b - a]], dtype=np.int64) if a < b else np.zeros((0, 2), dtype=np.int64)
+
+    def members(self, ids) -> np.ndarray:
+        ids = _ids_array(ids)
+        return (ids >= self.imin) & (ids < self.imax)
+
+
+class IDSelectorBatch(IDSelector):
+    """The given ids, in any order, duplicates allowed; ids that name no row select nothing."""
+
+    def __init__(self, ids):
+        self.ids = np.unique(_ids_array(ids))  # sorted
+
+    def is_member(self, i: int) -> bool:
+        p = int(np.searchsorted(self.ids, int(i)))
+        return p < self.ids.size and int(self.ids[p]) == int(i)
+
+    def runs(self, n: int) -> np.ndarray:
+        return _runs_of_sorted(self.ids[(self.ids >= 0) & (self.ids < int(n))])
+
+    def members(self, ids) -> np.ndarray:
+        return np.isin(_ids_array(ids), self.ids)
+
+
+class IDSelectorArray(IDSelectorBatch):
+    """Faiss's linear-scan form of IDSelectorBatch: the same members."""
+
+
+class IDSelectorNot(IDSelector):
+    """Every id ``sel`` does not select."""
+
+    def __init__(self, sel: IDSelector):
+        self.sel = sel
+
+    def is_member(self, i: int) -> bool:
+        return not self.sel.is_member(i)
+
+    def runs(self, n: int) -> np.ndarray:
+        n = int(n)
+        r = self.sel.runs(n)
+        starts = np.concatenate(([0], r[:, 0] + r[:, 1]))
+        ends = np.concatenate((r[:, 0], [n]))
+        keep = ends > starts
+        return np.stack([starts[keep], (ends - starts)[keep]], axis=1).astype(np.int64)
+
+    def members(self, ids) -> np.ndarray:
+        return ~self.sel.members(ids)
+
+
+def _runs_to_ids(runs: np.ndarray) -> np.ndarray:
+    if len(runs) == 0:
+        return np.zeros(0, dtype=np.int64)
+    return np.concatenate([np.arange(a, a + m, dtype=np.int64) for a, m in runs])
 
 
 class IndexFlat:
@@ -197,6 +296,38 @@ class IndexFlat:
         st = torch.cuda.current_stream(x.device).cuda_stream
         _n.check(_n.lib.ise_index_add_device(self._h, x.data_ptr(), x.shape[0], st))
         torch.cuda.current_stream(x.device).synchronize()  # x may be freed by the caller
+
+    def remove_ids(self, sel) -> int:
+        """faiss ``index.remove_ids``: remove the rows an ``IDSelector`` names -- or an int64 array-like, taken as an
+        ``IDSelectorBatch`` as the Faiss wrapper does -- and return how many went.  The other rows keep their order
+        and are renumbered densely (``IndexIDMap`` keeps external ids).  In place on the device: the rows, their
+        norms and shadows move, nothing is re-uploaded (include/ise_knn.h, ise_index_remove_ids_host)."""
+        out = ctypes.c_int64(0)
+        if isinstance(sel, IDSelectorRange):
+            _n.check(_n.lib.ise_index_remove_range(self._h, sel.imin, sel.imax, ctypes.byref(out)))
+            return int(out.value)
+        if isinstance(sel, IDSelectorBatch):
+            ids = sel.ids
+        elif isinstance(sel, IDSelector):  # Not, or a user's selector: complemented / evaluated against ntotal here
+            ids = _runs_to_ids(sel.runs(self.ntotal))
+        else:
+            ids = _ids_array(sel)
+        if ids.size:
+            _n.check(_n.lib.ise_index_remove_ids_host(self._h, ids.ctypes.data, ids.size, ctypes.byref(out)))
+        return int(out.value)
+
+    def remove_stats(self) -> dict:
+        """Removals since the index was created (include/ise_knn.h, ise_index_remove_stats): calls that removed
+        something, rows removed, rows that moved to a new position."""
+        out = (ctypes.c_uint64 * 3)()
+        _n.check(_n.lib.ise_index_remove_stats(self._h, out))
+        return {"remove_calls": int(out[0]), "rows_removed": int(out[1]), "rows_moved": int(out[2])}
+
+    def remove_last_timing(self) -> tuple:
+        """(milliseconds, bytes) of the last removal's slab launches (include/ise_knn.h, ise_index_remove_last_timing)."""
+        ms, nb = ctypes.c_float(0), ctypes.c_uint64(0)
+        _n.check(_n.lib.ise_index_remove_last_timing(self._h, ctypes.byref(ms), ctypes.byref(nb)))
+        return float(ms.value), int(nb.value)
 
     def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
         n = self.ntotal - i0 if n is None else n
@@ -347,6 +478,62 @@ class IndexFlatIP(IndexFlat):
         super().__init__(d, METRIC_INNER_PRODUCT, device, storage)
 
 
+class IndexIDMap:
+    """faiss.IndexIDMap over a flat index: rows carry the caller's 64-bit ids, which survive ``remove_ids`` (the
+    sub-index renumbers its rows; ``id_map[row]`` follows).  The mapping is host numpy, off the hot path."""
+
+    def __init__(self, index: IndexFlat):
+        assert index.ntotal == 0, "IndexIDMap wraps an empty index (Faiss: index is empty on input)"
+        self.index = index
+        self.id_map = np.zeros(0, dtype=np.int64)
+
+    d = property(lambda self: self.index.d)
+    metric_type = property(lambda self: self.index.metric_type)
+    is_trained = property(lambda self: self.index.is_trained)
+    ntotal = property(lambda self: self.index.ntotal)
+
+    def add(self, x) -> None:
+        raise RuntimeError("add does not work with IndexIDMap, call add_with_ids")  # Faiss throws the same
+
+    def add_with_ids(self, x, ids) -> None:
+        x = _as_rows(x, self.index.d)
+        ids = _ids_array(ids)
+        assert ids.shape[0] == x.shape[0], "one id per row"
+        self.index.add(x)
+        self.id_map = np.concatenate((self.id_map, ids))
+
+    def _map(self, I: np.ndarray) -> np.ndarray:
+        out = np.full(I.shape, -1, dtype=np.int64)
+        ok = I >= 0
+        out[ok] = self.id_map[I[ok]]
+        return out
+
+    def search(self, x, k: int):
+        D, I = self.index.search(x, k)
+        return D, self._map(I)
+
+    def range_search(self, x, radius: float):
+        lims, D, I = self.index.range_search(x, radius)
+        return lims, D, self._map(I)
+
+    def remove_ids(self, sel) -> int:
+        """``sel`` selects EXTERNAL ids (a selector, or an int64 array-like taken as a batch)."""
+        if not isinstance(sel, IDSelector):
+            sel = IDSelectorBatch(sel)
+        gone = sel.members(self.id_map)
+        rows = np.flatnonzero(gone).astype(np.int64)
+        if rows.size == 0:
+            return 0
+        n = self.index.remove_ids(rows)
+        assert n == rows.size
+        self.id_map = self.id_map[~gone]
+        return n
+
+    def reset(self) -> None:
+        self.index.reset()
+        self.id_map = np.zeros(0, dtype=np.int64)
+
+
 def merge_keys_torch(keys, metric: int):
     """Merge all-gathered candidate lists: ``keys`` int64 CUDA (n_lists, nq, k) ->
     (D float32 (nq,k), I int64 (nq,k)) on the same device."""
@@ -393,7 +580,11 @@ def normalize_L2(x) -> None:
 #   fourcc "IxF2" (L2) / "IxFI" (IP); int32 d; int64 ntotal; int64 1<<20;
 #   int64 1<<20; uint8 is_trained; int32 metric_type; uint64 count (= N*d
 #   float32 words); count float32.
+# IndexIDMap [upstream-faiss index_write.cpp, restated from the published format and UNPINNED like row 8f-1]:
+#   fourcc "IxMp"; the same index header (d, ntotal, 1<<20, 1<<20, is_trained, metric_type); the sub-index as
+#   written above; then the id vector: uint64 count (= ntotal); count int64.
 _FOURCC = {METRIC_L2: b"IxF2", METRIC_INNER_PRODUCT: b"IxFI"}
+_FOURCC_IDMAP = b"IxMp"
 _HDR = struct.Struct("<4siqqqBi")
 
 
@@ -402,6 +593,35 @@ def serialize_flat(d: int, metric: int, xb: np.ndarray) -> bytes:
     n = xb.shape[0] if xb.size else 0
     head = _HDR.pack(_FOURCC[metric], d, n, 1 << 20, 1 << 20, 1, metric)
     return head + struct.pack("<Q", n * d) + xb.tobytes()
+
+
+def serialize_idmap(d: int, metric: int, xb: np.ndarray, ids) -> bytes:
+    ids = np.ascontiguousarray(ids, dtype="<i8").reshape(-1)
+    n = xb.shape[0] if np.size(xb) else 0
+    assert ids.size == n, "one id per row"
+    head = _HDR.pack(_FOURCC_IDMAP, d, n, 1 << 20, 1 << 20, 1, metric)
+    return head + serialize_flat(d, metric, xb) + struct.pack("<Q", n) + ids.tobytes()
+
+
+def parse_idmap(buf: bytes):
+    """-> (d, metric, xb float32 (n, d), ids int64 (n,)); raises RuntimeError on a foreign or truncated file."""
+    if len(buf) < _HDR.size:
+        raise RuntimeError("truncated index file")
+    fourcc, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
+    if fourcc != _FOURCC_IDMAP:
+        raise RuntimeError(f"unsupported index type {fourcc!r}: not an IndexIDMap")
+    sub = buf[_HDR.size:]
+    d2, metric, xb = parse_flat(sub)
+    if d2 != d or xb.shape[0] != n:
+        raise RuntimeError("corrupt IndexIDMap: the sub-index does not match the header")
+    off = 2 * _HDR.size + 8 + 4 * n * d
+    if len(buf) < off + 8:
+        raise RuntimeError("truncated IndexIDMap id vector")
+    (count,) = struct.unpack_from("<Q", buf, off)
+    if count != n or len(buf) < off + 8 + 8 * count:
+        raise RuntimeError("truncated IndexIDMap id vector")
+    ids = np.frombuffer(buf, dtype="<i8", count=count, offset=off + 8).astype(np.int64)
+    return d, metric, xb, ids
 
 
 def parse_flat(buf: bytes):
@@ -422,16 +642,30 @@ def parse_flat(buf: bytes):
     return d, metric, xb
 
 
-def write_index(index: IndexFlat, path) -> None:
+def write_index(index, path) -> None:
     with open(str(path), "wb") as f:
-        f.write(serialize_flat(index.d, index.metric_type, index.reconstruct_n(0, index.ntotal)))
+        if isinstance(index, IndexIDMap):
+            sub = index.index
+            f.write(serialize_idmap(sub.d, sub.metric_type, sub.reconstruct_n(0, sub.ntotal), index.id_map))
+        else:
+            f.write(serialize_flat(index.d, index.metric_type, index.reconstruct_n(0, index.ntotal)))
 
 
-def read_index(path, device: int | None = None) -> IndexFlat:
+def read_index(path, device: int | None = None):
+    """-> IndexFlat, or IndexIDMap for a file written from one."""
     with open(str(path), "rb") as f:
-        d, metric, xb = parse_flat(f.read())
+        buf = f.read()
+    ids = None
+    if buf[:4] == _FOURCC_IDMAP:
+        d, metric, xb, ids = parse_idmap(buf)
+    else:
+        d, metric, xb = parse_flat(buf)
     index = IndexFlat(d, metric, device)
-    if xb.shape[0]:
+    if ids is not None:
+        index = IndexIDMap(index)
+        if xb.shape[0]:
+            index.add_with_ids(xb, ids)
+    elif xb.shape[0]:
         index.add(xb)
     return index
 

@@ -127,7 +127,7 @@ int ise_index_stage_query_debug(ise_index_t* h, const void* q_dev, int route, vo
                                 float* out2, int32_t* info3);
 
 /* Test / rehearsal knobs ($ISE_FORCE_EXACT, $ISE_NO_DIRECT, $ISE_NO_SHORT, $ISE_SHORT_TPB_MAX,
- * $ISE_DIRECT_SHORT_MAX_TILES, $ISE_RANGE_STAGE_CAP, $ISE_NO_HALF_FILTER, $ISE_NO_BYTE_FILTER, $ISE_FAIL_BYTE_ALLOC) are read from the environment when the library is first used and again when
+ * $ISE_DIRECT_SHORT_MAX_TILES, $ISE_RANGE_STAGE_CAP, $ISE_NO_HALF_FILTER, $ISE_NO_BYTE_FILTER, $ISE_FAIL_BYTE_ALLOC, $ISE_REMOVE_SLAB_ROWS) are read from the environment when the library is first used and again when
  * this is called -- never inside a search. */
 int ise_refresh_env_knobs(void);
 
@@ -174,6 +174,29 @@ int ise_range_result_destroy(ise_range_result_t* r); /* NULL is a no-op */
 /* out2[0] = range batches (<= 256 queries of a call against a non-empty index), out2[1] = batches that needed
  * the overflow pass ($ISE_RANGE_STAGE_CAP: staging entries per segment, default 16; tests set it small) */
 int ise_index_range_stats(ise_index_t* h, uint64_t* out2);
+
+/* index.remove_ids(faiss.IDSelectorBatch(ids)) (Faiss IndexFlatCodes::remove_ids; the reference never removes rows:
+ * it rebuilds its index file with backend/indexer.py).  Every existing row named in ids (host, n_ids int64, in any
+ * order; duplicates and values outside [0, ntotal) are ignored) is removed once; the other rows keep their order and
+ * are renumbered densely, so ids handed out earlier shift (IndexIDMap in faiss_compat.py keeps external ids).  The
+ * rows, their norms and, where the index has them, both shadows and their metadata are compacted IN PLACE on the
+ * device (csrc/ise_remove.hpp): capacity is kept, the extra memory is one bounce buffer of at most 256 MiB
+ * ($ISE_REMOVE_SLAB_ROWS: destination rows per slab; tests set it small), nothing is re-uploaded or rebuilt.
+ * The shift vector stays (results never depend on it); an unpinned index that has shrunk below three quarters of
+ * the rows it was taken from refreshes it at the next search, and an index at or below 262144 rows drops its shadows.
+ * *n_removed (may be NULL) = rows removed.  Blocks; searches and range searches of other threads run entirely
+ * before or entirely after it.  A call that removes nothing returns at once. */
+int ise_index_remove_ids_host(ise_index_t* h, const int64_t* ids, int64_t n_ids, int64_t* n_removed);
+/* index.remove_ids(faiss.IDSelectorRange(i0, i1)): rows [i0, i1), clipped to [0, ntotal); as above (the
+ * reference never removes rows). */
+int ise_index_remove_range(ise_index_t* h, int64_t i0, int64_t i1, int64_t* n_removed);
+/* Counters of the two calls above since the index was created (Faiss keeps none; the reference never removes
+ * rows): out3[0] = calls that removed something, out3[1] = rows removed, out3[2] = rows moved to a new position. */
+int ise_index_remove_stats(ise_index_t* h, uint64_t* out3);
+/* measurement hook for scripts/remove_probe.py (Faiss has no counterpart; the reference never removes rows): the
+ * slab launches of the last call that removed something, as HIP events on the index's stream timed them
+ * (milliseconds), and the bytes they moved, each counted once (they are read twice and written twice). */
+int ise_index_remove_last_timing(ise_index_t* h, float* ms, uint64_t* bytes);
 int ise_index_search_device(ise_index_t* h, const float* q_dev, int64_t nq, int k,
                             float* D_dev, int64_t* I_dev, void* stream);
 
