@@ -72,6 +72,15 @@ PROTOTYPES = [
     ("ise_index_remove_range", _int, [_vp, _i64, _i64, _i64p]),
     ("ise_index_remove_stats", _int, [_vp, _u64p]),
     ("ise_index_remove_last_timing", _int, [_vp, _f32p, _u64p]),
+    ("ise_selector_create_range", _int, [_vp, _i64, _i64, ctypes.POINTER(_vp)]),
+    ("ise_selector_create_ids", _int, [_vp, _vp, _i64, _int, ctypes.POINTER(_vp)]),
+    ("ise_selector_create_bitmap", _int, [_vp, _vp, _i64, ctypes.POINTER(_vp)]),
+    ("ise_selector_info", _int, [_vp, _i64p]),
+    ("ise_selector_destroy", _int, [_vp]),
+    ("ise_index_search_sel_device", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    ("ise_index_search_sel_host", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
+    ("ise_index_range_search_sel_host", _int, [_vp, _vp, _i64, ctypes.c_float, _vp, ctypes.POINTER(_vp)]),
+    ("ise_index_sel_stats", _int, [_vp, _u64p]),
     ("ise_refresh_env_knobs", _int, []),
     ("ise_comm_precheck", _int, [_int]),
     ("ise_comm_unique_id", _int, [_vp]),

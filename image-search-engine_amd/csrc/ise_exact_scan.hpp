@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256, QN == 1 ? 2 : 4) void exact_scan_kernel(const 
 
 // k > 32 on the exact path: copy one exact pass's keys [list position][kp] into the final outputs at
 // column `off` and keep each query's last key as the floor of the next pass
-__global__ __launch_bounds__(256) void exact_scatter_kernel(const ExactParams p, const u64* pass_keys, int kp, int off,
+static __global__ __launch_bounds__(256) void exact_scatter_kernel(const ExactParams p, const u64* pass_keys, int kp, int off,
                                                             u64* floor_out) {
     const u64 st = __hip_atomic_load(p.fl_state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if ((uint32_t)(st >> 32) != p.seq) return;

@@ -25,6 +25,7 @@
 //   row helpers    ise_rows.hpp    norms, padding / bf16 conversion, normalize_L2, shift
 //   range search   ise_range.hpp   every row within a radius: one pass per 16 queries + offset / compaction kernels
 //   remove_ids     ise_remove.hpp  stable in-place compaction of the rows and of everything kept per row
+//   selectors      ise_sel_scan.hpp  search / range search among the rows a device bitmap names: one masked pass per 16 queries
 //
 // Candidate order: a 64-bit key = ord(score) << 32 | row id, where ord() is the
 // order-preserving map float -> uint32 and score = squared L2 (or -inner product).
@@ -45,6 +46,7 @@
 #include "ise_rows.hpp"
 #include "ise_short_scan.hpp"
 #include "ise_range.hpp"
+#include "ise_sel_scan.hpp"
 #include "ise_stage.hpp"
 #include "ise_remove.hpp"
 
@@ -201,6 +203,25 @@ struct ise_index {
     unsigned long long remove_calls = 0, remove_rows = 0, remove_moved = 0;
     float remove_last_ms = 0.f;
     unsigned long long remove_last_bytes = 0;
+    // selectors (ise_sel_scan.hpp).  row_epoch: bumped by whatever removes rows (reset, remove_ids, remove_range), never
+    // by add; a selector made at another epoch or ntotal is refused (under mu_).  The masked pass has a slot scheme
+    // of its own, NSS slots handed out like the WorkSlots (a stream keeps its slot; another stream takes a fresh one,
+    // or the least recently taken one behind an event wait), so filtered searches of several threads and streams
+    // run beside unfiltered ones and beside each other
+    unsigned long long row_epoch = 0;
+    struct SelSlot {
+        Buf<float> q;      // [chunk][dp] padded queries
+        Buf<u64> part;     // [groups][blocks][16][kpass]
+        Buf<u64> keys;     // [chunk][32] one pass's merged keys (k > 32) | [chunk] floors
+        hipEvent_t done = nullptr;
+        bool used = false;
+        hipStream_t last_stream = nullptr;
+    };
+    static constexpr int NSS = 4;
+    SelSlot ss[NSS];
+    unsigned ss_next = 0;
+    unsigned long long sel_batches = 0, sel_passes = 0;  // under mu_
+    unsigned long long sel_range_batches = 0;            // under rg_mu
 };
 
 // rows are padded to whole k-steps of 64 bytes (16 floats / 32 bf16); rows longer than
@@ -362,6 +383,12 @@ static void free_all(ise_index* h) {
             if (p) (void)hipHostFree(p);
         r = ise_index::RangeWs();
     }
+    for (auto& sl : h->ss) {
+        for (void* p : {(void*)sl.q.p, (void*)sl.part.p, (void*)sl.keys.p})
+            if (p) (void)hipFree(p);
+        if (sl.done) (void)hipEventDestroy(sl.done);
+        sl = ise_index::SelSlot();
+    }
     h->xb = h->norms = nullptr;
     h->n = h->cap = 0;
 }
@@ -390,6 +417,7 @@ extern "C" int ise_index_reset(ise_index_t* h) {
     free_shadow(h);
     h->shadow_off = false;
     h->byte_off = false;
+    if (h->n > 0) h->row_epoch++;  // rows went: selectors made before are stale
     h->xb = h->norms = nullptr;
     h->n = h->cap = 0;
     h->shift_pinned = false;
@@ -2091,8 +2119,44 @@ static void range_params_index(const ise_index* h, RangeParams* rp) {
     rp->beta = uses_shift(h) ? exact_beta(h) : 0.f;
 }
 
-// one batch of m <= RANGE_NQ_CHUNK queries, appended to r (rg_mu held)
-static int range_batch(ise_index* h, hipStream_t st, const float* q, long long m, float radius, ise_range_result* r) {
+// ---- selectors (ise_sel_scan.hpp): a device bitmap over the rows of ONE index at ONE (ntotal, row epoch)
+struct ise_selector {
+    ise_index* owner = nullptr;
+    uint32_t* bits = nullptr;  // ceil(ntotal / 32) words + zero padding (pad rows of the last tile and word: zero bits)
+    long long nwords = 0;      // allocated words
+    long long ntotal = 0;
+    unsigned long long epoch = 0;
+    long long count = 0, r0 = 0, r1 = 0, tiles = 0;  // selected rows, window [r0, r1), non-empty 16-row tiles
+};
+
+// mu_ held.  A selector is good for the handle it was made from while ntotal and the row epoch stand
+static int selector_check_locked(const ise_index* h, const ise_selector* sel) {
+    if (!sel) return fail(ISE_E_INVALID, "selector is NULL");
+    if (sel->owner != h) return fail(ISE_E_INVALID, "the selector was made for another index");
+    if (sel->epoch != h->row_epoch)
+        return fail(ISE_E_INVALID, "stale selector: rows were removed from the index (row epoch changed) since it was made");
+    if (sel->ntotal != h->n)
+        return fail(ISE_E_INVALID, "stale selector: ntotal changed (" + std::to_string(sel->ntotal) + " -> " +
+                                       std::to_string(h->n) + ") since it was made");
+    return ISE_OK;
+}
+
+// the streaming kernel's query staging for this index (the bits of |x|^2 for bf16 L2): threads per query row from
+// the waves of its one-tile plan, the vector path where the rows allow it (padded queries are 16-byte aligned)
+static int range_staging(const ise_index* h, int qs_stride, int* tpr, int* vec_q) {
+    ScanPlan pl;
+    const int rc = make_plan(h, 16, 1, &pl, false, false);
+    if (rc) return rc;
+    const bool bf16 = h->storage == ISE_STORE_BF16;
+    *tpr = pl.waves >= 8 ? 32 : 16;
+    *vec_q = (h->d & (bf16 ? 7 : 3)) == 0 && (qs_stride >> 2) <= *tpr * (bf16 ? 4 : 8);
+    return ISE_OK;
+}
+
+// one batch of m <= RANGE_NQ_CHUNK queries, appended to r (rg_mu held).  sel: restricted to a selector's window and
+// mask (the MASK instantiations), or null
+static int range_batch(ise_index* h, hipStream_t st, const float* q, long long m, float radius, const ise_selector* sel,
+                       ise_range_result* r) {
     auto& ws = h->rg;
     const int dp = h->dp, d = h->d;
     // queries zero padded to dp: the staging reads them per row, the direct difference as exact_l2_rows does
@@ -2119,22 +2183,27 @@ static int range_batch(ise_index* h, hipStream_t st, const float* q, long long m
             r->lims.resize(r->lims.size() + (size_t)m, r->lims.back());
             return ISE_OK;
         }
+        if (sel) {
+            rc = selector_check_locked(h, sel);
+            if (rc) return rc;
+            if (sel->count == 0) {  // an empty selection: every list is empty
+                r->lims.resize(r->lims.size() + (size_t)m, r->lims.back());
+                h->sel_range_batches++;
+                return ISE_OK;
+            }
+        }
         range_params_index(h, &rp);
-        // the streaming kernel's query staging for this index (the bits of |x|^2 for bf16 L2): threads per query
-        // row from the waves of its one-tile plan, the vector path where the rows allow it (its host queries are
-        // 16-byte aligned)
-        ScanPlan pl;
-        rc = make_plan(h, 16, 1, &pl, false, false);
+        rc = range_staging(h, rp.qs_stride, &rp.tpr, &rp.vec_q);
         if (rc) return rc;
-        const bool bf16 = h->storage == ISE_STORE_BF16;
-        rp.tpr = pl.waves >= 8 ? 32 : 16;
-        rp.vec_q = (d & (bf16 ? 7 : 3)) == 0 && (rp.qs_stride >> 2) <= rp.tpr * (bf16 ? 4 : 8);
         ch = std::min(chunk_steps(h), 4);
-        // blocks own contiguous slabs of row tiles, up to 4 blocks per CU
-        rp.tiles_total = (int)((n0 + 15) / 16);
-        int nb = std::max(1, std::min(rp.tiles_total, 4 * h->num_cu));
-        rp.tiles_per_block = (rp.tiles_total + nb - 1) / nb;
-        nb = (rp.tiles_total + rp.tiles_per_block - 1) / rp.tiles_per_block;
+        // blocks own contiguous slabs of row tiles (of the selector's window), up to 4 blocks per CU
+        rp.tile0 = sel ? (int)(sel->r0 / 16) : 0;
+        rp.bits = sel ? sel->bits : nullptr;
+        rp.tiles_total = sel ? (int)((sel->r1 + 15) / 16) : (int)((n0 + 15) / 16);
+        const int span = rp.tiles_total - rp.tile0;
+        int nb = std::max(1, std::min(span, 4 * h->num_cu));
+        rp.tiles_per_block = (span + nb - 1) / nb;
+        nb = (span + rp.tiles_per_block - 1) / rp.tiles_per_block;
         rp.nseg = nb * RANGE_W;
         rp.n = n0;
         rp.nq = (int)m;
@@ -2161,7 +2230,8 @@ static int range_batch(ise_index* h, hipStream_t st, const float* q, long long m
         grid = dim3((unsigned)nb, (unsigned)((m + 15) / 16));
         lds = range_lds_bytes(rp.qs_stride);
         HIP_TRY(hipMemsetAsync(ws.flag.p, 0, sizeof(unsigned), st));
-        launch_range(h, ch, grid, lds, st, rp);
+        if (sel) ise_launch_range_masked(h->storage == ISE_STORE_BF16, uses_shift(h), ch, grid, lds, st, rp);
+        else launch_range(h, ch, grid, lds, st, rp);
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(range_offsets_kernel, dim3((unsigned)m), dim3(256), 0, st, ws.cnt.p, rp.nseg, rp.cap,
@@ -2184,13 +2254,18 @@ static int range_batch(ise_index* h, hipStream_t st, const float* q, long long m
             rc = prepare_shift_locked(h, st);
             if (rc) return rc;
             if (h->n < n0 || !h->xb) return fail(ISE_E_INVALID, "the index was reset during range_search");
+            if (sel) {  // an add since the first pass: the selector no longer names this index's rows
+                rc = selector_check_locked(h, sel);
+                if (rc) return rc;
+            }
             range_params_index(h, &rp);
             rp.mode = 1;
             rp.lims = ws.lims.p;
             rp.segoff = ws.segoff.p;
             rp.D = ws.D.p;
             rp.I = ws.I.p;
-            launch_range(h, ch, grid, lds, st, rp);
+            if (sel) ise_launch_range_masked(h->storage == ISE_STORE_BF16, uses_shift(h), ch, grid, lds, st, rp);
+            else launch_range(h, ch, grid, lds, st, rp);
             HIP_TRY(hipGetLastError());
         } else {
             hipLaunchKernelGGL(range_compact_kernel, dim3((unsigned)((rp.nseg + 3) / 4), (unsigned)m), dim3(256), 0,
@@ -2205,13 +2280,14 @@ static int range_batch(ise_index* h, hipStream_t st, const float* q, long long m
     }
     const int64_t base = r->lims.back();
     for (long long i = 1; i <= m; i++) r->lims.push_back(base + ws.lims_pin.p[i]);
-    h->range_batches++;
+    if (sel) h->sel_range_batches++;
+    else h->range_batches++;
     if (overflow) h->range_overflows++;
     return ISE_OK;
 }
 
-extern "C" int ise_index_range_search_host(ise_index_t* h, const float* q, int64_t nq, float radius,
-                                           ise_range_result_t** out) {
+static int range_search_host(ise_index_t* h, const float* q, int64_t nq, float radius, const ise_selector* sel,
+                             ise_range_result_t** out) {
     if (!h) return fail(ISE_E_INVALID, "handle is NULL");
     if (!out) return fail(ISE_E_INVALID, "output pointer is NULL");
     *out = nullptr;
@@ -2235,7 +2311,7 @@ extern "C" int ise_index_range_search_host(ise_index_t* h, const float* q, int64
             std::lock_guard<std::mutex> lk(h->rg_mu);
             for (long long i0 = 0; i0 < nq; i0 += RANGE_NQ_CHUNK) {
                 const long long m = std::min<long long>(RANGE_NQ_CHUNK, nq - i0);
-                const int rc = range_batch(h, c->stream, q + (size_t)i0 * h->d, m, radius, r);
+                const int rc = range_batch(h, c->stream, q + (size_t)i0 * h->d, m, radius, sel, r);
                 if (rc) {
                     delete r;
                     return rc;
@@ -2251,6 +2327,24 @@ extern "C" int ise_index_range_search_host(ise_index_t* h, const float* q, int64
     return ISE_OK;
 }
 
+extern "C" int ise_index_range_search_host(ise_index_t* h, const float* q, int64_t nq, float radius,
+                                           ise_range_result_t** out) {
+    return range_search_host(h, q, nq, radius, nullptr, out);
+}
+
+extern "C" int ise_index_range_search_sel_host(ise_index_t* h, const float* q, int64_t nq, float radius,
+                                               const ise_selector_t* sel, ise_range_result_t** out) {
+    if (out) *out = nullptr;
+    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
+    if (!sel) return fail(ISE_E_INVALID, "selector is NULL");
+    {
+        std::lock_guard<std::mutex> lk(h->mu_);
+        const int rc = selector_check_locked(h, sel);  // also when the index is empty or nq == 0
+        if (rc) return rc;
+    }
+    return range_search_host(h, q, nq, radius, sel, out);
+}
+
 extern "C" int ise_range_result_get(const ise_range_result_t* r, int64_t* nq, const int64_t** lims, const float** D,
                                     const int64_t** I) {
     if (!r) return fail(ISE_E_INVALID, "result is NULL");
@@ -2263,6 +2357,328 @@ extern "C" int ise_range_result_get(const ise_range_result_t* r, int64_t* nq, co
 
 extern "C" int ise_range_result_destroy(ise_range_result_t* r) {
     delete r;
+    return ISE_OK;
+}
+
+// ---- selector objects and the selector-filtered search (ise_sel_scan.hpp)
+#define SEL_NQ_CHUNK 64 /* queries per masked launch (4 groups of 16): bounds the per-block lists of a slot */
+
+// the bitmap of a new selector for h as it stands (mu_ held): ceil(n / 32) words and a word of padding, so that the
+// half-word of every tile below the capacity's last one is there to read, zero
+static int selector_alloc_locked(ise_index* h, ise_selector** out) {
+    ise_selector* s = new (std::nothrow) ise_selector;
+    if (!s) return fail(ISE_E_NOMEM, "selector: host allocation failed");
+    s->owner = h;
+    s->ntotal = h->n;
+    s->epoch = h->row_epoch;
+    s->nwords = (h->n + 31) / 32 + 1;
+    const hipError_t e = hipMalloc((void**)&s->bits, (size_t)s->nwords * sizeof(uint32_t));
+    if (e != hipSuccess) {
+        delete s;
+        return fail(e == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP, std::string("selector bitmap: ") + hipGetErrorString(e));
+    }
+    *out = s;
+    return ISE_OK;
+}
+
+static void selector_free(ise_selector* s) {
+    if (s->bits) (void)hipFree(s->bits);
+    delete s;
+}
+
+// clears bits at or beyond ntotal, then count / window / non-empty tiles on the device (mu_ held; blocks)
+static int selector_census_locked(ise_index* h, ise_selector* s, hipStream_t st) {
+    unsigned long long* dev = nullptr;
+    HIP_TRY(hipMalloc((void**)&dev, 4 * sizeof(unsigned long long)));
+    struct Free { void* p; ~Free() { (void)hipFree(p); } } fr{dev};
+    const unsigned long long init[4] = {0ull, 0ull, ~0ull, 0ull};
+    unsigned long long got[4];
+    HIP_TRY(hipMemcpyAsync(dev, init, sizeof(init), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(sel_census_kernel, dim3((unsigned)((s->nwords + 255) / 256)), dim3(256), 0, st, s->bits, s->nwords,
+                       s->ntotal, dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(got, dev, sizeof(got), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    s->count = (long long)got[0];
+    s->tiles = (long long)got[1];
+    s->r0 = got[0] ? (long long)got[2] : 0;
+    s->r1 = got[0] ? (long long)got[3] : 0;
+    return ISE_OK;
+}
+
+extern "C" int ise_selector_create_range(ise_index_t* h, int64_t i0, int64_t i1, ise_selector_t** out) {
+    if (!out) return fail(ISE_E_INVALID, "output pointer is NULL");
+    *out = nullptr;
+    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    DeviceGuard gd(h->device);
+    ise_selector* s = nullptr;
+    int rc = selector_alloc_locked(h, &s);
+    if (rc) return rc;
+    const long long a = std::max<long long>(i0, 0), b = std::min<long long>(i1, h->n);
+    hipLaunchKernelGGL(sel_fill_range_kernel, dim3((unsigned)((s->nwords + 255) / 256)), dim3(256), 0, h->stream, s->bits,
+                       s->nwords, a, std::max(a, b));
+    rc = selector_census_locked(h, s, h->stream);
+    if (rc) { selector_free(s); return rc; }
+    *out = s;
+    return ISE_OK;
+}
+
+extern "C" int ise_selector_create_ids(ise_index_t* h, const int64_t* ids, int64_t n_ids, int invert, ise_selector_t** out) {
+    if (!out) return fail(ISE_E_INVALID, "output pointer is NULL");
+    *out = nullptr;
+    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(ISE_E_INVALID, "ids is NULL");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    DeviceGuard gd(h->device);
+    ise_selector* s = nullptr;
+    int rc = selector_alloc_locked(h, &s);
+    if (rc) return rc;
+    long long* ids_dev = nullptr;
+    struct Free { long long** p; ~Free() { if (*p) (void)hipFree(*p); } } fr{&ids_dev};
+    auto body = [&]() -> int {
+        // the fill runs on the device: nothing (invert: every row), then the ids are scattered in -- only they travel
+        hipLaunchKernelGGL(sel_fill_range_kernel, dim3((unsigned)((s->nwords + 255) / 256)), dim3(256), 0, h->stream,
+                           s->bits, s->nwords, 0ll, invert ? h->n : 0ll);
+        if (n_ids > 0) {
+            HIP_TRY(hipMalloc((void**)&ids_dev, (size_t)n_ids * sizeof(long long)));
+            HIP_TRY(hipMemcpyAsync(ids_dev, ids, (size_t)n_ids * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+            hipLaunchKernelGGL(sel_scatter_ids_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, h->stream,
+                               s->bits, (const long long*)ids_dev, (long long)n_ids, h->n, invert ? 0 : 1);
+        }
+        HIP_TRY(hipGetLastError());
+        return selector_census_locked(h, s, h->stream);
+    };
+    rc = body();
+    if (rc) { selector_free(s); return rc; }
+    *out = s;
+    return ISE_OK;
+}
+
+extern "C" int ise_selector_create_bitmap(ise_index_t* h, const uint32_t* words, int64_t n_words, ise_selector_t** out) {
+    if (!out) return fail(ISE_E_INVALID, "output pointer is NULL");
+    *out = nullptr;
+    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
+    if (n_words < 0 || (n_words > 0 && !words)) return fail(ISE_E_INVALID, "words is NULL");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    if (n_words != (h->n + 31) / 32)
+        return fail(ISE_E_INVALID, "the bitmap must have ceil(ntotal / 32) = " + std::to_string((h->n + 31) / 32) + " words");
+    DeviceGuard gd(h->device);
+    ise_selector* s = nullptr;
+    int rc = selector_alloc_locked(h, &s);
+    if (rc) return rc;
+    auto body = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(s->bits + n_words, 0, (size_t)(s->nwords - n_words) * sizeof(uint32_t), h->stream));
+        if (n_words > 0)
+            HIP_TRY(hipMemcpyAsync(s->bits, words, (size_t)n_words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        return selector_census_locked(h, s, h->stream);  // clears the bits at or beyond ntotal
+    };
+    rc = body();
+    if (rc) { selector_free(s); return rc; }
+    *out = s;
+    return ISE_OK;
+}
+
+extern "C" int ise_selector_info(const ise_selector_t* sel, int64_t* out5) {
+    if (!sel || !out5) return fail(ISE_E_INVALID, "NULL argument");
+    out5[0] = sel->ntotal;
+    out5[1] = sel->count;
+    out5[2] = sel->r0;
+    out5[3] = sel->r1;
+    out5[4] = sel->tiles;
+    return ISE_OK;
+}
+
+extern "C" int ise_selector_destroy(ise_selector_t* sel) {
+    if (!sel) return ISE_OK;
+    // hipFree waits for the device: a masked pass still in flight has finished reading the bitmap
+    selector_free(sel);
+    return ISE_OK;
+}
+
+// one chunk of m <= SEL_NQ_CHUNK queries (mu_ held, the selector checked, the shift prepared): pad the queries, then
+// per 32 results one masked pass + the merge of its per-block lists
+static int sel_chunk_enqueue(ise_index* h, ise_index::SelSlot* sl, const ise_selector* sel, const float* q_dev, long long m,
+                             int k, float* D_dev, long long* I_dev, hipStream_t st) {
+    SelScanParams sp{};
+    sp.xb = h->xb; sp.norms = h->norms; sp.mu = h->mu; sp.bits = sel->bits;
+    sp.n = h->n; sp.d = h->d; sp.dp = h->dp;
+    sp.qs_stride = qs_stride_for(h);
+    sp.row_slots = (int)(row_bytes(h) / 16);
+    sp.nq = (int)m; sp.metric = h->metric;
+    sp.beta = uses_shift(h) ? exact_beta(h) : 0.f;
+    int rc = range_staging(h, sp.qs_stride, &sp.tpr, &sp.vec_q);
+    if (rc) return rc;
+    const int ch = std::min(chunk_steps(h), 4);
+    // the grid comes from the window's tiles, not from the index: at least a tile per wave, at most two blocks per CU
+    // (what their LDS lets a CU hold) and the merge's list count
+    sp.tile0 = (int)(sel->r0 / 16);
+    sp.tile1 = (int)((sel->r1 + 15) / 16);
+    const int span = sp.tile1 - sp.tile0;
+    int nb = std::max(1, std::min({(span + SEL_W - 1) / SEL_W, 2 * h->num_cu, MERGE_LISTS_MAX}));
+    sp.tiles_per_block = (span + nb - 1) / nb;
+    nb = (span + sp.tiles_per_block - 1) / sp.tiles_per_block;
+    const int groups = (int)((m + 15) / 16);
+    // results per pass: XPASS_MAX, or what the wave lists' LDS holds beside long query rows (d = 2048: 19)
+    static_assert(XPASS_MAX == SEL_KPASS_MAX, "one masked pass yields what one exact pass yields");
+    const long long lds_left = (long long)LDS_LIMIT - (long long)range_lds_bytes(sp.qs_stride);
+    const int kp = (int)std::min<long long>(std::min(k, XPASS_MAX), lds_left / (SEL_W * 16 * 8));
+    if (kp < 1) return fail(ISE_E_INVALID, "rows too long for the selector-filtered search");
+    rc = range_grow(sl->q, (size_t)m * h->dp);
+    if (!rc) rc = range_grow(sl->part, (size_t)groups * nb * 16 * kp);
+    if (!rc && k > kp) rc = range_grow(sl->keys, (size_t)m * kp + (size_t)m);
+    if (rc) return rc;
+    const long long qtot = m * h->dp;
+    hipLaunchKernelGGL(sel_pad_queries_kernel, dim3((unsigned)((qtot + 255) / 256)), dim3(256), 0, st, q_dev, h->d, h->dp,
+                       qtot, sl->q.p);
+    sp.q = sl->q.p;
+    sp.part = sl->part.p;
+    sp.kpass = kp;
+    MergeParams mp{};
+    mp.lists = sl->part.p; mp.qt = 16; mp.n_lists = nb; mp.nq = (int)m; mp.k = kp; mp.metric = h->metric;
+    mp.stride_list = 16ll * kp; mp.stride_qtile = (long long)nb * 16 * kp;
+    const ExactParams xp{};
+    const dim3 grid((unsigned)nb, (unsigned)groups);
+    const size_t lds = sel_lds_bytes(sp.qs_stride, kp);
+    const int bf16 = h->storage == ISE_STORE_BF16, shift = uses_shift(h);
+    if (k <= kp) {
+        sp.floor_keys = nullptr;
+        ise_launch_sel_scan(bf16, shift, ch, grid, lds, st, sp);
+        mp.D = D_dev; mp.I = I_dev;
+        launch_merge<false>((unsigned)m, 0, st, mp, xp);
+        h->sel_passes++;
+    } else {
+        u64* pass_keys = sl->keys.p;
+        u64* floors = pass_keys + (size_t)m * kp;
+        for (int off = 0; off < k; off += kp) {
+            sp.floor_keys = off ? floors : nullptr;
+            ise_launch_sel_scan(bf16, shift, ch, grid, lds, st, sp);
+            mp.keys_out = pass_keys;
+            launch_merge<false>((unsigned)m, 0, st, mp, xp);
+            const long long tot = m * kp;
+            hipLaunchKernelGGL(sel_scatter_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st,
+                               (const u64*)pass_keys, (int)m, kp, off, k, h->metric, D_dev, I_dev, floors);
+            h->sel_passes++;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return ISE_OK;
+}
+
+// mu_ held.  Enqueues only
+static int search_sel_enqueue(ise_index* h, const ise_selector* sel, const float* q_dev, long long nq, int k, float* D_dev,
+                              long long* I_dev, hipStream_t st) {
+    int rc = selector_check_locked(h, sel);
+    if (rc) return rc;
+    h->sel_batches++;
+    if (sel->count == 0) {  // an empty window: padding, no pass
+        const long long tot = nq * k;
+        hipLaunchKernelGGL(sel_fill_pad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, tot,
+                           h->metric);
+        HIP_TRY(hipGetLastError());
+        return ISE_OK;
+    }
+    rc = prepare_shift_locked(h, st);
+    if (rc) return rc;
+    ise_index::SelSlot* sl = nullptr;
+    bool same_stream = false;
+    for (auto& s : h->ss)
+        if (s.used && s.last_stream == st) { sl = &s; same_stream = true; break; }
+    if (!sl)
+        for (auto& s : h->ss)
+            if (!s.used) { sl = &s; break; }
+    if (!sl) sl = &h->ss[h->ss_next++ % ise_index::NSS];
+    if (!sl->done) HIP_TRY(hipEventCreateWithFlags(&sl->done, hipEventDisableTiming));
+    if (sl->used && !same_stream) {
+        HIP_TRY(hipStreamWaitEvent(st, sl->done, 0));
+        // its buffers may grow (free + allocate) below: the other stream's passes have to be through with them
+        HIP_TRY(hipEventSynchronize(sl->done));
+    }
+    struct Release {  // whatever path returns, a later user on another stream waits for this call
+        ise_index::SelSlot* sl;
+        hipStream_t st;
+        ~Release() {
+            if (hipEventRecord(sl->done, st) == hipSuccess) { sl->used = true; sl->last_stream = st; }
+        }
+    } release{sl, st};
+    for (long long i0 = 0; i0 < nq; i0 += SEL_NQ_CHUNK) {
+        const long long m = std::min<long long>(SEL_NQ_CHUNK, nq - i0);
+        rc = sel_chunk_enqueue(h, sl, sel, q_dev + (size_t)i0 * h->d, m, k, D_dev + (size_t)i0 * k, I_dev + (size_t)i0 * k, st);
+        if (rc) return rc;
+    }
+    return ISE_OK;
+}
+
+extern "C" int ise_index_search_sel_device(ise_index_t* h, const float* q_dev, int64_t nq, int k, const ise_selector_t* sel,
+                                           float* D_dev, int64_t* I_dev, void* stream) {
+    int rc = check_search_args(h, q_dev, nq, k);
+    if (rc) return rc;
+    if (!sel) return fail(ISE_E_INVALID, "selector is NULL");
+    if (nq > 0 && (!D_dev || !I_dev)) return fail(ISE_E_INVALID, "output pointer is NULL");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    if (nq == 0) return selector_check_locked(h, sel);
+    DeviceGuard gd(h->device);
+    return search_sel_enqueue(h, sel, q_dev, nq, k, D_dev, (long long*)I_dev, (hipStream_t)stream);
+}
+
+// blocks; on one of the host contexts, never through the request combiner: a filtered call is not merged with others
+extern "C" int ise_index_search_sel_host(ise_index_t* h, const float* q, int64_t nq, int k, const ise_selector_t* sel,
+                                         float* D, int64_t* I) {
+    int rc = check_search_args(h, q, nq, k);
+    if (rc) return rc;
+    if (!sel) return fail(ISE_E_INVALID, "selector is NULL");
+    if (nq > 0 && (!D || !I)) return fail(ISE_E_INVALID, "output pointer is NULL");
+    if (nq == 0) {
+        std::lock_guard<std::mutex> lk(h->mu_);
+        return selector_check_locked(h, sel);
+    }
+    DeviceGuard gd(h->device);
+    ise_index::HostCtx* c = acquire_ctx(h);
+    struct Rel { ise_index* h; ise_index::HostCtx* c; ~Rel() { release_ctx(h, c); } } rel{h, c};
+    if (!c->stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    const long long batch = 1024;
+    const size_t qe = (size_t)std::min<long long>(nq, batch) * h->d;
+    const size_t oe = (size_t)std::min<long long>(nq, batch) * k;
+    if (qe > c->q_elems) {
+        if (c->q_dev) (void)hipFree(c->q_dev);
+        c->q_dev = nullptr; c->q_elems = 0;
+        HIP_TRY(hipMalloc(&c->q_dev, qe * sizeof(float)));
+        c->q_elems = qe;
+    }
+    if (oe > c->out_elems) {
+        if (c->D_dev) (void)hipFree(c->D_dev);
+        if (c->I_dev) (void)hipFree(c->I_dev);
+        c->D_dev = nullptr; c->I_dev = nullptr; c->out_elems = 0;
+        HIP_TRY(hipMalloc(&c->D_dev, oe * sizeof(float)));
+        HIP_TRY(hipMalloc(&c->I_dev, oe * sizeof(long long)));
+        c->out_elems = oe;
+    }
+    for (long long i0 = 0; i0 < nq; i0 += batch) {
+        const long long m = std::min<long long>(batch, nq - i0);
+        HIP_TRY(hipMemcpyAsync(c->q_dev, q + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice,
+                               c->stream));
+        {
+            std::lock_guard<std::mutex> lk(h->mu_);
+            rc = search_sel_enqueue(h, sel, c->q_dev, m, k, c->D_dev, c->I_dev, c->stream);
+        }
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(D + (size_t)i0 * k, c->D_dev, (size_t)m * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(I + (size_t)i0 * k, c->I_dev, (size_t)m * k * sizeof(long long), hipMemcpyDeviceToHost,
+                               c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return ISE_OK;
+}
+
+extern "C" int ise_index_sel_stats(ise_index_t* h, uint64_t* out3) {
+    if (!h || !out3) return fail(ISE_E_INVALID, "NULL argument");
+    {
+        std::lock_guard<std::mutex> lk(h->mu_);
+        out3[0] = h->sel_batches;
+        out3[1] = h->sel_passes;
+    }
+    std::lock_guard<std::mutex> lk(h->rg_mu);
+    out3[2] = h->sel_range_batches;
     return ISE_OK;
 }
 
@@ -2385,6 +2801,7 @@ static int remove_runs_locked(ise_index* h, const std::vector<RemoveRun>& runs, 
         HIP_TRY(hipMemsetAsync(h->bmeta + n_new, 0, (size_t)removed * sizeof(uint32_t), st));
     }
     h->n = n_new;
+    h->row_epoch++;  // rows were renumbered: selectors made before are stale
     h->norms_rows = meta ? n_new : 0;  // 0: retaken with the shadows at the next search (prepare_shift_locked)
     // mu stays: results never depend on it.  An unpinned index that has shrunk below three quarters of the rows mu
     // was taken from refreshes it at the next search (the mirror of "grown by a quarter"); a pinned one stays pinned

@@ -25,6 +25,10 @@
 //                    and sizes the output;
 //   range_compact    copies the segments to their offsets -- or, when a segment overflowed, pass 2 (mode 1)
 //                    reads the index again and writes every hit straight to its now exact offset.
+//
+// The query staging, a tile's dot products and a pair's value are device functions (range_stage_queries,
+// range_tile_dots, range_pair_value) that the masked k-best pass of ise_sel_scan.hpp calls too; MASK instantiations of
+// this kernel restrict the pass to a selector's window and bitmap.
 #pragma once
 #include "ise_common.hpp"
 #include "ise_exact.hpp"
@@ -52,27 +56,35 @@ struct RangeParams {
     const long long* segoff;  // [nq][nseg] offset of a segment within its query (mode 1)
     float* D;             // [total] (mode 1)
     long long* I;         // [total] (mode 1)
+    // MASK instantiations (a selector, ise_sel_scan.hpp): one bit per row, and the first tile of the selector's
+    // window -- blocks then split the tiles [tile0, tiles_total)
+    const uint32_t* bits;
+    int tile0;
 };
 
 __host__ __device__ constexpr size_t range_lds_bytes(int S) {
     return (size_t)S * 4 /* mus */ + (size_t)16 * S * 4 /* qs */ + 16 * 4 /* xn */;
 }
 
-template <int CH, bool BF16, bool SHIFT>
-__global__ __launch_bounds__(RANGE_W * 64) void range_scan_kernel(const RangeParams p) {
-    static_assert(!(BF16 && SHIFT), "the shift is applied to fp32 rows only");
-    constexpr int W = RANGE_W;
-    extern __shared__ __align__(16) unsigned char smem_rg[];
-    const int S = p.qs_stride;
-    float* mus = reinterpret_cast<float*>(smem_rg);  // [S]
-    float* qs = mus + S;                             // [16][S]
-    float* xn = qs + 16 * S;                         // [16]
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 15, g = lane >> 4;
-    const int q0 = (p.g0 + (int)blockIdx.y) * 16;
-    const int nqt = min(16, p.nq - q0);
-    const bool l2 = p.metric == ISE_METRIC_L2;
+// ---- the pieces the range pass shares with the masked k-best pass (ise_sel_scan.hpp): both call these, so a
+// (query, row) pair has the same bits in either
+// the half-word of mask bits of one 16-row tile (bit r: row 16 tile + r)
+__device__ __forceinline__ uint32_t sel_tile_bits(const uint32_t* bits, int tile) {
+    return (bits[tile >> 1] >> ((tile & 1) << 4)) & 0xFFFFu;
+}
 
+// what the staging reads of an index and a query batch
+struct RangeStage {
+    const float* q;   // [nq][dp] float32 queries, zero padded to dp
+    const float* mu;  // [dp] (SHIFT)
+    int d, dp, S, tpr, vec_q;
+};
+
+// Query staging of the 16 queries from q0 (nqt of them real) into mus [S] | qs [16][S] | xn [16].  No barrier.
+template <bool BF16, bool SHIFT>
+__device__ __forceinline__ void range_stage_queries(const RangeStage p, int q0, int nqt, float* mus, float* qs, float* xn) {
+    const int tid = threadIdx.x;
+    const int S = p.S;
     // ---- query staging: the streaming kernel's values and |x|^2 summation order (ise_scan.hpp, step 2):
     // TPR threads per query row, thread t taking 16-byte slots (vector path) or 4-byte units (scalar path)
     // t, t + TPR, ..., then an xor butterfly over the TPR threads
@@ -149,15 +161,79 @@ __global__ __launch_bounds__(RANGE_W * 64) void range_scan_kernel(const RangePar
         for (int o = TPR / 2; o > 0; o >>= 1) sn += __shfl_xor(sn, o);
         if (t == 0) xn[cc] = sn;
     }
+}
+
+// the scan's dot products for (row 16 tile + 4 g + j, query c): two accumulator chains, k-steps in order
+template <int CH, bool BF16, bool SHIFT>
+__device__ __forceinline__ f32x4 range_tile_dots(const void* xb, int tile, int row_slots, int c, int g, const float* qrow,
+                                                 const float* mus) {
+    const int nsteps = row_slots >> 2;
+    f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const char* base = static_cast<const char*>(xb) + ((((size_t)tile * 16 + c) * row_slots + g) << 4);
+    for (int s0 = 0; s0 < nsteps; s0 += CH) {
+        f32x4 a[CH];
+#pragma unroll
+        for (int s = 0; s < CH; s++) a[s] = *reinterpret_cast<const f32x4*>(base + 64 * (s0 + s));
+#pragma unroll
+        for (int s = 0; s < CH; s++) {
+            const f32x4 b = *reinterpret_cast<const f32x4*>(qrow + 16 * (s0 + s));
+            if (BF16) {
+                const bf16x8 av = __builtin_bit_cast(bf16x8, a[s]), bv = __builtin_bit_cast(bf16x8, b);
+                if (s & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc1, 0, 0, 0);
+                else acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc0, 0, 0, 0);
+            } else {
+                f32x4 as = a[s];
+                if (SHIFT) as = as - *reinterpret_cast<const f32x4*>(mus + 4 * g + 16 * (s0 + s));
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(as[0], b[0], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(as[1], b[1], acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(as[2], b[2], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(as[3], b[3], acc1, 0, 0, 0);
+            }
+        }
+    }
+    return acc0 + acc1;
+}
+
+// one pair's value as both passes test it.  L2: the float32 rows' lower bound lo (SHIFT), or the expanded form
+// clamped at 0 (NaN kept; Faiss: if (dis < 0) dis = 0); inner product: the dot product
+template <bool SHIFT>
+__device__ __forceinline__ float range_pair_value(bool l2, float beta, float xq_n, float yn, float dot) {
+    if (l2) {
+        const float tt = xq_n + yn;
+        const float sc = tt - 2.f * dot;
+        if (SHIFT) return l2_lower_bound(beta, tt, sc);
+        return sc < 0.f ? 0.f : sc;
+    }
+    return dot;
+}
+
+// MASK: restricted to a selector (ise_sel_scan.hpp) -- the blocks split the tiles of its window [tile0, tiles_total), a
+// tile whose 16 mask bits are all zero is not loaded, and a row is a hit only if its bit is set.  The segment layout
+// and the ascending order within a segment are those of the unmasked pass.
+template <int CH, bool BF16, bool SHIFT, bool MASK = false>
+__global__ __launch_bounds__(RANGE_W * 64) void range_scan_kernel(const RangeParams p) {
+    static_assert(!(BF16 && SHIFT), "the shift is applied to fp32 rows only");
+    constexpr int W = RANGE_W;
+    extern __shared__ __align__(16) unsigned char smem_rg[];
+    const int S = p.qs_stride;
+    float* mus = reinterpret_cast<float*>(smem_rg);  // [S]
+    float* qs = mus + S;                             // [16][S]
+    float* xn = qs + 16 * S;                         // [16]
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 15, g = lane >> 4;
+    const int q0 = (p.g0 + (int)blockIdx.y) * 16;
+    const int nqt = min(16, p.nq - q0);
+    const bool l2 = p.metric == ISE_METRIC_L2;
+
+    range_stage_queries<BF16, SHIFT>(RangeStage{p.q, p.mu, p.d, p.dp, S, p.tpr, p.vec_q}, q0, nqt, mus, qs, xn);
     __syncthreads();
 
     // ---- this wave's contiguous sub-slab of the block's row tiles
-    const int t0 = blockIdx.x * p.tiles_per_block;
+    const int t0 = (MASK ? p.tile0 : 0) + blockIdx.x * p.tiles_per_block;
     const int t1 = min(t0 + p.tiles_per_block, p.tiles_total);
     const int per_wave = (max(t1 - t0, 0) + W - 1) / W;
     const int tw0 = t0 + w * per_wave, tw1 = min(tw0 + per_wave, t1);
     const int seg = blockIdx.x * W + w;
-    const int nsteps = p.row_slots >> 2;
     const float* qrow = qs + c * S + 4 * g;
     const float xq_n = xn[c];
     const bool qok = c < nqt;
@@ -179,31 +255,12 @@ __global__ __launch_bounds__(RANGE_W * 64) void range_scan_kernel(const RangePar
     };
 
     for (int tile = tw0; tile < tw1; tile++) {
-        // the scan's dot products for (row 16 tile + 4 g + j, query c): two accumulator chains, k-steps in order
-        f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const char* base = static_cast<const char*>(p.xb) + ((((size_t)tile * 16 + c) * p.row_slots + g) << 4);
-        for (int s0 = 0; s0 < nsteps; s0 += CH) {
-            f32x4 a[CH];
-#pragma unroll
-            for (int s = 0; s < CH; s++) a[s] = *reinterpret_cast<const f32x4*>(base + 64 * (s0 + s));
-#pragma unroll
-            for (int s = 0; s < CH; s++) {
-                const f32x4 b = *reinterpret_cast<const f32x4*>(qrow + 16 * (s0 + s));
-                if (BF16) {
-                    const bf16x8 av = __builtin_bit_cast(bf16x8, a[s]), bv = __builtin_bit_cast(bf16x8, b);
-                    if (s & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc1, 0, 0, 0);
-                    else acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc0, 0, 0, 0);
-                } else {
-                    f32x4 as = a[s];
-                    if (SHIFT) as = as - *reinterpret_cast<const f32x4*>(mus + 4 * g + 16 * (s0 + s));
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(as[0], b[0], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(as[1], b[1], acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(as[2], b[2], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(as[3], b[3], acc1, 0, 0, 0);
-                }
-            }
+        uint32_t tb = 0xFFFFu;
+        if (MASK) {
+            tb = __builtin_amdgcn_readfirstlane(sel_tile_bits(p.bits, tile));  // wave-uniform, before the tile's loads
+            if (tb == 0u) continue;
         }
-        const f32x4 dot = acc0 + acc1;
+        const f32x4 dot = range_tile_dots<CH, BF16, SHIFT>(p.xb, tile, p.row_slots, c, g, qrow, mus);
         const f32x4 yn = *reinterpret_cast<const f32x4*>(p.norms + (size_t)tile * 16 + 4 * g);
         const long long row0 = (long long)tile * 16 + 4 * g;
         float val[4];
@@ -211,20 +268,9 @@ __global__ __launch_bounds__(RANGE_W * 64) void range_scan_kernel(const RangePar
         u64 any = 0;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            bool pass;
-            if (l2) {
-                const float tt = xq_n + yn[j];
-                const float sc = tt - 2.f * dot[j];
-                if (SHIFT) {
-                    val[j] = l2_lower_bound(p.beta, tt, sc);
-                } else {
-                    val[j] = sc < 0.f ? 0.f : sc;  // keeps NaN (Faiss: if (dis < 0) dis = 0)
-                }
-                pass = val[j] < p.radius;  // false on NaN
-            } else {
-                val[j] = dot[j];
-                pass = val[j] > p.radius;
-            }
+            val[j] = range_pair_value<SHIFT>(l2, p.beta, xq_n, yn[j], dot[j]);
+            bool pass = l2 ? val[j] < p.radius : val[j] > p.radius;  // false on NaN
+            if (MASK) pass = pass && ((tb >> (4 * g + j)) & 1u);
             m[j] = __ballot(pass && qok && row0 + j < p.n);
             any |= m[j];
         }
@@ -263,7 +309,7 @@ __global__ __launch_bounds__(RANGE_W * 64) void range_scan_kernel(const RangePar
 
 // per query (block y): exclusive scan of the segment counts -> segoff, the query's total -> tot; a segment
 // past its capacity raises the overflow flag (plain stores of 1)
-__global__ __launch_bounds__(256) void range_offsets_kernel(const unsigned* cnt, int nseg, int cap, long long* segoff,
+static __global__ __launch_bounds__(256) void range_offsets_kernel(const unsigned* cnt, int nseg, int cap, long long* segoff,
                                                             long long* tot, unsigned* overflow) {
     __shared__ long long part[256];
     const int q = blockIdx.x, tid = threadIdx.x;
@@ -294,7 +340,7 @@ __global__ __launch_bounds__(256) void range_offsets_kernel(const unsigned* cnt,
 }
 
 // lims[0] = 0, lims[i + 1] = lims[i] + tot[i] (one block)
-__global__ __launch_bounds__(1024) void range_lims_kernel(const long long* tot, int nq, long long* lims) {
+static __global__ __launch_bounds__(1024) void range_lims_kernel(const long long* tot, int nq, long long* lims) {
     __shared__ long long part[1024];
     const int tid = threadIdx.x;
     const int per = (nq + 1023) / 1024;
@@ -318,7 +364,7 @@ __global__ __launch_bounds__(1024) void range_lims_kernel(const long long* tot, 
 }
 
 // staged segments -> their offsets: one wave per segment (grid.x: segments / 4, grid.y: queries)
-__global__ __launch_bounds__(256) void range_compact_kernel(const unsigned* cnt, const float* sD, const uint32_t* sI,
+static __global__ __launch_bounds__(256) void range_compact_kernel(const unsigned* cnt, const float* sD, const uint32_t* sI,
                                                             const long long* lims, const long long* segoff, int nseg,
                                                             int cap, float* D, long long* I) {
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6), q = blockIdx.y, lane = threadIdx.x & 63;

@@ -116,15 +116,20 @@ def remove_images(paths) -> int:
     return n
 
 
-def run_image_query(image_features, n_images, normalize=False):
+def _search(x, n_images, params):
+    # params (faiss.SearchParameters(sel=...)): handed through to index.search only when given
+    return index.search(x, n_images) if params is None else index.search(x, n_images, params=params)
+
+
+def run_image_query(image_features, n_images, normalize=False, params=None):
     """backend/engine.py:46-65: tensor -> (1, d) float32, optional normalize_L2,
-    index.search, ravel, id -> path -> thumbnail."""
+    index.search, ravel, id -> path -> thumbnail.  ``params``: optional faiss.SearchParameters(sel=...)."""
     if isinstance(image_features, torch.Tensor):
         image_features = image_features.detach().cpu().numpy().reshape(1, -1)
     image_features = np.ascontiguousarray(image_features, dtype=np.float32)
     if normalize:
         faiss.normalize_L2(image_features)
-    distances, indices = index.search(image_features, n_images)
+    distances, indices = _search(image_features, n_images, params)
     distances = distances.ravel().tolist()
     indices = indices.ravel().tolist()
     predictions = []
@@ -135,15 +140,15 @@ def run_image_query(image_features, n_images, normalize=False):
     return predictions
 
 
-def run_image_queries(features, n_images, normalize=False):
+def run_image_queries(features, n_images, normalize=False, params=None):
     """Batched form (new capability): (nq, d) features -> list of per-query predictions
-    with one index.search call."""
+    with one index.search call.  ``params``: optional faiss.SearchParameters(sel=...)."""
     if isinstance(features, torch.Tensor):
         features = features.detach().cpu().numpy()
     features = np.ascontiguousarray(features, dtype=np.float32).reshape(len(features), -1)
     if normalize:
         faiss.normalize_L2(features)
-    D, I = index.search(features, n_images)
+    D, I = _search(features, n_images, params)
     return [[(float(d), get_image(images_paths[i]), str(images_paths[i])) for d, i in zip(dr, ir)]
             for dr, ir in zip(D.tolist(), I.tolist())]
 

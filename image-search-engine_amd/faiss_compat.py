@@ -15,6 +15,11 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          Not: the other rows keep their order and are renumbered (in-place
                                          compaction on the device, csrc/ise_remove.hpp); never called by the reference
     IndexIDMap(index).add_with_ids       Faiss's id-mapping wrapper, so that ids handed out earlier survive a removal
+    SearchParameters(sel=sel)            ``search`` / ``range_search`` / ``search_torch(..., params=)``: only the rows an
+                                         IDSelector names (for IndexIDMap: external ids) -- one masked pass per 16
+                                         queries that skips tiles without a selected row (csrc/ise_sel_scan.hpp); never
+                                         called by the reference.  ``index.make_selector(sel)`` (extension) keeps the
+                                         device bitmap for reuse
     normalize_L2(x)                      backend/utils.py:303, backend/engine.py:53
     write_index / read_index             backend/indexer.py:59, backend/engine.py:116 (IndexFlat and IndexIDMap)
     Kmeans(...).index / .centroids       backend/kmeans_faiss.py:29-44 (assignment only)
@@ -142,6 +147,86 @@ class IDSelectorNot(IDSelector):
 
     def members(self, ids) -> np.ndarray:
         return ~self.sel.members(ids)
+
+
+class SearchParameters:
+    """faiss.SearchParameters: ``sel`` is an ``IDSelector`` (or a ``DeviceSelector`` made by
+    ``IndexFlat.make_selector``, an extension), or None for an unfiltered search."""
+
+    def __init__(self, sel=None):
+        if sel is not None and not isinstance(sel, (IDSelector, DeviceSelector)):
+            raise TypeError(f"SearchParameters.sel must be an IDSelector or a DeviceSelector, not {type(sel).__name__}")
+        self.sel = sel
+
+
+def _params_sel(params):
+    """The selector of a ``params=`` argument, or None for today's unfiltered path."""
+    if params is None:
+        return None
+    if not isinstance(params, SearchParameters):
+        raise TypeError(f"params must be a SearchParameters, not {type(params).__name__}")
+    return params.sel
+
+
+def _bitmap_words(members: np.ndarray) -> np.ndarray:
+    """bool (n,) -> uint32 words, bit ``r & 31`` of word ``r >> 5``, ceil(n / 32) of them."""
+    members = np.asarray(members, dtype=bool).reshape(-1)
+    nw = (members.size + 31) // 32
+    by = np.zeros(4 * nw, dtype=np.uint8)
+    packed = np.packbits(members, bitorder="little")
+    by[:packed.size] = packed
+    return by.view("<u4")
+
+
+def lower_selector(sel: IDSelector, ntotal: int):
+    """How a selector reaches the device (include/ise_knn.h): ``("range", imin, imax)``, ``("ids", ids, invert)`` -- the
+    ids travel, not a bitmap -- or ``("bitmap", words)`` for everything else."""
+    if isinstance(sel, IDSelectorRange):
+        return ("range", sel.imin, sel.imax)
+    if isinstance(sel, IDSelectorBatch):
+        return ("ids", sel.ids, 0)
+    if isinstance(sel, IDSelectorNot) and isinstance(sel.sel, IDSelectorBatch):
+        return ("ids", sel.sel.ids, 1)
+    if not isinstance(sel, IDSelector):
+        raise TypeError(f"expected an IDSelector, not {type(sel).__name__}")
+    return ("bitmap", _bitmap_words(sel.members(np.arange(int(ntotal), dtype=np.int64))))
+
+
+class DeviceSelector:
+    """A selector on an index's device (``IndexFlat.make_selector``; an extension, Faiss has no counterpart): the
+    bitmap, its row window and counts.  Valid while the index keeps its rows: after ``add``, ``remove_ids`` or
+    ``reset`` a search with it raises ``IseError``."""
+
+    def __init__(self, index: "IndexFlat", lowered):
+        self.index = index
+        self._s = ctypes.c_void_p()
+        kind = lowered[0]
+        if kind == "range":
+            _n.check(_n.lib.ise_selector_create_range(index._h, int(lowered[1]), int(lowered[2]), ctypes.byref(self._s)))
+        elif kind == "ids":
+            ids = _ids_array(lowered[1])
+            _n.check(_n.lib.ise_selector_create_ids(index._h, ids.ctypes.data, ids.size, int(lowered[2]),
+                                                    ctypes.byref(self._s)))
+        else:
+            words = np.ascontiguousarray(lowered[1], dtype="<u4")
+            _n.check(_n.lib.ise_selector_create_bitmap(index._h, words.ctypes.data, words.size, ctypes.byref(self._s)))
+
+    def close(self) -> None:
+        s = getattr(self, "_s", None)
+        if s is not None and s.value:
+            try:
+                _n.lib.ise_selector_destroy(s)
+            except Exception:  # interpreter shutdown
+                pass
+            s.value = None
+
+    __del__ = close
+
+    def info(self) -> dict:
+        out = (ctypes.c_int64 * 5)()
+        _n.check(_n.lib.ise_selector_info(self._s, out))
+        return {"ntotal": int(out[0]), "selected": int(out[1]), "window": (int(out[2]), int(out[3])),
+                "tiles": int(out[4])}
 
 
 def _runs_to_ids(runs: np.ndarray) -> np.ndarray:
@@ -357,13 +442,44 @@ class IndexFlat:
         _n.check(_n.lib.ise_index_assign_device(self._h, x.data_ptr(), n, D.data_ptr(), I.data_ptr(), st))
         return D, I
 
-    def search(self, x, k: int):
+    # -- selector-filtered search (faiss.SearchParameters(sel=...))
+    def make_selector(self, sel) -> DeviceSelector:
+        """Extension (not in Faiss): ``sel`` lowered to a device object that can be reused across ``search``,
+        ``range_search`` and ``search_torch`` calls through ``SearchParameters(sel=...)`` until the index changes."""
+        return DeviceSelector(self, lower_selector(sel, self.ntotal))
+
+    def _with_selector(self, sel, fn):
+        """``fn(handle)`` with the device selector of ``sel``; one built here is destroyed before returning."""
+        if isinstance(sel, DeviceSelector):
+            return fn(sel._s)
+        ds = self.make_selector(sel)
+        try:
+            return fn(ds._s)
+        finally:
+            ds.close()
+
+    def sel_stats(self) -> dict:
+        """Filtered search batches, masked passes launched, filtered range batches (include/ise_knn.h,
+        ise_index_sel_stats)."""
+        out = (ctypes.c_uint64 * 3)()
+        _n.check(_n.lib.ise_index_sel_stats(self._h, out))
+        return {"sel_batches": int(out[0]), "sel_passes": int(out[1]), "sel_range_batches": int(out[2])}
+
+    def search(self, x, k: int, params=None):
         """(D float32 (nq,k), I int64 (nq,k)), fresh arrays.  L2: squared distance
-        ascending; IP: descending; unfilled slots -1 / +-FLT_MAX."""
+        ascending; IP: descending; unfilled slots -1 / +-FLT_MAX.  ``params=SearchParameters(sel=...)``: among the
+        rows the selector names only."""
         x = _as_rows(x, self.d)
         k = int(k)
         assert k > 0
         nq = x.shape[0]
+        sel = _params_sel(params)
+        if sel is not None:
+            D = np.empty((nq, k), dtype=np.float32)
+            I = np.empty((nq, k), dtype=np.int64)
+            self._with_selector(sel, lambda s: _n.check(_n.lib.ise_index_search_sel_host(
+                self._h, x.ctypes.data, nq, k, s, D.ctypes.data, I.ctypes.data)))
+            return D, I
         if self._assign_applies(nq, k):
             import torch
 
@@ -381,15 +497,20 @@ class IndexFlat:
         _n.check(_n.lib.ise_index_search_host(self._h, x.ctypes.data, nq, k, D.ctypes.data, I.ctypes.data))
         return D, I
 
-    def range_search(self, x, radius: float):
+    def range_search(self, x, radius: float, params=None):
         """(lims uint64 (nq+1,), D float32, I int64), fresh arrays, as Faiss returns them: query i's rows are
         ``I[lims[i]:lims[i+1]]`` in ascending id order, every row with D < radius (L2) or D > radius (inner
-        product), D as ``search`` reports it."""
+        product), D as ``search`` reports it.  ``params=SearchParameters(sel=...)``: among the selected rows only."""
         x = _as_rows(x, self.d)
         nq = x.shape[0]
         res = ctypes.c_void_p()
-        _n.check(_n.lib.ise_index_range_search_host(self._h, x.ctypes.data, nq, ctypes.c_float(float(radius)),
-                                                    ctypes.byref(res)))
+        sel = _params_sel(params)
+        if sel is not None:
+            self._with_selector(sel, lambda s: _n.check(_n.lib.ise_index_range_search_sel_host(
+                self._h, x.ctypes.data, nq, ctypes.c_float(float(radius)), s, ctypes.byref(res))))
+        else:
+            _n.check(_n.lib.ise_index_range_search_host(self._h, x.ctypes.data, nq, ctypes.c_float(float(radius)),
+                                                        ctypes.byref(res)))
         try:
             n = ctypes.c_int64()
             lp, dp_, ip = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
@@ -407,9 +528,10 @@ class IndexFlat:
             _n.lib.ise_range_result_destroy(res)
         return lims, D, I
 
-    def search_torch(self, xq, k: int):
+    def search_torch(self, xq, k: int, params=None):
         """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out, enqueued on
-        the current torch stream (no host synchronisation)."""
+        the current torch stream (no host synchronisation).  ``params=SearchParameters(sel=...)`` as ``search``; a
+        selector that is not a ``DeviceSelector`` is built and destroyed here, which waits for the device."""
         import torch
 
         assert xq.is_cuda and xq.dtype == torch.float32 and xq.dim() == 2 and xq.shape[1] == self.d
@@ -418,6 +540,14 @@ class IndexFlat:
         D = torch.empty((nq, k), dtype=torch.float32, device=xq.device)
         I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
         st = torch.cuda.current_stream(xq.device).cuda_stream
+        sel = _params_sel(params)
+        if sel is not None:
+            def run(s):
+                with self._lock:
+                    _n.check(_n.lib.ise_index_search_sel_device(self._h, xq.data_ptr(), nq, int(k), s, D.data_ptr(),
+                                                                I.data_ptr(), st))
+            self._with_selector(sel, run)
+            return D, I
         with self._lock:
             _n.check(_n.lib.ise_index_search_device(self._h, xq.data_ptr(), nq, int(k), D.data_ptr(),
                                                     I.data_ptr(), st))
@@ -478,6 +608,23 @@ class IndexFlatIP(IndexFlat):
         super().__init__(d, METRIC_INNER_PRODUCT, device, storage)
 
 
+class _RowMask(IDSelector):
+    """Rows by a bool mask (IndexIDMap's external-id selectors, already evaluated against ``id_map``)."""
+
+    def __init__(self, mask: np.ndarray):
+        self.mask = np.asarray(mask, dtype=bool).reshape(-1)
+
+    def is_member(self, i: int) -> bool:
+        return 0 <= int(i) < self.mask.size and bool(self.mask[int(i)])
+
+    def members(self, ids) -> np.ndarray:
+        ids = _ids_array(ids)
+        ok = (ids >= 0) & (ids < self.mask.size)
+        out = np.zeros(ids.shape, dtype=bool)
+        out[ok] = self.mask[ids[ok]]
+        return out
+
+
 class IndexIDMap:
     """faiss.IndexIDMap over a flat index: rows carry the caller's 64-bit ids, which survive ``remove_ids`` (the
     sub-index renumbers its rows; ``id_map[row]`` follows).  The mapping is host numpy, off the hot path."""
@@ -508,12 +655,21 @@ class IndexIDMap:
         out[ok] = self.id_map[I[ok]]
         return out
 
-    def search(self, x, k: int):
-        D, I = self.index.search(x, k)
+    def _row_params(self, params):
+        """A selector over EXTERNAL ids -> one over rows (a bitmap from ``sel.members(id_map)``)."""
+        sel = _params_sel(params)
+        if sel is None:
+            return None
+        if isinstance(sel, DeviceSelector):
+            raise TypeError("IndexIDMap takes an IDSelector over external ids, not a DeviceSelector over rows")
+        return SearchParameters(sel=_RowMask(sel.members(self.id_map)))
+
+    def search(self, x, k: int, params=None):
+        D, I = self.index.search(x, k, params=self._row_params(params))
         return D, self._map(I)
 
-    def range_search(self, x, radius: float):
-        lims, D, I = self.index.range_search(x, radius)
+    def range_search(self, x, radius: float, params=None):
+        lims, D, I = self.index.range_search(x, radius, params=self._row_params(params))
         return lims, D, self._map(I)
 
     def remove_ids(self, sel) -> int:

@@ -200,6 +200,54 @@ int ise_index_remove_last_timing(ise_index_t* h, float* ms, uint64_t* bytes);
 int ise_index_search_device(ise_index_t* h, const float* q_dev, int64_t nq, int k,
                             float* D_dev, int64_t* I_dev, void* stream);
 
+/* Selector-filtered search: index.search(x, k, params=faiss.SearchParameters(sel=sel)) and the same for
+ * range_search (Faiss IndexFlat with an IDSelector; the reference never filters: "similar images, but not the one I
+ * uploaded" or "only within this album" it would answer by oversampling and dropping on the host).
+ *
+ * ise_selector_t is a selector that lives on the index's device, so a serving loop that filters by the same category
+ * pays for it once: a bitmap of uint32 words, one bit per row (bit r & 31 of word r >> 5; a 16-row tile is one
+ * half-word), zero padded past ntotal like the pad rows of the index; with it the row WINDOW [r0, r1) from the first
+ * to the last selected row, the selected count and the number of non-empty 16-row tiles, all taken on the device at
+ * creation.  The constructors block:
+ *   ise_selector_create_range   rows [i0, i1) clipped to [0, ntotal); nothing is uploaded, the bitmap is filled on
+ *                               the device
+ *   ise_selector_create_ids     ids in any order; duplicates and ids outside [0, ntotal) are ignored, as in
+ *                               ise_index_remove_ids_host; invert != 0 selects every OTHER row.  The ids travel, not a
+ *                               bitmap: a device fill, then a scatter kernel
+ *   ise_selector_create_bitmap  the general form: n_words must be ceil(ntotal / 32); bits at or beyond ntotal are
+ *                               cleared
+ *   ise_selector_info           out5 = ntotal, selected count, r0, r1, non-empty tiles
+ *   ise_selector_destroy        NULL is a no-op
+ * A selector is valid only for the handle it was made from, and only while that handle's ntotal and ROW EPOCH are
+ * unchanged: the epoch is a per-handle counter that ise_index_reset, ise_index_remove_ids_host and
+ * ise_index_remove_range bump when they remove something (an add changes ntotal instead).  The filtered entry points
+ * return ISE_E_INVALID otherwise, with a message that says which of the two changed; they never read a stale bitmap.
+ *
+ * ise_index_search_sel_device / _host: the k best rows among the selected ones, D and I as ise_index_search_* report
+ * them (the same bits for the same (query, row) pair on the streaming path; ties by ascending id; unfilled slots
+ * -1 / +-FLT_MAX).  One masked pass per 16 queries over the tiles of the window, tiles without a selected row are not
+ * read (csrc/ise_sel_scan.hpp); float32 L2 results are exact by construction (every row whose lower bound does not
+ * prove it out is re-evaluated by direct difference), whatever the shift vector.  k > 32 repeats the pass per 32
+ * results.  An empty selection costs no pass.  The device form only enqueues; the host form blocks, is thread-safe
+ * and is never combined with other callers' requests.  sel == NULL, a foreign or stale selector, k out of range and
+ * NULL buffers return ISE_E_INVALID.
+ * ise_index_range_search_sel_host: ise_index_range_search_host restricted to the window and the mask.
+ * ise_index_sel_stats: out3[0] = filtered search batches, out3[1] = masked passes launched, out3[2] = filtered range
+ * batches. */
+typedef struct ise_selector ise_selector_t;
+int ise_selector_create_range(ise_index_t* h, int64_t i0, int64_t i1, ise_selector_t** out);
+int ise_selector_create_ids(ise_index_t* h, const int64_t* ids_host, int64_t n_ids, int invert, ise_selector_t** out);
+int ise_selector_create_bitmap(ise_index_t* h, const uint32_t* words_host, int64_t n_words, ise_selector_t** out);
+int ise_selector_info(const ise_selector_t* sel, int64_t* out5);
+int ise_selector_destroy(ise_selector_t* sel);
+int ise_index_search_sel_device(ise_index_t* h, const float* q_dev, int64_t nq, int k, const ise_selector_t* sel,
+                                float* D_dev, int64_t* I_dev, void* stream);
+int ise_index_search_sel_host(ise_index_t* h, const float* q, int64_t nq, int k, const ise_selector_t* sel, float* D,
+                              int64_t* I);
+int ise_index_range_search_sel_host(ise_index_t* h, const float* q, int64_t nq, float radius, const ise_selector_t* sel,
+                                    ise_range_result_t** out);
+int ise_index_sel_stats(ise_index_t* h, uint64_t* out3);
+
 /* Shard-local search for the multi-GPU path: writes nq x k
  * packed candidates, sorted best-first, suitable for one all-gather:
  *   key = (order-preserving uint32 image of the score) << 32 | (row + id_base)
