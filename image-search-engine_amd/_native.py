@@ -81,6 +81,19 @@ PROTOTYPES = [
     ("ise_index_search_sel_host", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
     ("ise_index_range_search_sel_host", _int, [_vp, _vp, _i64, ctypes.c_float, _vp, ctypes.POINTER(_vp)]),
     ("ise_index_sel_stats", _int, [_vp, _u64p]),
+    ("ise_binary_index_create", _int, [ctypes.POINTER(_vp), _int, _int]),
+    ("ise_binary_index_destroy", _int, [_vp]),
+    ("ise_binary_index_reset", _int, [_vp]),
+    ("ise_binary_index_info", _int, [_vp, ctypes.POINTER(_int), _i64p, ctypes.POINTER(_int)]),
+    ("ise_binary_index_add_host", _int, [_vp, _vp, _i64]),
+    ("ise_binary_index_add_device", _int, [_vp, _vp, _i64, _vp]),
+    ("ise_binary_index_reconstruct_host", _int, [_vp, _i64, _i64, _vp]),
+    ("ise_binary_index_search_host", _int, [_vp, _vp, _i64, _int, _vp, _vp]),
+    ("ise_binary_index_search_device", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
+    ("ise_binary_index_range_search_host", _int, [_vp, _vp, _i64, ctypes.c_int32, ctypes.POINTER(_vp)]),
+    ("ise_binary_range_result_get", _int, [_vp, _i64p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    ("ise_binary_range_result_destroy", _int, [_vp]),
+    ("ise_binary_index_stats", _int, [_vp, _u64p]),
     ("ise_refresh_env_knobs", _int, []),
     ("ise_comm_precheck", _int, [_int]),
     ("ise_comm_unique_id", _int, [_vp]),

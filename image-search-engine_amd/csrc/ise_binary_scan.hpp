@@ -1,0 +1,355 @@
+// ise_binary_scan.hpp -- kernels of the binary flat index (include/ise_knn.h, ise_binary_index_*): exact Hamming
+// kNN and range search over bit codes, faiss.IndexBinaryFlat.  DESIGN.md 4.10.
+//
+// Storage: a row is `ws` 64-bit words (ws = 1, or ceil(code_size / 8) rounded up to an even count so that every row
+// starts on 16 bytes); the bytes past code_size are zero in the rows AND in the staged queries, so they add nothing to
+// any distance.  Rows at or beyond n are masked by row number.
+//
+// Scan: a lane owns a row, a wave a tile of 64 consecutive rows, 16 queries per pass.  ws = 1: one coalesced 8-byte
+// load per lane, ws >= 2: 16-byte loads (a loop over 16-byte chunks for ws > 2).  The tile's queries are wave-uniform:
+// ws <= 2 holds them in scalar registers, loaded once per wave before the tile loop (BinQueries), larger rows stage
+// them once per block in LDS.  Distance = xor + popcount, accumulated in int.
+//
+// Selection: key = (u64)(dist + 1) << 32 | row (bin_key: the + 1 keeps every real key above 0) -- ascending key is
+// ascending (distance, id), so the "ties by ascending id" rule is key order.  Per wave and query: a threshold key (KEY_PAD until kp keys are held), lanes under it are
+// ballot-appended to an LDS buffer of BIN_CAP keys; when fewer than 64 slots are free, wave_cut (a windowed cut: a few
+// rounds, no sort) keeps between kp and kp + kp / 2 + 4 (at most BIN_CUT_MAX) of them and its cut key becomes the
+// threshold -- a window close to kp, so that the threshold is tight and a wave rarely cuts twice.  At the end the
+// block selects once per query: a wave takes every fourth query, gathers the four waves' buffers (at most 512 keys)
+// and wave_select writes the kp smallest, SORTED, as the block's list.  binary_merge_kernel walks the blocks' lists
+// (merge_waves, ise_merge.hpp) and writes int32 D / int64 I.  A pass yields at most BIN_KPASS results per query; a
+// larger k repeats the pass with lo = (last key found) + 1 as the smallest key admitted.
+#pragma once
+#include <climits>
+
+#include "ise_common.hpp"
+#include "ise_merge.hpp"
+#include "ise_select.hpp"
+
+#define BIN_QT 16     /* queries per pass */
+#define BIN_WAVES 4   /* waves per block */
+#define BIN_KPASS 32  /* results per query and pass */
+#define BIN_CAP 128   /* keys of a wave's buffer per query: two registers per lane in wave_cut */
+#define BIN_CUT_MAX 48 /* most keys a cut in the stream keeps (at least kp) */
+#define BIN_BUF_BYTES (BIN_WAVES * BIN_QT * BIN_CAP * 8)
+#define BIN_CNT_BYTES (BIN_WAVES * BIN_QT * 4)
+#define BIN_CHUNK_UNROLL 4 /* 16-byte chunks of a long row in flight per lane */
+#define BIN_MAX_WS 128 /* ISE_BINARY_MAX_BITS / 64 */
+#define BIN_LDS_MAX (BIN_BUF_BYTES + BIN_CNT_BYTES + BIN_QT * BIN_MAX_WS * 8)
+
+static_assert(BIN_CUT_MAX + 64 <= BIN_CAP && BIN_KPASS <= BIN_CUT_MAX, "a tile's 64 keys fit behind the kept ones");
+static_assert(BIN_WAVES * BIN_CAP == 512, "the block's selection holds the waves' buffers in eight registers per lane");
+static_assert(BIN_KPASS <= MERGE_FAST_K, "merge_waves serves every pass");
+
+// The tile's 16 queries as a wave reads them.  WT = 1, 2 (a row is one or two words): 16 or 32 words held in SCALAR
+// registers, loaded once per wave before the tile loop from wave-uniform addresses (qpad: 16 padded queries readable;
+// the words of queries the tile does not have are never used).  WT = 0: the block's LDS copy, [16][ws], staged once
+// per block, rows of queries the tile does not have zero; init ends with a block barrier.
+template <int WT>
+struct BinQueries {
+    u64 w[WT == 0 ? 1 : BIN_QT * WT];
+    const u64* lds;
+    __device__ __forceinline__ void init(u64* qs, const u64* __restrict__ qpad, int ws, int nqt) {
+        lds = qs;
+        if constexpr (WT == 0) {
+            for (int i = threadIdx.x; i < BIN_QT * ws; i += BIN_WAVES * 64) qs[i] = i < nqt * ws ? qpad[i] : 0ull;
+            __syncthreads();
+        } else {
+#pragma unroll
+            for (int i = 0; i < BIN_QT * WT; i++) w[i] = readlane_u64(qpad[i], 0);  // every lane is active here
+        }
+    }
+};
+
+// Hamming distance of one row (this lane's) to the 16 queries of the tile.
+template <int WT>
+__device__ __forceinline__ void hamming16(const u64* __restrict__ codes, int ws, long long row, bool valid,
+                                          const BinQueries<WT>& qr, int (&acc)[BIN_QT]) {
+    if constexpr (WT == 1) {
+        const u64 r = valid ? codes[row] : 0ull;
+#pragma unroll
+        for (int q = 0; q < BIN_QT; q++) acc[q] = __popcll(r ^ qr.w[q]);
+    } else if constexpr (WT == 2) {
+        ulonglong2 r = make_ulonglong2(0ull, 0ull);
+        if (valid) r = *reinterpret_cast<const ulonglong2*>(codes + row * 2);
+#pragma unroll
+        for (int q = 0; q < BIN_QT; q++) acc[q] = __popcll(r.x ^ qr.w[2 * q]) + __popcll(r.y ^ qr.w[2 * q + 1]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < BIN_QT; q++) acc[q] = 0;
+        const int nch = ws >> 1;
+        const ulonglong2* rp = reinterpret_cast<const ulonglong2*>(codes + (valid ? row : 0ll) * ws);
+        const ulonglong2* qp = reinterpret_cast<const ulonglong2*>(qr.lds);
+#pragma unroll BIN_CHUNK_UNROLL
+        for (int c = 0; c < nch; c++) {
+            const ulonglong2 r = rp[c];
+#pragma unroll
+            for (int q = 0; q < BIN_QT; q++) {
+                const ulonglong2 v = qp[q * nch + c];
+                acc[q] += __popcll(r.x ^ v.x) + __popcll(r.y ^ v.y);
+            }
+        }
+    }
+}
+
+// The candidate key: ascending key = ascending (distance, row).  The distance is stored + 1 so that every real key
+// lies strictly between 0 and KEY_PAD -- what wave_cut and wave_select (ise_select.hpp) require: (distance 0, row 0),
+// a query that is the index's first row, would otherwise be key 0, which wave_cut keeps but does not count.
+__device__ __forceinline__ u64 bin_key(int dist, long long row) { return ((u64)((uint32_t)dist + 1u) << 32) | (uint32_t)row; }
+__device__ __forceinline__ int bin_key_dist(u64 key) { return (int)((uint32_t)(key >> 32) - 1u); }
+
+struct BinScanParams {
+    const u64* codes;  // [n][ws]
+    int ws;
+    long long n;
+    const u64* qpad;  // the tile's queries, [16][ws] readable
+    int nqt, kp;      // queries of the tile (<= 16), results of this pass (<= BIN_KPASS)
+    const u64* lo;    // [nqt] smallest key admitted (KEY_PAD: the query is finished); null in the first pass: 0
+    u64* lists;       // [grid][16][BIN_KPASS]: one sorted list per block and query, KEY_PAD behind the last
+};
+
+template <int WT>
+__global__ __launch_bounds__(BIN_WAVES * 64) void binary_scan_kernel(const BinScanParams p) {
+    extern __shared__ __align__(16) unsigned char smem_bin[];
+    u64* buf = reinterpret_cast<u64*>(smem_bin);  // [BIN_WAVES][16][BIN_CAP]
+    int* cnts = reinterpret_cast<int*>(buf + BIN_WAVES * BIN_QT * BIN_CAP);  // [BIN_WAVES][16] keys held at the end
+    u64* qs = buf + BIN_WAVES * BIN_QT * BIN_CAP + BIN_CNT_BYTES / 8;  // WT == 0: [16][ws]
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    BinQueries<WT> qr;
+    qr.init(qs, p.qpad, p.ws, p.nqt);
+    u64* mybuf = buf + w * BIN_QT * BIN_CAP;
+    const int kp = p.kp;
+    // per-query state of the wave, query q in lane q: keys held, threshold (a new key must be below it), floor
+    int cnt_v = 0;
+    u64 thr_v = KEY_PAD;
+    const u64 lo_v = lane < p.nqt ? (p.lo ? p.lo[lane] : 0ull) : KEY_PAD;
+    const u64 lt_mask = (1ull << lane) - 1ull;
+
+    // query q's buffer is nearly full (more than BIN_CAP - 64 >= BIN_CUT_MAX keys): keep between kp and kmax of them,
+    // unsorted; everything kept is <= the cut key, which becomes the threshold
+    const int kmax = kp + kp / 2 + 4 < BIN_CUT_MAX ? kp + kp / 2 + 4 : BIN_CUT_MAX;
+    auto cut = [&](int q) {
+        const int cnt = __builtin_amdgcn_readlane(cnt_v, q);
+        u64 kk[2];
+#pragma unroll
+        for (int e = 0; e < 2; e++) kk[e] = lane + 64 * e < cnt ? mybuf[q * BIN_CAP + lane + 64 * e] : KEY_PAD;
+        u64 ckey = KEY_PAD;
+        const int nw = wave_cut<2>(kk, BIN_CAP, kp, kmax, mybuf + q * BIN_CAP, &ckey);
+        wave_lds_fence();
+        if (lane == q) {
+            cnt_v = nw;
+            thr_v = ckey;
+        }
+    };
+
+    const long long ntiles = (p.n + 63) >> 6;
+    for (long long t = (long long)blockIdx.x * BIN_WAVES + w; t < ntiles; t += (long long)gridDim.x * BIN_WAVES) {
+        const long long row = t * 64 + lane;
+        const bool valid = row < p.n;
+        int acc[BIN_QT];
+        hamming16<WT>(p.codes, p.ws, row, valid, qr, acc);
+#pragma unroll
+        for (int q = 0; q < BIN_QT; q++) {
+            if (q < p.nqt) {
+                const u64 key = bin_key(acc[q], row);
+                const bool c = valid && key >= readlane_u64(lo_v, q) && key < readlane_u64(thr_v, q);
+                const u64 m = __ballot(c);
+                if (m) {
+                    const int cnt = __builtin_amdgcn_readlane(cnt_v, q);
+                    if (c) mybuf[q * BIN_CAP + cnt + __popcll(m & lt_mask)] = key;
+                    if (lane == q) cnt_v += __popcll(m);
+                }
+            }
+        }
+        wave_lds_fence();
+        u64 need = __ballot(cnt_v > BIN_CAP - 64);  // the next tile may not fit
+        while (need) {
+            const int q = __ffsll((long long)need) - 1;
+            need &= need - 1;
+            cut(q);
+        }
+    }
+    if (lane < BIN_QT) cnts[w * BIN_QT + lane] = cnt_v;
+    __syncthreads();
+    // the waves' buffers -> the block's sorted list
+    for (int q = w; q < p.nqt; q += BIN_WAVES) {
+        u64 kk[2 * BIN_WAVES];
+#pragma unroll
+        for (int e = 0; e < 2 * BIN_WAVES; e++) {
+            const int sw = e >> 1, i = lane + 64 * (e & 1);
+            kk[e] = i < cnts[sw * BIN_QT + q] ? buf[(sw * BIN_QT + q) * BIN_CAP + i] : KEY_PAD;
+        }
+        u64* dst = p.lists + ((size_t)blockIdx.x * BIN_QT + q) * BIN_KPASS;
+        u64 kth_unused = 0;
+        const int nw = wave_select<2 * BIN_WAVES>(kk, BIN_WAVES * BIN_CAP, kp, dst, &kth_unused);
+        for (int i = nw + lane; i < kp; i += 64) dst[i] = KEY_PAD;
+    }
+}
+
+// One block per query of the tile: the k-way walk over the blocks' lists (merge_waves), then positions
+// [off, off + kp) of the query's results as int32 distance / int64 id (unfilled: INT32_MAX / -1) and the floor of
+// the next pass.
+struct BinMergeOut {
+    int* D;         // the tile's first query, [nqt][k]
+    long long* I;
+    u64* lo;        // [nqt]
+    int k, off;
+};
+static __global__ __launch_bounds__(MERGE_THREADS) void binary_merge_kernel(const MergeParams p, const BinMergeOut o) {
+    __shared__ MergeFastScratch fast;
+    __shared__ u64 res[MERGE_FAST_K];
+    const int lq = blockIdx.x;
+    merge_waves(p, p.lists + (size_t)lq * BIN_KPASS, fast, res);
+    const int t = threadIdx.x;
+    if (t < p.k) {
+        const u64 key = res[t];
+        const bool pad = key == KEY_PAD;
+        const size_t at = (size_t)lq * o.k + o.off + t;
+        o.D[at] = pad ? INT_MAX : bin_key_dist(key);
+        o.I[at] = pad ? -1ll : (long long)(uint32_t)key;
+        if (t == p.k - 1) o.lo[lq] = pad ? KEY_PAD : key + 1;
+    }
+}
+
+// ---- range search: every row with dist < radius, per query in ascending row order.  The rows are cut into S
+// consecutive SEGMENTS of seg_rows (a multiple of 64), one per wave, segment s = 4 * block + wave: the count pass
+// leaves counts[q][s], an exclusive scan over (q, s) gives every segment's first output slot, and the fill pass
+// writes a segment's matches tile by tile at ballot-prefix positions -- ascending id by construction, no sort.
+// The scan is two small kernels: binary_offsets_kernel, one block per query, scans the query's S counts;
+// binary_lims_kernel scans the queries' totals into lims.
+struct BinRangeParams {
+    const u64* codes;
+    int ws;
+    long long n;
+    const u64* qpad;  // the tile's queries
+    int nqt, radius;
+    long long seg_rows;
+    int S;
+    int* counts;            // count pass: the tile's first query, [nqt][S]
+    const long long* offs;  // fill pass: the same shape, first output slot of (q, s) within query q's results
+    const long long* lims;  // fill pass: the tile's first query, [nqt] first output slot of the query
+    int* D;                 // fill pass: the batch's results
+    long long* I;
+};
+
+template <int WT, bool FILL>
+__global__ __launch_bounds__(BIN_WAVES * 64) void binary_range_kernel(const BinRangeParams p) {
+    extern __shared__ __align__(16) unsigned char smem_bin[];
+    u64* qs = reinterpret_cast<u64*>(smem_bin);  // WT == 0: [16][ws]
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    BinQueries<WT> qr;
+    qr.init(qs, p.qpad, p.ws, p.nqt);
+    const int s = blockIdx.x * BIN_WAVES + w;
+    const long long r0 = (long long)s * p.seg_rows;
+    const long long r1 = r0 + p.seg_rows < p.n ? r0 + p.seg_rows : p.n;
+    const u64 lt_mask = (1ull << lane) - 1ull;
+    int cnt_v = 0;  // query q in lane q
+    u64 base_v = 0;
+    if (FILL && lane < p.nqt) base_v = (u64)(p.lims[lane] + p.offs[(size_t)lane * p.S + s]);
+    for (long long rb = r0; rb < r1; rb += 64) {
+        const long long row = rb + lane;
+        const bool valid = row < r1;
+        int acc[BIN_QT];
+        hamming16<WT>(p.codes, p.ws, row, valid, qr, acc);
+#pragma unroll
+        for (int q = 0; q < BIN_QT; q++) {
+            if (q < p.nqt) {
+                const bool c = valid && acc[q] < p.radius;
+                const u64 m = __ballot(c);
+                if (m) {
+                    if (FILL) {
+                        const u64 at = readlane_u64(base_v, q) + (u64)__popcll(m & lt_mask);
+                        if (c) {
+                            p.D[at] = acc[q];
+                            p.I[at] = row;
+                        }
+                        if (lane == q) base_v += (u64)__popcll(m);
+                    } else if (lane == q) {
+                        cnt_v += __popcll(m);
+                    }
+                }
+            }
+        }
+    }
+    if (!FILL && lane < p.nqt) p.counts[(size_t)lane * p.S + s] = cnt_v;
+}
+
+// inclusive scan over the block's threads (NT a multiple of 64, at most 1024); wsum: NT / 64 entries of LDS
+template <int NT>
+__device__ __forceinline__ long long block_inclusive_scan(long long v, long long* wsum) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long up = __shfl_up(v, o);
+        if (lane >= o) v += up;
+    }
+    if (lane == 63) wsum[w] = v;
+    __syncthreads();
+    long long before = 0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; i++) before += i < w ? wsum[i] : 0;
+    return v + before;
+}
+
+// block q: offs[q][s] = counts[q][0] + .. + counts[q][s - 1], totals[q] = the sum of the row.  S <= 4096.
+#define BIN_SCAN_THREADS 1024
+static_assert(MERGE_LISTS_MAX * BIN_WAVES <= 4 * BIN_SCAN_THREADS, "four segments per thread cover the largest grid");
+static __global__ __launch_bounds__(BIN_SCAN_THREADS) void binary_offsets_kernel(const int* __restrict__ counts, int S,
+                                                                                 long long* __restrict__ offs,
+                                                                                 long long* __restrict__ totals) {
+    __shared__ long long wsum[BIN_SCAN_THREADS / 64];
+    const int t = threadIdx.x;
+    const int* c = counts + (size_t)blockIdx.x * S;
+    long long* o = offs + (size_t)blockIdx.x * S;
+    int v[4];
+    long long sum = 0;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        v[e] = 4 * t + e < S ? c[4 * t + e] : 0;
+        sum += v[e];
+    }
+    long long run = block_inclusive_scan<BIN_SCAN_THREADS>(sum, wsum) - sum;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        if (4 * t + e < S) o[4 * t + e] = run;
+        run += v[e];
+    }
+    if (t == BIN_SCAN_THREADS - 1) totals[blockIdx.x] = run;
+}
+
+// lims[q] = totals[0] + .. + totals[q - 1] for q <= nq; nq <= 256, one block
+static __global__ __launch_bounds__(256) void binary_lims_kernel(const long long* __restrict__ totals, int nq,
+                                                                 long long* __restrict__ lims) {
+    __shared__ long long wsum[4];
+    const int t = threadIdx.x;
+    const long long v = t < nq ? totals[t] : 0;
+    const long long incl = block_inclusive_scan<256>(v, wsum);
+    if (t < nq) lims[t + 1] = incl;
+    if (t == 0) lims[0] = 0;
+}
+
+// n rows of code_size bytes -> n rows of ws words, the bytes past code_size zero (queries and device-side adds)
+static __global__ void binary_pad_kernel(const uint8_t* __restrict__ src, int code_size, u64* __restrict__ dst, int ws,
+                                         long long n) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * ws) return;
+    const long long r = i / ws;
+    const int wd = (int)(i % ws);
+    const uint8_t* s = src + r * code_size;
+    u64 v = 0;
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        const int j = wd * 8 + b;
+        if (j < code_size) v |= (u64)s[j] << (8 * b);
+    }
+    dst[i] = v;
+}
+
+// unfilled results (an empty index)
+static __global__ void binary_fill_kernel(int* D, long long* I, long long cnt) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cnt) {
+        D[i] = INT_MAX;
+        I[i] = -1ll;
+    }
+}

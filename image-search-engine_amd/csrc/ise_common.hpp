@@ -126,6 +126,20 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// makes `dev` the current device for a scope of host code
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: set once per (kernel, device),
 // race-free (one static LdsAttrOnce per launcher; the launch that follows is ordered behind the set by the mutex)
 struct LdsAttrOnce {

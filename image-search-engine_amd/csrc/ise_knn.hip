@@ -65,19 +65,6 @@ int ise_fail_(int code, const std::string& msg) { return fail(code, msg); }  // 
                         std::string(#expr) + ": " + hipGetErrorString(e_));                \
     } while (0)
 
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 struct ise_index {
     int d = 0, dp = 0, metric = ISE_METRIC_L2, device = 0;
     int storage = ISE_STORE_F32;  // element type of xb

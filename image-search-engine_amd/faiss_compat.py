@@ -23,6 +23,11 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
     normalize_L2(x)                      backend/utils.py:303, backend/engine.py:53
     write_index / read_index             backend/indexer.py:59, backend/engine.py:116 (IndexFlat and IndexIDMap)
     Kmeans(...).index / .centroids       backend/kmeans_faiss.py:29-44 (assignment only)
+    IndexBinaryFlat(d)                   Faiss's exact Hamming index over d-bit codes: ``add`` / ``search`` (int32 D) /
+                                         ``range_search`` / ``reconstruct_n`` / ``reset`` (csrc/ise_binary_scan.hpp); the
+                                         near-duplicate search the reference's DHASH method (backend/engine.py:82-91)
+                                         answers with a dict lookup of bit-identical hashes; never called by the reference
+    write_index_binary / read_index_binary   Faiss's names for IndexBinaryFlat files ("IBxF")
 
 All arithmetic runs on the MI355X through ``include/ise_knn.h``; there is no
 CPU path here.  Without the HIP library or without a GPU the constructors and
@@ -822,6 +827,189 @@ def read_index(path, device: int | None = None):
         if xb.shape[0]:
             index.add_with_ids(xb, ids)
     elif xb.shape[0]:
+        index.add(xb)
+    return index
+
+
+# ---------------------------------------------------------------- binary flat index (faiss.IndexBinaryFlat)
+_INT32_MAX = int(np.iinfo(np.int32).max)
+
+
+def _as_codes(x, code_size=None) -> np.ndarray:
+    """C-contiguous uint8 (n, code_size); a wrong dtype or width is an assertion, as in ``_as_rows``."""
+    x = np.asarray(x)
+    assert x.dtype == np.uint8, f"binary codes are uint8, got {x.dtype}"
+    x = np.ascontiguousarray(x)
+    assert x.ndim == 2, "expected a 2-D array"
+    if code_size is not None:
+        assert x.shape[1] == code_size, f"code size mismatch: got {x.shape[1]} bytes, index has {code_size}"
+    return x
+
+
+class IndexBinaryFlat:
+    """faiss.IndexBinaryFlat(d): exact brute-force search over ``d``-bit codes (uint8 rows of ``d / 8`` bytes) under the
+    Hamming distance, on the device (include/ise_knn.h, ise_binary_index_*).  Distances are int32, ascending; ties go
+    by ascending id, always (Faiss promises no order among equal distances); unfilled slots are -1 / INT32_MAX.  No
+    CPU path: the constructor raises without a GPU."""
+
+    def __init__(self, d: int, device: int | None = None):
+        self.d = int(d)
+        self.code_size = self.d // 8
+        self.is_trained = True
+        self.device = _default_device() if device is None else int(device)
+        self._h = ctypes.c_void_p()
+        self._lock = threading.Lock()
+        _n.check(_n.lib.ise_binary_index_create(ctypes.byref(self._h), self.d, self.device))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                _n.lib.ise_binary_index_destroy(h)
+            except Exception:  # interpreter shutdown: module globals may already be gone
+                pass
+            h.value = None
+
+    @property
+    def ntotal(self) -> int:
+        n = ctypes.c_int64(0)
+        _n.check(_n.lib.ise_binary_index_info(self._h, None, ctypes.byref(n), None))
+        return int(n.value)
+
+    def reset(self) -> None:
+        _n.check(_n.lib.ise_binary_index_reset(self._h))
+
+    def binary_stats(self) -> dict:
+        """Search batches, scan passes launched (one per 16 queries and per 32 results), range batches
+        (include/ise_knn.h, ise_binary_index_stats)."""
+        out = (ctypes.c_uint64 * 3)()
+        _n.check(_n.lib.ise_binary_index_stats(self._h, out))
+        return {"search_batches": int(out[0]), "scan_passes": int(out[1]), "range_batches": int(out[2])}
+
+    def add(self, x) -> None:
+        """Append codes (copied): uint8 (n, d / 8)."""
+        x = _as_codes(x, self.code_size)
+        _n.check(_n.lib.ise_binary_index_add_host(self._h, x.ctypes.data, x.shape[0]))
+
+    def add_torch(self, x) -> None:
+        """Append codes from a CUDA uint8 tensor on this index's device (no host hop)."""
+        import torch
+
+        assert x.is_cuda and x.dtype == torch.uint8 and x.dim() == 2 and x.shape[1] == self.code_size
+        x = x.contiguous()
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        with self._lock:
+            _n.check(_n.lib.ise_binary_index_add_device(self._h, x.data_ptr(), x.shape[0], st))
+        torch.cuda.current_stream(x.device).synchronize()  # x may be freed by the caller
+
+    def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
+        n = self.ntotal - i0 if n is None else n
+        out = np.empty((n, self.code_size), dtype=np.uint8)
+        _n.check(_n.lib.ise_binary_index_reconstruct_host(self._h, int(i0), int(n), out.ctypes.data))
+        return out
+
+    def reconstruct(self, i: int) -> np.ndarray:
+        return self.reconstruct_n(int(i), 1)[0]
+
+    def search(self, x, k: int):
+        """(D int32 (nq, k), I int64 (nq, k)), fresh arrays: Hamming distance ascending, ties by ascending id."""
+        x = _as_codes(x, self.code_size)
+        k = int(k)
+        assert k > 0
+        nq = x.shape[0]
+        D = np.empty((nq, k), dtype=np.int32)
+        I = np.empty((nq, k), dtype=np.int64)
+        _n.check(_n.lib.ise_binary_index_search_host(self._h, x.ctypes.data, nq, k, D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def search_torch(self, xq, k: int):
+        """Device-resident search: CUDA uint8 (nq, d / 8) in, CUDA (D int32, I int64) out, enqueued on the current
+        torch stream (no host synchronisation)."""
+        import torch
+
+        assert xq.is_cuda and xq.dtype == torch.uint8 and xq.dim() == 2 and xq.shape[1] == self.code_size
+        xq = xq.contiguous()
+        nq = xq.shape[0]
+        D = torch.empty((nq, int(k)), dtype=torch.int32, device=xq.device)
+        I = torch.empty((nq, int(k)), dtype=torch.int64, device=xq.device)
+        st = torch.cuda.current_stream(xq.device).cuda_stream
+        with self._lock:
+            _n.check(_n.lib.ise_binary_index_search_device(self._h, xq.data_ptr(), nq, int(k), D.data_ptr(),
+                                                           I.data_ptr(), st))
+        return D, I
+
+    def range_search(self, x, radius: int):
+        """(lims uint64 (nq + 1,), D int32, I int64), fresh arrays: query i's rows are ``I[lims[i]:lims[i+1]]`` in
+        ascending id order, every row with distance < radius (strict, as Faiss's hamming_range_search), D the numbers
+        ``search`` reports.  Faiss's Python wrapper may hand D out as float32; here it stays int32."""
+        x = _as_codes(x, self.code_size)
+        nq = x.shape[0]
+        res = ctypes.c_void_p()
+        _n.check(_n.lib.ise_binary_index_range_search_host(self._h, x.ctypes.data, nq, int(radius), ctypes.byref(res)))
+        try:
+            n = ctypes.c_int64()
+            lp, dp_, ip = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+            _n.check(_n.lib.ise_binary_range_result_get(res, ctypes.byref(n), ctypes.byref(lp), ctypes.byref(dp_),
+                                                        ctypes.byref(ip)))
+            lims = np.ctypeslib.as_array(ctypes.cast(lp, ctypes.POINTER(ctypes.c_int64)), (n.value + 1,))
+            lims = lims.astype(np.uint64)
+            total = int(lims[-1])
+            D = np.empty(total, dtype=np.int32)
+            I = np.empty(total, dtype=np.int64)
+            if total:
+                ctypes.memmove(D.ctypes.data, dp_.value, total * 4)
+                ctypes.memmove(I.ctypes.data, ip.value, total * 8)
+        finally:
+            _n.lib.ise_binary_range_result_destroy(res)
+        return lims, D, I
+
+
+# Faiss on-disk IndexBinaryFlat layout [upstream-faiss index_write.cpp write_index_binary, restated from the published
+# format; no sample file exists in the reference, so byte compatibility with real Faiss files is UNPINNED like the two
+# layouts above]:
+#   fourcc "IBxF"; int32 d; int32 code_size; int64 ntotal; uint8 is_trained; int32 metric_type (1); uint64 count
+#   (= ntotal * code_size); count bytes.
+_FOURCC_BINARY = b"IBxF"
+_BHDR = struct.Struct("<4siiqBi")
+
+
+def serialize_binary_flat(d: int, xb) -> bytes:
+    d = int(d)
+    assert d > 0 and d % 8 == 0, "d must be a positive multiple of 8"
+    cs = d // 8
+    xb = np.asarray(xb, dtype=np.uint8)
+    xb = _as_codes(xb.reshape(-1, cs), cs)
+    n = xb.shape[0]
+    return _BHDR.pack(_FOURCC_BINARY, d, cs, n, 1, 1) + struct.pack("<Q", n * cs) + xb.tobytes()
+
+
+def parse_binary_flat(buf: bytes):
+    """-> (d, xb uint8 (n, d / 8)); raises RuntimeError on a foreign or truncated file."""
+    if len(buf) >= 4 and buf[:4] != _FOURCC_BINARY:
+        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexBinaryFlat")
+    if len(buf) < _BHDR.size + 8:
+        raise RuntimeError("truncated binary index file")
+    _, d, cs, n, _, _ = _BHDR.unpack_from(buf, 0)
+    (count,) = struct.unpack_from("<Q", buf, _BHDR.size)
+    if d <= 0 or d % 8 != 0 or cs != d // 8 or n < 0 or count != n * cs:
+        raise RuntimeError("corrupt binary flat index header")
+    if len(buf) < _BHDR.size + 8 + count:
+        raise RuntimeError("truncated binary flat index payload")
+    xb = np.frombuffer(buf, dtype=np.uint8, count=count, offset=_BHDR.size + 8).reshape(n, cs).copy()
+    return d, xb
+
+
+def write_index_binary(index: IndexBinaryFlat, path) -> None:
+    with open(str(path), "wb") as f:
+        f.write(serialize_binary_flat(index.d, index.reconstruct_n(0, index.ntotal)))
+
+
+def read_index_binary(path, device: int | None = None) -> IndexBinaryFlat:
+    with open(str(path), "rb") as f:
+        buf = f.read()
+    d, xb = parse_binary_flat(buf)
+    index = IndexBinaryFlat(d, device)
+    if xb.shape[0]:
         index.add(xb)
     return index
 

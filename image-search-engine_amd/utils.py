@@ -49,6 +49,29 @@ def get_image(image_path):
     return base64.encodebytes(buf.getvalue()).decode("ascii")
 
 
+def hamming(a, b):
+    """Hamming distance between two integer hashes (the signature of backend/utils.py:84-88, which nothing in the
+    reference calls)."""
+    return (int(a) ^ int(b)).bit_count()
+
+
+def hashes_to_codes(hashes, nbits=64):
+    """Python-int hashes, as the reference's ``dhash`` yields them (bit i has the value 2**i, backend/utils.py:65-76),
+    as the uint8 (n, nbits / 8) codes of ``faiss.IndexBinaryFlat(nbits)``: little-endian, bit i of a hash is bit
+    ``i % 8`` of byte ``i // 8``.  The index's distance between ``codes[a]`` and ``codes[b]`` is then
+    ``hamming(hashes[a], hashes[b])``."""
+    import numpy as np
+
+    nbits = int(nbits)
+    assert nbits > 0 and nbits % 8 == 0, "nbits must be a positive multiple of 8"
+    hashes = [int(h) for h in hashes]
+    out = np.zeros((len(hashes), nbits // 8), dtype=np.uint8)
+    for i, h in enumerate(hashes):
+        assert 0 <= h < (1 << nbits), f"hash {h} does not fit in {nbits} bits"
+        out[i] = np.frombuffer(h.to_bytes(nbits // 8, "little"), dtype=np.uint8)
+    return out
+
+
 def create_search_index(data_array, index_type="cosine"):
     """backend/utils.py:293-330.  'cosine' -> IndexFlatIP over rows normalised IN
     PLACE in the caller's array (quirk 5.9-6); 'l2' -> IndexFlatL2; then add.

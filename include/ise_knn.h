@@ -248,6 +248,58 @@ int ise_index_range_search_sel_host(ise_index_t* h, const float* q, int64_t nq, 
                                     ise_range_result_t** out);
 int ise_index_sel_stats(ise_index_t* h, uint64_t* out3);
 
+/* Binary flat index: faiss.IndexBinaryFlat(d_bits) -- exact brute-force kNN and range search over bit codes under
+ * the HAMMING distance (csrc/ise_binary_scan.hpp).  The reference's DHASH method keeps 64-bit difference hashes
+ * (backend/indexer.py:39-49) and answers a query with a dict lookup that finds bit-identical hashes only
+ * (backend/engine.py:82-91); its hamming(a, b) helper (backend/utils.py:84-88) is never called.  "Every image within
+ * r bits of this hash" is ise_binary_index_range_search_host, "the k nearest hashes" ise_binary_index_search_*.
+ *
+ * A code is d_bits / 8 bytes (d_bits a positive multiple of 8, at most ISE_BINARY_MAX_BITS; anything else is
+ * ISE_E_INVALID); rows are copied on add and numbered in insertion order; an index holds fewer than 2^32 rows.  All
+ * the conventions at the top of this header hold (0 / ISE_E_* returns, ise_last_error, caller-owned buffers, *_host
+ * blocks, *_device only enqueues on the given stream).  Calls on one handle run one at a time; *_device calls on
+ * different streams are ordered one behind the other on the device (one set of workspaces per handle).
+ *   distance      the Hamming distance (number of differing bits), int32, ascending.  Every score is an integer, so
+ *                 results do not depend on the kernel path taken
+ *   tie order     ties go by ascending row id, ALWAYS.  This is the project's convention (see the top of this header):
+ *                 Faiss's heap promises no order among equal distances
+ *   unfilled      k > ntotal, or an empty index: id -1 and distance INT32_MAX (Faiss's CMax<int32_t> neutral, restated
+ *                 from memory and unpinned like the rest of the oracle)
+ *   k             1 .. ISE_MAX_K; one pass over the codes per 16 queries and per 32 results (k = 70: three passes, the
+ *                 later ones admit only keys behind the last result of the one before).  nq = 0 is legal and returns at
+ *                 once; an empty index costs no pass
+ *   range search  every row with dist < radius (strict, as Faiss's hamming_range_search), per query in ascending id
+ *                 order; lims has nq + 1 entries, lims[0] = 0; no cap on the count; radius <= 0 returns nothing without
+ *                 a pass.  D is int32, the numbers search reports (Faiss's Python wrapper may hand them out as
+ *                 float32).  A count pass and a fill pass over the codes per 16 queries, one host synchronisation per
+ *                 256 queries
+ *   stats         out3[0] = search batches (calls with nq > 0), out3[1] = scan passes launched, out3[2] = range batches
+ *                 (<= 256 queries of a call with radius > 0 against a non-empty index) */
+#define ISE_BINARY_MAX_BITS 8192
+typedef struct ise_binary_index ise_binary_index_t;
+typedef struct ise_binary_range_result ise_binary_range_result_t;
+int ise_binary_index_create(ise_binary_index_t** out, int d_bits, int device);
+int ise_binary_index_destroy(ise_binary_index_t* h); /* NULL is a no-op */
+int ise_binary_index_reset(ise_binary_index_t* h);   /* drop all rows, keep d_bits and the capacity */
+int ise_binary_index_info(const ise_binary_index_t* h, int* d_bits, int64_t* ntotal, int* device);
+/* append n codes of d_bits / 8 bytes each, copied */
+int ise_binary_index_add_host(ise_binary_index_t* h, const uint8_t* codes, int64_t n);
+int ise_binary_index_add_device(ise_binary_index_t* h, const uint8_t* codes_dev, int64_t n, void* stream);
+/* rows [i0, i0 + n) back to the host as n x d_bits / 8 bytes */
+int ise_binary_index_reconstruct_host(ise_binary_index_t* h, int64_t i0, int64_t n, uint8_t* out);
+/* q: nq x d_bits / 8 bytes; D: nq x k int32; I: nq x k int64 */
+int ise_binary_index_search_host(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int k, int32_t* D, int64_t* I);
+int ise_binary_index_search_device(ise_binary_index_t* h, const uint8_t* q_dev, int64_t nq, int k, int32_t* D_dev,
+                                   int64_t* I_dev, void* stream);
+/* *out is NULL on error */
+int ise_binary_index_range_search_host(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int32_t radius,
+                                       ise_binary_range_result_t** out);
+/* pointers valid until ise_binary_range_result_destroy; any output pointer may be NULL */
+int ise_binary_range_result_get(const ise_binary_range_result_t* r, int64_t* nq, const int64_t** lims, const int32_t** D,
+                                const int64_t** I);
+int ise_binary_range_result_destroy(ise_binary_range_result_t* r); /* NULL is a no-op */
+int ise_binary_index_stats(ise_binary_index_t* h, uint64_t* out3);
+
 /* Shard-local search for the multi-GPU path: writes nq x k
  * packed candidates, sorted best-first, suitable for one all-gather:
  *   key = (order-preserving uint32 image of the score) << 32 | (row + id_base)
