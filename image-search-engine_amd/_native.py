@@ -94,6 +94,18 @@ PROTOTYPES = [
     ("ise_binary_range_result_get", _int, [_vp, _i64p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     ("ise_binary_range_result_destroy", _int, [_vp]),
     ("ise_binary_index_stats", _int, [_vp, _u64p]),
+    ("ise_binary_index_remove_ids_host", _int, [_vp, _vp, _i64, _i64p]),
+    ("ise_binary_index_remove_range", _int, [_vp, _i64, _i64, _i64p]),
+    ("ise_binary_index_remove_stats", _int, [_vp, _u64p]),
+    ("ise_binary_selector_create_range", _int, [_vp, _i64, _i64, ctypes.POINTER(_vp)]),
+    ("ise_binary_selector_create_ids", _int, [_vp, _vp, _i64, _int, ctypes.POINTER(_vp)]),
+    ("ise_binary_selector_create_bitmap", _int, [_vp, _vp, _i64, ctypes.POINTER(_vp)]),
+    ("ise_binary_selector_info", _int, [_vp, _i64p]),
+    ("ise_binary_selector_destroy", _int, [_vp]),
+    ("ise_binary_index_search_sel_host", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
+    ("ise_binary_index_search_sel_device", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    ("ise_binary_index_range_search_sel_host", _int, [_vp, _vp, _i64, ctypes.c_int32, _vp, ctypes.POINTER(_vp)]),
+    ("ise_binary_index_sel_stats", _int, [_vp, _u64p]),
     ("ise_refresh_env_knobs", _int, []),
     ("ise_comm_precheck", _int, [_int]),
     ("ise_comm_unique_id", _int, [_vp]),

@@ -6,9 +6,18 @@
 // forms while they enqueue).  The handle has ONE set of workspaces: work enqueued on another stream than the previous
 // call's waits for that call through an event, and a workspace that has to grow is replaced only after the device
 // has drained.
+//
+// Selectors and removal mirror the float index (ise_knn.hip): a selector is a device bitmap bound to
+// the handle, its ntotal and its ROW EPOCH (bumped by whatever removes rows: a reset of a non-empty index, a removal
+// that removes something; never by add); every filtered entry point checks the three before anything else.  A removal
+// holds the mutex from its device-wide synchronisation to the end of its last copy: other calls on the handle run
+// entirely before or entirely after it.
 #include "ise_binary_scan.hpp"
+#include "ise_remove.hpp"
+#include "ise_sel_scan.hpp"
 
 extern int ise_fail_(int code, const std::string& msg);  // ise_knn.hip: sets the thread-local message
+extern int ise_remove_slab_rows_();                      // ise_knn.hip: $ISE_REMOVE_SLAB_ROWS as last refreshed
 
 #define BIN_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -58,6 +67,20 @@ struct ise_binary_index {
     BinBuf<int> oD, counts, rD;
     BinBuf<long long> oI, offs, totals, lims, rI;
     uint64_t st_search = 0, st_passes = 0, st_range = 0;
+    unsigned long long row_epoch = 0;  // bumped when rows go or are renumbered: selectors made before are stale
+    uint64_t st_sel = 0, st_sel_passes = 0, st_sel_range = 0;    // filtered batches, masked passes, filtered range batches
+    uint64_t st_rm_calls = 0, st_rm_rows = 0, st_rm_moved = 0;   // removals that removed something, rows removed, rows moved
+};
+
+// a device bitmap over the rows of ONE binary index at ONE (ntotal, row epoch)
+struct ise_binary_selector {
+    ise_binary_index* owner = nullptr;
+    int device = 0;
+    uint32_t* bits = nullptr;  // 2 * max(1, ceil(ntotal / 64)) words: one aligned 8-byte word per 64-row tile
+    long long nwords = 0;      // allocated uint32 words (even)
+    long long ntotal = 0;
+    unsigned long long epoch = 0;
+    long long count = 0, r0 = 0, r1 = 0, tiles = 0;  // selected rows, window [r0, r1), non-empty 64-row tiles
 };
 
 struct ise_binary_range_result {
@@ -82,30 +105,64 @@ int bin_end(ise_binary_index* h, hipStream_t st) {
     return ISE_OK;
 }
 
-void launch_scan(int wt, unsigned grid, size_t lds, hipStream_t st, const BinScanParams& sp) {
-    static LdsAttrOnce attr[3];
+// mk: the selector's mask and window (the masked kernels), or null
+void launch_scan(int wt, unsigned grid, size_t lds, hipStream_t st, const BinScanParams& sp, const BinMask* mk) {
+    static LdsAttrOnce attr[6];
     auto go = [&](auto kern, LdsAttrOnce& a) {
         a.ensure(reinterpret_cast<const void*>(kern), BIN_LDS_MAX);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(BIN_WAVES * 64), lds, st, sp);
+        if constexpr (std::is_invocable_v<decltype(kern), BinScanParams, BinMask>)
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(BIN_WAVES * 64), lds, st, sp, *mk);
+        else
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(BIN_WAVES * 64), lds, st, sp);
     };
-    if (wt == 1) go(binary_scan_kernel<1>, attr[0]);
+    if (mk) {
+        if (wt == 1) go(binary_scan_masked_kernel<1>, attr[3]);
+        else if (wt == 2) go(binary_scan_masked_kernel<2>, attr[4]);
+        else go(binary_scan_masked_kernel<0>, attr[5]);
+    } else if (wt == 1) go(binary_scan_kernel<1>, attr[0]);
     else if (wt == 2) go(binary_scan_kernel<2>, attr[1]);
     else go(binary_scan_kernel<0>, attr[2]);
 }
 
 template <bool FILL>
-void launch_range(int wt, unsigned grid, size_t lds, hipStream_t st, const BinRangeParams& rp) {
-    if (wt == 1) hipLaunchKernelGGL((binary_range_kernel<1, FILL>), dim3(grid), dim3(BIN_WAVES * 64), lds, st, rp);
-    else if (wt == 2) hipLaunchKernelGGL((binary_range_kernel<2, FILL>), dim3(grid), dim3(BIN_WAVES * 64), lds, st, rp);
-    else hipLaunchKernelGGL((binary_range_kernel<0, FILL>), dim3(grid), dim3(BIN_WAVES * 64), lds, st, rp);
+void launch_range(int wt, unsigned grid, size_t lds, hipStream_t st, const BinRangeParams& rp, const BinMask* mk) {
+    const dim3 g(grid), b(BIN_WAVES * 64);
+    if (mk) {
+        if (wt == 1) hipLaunchKernelGGL((binary_range_masked_kernel<1, FILL>), g, b, lds, st, rp, *mk);
+        else if (wt == 2) hipLaunchKernelGGL((binary_range_masked_kernel<2, FILL>), g, b, lds, st, rp, *mk);
+        else hipLaunchKernelGGL((binary_range_masked_kernel<0, FILL>), g, b, lds, st, rp, *mk);
+    } else if (wt == 1) hipLaunchKernelGGL((binary_range_kernel<1, FILL>), g, b, lds, st, rp);
+    else if (wt == 2) hipLaunchKernelGGL((binary_range_kernel<2, FILL>), g, b, lds, st, rp);
+    else hipLaunchKernelGGL((binary_range_kernel<0, FILL>), g, b, lds, st, rp);
 }
 
-// blocks of a pass over the rows: about two 64-row tiles per wave on a short index, at most two blocks per CU
-unsigned bin_grid(const ise_binary_index* h) {
-    const long long tiles = (h->n + 63) / 64;
+// blocks of a pass over `tiles` 64-row tiles: about two per wave on a short index, at most two blocks per CU
+unsigned bin_grid_tiles(const ise_binary_index* h, long long tiles) {
     long long g = (tiles + 2 * BIN_WAVES - 1) / (2 * BIN_WAVES);
     g = std::min<long long>(g, std::min<long long>(2ll * h->num_cu, MERGE_LISTS_MAX));
     return (unsigned)std::max<long long>(g, 1);
+}
+unsigned bin_grid(const ise_binary_index* h) { return bin_grid_tiles(h, (h->n + 63) / 64); }
+
+// mu held.  A selector is good for the handle it was made from while ntotal and the row epoch stand
+int selector_check_locked(const ise_binary_index* h, const ise_binary_selector* sel) {
+    if (!sel) return ise_fail_(ISE_E_INVALID, "selector is NULL");
+    if (sel->owner != h) return ise_fail_(ISE_E_INVALID, "the selector was made for another index");
+    if (sel->epoch != h->row_epoch)
+        return ise_fail_(ISE_E_INVALID,
+                         "stale selector: rows were removed from the index (row epoch changed) since it was made");
+    if (sel->ntotal != h->n)
+        return ise_fail_(ISE_E_INVALID, "stale selector: ntotal changed (" + std::to_string(sel->ntotal) + " -> " +
+                                            std::to_string(h->n) + ") since it was made");
+    return ISE_OK;
+}
+
+BinMask selector_mask(const ise_binary_selector* sel) {
+    BinMask mk{};
+    mk.words = reinterpret_cast<const u64*>(sel->bits);
+    mk.tile0 = sel->r0 >> 6;
+    mk.tile1 = (sel->r1 + 63) >> 6;
+    return mk;
 }
 
 int reserve_codes(ise_binary_index* h, long long need, hipStream_t st) {
@@ -149,24 +206,29 @@ int add_device_locked(ise_binary_index* h, const uint8_t* x_dev, long long n, hi
     return bin_end(h, st);
 }
 
-// q_dev: nq x code_size bytes on the device; D_dev / I_dev: nq x k
+// q_dev: nq x code_size bytes on the device; D_dev / I_dev: nq x k.  sel: among the selector's rows only (checked by
+// the caller; the masked kernels over its window), or null
 int search_enqueue(ise_binary_index* h, const uint8_t* q_dev, long long nq, int k, int* D_dev, long long* I_dev,
-                   hipStream_t st) {
+                   hipStream_t st, const ise_binary_selector* sel = nullptr) {
     int rc = bin_begin(h, st);
     if (rc) return rc;
-    if (h->n == 0) {
-        h->st_search++;
+    uint64_t& st_batches = sel ? h->st_sel : h->st_search;
+    uint64_t& st_pass = sel ? h->st_sel_passes : h->st_passes;
+    if (h->n == 0 || (sel && sel->count == 0)) {  // nothing to rank: a fill, no pass
+        st_batches++;
         const long long cnt = nq * k;
         hipLaunchKernelGGL(binary_fill_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, cnt);
         BIN_TRY(hipGetLastError());
         return bin_end(h, st);
     }
-    const unsigned grid = bin_grid(h);
+    BinMask mk{};
+    if (sel) mk = selector_mask(sel);
+    const unsigned grid = sel ? bin_grid_tiles(h, mk.tile1 - mk.tile0) : bin_grid(h);
     const long long nq16 = (nq + BIN_QT - 1) / BIN_QT * BIN_QT;
     if ((rc = bin_grow(h->qpad, (size_t)nq16 * h->ws))) return rc;
     if ((rc = bin_grow(h->lo, (size_t)nq16))) return rc;
     if ((rc = bin_grow(h->lists, (size_t)grid * BIN_QT * BIN_KPASS))) return rc;
-    h->st_search++;  // counted once the batch is certain to be enqueued
+    st_batches++;  // counted once the batch is certain to be enqueued
     pad_rows(q_dev, h->code_size, h->qpad.p, h->ws, nq, st);
     const int wt = bin_wt(h);
     const size_t lds = BIN_BUF_BYTES + BIN_CNT_BYTES + bin_query_lds(h);
@@ -183,7 +245,7 @@ int search_enqueue(ise_binary_index* h, const uint8_t* q_dev, long long nq, int 
             sp.kp = kp;
             sp.lo = off == 0 ? nullptr : h->lo.p + q0;  // the merge of the pass before wrote it
             sp.lists = h->lists.p;
-            launch_scan(wt, grid, lds, st, sp);
+            launch_scan(wt, grid, lds, st, sp, sel ? &mk : nullptr);
             MergeParams mp{};
             mp.lists = h->lists.p;
             mp.stride_list = (long long)BIN_QT * BIN_KPASS;
@@ -199,7 +261,7 @@ int search_enqueue(ise_binary_index* h, const uint8_t* q_dev, long long nq, int 
             mo.k = k;
             mo.off = off;
             hipLaunchKernelGGL(binary_merge_kernel, dim3((unsigned)nqt), dim3(MERGE_THREADS), 0, st, mp, mo);
-            h->st_passes++;
+            st_pass++;
         }
     }
     BIN_TRY(hipGetLastError());
@@ -217,13 +279,18 @@ int check_search_args(const ise_binary_index* h, const void* q, long long nq, in
     return ISE_OK;
 }
 
-// one batch of m <= BIN_RANGE_NQ_CHUNK queries (host pointer) appended to the result
-int range_batch(ise_binary_index* h, hipStream_t st, const uint8_t* q, long long m, int radius, ise_binary_range_result* res) {
+// one batch of m <= BIN_RANGE_NQ_CHUNK queries (host pointer) appended to the result.  sel: the segments cut the
+// selector's window (whole tiles) instead of [0, n), or null
+int range_batch(ise_binary_index* h, hipStream_t st, const uint8_t* q, long long m, int radius, ise_binary_range_result* res,
+                const ise_binary_selector* sel) {
     int rc;
     const long long m16 = (m + BIN_QT - 1) / BIN_QT * BIN_QT;
-    const unsigned grid = bin_grid(h);
+    BinMask mkv{};
+    if (sel) mkv = selector_mask(sel);
+    const BinMask* mk = sel ? &mkv : nullptr;
+    const unsigned grid = sel ? bin_grid_tiles(h, mkv.tile1 - mkv.tile0) : bin_grid(h);
     const int S = (int)grid * BIN_WAVES;
-    long long seg_rows = (h->n + S - 1) / S;
+    long long seg_rows = ((sel ? (mkv.tile1 - mkv.tile0) * 64 : h->n) + S - 1) / S;
     seg_rows = (seg_rows + 63) / 64 * 64;
     const long long M = m * S;
     if ((rc = bin_grow(h->raw, (size_t)m * h->code_size))) return rc;
@@ -247,7 +314,7 @@ int range_batch(ise_binary_index* h, hipStream_t st, const uint8_t* q, long long
         rp.qpad = h->qpad.p + (size_t)q0 * h->ws;
         rp.nqt = (int)std::min<long long>(BIN_QT, m - q0);
         rp.counts = h->counts.p + (size_t)q0 * S;
-        launch_range<false>(wt, grid, lds, st, rp);
+        launch_range<false>(wt, grid, lds, st, rp, mk);
     }
     hipLaunchKernelGGL(binary_offsets_kernel, dim3((unsigned)m), dim3(BIN_SCAN_THREADS), 0, st, h->counts.p, S, h->offs.p,
                        h->totals.p);
@@ -269,7 +336,7 @@ int range_batch(ise_binary_index* h, hipStream_t st, const uint8_t* q, long long
         rp.nqt = (int)std::min<long long>(BIN_QT, m - q0);
         rp.offs = h->offs.p + (size_t)q0 * S;
         rp.lims = h->lims.p + q0;
-        launch_range<true>(wt, grid, lds, st, rp);
+        launch_range<true>(wt, grid, lds, st, rp, mk);
     }
     BIN_TRY(hipGetLastError());
     res->D.resize(at + (size_t)total);
@@ -346,6 +413,7 @@ extern "C" int ise_binary_index_destroy(ise_binary_index_t* h) {
 extern "C" int ise_binary_index_reset(ise_binary_index_t* h) {
     if (check_handle(h)) return ISE_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
+    if (h->n > 0) h->row_epoch++;  // rows went: selectors made before are stale
     h->n = 0;  // capacity is kept; stale rows are masked by row number, their pad bytes are zero already
     return ISE_OK;
 }
@@ -441,11 +509,13 @@ extern "C" int ise_binary_index_search_host(ise_binary_index_t* h, const uint8_t
     return ISE_OK;
 }
 
-extern "C" int ise_binary_index_range_search_host(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int32_t radius,
-                                                  ise_binary_range_result_t** out) {
+// filtered: sel must be a selector (checked first, under the mutex, also for nq == 0 or an empty index)
+static int range_search_impl(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int32_t radius, bool filtered,
+                             const ise_binary_selector* sel, ise_binary_range_result_t** out) {
     if (!out) return ise_fail_(ISE_E_INVALID, "out is NULL");
     *out = nullptr;
     if (check_handle(h)) return ISE_E_INVALID;
+    if (filtered && !sel) return ise_fail_(ISE_E_INVALID, "selector is NULL");
     if (nq < 0 || (nq > 0 && !q)) return ise_fail_(ISE_E_INVALID, "bad queries / nq");
     ise_binary_range_result* res = new (std::nothrow) ise_binary_range_result();
     if (!res) return ise_fail_(ISE_E_NOMEM, "host allocation failed");
@@ -456,14 +526,15 @@ extern "C" int ise_binary_index_range_search_host(ise_binary_index_t* h, const u
         DeviceGuard gd(h->device);
         if (!gd.ok) rc = ise_fail_(ISE_E_HIP, "hipSetDevice failed");
         std::lock_guard<std::mutex> lk(h->mu);
-        if (!rc && (h->n == 0 || radius <= 0)) {
+        if (!rc && filtered) rc = selector_check_locked(h, sel);
+        if (!rc && (h->n == 0 || radius <= 0 || (filtered && sel->count == 0))) {
             res->lims.resize((size_t)nq + 1, 0);  // nothing can match: no pass
         } else if (!rc) {
             rc = bin_begin(h, h->stream);
             for (long long q0 = 0; q0 < nq && !rc; q0 += BIN_RANGE_NQ_CHUNK) {
                 const long long m = std::min<long long>(BIN_RANGE_NQ_CHUNK, nq - q0);
-                h->st_range++;
-                rc = range_batch(h, h->stream, q + (size_t)q0 * h->code_size, m, radius, res);
+                (filtered ? h->st_sel_range : h->st_range)++;
+                rc = range_batch(h, h->stream, q + (size_t)q0 * h->code_size, m, radius, res, sel);
             }
             if (!rc) rc = bin_end(h, h->stream);  // the workspaces' last user, as after every other call
         }
@@ -476,6 +547,16 @@ extern "C" int ise_binary_index_range_search_host(ise_binary_index_t* h, const u
     }
     *out = res;
     return ISE_OK;
+}
+
+extern "C" int ise_binary_index_range_search_host(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int32_t radius,
+                                                  ise_binary_range_result_t** out) {
+    return range_search_impl(h, q, nq, radius, false, nullptr, out);
+}
+
+extern "C" int ise_binary_index_range_search_sel_host(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int32_t radius,
+                                                      const ise_binary_selector_t* sel, ise_binary_range_result_t** out) {
+    return range_search_impl(h, q, nq, radius, true, sel, out);
 }
 
 extern "C" int ise_binary_range_result_get(const ise_binary_range_result_t* r, int64_t* nq, const int64_t** lims,
@@ -500,5 +581,342 @@ extern "C" int ise_binary_index_stats(ise_binary_index_t* h, uint64_t* out3) {
     out3[0] = h->st_search;
     out3[1] = h->st_passes;
     out3[2] = h->st_range;
+    return ISE_OK;
+}
+
+// ---- selectors
+namespace {
+// the bitmap of a new selector for h as it stands (mu held): one 8-byte word per 64-row tile, at least one
+int selector_alloc_locked(ise_binary_index* h, ise_binary_selector** out) {
+    ise_binary_selector* s = new (std::nothrow) ise_binary_selector;
+    if (!s) return ise_fail_(ISE_E_NOMEM, "selector: host allocation failed");
+    s->owner = h;
+    s->device = h->device;
+    s->ntotal = h->n;
+    s->epoch = h->row_epoch;
+    s->nwords = 2 * std::max<long long>(1, (h->n + 63) / 64);
+    const hipError_t e = hipMalloc((void**)&s->bits, (size_t)s->nwords * sizeof(uint32_t));
+    if (e != hipSuccess) {
+        delete s;
+        return ise_fail_(e == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP, std::string("selector bitmap: ") + hipGetErrorString(e));
+    }
+    *out = s;
+    return ISE_OK;
+}
+
+void selector_free(ise_binary_selector* s) {
+    if (s->bits) (void)hipFree(s->bits);  // waits for the device: a masked pass in flight is through with the bitmap
+    delete s;
+}
+
+// clears bits at or beyond ntotal, then count / window / non-empty 64-row tiles on the device (mu held; blocks)
+int selector_census_locked(ise_binary_selector* s, hipStream_t st) {
+    unsigned long long* dev = nullptr;
+    BIN_TRY(hipMalloc((void**)&dev, 4 * sizeof(unsigned long long)));
+    struct Free { void* p; ~Free() { (void)hipFree(p); } } fr{dev};
+    const unsigned long long init[4] = {0ull, 0ull, ~0ull, 0ull};
+    unsigned long long got[4];
+    BIN_TRY(hipMemcpyAsync(dev, init, sizeof(init), hipMemcpyHostToDevice, st));
+    const long long nw64 = s->nwords / 2;
+    hipLaunchKernelGGL(binary_sel_census_kernel, dim3((unsigned)((nw64 + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<u64*>(s->bits), nw64, s->ntotal, dev);
+    BIN_TRY(hipGetLastError());
+    BIN_TRY(hipMemcpyAsync(got, dev, sizeof(got), hipMemcpyDeviceToHost, st));
+    BIN_TRY(hipStreamSynchronize(st));
+    s->count = (long long)got[0];
+    s->tiles = (long long)got[1];
+    s->r0 = got[0] ? (long long)got[2] : 0;
+    s->r1 = got[0] ? (long long)got[3] : 0;
+    return ISE_OK;
+}
+
+void selector_fill(ise_binary_index* h, ise_binary_selector* s, long long a, long long b) {
+    hipLaunchKernelGGL(sel_fill_range_kernel, dim3((unsigned)((s->nwords + 255) / 256)), dim3(256), 0, h->stream, s->bits,
+                       s->nwords, a, std::max(a, b));
+}
+}  // namespace
+
+extern "C" int ise_binary_selector_create_range(ise_binary_index_t* h, int64_t i0, int64_t i1, ise_binary_selector_t** out) {
+    if (!out) return ise_fail_(ISE_E_INVALID, "output pointer is NULL");
+    *out = nullptr;
+    if (check_handle(h)) return ISE_E_INVALID;
+    DeviceGuard gd(h->device);
+    if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ise_binary_selector* s = nullptr;
+    int rc = selector_alloc_locked(h, &s);
+    if (rc) return rc;
+    selector_fill(h, s, std::max<long long>(i0, 0), std::min<long long>(i1, h->n));
+    rc = selector_census_locked(s, h->stream);
+    if (rc) { selector_free(s); return rc; }
+    *out = s;
+    return ISE_OK;
+}
+
+extern "C" int ise_binary_selector_create_ids(ise_binary_index_t* h, const int64_t* ids, int64_t n_ids, int invert,
+                                              ise_binary_selector_t** out) {
+    if (!out) return ise_fail_(ISE_E_INVALID, "output pointer is NULL");
+    *out = nullptr;
+    if (check_handle(h)) return ISE_E_INVALID;
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return ise_fail_(ISE_E_INVALID, "ids is NULL");
+    DeviceGuard gd(h->device);
+    if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ise_binary_selector* s = nullptr;
+    int rc = selector_alloc_locked(h, &s);
+    if (rc) return rc;
+    long long* ids_dev = nullptr;
+    struct Free { long long** p; ~Free() { if (*p) (void)hipFree(*p); } } fr{&ids_dev};
+    auto body = [&]() -> int {
+        // the fill runs on the device: nothing (invert: every row), then the ids are scattered in -- only they travel
+        selector_fill(h, s, 0ll, invert ? h->n : 0ll);
+        if (n_ids > 0) {
+            BIN_TRY(hipMalloc((void**)&ids_dev, (size_t)n_ids * sizeof(long long)));
+            BIN_TRY(hipMemcpyAsync(ids_dev, ids, (size_t)n_ids * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+            hipLaunchKernelGGL(sel_scatter_ids_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, h->stream, s->bits,
+                               (const long long*)ids_dev, (long long)n_ids, h->n, invert ? 0 : 1);
+        }
+        BIN_TRY(hipGetLastError());
+        return selector_census_locked(s, h->stream);
+    };
+    rc = body();
+    if (rc) { selector_free(s); return rc; }
+    *out = s;
+    return ISE_OK;
+}
+
+extern "C" int ise_binary_selector_create_bitmap(ise_binary_index_t* h, const uint32_t* words, int64_t n_words,
+                                                 ise_binary_selector_t** out) {
+    if (!out) return ise_fail_(ISE_E_INVALID, "output pointer is NULL");
+    *out = nullptr;
+    if (check_handle(h)) return ISE_E_INVALID;
+    if (n_words < 0 || (n_words > 0 && !words)) return ise_fail_(ISE_E_INVALID, "words is NULL");
+    DeviceGuard gd(h->device);
+    if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (n_words != (h->n + 31) / 32)
+        return ise_fail_(ISE_E_INVALID, "the bitmap must have ceil(ntotal / 32) = " + std::to_string((h->n + 31) / 32) + " words");
+    ise_binary_selector* s = nullptr;
+    int rc = selector_alloc_locked(h, &s);
+    if (rc) return rc;
+    auto body = [&]() -> int {
+        BIN_TRY(hipMemsetAsync(s->bits + n_words, 0, (size_t)(s->nwords - n_words) * sizeof(uint32_t), h->stream));
+        if (n_words > 0)
+            BIN_TRY(hipMemcpyAsync(s->bits, words, (size_t)n_words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        return selector_census_locked(s, h->stream);  // clears the bits at or beyond ntotal
+    };
+    rc = body();
+    if (rc) { selector_free(s); return rc; }
+    *out = s;
+    return ISE_OK;
+}
+
+extern "C" int ise_binary_selector_info(const ise_binary_selector_t* sel, int64_t* out5) {
+    if (!sel || !out5) return ise_fail_(ISE_E_INVALID, "NULL argument");
+    out5[0] = sel->ntotal;
+    out5[1] = sel->count;
+    out5[2] = sel->r0;
+    out5[3] = sel->r1;
+    out5[4] = sel->tiles;
+    return ISE_OK;
+}
+
+extern "C" int ise_binary_selector_destroy(ise_binary_selector_t* sel) {
+    if (!sel) return ISE_OK;
+    DeviceGuard gd(sel->device);
+    selector_free(sel);
+    return ISE_OK;
+}
+
+extern "C" int ise_binary_index_search_sel_device(ise_binary_index_t* h, const uint8_t* q_dev, int64_t nq, int k,
+                                                  const ise_binary_selector_t* sel, int32_t* D_dev, int64_t* I_dev,
+                                                  void* stream) {
+    int rc = check_search_args(h, q_dev, nq, k);
+    if (rc) return rc;
+    if (!sel) return ise_fail_(ISE_E_INVALID, "selector is NULL");
+    if (nq > 0 && (!D_dev || !I_dev)) return ise_fail_(ISE_E_INVALID, "output pointer is NULL");
+    DeviceGuard gd(h->device);
+    if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if ((rc = selector_check_locked(h, sel))) return rc;  // first, and also for nq == 0 or an empty index
+    if (nq == 0) return ISE_OK;
+    return search_enqueue(h, q_dev, nq, k, (int*)D_dev, (long long*)I_dev, (hipStream_t)stream, sel);
+}
+
+extern "C" int ise_binary_index_search_sel_host(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int k,
+                                                const ise_binary_selector_t* sel, int32_t* D, int64_t* I) {
+    int rc = check_search_args(h, q, nq, k);
+    if (rc) return rc;
+    if (!sel) return ise_fail_(ISE_E_INVALID, "selector is NULL");
+    if (nq > 0 && (!D || !I)) return ise_fail_(ISE_E_INVALID, "output pointer is NULL");
+    DeviceGuard gd(h->device);
+    if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if ((rc = selector_check_locked(h, sel))) return rc;
+    if (nq == 0) return ISE_OK;
+    const size_t cnt = (size_t)nq * k;
+    if ((rc = bin_grow(h->raw, (size_t)nq * h->code_size))) return rc;
+    if ((rc = bin_grow(h->oD, cnt))) return rc;
+    if ((rc = bin_grow(h->oI, cnt))) return rc;
+    if ((rc = bin_begin(h, h->stream))) return rc;
+    BIN_TRY(hipMemcpyAsync(h->raw.p, q, (size_t)nq * h->code_size, hipMemcpyHostToDevice, h->stream));
+    if ((rc = search_enqueue(h, h->raw.p, nq, k, h->oD.p, h->oI.p, h->stream, sel))) return rc;
+    BIN_TRY(hipMemcpyAsync(D, h->oD.p, cnt * 4, hipMemcpyDeviceToHost, h->stream));
+    BIN_TRY(hipMemcpyAsync(I, h->oI.p, cnt * 8, hipMemcpyDeviceToHost, h->stream));
+    BIN_TRY(hipStreamSynchronize(h->stream));
+    return ISE_OK;
+}
+
+extern "C" int ise_binary_index_sel_stats(ise_binary_index_t* h, uint64_t* out3) {
+    if (check_handle(h)) return ISE_E_INVALID;
+    if (!out3) return ise_fail_(ISE_E_INVALID, "out3 is NULL");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out3[0] = h->st_sel;
+    out3[1] = h->st_sel_passes;
+    out3[2] = h->st_sel_range;
+    return ISE_OK;
+}
+
+// ---- remove_ids: stable in-place compaction of the code rows (ise_remove.hpp)
+namespace {
+struct BinRemoveRun {
+    long long start, len;
+};
+
+// everything a removal allocates for the duration of the call
+struct BinRemoveScratch {
+    uint32_t* g = nullptr;        // [T] destination row at which run t bites
+    uint32_t* cend = nullptr;     // [T] rows removed up to and including run t
+    uint32_t* src_idx = nullptr;  // [slab] source rows of the current slab
+    char* bounce = nullptr;       // one slab of rows
+    ~BinRemoveScratch() {
+        for (void* p : {(void*)g, (void*)cend, (void*)src_idx, (void*)bounce})
+            if (p) (void)hipFree(p);
+    }
+};
+
+// runs: sorted, disjoint, non-adjacent, non-empty, inside [0, h->n).  mu held.
+int remove_runs_locked(ise_binary_index* h, const std::vector<BinRemoveRun>& runs, long long removed) {
+    const long long n_old = h->n, n_new = n_old - removed, first = runs[0].start;
+    const long long moved = n_new - first;  // destination rows [first, n_new) get a new row
+    hipStream_t st = h->stream;
+    BIN_TRY(hipDeviceSynchronize());  // nothing in flight reads the rows while they move
+    if (moved > 0) {
+        BinRemoveScratch sc;
+        const long long T = (long long)runs.size();
+        std::vector<uint32_t> g((size_t)T), cend((size_t)T);
+        long long c = 0;
+        for (long long t = 0; t < T; t++) {
+            g[(size_t)t] = (uint32_t)(runs[(size_t)t].start - c);
+            c += runs[(size_t)t].len;
+            cend[(size_t)t] = (uint32_t)c;
+        }
+        // slab: at most 256 MiB of rows in the bounce buffer, as the float index; a slab's units (16 bytes, or the
+        // 8-byte rows of ws == 1) stay below 2^31 whatever $ISE_REMOVE_SLAB_ROWS says
+        const size_t rb = (size_t)h->ws * 8;
+        const uint32_t upr = (uint32_t)std::max(1, h->ws / 2);
+        long long slab = ise_remove_slab_rows_();
+        if (slab <= 0) slab = std::max<long long>(1, (256ll << 20) / (long long)rb);
+        slab = std::min(slab, std::max<long long>(1, (1ll << 31) / (long long)upr));
+        slab = std::min(slab, moved);
+        BIN_TRY(hipMalloc((void**)&sc.g, (size_t)T * sizeof(uint32_t)));
+        BIN_TRY(hipMalloc((void**)&sc.cend, (size_t)T * sizeof(uint32_t)));
+        BIN_TRY(hipMalloc((void**)&sc.src_idx, (size_t)slab * sizeof(uint32_t)));
+        BIN_TRY(hipMalloc((void**)&sc.bounce, (size_t)slab * rb));
+        BIN_TRY(hipMemcpyAsync(sc.g, g.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        BIN_TRY(hipMemcpyAsync(sc.cend, cend.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        BIN_TRY(hipStreamSynchronize(st));  // g and cend are pageable host vectors
+        for (long long a = first; a < n_new; a += slab) {
+            const long long m = std::min(slab, n_new - a);
+            const unsigned gw = (unsigned)std::min<long long>((m + 255) / 256, (long long)h->num_cu * 8);
+            hipLaunchKernelGGL(remove_src_kernel, dim3(gw), dim3(256), 0, st, (const uint32_t*)sc.g, (const uint32_t*)sc.cend,
+                               (int)T, (uint32_t)a, (uint32_t)m, sc.src_idx);
+            // rows src_idx[0 .. m) -> bounce -> rows [a, a + m)
+            const uint32_t total = (uint32_t)(m * upr);
+            const uint32_t per = 64 * (h->ws == 1 ? BIN_REMOVE_UNROLL : REMOVE_UNROLL);
+            const uint32_t pieces = (total + per - 1) / per;
+            const unsigned grid = std::max(1u, std::min((pieces + 3) / 4, (unsigned)h->num_cu * 4u));  // 16 waves per CU
+            if (h->ws == 1) {
+                hipLaunchKernelGGL(binary_remove_words_kernel<true>, dim3(grid), dim3(256), 0, st, (const u64*)h->codes,
+                                   (const uint32_t*)sc.src_idx, (u64*)sc.bounce, total);
+                hipLaunchKernelGGL(binary_remove_words_kernel<false>, dim3(grid), dim3(256), 0, st, (const u64*)sc.bounce,
+                                   (const uint32_t*)nullptr, h->codes + a, total);
+            } else {
+                hipLaunchKernelGGL(remove_rows_kernel<true>, dim3(grid), dim3(256), 0, st, (const u32x4*)h->codes,
+                                   (const uint32_t*)sc.src_idx, (u32x4*)sc.bounce, total, upr);
+                hipLaunchKernelGGL(remove_rows_kernel<false>, dim3(grid), dim3(256), 0, st, (const u32x4*)sc.bounce,
+                                   (const uint32_t*)nullptr, (u32x4*)(h->codes + (size_t)a * h->ws), total, upr);
+            }
+            BIN_TRY(hipGetLastError());
+        }
+        BIN_TRY(hipStreamSynchronize(st));  // before the scratch is freed; a removal blocks
+    }
+    // the tail [n_new, n_old) keeps its stale rows: masked by row number, like the rows a reset leaves behind
+    h->n = n_new;
+    h->row_epoch++;  // rows were renumbered: selectors made before are stale
+    h->last_valid = false;  // the device has drained: nothing to order the next call behind
+    h->st_rm_calls++;
+    h->st_rm_rows += (uint64_t)removed;
+    h->st_rm_moved += (uint64_t)moved;
+    return ISE_OK;
+}
+}  // namespace
+
+extern "C" int ise_binary_index_remove_range(ise_binary_index_t* h, int64_t i0, int64_t i1, int64_t* n_removed) {
+    if (check_handle(h)) return ISE_E_INVALID;
+    if (n_removed) *n_removed = 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const long long a = std::max<long long>(i0, 0), b = std::min<long long>(i1, h->n);
+    if (a >= b) return ISE_OK;  // nothing to remove: no synchronisation, no counters
+    DeviceGuard gd(h->device);
+    if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
+    const int rc = remove_runs_locked(h, {BinRemoveRun{a, b - a}}, b - a);
+    if (rc == ISE_OK && n_removed) *n_removed = b - a;
+    return rc;
+}
+
+extern "C" int ise_binary_index_remove_ids_host(ise_binary_index_t* h, const int64_t* ids, int64_t n_ids, int64_t* n_removed) {
+    if (check_handle(h)) return ISE_E_INVALID;
+    if (n_removed) *n_removed = 0;
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return ise_fail_(ISE_E_INVALID, "ids is NULL");
+    if (n_ids == 0) return ISE_OK;
+    std::vector<long long> v;
+    std::vector<BinRemoveRun> runs;
+    long long removed = 0;
+    try {
+        v.reserve((size_t)n_ids);
+        for (int64_t i = 0; i < n_ids; i++)
+            if (ids[i] >= 0) v.push_back(ids[i]);
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+    } catch (const std::bad_alloc&) {
+        return ise_fail_(ISE_E_NOMEM, "remove_ids: host allocation failed");
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    try {
+        for (long long id : v) {
+            if (id >= h->n) break;  // sorted: the rest does not exist either
+            if (!runs.empty() && runs.back().start + runs.back().len == id) runs.back().len++;
+            else runs.push_back(BinRemoveRun{id, 1});
+            removed++;
+        }
+    } catch (const std::bad_alloc&) {
+        return ise_fail_(ISE_E_NOMEM, "remove_ids: host allocation failed");
+    }
+    if (removed == 0) return ISE_OK;  // nothing to remove: no synchronisation, no counters
+    DeviceGuard gd(h->device);
+    if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
+    const int rc = remove_runs_locked(h, runs, removed);
+    if (rc == ISE_OK && n_removed) *n_removed = removed;
+    return rc;
+}
+
+extern "C" int ise_binary_index_remove_stats(ise_binary_index_t* h, uint64_t* out3) {
+    if (check_handle(h)) return ISE_E_INVALID;
+    if (!out3) return ise_fail_(ISE_E_INVALID, "out3 is NULL");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out3[0] = h->st_rm_calls;
+    out3[1] = h->st_rm_rows;
+    out3[2] = h->st_rm_moved;
     return ISE_OK;
 }

@@ -19,6 +19,17 @@
 // and wave_select writes the kp smallest, SORTED, as the block's list.  binary_merge_kernel walks the blocks' lists
 // (merge_waves, ise_merge.hpp) and writes int32 D / int64 I.  A pass yields at most BIN_KPASS results per query; a
 // larger k repeats the pass with lo = (last key found) + 1 as the smallest key admitted.
+//
+// Selectors: binary_scan_masked_kernel / binary_range_masked_kernel are the same passes over the tiles
+// of a selector's row window, skipping every 64-row tile whose mask word is zero (BinMask); the unmasked kernels are
+// the same body with the mask compiled out.  binary_sel_census_kernel counts a bitmap's rows, window and non-empty
+// 64-row tiles.
+//
+// remove_ids: the stable in-place compaction of ise_remove.hpp (source map, ascending slabs, gather into a bounce
+// buffer, copy back, ordered by one stream).  Rows of ws >= 2 words are whole 16-byte units and move with
+// remove_rows_kernel (upr = ws / 2); the 8-byte rows of ws == 1 move with binary_remove_words_kernel below.  The tail
+// [n_new, n_old) is NOT zeroed: rows at or beyond n are masked by row number in every kernel here, and an add
+// overwrites whole padded rows.
 #pragma once
 #include <climits>
 
@@ -108,8 +119,20 @@ struct BinScanParams {
     u64* lists;       // [grid][16][BIN_KPASS]: one sorted list per block and query, KEY_PAD behind the last
 };
 
-template <int WT>
-__global__ __launch_bounds__(BIN_WAVES * 64) void binary_scan_kernel(const BinScanParams p) {
+// A selector's device side (ise_binary_selector, ise_binary_scan.hip): the bitmap read as one 8-byte word per 64-row
+// tile -- bit r & 63 of word r >> 6, which is bit r & 31 of uint32 word r >> 5 -- and the tiles [tile0, tile1) of
+// the window from the first to the last selected row.  The allocation holds a whole word for every tile below
+// ceil(ntotal / 64); bits at or beyond ntotal are zero.
+struct BinMask {
+    const u64* words;
+    long long tile0, tile1;
+};
+
+// MASK: the pass runs over the window's tiles only; a wave reads the tile's mask word (wave-uniform, before any row
+// load is issued) and skips a tile without a selected row -- no load, no append, no cut check.  Behind `valid`
+// nothing differs from the unmasked pass, and all 64 lanes stay active at every readlane / ballot.
+template <int WT, bool MASK>
+__device__ __forceinline__ void binary_scan_body(const BinScanParams p, const BinMask mk) {
     extern __shared__ __align__(16) unsigned char smem_bin[];
     u64* buf = reinterpret_cast<u64*>(smem_bin);  // [BIN_WAVES][16][BIN_CAP]
     int* cnts = reinterpret_cast<int*>(buf + BIN_WAVES * BIN_QT * BIN_CAP);  // [BIN_WAVES][16] keys held at the end
@@ -142,10 +165,16 @@ __global__ __launch_bounds__(BIN_WAVES * 64) void binary_scan_kernel(const BinSc
         }
     };
 
-    const long long ntiles = (p.n + 63) >> 6;
-    for (long long t = (long long)blockIdx.x * BIN_WAVES + w; t < ntiles; t += (long long)gridDim.x * BIN_WAVES) {
+    const long long ntiles = MASK ? mk.tile1 : (p.n + 63) >> 6;
+    for (long long t = (MASK ? mk.tile0 : 0ll) + (long long)blockIdx.x * BIN_WAVES + w; t < ntiles;
+         t += (long long)gridDim.x * BIN_WAVES) {
         const long long row = t * 64 + lane;
-        const bool valid = row < p.n;
+        u64 mw = ~0ull;
+        if constexpr (MASK) {
+            mw = readlane_u64(mk.words[t], 0);  // t is wave-uniform: one scalar 8-byte load
+            if (mw == 0ull) continue;
+        }
+        const bool valid = MASK ? (row < p.n && ((mw >> lane) & 1ull)) : row < p.n;
         int acc[BIN_QT];
         hamming16<WT>(p.codes, p.ws, row, valid, qr, acc);
 #pragma unroll
@@ -184,6 +213,16 @@ __global__ __launch_bounds__(BIN_WAVES * 64) void binary_scan_kernel(const BinSc
         const int nw = wave_select<2 * BIN_WAVES>(kk, BIN_WAVES * BIN_CAP, kp, dst, &kth_unused);
         for (int i = nw + lane; i < kp; i += 64) dst[i] = KEY_PAD;
     }
+}
+
+template <int WT>
+__global__ __launch_bounds__(BIN_WAVES * 64) void binary_scan_kernel(const BinScanParams p) {
+    binary_scan_body<WT, false>(p, BinMask{});
+}
+
+template <int WT>
+__global__ __launch_bounds__(BIN_WAVES * 64) void binary_scan_masked_kernel(const BinScanParams p, const BinMask mk) {
+    binary_scan_body<WT, true>(p, mk);
 }
 
 // One block per query of the tile: the k-way walk over the blocks' lists (merge_waves), then positions
@@ -232,23 +271,32 @@ struct BinRangeParams {
     long long* I;
 };
 
-template <int WT, bool FILL>
-__global__ __launch_bounds__(BIN_WAVES * 64) void binary_range_kernel(const BinRangeParams p) {
+// MASK: the segments cut the selector's window instead of [0, n): segment s starts at mk.tile0 * 64 + s * seg_rows --
+// a multiple of 64 in absolute row numbers, so a tile's mask word is still index row >> 6 -- and the last one ends
+// at mk.tile1 * 64 or n; a tile without a selected row is skipped before its loads, as in the scan.
+template <int WT, bool FILL, bool MASK>
+__device__ __forceinline__ void binary_range_body(const BinRangeParams p, const BinMask mk) {
     extern __shared__ __align__(16) unsigned char smem_bin[];
     u64* qs = reinterpret_cast<u64*>(smem_bin);  // WT == 0: [16][ws]
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     BinQueries<WT> qr;
     qr.init(qs, p.qpad, p.ws, p.nqt);
     const int s = blockIdx.x * BIN_WAVES + w;
-    const long long r0 = (long long)s * p.seg_rows;
-    const long long r1 = r0 + p.seg_rows < p.n ? r0 + p.seg_rows : p.n;
+    const long long r0 = (MASK ? mk.tile0 * 64 : 0ll) + (long long)s * p.seg_rows;
+    const long long rend = MASK && mk.tile1 * 64 < p.n ? mk.tile1 * 64 : p.n;
+    const long long r1 = r0 + p.seg_rows < rend ? r0 + p.seg_rows : rend;
     const u64 lt_mask = (1ull << lane) - 1ull;
     int cnt_v = 0;  // query q in lane q
     u64 base_v = 0;
     if (FILL && lane < p.nqt) base_v = (u64)(p.lims[lane] + p.offs[(size_t)lane * p.S + s]);
     for (long long rb = r0; rb < r1; rb += 64) {
         const long long row = rb + lane;
-        const bool valid = row < r1;
+        u64 mw = ~0ull;
+        if constexpr (MASK) {
+            mw = readlane_u64(mk.words[rb >> 6], 0);  // rb is wave-uniform
+            if (mw == 0ull) continue;
+        }
+        const bool valid = MASK ? (row < r1 && ((mw >> lane) & 1ull)) : row < r1;
         int acc[BIN_QT];
         hamming16<WT>(p.codes, p.ws, row, valid, qr, acc);
 #pragma unroll
@@ -272,6 +320,16 @@ __global__ __launch_bounds__(BIN_WAVES * 64) void binary_range_kernel(const BinR
         }
     }
     if (!FILL && lane < p.nqt) p.counts[(size_t)lane * p.S + s] = cnt_v;
+}
+
+template <int WT, bool FILL>
+__global__ __launch_bounds__(BIN_WAVES * 64) void binary_range_kernel(const BinRangeParams p) {
+    binary_range_body<WT, FILL, false>(p, BinMask{});
+}
+
+template <int WT, bool FILL>
+__global__ __launch_bounds__(BIN_WAVES * 64) void binary_range_masked_kernel(const BinRangeParams p, const BinMask mk) {
+    binary_range_body<WT, FILL, true>(p, mk);
 }
 
 // inclusive scan over the block's threads (NT a multiple of 64, at most 1024); wsum: NT / 64 entries of LDS
@@ -351,5 +409,76 @@ static __global__ void binary_fill_kernel(int* D, long long* I, long long cnt) {
     if (i < cnt) {
         D[i] = INT_MAX;
         I[i] = -1ll;
+    }
+}
+
+// ---- selectors: the census of a bitmap, read as one 8-byte word per 64-row tile.  Bits at or beyond n are cleared
+// (a user's bitmap); out[0] selected rows, out[1] non-empty 64-row tiles, out[2] first selected row (init: ~0),
+// out[3] last selected row + 1 (init: 0)
+static __global__ __launch_bounds__(256) void binary_sel_census_kernel(u64* words, long long nwords, long long n,
+                                                                       unsigned long long* out) {
+    const long long wd = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long cnt = 0, tiles = 0, lo = ~0ull, hi = 0;
+    if (wd < nwords) {
+        u64 v = words[wd];
+        const long long left = n - wd * 64;
+        if (left < 64) {
+            const u64 keep = left <= 0 ? 0ull : ((1ull << left) - 1ull);
+            if (v & ~keep) words[wd] = v & keep;
+            v &= keep;
+        }
+        if (v) {
+            cnt = (unsigned long long)__popcll(v);
+            tiles = 1;
+            lo = (unsigned long long)(wd * 64 + (__ffsll((long long)v) - 1));
+            hi = (unsigned long long)(wd * 64 + (64 - __clzll((long long)v)));
+        }
+    }
+    // one atomic per wave and field
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_xor(cnt, o);
+        tiles += __shfl_xor(tiles, o);
+        const unsigned long long l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+    }
+    if ((threadIdx.x & 63) == 0 && cnt) {
+        atomicAdd(out + 0, cnt);
+        atomicAdd(out + 1, tiles);
+        atomicMin(out + 2, lo);
+        atomicMax(out + 3, hi);
+    }
+}
+
+// ---- remove_ids, ws == 1: rows of 8 bytes, half a 16-byte unit, which remove_rows_kernel (ise_remove.hpp) cannot
+// gather.  The same shape: dst[i] <- src[GATHER ? idx[i] : i], i < total, dealt to the waves grid-stride in pieces of
+// BIN_REMOVE_UNROLL wave-loads; a wave issues all of a piece's loads before its first store.
+#define BIN_REMOVE_UNROLL 8 /* independent 8-byte loads per lane in flight (4 KiB per wave and piece) */
+template <bool GATHER>
+__global__ __launch_bounds__(256) void binary_remove_words_kernel(const u64* __restrict__ src, const uint32_t* __restrict__ idx,
+                                                                  u64* __restrict__ dst, uint32_t total) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
+    const uint32_t piece = 64 * BIN_REMOVE_UNROLL;
+    const uint32_t npieces = (total + piece - 1) / piece;
+    for (uint32_t p = wave; p < npieces; p += nwaves) {
+        const uint32_t base = p * piece + lane;
+        // a piece's tail past `total` re-reads the last row (no branch between the loads) and is not stored
+        size_t s[BIN_REMOVE_UNROLL];
+#pragma unroll
+        for (int t = 0; t < BIN_REMOVE_UNROLL; t++) {
+            const uint32_t i = min(base + 64 * t, total - 1);
+            s[t] = GATHER ? (size_t)idx[i] : (size_t)i;
+        }
+        u64 v[BIN_REMOVE_UNROLL];
+#pragma unroll
+        for (int t = 0; t < BIN_REMOVE_UNROLL; t++) v[t] = __builtin_nontemporal_load(src + s[t]);
+#pragma unroll
+        for (int t = 0; t < BIN_REMOVE_UNROLL; t++) {
+            const uint32_t i = base + 64 * t;
+            if (i < total) dst[i] = v[t];
+        }
     }
 }

@@ -893,6 +893,7 @@ extern "C" int ise_refresh_env_knobs(void) {
     knobs().refresh();
     return ISE_OK;
 }
+int ise_remove_slab_rows_() { return knobs().remove_slab_rows.load(std::memory_order_relaxed); }  // ise_binary_scan.hip
 static bool force_exact() { return knobs().force_exact.load(std::memory_order_relaxed) != 0; }
 static bool byte_alloc_refused() { return knobs().fail_byte_alloc.load(std::memory_order_relaxed) != 0; }
 

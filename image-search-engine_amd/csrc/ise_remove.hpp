@@ -27,7 +27,7 @@
 #define REMOVE_UNROLL 4       /* independent 16-byte loads per lane in flight (1 KiB per wave-instruction) */
 
 // src_idx[j - a] = src(j) for j in [a, b)
-__global__ __launch_bounds__(256) void remove_src_kernel(const uint32_t* __restrict__ g, const uint32_t* __restrict__ cend,
+static __global__ __launch_bounds__(256) void remove_src_kernel(const uint32_t* __restrict__ g, const uint32_t* __restrict__ cend,
                                                          int n_runs, uint32_t a, uint32_t count,
                                                          uint32_t* __restrict__ src_idx) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {

@@ -27,7 +27,13 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          ``range_search`` / ``reconstruct_n`` / ``reset`` (csrc/ise_binary_scan.hpp); the
                                          near-duplicate search the reference's DHASH method (backend/engine.py:82-91)
                                          answers with a dict lookup of bit-identical hashes; never called by the reference
-    write_index_binary / read_index_binary   Faiss's names for IndexBinaryFlat files ("IBxF")
+    index.remove_ids / params=           the binary index takes the same ``remove_ids`` arguments and the same
+                                         ``SearchParameters(sel=...)`` on ``search`` / ``range_search`` / ``search_torch`` as
+                                         the float index: a masked Hamming pass that skips 64-row tiles without a selected
+                                         row, an in-place compaction of the code rows (csrc/ise_binary_scan.hpp)
+    IndexBinaryIDMap(index)              Faiss's id-mapping wrapper over a binary index: ``add_with_ids``, external ids in
+                                         results, selectors and ``remove_ids``
+    write_index_binary / read_index_binary   Faiss's names for IndexBinaryFlat ("IBxF") and IndexBinaryIDMap ("IBMp") files
 
 All arithmetic runs on the MI355X through ``include/ise_knn.h``; there is no
 CPU path here.  Without the HIP library or without a GPU the constructors and
@@ -155,8 +161,9 @@ class IDSelectorNot(IDSelector):
 
 
 class SearchParameters:
-    """faiss.SearchParameters: ``sel`` is an ``IDSelector`` (or a ``DeviceSelector`` made by
-    ``IndexFlat.make_selector``, an extension), or None for an unfiltered search."""
+    """faiss.SearchParameters: ``sel`` is an ``IDSelector`` (or a ``DeviceSelector`` made by ``IndexFlat.make_selector``
+    / a ``BinaryDeviceSelector`` made by ``IndexBinaryFlat.make_selector``, extensions), or None for an unfiltered
+    search."""
 
     def __init__(self, sel=None):
         if sel is not None and not isinstance(sel, (IDSelector, DeviceSelector)):
@@ -202,25 +209,29 @@ class DeviceSelector:
     bitmap, its row window and counts.  Valid while the index keeps its rows: after ``add``, ``remove_ids`` or
     ``reset`` a search with it raises ``IseError``."""
 
-    def __init__(self, index: "IndexFlat", lowered):
+    _ABI = "ise_selector"  # the family of entry points (include/ise_knn.h); "tiles" of ``info`` are 16-row tiles
+
+    def _fn(self, name: str):
+        return getattr(_n.lib, f"{self._ABI}_{name}")
+
+    def __init__(self, index, lowered):
         self.index = index
         self._s = ctypes.c_void_p()
         kind = lowered[0]
         if kind == "range":
-            _n.check(_n.lib.ise_selector_create_range(index._h, int(lowered[1]), int(lowered[2]), ctypes.byref(self._s)))
+            _n.check(self._fn("create_range")(index._h, int(lowered[1]), int(lowered[2]), ctypes.byref(self._s)))
         elif kind == "ids":
             ids = _ids_array(lowered[1])
-            _n.check(_n.lib.ise_selector_create_ids(index._h, ids.ctypes.data, ids.size, int(lowered[2]),
-                                                    ctypes.byref(self._s)))
+            _n.check(self._fn("create_ids")(index._h, ids.ctypes.data, ids.size, int(lowered[2]), ctypes.byref(self._s)))
         else:
             words = np.ascontiguousarray(lowered[1], dtype="<u4")
-            _n.check(_n.lib.ise_selector_create_bitmap(index._h, words.ctypes.data, words.size, ctypes.byref(self._s)))
+            _n.check(self._fn("create_bitmap")(index._h, words.ctypes.data, words.size, ctypes.byref(self._s)))
 
     def close(self) -> None:
         s = getattr(self, "_s", None)
         if s is not None and s.value:
             try:
-                _n.lib.ise_selector_destroy(s)
+                self._fn("destroy")(s)
             except Exception:  # interpreter shutdown
                 pass
             s.value = None
@@ -229,9 +240,17 @@ class DeviceSelector:
 
     def info(self) -> dict:
         out = (ctypes.c_int64 * 5)()
-        _n.check(_n.lib.ise_selector_info(self._s, out))
+        _n.check(self._fn("info")(self._s, out))
         return {"ntotal": int(out[0]), "selected": int(out[1]), "window": (int(out[2]), int(out[3])),
                 "tiles": int(out[4])}
+
+
+class BinaryDeviceSelector(DeviceSelector):
+    """``IndexBinaryFlat.make_selector``: the same object over a binary index (ise_binary_selector_*); "tiles" of
+    ``info`` are the non-empty 64-row tiles, the unit the masked Hamming pass skips.  It serves the binary index it
+    was made from only; a float index refuses it, and a binary index refuses a float index's ``DeviceSelector``."""
+
+    _ABI = "ise_binary_selector"
 
 
 def _runs_to_ids(runs: np.ndarray) -> np.ndarray:
@@ -455,6 +474,8 @@ class IndexFlat:
 
     def _with_selector(self, sel, fn):
         """``fn(handle)`` with the device selector of ``sel``; one built here is destroyed before returning."""
+        if isinstance(sel, BinaryDeviceSelector):
+            raise TypeError("a binary index's selector cannot filter a float index")
         if isinstance(sel, DeviceSelector):
             return fn(sel._s)
         ds = self.make_selector(sel)
@@ -911,20 +932,78 @@ class IndexBinaryFlat:
     def reconstruct(self, i: int) -> np.ndarray:
         return self.reconstruct_n(int(i), 1)[0]
 
-    def search(self, x, k: int):
-        """(D int32 (nq, k), I int64 (nq, k)), fresh arrays: Hamming distance ascending, ties by ascending id."""
+    def remove_ids(self, sel) -> int:
+        """faiss ``index.remove_ids``, with the arguments of ``IndexFlat.remove_ids``: an ``IDSelector`` or an int64
+        array-like taken as a batch; returns how many rows went.  The other rows keep their order and are renumbered
+        densely (``IndexBinaryIDMap`` keeps external ids).  In place on the device (include/ise_knn.h,
+        ise_binary_index_remove_ids_host)."""
+        out = ctypes.c_int64(0)
+        if isinstance(sel, IDSelectorRange):
+            _n.check(_n.lib.ise_binary_index_remove_range(self._h, sel.imin, sel.imax, ctypes.byref(out)))
+            return int(out.value)
+        if isinstance(sel, IDSelectorBatch):
+            ids = sel.ids
+        elif isinstance(sel, IDSelector):  # Not, or a user's selector: complemented / evaluated against ntotal here
+            ids = _runs_to_ids(sel.runs(self.ntotal))
+        else:
+            ids = _ids_array(sel)
+        if ids.size:
+            _n.check(_n.lib.ise_binary_index_remove_ids_host(self._h, ids.ctypes.data, ids.size, ctypes.byref(out)))
+        return int(out.value)
+
+    def remove_stats(self) -> dict:
+        """Removals since the index was created (include/ise_knn.h, ise_binary_index_remove_stats): calls that removed
+        something, rows removed, rows that moved to a new position."""
+        out = (ctypes.c_uint64 * 3)()
+        _n.check(_n.lib.ise_binary_index_remove_stats(self._h, out))
+        return {"remove_calls": int(out[0]), "rows_removed": int(out[1]), "rows_moved": int(out[2])}
+
+    # -- selector-filtered search (faiss.SearchParameters(sel=...))
+    def make_selector(self, sel) -> BinaryDeviceSelector:
+        """Extension (not in Faiss): ``sel`` lowered to a device object that can be reused across ``search``,
+        ``range_search`` and ``search_torch`` calls through ``SearchParameters(sel=...)`` until the index changes."""
+        return BinaryDeviceSelector(self, lower_selector(sel, self.ntotal))
+
+    def _with_selector(self, sel, fn):
+        """``fn(handle)`` with the device selector of ``sel``; one built here is destroyed before returning."""
+        if isinstance(sel, BinaryDeviceSelector):
+            return fn(sel._s)
+        if isinstance(sel, DeviceSelector):
+            raise TypeError("a float index's selector cannot filter a binary index")
+        ds = self.make_selector(sel)
+        try:
+            return fn(ds._s)
+        finally:
+            ds.close()
+
+    def sel_stats(self) -> dict:
+        """Filtered search batches, masked passes launched (one per 16 queries and per 32 results), filtered range
+        batches (include/ise_knn.h, ise_binary_index_sel_stats)."""
+        out = (ctypes.c_uint64 * 3)()
+        _n.check(_n.lib.ise_binary_index_sel_stats(self._h, out))
+        return {"sel_batches": int(out[0]), "sel_passes": int(out[1]), "sel_range_batches": int(out[2])}
+
+    def search(self, x, k: int, params=None):
+        """(D int32 (nq, k), I int64 (nq, k)), fresh arrays: Hamming distance ascending, ties by ascending id.
+        ``params=SearchParameters(sel=...)``: among the rows the selector names only."""
         x = _as_codes(x, self.code_size)
         k = int(k)
         assert k > 0
         nq = x.shape[0]
         D = np.empty((nq, k), dtype=np.int32)
         I = np.empty((nq, k), dtype=np.int64)
+        sel = _params_sel(params)
+        if sel is not None:
+            self._with_selector(sel, lambda s: _n.check(_n.lib.ise_binary_index_search_sel_host(
+                self._h, x.ctypes.data, nq, k, s, D.ctypes.data, I.ctypes.data)))
+            return D, I
         _n.check(_n.lib.ise_binary_index_search_host(self._h, x.ctypes.data, nq, k, D.ctypes.data, I.ctypes.data))
         return D, I
 
-    def search_torch(self, xq, k: int):
+    def search_torch(self, xq, k: int, params=None):
         """Device-resident search: CUDA uint8 (nq, d / 8) in, CUDA (D int32, I int64) out, enqueued on the current
-        torch stream (no host synchronisation)."""
+        torch stream (no host synchronisation).  ``params=SearchParameters(sel=...)`` as ``search``; a selector that is
+        not a ``BinaryDeviceSelector`` is built and destroyed here, which waits for the device."""
         import torch
 
         assert xq.is_cuda and xq.dtype == torch.uint8 and xq.dim() == 2 and xq.shape[1] == self.code_size
@@ -933,19 +1012,34 @@ class IndexBinaryFlat:
         D = torch.empty((nq, int(k)), dtype=torch.int32, device=xq.device)
         I = torch.empty((nq, int(k)), dtype=torch.int64, device=xq.device)
         st = torch.cuda.current_stream(xq.device).cuda_stream
+        sel = _params_sel(params)
+        if sel is not None:
+            def run(s):
+                with self._lock:
+                    _n.check(_n.lib.ise_binary_index_search_sel_device(self._h, xq.data_ptr(), nq, int(k), s,
+                                                                       D.data_ptr(), I.data_ptr(), st))
+            self._with_selector(sel, run)
+            return D, I
         with self._lock:
             _n.check(_n.lib.ise_binary_index_search_device(self._h, xq.data_ptr(), nq, int(k), D.data_ptr(),
                                                            I.data_ptr(), st))
         return D, I
 
-    def range_search(self, x, radius: int):
+    def range_search(self, x, radius: int, params=None):
         """(lims uint64 (nq + 1,), D int32, I int64), fresh arrays: query i's rows are ``I[lims[i]:lims[i+1]]`` in
         ascending id order, every row with distance < radius (strict, as Faiss's hamming_range_search), D the numbers
-        ``search`` reports.  Faiss's Python wrapper may hand D out as float32; here it stays int32."""
+        ``search`` reports.  Faiss's Python wrapper may hand D out as float32; here it stays int32.
+        ``params=SearchParameters(sel=...)``: among the selected rows only."""
         x = _as_codes(x, self.code_size)
         nq = x.shape[0]
         res = ctypes.c_void_p()
-        _n.check(_n.lib.ise_binary_index_range_search_host(self._h, x.ctypes.data, nq, int(radius), ctypes.byref(res)))
+        sel = _params_sel(params)
+        if sel is not None:
+            self._with_selector(sel, lambda s: _n.check(_n.lib.ise_binary_index_range_search_sel_host(
+                self._h, x.ctypes.data, nq, int(radius), s, ctypes.byref(res))))
+        else:
+            _n.check(_n.lib.ise_binary_index_range_search_host(self._h, x.ctypes.data, nq, int(radius),
+                                                               ctypes.byref(res)))
         try:
             n = ctypes.c_int64()
             lp, dp_, ip = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
@@ -999,17 +1093,133 @@ def parse_binary_flat(buf: bytes):
     return d, xb
 
 
-def write_index_binary(index: IndexBinaryFlat, path) -> None:
+class IndexBinaryIDMap:
+    """faiss.IndexBinaryIDMap over a binary flat index: rows carry the caller's 64-bit ids, which survive ``remove_ids``
+    (the sub-index renumbers its rows; ``id_map[row]`` follows).  The mapping is host numpy, off the hot path.
+    Selectors -- in ``remove_ids`` and in ``params=`` -- are over EXTERNAL ids."""
+
+    def __init__(self, index: IndexBinaryFlat):
+        assert index.ntotal == 0, "IndexBinaryIDMap wraps an empty index (Faiss: index is empty on input)"
+        self.index = index
+        self.id_map = np.zeros(0, dtype=np.int64)
+
+    d = property(lambda self: self.index.d)
+    code_size = property(lambda self: self.index.code_size)
+    is_trained = property(lambda self: self.index.is_trained)
+    ntotal = property(lambda self: self.index.ntotal)
+
+    def add(self, x) -> None:
+        raise RuntimeError("add does not work with IndexBinaryIDMap, call add_with_ids")  # Faiss throws the same
+
+    def add_with_ids(self, x, ids) -> None:
+        x = _as_codes(x, self.index.code_size)
+        ids = _ids_array(ids)
+        assert ids.shape[0] == x.shape[0], "one id per row"
+        self.index.add(x)
+        self.id_map = np.concatenate((self.id_map, ids))
+
+    def _map(self, I: np.ndarray) -> np.ndarray:
+        out = np.full(I.shape, -1, dtype=np.int64)
+        ok = I >= 0
+        out[ok] = self.id_map[I[ok]]
+        return out
+
+    def _row_params(self, params):
+        """A selector over EXTERNAL ids -> one over rows (a bitmap from ``sel.members(id_map)``)."""
+        sel = _params_sel(params)
+        if sel is None:
+            return None
+        if isinstance(sel, DeviceSelector):
+            raise TypeError("IndexBinaryIDMap takes an IDSelector over external ids, not a DeviceSelector over rows")
+        return SearchParameters(sel=_RowMask(sel.members(self.id_map)))
+
+    def search(self, x, k: int, params=None):
+        D, I = self.index.search(x, k, params=self._row_params(params))
+        return D, self._map(I)
+
+    def range_search(self, x, radius: int, params=None):
+        lims, D, I = self.index.range_search(x, radius, params=self._row_params(params))
+        return lims, D, self._map(I)
+
+    def remove_ids(self, sel) -> int:
+        """``sel`` selects EXTERNAL ids (a selector, or an int64 array-like taken as a batch)."""
+        if not isinstance(sel, IDSelector):
+            sel = IDSelectorBatch(sel)
+        gone = sel.members(self.id_map)
+        rows = np.flatnonzero(gone).astype(np.int64)
+        if rows.size == 0:
+            return 0
+        n = self.index.remove_ids(rows)
+        assert n == rows.size
+        self.id_map = self.id_map[~gone]
+        return n
+
+    def reset(self) -> None:
+        self.index.reset()
+        self.id_map = np.zeros(0, dtype=np.int64)
+
+
+# IndexBinaryIDMap [upstream-faiss index_write.cpp write_index_binary, restated from memory of the published format and
+# UNPINNED like the three layouts above]:
+#   fourcc "IBMp"; the binary header (int32 d; int32 code_size; int64 ntotal; uint8 is_trained; int32 metric_type); the
+#   sub-index as "IBxF" writes it; then the id vector: uint64 count (= ntotal); count int64.
+_FOURCC_BINARY_IDMAP = b"IBMp"
+
+
+def serialize_binary_idmap(d: int, xb, ids) -> bytes:
+    sub = serialize_binary_flat(d, xb)
+    _, _, cs, n, _, _ = _BHDR.unpack_from(sub, 0)
+    ids = np.ascontiguousarray(ids, dtype="<i8").reshape(-1)
+    assert ids.size == n, "one id per row"
+    return _BHDR.pack(_FOURCC_BINARY_IDMAP, int(d), cs, n, 1, 1) + sub + struct.pack("<Q", n) + ids.tobytes()
+
+
+def parse_binary_idmap(buf: bytes):
+    """-> (d, xb uint8 (n, d / 8), ids int64 (n,)); raises RuntimeError on a foreign or truncated file."""
+    if len(buf) >= 4 and buf[:4] != _FOURCC_BINARY_IDMAP:
+        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexBinaryIDMap")
+    if len(buf) < _BHDR.size:
+        raise RuntimeError("truncated binary index file")
+    _, d, cs, n, _, _ = _BHDR.unpack_from(buf, 0)
+    d2, xb = parse_binary_flat(buf[_BHDR.size:])
+    if d2 != d or xb.shape[1] != cs or xb.shape[0] != n:
+        raise RuntimeError("corrupt IndexBinaryIDMap: the sub-index does not match the header")
+    off = 2 * _BHDR.size + 8 + n * cs
+    if len(buf) < off + 8:
+        raise RuntimeError("truncated IndexBinaryIDMap id vector")
+    (count,) = struct.unpack_from("<Q", buf, off)
+    if count != n:
+        raise RuntimeError("corrupt IndexBinaryIDMap: the id vector does not have one id per row")
+    if len(buf) < off + 8 + 8 * count:
+        raise RuntimeError("truncated IndexBinaryIDMap id vector")
+    ids = np.frombuffer(buf, dtype="<i8", count=count, offset=off + 8).astype(np.int64)
+    return d, xb, ids
+
+
+def write_index_binary(index, path) -> None:
     with open(str(path), "wb") as f:
-        f.write(serialize_binary_flat(index.d, index.reconstruct_n(0, index.ntotal)))
+        if isinstance(index, IndexBinaryIDMap):
+            sub = index.index
+            f.write(serialize_binary_idmap(sub.d, sub.reconstruct_n(0, sub.ntotal), index.id_map))
+        else:
+            f.write(serialize_binary_flat(index.d, index.reconstruct_n(0, index.ntotal)))
 
 
-def read_index_binary(path, device: int | None = None) -> IndexBinaryFlat:
+def read_index_binary(path, device: int | None = None):
+    """-> IndexBinaryFlat, or IndexBinaryIDMap for a file written from one."""
     with open(str(path), "rb") as f:
         buf = f.read()
-    d, xb = parse_binary_flat(buf)
+    ids = None
+    if buf[:4] == _FOURCC_BINARY_IDMAP:
+        d, xb, ids = parse_binary_idmap(buf)
+    else:
+        d, xb = parse_binary_flat(buf)
     index = IndexBinaryFlat(d, device)
-    if xb.shape[0]:
+    if ids is not None:
+        index = IndexBinaryIDMap(index)
+        if xb.shape[0]:
+            index.add_with_ids(xb, ids)
+    elif xb.shape[0]:
         index.add(xb)
     return index
 

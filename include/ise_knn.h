@@ -300,6 +300,53 @@ int ise_binary_range_result_get(const ise_binary_range_result_t* r, int64_t* nq,
 int ise_binary_range_result_destroy(ise_binary_range_result_t* r); /* NULL is a no-op */
 int ise_binary_index_stats(ise_binary_index_t* h, uint64_t* out3);
 
+/* remove_ids, selectors and selector-filtered search on the binary index (Faiss: IndexBinaryFlat::remove_ids,
+ * SearchParameters(sel=...), IndexBinaryIDMap on top of them in faiss_compat.py).  The semantics are those of the
+ * float index, documented at ise_index_remove_ids_host and ise_selector_* above:
+ *   removal       duplicate, negative and out-of-range ids are ignored; the rows that stay keep their order and are
+ *                 renumbered densely, in place on the device (the capacity is kept; the rows behind the new ntotal are
+ *                 not zeroed: every kernel masks them by row number).  A call that removes nothing returns at once and
+ *                 counts nothing.  A removal blocks, and other calls on the handle run entirely before or entirely after
+ *                 it.  remove_stats: out3[0] = calls that removed something, out3[1] = rows removed, out3[2] = rows that
+ *                 moved to a new position (n_new - first removed row, summed)
+ *   selectors     a device bitmap over the rows of ONE binary index: bit r & 31 of uint32 word r >> 5, bits at or beyond
+ *                 ntotal cleared at creation, the allocation padded to an even word count so that the mask of a 64-row
+ *                 tile is one aligned 8-byte word.  create_range: rows [i0, i1) clipped to [0, ntotal); create_ids: the
+ *                 ids (host pointer, any order, duplicates and out-of-range values ignored), or with invert != 0 every
+ *                 OTHER row; create_bitmap: exactly ceil(ntotal / 32) words.  info: out5 = ntotal, selected rows, first
+ *                 selected row, last selected row + 1 (0, 0 for an empty selection), non-empty 64-row tiles
+ *   validity      a selector is good only for the handle it was made from and only while that handle's ntotal and ROW
+ *                 EPOCH stand: add changes ntotal; reset (of a non-empty index) and every removal that removes something
+ *                 bump the epoch, so remove + add back to the old ntotal is caught too.  Every filtered entry point
+ *                 checks this first -- also for nq == 0 or an empty index -- and returns ISE_E_INVALID with a message
+ *                 naming what changed; a stale bitmap is never read
+ *   search        the k best rows AMONG THE SELECTED ONES: int32 distance ascending, ties by ascending id, unfilled slots
+ *                 INT32_MAX / -1 (a selection smaller than k); k up to ISE_MAX_K.  One masked pass per 16 queries and per
+ *                 32 results over the 64-row tiles from the first to the last selected row; a tile without a selected row
+ *                 is not loaded.  An empty selection or an empty index costs a fill and no pass
+ *   range search  every selected row with dist < radius, per query in ascending id order; radius <= 0 and an empty
+ *                 selection return nothing without a pass
+ *   stats         filtered calls count here only (ise_binary_index_stats keeps its meanings): out3[0] = filtered search
+ *                 batches, out3[1] = masked passes launched, out3[2] = filtered range batches */
+typedef struct ise_binary_selector ise_binary_selector_t;
+int ise_binary_index_remove_ids_host(ise_binary_index_t* h, const int64_t* ids, int64_t n_ids, int64_t* n_removed);
+int ise_binary_index_remove_range(ise_binary_index_t* h, int64_t i0, int64_t i1, int64_t* n_removed);
+int ise_binary_index_remove_stats(ise_binary_index_t* h, uint64_t* out3);
+int ise_binary_selector_create_range(ise_binary_index_t* h, int64_t i0, int64_t i1, ise_binary_selector_t** out);
+int ise_binary_selector_create_ids(ise_binary_index_t* h, const int64_t* ids_host, int64_t n_ids, int invert,
+                                   ise_binary_selector_t** out);
+int ise_binary_selector_create_bitmap(ise_binary_index_t* h, const uint32_t* words_host, int64_t n_words,
+                                      ise_binary_selector_t** out);
+int ise_binary_selector_info(const ise_binary_selector_t* sel, int64_t* out5);
+int ise_binary_selector_destroy(ise_binary_selector_t* sel); /* NULL is a no-op */
+int ise_binary_index_search_sel_host(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int k,
+                                     const ise_binary_selector_t* sel, int32_t* D, int64_t* I);
+int ise_binary_index_search_sel_device(ise_binary_index_t* h, const uint8_t* q_dev, int64_t nq, int k,
+                                       const ise_binary_selector_t* sel, int32_t* D_dev, int64_t* I_dev, void* stream);
+int ise_binary_index_range_search_sel_host(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int32_t radius,
+                                           const ise_binary_selector_t* sel, ise_binary_range_result_t** out);
+int ise_binary_index_sel_stats(ise_binary_index_t* h, uint64_t* out3);
+
 /* Shard-local search for the multi-GPU path: writes nq x k
  * packed candidates, sorted best-first, suitable for one all-gather:
  *   key = (order-preserving uint32 image of the score) << 32 | (row + id_base)
