@@ -917,7 +917,7 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
     pl->half = shadow_ok && (pl->byte || pl->kc <= SHADOW_MAX_KC);
     const size_t rb = pl->byte ? byte_row_bytes(h) : (pl->half ? shadow_row_bytes(h) : row_bytes(h));
     auto lds_bytes = [&](int waves, int T) {
-        if (pl->byte) return scan_lds_layout(qs_stride_byte(h), waves, T, pl->kb, true);
+        if (pl->byte) return scan_lds_layout(qs_stride_byte(h), waves, T, pl->kb, true, scan_seeded_boot(true, waves, T));
         return pl->half ? scan_lds_layout(qs_stride_half(h), waves, T, pl->kb, true) : scan_lds_bytes(h, waves, T, pl->kb);
     };
     pl->ch = chunk_steps_rb(rb);

@@ -38,6 +38,12 @@
 //   boot   every wave scores its first row tile and dumps all 16x16 keys; two block
 //          barriers later the query has a block list bootw of between k and kb of
 //          the best of those W*16 rows (windowed cut) and a threshold tauS = the cut.
+//          SEEDED boot (byte shadow rows, T = 1, W = 8; blocks whose every wave reads the exchange): no cut.  A
+//          wave's first TWO row tiles are the boot window; their 2 x 16 x 16 keys go unfiltered to an LDS home.  The
+//          block's best first-tile key per query is folded with LDS atomics and published by the last wave to
+//          arrive; behind the second tile (one barrier) the query's owner wave reads the exchange and seeds bootw
+//          with the home keys at or below the bound, tauS = the bound; a second barrier, then steady state.  Without
+//          a bound, or with more than kb home keys under it, the owner cuts the 256 home keys as above.
 //   steady a lane holds 4 scores per row tile for one query per query tile and
 //          compares them with its copy of the threshold; survivors (a few per wave
 //          over the whole kernel) are appended to the wave's private list; at
@@ -58,7 +64,9 @@
 //          distance -- as tight as the k-th best of a W*16*nblocks-row sample (32k-64k rows)
 //          instead of the block's own W*16.  It lowers tauS, and the wave keeps it for the final
 //          phase of its queries (xbound); entries not yet written (or of an older launch: seq
-//          mismatch) just count as absent.  No polling, no ordering needed.
+//          mismatch) just count as absent.  No polling, no ordering needed.  The seeded-boot kernel reads after
+//          its second tile, requests a lane's entries four at a time and selects among the 64 per-lane minima
+//          (still k distinct rows: a valid bound); its thresholds obey the two invariants stated at seed_phase.
 //
 // SHIFT (fp32 L2 only): distances are translation invariant, and the expanded form
 // |x|^2 + |y|^2 - 2 x.y loses digits when the rows share a large common component
@@ -98,6 +106,9 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     // candidates of the k + 4 lists, and a grid-wide threshold after the first tile cuts that bookkeeping.
     constexpr bool XCHG = T >= 3 || (T == 2 && W == 8) || (RM == ROWS_I8 && T == 1 && W == 8);
     constexpr bool FFILT = XCHG && ISE_FINAL_FILTER;    // final phase filtered by the exchange bound (below)
+    // boot without the cut (the byte shadow one-tile kernel): a two-tile boot window seeded from the exchange bound
+    constexpr bool NBOOT = scan_seeded_boot(RM == ROWS_I8, W, T);
+    static_assert(!NBOOT || XCHG, "the seeded boot reads the exchange");
     constexpr int NQ = 16 * T;                        // queries per block pass
     // threads staging one query row (per tile).  16-wave blocks stage with their first 8 waves: |x|^2 then has the
     // summation order of the 8-wave kernels (and of short_scan_kernel), and the bf16 L2 distances, which carry it,
@@ -121,6 +132,9 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     u64* bootw = reinterpret_cast<u64*>(cntS + W * NQ);         // [NQ][kb]
     u64* cand = bootw + NQ * kb;                                // [W][NQ][CAP]
     u64* boot = cand;                                           // [NQ][W*16], dead before cand is used
+    u64* home2 = cand + (size_t)W * NQ * CAP;                   // NBOOT: [NQ][W*16] keys of the window's second tile
+    u64* bminS = home2 + (size_t)NQ * W * 16;                   // NBOOT: [NQ] smallest first-tile key of the block
+    int* arrS = reinterpret_cast<int*>(bminS + NQ);             // NBOOT: waves whose first tile is folded into bminS
 
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: a scalar
     const int c = lane & 15, g = lane >> 4;
@@ -349,6 +363,10 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
         tauS[i] = TAU0;
         bwc[i] = 0;
         lockS[i] = 0;
+        if constexpr (NBOOT) {
+            bminS[i] = KEY_PAD;
+            if (i == 0) *arrS = 0;
+        }
     }
     __syncthreads();
     STAMP(1);
@@ -375,6 +393,12 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     }
     u64 xbound = KEY_PAD;  // FFILT: lane i keeps the exchange bound of the wave's i-th query (w + i W), KEY_PAD = none
     bool booted = false;
+    // NBOOT: the seeded boot is taken by a block whose EVERY wave has, behind its two window tiles, the 4 W row tiles
+    // that make the exchange read pay (block-uniform: the seeding needs every owner wave at the read).  Other blocks
+    // -- short ones, the exchange switched off, floor keys of a multi-pass k -- boot with the cut, as every other kernel.
+    const bool nboot = NBOOT && p.xchg != nullptr && !use_floor && !ABL(8 | 16 | 256 | 16384) &&
+                       (int)gridDim.x <= 512 /* what the folded read of seed_phase covers */ &&
+                       t1 - (t0 + (W - 1) + 2 * W) >= 4 * W;
 
     // fold the wave's private list of query qq = 16 t + cq into the block list bootw[qq]
     // (exact sorted top-k of their union) under the query's LDS lock; publish the k-th key
@@ -437,6 +461,36 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
         for (int t = 0; t < T; t++) tau[t] = tauS[t * 16 + c];
         booted = true;
         STAMP(3);
+    };
+
+    // NBOOT, blocks all of whose waves will read the exchange (nboot): no cut.  A wave's first TWO row tiles are its
+    // boot window: their keys go to the home unfiltered (first tile: the boot staging; second: home2), so no
+    // threshold is needed before the exchange bound exists.  The block's smallest first-tile key per query is folded
+    // with LDS atomics, and the last wave to arrive publishes the entries -- no barrier: a wave goes straight on to
+    // its second tile, and that tile's streaming is the distance between the publish and the read (seed_phase).
+    int wtiles = 0;  // window tiles this wave has stored (wave-uniform)
+    auto boot_window = [&](const u64(&key)[T][4]) {
+        u64* dst = (wtiles == 0 ? boot : home2) + (size_t)c * (W * 16) + w * 16 + 4 * g;
+#pragma unroll
+        for (int j = 0; j < 4; j++) dst[j] = key[0][j];
+        if (wtiles == 0) {
+            STAMP(2);
+            u64 m = min_u64(min_u64(key[0][0], key[0][1]), min_u64(key[0][2], key[0][3]));
+            m = min_u64(m, __shfl_xor(m, 16));
+            m = min_u64(m, __shfl_xor(m, 32));
+            if (g == 0 && m != KEY_PAD) atomicMin(reinterpret_cast<unsigned long long*>(bminS + c), (unsigned long long)m);
+            wave_lds_fence();
+            int arrived = 0;
+            if (lane == 0) arrived = __hip_atomic_fetch_add(arrS, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+            arrived = __builtin_amdgcn_readfirstlane(arrived);
+            wave_lds_fence();
+            if (arrived == W - 1 && lane < NQ)  // the score of one real row of this block, or 0xFFFFFFFF
+                __hip_atomic_store(p.xchg + ((size_t)blockIdx.y * NQ + lane) * gridDim.x + blockIdx.x,
+                                   ((u64)p.xchg_seq << 32) | (bminS[lane] >> 32), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            STAMP(7);
+        }
+        wtiles++;
     };
 
     // score of (query tile t, row slot j) exactly as it is keyed.
@@ -504,6 +558,12 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
         if (!booted) {
             u64 key[T][4];
             make_keys(etile, sc, key);
+            if constexpr (NBOOT) {
+                if (nboot) {
+                    boot_window(key);
+                    return;
+                }
+            }
             boot_phase(key);
 #pragma unroll
             for (int t = 0; t < T; t++) tau_sc[t] = unord_f32((uint32_t)(tau[t] >> 32));
@@ -563,35 +623,93 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     // one-shot threshold exchange (see the header comment): queries w, w + W, ... of this wave.
     // 256 slots (4 per lane) cover the grid, a slot folding G entries by their minimum; the k-th
     // smallest slot value is found bit by bit with ballot counts (absent entries = 0xFFFFFFFF).
-    auto exchange = [&]() {
+    auto xchg_prefix = [&](int qq) -> uint32_t {  // the k-th smallest published score of query qq, 0xFFFFFFFF = none
         const int nb = (int)gridDim.x;
         const int G = (nb + 255) >> 8;
+        const u64* src = p.xchg + ((size_t)blockIdx.y * NQ + qq) * nb;
+        auto slot_value = [&](int slot) -> uint32_t {
+            uint32_t best = 0xFFFFFFFFu;
+            for (int j = 0; j < G; j++) {
+                const int i = slot * G + j;
+                if (i < nb) {
+                    const u64 v = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if ((uint32_t)(v >> 32) == p.xchg_seq) best = min(best, (uint32_t)v);
+                }
+            }
+            return best;
+        };
+        const uint32_t v0 = slot_value(lane), v1 = slot_value(lane + 64), v2 = slot_value(lane + 128),
+                       v3 = slot_value(lane + 192);
+        uint32_t prefix = 0;
+        int rank = k;  // 1-based rank of the wanted value among those matching the prefix
+        for (int b = 31; b >= 0; b--) {
+            const uint32_t hm = b == 31 ? 0u : 0xFFFFFFFFu << (b + 1);
+            auto zero_here = [&](uint32_t v) { return ((v ^ prefix) & hm) == 0u && ((v >> b) & 1u) == 0u; };
+            const int c0 = __popcll(__ballot(zero_here(v0))) + __popcll(__ballot(zero_here(v1))) +
+                           __popcll(__ballot(zero_here(v2))) + __popcll(__ballot(zero_here(v3)));
+            if (rank > c0) {
+                rank -= c0;
+                prefix |= 1u << b;
+            }
+        }
+        return prefix;
+    };
+    // XFOLD (the seeded-boot kernel): the same bound from ONE value per lane.  Stamped, the read above cost 6.5 us per
+    // query -- eight dependent agent-scope loads per lane, each behind the ring's prefetch, then 32 rounds of four
+    // ballots.  Here the eight entries of a lane (grids of up to 512 blocks; a larger
+    // grid boots with the cut and reads as above) are requested four at a time, clamped instead of branched around, and folded to their minimum: 64 values, each the score of one real row, all of different
+    // blocks, so their k-th smallest (one ballot per bit, k <= KB_MAX < 64) is still the k-th best of k distinct rows
+    // -- a valid bound, at k = 32 about 1.4 times as far out in the distribution as the k-th of all entries.
+    constexpr bool XFOLD = NBOOT;
+    constexpr int XE = 4;  // entries per lane in flight at once (8 would spill the one-tile kernel): two halves per query
+    constexpr int XGRID = 512;  // blocks the folded read covers (64 lanes x 2 halves x XE); larger grids: nboot is off
+    auto xchg_request = [&](int qq, int half, u64(&e)[XE]) {  // gridDim.x <= XGRID
+        const int nb = (int)gridDim.x;
+        const int G = (nb + 255) >> 8;
+        const u64* src = p.xchg + ((size_t)blockIdx.y * NQ + qq) * nb;
+#pragma unroll
+        for (int i = 0; i < XE; i++) {
+            const int idx = (lane + 64 * (2 * half + (i >> 1))) * G + (i & 1);
+            e[i] = __hip_atomic_load(src + (((i & 1) < G && idx < nb) ? idx : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    };
+    auto xchg_fold = [&](int half, const u64(&e)[XE], uint32_t best) -> uint32_t {
+        const int nb = (int)gridDim.x;
+        const int G = (nb + 255) >> 8;
+#pragma unroll
+        for (int i = 0; i < XE; i++) {
+            const int idx = (lane + 64 * (2 * half + (i >> 1))) * G + (i & 1);
+            if ((i & 1) < G && idx < nb && (uint32_t)(e[i] >> 32) == p.xchg_seq) best = min(best, (uint32_t)e[i]);
+        }
+        return best;
+    };
+    auto lanes_kth = [&](uint32_t v) -> uint32_t {  // the k-th smallest of the lanes' values, 0xFFFFFFFF = fewer than k
+        uint32_t prefix = 0;
+        int rank = k;
+        for (int b = 31; b >= 0; b--) {
+            const uint32_t hm = b == 31 ? 0u : 0xFFFFFFFFu << (b + 1);
+            const int c0 = __popcll(__ballot(((v ^ prefix) & hm) == 0u && ((v >> b) & 1u) == 0u));
+            if (rank > c0) {
+                rank -= c0;
+                prefix |= 1u << b;
+            }
+        }
+        return prefix;
+    };
+    auto exchange = [&]() {
+        STAMP(12);
         for (int qq = w; qq < NQ; qq += W) {
-            const u64* src = p.xchg + ((size_t)blockIdx.y * NQ + qq) * nb;
-            auto slot_value = [&](int slot) -> uint32_t {
-                uint32_t best = 0xFFFFFFFFu;
-                for (int j = 0; j < G; j++) {
-                    const int i = slot * G + j;
-                    if (i < nb) {
-                        const u64 v = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if ((uint32_t)(v >> 32) == p.xchg_seq) best = min(best, (uint32_t)v);
-                    }
-                }
-                return best;
-            };
-            const uint32_t v0 = slot_value(lane), v1 = slot_value(lane + 64), v2 = slot_value(lane + 128),
-                           v3 = slot_value(lane + 192);
-            uint32_t prefix = 0;
-            int rank = k;  // 1-based rank of the wanted value among those matching the prefix
-            for (int b = 31; b >= 0; b--) {
-                const uint32_t hm = b == 31 ? 0u : 0xFFFFFFFFu << (b + 1);
-                auto zero_here = [&](uint32_t v) { return ((v ^ prefix) & hm) == 0u && ((v >> b) & 1u) == 0u; };
-                const int c0 = __popcll(__ballot(zero_here(v0))) + __popcll(__ballot(zero_here(v1))) +
-                               __popcll(__ballot(zero_here(v2))) + __popcll(__ballot(zero_here(v3)));
-                if (rank > c0) {
-                    rank -= c0;
-                    prefix |= 1u << b;
-                }
+            uint32_t prefix;
+            // (a larger grid than the folded read covers -- none on a 256-CU device -- keeps the read above; so does
+            // dev bit 16384, which with the cut boot it selects is the path of every other exchange kernel)
+            if (XFOLD && (int)gridDim.x <= XGRID && !ABL(16384)) {
+                u64 e[XE];
+                xchg_request(qq, 0, e);
+                const uint32_t b0 = xchg_fold(0, e, 0xFFFFFFFFu);
+                xchg_request(qq, 1, e);
+                prefix = lanes_kth(xchg_fold(1, e, b0));
+            } else {
+                prefix = xchg_prefix(qq);
             }
             if (prefix != 0xFFFFFFFFu) {  // at least k entries of this launch were there
                 const u64 bound = ((u64)prefix << 32) | 0xFFFFFFFFull;  // every id at that score stays admissible
@@ -605,6 +723,80 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
                 if (lane == 0) atomicExch(&lockS[qq], 0);
             }
         }
+        STAMP(13);
+    };
+
+    // NBOOT: the end of the seeded boot, once per block and with every wave in it, after the wave's second window
+    // tile.  The owner wave of a query reads the exchange and seeds the query's block list with the home keys <= bound.
+    // Invariants (with the cut of boot_phase and merge_out they hold in every kernel):
+    //   (a) tauS[q], whenever it is below TAU0, is at or above the launch's final k-th key of q: it is either the
+    //       block's own k-th smallest key so far (cut, merge_out) or an exchange bound of this launch -- the k-th
+    //       smallest score of k DISTINCT published rows, with id part 0xFFFFFFFF;
+    //   (b) every key of the block that is <= that final k-th key is in bootw or a private list, hence in the list
+    //       the block writes: a key is dropped only for being above some tauS value (here: above the bound; steady
+    //       state: not below tau; merge_out: above the union's k-th), or above xbound in the final phase.
+    // Fallback to the exact path -- wave_cut over the home keys, kmin = k, kmax = kb as in boot_phase -- when no bound
+    // arrived (fewer than k entries of this launch visible) or more than kb home keys lie under it (many equal rows in
+    // the window).  Nothing here needs lockS: bootw, bwc and tauS of a query are written by its owner alone, between
+    // two block barriers, and no merge_out runs before the second (a wave's private lists are empty until then).
+    auto seed_phase = [&]() {
+        STAMP(10);
+        // the entries of the wave's first query are requested ahead of the barrier, those of its second ahead of the
+        // first one's seeding: the round trips overlap the wait and the LDS work
+        u64 xe_[XE];
+        xchg_request(w, 0, xe_);
+        __syncthreads();  // every wave's window keys are in the home
+        STAMP(11);
+        const u64 lt_mask = (1ull << lane) - 1ull;
+        for (int qq = w; qq < NQ; qq += W) {
+            u64 kk[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                kk[e] = ((e < 2 ? boot : home2) + (size_t)qq * (W * 16))[lane + 64 * (e & 1)];
+            uint32_t folded = xchg_fold(0, xe_, 0xFFFFFFFFu);
+            xchg_request(qq, 1, xe_);
+            folded = xchg_fold(1, xe_, folded);
+            if (qq + W < NQ) xchg_request(qq + W, 0, xe_);
+            const uint32_t prefix = lanes_kth(folded);
+            if (qq == w) STAMP(12);
+            const u64 bound = ((u64)prefix << 32) | 0xFFFFFFFFull;  // KEY_PAD when no bound arrived
+            if (FFILT && prefix != 0xFFFFFFFFu && lane == (qq - w) / W) xbound = bound;
+            u64 keep[4];
+            int n_in = 0;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                keep[e] = __ballot(kk[e] <= bound && kk[e] != KEY_PAD);
+                n_in += __popcll(keep[e]);
+            }
+            if (prefix != 0xFFFFFFFFu && n_in <= kb) {
+                int off = 0;
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    if ((keep[e] >> lane) & 1ull) bootw[qq * kb + off + __popcll(keep[e] & lt_mask)] = kk[e];
+                    off += __popcll(keep[e]);
+                }
+                if (lane == 0) {
+                    bwc[qq] = n_in;
+                    tauS[qq] = bound;
+                }
+            } else {
+                u64 ktau = TAU0;
+                const int nw = wave_cut<4>(kk, 4 * 64, k, kb, bootw + qq * kb, &ktau);
+                if (lane == 0) {
+                    bwc[qq] = nw;
+                    tauS[qq] = min_u64(ktau, bound);  // TAU0 when fewer than k real keys were seen and no bound arrived
+                }
+            }
+            if (qq == w) STAMP(13);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < T; t++) {
+            tau[t] = tauS[t * 16 + c];
+            tau_sc[t] = unord_f32((uint32_t)(tau[t] >> 32));
+        }
+        booted = true;
+        STAMP(3);
     };
 
     // B operand (queries, from LDS) is software-pipelined one k-step ahead of the MFMAs
@@ -698,8 +890,11 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
             // outside the unrolled ring steps (one copy of the code): after the wave's second row tile
             // -- and only when enough row tiles remain for the tighter threshold to pay for the read
             if constexpr (XCHG) {
-                if (!exchanged && tiles_done >= 1) {
-                    if (t1 - tile >= 4 * W) exchange();
+                if (!exchanged && tiles_done >= (nboot ? 2 : 1)) {
+                    if constexpr (NBOOT) {
+                        if (nboot) seed_phase();
+                    }
+                    if (!nboot && t1 - tile >= 4 * W) exchange();
                     exchanged = true;
                 }
             }

@@ -42,14 +42,24 @@ struct ScanParams {
 
 #define LDS_LIMIT (160 * 1024)
 
+// which scan kernels boot without the cut (ise_scan.hpp, NBOOT): the byte shadow kernel with one query tile and 8
+// waves.  Their blocks keep the keys of a two-tile boot window: the first tile's where the boot staging is, the
+// second tile's in a region of their own (seeded), with the block's smallest first-tile keys and an arrival count.
+__host__ __device__ constexpr bool scan_seeded_boot(bool byte_rows, int waves, int T) {
+    return byte_rows && waves == 8 && T == 1;
+}
+
 // LDS bytes of one scan block (host and device agree through this function)
 // (shadow: the fp16 or byte shadow-row kernel, whose query rows hold hi | lo limbs and which keeps e_q and the
-// query's scale exponent beside |x|^2)
-__host__ __device__ constexpr size_t scan_lds_layout(int S, int waves, int T, int kb, bool shadow = false) {
+// query's scale exponent beside |x|^2; seeded: scan_seeded_boot of the kernel)
+__host__ __device__ constexpr size_t scan_lds_layout(int S, int waves, int T, int kb, bool shadow = false,
+                                                     bool seeded = false) {
     return (size_t)S * 4 /* mus: the shift vector, laid out like one query row */ +
            (size_t)(16 * T) * ((size_t)S * 4 + 4 /* qs, xn */ + (shadow ? 8 : 0) /* xe, xsh */ + 8 /* tauS */ + 8 /* bwc, lockS */ +
                                (size_t)waves * 4 /* cntS */ + (size_t)kb * 8 /* bootw */ +
-                               (size_t)waves * CAP * 8 /* cand; boot staging aliases it */);
+                               (size_t)waves * CAP * 8 /* cand; boot staging aliases it */ +
+                               (seeded ? (size_t)waves * 16 * 8 + 8 : 0) /* home2, bminS */) +
+           (seeded ? 16 : 0) /* arrS */;
 }
 
 // Launch the (ch, waves, T) variant of one kernel family.  Variants built per family:

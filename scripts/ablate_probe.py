@@ -13,7 +13,7 @@ names = {0: "full", 128 | 1 | 8 | 4: "mfma+lds only, no A loads", 128 | 64 | 1 |
          32 | 8 | 4: "L1-hot A, mfma only"}
 if os.environ.get("ABL"):  # ABL=0,8,2,4,256: only these bit masks
     names = {int(a): names.get(int(a), {256: "no exchange", 2048: "boot only (no epilogue after boot)",
-                                               8192: "no final filter"}.get(int(a), "")) for a in os.environ["ABL"].split(",")}
+                                               8192: "no final filter", 16384: "boot with the cut"}.get(int(a), "")) for a in os.environ["ABL"].split(",")}
 for n in (1_000_000,):
     xb = torch.rand((n, d), device="cuda"); xq = torch.rand((nq, d), device="cuda")
     index = faiss.IndexFlatL2(d); index.add_torch(xb)

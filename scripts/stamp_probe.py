@@ -32,5 +32,18 @@ for n, nq in shapes:
     print(f"  per-wave boot (out - in): median {np.median(us[:,:,3]-us[:,:,2]):.2f} max {(us[:,:,3]-us[:,:,2]).max():.2f}")
     print(f"  boot: wait for block (barrier1 - in): median {np.median(us[:,:,7]-us[:,:,2]):.2f} max {(us[:,:,7]-us[:,:,2]).max():.2f};"
           f" select+barrier2 (out - barrier1): median {np.median(us[:,:,3]-us[:,:,7]):.2f} max {(us[:,:,3]-us[:,:,7]).max():.2f}")
+    # boot, finer (stamps 10-13; zero where the path does not set them).  Seeded boot (byte shadow, one query tile):
+    # 2 first tile scored, 7 minimum folded / published, 10 second tile scored, 11 past the barrier, 12 exchange read
+    # + selection of the wave's first query done, 13 that query seeded, 3 boot out.  Boot with the cut: 12 / 13 are the
+    # start and end of exchange() (both queries of the wave).
+    def diff(a, b):
+        ok = (s[:, :, a] > 0) & (s[:, :, b] > 0)
+        v = (s[:, :, a] - s[:, :, b])[ok] / 100.0
+        return f"median {np.median(v):.2f} max {v.max():.2f} ({ok.sum()} waves)" if ok.any() else "not stamped"
+    if (s[:, :, 10] > 0).any():  # the seeded boot ran (stamp 10 is its alone)
+        print(f"  seeded boot: fold + publish (7 - 2): {diff(7, 2)}; second tile (10 - 7): {diff(10, 7)}; barrier wait (11 - 10): {diff(11, 10)}")
+        print(f"  seeded boot: exchange of one query (12 - 11): {diff(12, 11)}; seeding it (13 - 12): {diff(13, 12)}; second query + barrier (3 - 13): {diff(3, 13)}")
+    else:
+        print(f"  boot with the cut: exchange() of two queries (13 - 12): {diff(13, 12)}; boot out to exchange start (12 - 3): {diff(12, 3)}")
     print(f"  barrier wait (final barrier - loop end): median {np.median(us[:,:,5]-us[:,:,4]):.2f} max {(us[:,:,5]-us[:,:,4]).max():.2f}")
     del index, xb
