@@ -95,6 +95,10 @@ struct ise_index {
     double byte_rho = 1.0;     // ... and the sample rows' mean nearest-neighbour over mean pair distance (byte_rel_ok)
     unsigned long long half_batches = 0;  // batches whose filter read shadow rows, fp16 or byte (under mu_)
     unsigned long long byte_batches = 0;  // ... of them, those that read the byte shadow rows (under mu_)
+    unsigned long long byte_deep_batches = 0;  // ... of those, the ones scanned with a deep plan (make_plan, depth > 1)
+    // the stream of the index's previous search (search_enqueue, under mu_): a batch on another one is pipelined
+    hipStream_t prev_stream = nullptr;
+    bool prev_search = false;
     unsigned long long* stats_dev = nullptr;  // [4]: reranked queries, exact-scan queries
     unsigned long long mu_updates = 0;
     unsigned long long gemm_chunks = 0;  // query chunks that took the large-batch path
@@ -105,6 +109,8 @@ struct ise_index {
     // batches round-robin on more streams than that (bench.py: 16) gets at most six scans in
     // flight, chained slot to slot on the GPU, with the next ones already queued -- measured
     // best at 1M x 512 (303 us per batch against 328 with 4 streams and 319 with 16 slots)
+    // With the byte route's deep plan (make_plan, depth 2) a scan fills half the block slots, so two of
+    // the six slots' scans are resident together and the other four are the queue behind them.
     struct WorkSlot {
         u64* part = nullptr;
         size_t part_elems = 0;
@@ -820,6 +826,11 @@ struct ScanPlan {
     bool byte;    // ... through the byte shadow rows (ise_scan.hpp BYTE)
     bool short_;  // the batch's scan is the short-index kernel (ise_short_scan.hpp)
     int short_bpc;  // ... with this many blocks per CU
+    // depth > 1 (byte shadow, T = 1, 8 waves only): the scan runs on 1 / depth of the block slots, each block over
+    // depth times the rows, so that `depth` consecutive batches are resident together and a block pays its fixed
+    // phases once per depth times the rows (make_plan).  fb_*: the grid of the depth-1 plan, which the exact fallback
+    // scan keeps and the slots are sized by; equal to nblocks / tiles_per_block at depth 1
+    int depth, fb_nblocks, fb_tiles_per_block;
 };
 
 static void launch_scan(const ise_index* h, const ScanPlan& pl, dim3 grid, hipStream_t st, const ScanParams& sp) {
@@ -868,6 +879,7 @@ struct EnvKnobs {
     std::atomic<int> no_byte{0};        // ISE_NO_BYTE_FILTER=1: ... filter through the fp16 shadow, never the byte one
     std::atomic<int> fail_byte_alloc{0};  // ISE_FAIL_BYTE_ALLOC=1: the byte shadow's allocation fails as out of memory (tests)
     std::atomic<int> remove_slab_rows{0};  // ISE_REMOVE_SLAB_ROWS: destination rows per slab of a removal (tests: cross many slabs)
+    std::atomic<int> scan_depth{0};     // ISE_SCAN_DEPTH: 0 = by the stream rule of search_enqueue, 1 = isolated plan, N >= 2 = depth N
     void refresh() {
         auto flag = [](const char* name) { const char* e = getenv(name); return (e && e[0] == '1') ? 1 : 0; };
         auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
@@ -881,6 +893,7 @@ struct EnvKnobs {
         no_byte.store(flag("ISE_NO_BYTE_FILTER"));
         fail_byte_alloc.store(flag("ISE_FAIL_BYTE_ALLOC"));
         remove_slab_rows.store(num("ISE_REMOVE_SLAB_ROWS"));
+        scan_depth.store(std::max(0, num("ISE_SCAN_DEPTH")));
     }
 };
 static EnvKnobs& knobs() {
@@ -905,7 +918,7 @@ static bool xchg_enabled() {  // dev knob: ISE_NO_XCHG=1 switches the threshold 
 // pick (query tiles per pass T, waves per block) for nq queries: the largest T <= 3
 // that the batch can use and whose LDS image fits, preferring 8 waves
 static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool allow_short = true,
-                     bool allow_half = true) {
+                     bool allow_half = true, int depth = 1) {
     pl->exact = uses_shift(h);
     // the streamed rows: the byte or the fp16 shadow of a long float32 L2 index, else the index's own rows
     const bool shadow_ok = allow_half && pl->exact && h->xh != nullptr && !knobs().no_half.load(std::memory_order_relaxed);
@@ -973,12 +986,14 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
     pl->tiles_total = (int)((h->n + 15) / 16);
     int blocks_per_cu = (pl->T == 1 && pl->waves <= 8 && pl->lds <= LDS_LIMIT / 2) ? 2 : 1;
 #ifdef ISE_ABLATE
-    if (const char* e = getenv("ISE_PLAN")) {  // dev: "waves,blocks_per_cu" (T = 1 only)
-        int wv = 8, bpc = 2;
-        if (pl->T == 1 && sscanf(e, "%d,%d", &wv, &bpc) == 2 && (wv == 4 || wv == 8) && bpc >= 1) {
+    int slot_div = 1;
+    if (const char* e = getenv("ISE_PLAN")) {  // dev: "waves,blocks_per_cu[,slot divisor]" (T = 1 only)
+        int wv = 8, bpc = 2, div = 1;
+        if (pl->T == 1 && sscanf(e, "%d,%d,%d", &wv, &bpc, &div) >= 2 && (wv == 4 || wv == 8) && bpc >= 1 && div >= 1) {
             pl->waves = wv;
             pl->lds = lds_bytes(wv, 1);
             blocks_per_cu = bpc;
+            slot_div = div;
         }
     }
 #endif
@@ -991,7 +1006,11 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
     const bool long_rows = rb > 2048;
     const int nqt_plan = (int)((nq + 16 * pl->T - 1) / (16 * pl->T));
     const int min_tiles = (int)std::max<size_t>(1, 65536 / (16 * rb));
+#ifdef ISE_ABLATE
+    const int slots = std::max(1, h->num_cu * blocks_per_cu / slot_div);
+#else
     const int slots = h->num_cu * blocks_per_cu;
+#endif
     const int nb_packed = std::min(slots, (pl->tiles_total + pl->waves - 1) / pl->waves);
     const int nb_spread = std::min(std::max(1, slots / nqt_plan), (pl->tiles_total + min_tiles - 1) / min_tiles);
     int nb = std::max(nb_packed, nb_spread);
@@ -1001,6 +1020,24 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
     if (pl->tiles_per_block < 1) pl->tiles_per_block = 1;
     pl->nblocks = (pl->tiles_total + pl->tiles_per_block - 1) / pl->tiles_per_block;
     if (pl->nblocks < 1) pl->nblocks = 1;
+    pl->depth = 1;
+    pl->fb_nblocks = pl->nblocks;
+    pl->fb_tiles_per_block = pl->tiles_per_block;
+    // The deep plan (a batch that other batches are in flight beside, search_enqueue): slots / depth blocks of depth
+    // times the rows.  Only where the isolated plan packs every slot (a shorter index is spread, and half a grid
+    // would leave CUs without rows) and every full block still has the rows behind its boot window that the seeded
+    // boot asks for (ise_scan.hpp nboot: 2 W window tiles + 4 W more from the last wave's first tile = 55 tiles).
+    if (depth > 1 && pl->byte && pl->T == 1 && pl->waves == 8 && nb == slots && nb_packed == slots && slots / depth >= 1) {
+        const int nbd = slots / depth;
+        const int tpb = (pl->tiles_total + nbd - 1) / nbd;
+        if (tpb >= 55) {
+            pl->depth = depth;
+            pl->tiles_per_block = tpb;
+            pl->nblocks = (pl->tiles_total + tpb - 1) / tpb;
+        }
+    }
+    // the slots' lists and exchange entries are sized by the depth-1 grid (ensure_workspace): it is the larger
+    if (pl->nblocks > pl->fb_nblocks) return fail(ISE_E_INVALID, "internal: the deep plan has more blocks than the isolated one");
     // ... and a wave that owns ONE tile of long rows is latency-bound on its own loads: 8-step chunks (2 x 8 KB in
     // flight) where the register budget has them (8-wave blocks)
     // (never shadow rows: they are at most 2 KB)
@@ -1047,8 +1084,8 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
             const size_t lds = short_lds_layout(S, tpb, wv, short_T);
             if (tpb <= tpb_max && lds <= (size_t)LDS_LIMIT / bpc) {
                 pl->short_ = true;
-                pl->nblocks = nbs;
-                pl->tiles_per_block = tpb;
+                pl->nblocks = pl->fb_nblocks = nbs;
+                pl->tiles_per_block = pl->fb_tiles_per_block = tpb;
                 pl->lds = lds;
                 pl->waves = wv;
                 pl->short_bpc = bpc;
@@ -1069,7 +1106,9 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
 static int ensure_workspace(ise_index::WorkSlot* w, const ScanPlan& pl, long long nq, bool* changed) {
     if (!w->done) HIP_TRY(hipEventCreateWithFlags(&w->done, hipEventDisableTiming));
     // at least what the direct one-query scan can ask for (direct_applies): MERGE_LISTS_MAX lists of XPASS_MAX keys
-    const size_t need = std::max<size_t>((size_t)pl.nqt * pl.nblocks * (16 * pl.T) * pl.kpass, (size_t)MERGE_LISTS_MAX * XPASS_MAX);
+    // (fb_nblocks: the depth-1 grid, never smaller than the deep plan's -- make_plan checks -- so that a slot sized
+    // once serves both plans and nothing is allocated when a stream's batches change plan)
+    const size_t need = std::max<size_t>((size_t)pl.nqt * pl.fb_nblocks * (16 * pl.T) * pl.kpass, (size_t)MERGE_LISTS_MAX * XPASS_MAX);
     if (need > w->part_elems) {
         if (w->part) (void)hipFree(w->part);  // hipFree waits for outstanding work
         w->part = nullptr;
@@ -1078,7 +1117,7 @@ static int ensure_workspace(ise_index::WorkSlot* w, const ScanPlan& pl, long lon
         w->part_elems = need;
         *changed = true;
     }
-    const size_t needx = (size_t)pl.nqt * (16 * pl.T) * pl.nblocks;
+    const size_t needx = (size_t)pl.nqt * (16 * pl.T) * pl.fb_nblocks;
     if (needx > w->xchg_elems) {
         if (w->xchg) (void)hipFree(w->xchg);
         w->xchg = nullptr;
@@ -1176,7 +1215,11 @@ struct TimedOut {
     bool on = false;
 };
 
-// a launch tag no older entry of the slot's exchange buffer carries
+// a launch tag no older entry of the slot's exchange buffer carries.  The buffer is indexed [query][gridDim.x], so
+// batches of different plans that share a slot (the isolated and the deep one, search_enqueue) lay their entries out
+// differently: a reader may find another layout's entry at its index.  Every entry carries the tag of the launch that
+// wrote it and one of another launch counts as absent, whichever layout put it there; the slot's launches are ordered
+// (one stream, or an event wait), so no two of them write the buffer at once.
 static int next_xchg_seq(ise_index::WorkSlot* w, hipStream_t st, uint32_t* seq) {
     if (w->xchg_seq >= 0xFFFFFFF0u) {  // wrap: wipe the tags (stream-ordered behind the slot's last use)
         HIP_TRY(hipMemsetAsync(w->xchg, 0xFF, w->xchg_elems * sizeof(u64), st));
@@ -1209,19 +1252,20 @@ static int enqueue_exact_fallback(ise_index* h, ise_index::WorkSlot* w, const Sc
     xs.xb = (const float*)h->xb; xs.q = xp.q; xs.n = h->n; xs.d = h->d; xs.dp = h->dp;
     xs.id_base = xp.id_base; xs.fl_state = w->fl_state; xs.fl_list = w->fl_list; xs.seq = xp.seq;
     xs.part = w->part;  // the filter's lists are dead: [position][nblocks][kp] fits (kp <= kpass, positions <= nq)
-    xs.rows_per_block = (long long)pl.tiles_per_block * 16;
+    // (the depth-1 grid whatever plan the filter ran with: adversarial data is not scanned at half occupancy)
+    xs.rows_per_block = (long long)pl.fb_tiles_per_block * 16;
     xs.arrive = reinterpret_cast<unsigned int*>(w->fl_state + 1);
     xs.direct_n = 0;
     const size_t lds = (size_t)XQ * h->dp * 4 + (size_t)XQ * 4 * 32 * 8;
     MergeParams mp;  // the per-block lists are merged by the scan's last block
-    mp.lists = w->part; mp.qt = 1; mp.n_lists = pl.nblocks; mp.nq = (int)nq; mp.metric = h->metric;
+    mp.lists = w->part; mp.qt = 1; mp.n_lists = pl.fb_nblocks; mp.nq = (int)nq; mp.metric = h->metric;
     mp.fl_state = w->fl_state; mp.fl_list = w->fl_list; mp.seq = xp.seq; mp.dbg = nullptr; mp.gate = nullptr;
     const int k = xp.k;
     if (k <= XPASS_MAX) {
         xs.kpass = k; xs.floor_keys = nullptr;
-        mp.k = k; mp.stride_list = k; mp.stride_qtile = (long long)pl.nblocks * k;
+        mp.k = k; mp.stride_list = k; mp.stride_qtile = (long long)pl.fb_nblocks * k;
         mp.D = xp.D; mp.I = xp.I; mp.keys_out = xp.keys_out; mp.out_by_pos = 0;
-        hipLaunchKernelGGL(exact_scan_kernel<XQ>, dim3((unsigned)pl.nblocks), dim3(256), lds, st, xs, mp);
+        hipLaunchKernelGGL(exact_scan_kernel<XQ>, dim3((unsigned)pl.fb_nblocks), dim3(256), lds, st, xs, mp);
         HIP_TRY(hipGetLastError());
         return ISE_OK;
     }
@@ -1230,9 +1274,9 @@ static int enqueue_exact_fallback(ise_index* h, ise_index::WorkSlot* w, const Sc
     const int kp = XPASS_MAX;
     for (int off = 0; off < k; off += kp) {
         xs.kpass = kp; xs.floor_keys = off ? fb_floor : nullptr;
-        mp.k = kp; mp.stride_list = kp; mp.stride_qtile = (long long)pl.nblocks * kp;
+        mp.k = kp; mp.stride_list = kp; mp.stride_qtile = (long long)pl.fb_nblocks * kp;
         mp.D = nullptr; mp.I = nullptr; mp.keys_out = fb_pass; mp.out_by_pos = 1;
-        hipLaunchKernelGGL(exact_scan_kernel<XQ>, dim3((unsigned)pl.nblocks), dim3(256), lds, st, xs, mp);
+        hipLaunchKernelGGL(exact_scan_kernel<XQ>, dim3((unsigned)pl.fb_nblocks), dim3(256), lds, st, xs, mp);
         const long long tot = nq * kp;
         hipLaunchKernelGGL(exact_scatter_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, xp,
                            (const u64*)fb_pass, kp, off, fb_floor);
@@ -1343,9 +1387,9 @@ static GemmLayout gemm_layout(const ise_index* h) {
 
 // the plan a batch is enqueued with: large batches of float32 L2 queries go through the GEMM-shaped path
 // in chunks of GEMM_NQ_MAX, so their streaming plan (the exact fallback's shape, the slot's lists) is a chunk's
-static int plan_for_batch(const ise_index* h, long long nq, int k, ScanPlan* pl) {
+static int plan_for_batch(const ise_index* h, long long nq, int k, ScanPlan* pl, int depth = 1) {
     const bool big = gemm_applies(h, nq, k);
-    int rc = make_plan(h, big ? std::min<long long>(nq, GEMM_NQ_MAX) : nq, k, pl);
+    int rc = make_plan(h, big ? std::min<long long>(nq, GEMM_NQ_MAX) : nq, k, pl, true, true, depth);
     if (rc) return rc;
     pl->gemm = big;
     pl->gemm_bytes = big ? gemm_layout(h).total : 0;
@@ -1472,6 +1516,7 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
         sp.beta = byte_beta(h); sp.lo_shrink = half_lo_shrink(h);
         h->half_batches++;
         h->byte_batches++;
+        if (pl.depth > 1) h->byte_deep_batches++;
     } else if (pl.half) {  // the filter streams the fp16 shadow rows (ise_scan.hpp HALF)
         sp.xb = h->xh; sp.norms = h->hmeta; sp.herr = h->hmeta + h->cap; sp.hexp = h->hmeta + 2 * h->cap;
         sp.qs_stride = qs_stride_half(h); sp.row_slots = (int)(shadow_row_bytes(h) / 16);
@@ -1760,8 +1805,17 @@ static int search_enqueue(ise_index* h, const float* q_dev, long long nq, int k,
                           long long* I_dev, u64* keys_out, hipStream_t st, TimedOut* tm) {
     int rc = prepare_shift_locked(h, st);
     if (rc) return rc;
+    // Which plan (make_plan, depth): a batch on another stream than the index's previous search has batches in
+    // flight beside it -- step time counts, not latency -- and takes the deep plan; a caller that stays on one stream
+    // (and the first search) takes the isolated one.  A pointer compare under mu_: no HIP call, so nothing here can
+    // leave an error behind for a later launch's check or disturb another thread's graph capture.
+    // $ISE_SCAN_DEPTH: 0 / unset = this rule, 1 = always isolated, N >= 2 = depth N wherever the plan allows.
+    int depth = knobs().scan_depth.load(std::memory_order_relaxed);
+    if (depth <= 0) depth = (h->prev_search && h->prev_stream != st) ? 2 : 1;
+    h->prev_search = true;
+    h->prev_stream = st;
     ScanPlan pl;
-    rc = plan_for_batch(h, nq, k, &pl);
+    rc = plan_for_batch(h, nq, k, &pl, depth);
     if (rc) return rc;
     rc = ensure_workspaces(h, pl, pl.gemm ? std::min<long long>(nq, GEMM_NQ_MAX) : nq);
     if (rc) return rc;
@@ -2889,6 +2943,14 @@ extern "C" int ise_index_short_stats(ise_index_t* h, uint64_t* out1) {
     if (!h || !out1) return fail(ISE_E_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu_);
     out1[0] = h->short_batches;
+    return ISE_OK;
+}
+
+extern "C" int ise_index_depth_stats(ise_index_t* h, uint64_t* out2) {
+    if (!h || !out2) return fail(ISE_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    out2[0] = h->byte_batches - h->byte_deep_batches;
+    out2[1] = h->byte_deep_batches;
     return ISE_OK;
 }
 

@@ -92,7 +92,7 @@
 // float32 norm |y - mu|^2 and bounds only the cross terms by e_r and e_q (tests/byte_filter_ref.py).
 template <int CH, int W, int T, bool BF16, bool SHIFT, int RM = ROWS_OWN>
 __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) void scan_kernel(const ScanParams p) {
-    constexpr bool HALF = RM == ROWS_F16, BYTE = RM == ROWS_I8, SHADOW = HALF || BYTE;
+    constexpr bool HALF = RM == ROWS_F16, BYTE = RM == ROWS_I8 || RM == ROWS_I8_ONE, SHADOW = HALF || BYTE;
     static_assert(!(BF16 && SHIFT), "the shift is applied to fp32 rows only");
     static_assert(!SHADOW || SHIFT, "shadow rows belong to float32 L2 indexes");
     constexpr bool F32S = SHIFT && !SHADOW;  // float32 rows shifted in registers
@@ -104,10 +104,10 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     // for short indexes, where the exchange would not run anyway) nor at T = 1 (neutral).
     // The byte shadow kernel takes it at T = 1 as well: its kc = 32 lists over ~2000-row blocks admit twice the
     // candidates of the k + 4 lists, and a grid-wide threshold after the first tile cuts that bookkeeping.
-    constexpr bool XCHG = T >= 3 || (T == 2 && W == 8) || (RM == ROWS_I8 && T == 1 && W == 8);
+    constexpr bool XCHG = T >= 3 || (T == 2 && W == 8) || (BYTE && T == 1 && W == 8);
     constexpr bool FFILT = XCHG && ISE_FINAL_FILTER;    // final phase filtered by the exchange bound (below)
     // boot without the cut (the byte shadow one-tile kernel): a two-tile boot window seeded from the exchange bound
-    constexpr bool NBOOT = scan_seeded_boot(RM == ROWS_I8, W, T);
+    constexpr bool NBOOT = scan_seeded_boot(BYTE, W, T);
     static_assert(!NBOOT || XCHG, "the seeded boot reads the exchange");
     constexpr int NQ = 16 * T;                        // queries per block pass
     // threads staging one query row (per tile).  16-wave blocks stage with their first 8 waves: |x|^2 then has the
@@ -661,25 +661,30 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     // blocks, so their k-th smallest (one ballot per bit, k <= KB_MAX < 64) is still the k-th best of k distinct rows
     // -- a valid bound, at k = 32 about 1.4 times as far out in the distribution as the k-th of all entries.
     constexpr bool XFOLD = NBOOT;
+    // ROWS_I8_ONE, the kernel the launcher picks for a grid of at most 64 XE = 256 blocks (the deep plan of the host's
+    // make_plan): a lane has at most XE entries, lane + 64 i, all in ONE request (half 0; there is no half 1), so no
+    // round trip is left behind the barrier.  The bound is still the k-th smallest of 64 values of distinct blocks.
+    // (A compile-time split, not a branch on gridDim.x: the branch cost the one-tile kernel its last registers.)
     constexpr int XE = 4;  // entries per lane in flight at once (8 would spill the one-tile kernel): two halves per query
     constexpr int XGRID = 512;  // blocks the folded read covers (64 lanes x 2 halves x XE); larger grids: nboot is off
+    constexpr bool XREQ1 = RM == ROWS_I8_ONE;
     auto xchg_request = [&](int qq, int half, u64(&e)[XE]) {  // gridDim.x <= XGRID
         const int nb = (int)gridDim.x;
-        const int G = (nb + 255) >> 8;
+        const int G = XREQ1 ? 1 : (nb + 255) >> 8;
         const u64* src = p.xchg + ((size_t)blockIdx.y * NQ + qq) * nb;
 #pragma unroll
         for (int i = 0; i < XE; i++) {
-            const int idx = (lane + 64 * (2 * half + (i >> 1))) * G + (i & 1);
-            e[i] = __hip_atomic_load(src + (((i & 1) < G && idx < nb) ? idx : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int idx = XREQ1 ? lane + 64 * i : (lane + 64 * (2 * half + (i >> 1))) * G + (i & 1);
+            e[i] = __hip_atomic_load(src + (((XREQ1 || (i & 1) < G) && idx < nb) ? idx : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
     auto xchg_fold = [&](int half, const u64(&e)[XE], uint32_t best) -> uint32_t {
         const int nb = (int)gridDim.x;
-        const int G = (nb + 255) >> 8;
+        const int G = XREQ1 ? 1 : (nb + 255) >> 8;
 #pragma unroll
         for (int i = 0; i < XE; i++) {
-            const int idx = (lane + 64 * (2 * half + (i >> 1))) * G + (i & 1);
-            if ((i & 1) < G && idx < nb && (uint32_t)(e[i] >> 32) == p.xchg_seq) best = min(best, (uint32_t)e[i]);
+            const int idx = XREQ1 ? lane + 64 * i : (lane + 64 * (2 * half + (i >> 1))) * G + (i & 1);
+            if ((XREQ1 || (i & 1) < G) && idx < nb && (uint32_t)(e[i] >> 32) == p.xchg_seq) best = min(best, (uint32_t)e[i]);
         }
         return best;
     };
@@ -696,6 +701,28 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
         }
         return prefix;
     };
+    // dev bit 32768 (ROWS_I8_ONE): the k-th smallest of ALL the grid's entries, four ballots per bit as in xchg_prefix,
+    // instead of the k-th of the lanes' folded minima -- a tighter bound for four times the ballot work
+    auto lanes_kth4 = [&](const u64(&e)[XE]) -> uint32_t {
+        const int nb = (int)gridDim.x;
+        uint32_t v[XE];
+#pragma unroll
+        for (int i = 0; i < XE; i++)
+            v[i] = (lane + 64 * i < nb && (uint32_t)(e[i] >> 32) == p.xchg_seq) ? (uint32_t)e[i] : 0xFFFFFFFFu;
+        uint32_t prefix = 0;
+        int rank = k;
+        for (int b = 31; b >= 0; b--) {
+            const uint32_t hm = b == 31 ? 0u : 0xFFFFFFFFu << (b + 1);
+            int c0 = 0;
+#pragma unroll
+            for (int i = 0; i < XE; i++) c0 += __popcll(__ballot(((v[i] ^ prefix) & hm) == 0u && ((v[i] >> b) & 1u) == 0u));
+            if (rank > c0) {
+                rank -= c0;
+                prefix |= 1u << b;
+            }
+        }
+        return prefix;
+    };
     auto exchange = [&]() {
         STAMP(12);
         for (int qq = w; qq < NQ; qq += W) {
@@ -705,9 +732,12 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
             if (XFOLD && (int)gridDim.x <= XGRID && !ABL(16384)) {
                 u64 e[XE];
                 xchg_request(qq, 0, e);
-                const uint32_t b0 = xchg_fold(0, e, 0xFFFFFFFFu);
-                xchg_request(qq, 1, e);
-                prefix = lanes_kth(xchg_fold(1, e, b0));
+                uint32_t folded = xchg_fold(0, e, 0xFFFFFFFFu);
+                if constexpr (!XREQ1) {
+                    xchg_request(qq, 1, e);
+                    folded = xchg_fold(1, e, folded);
+                }
+                prefix = lanes_kth(folded);
             } else {
                 prefix = xchg_prefix(qq);
             }
@@ -754,10 +784,13 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
             for (int e = 0; e < 4; e++)
                 kk[e] = ((e < 2 ? boot : home2) + (size_t)qq * (W * 16))[lane + 64 * (e & 1)];
             uint32_t folded = xchg_fold(0, xe_, 0xFFFFFFFFu);
-            xchg_request(qq, 1, xe_);
-            folded = xchg_fold(1, xe_, folded);
+            if constexpr (!XREQ1) {  // (ROWS_I8_ONE: all the entries were in the first request)
+                xchg_request(qq, 1, xe_);
+                folded = xchg_fold(1, xe_, folded);
+            }
+            const uint32_t all4 = (XREQ1 && ABL(32768)) ? lanes_kth4(xe_) : 0u;
             if (qq + W < NQ) xchg_request(qq + W, 0, xe_);
-            const uint32_t prefix = lanes_kth(folded);
+            const uint32_t prefix = (XREQ1 && ABL(32768)) ? all4 : lanes_kth(folded);
             if (qq == w) STAMP(12);
             const u64 bound = ((u64)prefix << 32) | 0xFFFFFFFFull;  // KEY_PAD when no bound arrived
             if (FFILT && prefix != 0xFFFFFFFFu && lane == (qq - w) / W) xbound = bound;

@@ -29,7 +29,9 @@ static void launch_scan_ch(int ch, dim3 grid, size_t lds, hipStream_t st, const 
 template <bool BF16, bool SHIFT, int RM = ROWS_OWN>
 static void launch_scan_v(int ch, int waves, int T, dim3 grid, size_t lds, hipStream_t st, const ScanParams& sp) {
     if constexpr (RM == ROWS_I8) {  // byte shadow rows: one query tile only (the plan routes nothing else to them)
+        // (a grid of at most 256 blocks -- the deep plan -- has the exchange read that is one request: ROWS_I8_ONE)
         if (waves == 4) launch_scan_ch<4, 1, BF16, SHIFT, RM>(ch, grid, lds, st, sp);
+        else if (grid.x <= 256) launch_scan_ch<8, 1, BF16, SHIFT, ROWS_I8_ONE>(ch, grid, lds, st, sp);
         else launch_scan_ch<8, 1, BF16, SHIFT, RM>(ch, grid, lds, st, sp);
     } else if (T == 1 && waves == 4) launch_scan_ch<4, 1, BF16, SHIFT, RM>(ch, grid, lds, st, sp);
     else if (T == 1) launch_scan_ch<8, 1, BF16, SHIFT, RM>(ch, grid, lds, st, sp);

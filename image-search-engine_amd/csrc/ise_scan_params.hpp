@@ -7,7 +7,8 @@
 
 // ---------------------------------------------------------------- scan kernel
 // what scan_kernel streams (its RM parameter): the index's own rows, or a shadow of float32 L2 rows
-enum RowMode : int { ROWS_OWN = 0, ROWS_F16 = 1, ROWS_I8 = 2 };
+// (ROWS_I8_ONE: the byte shadow on a grid of at most 256 blocks, whose exchange read is one request; ise_scan.hpp)
+enum RowMode : int { ROWS_OWN = 0, ROWS_F16 = 1, ROWS_I8 = 2, ROWS_I8_ONE = 3 };
 
 struct ScanParams {
     const void* xb;      // [cap][dp] float32 or bf16 rows, or the fp16 / byte shadow rows [cap][dph] / [cap][dpb]; 16-byte "slots": row_slots per row

@@ -337,6 +337,13 @@ class IndexFlat:
         _n.check(_n.lib.ise_index_byte_stats(self._h, out))
         return {"byte_batches": int(out[0]), "byte_route": bool(out[1])}
 
+    def depth_stats(self) -> dict:
+        """Byte-shadow batches scanned with the isolated plan and with a deep one (include/ise_knn.h,
+        ise_index_depth_stats)."""
+        out = (ctypes.c_uint64 * 2)()
+        _n.check(_n.lib.ise_index_depth_stats(self._h, out))
+        return {"isolated_batches": int(out[0]), "deep_batches": int(out[1])}
+
     def byte_row(self, i: int) -> tuple:
         """(c_r, e_r) of byte shadow row i (include/ise_knn.h, ise_index_byte_row)."""
         out = (ctypes.c_float * 2)()

@@ -115,6 +115,14 @@ int ise_index_short_stats(ise_index_t* h, uint64_t* out1);
  * index has no such shadow. */
 int ise_index_half_stats(ise_index_t* h, uint64_t* out1);
 int ise_index_byte_stats(ise_index_t* h, uint64_t* out2);
+/* The byte-shadow scan has two plans.  A batch enqueued on another stream than the index's previous search has
+ * other batches in flight beside it and is scanned by half as many blocks of twice the rows (depth 2), so that two
+ * consecutive batches are resident together and a block's fixed phases are paid once per twice the rows; a caller
+ * that stays on one stream, and the first search, keep the isolated plan (depth 1), which has the lower latency.
+ * Same bits either way.  $ISE_SCAN_DEPTH (read by ise_refresh_env_knobs): 0 / unset = that rule, 1 = always the
+ * isolated plan, N >= 2 = depth N wherever the plan allows it.  out2[0] = byte-shadow batches scanned at depth 1,
+ * out2[1] = at depth > 1 (their sum is ise_index_byte_stats' out2[0]). */
+int ise_index_depth_stats(ise_index_t* h, uint64_t* out2);
 int ise_index_shadow_row(ise_index_t* h, int64_t i, float* out3);
 int ise_index_byte_row(ise_index_t* h, int64_t i, float* out2);
 
