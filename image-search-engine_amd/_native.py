@@ -107,6 +107,17 @@ PROTOTYPES = [
     ("ise_binary_index_search_sel_device", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
     ("ise_binary_index_range_search_sel_host", _int, [_vp, _vp, _i64, ctypes.c_int32, _vp, ctypes.POINTER(_vp)]),
     ("ise_binary_index_sel_stats", _int, [_vp, _u64p]),
+    ("ise_ivf_create", _int, [ctypes.POINTER(_vp), _int, _int, _int, _int]),
+    ("ise_ivf_destroy", _int, [_vp]),
+    ("ise_ivf_reset", _int, [_vp]),
+    ("ise_ivf_info", _int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), _i64p, ctypes.POINTER(_int)]),
+    ("ise_ivf_add_host", _int, [_vp, _vp, _vp, _i64]),
+    ("ise_ivf_add_device", _int, [_vp, _vp, _vp, _i64, _vp]),
+    ("ise_ivf_list_sizes_host", _int, [_vp, _vp]),
+    ("ise_ivf_list_host", _int, [_vp, _int, _vp, _vp]),
+    ("ise_ivf_search_device", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp]),
+    ("ise_ivf_search_host", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp]),
+    ("ise_ivf_stats", _int, [_vp, _u64p]),
     ("ise_refresh_env_knobs", _int, []),
     ("ise_comm_precheck", _int, [_int]),
     ("ise_comm_unique_id", _int, [_vp]),

@@ -36,6 +36,7 @@
 // This file: the host side and the C ABI (include/ise_knn.h).
 
 #include "ise_common.hpp"
+#include "ise_geometry.hpp"
 #include "ise_scan_params.hpp"
 #include "ise_assign.hpp"
 #include "ise_exact.hpp"
@@ -217,14 +218,6 @@ struct ise_index {
     unsigned long long sel_range_batches = 0;            // under rg_mu
 };
 
-// rows are padded to whole k-steps of 64 bytes (16 floats / 32 bf16); rows longer than
-// 4 steps to a multiple of 4 steps so that wider register chunks divide them
-static int elem_size(int storage) { return storage == ISE_STORE_BF16 ? 2 : 4; }
-static int pad_dim(int d, int storage) {
-    const int per_step = 64 / elem_size(storage);
-    const int steps = (d + per_step - 1) / per_step;
-    return (steps > 4 ? (steps + 3) / 4 * 4 : steps) * per_step;
-}
 // byte rows (the int8 shadow): 64 values per k-step, padded as above
 static int pad_bytes(int d) {
     const int steps = (d + 63) / 64;
@@ -233,19 +226,7 @@ static int pad_bytes(int d) {
 static size_t row_bytes(const ise_index* h) { return (size_t)h->dp * elem_size(h->storage); }
 static size_t shadow_row_bytes(const ise_index* h) { return (size_t)h->dph * 2; }
 static size_t byte_row_bytes(const ise_index* h) { return (size_t)h->dpb; }
-static int chunk_steps_rb(size_t rb) {
-    const int steps = (int)(rb / 64);
-    for (int ch = 8; ch > 1; ch >>= 1)
-        if (steps % ch == 0) return ch;
-    return 1;
-}
 static int chunk_steps(const ise_index* h) { return chunk_steps_rb(row_bytes(h)); }
-// LDS query row stride in 4-byte units: (stride/4) % 16 == 2 makes the 16 rows x 4 k-groups
-// ds_read_b128 pattern bank-conflict-free
-static int qs_stride_units(int units) {
-    const int pad = ((2 - (units / 4)) % 16 + 16) % 16 * 4;
-    return units + pad;
-}
 static int qs_stride_for(const ise_index* h) { return qs_stride_units((int)(row_bytes(h) / 4)); }
 // the shadow-row kernel's query row: fp16 hi halves | lo halves, dph each
 static int qs_stride_half(const ise_index* h) { return qs_stride_units(h->dph); }
@@ -854,7 +835,7 @@ static int exact_extra(int k) {
 }
 // relative width of the scan's lower bound: every rounding between the stored floats and the keyed
 // value, in units of u = 2^-24 times (|x-mu|^2 + |y-mu|^2) (derivation: DESIGN.md section 4.1)
-static float exact_beta(const ise_index* h) { return (0.5625f * h->dp + 256.f) * 5.9604645e-8f * 1.02f; }
+static float exact_beta(const ise_index* h) { return exact_beta_dp(h->dp); }
 // the shadow-row filter's beta: the f16 MFMA dot of 2 dph exact products in any accumulation order, twice the
 // worst-case n u, plus the roundings of |u~|^2, |v~|^2 and the expanded form, relative to |u~|^2 + |v~|^2 (DESIGN.md
 // 4.1); and the factor that takes its square below the float32 direct-difference value (fmaf chains of dp / 64
@@ -2189,9 +2170,7 @@ static int range_staging(const ise_index* h, int qs_stride, int* tpr, int* vec_q
     ScanPlan pl;
     const int rc = make_plan(h, 16, 1, &pl, false, false);
     if (rc) return rc;
-    const bool bf16 = h->storage == ISE_STORE_BF16;
-    *tpr = pl.waves >= 8 ? 32 : 16;
-    *vec_q = (h->d & (bf16 ? 7 : 3)) == 0 && (qs_stride >> 2) <= *tpr * (bf16 ? 4 : 8);
+    range_staging_rule(pl.waves, h->storage == ISE_STORE_BF16, h->d, qs_stride, tpr, vec_q);
     return ISE_OK;
 }
 

@@ -33,6 +33,10 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          row, an in-place compaction of the code rows (csrc/ise_binary_scan.hpp)
     IndexBinaryIDMap(index)              Faiss's id-mapping wrapper over a binary index: ``add_with_ids``, external ids in
                                          results, selectors and ``remove_ids``
+    IndexIVFFlat(quantizer, d, nlist)    Faiss's cell-probe index WITHOUT compression (the "IndexIVFFlat" the comment at
+                                         backend/utils.py:312 points to): ``train`` / ``add`` / ``search`` with ``nprobe`` /
+                                         ``search_preassigned``; rows scattered into inverted lists on the device, one
+                                         pass over the probed lists only (csrc/ise_ivf.hpp); never called by the reference
     write_index_binary / read_index_binary   Faiss's names for IndexBinaryFlat ("IBxF") and IndexBinaryIDMap ("IBMp") files
 
 All arithmetic runs on the MI355X through ``include/ise_knn.h``; there is no
@@ -663,6 +667,8 @@ class IndexIDMap:
     sub-index renumbers its rows; ``id_map[row]`` follows).  The mapping is host numpy, off the hot path."""
 
     def __init__(self, index: IndexFlat):
+        if isinstance(index, IndexIVFFlat):
+            raise NotImplementedError("IndexIDMap over an IndexIVFFlat is not provided")
         assert index.ntotal == 0, "IndexIDMap wraps an empty index (Faiss: index is empty on input)"
         self.index = index
         self.id_map = np.zeros(0, dtype=np.int64)
@@ -832,6 +838,8 @@ def parse_flat(buf: bytes):
 
 
 def write_index(index, path) -> None:
+    if isinstance(index, IndexIVFFlat):
+        raise NotImplementedError("write_index of an IndexIVFFlat is not provided")
     with open(str(path), "wb") as f:
         if isinstance(index, IndexIDMap):
             sub = index.index
@@ -845,6 +853,8 @@ def read_index(path, device: int | None = None):
     with open(str(path), "rb") as f:
         buf = f.read()
     ids = None
+    if buf[:4] in (b"IwFl", b"IwF2"):  # Faiss's fourccs of IndexIVFFlat files
+        raise NotImplementedError("read_index of an IndexIVFFlat file is not provided")
     if buf[:4] == _FOURCC_IDMAP:
         d, metric, xb, ids = parse_idmap(buf)
     else:
@@ -1319,3 +1329,198 @@ class Kmeans:
         self.obj = np.asarray(obj, dtype=np.float32)
         self.index = self._make_index(self.centroids)
         return float(self.obj[-1])
+
+
+# ---------------------------------------------------------------- inverted lists (faiss.IndexIVFFlat)
+class ClusteringParameters:
+    """The two fields of faiss.ClusteringParameters that ``IndexIVFFlat.train`` reads (``index.cp``)."""
+
+    def __init__(self, niter: int = 10, seed: int = 1234):
+        self.niter = int(niter)
+        self.seed = int(seed)
+
+
+class IndexIVFFlat:
+    """faiss.IndexIVFFlat: a coarse quantiser (an ``IndexFlat`` of ``nlist`` centroids, the caller's object) in front of
+    uncompressed float32 rows.  ``add`` puts every row into the inverted list of its nearest centroid; ``search`` visits
+    the ``nprobe`` lists whose centroids are nearest to the query and returns the exact k best among THEIR rows -- D has
+    the bits ``IndexFlat.search`` reports for the same (query, row) pair, ties go by ascending id, unfilled slots are
+    -1 / +-FLT_MAX.  With ``nprobe == nlist`` the result is ``IndexFlat.search`` itself.
+
+    For given centroids everything here is determined, and it is checked bit for bit against this package's own flat
+    index; Faiss's own IVF (its k-means seeding, its scanning order among equal distances) is unpinned.
+
+    The lists live on the device (include/ise_knn.h, ise_ivf_*): ``add`` appends to a pending buffer, the first search
+    after an ``add`` rebuilds the lists, which moves the whole index once.  Not provided (they raise
+    ``NotImplementedError``): ``range_search``, ``remove_ids``, ``params=``, ``write_index`` / ``read_index`` and
+    ``IndexIDMap`` over this type."""
+
+    def __init__(self, quantizer: IndexFlat, d: int, nlist: int, metric: int = METRIC_L2):
+        assert isinstance(quantizer, IndexFlat), "the coarse quantiser is an IndexFlat"
+        assert quantizer.d == int(d), f"dimension mismatch: quantizer has d={quantizer.d}, index d={d}"
+        self.quantizer = quantizer
+        self.d = int(d)
+        self.nlist = int(nlist)
+        self.nprobe = 1
+        self.metric_type = int(metric)
+        self.cp = ClusteringParameters()
+        self.device = quantizer.device
+        self._h = ctypes.c_void_p()
+        self._lock = threading.Lock()
+        _n.check(_n.lib.ise_ivf_create(ctypes.byref(self._h), self.d, self.metric_type, self.nlist, self.device))
+        self.is_trained = quantizer.ntotal == self.nlist
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                _n.lib.ise_ivf_destroy(h)
+            except Exception:  # interpreter shutdown: module globals may already be gone
+                pass
+            h.value = None
+
+    @property
+    def ntotal(self) -> int:
+        n = ctypes.c_int64(0)
+        _n.check(_n.lib.ise_ivf_info(self._h, None, None, None, ctypes.byref(n), None))
+        return int(n.value)
+
+    def reset(self) -> None:
+        """Drop the rows; the quantiser (and ``is_trained``) stay."""
+        _n.check(_n.lib.ise_ivf_reset(self._h))
+
+    # -- build side
+    def train(self, x) -> None:
+        """A no-op when the quantiser already holds ``nlist`` centroids.  With an empty quantiser: ``Kmeans(d, nlist)``
+        on ``x`` (spherical when the quantiser is an inner-product index), ``niter`` and ``seed`` from ``self.cp``, and
+        the centroids are added to the quantiser.  ``cp.niter`` defaults to 10, Faiss's default for an IVF's clustering
+        as restated from memory: unpinned, like the seeding of ``Kmeans`` itself."""
+        if self.quantizer.ntotal == self.nlist:
+            self.is_trained = True
+            return
+        if self.quantizer.ntotal != 0:
+            raise RuntimeError(f"the quantizer holds {self.quantizer.ntotal} centroids, neither 0 nor nlist = {self.nlist}")
+        x = _as_rows(x, self.d)
+        if x.shape[0] < self.nlist:
+            raise RuntimeError(f"{x.shape[0]} training rows for nlist = {self.nlist} centroids")
+        km = Kmeans(self.d, self.nlist, niter=self.cp.niter, seed=self.cp.seed,
+                    spherical=self.quantizer.metric_type == METRIC_INNER_PRODUCT)
+        km.train(x)
+        self.quantizer.add(km.centroids)
+        self.is_trained = True
+
+    def _check_assignment(self, lists: np.ndarray) -> None:
+        bad = np.flatnonzero(lists < 0)
+        if bad.size:
+            raise ValueError(f"row {int(bad[0])} has no nearest centroid (a NaN or inf entry?): nothing was added")
+
+    def add(self, x) -> None:
+        """Append rows (copied); row i of the call goes to list ``quantizer.search(x, 1)[1][i]``."""
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFFlat.add before train")
+        x = _as_rows(x, self.d)
+        if x.shape[0] == 0:
+            return
+        lists = np.ascontiguousarray(self.quantizer.search(x, 1)[1].reshape(-1), dtype=np.int64)
+        self._check_assignment(lists)
+        _n.check(_n.lib.ise_ivf_add_host(self._h, x.ctypes.data, lists.ctypes.data, x.shape[0]))
+
+    def add_torch(self, x) -> None:
+        """Append rows from a CUDA float32 tensor on this index's device (the rows make no host hop; the list numbers
+        are read back to be checked)."""
+        import torch
+
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFFlat.add before train")
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
+        x = x.contiguous()
+        n = x.shape[0]
+        if n == 0:
+            return
+        # the route quantizer.search(x, 1) takes for this many rows, so that the ids are the same
+        qz = self.quantizer
+        lists = (qz.assign_torch(x) if qz._assign_applies(n, 1) else qz.search_torch(x, 1))[1].reshape(-1).contiguous()
+        self._check_assignment(lists.cpu().numpy())
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        _n.check(_n.lib.ise_ivf_add_device(self._h, x.data_ptr(), lists.data_ptr(), n, st))
+
+    # -- lists
+    def list_size(self, l: int) -> int:
+        sizes = np.zeros(self.nlist, dtype=np.int64)
+        _n.check(_n.lib.ise_ivf_list_sizes_host(self._h, sizes.ctypes.data))
+        return int(sizes[int(l)])
+
+    def get_list(self, l: int):
+        """(ids int64 (m,), rows float32 (m, d)) of list ``l``, in list order (ascending ids)."""
+        m = self.list_size(l)
+        ids = np.empty(m, dtype=np.int64)
+        rows = np.empty((m, self.d), dtype=np.float32)
+        _n.check(_n.lib.ise_ivf_list_host(self._h, int(l), ids.ctypes.data, rows.ctypes.data))
+        return ids, rows
+
+    def ivf_stats(self) -> dict:
+        """Search batches, scan passes launched, 16-row tiles of list rows the passes loaded (include/ise_knn.h,
+        ise_ivf_stats).  Waits for the device."""
+        out = (ctypes.c_uint64 * 3)()
+        _n.check(_n.lib.ise_ivf_stats(self._h, out))
+        return {"batches": int(out[0]), "passes": int(out[1]), "tiles_loaded": int(out[2])}
+
+    # -- query side
+    def _nprobe(self) -> int:
+        return max(1, min(int(self.nprobe), self.nlist))
+
+    def search_preassigned(self, x, k: int, probes):
+        """``search`` with the probed lists given: ``probes`` int64 (nq, nprobe); -1 entries are ignored."""
+        x = _as_rows(x, self.d)
+        k = int(k)
+        assert k > 0
+        nq = x.shape[0]
+        probes = np.ascontiguousarray(np.asarray(probes), dtype=np.int64)
+        assert probes.ndim == 2 and probes.shape[0] == nq and probes.shape[1] >= 1
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        _n.check(_n.lib.ise_ivf_search_host(self._h, x.ctypes.data, nq, k, probes.ctypes.data, probes.shape[1],
+                                            D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def search(self, x, k: int, params=None):
+        """(D float32 (nq,k), I int64 (nq,k)), fresh arrays: the k best among the rows of the ``nprobe`` lists nearest
+        to each query (``quantizer.search(x, min(nprobe, nlist))[1]``)."""
+        if params is not None:
+            raise NotImplementedError("search parameters are not provided on IndexIVFFlat: set index.nprobe")
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFFlat.search before train")
+        x = _as_rows(x, self.d)
+        if x.shape[0] == 0:
+            return np.empty((0, int(k)), dtype=np.float32), np.empty((0, int(k)), dtype=np.int64)
+        return self.search_preassigned(x, k, self.quantizer.search(x, self._nprobe())[1])
+
+    def search_torch(self, xq, k: int, params=None):
+        """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out; the quantiser's search and the scan are
+        enqueued on the current torch stream.  No host synchronisation, except that the first search after an ``add``
+        rebuilds the lists and waits for that."""
+        import torch
+
+        if params is not None:
+            raise NotImplementedError("search parameters are not provided on IndexIVFFlat: set index.nprobe")
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFFlat.search before train")
+        assert xq.is_cuda and xq.dtype == torch.float32 and xq.dim() == 2 and xq.shape[1] == self.d
+        xq = xq.contiguous()
+        nq, k = xq.shape[0], int(k)
+        D = torch.empty((nq, k), dtype=torch.float32, device=xq.device)
+        I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
+        if nq == 0:
+            return D, I
+        probes = self.quantizer.search_torch(xq, self._nprobe())[1].contiguous()
+        st = torch.cuda.current_stream(xq.device).cuda_stream
+        with self._lock:
+            _n.check(_n.lib.ise_ivf_search_device(self._h, xq.data_ptr(), nq, k, probes.data_ptr(), probes.shape[1],
+                                                  D.data_ptr(), I.data_ptr(), st))
+        return D, I
+
+    def range_search(self, *a, **kw):
+        raise NotImplementedError("range_search is not provided on IndexIVFFlat")
+
+    def remove_ids(self, *a, **kw):
+        raise NotImplementedError("remove_ids is not provided on IndexIVFFlat")

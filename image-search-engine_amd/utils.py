@@ -75,7 +75,9 @@ def hashes_to_codes(hashes, nbits=64):
 def create_search_index(data_array, index_type="cosine"):
     """backend/utils.py:293-330.  'cosine' -> IndexFlatIP over rows normalised IN
     PLACE in the caller's array (quirk 5.9-6); 'l2' -> IndexFlatL2; then add.
-    'cell-probe' (IndexIVFPQ) is approximate and outside the scoped path."""
+    'cell-probe' (IndexIVFPQ) is approximate and outside the scoped path; 'cell-probe-flat' is that branch
+    (backend/utils.py:311-325) without the product quantiser: IndexIVFFlat over an L2 coarse quantiser with the
+    reference's 8 centroids and nprobe = 5, trained on the data, then add."""
     num_features = data_array.shape[1]
     if index_type == "cosine":
         index = faiss.IndexFlatIP(num_features)
@@ -84,6 +86,12 @@ def create_search_index(data_array, index_type="cosine"):
         index = faiss.IndexFlatL2(num_features)
     elif index_type == "cell-probe":
         raise NotImplementedError("'cell-probe' (IndexIVFPQ) is outside the exact brute-force hot path")
+    elif index_type == "cell-probe-flat":
+        ncentroids = 8
+        coarse_quantizer = faiss.IndexFlatL2(num_features)
+        index = faiss.IndexIVFFlat(coarse_quantizer, num_features, ncentroids)
+        index.nprobe = 5  # find n most similar clusters
+        index.train(data_array)
     else:
         raise ValueError(f"unknown index_type {index_type!r}")
     index.add(data_array)

@@ -355,6 +355,55 @@ int ise_binary_index_range_search_sel_host(ise_binary_index_t* h, const uint8_t*
                                            const ise_binary_selector_t* sel, ise_binary_range_result_t** out);
 int ise_binary_index_sel_stats(ise_binary_index_t* h, uint64_t* out3);
 
+/* Inverted lists: faiss.IndexIVFFlat's storage and its search_preassigned (csrc/ise_ivf.hpp; the third, "cell-probe"
+ * branch of the reference's create_search_index, backend/utils.py:311-325, without its product quantiser).  An
+ * ise_ivf_t holds nlist lists of float32 rows of dimension d on one device and NO centroids: the coarse quantiser is
+ * the caller's (faiss_compat.IndexIVFFlat keeps an ordinary flat index for it).  add takes a list number per row,
+ * search a table of probed lists per query.  All the conventions at the top of this header hold (0 / ISE_E_* returns,
+ * ise_last_error, caller-owned buffers, *_host blocks, *_device only enqueues on the given stream).  Calls on one
+ * handle run one at a time; *_device searches on different streams are ordered one behind the other on the device (one
+ * set of workspaces per handle).  ise_ivf_search_device waits on the host in two cases only: rows are pending (the
+ * rebuild, see add), or a workspace has to be replaced by a larger one (the first call, a larger nq or k than before),
+ * which waits for the passes that still use the old one.
+ *   create        d <= 0, nlist <= 0, a metric other than the two and a NULL out are ISE_E_INVALID before the device is
+ *                 touched; float32 storage only
+ *   ids           a row's id is its insertion number (0, 1, 2, ... across all add calls, fewer than 2^32 rows); inside a
+ *                 list the rows are in ascending id order whatever the number and size of the add calls
+ *   add           list_no: one entry per row in [0, nlist).  An entry outside makes the call ISE_E_INVALID and NOTHING of
+ *                 that call is added.  Both forms block (the device form reads the list numbers back to check them).
+ *                 The rows wait in insertion order in a pending buffer; the first search or ise_ivf_list_host after an
+ *                 add rebuilds the lists (one rebuild moves the whole index, and that call blocks: DESIGN.md 4.12)
+ *   lists         list_sizes_host: rows per list, pending ones included.  list_host: the ids (int64) and / or the rows
+ *                 (size x d floats, bit-equal to what was added) of one list in list order; either pointer may be NULL
+ *   search        probes: nq x nprobe int64 list numbers (nprobe >= 1); an entry that is -1 or otherwise outside
+ *                 [0, nlist) is ignored, a list named twice in a row delivers its rows once.  The result is the exact k
+ *                 best among the rows of the query's probed lists: D has the bits ise_index_search_* reports for the
+ *                 same (query, row) pair (float32 L2: the direct-difference value; inner product: the scan's dot
+ *                 product), ties go by ascending id, unfilled slots are id -1 with +-FLT_MAX (fewer than k rows in the
+ *                 probed lists, a NaN query).  k in 1 .. ISE_MAX_K: one pass per 16 queries and per 32 results, which
+ *                 loads only the 16-row tiles of lists that one of the 16 queries probes (one launch makes the passes
+ *                 of up to 64 queries).  k outside the range, nprobe
+ *                 < 1 and NULL buffers are ISE_E_INVALID; nq = 0 returns at once; an empty index fills the padding
+ *                 without a pass
+ *   stats         out3[0] = search batches (calls with nq > 0), out3[1] = scan launches (per 64 queries and 32 results), out3[2] = 16-row tiles
+ *                 of list rows the passes loaded (counted on the device; the call waits for the device) */
+typedef struct ise_ivf ise_ivf_t;
+int ise_ivf_create(ise_ivf_t** out, int d, int metric, int nlist, int device);
+int ise_ivf_destroy(ise_ivf_t* h); /* NULL is a no-op */
+int ise_ivf_reset(ise_ivf_t* h);   /* drop all rows, keep d / metric / nlist */
+int ise_ivf_info(const ise_ivf_t* h, int* d, int* metric, int* nlist, int64_t* ntotal, int* device);
+/* append n rows of d floats with their list numbers, copied */
+int ise_ivf_add_host(ise_ivf_t* h, const float* x, const int64_t* list_no, int64_t n);
+int ise_ivf_add_device(ise_ivf_t* h, const float* x_dev, const int64_t* list_no_dev, int64_t n, void* stream);
+int ise_ivf_list_sizes_host(ise_ivf_t* h, int64_t* sizes /* nlist */);
+int ise_ivf_list_host(ise_ivf_t* h, int list, int64_t* ids, float* rows); /* either may be NULL */
+/* q: nq x d; probes: nq x nprobe; D: nq x k float32; I: nq x k int64 */
+int ise_ivf_search_device(ise_ivf_t* h, const float* q_dev, int64_t nq, int k, const int64_t* probes_dev, int nprobe,
+                          float* D_dev, int64_t* I_dev, void* stream);
+int ise_ivf_search_host(ise_ivf_t* h, const float* q, int64_t nq, int k, const int64_t* probes, int nprobe, float* D,
+                        int64_t* I);
+int ise_ivf_stats(ise_ivf_t* h, uint64_t* out3);
+
 /* Shard-local search for the multi-GPU path: writes nq x k
  * packed candidates, sorted best-first, suitable for one all-gather:
  *   key = (order-preserving uint32 image of the score) << 32 | (row + id_base)
