@@ -13,41 +13,27 @@
 // holds the mutex from its device-wide synchronisation to the end of its last copy: other calls on the handle run
 // entirely before or entirely after it.
 #include "ise_binary_scan.hpp"
+#include "ise_host.hpp"
 #include "ise_remove.hpp"
-#include "ise_sel_scan.hpp"
-
-extern int ise_fail_(int code, const std::string& msg);  // ise_knn.hip: sets the thread-local message
-extern int ise_remove_slab_rows_();                      // ise_knn.hip: $ISE_REMOVE_SLAB_ROWS as last refreshed
-
-#define BIN_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return ise_fail_(e_ == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP,                  \
-                             std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
+#include "ise_remove_plan.hpp"
+#include "ise_selector.hpp"
 
 #define BIN_RANGE_NQ_CHUNK 256 /* queries per range batch: one host synchronisation each */
 static_assert(BIN_RANGE_NQ_CHUNK <= 256, "binary_lims_kernel scans a batch's totals in one block of 256 threads");
 
 namespace {
+// rule: device-wide drain before a free (any stream may still use the handle's ONE set), and half again on top so growth drains rarely
 template <class T>
-struct BinBuf {  // grown lazily, contents not kept
-    T* p = nullptr;
-    size_t n = 0;
-};
-
-template <class T>
-int bin_grow(BinBuf<T>& b, size_t need) {
+int bin_grow(DevBuf<T>& b, size_t need) {
     if (b.p && need <= b.n) return ISE_OK;
     if (b.p) {
-        BIN_TRY(hipDeviceSynchronize());  // work in flight on any stream may still use the old one
+        HIP_TRY(hipDeviceSynchronize());  // work in flight on any stream may still use the old one
         (void)hipFree(b.p);
     }
     b.p = nullptr;
     b.n = 0;
     const size_t want = std::max<size_t>(need + need / 2, 16);
-    BIN_TRY(hipMalloc((void**)&b.p, want * sizeof(T)));
+    HIP_TRY(hipMalloc((void**)&b.p, want * sizeof(T)));
     b.n = want;
     return ISE_OK;
 }
@@ -62,26 +48,19 @@ struct ise_binary_index {
     hipStream_t last_stream = nullptr;
     bool last_valid = false;
     mutable std::mutex mu;
-    BinBuf<uint8_t> raw;       // host forms: the queries as passed
-    BinBuf<u64> qpad, lo, lists;
-    BinBuf<int> oD, counts, rD;
-    BinBuf<long long> oI, offs, totals, lims, rI;
+    DevBuf<uint8_t> raw;       // host forms: the queries as passed
+    DevBuf<u64> qpad, lo, lists;
+    DevBuf<int> oD, counts, rD;
+    DevBuf<long long> oI, offs, totals, lims, rI;
     uint64_t st_search = 0, st_passes = 0, st_range = 0;
     unsigned long long row_epoch = 0;  // bumped when rows go or are renumbered: selectors made before are stale
     uint64_t st_sel = 0, st_sel_passes = 0, st_sel_range = 0;    // filtered batches, masked passes, filtered range batches
     uint64_t st_rm_calls = 0, st_rm_rows = 0, st_rm_moved = 0;   // removals that removed something, rows removed, rows moved
 };
 
-// a device bitmap over the rows of ONE binary index at ONE (ntotal, row epoch)
-struct ise_binary_selector {
-    ise_binary_index* owner = nullptr;
-    int device = 0;
-    uint32_t* bits = nullptr;  // 2 * max(1, ceil(ntotal / 64)) words: one aligned 8-byte word per 64-row tile
-    long long nwords = 0;      // allocated uint32 words (even)
-    long long ntotal = 0;
-    unsigned long long epoch = 0;
-    long long count = 0, r0 = 0, r1 = 0, tiles = 0;  // selected rows, window [r0, r1), non-empty 64-row tiles
-};
+// a device bitmap over the rows of ONE binary index at ONE (ntotal, row epoch); bits: 2 * max(1, ceil(ntotal / 64))
+// words, one aligned 8-byte word per 64-row tile
+struct ise_binary_selector : SelectorBase {};
 
 struct ise_binary_range_result {
     std::vector<int64_t> lims;
@@ -95,11 +74,11 @@ size_t bin_query_lds(const ise_binary_index* h) { return bin_wt(h) == 0 ? (size_
 
 // order this call's device work behind the previous call's, and mark its own end
 int bin_begin(ise_binary_index* h, hipStream_t st) {
-    if (h->last_valid && h->last_stream != st) BIN_TRY(hipStreamWaitEvent(st, h->last, 0));
+    if (h->last_valid && h->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->last, 0));
     return ISE_OK;
 }
 int bin_end(ise_binary_index* h, hipStream_t st) {
-    BIN_TRY(hipEventRecord(h->last, st));
+    HIP_TRY(hipEventRecord(h->last, st));
     h->last_stream = st;
     h->last_valid = true;
     return ISE_OK;
@@ -172,7 +151,7 @@ int reserve_codes(ise_binary_index* h, long long need, hipStream_t st) {
     want = (want + 63) / 64 * 64;
     const size_t rb = (size_t)h->ws * 8;
     u64* nx = nullptr;
-    BIN_TRY(hipMalloc((void**)&nx, (size_t)want * rb));
+    HIP_TRY(hipMalloc((void**)&nx, (size_t)want * rb));
     hipError_t e = hipSuccess;
     if (h->n > 0) e = hipMemcpyAsync(nx, h->codes, (size_t)h->n * rb, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync((char*)nx + (size_t)h->n * rb, 0, (size_t)(want - h->n) * rb, st);
@@ -201,7 +180,7 @@ int add_device_locked(ise_binary_index* h, const uint8_t* x_dev, long long n, hi
     rc = reserve_codes(h, h->n + n, st);
     if (rc) return rc;
     pad_rows(x_dev, h->code_size, h->codes + (size_t)h->n * h->ws, h->ws, n, st);
-    BIN_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     h->n += n;
     return bin_end(h, st);
 }
@@ -218,7 +197,7 @@ int search_enqueue(ise_binary_index* h, const uint8_t* q_dev, long long nq, int 
         st_batches++;
         const long long cnt = nq * k;
         hipLaunchKernelGGL(binary_fill_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, cnt);
-        BIN_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         return bin_end(h, st);
     }
     BinMask mk{};
@@ -264,7 +243,7 @@ int search_enqueue(ise_binary_index* h, const uint8_t* q_dev, long long nq, int 
             st_pass++;
         }
     }
-    BIN_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return bin_end(h, st);
 }
 
@@ -299,7 +278,7 @@ int range_batch(ise_binary_index* h, hipStream_t st, const uint8_t* q, long long
     if ((rc = bin_grow(h->offs, (size_t)M))) return rc;
     if ((rc = bin_grow(h->lims, (size_t)m + 1))) return rc;
     if ((rc = bin_grow(h->totals, (size_t)m))) return rc;
-    BIN_TRY(hipMemcpyAsync(h->raw.p, q, (size_t)m * h->code_size, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->raw.p, q, (size_t)m * h->code_size, hipMemcpyHostToDevice, st));
     pad_rows(h->raw.p, h->code_size, h->qpad.p, h->ws, m, st);
     const int wt = bin_wt(h);
     const size_t lds = bin_query_lds(h);
@@ -319,10 +298,10 @@ int range_batch(ise_binary_index* h, hipStream_t st, const uint8_t* q, long long
     hipLaunchKernelGGL(binary_offsets_kernel, dim3((unsigned)m), dim3(BIN_SCAN_THREADS), 0, st, h->counts.p, S, h->offs.p,
                        h->totals.p);
     hipLaunchKernelGGL(binary_lims_kernel, dim3(1), dim3(256), 0, st, h->totals.p, (int)m, h->lims.p);
-    BIN_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     std::vector<long long> lims((size_t)m + 1);
-    BIN_TRY(hipMemcpyAsync(lims.data(), h->lims.p, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, st));
-    BIN_TRY(hipStreamSynchronize(st));  // the one host synchronisation that sizes the result
+    HIP_TRY(hipMemcpyAsync(lims.data(), h->lims.p, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the one host synchronisation that sizes the result
     const long long total = lims[(size_t)m];
     const size_t at = res->D.size();
     for (long long i = 1; i <= m; i++) res->lims.push_back((int64_t)at + lims[(size_t)i]);
@@ -338,12 +317,12 @@ int range_batch(ise_binary_index* h, hipStream_t st, const uint8_t* q, long long
         rp.lims = h->lims.p + q0;
         launch_range<true>(wt, grid, lds, st, rp, mk);
     }
-    BIN_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     res->D.resize(at + (size_t)total);
     res->I.resize(at + (size_t)total);
-    BIN_TRY(hipMemcpyAsync(res->D.data() + at, h->rD.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-    BIN_TRY(hipMemcpyAsync(res->I.data() + at, h->rI.p, (size_t)total * 8, hipMemcpyDeviceToHost, st));
-    BIN_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(res->D.data() + at, h->rD.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(res->I.data() + at, h->rI.p, (size_t)total * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return ISE_OK;
 }
 
@@ -370,7 +349,7 @@ extern "C" int ise_binary_index_create(ise_binary_index_t** out, int d_bits, int
         return ise_fail_(ISE_E_NODEVICE, "no HIP device visible: the kNN path needs an MI355X (gfx950) GPU");
     if (device < 0 || device >= ndev) return ise_fail_(ISE_E_INVALID, "device out of range");
     hipDeviceProp_t prop;
-    BIN_TRY(hipGetDeviceProperties(&prop, device));
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return ise_fail_(ISE_E_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
     ise_binary_index* h = new (std::nothrow) ise_binary_index();
@@ -449,11 +428,11 @@ extern "C" int ise_binary_index_add_host(ise_binary_index_t* h, const uint8_t* c
         const long long m = std::min<long long>(step, n - i0);
         int rc = bin_grow(h->raw, (size_t)m * h->code_size);
         if (rc) return rc;
-        BIN_TRY(hipMemcpyAsync(h->raw.p, codes + (size_t)i0 * h->code_size, (size_t)m * h->code_size, hipMemcpyHostToDevice,
+        HIP_TRY(hipMemcpyAsync(h->raw.p, codes + (size_t)i0 * h->code_size, (size_t)m * h->code_size, hipMemcpyHostToDevice,
                                h->stream));
         rc = add_device_locked(h, h->raw.p, m, h->stream);
         if (rc) return rc;
-        BIN_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return ISE_OK;
 }
@@ -468,10 +447,10 @@ extern "C" int ise_binary_index_reconstruct_host(ise_binary_index_t* h, int64_t 
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     int rc = bin_begin(h, h->stream);
     if (rc) return rc;
-    BIN_TRY(hipMemcpy2DAsync(out, (size_t)h->code_size, h->codes + (size_t)i0 * h->ws, (size_t)h->ws * 8, (size_t)h->code_size,
+    HIP_TRY(hipMemcpy2DAsync(out, (size_t)h->code_size, h->codes + (size_t)i0 * h->ws, (size_t)h->ws * 8, (size_t)h->code_size,
                              (size_t)n, hipMemcpyDeviceToHost, h->stream));
     if ((rc = bin_end(h, h->stream))) return rc;
-    BIN_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return ISE_OK;
 }
 
@@ -501,11 +480,11 @@ extern "C" int ise_binary_index_search_host(ise_binary_index_t* h, const uint8_t
     if ((rc = bin_grow(h->oD, cnt))) return rc;
     if ((rc = bin_grow(h->oI, cnt))) return rc;
     if ((rc = bin_begin(h, h->stream))) return rc;
-    BIN_TRY(hipMemcpyAsync(h->raw.p, q, (size_t)nq * h->code_size, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->raw.p, q, (size_t)nq * h->code_size, hipMemcpyHostToDevice, h->stream));
     if ((rc = search_enqueue(h, h->raw.p, nq, k, h->oD.p, h->oI.p, h->stream))) return rc;
-    BIN_TRY(hipMemcpyAsync(D, h->oD.p, cnt * 4, hipMemcpyDeviceToHost, h->stream));
-    BIN_TRY(hipMemcpyAsync(I, h->oI.p, cnt * 8, hipMemcpyDeviceToHost, h->stream));
-    BIN_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(D, h->oD.p, cnt * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(I, h->oI.p, cnt * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return ISE_OK;
 }
 
@@ -586,53 +565,14 @@ extern "C" int ise_binary_index_stats(ise_binary_index_t* h, uint64_t* out3) {
 
 // ---- selectors
 namespace {
-// the bitmap of a new selector for h as it stands (mu held): one 8-byte word per 64-row tile, at least one
-int selector_alloc_locked(ise_binary_index* h, ise_binary_selector** out) {
-    ise_binary_selector* s = new (std::nothrow) ise_binary_selector;
-    if (!s) return ise_fail_(ISE_E_NOMEM, "selector: host allocation failed");
-    s->owner = h;
-    s->device = h->device;
-    s->ntotal = h->n;
-    s->epoch = h->row_epoch;
-    s->nwords = 2 * std::max<long long>(1, (h->n + 63) / 64);
-    const hipError_t e = hipMalloc((void**)&s->bits, (size_t)s->nwords * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        delete s;
-        return ise_fail_(e == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP, std::string("selector bitmap: ") + hipGetErrorString(e));
-    }
-    *out = s;
-    return ISE_OK;
+// a new selector for h as it stands (mu held): one 8-byte word per 64-row tile, at least one
+SelectorFor selector_for(const ise_binary_index* h) {
+    return SelectorFor{h, h->device, h->n, h->row_epoch, h->stream, 2 * std::max<long long>(1, (h->n + 63) / 64)};
 }
-
-void selector_free(ise_binary_selector* s) {
-    if (s->bits) (void)hipFree(s->bits);  // waits for the device: a masked pass in flight is through with the bitmap
-    delete s;
-}
-
-// clears bits at or beyond ntotal, then count / window / non-empty 64-row tiles on the device (mu held; blocks)
-int selector_census_locked(ise_binary_selector* s, hipStream_t st) {
-    unsigned long long* dev = nullptr;
-    BIN_TRY(hipMalloc((void**)&dev, 4 * sizeof(unsigned long long)));
-    struct Free { void* p; ~Free() { (void)hipFree(p); } } fr{dev};
-    const unsigned long long init[4] = {0ull, 0ull, ~0ull, 0ull};
-    unsigned long long got[4];
-    BIN_TRY(hipMemcpyAsync(dev, init, sizeof(init), hipMemcpyHostToDevice, st));
+void selector_census_launch(SelectorBase* s, hipStream_t st, unsigned long long* out4) {
     const long long nw64 = s->nwords / 2;
     hipLaunchKernelGGL(binary_sel_census_kernel, dim3((unsigned)((nw64 + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<u64*>(s->bits), nw64, s->ntotal, dev);
-    BIN_TRY(hipGetLastError());
-    BIN_TRY(hipMemcpyAsync(got, dev, sizeof(got), hipMemcpyDeviceToHost, st));
-    BIN_TRY(hipStreamSynchronize(st));
-    s->count = (long long)got[0];
-    s->tiles = (long long)got[1];
-    s->r0 = got[0] ? (long long)got[2] : 0;
-    s->r1 = got[0] ? (long long)got[3] : 0;
-    return ISE_OK;
-}
-
-void selector_fill(ise_binary_index* h, ise_binary_selector* s, long long a, long long b) {
-    hipLaunchKernelGGL(sel_fill_range_kernel, dim3((unsigned)((s->nwords + 255) / 256)), dim3(256), 0, h->stream, s->bits,
-                       s->nwords, a, std::max(a, b));
+                       reinterpret_cast<u64*>(s->bits), nw64, s->ntotal, out4);
 }
 }  // namespace
 
@@ -643,14 +583,9 @@ extern "C" int ise_binary_selector_create_range(ise_binary_index_t* h, int64_t i
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(h->mu);
-    ise_binary_selector* s = nullptr;
-    int rc = selector_alloc_locked(h, &s);
-    if (rc) return rc;
-    selector_fill(h, s, std::max<long long>(i0, 0), std::min<long long>(i1, h->n));
-    rc = selector_census_locked(s, h->stream);
-    if (rc) { selector_free(s); return rc; }
-    *out = s;
-    return ISE_OK;
+    const long long a = std::max<long long>(i0, 0), b = std::min<long long>(i1, h->n);
+    return selector_create(selector_for(h), [&](SelectorBase* s) { return selector_fill_range(s, h->stream, a, b); },
+                           selector_census_launch, out);
 }
 
 extern "C" int ise_binary_selector_create_ids(ise_binary_index_t* h, const int64_t* ids, int64_t n_ids, int invert,
@@ -662,27 +597,10 @@ extern "C" int ise_binary_selector_create_ids(ise_binary_index_t* h, const int64
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(h->mu);
-    ise_binary_selector* s = nullptr;
-    int rc = selector_alloc_locked(h, &s);
-    if (rc) return rc;
-    long long* ids_dev = nullptr;
-    struct Free { long long** p; ~Free() { if (*p) (void)hipFree(*p); } } fr{&ids_dev};
-    auto body = [&]() -> int {
-        // the fill runs on the device: nothing (invert: every row), then the ids are scattered in -- only they travel
-        selector_fill(h, s, 0ll, invert ? h->n : 0ll);
-        if (n_ids > 0) {
-            BIN_TRY(hipMalloc((void**)&ids_dev, (size_t)n_ids * sizeof(long long)));
-            BIN_TRY(hipMemcpyAsync(ids_dev, ids, (size_t)n_ids * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-            hipLaunchKernelGGL(sel_scatter_ids_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, h->stream, s->bits,
-                               (const long long*)ids_dev, (long long)n_ids, h->n, invert ? 0 : 1);
-        }
-        BIN_TRY(hipGetLastError());
-        return selector_census_locked(s, h->stream);
-    };
-    rc = body();
-    if (rc) { selector_free(s); return rc; }
-    *out = s;
-    return ISE_OK;
+    DevFree ids_dev;
+    return selector_create(selector_for(h),
+                           [&](SelectorBase* s) { return selector_scatter_ids(s, h->stream, ids, n_ids, invert, &ids_dev); },
+                           selector_census_launch, out);
 }
 
 extern "C" int ise_binary_selector_create_bitmap(ise_binary_index_t* h, const uint32_t* words, int64_t n_words,
@@ -696,30 +614,11 @@ extern "C" int ise_binary_selector_create_bitmap(ise_binary_index_t* h, const ui
     std::lock_guard<std::mutex> lk(h->mu);
     if (n_words != (h->n + 31) / 32)
         return ise_fail_(ISE_E_INVALID, "the bitmap must have ceil(ntotal / 32) = " + std::to_string((h->n + 31) / 32) + " words");
-    ise_binary_selector* s = nullptr;
-    int rc = selector_alloc_locked(h, &s);
-    if (rc) return rc;
-    auto body = [&]() -> int {
-        BIN_TRY(hipMemsetAsync(s->bits + n_words, 0, (size_t)(s->nwords - n_words) * sizeof(uint32_t), h->stream));
-        if (n_words > 0)
-            BIN_TRY(hipMemcpyAsync(s->bits, words, (size_t)n_words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        return selector_census_locked(s, h->stream);  // clears the bits at or beyond ntotal
-    };
-    rc = body();
-    if (rc) { selector_free(s); return rc; }
-    *out = s;
-    return ISE_OK;
+    return selector_create(selector_for(h), [&](SelectorBase* s) { return selector_copy_bitmap(s, h->stream, words, n_words); },
+                           selector_census_launch, out);  // the census clears the bits at or beyond ntotal
 }
 
-extern "C" int ise_binary_selector_info(const ise_binary_selector_t* sel, int64_t* out5) {
-    if (!sel || !out5) return ise_fail_(ISE_E_INVALID, "NULL argument");
-    out5[0] = sel->ntotal;
-    out5[1] = sel->count;
-    out5[2] = sel->r0;
-    out5[3] = sel->r1;
-    out5[4] = sel->tiles;
-    return ISE_OK;
-}
+extern "C" int ise_binary_selector_info(const ise_binary_selector_t* sel, int64_t* out5) { return selector_info(sel, out5); }
 
 extern "C" int ise_binary_selector_destroy(ise_binary_selector_t* sel) {
     if (!sel) return ISE_OK;
@@ -759,11 +658,11 @@ extern "C" int ise_binary_index_search_sel_host(ise_binary_index_t* h, const uin
     if ((rc = bin_grow(h->oD, cnt))) return rc;
     if ((rc = bin_grow(h->oI, cnt))) return rc;
     if ((rc = bin_begin(h, h->stream))) return rc;
-    BIN_TRY(hipMemcpyAsync(h->raw.p, q, (size_t)nq * h->code_size, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->raw.p, q, (size_t)nq * h->code_size, hipMemcpyHostToDevice, h->stream));
     if ((rc = search_enqueue(h, h->raw.p, nq, k, h->oD.p, h->oI.p, h->stream, sel))) return rc;
-    BIN_TRY(hipMemcpyAsync(D, h->oD.p, cnt * 4, hipMemcpyDeviceToHost, h->stream));
-    BIN_TRY(hipMemcpyAsync(I, h->oI.p, cnt * 8, hipMemcpyDeviceToHost, h->stream));
-    BIN_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(D, h->oD.p, cnt * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(I, h->oI.p, cnt * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return ISE_OK;
 }
 
@@ -779,10 +678,6 @@ extern "C" int ise_binary_index_sel_stats(ise_binary_index_t* h, uint64_t* out3)
 
 // ---- remove_ids: stable in-place compaction of the code rows (ise_remove.hpp)
 namespace {
-struct BinRemoveRun {
-    long long start, len;
-};
-
 // everything a removal allocates for the duration of the call
 struct BinRemoveScratch {
     uint32_t* g = nullptr;        // [T] destination row at which run t bites
@@ -796,36 +691,28 @@ struct BinRemoveScratch {
 };
 
 // runs: sorted, disjoint, non-adjacent, non-empty, inside [0, h->n).  mu held.
-int remove_runs_locked(ise_binary_index* h, const std::vector<BinRemoveRun>& runs, long long removed) {
+int remove_runs_locked(ise_binary_index* h, const std::vector<RemoveRun>& runs, long long removed) {
     const long long n_old = h->n, n_new = n_old - removed, first = runs[0].start;
     const long long moved = n_new - first;  // destination rows [first, n_new) get a new row
     hipStream_t st = h->stream;
-    BIN_TRY(hipDeviceSynchronize());  // nothing in flight reads the rows while they move
+    HIP_TRY(hipDeviceSynchronize());  // nothing in flight reads the rows while they move
     if (moved > 0) {
         BinRemoveScratch sc;
         const long long T = (long long)runs.size();
-        std::vector<uint32_t> g((size_t)T), cend((size_t)T);
-        long long c = 0;
-        for (long long t = 0; t < T; t++) {
-            g[(size_t)t] = (uint32_t)(runs[(size_t)t].start - c);
-            c += runs[(size_t)t].len;
-            cend[(size_t)t] = (uint32_t)c;
-        }
+        std::vector<uint32_t> g, cend;
+        remove_plan_tables(runs, &g, &cend);
         // slab: at most 256 MiB of rows in the bounce buffer, as the float index; a slab's units (16 bytes, or the
         // 8-byte rows of ws == 1) stay below 2^31 whatever $ISE_REMOVE_SLAB_ROWS says
         const size_t rb = (size_t)h->ws * 8;
         const uint32_t upr = (uint32_t)std::max(1, h->ws / 2);
-        long long slab = ise_remove_slab_rows_();
-        if (slab <= 0) slab = std::max<long long>(1, (256ll << 20) / (long long)rb);
-        slab = std::min(slab, std::max<long long>(1, (1ll << 31) / (long long)upr));
-        slab = std::min(slab, moved);
-        BIN_TRY(hipMalloc((void**)&sc.g, (size_t)T * sizeof(uint32_t)));
-        BIN_TRY(hipMalloc((void**)&sc.cend, (size_t)T * sizeof(uint32_t)));
-        BIN_TRY(hipMalloc((void**)&sc.src_idx, (size_t)slab * sizeof(uint32_t)));
-        BIN_TRY(hipMalloc((void**)&sc.bounce, (size_t)slab * rb));
-        BIN_TRY(hipMemcpyAsync(sc.g, g.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        BIN_TRY(hipMemcpyAsync(sc.cend, cend.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        BIN_TRY(hipStreamSynchronize(st));  // g and cend are pageable host vectors
+        const long long slab = remove_plan_slab_rows(ise_remove_slab_rows_(), (long long)rb, (long long)upr, moved);
+        HIP_TRY(hipMalloc((void**)&sc.g, (size_t)T * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void**)&sc.cend, (size_t)T * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void**)&sc.src_idx, (size_t)slab * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void**)&sc.bounce, (size_t)slab * rb));
+        HIP_TRY(hipMemcpyAsync(sc.g, g.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(sc.cend, cend.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));  // g and cend are pageable host vectors
         for (long long a = first; a < n_new; a += slab) {
             const long long m = std::min(slab, n_new - a);
             const unsigned gw = (unsigned)std::min<long long>((m + 255) / 256, (long long)h->num_cu * 8);
@@ -847,9 +734,9 @@ int remove_runs_locked(ise_binary_index* h, const std::vector<BinRemoveRun>& run
                 hipLaunchKernelGGL(remove_rows_kernel<false>, dim3(grid), dim3(256), 0, st, (const u32x4*)sc.bounce,
                                    (const uint32_t*)nullptr, (u32x4*)(h->codes + (size_t)a * h->ws), total, upr);
             }
-            BIN_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
-        BIN_TRY(hipStreamSynchronize(st));  // before the scratch is freed; a removal blocks
+        HIP_TRY(hipStreamSynchronize(st));  // before the scratch is freed; a removal blocks
     }
     // the tail [n_new, n_old) keeps its stale rows: masked by row number, like the rows a reset leaves behind
     h->n = n_new;
@@ -870,7 +757,7 @@ extern "C" int ise_binary_index_remove_range(ise_binary_index_t* h, int64_t i0, 
     if (a >= b) return ISE_OK;  // nothing to remove: no synchronisation, no counters
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
-    const int rc = remove_runs_locked(h, {BinRemoveRun{a, b - a}}, b - a);
+    const int rc = remove_runs_locked(h, {RemoveRun{a, b - a}}, b - a);
     if (rc == ISE_OK && n_removed) *n_removed = b - a;
     return rc;
 }
@@ -881,25 +768,16 @@ extern "C" int ise_binary_index_remove_ids_host(ise_binary_index_t* h, const int
     if (n_ids < 0 || (n_ids > 0 && !ids)) return ise_fail_(ISE_E_INVALID, "ids is NULL");
     if (n_ids == 0) return ISE_OK;
     std::vector<long long> v;
-    std::vector<BinRemoveRun> runs;
+    std::vector<RemoveRun> runs;
     long long removed = 0;
     try {
-        v.reserve((size_t)n_ids);
-        for (int64_t i = 0; i < n_ids; i++)
-            if (ids[i] >= 0) v.push_back(ids[i]);
-        std::sort(v.begin(), v.end());
-        v.erase(std::unique(v.begin(), v.end()), v.end());
+        v = remove_plan_ids(ids, n_ids);
     } catch (const std::bad_alloc&) {
         return ise_fail_(ISE_E_NOMEM, "remove_ids: host allocation failed");
     }
     std::lock_guard<std::mutex> lk(h->mu);
     try {
-        for (long long id : v) {
-            if (id >= h->n) break;  // sorted: the rest does not exist either
-            if (!runs.empty() && runs.back().start + runs.back().len == id) runs.back().len++;
-            else runs.push_back(BinRemoveRun{id, 1});
-            removed++;
-        }
+        removed = remove_plan_runs(v, h->n, &runs);
     } catch (const std::bad_alloc&) {
         return ise_fail_(ISE_E_NOMEM, "remove_ids: host allocation failed");
     }

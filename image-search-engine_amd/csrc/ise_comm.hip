@@ -15,9 +15,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
-#include "ise_common.hpp"
-
-extern int ise_fail_(int code, const std::string& msg);  // ise_knn.hip: sets the thread-local message
+#include "ise_host.hpp"
 
 namespace {
 struct RcclApi {

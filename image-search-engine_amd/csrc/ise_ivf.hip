@@ -10,40 +10,27 @@
 // swapped in together (a pass still in flight on another stream keeps a consistent set); the old ones and the pending
 // buffer are freed when it is done.  Between calls the index holds the sorted array (exact size) plus the pending
 // buffer (at most twice the pending rows).
+#include "ise_host.hpp"
 #include "ise_geometry.hpp"
 #include "ise_scan_params.hpp"
 #include "ise_ivf.hpp"
 #include "ise_ivf_plan.hpp"
 
-extern int ise_fail_(int code, const std::string& msg);  // ise_knn.hip: sets the thread-local message
-
-#define IVF_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return ise_fail_(e_ == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP,                  \
-                             std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
-
 #define IVF_NQ_CHUNK 64 /* queries per launch (4 groups of 16): bounds the per-block lists */
 
 namespace {
 
-template <class T>
-struct DevBuf {  // grown lazily, contents not kept
-    T* p = nullptr;
-    size_t n = 0;
-};
 // busy: the event behind the last pass that used the workspaces, or null -- waited for only when the buffer really has
 // to be replaced (then the call blocks)
+// rule: a free waits for that one event only -- every pass that used the workspaces is ordered before it
 template <class T>
 int grow(DevBuf<T>& b, size_t need, hipEvent_t busy) {
     if (need <= b.n) return ISE_OK;
-    if (b.p && busy) IVF_TRY(hipEventSynchronize(busy));
+    if (b.p && busy) HIP_TRY(hipEventSynchronize(busy));
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr;
     b.n = 0;
-    IVF_TRY(hipMalloc((void**)&b.p, need * sizeof(T)));
+    HIP_TRY(hipMalloc((void**)&b.p, need * sizeof(T)));
     b.n = need;
     return ISE_OK;
 }
@@ -110,7 +97,7 @@ extern "C" int ise_ivf_create(ise_ivf_t** out, int d, int metric, int nlist, int
         return ise_fail_(ISE_E_NODEVICE, "no HIP device visible: the kNN path needs an MI355X (gfx950) GPU");
     if (device < 0 || device >= ndev) return ise_fail_(ISE_E_INVALID, "device out of range");
     hipDeviceProp_t prop;
-    IVF_TRY(hipGetDeviceProperties(&prop, device));
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return ise_fail_(ISE_E_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
     ise_ivf* h = new (std::nothrow) ise_ivf();
@@ -162,7 +149,7 @@ extern "C" int ise_ivf_reset(ise_ivf_t* h) {
     if (!h) return ise_fail_(ISE_E_INVALID, "handle is NULL");
     std::lock_guard<std::mutex> lk(h->mu_);
     DeviceGuard gd(h->device);
-    IVF_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipDeviceSynchronize());
     ivf_free_rows(h);
     return ISE_OK;
 }
@@ -184,7 +171,7 @@ static int ivf_reserve_pending(ise_ivf* h, long long n, hipStream_t st) {
     if (need <= h->pend_cap) return ISE_OK;
     const long long cap = std::max(need, 2 * h->pend_cap);
     float* nx = nullptr;
-    IVF_TRY(hipMalloc((void**)&nx, (size_t)cap * h->dp * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&nx, (size_t)cap * h->dp * sizeof(float)));
     if (h->pend_n > 0) {
         hipError_t e = hipMemcpyAsync(nx, h->pend, (size_t)h->pend_n * h->dp * sizeof(float), hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -232,10 +219,10 @@ extern "C" int ise_ivf_add_host(ise_ivf_t* h, const float* x, const int64_t* lis
     rc = ivf_reserve_pending(h, n, h->stream);
     if (rc) return rc;
     float* dst = h->pend + (size_t)h->pend_n * h->dp;
-    if (h->dp != h->d) IVF_TRY(hipMemsetAsync(dst, 0, (size_t)n * h->dp * sizeof(float), h->stream));
-    IVF_TRY(hipMemcpy2DAsync(dst, (size_t)h->dp * sizeof(float), x, (size_t)h->d * sizeof(float), (size_t)h->d * sizeof(float),
+    if (h->dp != h->d) HIP_TRY(hipMemsetAsync(dst, 0, (size_t)n * h->dp * sizeof(float), h->stream));
+    HIP_TRY(hipMemcpy2DAsync(dst, (size_t)h->dp * sizeof(float), x, (size_t)h->d * sizeof(float), (size_t)h->d * sizeof(float),
                              (size_t)n, hipMemcpyHostToDevice, h->stream));
-    IVF_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     ivf_commit_add(h, list_no, n);
     return ISE_OK;
 }
@@ -249,8 +236,8 @@ extern "C" int ise_ivf_add_device(ise_ivf_t* h, const float* x_dev, const int64_
     std::lock_guard<std::mutex> lk(h->mu_);
     DeviceGuard gd(h->device);
     std::vector<int64_t> lists((size_t)n);
-    IVF_TRY(hipMemcpyAsync(lists.data(), list_no_dev, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    IVF_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(lists.data(), list_no_dev, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     int rc = ivf_check_lists(h, lists.data(), n);
     if (rc) return rc;
     rc = ivf_reserve_pending(h, n, st);
@@ -258,8 +245,8 @@ extern "C" int ise_ivf_add_device(ise_ivf_t* h, const float* x_dev, const int64_
     const long long tot = (long long)n * h->dp;
     hipLaunchKernelGGL(sel_pad_queries_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x_dev, h->d, h->dp, tot,
                        h->pend + (size_t)h->pend_n * h->dp);
-    IVF_TRY(hipGetLastError());
-    IVF_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
     ivf_commit_add(h, lists.data(), n);
     return ISE_OK;
 }
@@ -286,19 +273,19 @@ static int ivf_rebuild_locked(ise_ivf* h, hipStream_t st) {
         }
     } fr{{(void**)&nx, (void**)&nn, (void**)&partial, (void**)&nids, (void**)&nmeta, (void**)&dest, (void**)&nmu}};
     const size_t nmeta_n = 2 * nlist + 1 + (size_t)tiles;
-    IVF_TRY(hipMalloc((void**)&nx, slots * h->dp * sizeof(float)));
-    IVF_TRY(hipMalloc((void**)&nn, slots * sizeof(float)));
-    IVF_TRY(hipMalloc((void**)&nids, slots * sizeof(uint32_t)));
-    IVF_TRY(hipMalloc((void**)&nmeta, nmeta_n * sizeof(uint32_t)));
-    IVF_TRY(hipMalloc((void**)&dest, (size_t)h->pend_n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&nx, slots * h->dp * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&nn, slots * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&nids, slots * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&nmeta, nmeta_n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&dest, (size_t)h->pend_n * sizeof(uint32_t)));
     std::vector<uint32_t> meta_host(nmeta_n);
     std::copy(pl.tile0.begin(), pl.tile0.end(), meta_host.begin());
     for (size_t l = 0; l < nlist; l++) meta_host[nlist + 1 + l] = (uint32_t)pl.size[l];
     std::copy(pl.tile_list.begin(), pl.tile_list.end(), meta_host.begin() + 2 * nlist + 1);
-    IVF_TRY(hipMemcpyAsync(nmeta, meta_host.data(), nmeta_n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    IVF_TRY(hipMemcpyAsync(dest, pl.dest.data(), (size_t)h->pend_n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    IVF_TRY(hipMemsetAsync(nx, 0, slots * h->dp * sizeof(float), st));   // pad slots read as zero rows
-    IVF_TRY(hipMemsetAsync(nids, 0xFF, slots * sizeof(uint32_t), st));
+    HIP_TRY(hipMemcpyAsync(nmeta, meta_host.data(), nmeta_n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dest, pl.dest.data(), (size_t)h->pend_n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(nx, 0, slots * h->dp * sizeof(float), st));   // pad slots read as zero rows
+    HIP_TRY(hipMemsetAsync(nids, 0xFF, slots * sizeof(uint32_t), st));
     if (h->tiles > 0)
         hipLaunchKernelGGL(ivf_move_tiles_kernel, dim3((unsigned)h->tiles), dim3(256), 0, st, (const float*)h->xb,
                            (const uint32_t*)h->ids, h->tile_list_dev(), h->list_tile0_dev(), (const uint32_t*)nmeta, h->dp, nx, nids);
@@ -307,8 +294,8 @@ static int ivf_rebuild_locked(ise_ivf* h, hipStream_t st) {
     if (h->metric == ISE_METRIC_L2) {
         // the shift vector: the column mean of the rows as they stand (it decides how tight the bounds are, nothing else)
         // into a buffer of its own, swapped in with the rows: a pass still in flight keeps the mu its norms belong to
-        IVF_TRY(hipMalloc((void**)&nmu, (size_t)h->dp * sizeof(float)));
-        IVF_TRY(hipMalloc((void**)&partial, (size_t)groups * h->dp * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&nmu, (size_t)h->dp * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&partial, (size_t)groups * h->dp * sizeof(float)));
         const unsigned gx = (unsigned)((h->dp + 255) / 256);
         hipLaunchKernelGGL(ivf_col_sum_kernel, dim3(gx, (unsigned)groups), dim3(256), 0, st, (const float*)nx, (long long)slots,
                            h->d, h->dp, groups, partial);
@@ -317,10 +304,10 @@ static int ivf_rebuild_locked(ise_ivf* h, hipStream_t st) {
         hipLaunchKernelGGL(ivf_norms_kernel, dim3((unsigned)((slots + 3) / 4)), dim3(256), 0, st, (const float*)nx, (long long)slots,
                            h->dp, (const float*)nmu, nn);
     } else {
-        IVF_TRY(hipMemsetAsync(nn, 0, slots * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(nn, 0, slots * sizeof(float), st));
     }
-    IVF_TRY(hipGetLastError());
-    IVF_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
     std::swap(h->xb, nx);  // the old arrays go with the guard (hipFree waits for the passes that still read them)
     if (nmu) std::swap(h->mu, nmu);
     std::swap(h->norms, nn);
@@ -356,11 +343,11 @@ extern "C" int ise_ivf_list_host(ise_ivf_t* h, int list, int64_t* ids, float* ro
     const size_t slot0 = (size_t)h->tile0[(size_t)list] * 16;
     if (ids) {
         std::vector<uint32_t> tmp(m);
-        IVF_TRY(hipMemcpy(tmp.data(), h->ids + slot0, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tmp.data(), h->ids + slot0, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < m; i++) ids[i] = (int64_t)tmp[i];
     }
     if (rows)
-        IVF_TRY(hipMemcpy2D(rows, (size_t)h->d * sizeof(float), h->xb + slot0 * h->dp, (size_t)h->dp * sizeof(float),
+        HIP_TRY(hipMemcpy2D(rows, (size_t)h->d * sizeof(float), h->xb + slot0 * h->dp, (size_t)h->dp * sizeof(float),
                             (size_t)h->d * sizeof(float), m, hipMemcpyDeviceToHost));
     return ISE_OK;
 }
@@ -412,7 +399,7 @@ static int ivf_chunk_enqueue(ise_ivf* h, const float* q_dev, long long m, int k,
     const long long qtot = m * h->dp;
     hipLaunchKernelGGL(sel_pad_queries_kernel, dim3((unsigned)((qtot + 255) / 256)), dim3(256), 0, st, q_dev, h->d, h->dp, qtot,
                        h->q.p);
-    IVF_TRY(hipMemsetAsync(h->masks.p, 0, (size_t)groups * h->nlist * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(h->masks.p, 0, (size_t)groups * h->nlist * sizeof(uint32_t), st));
     const long long ptot = m * nprobe;
     hipLaunchKernelGGL(ivf_mask_kernel, dim3((unsigned)((ptot + 255) / 256)), dim3(256), 0, st, probes_dev, ptot, nprobe, h->nlist,
                        h->masks.p);
@@ -449,7 +436,7 @@ static int ivf_chunk_enqueue(ise_ivf* h, const float* q_dev, long long m, int k,
                                (int)m, kp, off, k, h->metric, D_dev, I_dev, floors);
         }
     }
-    IVF_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return ISE_OK;
 }
 
@@ -459,13 +446,13 @@ static int ivf_search_enqueue(ise_ivf* h, const float* q_dev, long long nq, int 
     h->batches++;
     // a search still in flight on another stream comes first on the device: before the rebuild and before the
     // workspaces are written.  (The host waits only where a buffer is replaced: grow, ivf_rebuild_locked.)
-    if (h->used && h->last_stream != st) IVF_TRY(hipStreamWaitEvent(st, h->done, 0));
+    if (h->used && h->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->done, 0));
     int rc = ivf_rebuild_locked(h, st);
     if (rc) return rc;
     if (h->tiles == 0) {  // an empty index: padding, no pass
         const long long tot = nq * k;
         hipLaunchKernelGGL(sel_fill_pad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, tot, h->metric);
-        IVF_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         return ISE_OK;
     }
     struct Release {  // whatever path returns, a later user on another stream waits for this call
@@ -523,21 +510,21 @@ extern "C" int ise_ivf_search_host(ise_ivf_t* h, const float* q, int64_t nq, int
                 if (*x) (void)hipFree(*x);
         }
     } fr{{(void**)&q_dev, (void**)&D_dev, (void**)&p_dev, (void**)&I_dev}};
-    IVF_TRY(hipMalloc((void**)&q_dev, (size_t)batch * h->d * sizeof(float)));
-    IVF_TRY(hipMalloc((void**)&p_dev, (size_t)batch * nprobe * sizeof(long long)));
-    IVF_TRY(hipMalloc((void**)&D_dev, (size_t)batch * k * sizeof(float)));
-    IVF_TRY(hipMalloc((void**)&I_dev, (size_t)batch * k * sizeof(long long)));
+    HIP_TRY(hipMalloc((void**)&q_dev, (size_t)batch * h->d * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&p_dev, (size_t)batch * nprobe * sizeof(long long)));
+    HIP_TRY(hipMalloc((void**)&D_dev, (size_t)batch * k * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&I_dev, (size_t)batch * k * sizeof(long long)));
     hipStream_t st = h->stream;
     for (long long i0 = 0; i0 < nq; i0 += batch) {
         const long long m = std::min<long long>(batch, nq - i0);
-        IVF_TRY(hipMemcpyAsync(q_dev, q + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice, st));
-        IVF_TRY(hipMemcpyAsync(p_dev, probes + (size_t)i0 * nprobe, (size_t)m * nprobe * sizeof(long long), hipMemcpyHostToDevice,
+        HIP_TRY(hipMemcpyAsync(q_dev, q + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(p_dev, probes + (size_t)i0 * nprobe, (size_t)m * nprobe * sizeof(long long), hipMemcpyHostToDevice,
                                st));
         rc = ivf_search_enqueue(h, q_dev, m, k, p_dev, nprobe, D_dev, I_dev, st);
         if (rc) return rc;
-        IVF_TRY(hipMemcpyAsync(D + (size_t)i0 * k, D_dev, (size_t)m * k * sizeof(float), hipMemcpyDeviceToHost, st));
-        IVF_TRY(hipMemcpyAsync(I + (size_t)i0 * k, I_dev, (size_t)m * k * sizeof(long long), hipMemcpyDeviceToHost, st));
-        IVF_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(D + (size_t)i0 * k, D_dev, (size_t)m * k * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(I + (size_t)i0 * k, I_dev, (size_t)m * k * sizeof(long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     return ISE_OK;
 }
@@ -547,8 +534,8 @@ extern "C" int ise_ivf_stats(ise_ivf_t* h, uint64_t* out3) {
     std::lock_guard<std::mutex> lk(h->mu_);
     DeviceGuard gd(h->device);
     unsigned long long loaded = 0;
-    IVF_TRY(hipDeviceSynchronize());  // the passes enqueued so far have added their tiles
-    IVF_TRY(hipMemcpy(&loaded, h->stats_dev, sizeof(loaded), hipMemcpyDeviceToHost));
+    HIP_TRY(hipDeviceSynchronize());  // the passes enqueued so far have added their tiles
+    HIP_TRY(hipMemcpy(&loaded, h->stats_dev, sizeof(loaded), hipMemcpyDeviceToHost));
     out3[0] = h->batches;
     out3[1] = h->passes;
     out3[2] = loaded;

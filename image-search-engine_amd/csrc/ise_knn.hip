@@ -27,6 +27,11 @@
 //   remove_ids     ise_remove.hpp  stable in-place compaction of the rows and of everything kept per row
 //   selectors      ise_sel_scan.hpp  search / range search among the rows a device bitmap names: one masked pass per 16 queries
 //
+// Host headers shared with the other index kinds (ise_binary_scan.hip, ise_ivf.hip)
+//   ise_host.hpp         ise_fail_ (defined here), HIP_TRY, DevBuf
+//   ise_selector.hpp     the selector object: allocate, fill, census, info, free
+//   ise_remove_plan.hpp  remove_ids planning without a device call: ids -> runs -> g / cend tables, slab size
+//
 // Candidate order: a 64-bit key = ord(score) << 32 | row id, where ord() is the
 // order-preserving map float -> uint32 and score = squared L2 (or -inner product).
 // Ascending key order is (score, id) order, which is the order Faiss reports (ties by
@@ -35,7 +40,7 @@
 //
 // This file: the host side and the C ABI (include/ise_knn.h).
 
-#include "ise_common.hpp"
+#include "ise_host.hpp"
 #include "ise_geometry.hpp"
 #include "ise_scan_params.hpp"
 #include "ise_assign.hpp"
@@ -50,21 +55,16 @@
 #include "ise_sel_scan.hpp"
 #include "ise_stage.hpp"
 #include "ise_remove.hpp"
+#include "ise_remove_plan.hpp"
+#include "ise_selector.hpp"
 
 // ---------------------------------------------------------------- host side
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) {
+int ise_fail_(int code, const std::string& msg) {  // ise_host.hpp: every translation unit's error path
     g_err = msg;
     return code;
 }
-int ise_fail_(int code, const std::string& msg) { return fail(code, msg); }  // for the other translation units
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(e_ == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP,               \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                \
-    } while (0)
+static int fail(int code, const std::string& msg) { return ise_fail_(code, msg); }
 
 struct ise_index {
     int d = 0, dp = 0, metric = ISE_METRIC_L2, device = 0;
@@ -169,25 +169,20 @@ struct ise_index {
     std::mutex mu_;
     // range search (ise_range.hpp): a workspace of its own, grown lazily and held by one call at a time (rg_mu,
     // taken before mu_); the WorkSlot rotation of search is never touched
-    template <class T>
-    struct Buf {  // grown lazily, contents not kept (ise_knn.hip, range_grow)
-        T* p = nullptr;
-        size_t n = 0;
-    };
     struct RangeWs {
-        Buf<float> q;                        // [m][dp] padded queries
-        Buf<unsigned> cnt;                   // [m][nseg] hits per segment
-        Buf<long long> segoff;               // [m][nseg] offset of a segment within its query
-        Buf<float> sD;                       // [m][nseg][cap] staged distances
-        Buf<uint32_t> sI;                    // [m][nseg][cap] staged row ids
-        Buf<long long> tot, lims;            // [m], [m + 1]
-        Buf<unsigned> flag;                  // overflow flag
-        Buf<float> D;                        // [total]
-        Buf<long long> I;                    // [total]
-        Buf<float> q_pin;                    // page-locked staging
-        Buf<long long> lims_pin;             // [m + 1] lims, then the overflow flag
-        Buf<float> D_pin;
-        Buf<long long> I_pin;
+        DevBuf<float> q;                        // [m][dp] padded queries
+        DevBuf<unsigned> cnt;                   // [m][nseg] hits per segment
+        DevBuf<long long> segoff;               // [m][nseg] offset of a segment within its query
+        DevBuf<float> sD;                       // [m][nseg][cap] staged distances
+        DevBuf<uint32_t> sI;                    // [m][nseg][cap] staged row ids
+        DevBuf<long long> tot, lims;            // [m], [m + 1]
+        DevBuf<unsigned> flag;                  // overflow flag
+        DevBuf<float> D;                        // [total]
+        DevBuf<long long> I;                    // [total]
+        DevBuf<float> q_pin;                    // page-locked staging
+        DevBuf<long long> lims_pin;             // [m + 1] lims, then the overflow flag
+        DevBuf<float> D_pin;
+        DevBuf<long long> I_pin;
     };
     RangeWs rg;
     std::mutex rg_mu;
@@ -204,9 +199,9 @@ struct ise_index {
     // run beside unfiltered ones and beside each other
     unsigned long long row_epoch = 0;
     struct SelSlot {
-        Buf<float> q;      // [chunk][dp] padded queries
-        Buf<u64> part;     // [groups][blocks][16][kpass]
-        Buf<u64> keys;     // [chunk][32] one pass's merged keys (k > 32) | [chunk] floors
+        DevBuf<float> q;      // [chunk][dp] padded queries
+        DevBuf<u64> part;     // [groups][blocks][16][kpass]
+        DevBuf<u64> keys;     // [chunk][32] one pass's merged keys (k > 32) | [chunk] floors
         hipEvent_t done = nullptr;
         bool used = false;
         hipStream_t last_stream = nullptr;
@@ -887,7 +882,7 @@ extern "C" int ise_refresh_env_knobs(void) {
     knobs().refresh();
     return ISE_OK;
 }
-int ise_remove_slab_rows_() { return knobs().remove_slab_rows.load(std::memory_order_relaxed); }  // ise_binary_scan.hip
+int ise_remove_slab_rows_() { return knobs().remove_slab_rows.load(std::memory_order_relaxed); }  // ise_host.hpp
 static bool force_exact() { return knobs().force_exact.load(std::memory_order_relaxed) != 0; }
 static bool byte_alloc_refused() { return knobs().fail_byte_alloc.load(std::memory_order_relaxed) != 0; }
 
@@ -1400,83 +1395,6 @@ static int launch_gemm(int ns, int grid, size_t lds, hipStream_t st, const GemmS
     return ISE_OK;
 }
 
-// one chunk of <= GEMM_NQ_MAX queries; the slot w is already this stream's
-static int search_large_chunk(ise_index* h, ise_index::WorkSlot* w, const float* q_dev, long long nq, int k,
-                              uint32_t id_base, float* D_dev, long long* I_dev, u64* keys_out, hipStream_t st,
-                              TimedOut* tm) {
-    const int kc = k + exact_extra(k);
-    const int S = qs_stride_for(h);
-    const GemmLayout gl = gemm_layout(h);
-    h->gemm_chunks++;
-    float* qprep = reinterpret_cast<float*>(w->gemm + gl.qprep);
-    float* xn = reinterpret_cast<float*>(w->gemm + gl.xn);
-    float* tau = reinterpret_cast<float*>(w->gemm + gl.tau);
-    unsigned int* ccnt = reinterpret_cast<unsigned int*>(w->gemm + gl.ccnt);
-    float* dump = reinterpret_cast<float*>(w->gemm + gl.dump);
-    u64* cand = reinterpret_cast<u64*>(w->gemm + gl.cand);
-    const int nq_pad = (int)((nq + GQ - 1) / GQ * GQ);
-    int rc;
-
-    if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e0, st));
-    hipLaunchKernelGGL(qprep_kernel, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, q_dev, (int)nq, nq_pad, h->d, S,
-                       (const float*)h->mu, qprep, xn);
-    HIP_TRY(hipGetLastError());
-
-    GemmScanParams gp;
-    gp.xb = (const float*)h->xb; gp.norms = h->norms; gp.mu = h->mu; gp.n = h->n; gp.rows16 = (h->n + 15) / 16 * 16;
-    gp.dp = h->dp; gp.S = S; gp.qprep = qprep; gp.xn = xn; gp.tau = tau; gp.nq = (int)nq; gp.nq_pad = nq_pad;
-    gp.beta = exact_beta(h); gp.id_base = id_base; gp.metric = ISE_METRIC_L2;
-    gp.wbuf = reinterpret_cast<u32x4*>(w->gemm + gl.wbuf); gp.wcnt = reinterpret_cast<unsigned int*>(w->gemm + gl.wcnt);
-    gp.capw = GEMM_CAPW;
-    gp.ablate = 0;
-    const int slabs_all = (int)((h->n + 127) / 128);
-    const size_t lds = gemm_lds_bytes(S);
-    const int ns = h->dp / 16;
-
-    // ---- thresholds: GEMM_SAMPLE_SLABS slabs spread over the index, every score dumped, k-th selected per query.
-    // One slab per block, the query stages split over qparts blocks per slab, so that the sample
-    // keeps every CU busy for a fraction of a slab's time.
-    gp.slabs = std::min(slabs_all, GEMM_SAMPLE_SLABS);
-    gp.slab_stride = slabs_all / gp.slabs;
-    const int nstages = nq_pad / GQ;
-    gp.qparts = std::max(1, std::min(nstages, (2 * h->num_cu) / gp.slabs));
-    gp.dump = dump;
-    if ((rc = launch_gemm<true>(ns, gp.slabs * gp.qparts, lds, st, gp))) return rc;
-    hipLaunchKernelGGL(kth_select_kernel, dim3((unsigned)nq_pad), dim3(256), 0, st, (const float*)dump, gp.slabs * 128, kc,
-                       (int)nq, tau);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(ccnt, 0, (size_t)(GEMM_NQ_MAX * GEMM_SUBS + 64) * 4, st));  // the counters and, behind them, the overflow flag
-
-    // ---- the GEMM-shaped pass over the whole index
-    gp.slabs = slabs_all; gp.slab_stride = 1; gp.qparts = 1; gp.dump = nullptr;
-    const int grid = std::min(slabs_all, h->num_cu);
-    if ((rc = launch_gemm<false>(ns, grid, lds, st, gp))) return rc;
-    unsigned int* overflow = ccnt + GEMM_NQ_MAX * GEMM_SUBS;
-    hipLaunchKernelGGL(regroup_kernel, dim3((unsigned)grid * 8), dim3(256), 0, st, (const u32x4*)gp.wbuf,
-                       (const unsigned int*)gp.wcnt, GEMM_CAPW, cand, ccnt, GEMM_CAPQ, overflow);
-    HIP_TRY(hipGetLastError());
-    if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e1, st));
-
-    // ---- select the kc best candidates, re-rank exactly, certify; the exact scan takes what fails
-    ScanPlan pl;  // shapes the exact fallback scan (blocks, rows per block) and sized the slot's lists
-    rc = make_plan(h, nq, k, &pl);
-    if (rc) return rc;
-    ExactParams xp;
-    xp.xb = (const float*)h->xb; xp.q = q_dev; xp.n = h->n; xp.d = h->d; xp.dp = h->dp; xp.nq = (int)nq;
-    xp.k = k; xp.kc = kc; xp.id_base = id_base; xp.D = D_dev; xp.I = I_dev; xp.keys_out = keys_out;
-    xp.fl_state = w->fl_state; xp.fl_list = w->fl_list; xp.seq = 0; xp.stats = h->stats_dev;
-    xp.force_fail = force_exact() ? 1 : 0;
-    xp.tau_bound = tau;
-    if ((rc = next_fl_seq(w, st, &xp.seq))) return rc;
-    hipLaunchKernelGGL(gemm_select_kernel, dim3((unsigned)nq), dim3(256),
-                       rerank_lds_bytes(h->dp, kc) + (size_t)(GEMM_CAPQ + 256) * 8, st, xp, (const u64*)cand,
-                       (const unsigned int*)ccnt, GEMM_CAPQ, (const unsigned int*)overflow);
-    HIP_TRY(hipGetLastError());
-    if ((rc = enqueue_exact_fallback(h, w, pl, xp, nq, st))) return rc;
-    if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e2, st));
-    return ISE_OK;
-}
-
 // The streaming path for one batch on slot w: scan pass(es) -> merge (-> exact re-rank -> gated exact scan
 // for float32 L2).  gate: optional device flag -- when given, every kernel of the batch exits at once
 // unless it is non-zero (the bf16 large-batch path queues this behind itself for the case that its
@@ -1640,85 +1558,47 @@ static int launch_gemm_bf16(int ns, int grid, size_t lds, hipStream_t st, const 
     return ISE_OK;
 }
 
-// bf16 rows, one chunk of <= GEMM_NQ_MAX queries (ise_gemm_bf16.hpp): sample dump -> thresholds -> GEMM pass ->
-// regroup -> select; then the streaming passes, gated on the rerun flag (set when a candidate buffer overflowed)
-static int search_large_chunk_bf16(ise_index* h, ise_index::WorkSlot* w, const float* q_dev, long long nq, int k,
-                                   uint32_t id_base, float* D_dev, long long* I_dev, u64* keys_out, hipStream_t st,
-                                   TimedOut* tm) {
+// What differs between the three flavours of the large-batch path:
+//   float32 L2 (ise_gemm_scan.hpp): shifted rows and norms, lower bounds with slack beta, kc = k + spare candidates
+//     selected and re-ranked exactly; the exact scan takes what the certificate cannot prove
+//   float32 inner product: the same pass without shift, norms or re-rank (the reference's default index type is
+//     "cosine" = IndexFlatIP over normalised rows, backend/utils.py:293,300-303); same bits as the streaming passes,
+//     the kernel sums a dot product in scan_kernel's order
+//   bf16 rows, either metric (ise_gemm_bf16.hpp)
+// The last two select k plainly and queue the streaming passes behind, gated on the rerun flag (set when a candidate
+// buffer overflowed).
+struct GemmFlavour {
+    bool bf16;        // the rows' element type: qprep_bf16_kernel + the launch_gemm_bf16 ladder, else qprep_kernel + launch_gemm
+    bool rerank;      // float32 L2: gemm_select_kernel + exact fallback; else gemm_select_plain_kernel + gated rerun
+    int gq;           // queries per stage (nq is padded to whole stages)
+    int rows;         // rows per slab
+    size_t lds;
+    int ns;           // k-steps: the ladder's template argument
+    float beta;
+    const float* mu;  // the shift, for the query prep and the pass
+    int kth;          // the sampled score that becomes a query's threshold
+};
+static GemmFlavour gemm_flavour(const ise_index* h, int k) {
     const int S = qs_stride_for(h);
-    const GemmLayout gl = gemm_layout(h);
-    h->gemm_chunks++;
-    uint32_t* qprep = reinterpret_cast<uint32_t*>(w->gemm + gl.qprep);
-    float* xn = reinterpret_cast<float*>(w->gemm + gl.xn);
-    float* tau = reinterpret_cast<float*>(w->gemm + gl.tau);
-    unsigned int* ccnt = reinterpret_cast<unsigned int*>(w->gemm + gl.ccnt);
-    float* dump = reinterpret_cast<float*>(w->gemm + gl.dump);
-    u64* cand = reinterpret_cast<u64*>(w->gemm + gl.cand);
-    const int nq_pad = (int)((nq + GB_GQ - 1) / GB_GQ * GB_GQ);
-    int rc;
-
-    if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e0, st));
-    hipLaunchKernelGGL(qprep_bf16_kernel, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, q_dev, (int)nq, nq_pad, h->d, S,
-                       qprep, xn);
-    HIP_TRY(hipGetLastError());
-
-    constexpr int ROWS = 8 * GB_XT * 16;
-    GemmScanParams gp;
-    gp.xb = (const float*)h->xb; gp.norms = h->norms; gp.mu = nullptr; gp.n = h->n; gp.rows16 = (h->n + 15) / 16 * 16;
-    gp.dp = h->dp; gp.S = S; gp.qprep = reinterpret_cast<const float*>(qprep); gp.xn = xn; gp.tau = tau; gp.nq = (int)nq;
-    gp.nq_pad = nq_pad; gp.beta = 0.f; gp.metric = h->metric; gp.id_base = id_base;
-    gp.wbuf = reinterpret_cast<u32x4*>(w->gemm + gl.wbuf); gp.wcnt = reinterpret_cast<unsigned int*>(w->gemm + gl.wcnt);
-    gp.capw = GEMM_CAPW;
-    gp.ablate = 0;
-#ifdef ISE_ABLATE
-    if (const char* e = getenv("ISE_GEMM_ABLATE")) gp.ablate = atoi(e);
-#endif
-    const int slabs_all = (int)((h->n + ROWS - 1) / ROWS);
-    const size_t lds = (size_t)2 * GB_GQ * S * 4 + (size_t)2 * GEMM_NQ_MAX * 4;
-    const int ns = h->dp / 32;
-
-    gp.slabs = std::min(slabs_all, GEMM_SAMPLE_SLABS * 128 / ROWS);  // the same 16384 sample rows
-    gp.slab_stride = slabs_all / gp.slabs;
-    const int nstages = nq_pad / GB_GQ;
-    gp.qparts = std::max(1, std::min(nstages, (2 * h->num_cu) / gp.slabs));
-    gp.dump = dump;
-    if ((rc = launch_gemm_bf16<true>(ns, gp.slabs * gp.qparts, lds, st, gp))) return rc;
-    hipLaunchKernelGGL(kth_select_kernel, dim3((unsigned)nq_pad), dim3(256), 0, st, (const float*)dump, gp.slabs * ROWS, k,
-                       (int)nq, tau);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(ccnt, 0, (size_t)(GEMM_NQ_MAX * GEMM_SUBS + 64) * 4, st));  // counters, overflow flag, rerun flag
-
-    gp.slabs = slabs_all; gp.slab_stride = 1; gp.qparts = 1; gp.dump = nullptr;
-    const int grid = std::min(slabs_all, h->num_cu);
-    if ((rc = launch_gemm_bf16<false>(ns, grid, lds, st, gp))) return rc;
-    unsigned int* overflow = ccnt + GEMM_NQ_MAX * GEMM_SUBS;
-    unsigned int* rerun = overflow + 1;
-    hipLaunchKernelGGL(regroup_kernel, dim3((unsigned)grid * 8), dim3(256), 0, st, (const u32x4*)gp.wbuf,
-                       (const unsigned int*)gp.wcnt, GEMM_CAPW, cand, ccnt, GEMM_CAPQ, overflow);
-    HIP_TRY(hipGetLastError());
-    if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e1, st));
-    hipLaunchKernelGGL(gemm_select_plain_kernel, dim3((unsigned)nq), dim3(256), (size_t)(GEMM_CAPQ + 320) * 8, st, (const u64*)cand,
-                       (const unsigned int*)ccnt, GEMM_CAPQ, (const unsigned int*)overflow, rerun, k, h->metric, D_dev, I_dev,
-                       keys_out);
-    HIP_TRY(hipGetLastError());
-    // incomplete candidates anywhere in the chunk: the streaming passes answer the whole chunk instead
-    ScanPlan pl;
-    rc = make_plan(h, nq, k, &pl, /*allow_short=*/false);  // a gated rerun: the streaming kernels carry the gate
-    if (rc) return rc;
-    rc = scan_path_enqueue(h, w, pl, q_dev, nq, k, id_base, D_dev, I_dev, keys_out, st, nullptr, rerun);
-    if (rc) return rc;
-    if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e2, st));
-    return ISE_OK;
+    GemmFlavour f;
+    f.bf16 = h->storage == ISE_STORE_BF16;
+    f.rerank = uses_shift(h);
+    f.gq = f.bf16 ? GB_GQ : GQ;
+    f.rows = f.bf16 ? 8 * GB_XT * 16 : 128;
+    f.lds = f.bf16 ? (size_t)2 * GB_GQ * S * 4 + (size_t)2 * GEMM_NQ_MAX * 4 : gemm_lds_bytes(S);
+    f.ns = f.bf16 ? h->dp / 32 : h->dp / 16;
+    f.beta = f.rerank ? exact_beta(h) : 0.f;
+    f.mu = f.rerank ? h->mu : nullptr;
+    f.kth = f.rerank ? k + exact_extra(k) : k;
+    return f;
 }
 
-// float32 INNER PRODUCT rows, one chunk of <= GEMM_NQ_MAX queries: the GEMM-shaped pass of ise_gemm_scan.hpp without
-// shift, norms or re-rank (the reference's default index type is "cosine" = IndexFlatIP over normalised rows,
-// backend/utils.py:293,300-303): sample dump -> thresholds (the k-th smallest sampled score) -> GEMM pass ->
-// regroup -> select; then the streaming passes, gated on the rerun flag (set when a candidate buffer overflowed).
-// Same bits as the streaming passes: the kernel sums a dot product in scan_kernel's order.
-static int search_large_chunk_ip(ise_index* h, ise_index::WorkSlot* w, const float* q_dev, long long nq, int k,
-                                 uint32_t id_base, float* D_dev, long long* I_dev, u64* keys_out, hipStream_t st,
-                                 TimedOut* tm) {
+// one chunk of <= GEMM_NQ_MAX queries; the slot w is already this stream's.  Sample dump -> thresholds -> GEMM pass ->
+// regroup -> select, then what the flavour queues behind the select
+static int search_large_chunk(ise_index* h, ise_index::WorkSlot* w, const float* q_dev, long long nq, int k,
+                              uint32_t id_base, float* D_dev, long long* I_dev, u64* keys_out, hipStream_t st,
+                              TimedOut* tm) {
+    const GemmFlavour fl = gemm_flavour(h, k);
     const int S = qs_stride_for(h);
     const GemmLayout gl = gemm_layout(h);
     h->gemm_chunks++;
@@ -1728,57 +1608,119 @@ static int search_large_chunk_ip(ise_index* h, ise_index::WorkSlot* w, const flo
     unsigned int* ccnt = reinterpret_cast<unsigned int*>(w->gemm + gl.ccnt);
     float* dump = reinterpret_cast<float*>(w->gemm + gl.dump);
     u64* cand = reinterpret_cast<u64*>(w->gemm + gl.cand);
-    const int nq_pad = (int)((nq + GQ - 1) / GQ * GQ);
+    const int nq_pad = (int)((nq + fl.gq - 1) / fl.gq * fl.gq);
+    auto launch = [&](bool sample, int grid, const GemmScanParams& gp) {
+        if (fl.bf16) return sample ? launch_gemm_bf16<true>(fl.ns, grid, fl.lds, st, gp) : launch_gemm_bf16<false>(fl.ns, grid, fl.lds, st, gp);
+        return sample ? launch_gemm<true>(fl.ns, grid, fl.lds, st, gp) : launch_gemm<false>(fl.ns, grid, fl.lds, st, gp);
+    };
     int rc;
 
     if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e0, st));
-    hipLaunchKernelGGL(qprep_kernel, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, q_dev, (int)nq, nq_pad, h->d, S,
-                       (const float*)nullptr, qprep, xn);
+    if (fl.bf16)
+        hipLaunchKernelGGL(qprep_bf16_kernel, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, q_dev, (int)nq, nq_pad, h->d, S,
+                           reinterpret_cast<uint32_t*>(qprep), xn);
+    else
+        hipLaunchKernelGGL(qprep_kernel, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, q_dev, (int)nq, nq_pad, h->d, S,
+                           fl.mu, qprep, xn);
     HIP_TRY(hipGetLastError());
 
     GemmScanParams gp;
-    gp.xb = (const float*)h->xb; gp.norms = h->norms; gp.mu = nullptr; gp.n = h->n; gp.rows16 = (h->n + 15) / 16 * 16;
+    gp.xb = (const float*)h->xb; gp.norms = h->norms; gp.mu = fl.mu; gp.n = h->n; gp.rows16 = (h->n + 15) / 16 * 16;
     gp.dp = h->dp; gp.S = S; gp.qprep = qprep; gp.xn = xn; gp.tau = tau; gp.nq = (int)nq; gp.nq_pad = nq_pad;
-    gp.beta = 0.f; gp.id_base = id_base; gp.metric = ISE_METRIC_INNER_PRODUCT;
+    gp.beta = fl.beta; gp.id_base = id_base; gp.metric = h->metric;
     gp.wbuf = reinterpret_cast<u32x4*>(w->gemm + gl.wbuf); gp.wcnt = reinterpret_cast<unsigned int*>(w->gemm + gl.wcnt);
     gp.capw = GEMM_CAPW;
     gp.ablate = 0;
-    const int slabs_all = (int)((h->n + 127) / 128);
-    const size_t lds = gemm_lds_bytes(S);
-    const int ns = h->dp / 16;
+#ifdef ISE_ABLATE
+    if (fl.bf16)
+        if (const char* e = getenv("ISE_GEMM_ABLATE")) gp.ablate = atoi(e);
+#endif
+    const int slabs_all = (int)((h->n + fl.rows - 1) / fl.rows);
 
-    gp.slabs = std::min(slabs_all, GEMM_SAMPLE_SLABS);
+    // ---- thresholds: the slabs of GEMM_SAMPLE_SLABS * 128 = 16384 rows spread over the index, every score dumped,
+    // the kth selected per query.  One slab per block, the query stages split over qparts blocks per slab, so that
+    // the sample keeps every CU busy for a fraction of a slab's time.
+    gp.slabs = std::min(slabs_all, GEMM_SAMPLE_SLABS * 128 / fl.rows);
     gp.slab_stride = slabs_all / gp.slabs;
-    const int nstages = nq_pad / GQ;
+    const int nstages = nq_pad / fl.gq;
     gp.qparts = std::max(1, std::min(nstages, (2 * h->num_cu) / gp.slabs));
     gp.dump = dump;
-    if ((rc = launch_gemm<true>(ns, gp.slabs * gp.qparts, lds, st, gp))) return rc;
-    hipLaunchKernelGGL(kth_select_kernel, dim3((unsigned)nq_pad), dim3(256), 0, st, (const float*)dump, gp.slabs * 128, k,
-                       (int)nq, tau);
+    if ((rc = launch(true, gp.slabs * gp.qparts, gp))) return rc;
+    hipLaunchKernelGGL(kth_select_kernel, dim3((unsigned)nq_pad), dim3(256), 0, st, (const float*)dump, gp.slabs * fl.rows,
+                       fl.kth, (int)nq, tau);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(ccnt, 0, (size_t)(GEMM_NQ_MAX * GEMM_SUBS + 64) * 4, st));  // counters, overflow flag, rerun flag
 
+    // ---- the GEMM-shaped pass over the whole index
     gp.slabs = slabs_all; gp.slab_stride = 1; gp.qparts = 1; gp.dump = nullptr;
     const int grid = std::min(slabs_all, h->num_cu);
-    if ((rc = launch_gemm<false>(ns, grid, lds, st, gp))) return rc;
+    if ((rc = launch(false, grid, gp))) return rc;
     unsigned int* overflow = ccnt + GEMM_NQ_MAX * GEMM_SUBS;
     unsigned int* rerun = overflow + 1;
     hipLaunchKernelGGL(regroup_kernel, dim3((unsigned)grid * 8), dim3(256), 0, st, (const u32x4*)gp.wbuf,
                        (const unsigned int*)gp.wcnt, GEMM_CAPW, cand, ccnt, GEMM_CAPQ, overflow);
     HIP_TRY(hipGetLastError());
     if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e1, st));
-    hipLaunchKernelGGL(gemm_select_plain_kernel, dim3((unsigned)nq), dim3(256), (size_t)(GEMM_CAPQ + 320) * 8, st, (const u64*)cand,
-                       (const unsigned int*)ccnt, GEMM_CAPQ, (const unsigned int*)overflow, rerun, k, h->metric, D_dev, I_dev,
-                       keys_out);
-    HIP_TRY(hipGetLastError());
+
     ScanPlan pl;
-    rc = make_plan(h, nq, k, &pl, /*allow_short=*/false);  // a gated rerun: the streaming kernels carry the gate
-    if (rc) return rc;
-    rc = scan_path_enqueue(h, w, pl, q_dev, nq, k, id_base, D_dev, I_dev, keys_out, st, nullptr, rerun);
-    if (rc) return rc;
+    if (fl.rerank) {
+        // ---- select the kc best candidates, re-rank exactly, certify; the exact scan takes what fails
+        rc = make_plan(h, nq, k, &pl);  // shapes the exact fallback scan (blocks, rows per block) and sized the slot's lists
+        if (rc) return rc;
+        ExactParams xp;
+        xp.xb = (const float*)h->xb; xp.q = q_dev; xp.n = h->n; xp.d = h->d; xp.dp = h->dp; xp.nq = (int)nq;
+        xp.k = k; xp.kc = fl.kth; xp.id_base = id_base; xp.D = D_dev; xp.I = I_dev; xp.keys_out = keys_out;
+        xp.fl_state = w->fl_state; xp.fl_list = w->fl_list; xp.seq = 0; xp.stats = h->stats_dev;
+        xp.force_fail = force_exact() ? 1 : 0;
+        xp.tau_bound = tau;
+        if ((rc = next_fl_seq(w, st, &xp.seq))) return rc;
+        hipLaunchKernelGGL(gemm_select_kernel, dim3((unsigned)nq), dim3(256),
+                           rerank_lds_bytes(h->dp, fl.kth) + (size_t)(GEMM_CAPQ + 256) * 8, st, xp, (const u64*)cand,
+                           (const unsigned int*)ccnt, GEMM_CAPQ, (const unsigned int*)overflow);
+        HIP_TRY(hipGetLastError());
+        if ((rc = enqueue_exact_fallback(h, w, pl, xp, nq, st))) return rc;
+    } else {
+        hipLaunchKernelGGL(gemm_select_plain_kernel, dim3((unsigned)nq), dim3(256), (size_t)(GEMM_CAPQ + 320) * 8, st, (const u64*)cand,
+                           (const unsigned int*)ccnt, GEMM_CAPQ, (const unsigned int*)overflow, rerun, k, h->metric, D_dev, I_dev,
+                           keys_out);
+        HIP_TRY(hipGetLastError());
+        // incomplete candidates anywhere in the chunk: the streaming passes answer the whole chunk instead
+        rc = make_plan(h, nq, k, &pl, /*allow_short=*/false);  // a gated rerun: the streaming kernels carry the gate
+        if (rc) return rc;
+        rc = scan_path_enqueue(h, w, pl, q_dev, nq, k, id_base, D_dev, I_dev, keys_out, st, nullptr, rerun);
+        if (rc) return rc;
+    }
     if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e2, st));
     return ISE_OK;
 }
+
+// Slot hand-out of the WorkSlots and the SelSlots (mu_ held): a stream keeps the slot it used last (stream order is
+// all the ordering that needs); a stream without one takes a fresh slot, or the least recently taken one behind an
+// event wait.  *waited (optional): the slot's last user was another stream.
+template <class Slot, int N>
+static int take_slot(Slot (&slots)[N], unsigned* next, hipStream_t st, Slot** out, bool* waited) {
+    Slot* w = nullptr;
+    bool same_stream = false;
+    for (auto& s : slots)
+        if (s.used && s.last_stream == st) { w = &s; same_stream = true; break; }
+    if (!w)
+        for (auto& s : slots)
+            if (!s.used) { w = &s; break; }
+    if (!w) w = &slots[(*next)++ % N];
+    const bool other = w->used && !same_stream;
+    if (other) HIP_TRY(hipStreamWaitEvent(st, w->done, 0));
+    if (waited) *waited = other;
+    *out = w;
+    return ISE_OK;
+}
+template <class Slot>
+struct SlotRelease {  // whatever path returns, a later user on another stream waits for this call
+    Slot* w;
+    hipStream_t st;
+    ~SlotRelease() {
+        if (hipEventRecord(w->done, st) == hipSuccess) { w->used = true; w->last_stream = st; }
+    }
+};
 
 // enqueue one search batch; outputs (D, I) and/or keys.  Nothing here blocks once the slots are
 // sized (first batch of a shape) and the shift is current (first batch after rows were added).
@@ -1801,30 +1743,15 @@ static int search_enqueue(ise_index* h, const float* q_dev, long long nq, int k,
     rc = ensure_workspaces(h, pl, pl.gemm ? std::min<long long>(nq, GEMM_NQ_MAX) : nq);
     if (rc) return rc;
     ise_index::WorkSlot* w = nullptr;
-    bool same_stream = false;
-    for (auto& s : h->ws)
-        if (s.used && s.last_stream == st) { w = &s; same_stream = true; break; }
-    if (!w)
-        for (auto& s : h->ws)
-            if (!s.used) { w = &s; break; }
-    if (!w) w = &h->ws[h->ws_next++ % ise_index::NWS];
-    if (w->used && !same_stream) HIP_TRY(hipStreamWaitEvent(st, w->done, 0));
-    struct Release {  // whatever path returns, a later user on another stream waits for this call
-        ise_index::WorkSlot* w;
-        hipStream_t st;
-        ~Release() {
-            if (hipEventRecord(w->done, st) == hipSuccess) { w->used = true; w->last_stream = st; }
-        }
-    } release{w, st};
+    if ((rc = take_slot(h->ws, &h->ws_next, st, &w, nullptr))) return rc;
+    SlotRelease<ise_index::WorkSlot> release{w, st};
 
     if (pl.gemm) {  // float32 L2 or bf16 rows, nq >= 256: GEMM-shaped pass, GEMM_NQ_MAX queries at a time
         for (long long q0 = 0; q0 < nq; q0 += GEMM_NQ_MAX) {
             const long long m = std::min<long long>(GEMM_NQ_MAX, nq - q0);
-            rc = (h->storage == ISE_STORE_BF16 ? search_large_chunk_bf16
-                  : uses_shift(h)               ? search_large_chunk
-                                                : search_large_chunk_ip)(
-                h, w, q_dev + (size_t)q0 * h->d, m, k, id_base, D_dev ? D_dev + (size_t)q0 * k : nullptr,
-                I_dev ? I_dev + (size_t)q0 * k : nullptr, keys_out ? keys_out + (size_t)q0 * k : nullptr, st, tm);
+            rc = search_large_chunk(h, w, q_dev + (size_t)q0 * h->d, m, k, id_base, D_dev ? D_dev + (size_t)q0 * k : nullptr,
+                                    I_dev ? I_dev + (size_t)q0 * k : nullptr, keys_out ? keys_out + (size_t)q0 * k : nullptr,
+                                    st, tm);
             if (rc) return rc;
         }
         return ISE_OK;
@@ -1920,14 +1847,15 @@ static void release_ctx(ise_index* h, ise_index::HostCtx* c) {
     h->hc_cv.notify_one();
 }
 
-// one caller, one scan: queries straight from the caller's memory, results straight into it
-static int search_host_direct(ise_index* h, const float* q, long long nq, int k, float* D, long long* I) {
+// The staging loop of the plain and the filtered host search, on one of the host contexts: `batch` queries at a time
+// (bounds the workspace; larger calls loop) are copied in, enqueued by enqueue(c, m) under mu_, copied out, waited for
+template <class Enqueue>
+static int search_host_staged(ise_index* h, const float* q, long long nq, int k, long long batch, float* D, long long* I,
+                              Enqueue enqueue) {
     DeviceGuard gd(h->device);
     ise_index::HostCtx* c = acquire_ctx(h);
     struct Rel { ise_index* h; ise_index::HostCtx* c; ~Rel() { release_ctx(h, c); } } rel{h, c};
     if (!c->stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    // bounds the workspace (part + multi-pass keys); larger calls loop
-    const long long batch = k + 6 <= XPASS_MAX ? 4096 : 1024;
     const size_t qe = (size_t)std::min<long long>(nq, batch) * h->d;
     const size_t oe = (size_t)std::min<long long>(nq, batch) * k;
     if (qe > c->q_elems) {
@@ -1951,7 +1879,7 @@ static int search_host_direct(ise_index* h, const float* q, long long nq, int k,
         int rc;
         {
             std::lock_guard<std::mutex> lk(h->mu_);
-            rc = search_enqueue(h, c->q_dev, m, k, 0u, c->D_dev, c->I_dev, nullptr, c->stream, nullptr);
+            rc = enqueue(c, m);
         }
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(D + (size_t)i0 * k, c->D_dev, (size_t)m * k * sizeof(float), hipMemcpyDeviceToHost,
@@ -1961,6 +1889,13 @@ static int search_host_direct(ise_index* h, const float* q, long long nq, int k,
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return ISE_OK;
+}
+
+// one caller, one scan: queries straight from the caller's memory, results straight into it
+static int search_host_direct(ise_index* h, const float* q, long long nq, int k, float* D, long long* I) {
+    return search_host_staged(h, q, nq, k, k + 6 <= XPASS_MAX ? 4096 : 1024, D, I, [&](ise_index::HostCtx* c, long long m) {
+        return search_enqueue(h, c->q_dev, m, k, 0u, c->D_dev, c->I_dev, nullptr, c->stream, nullptr);
+    });
 }
 
 // Largest number of queries a combined batch holds (0 = every caller runs its own scan).  A scan
@@ -2099,8 +2034,9 @@ struct ise_range_result {
 #define RANGE_STAGE_MAX (1ll << 23) /* most staged entries per batch (64 MiB): a smaller capacity beyond that */
 
 // grow a device (or, pinned, page-locked host) buffer to at least `need` elements; contents are not kept
+// rule: no wait before a free -- range search owns its workspace (rg_mu) and drains it per batch, a SelSlot's other user was waited for
 template <class T>
-static int range_grow(ise_index::Buf<T>& b, size_t need, bool pinned = false) {
+static int range_grow(DevBuf<T>& b, size_t need, bool pinned = false) {
     if (b.p && need <= b.n) return ISE_OK;
     if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
     b.p = nullptr;
@@ -2143,14 +2079,7 @@ static void range_params_index(const ise_index* h, RangeParams* rp) {
 }
 
 // ---- selectors (ise_sel_scan.hpp): a device bitmap over the rows of ONE index at ONE (ntotal, row epoch)
-struct ise_selector {
-    ise_index* owner = nullptr;
-    uint32_t* bits = nullptr;  // ceil(ntotal / 32) words + zero padding (pad rows of the last tile and word: zero bits)
-    long long nwords = 0;      // allocated words
-    long long ntotal = 0;
-    unsigned long long epoch = 0;
-    long long count = 0, r0 = 0, r1 = 0, tiles = 0;  // selected rows, window [r0, r1), non-empty 16-row tiles
-};
+struct ise_selector : SelectorBase {};  // bits: ceil(ntotal / 32) words + zero padding (pad rows of the last tile and word: zero bits)
 
 // mu_ held.  A selector is good for the handle it was made from while ntotal and the row epoch stand
 static int selector_check_locked(const ise_index* h, const ise_selector* sel) {
@@ -2384,47 +2313,14 @@ extern "C" int ise_range_result_destroy(ise_range_result_t* r) {
 // ---- selector objects and the selector-filtered search (ise_sel_scan.hpp)
 #define SEL_NQ_CHUNK 64 /* queries per masked launch (4 groups of 16): bounds the per-block lists of a slot */
 
-// the bitmap of a new selector for h as it stands (mu_ held): ceil(n / 32) words and a word of padding, so that the
-// half-word of every tile below the capacity's last one is there to read, zero
-static int selector_alloc_locked(ise_index* h, ise_selector** out) {
-    ise_selector* s = new (std::nothrow) ise_selector;
-    if (!s) return fail(ISE_E_NOMEM, "selector: host allocation failed");
-    s->owner = h;
-    s->ntotal = h->n;
-    s->epoch = h->row_epoch;
-    s->nwords = (h->n + 31) / 32 + 1;
-    const hipError_t e = hipMalloc((void**)&s->bits, (size_t)s->nwords * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        delete s;
-        return fail(e == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP, std::string("selector bitmap: ") + hipGetErrorString(e));
-    }
-    *out = s;
-    return ISE_OK;
+// a new selector for h as it stands (mu_ held): ceil(n / 32) words and a word of padding, so that the half-word of
+// every tile below the capacity's last one is there to read, zero
+static SelectorFor selector_for(const ise_index* h) {
+    return SelectorFor{h, h->device, h->n, h->row_epoch, h->stream, (h->n + 31) / 32 + 1};
 }
-
-static void selector_free(ise_selector* s) {
-    if (s->bits) (void)hipFree(s->bits);
-    delete s;
-}
-
-// clears bits at or beyond ntotal, then count / window / non-empty tiles on the device (mu_ held; blocks)
-static int selector_census_locked(ise_index* h, ise_selector* s, hipStream_t st) {
-    unsigned long long* dev = nullptr;
-    HIP_TRY(hipMalloc((void**)&dev, 4 * sizeof(unsigned long long)));
-    struct Free { void* p; ~Free() { (void)hipFree(p); } } fr{dev};
-    const unsigned long long init[4] = {0ull, 0ull, ~0ull, 0ull};
-    unsigned long long got[4];
-    HIP_TRY(hipMemcpyAsync(dev, init, sizeof(init), hipMemcpyHostToDevice, st));
+static void selector_census_launch(SelectorBase* s, hipStream_t st, unsigned long long* out4) {
     hipLaunchKernelGGL(sel_census_kernel, dim3((unsigned)((s->nwords + 255) / 256)), dim3(256), 0, st, s->bits, s->nwords,
-                       s->ntotal, dev);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(got, dev, sizeof(got), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    s->count = (long long)got[0];
-    s->tiles = (long long)got[1];
-    s->r0 = got[0] ? (long long)got[2] : 0;
-    s->r1 = got[0] ? (long long)got[3] : 0;
-    return ISE_OK;
+                       s->ntotal, out4);
 }
 
 extern "C" int ise_selector_create_range(ise_index_t* h, int64_t i0, int64_t i1, ise_selector_t** out) {
@@ -2433,16 +2329,9 @@ extern "C" int ise_selector_create_range(ise_index_t* h, int64_t i0, int64_t i1,
     if (!h) return fail(ISE_E_INVALID, "handle is NULL");
     std::lock_guard<std::mutex> lk(h->mu_);
     DeviceGuard gd(h->device);
-    ise_selector* s = nullptr;
-    int rc = selector_alloc_locked(h, &s);
-    if (rc) return rc;
     const long long a = std::max<long long>(i0, 0), b = std::min<long long>(i1, h->n);
-    hipLaunchKernelGGL(sel_fill_range_kernel, dim3((unsigned)((s->nwords + 255) / 256)), dim3(256), 0, h->stream, s->bits,
-                       s->nwords, a, std::max(a, b));
-    rc = selector_census_locked(h, s, h->stream);
-    if (rc) { selector_free(s); return rc; }
-    *out = s;
-    return ISE_OK;
+    return selector_create(selector_for(h), [&](SelectorBase* s) { return selector_fill_range(s, h->stream, a, b); },
+                           selector_census_launch, out);
 }
 
 extern "C" int ise_selector_create_ids(ise_index_t* h, const int64_t* ids, int64_t n_ids, int invert, ise_selector_t** out) {
@@ -2452,28 +2341,10 @@ extern "C" int ise_selector_create_ids(ise_index_t* h, const int64_t* ids, int64
     if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(ISE_E_INVALID, "ids is NULL");
     std::lock_guard<std::mutex> lk(h->mu_);
     DeviceGuard gd(h->device);
-    ise_selector* s = nullptr;
-    int rc = selector_alloc_locked(h, &s);
-    if (rc) return rc;
-    long long* ids_dev = nullptr;
-    struct Free { long long** p; ~Free() { if (*p) (void)hipFree(*p); } } fr{&ids_dev};
-    auto body = [&]() -> int {
-        // the fill runs on the device: nothing (invert: every row), then the ids are scattered in -- only they travel
-        hipLaunchKernelGGL(sel_fill_range_kernel, dim3((unsigned)((s->nwords + 255) / 256)), dim3(256), 0, h->stream,
-                           s->bits, s->nwords, 0ll, invert ? h->n : 0ll);
-        if (n_ids > 0) {
-            HIP_TRY(hipMalloc((void**)&ids_dev, (size_t)n_ids * sizeof(long long)));
-            HIP_TRY(hipMemcpyAsync(ids_dev, ids, (size_t)n_ids * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-            hipLaunchKernelGGL(sel_scatter_ids_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, h->stream,
-                               s->bits, (const long long*)ids_dev, (long long)n_ids, h->n, invert ? 0 : 1);
-        }
-        HIP_TRY(hipGetLastError());
-        return selector_census_locked(h, s, h->stream);
-    };
-    rc = body();
-    if (rc) { selector_free(s); return rc; }
-    *out = s;
-    return ISE_OK;
+    DevFree ids_dev;
+    return selector_create(selector_for(h),
+                           [&](SelectorBase* s) { return selector_scatter_ids(s, h->stream, ids, n_ids, invert, &ids_dev); },
+                           selector_census_launch, out);
 }
 
 extern "C" int ise_selector_create_bitmap(ise_index_t* h, const uint32_t* words, int64_t n_words, ise_selector_t** out) {
@@ -2485,35 +2356,14 @@ extern "C" int ise_selector_create_bitmap(ise_index_t* h, const uint32_t* words,
     if (n_words != (h->n + 31) / 32)
         return fail(ISE_E_INVALID, "the bitmap must have ceil(ntotal / 32) = " + std::to_string((h->n + 31) / 32) + " words");
     DeviceGuard gd(h->device);
-    ise_selector* s = nullptr;
-    int rc = selector_alloc_locked(h, &s);
-    if (rc) return rc;
-    auto body = [&]() -> int {
-        HIP_TRY(hipMemsetAsync(s->bits + n_words, 0, (size_t)(s->nwords - n_words) * sizeof(uint32_t), h->stream));
-        if (n_words > 0)
-            HIP_TRY(hipMemcpyAsync(s->bits, words, (size_t)n_words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        return selector_census_locked(h, s, h->stream);  // clears the bits at or beyond ntotal
-    };
-    rc = body();
-    if (rc) { selector_free(s); return rc; }
-    *out = s;
-    return ISE_OK;
+    return selector_create(selector_for(h), [&](SelectorBase* s) { return selector_copy_bitmap(s, h->stream, words, n_words); },
+                           selector_census_launch, out);  // the census clears the bits at or beyond ntotal
 }
 
-extern "C" int ise_selector_info(const ise_selector_t* sel, int64_t* out5) {
-    if (!sel || !out5) return fail(ISE_E_INVALID, "NULL argument");
-    out5[0] = sel->ntotal;
-    out5[1] = sel->count;
-    out5[2] = sel->r0;
-    out5[3] = sel->r1;
-    out5[4] = sel->tiles;
-    return ISE_OK;
-}
+extern "C" int ise_selector_info(const ise_selector_t* sel, int64_t* out5) { return selector_info(sel, out5); }
 
 extern "C" int ise_selector_destroy(ise_selector_t* sel) {
-    if (!sel) return ISE_OK;
-    // hipFree waits for the device: a masked pass still in flight has finished reading the bitmap
-    selector_free(sel);
+    if (sel) selector_free(sel);  // waits for the device: a masked pass still in flight has finished reading the bitmap
     return ISE_OK;
 }
 
@@ -2602,26 +2452,12 @@ static int search_sel_enqueue(ise_index* h, const ise_selector* sel, const float
     rc = prepare_shift_locked(h, st);
     if (rc) return rc;
     ise_index::SelSlot* sl = nullptr;
-    bool same_stream = false;
-    for (auto& s : h->ss)
-        if (s.used && s.last_stream == st) { sl = &s; same_stream = true; break; }
-    if (!sl)
-        for (auto& s : h->ss)
-            if (!s.used) { sl = &s; break; }
-    if (!sl) sl = &h->ss[h->ss_next++ % ise_index::NSS];
-    if (!sl->done) HIP_TRY(hipEventCreateWithFlags(&sl->done, hipEventDisableTiming));
-    if (sl->used && !same_stream) {
-        HIP_TRY(hipStreamWaitEvent(st, sl->done, 0));
-        // its buffers may grow (free + allocate) below: the other stream's passes have to be through with them
-        HIP_TRY(hipEventSynchronize(sl->done));
-    }
-    struct Release {  // whatever path returns, a later user on another stream waits for this call
-        ise_index::SelSlot* sl;
-        hipStream_t st;
-        ~Release() {
-            if (hipEventRecord(sl->done, st) == hipSuccess) { sl->used = true; sl->last_stream = st; }
-        }
-    } release{sl, st};
+    bool waited = false;
+    if ((rc = take_slot(h->ss, &h->ss_next, st, &sl, &waited))) return rc;
+    if (!sl->done) HIP_TRY(hipEventCreateWithFlags(&sl->done, hipEventDisableTiming));  // a slot never used: nothing was waited for
+    // its buffers may grow (free + allocate) below: the other stream's passes have to be through with them
+    if (waited) HIP_TRY(hipEventSynchronize(sl->done));
+    SlotRelease<ise_index::SelSlot> release{sl, st};
     for (long long i0 = 0; i0 < nq; i0 += SEL_NQ_CHUNK) {
         const long long m = std::min<long long>(SEL_NQ_CHUNK, nq - i0);
         rc = sel_chunk_enqueue(h, sl, sel, q_dev + (size_t)i0 * h->d, m, k, D_dev + (size_t)i0 * k, I_dev + (size_t)i0 * k, st);
@@ -2653,42 +2489,9 @@ extern "C" int ise_index_search_sel_host(ise_index_t* h, const float* q, int64_t
         std::lock_guard<std::mutex> lk(h->mu_);
         return selector_check_locked(h, sel);
     }
-    DeviceGuard gd(h->device);
-    ise_index::HostCtx* c = acquire_ctx(h);
-    struct Rel { ise_index* h; ise_index::HostCtx* c; ~Rel() { release_ctx(h, c); } } rel{h, c};
-    if (!c->stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    const long long batch = 1024;
-    const size_t qe = (size_t)std::min<long long>(nq, batch) * h->d;
-    const size_t oe = (size_t)std::min<long long>(nq, batch) * k;
-    if (qe > c->q_elems) {
-        if (c->q_dev) (void)hipFree(c->q_dev);
-        c->q_dev = nullptr; c->q_elems = 0;
-        HIP_TRY(hipMalloc(&c->q_dev, qe * sizeof(float)));
-        c->q_elems = qe;
-    }
-    if (oe > c->out_elems) {
-        if (c->D_dev) (void)hipFree(c->D_dev);
-        if (c->I_dev) (void)hipFree(c->I_dev);
-        c->D_dev = nullptr; c->I_dev = nullptr; c->out_elems = 0;
-        HIP_TRY(hipMalloc(&c->D_dev, oe * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->I_dev, oe * sizeof(long long)));
-        c->out_elems = oe;
-    }
-    for (long long i0 = 0; i0 < nq; i0 += batch) {
-        const long long m = std::min<long long>(batch, nq - i0);
-        HIP_TRY(hipMemcpyAsync(c->q_dev, q + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice,
-                               c->stream));
-        {
-            std::lock_guard<std::mutex> lk(h->mu_);
-            rc = search_sel_enqueue(h, sel, c->q_dev, m, k, c->D_dev, c->I_dev, c->stream);
-        }
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(D + (size_t)i0 * k, c->D_dev, (size_t)m * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(I + (size_t)i0 * k, c->I_dev, (size_t)m * k * sizeof(long long), hipMemcpyDeviceToHost,
-                               c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return ISE_OK;
+    return search_host_staged(h, q, nq, k, 1024, D, (long long*)I, [&](ise_index::HostCtx* c, long long m) {
+        return search_sel_enqueue(h, sel, c->q_dev, m, k, c->D_dev, c->I_dev, c->stream);
+    });
 }
 
 extern "C" int ise_index_sel_stats(ise_index_t* h, uint64_t* out3) {
@@ -2704,10 +2507,6 @@ extern "C" int ise_index_sel_stats(ise_index_t* h, uint64_t* out3) {
 }
 
 // ---- remove_ids: stable in-place compaction (ise_remove.hpp)
-struct RemoveRun {
-    long long start, len;
-};
-
 // everything a removal allocates for the duration of the call
 struct RemoveScratch {
     uint32_t* g = nullptr;        // [T] destination row at which run t bites
@@ -2752,19 +2551,11 @@ static int remove_runs_locked(ise_index* h, const std::vector<RemoveRun>& runs, 
     RemoveScratch sc;
     if (moved > 0) {
         const long long T = (long long)runs.size();
-        std::vector<uint32_t> g((size_t)T), cend((size_t)T);
-        long long c = 0;
-        for (long long t = 0; t < T; t++) {
-            g[(size_t)t] = (uint32_t)(runs[(size_t)t].start - c);
-            c += runs[(size_t)t].len;
-            cend[(size_t)t] = (uint32_t)c;
-        }
+        std::vector<uint32_t> g, cend;
+        remove_plan_tables(runs, &g, &cend);
         // slab: at most 256 MiB of the widest array (xb), as the upload slab of ise_index_add_host; a slab's 16-byte
         // units stay below 2^31 whatever $ISE_REMOVE_SLAB_ROWS says
-        long long slab = knobs().remove_slab_rows.load(std::memory_order_relaxed);
-        if (slab <= 0) slab = std::max<long long>(1, (256ll << 20) / (long long)rb);
-        slab = std::min(slab, std::max<long long>(1, (1ll << 31) / (long long)(rb / 16)));
-        slab = std::min(slab, moved);
+        const long long slab = remove_plan_slab_rows(ise_remove_slab_rows_(), (long long)rb, (long long)(rb / 16), moved);
         HIP_TRY(hipMalloc(&sc.g, (size_t)T * sizeof(uint32_t)));
         HIP_TRY(hipMalloc(&sc.cend, (size_t)T * sizeof(uint32_t)));
         HIP_TRY(hipMalloc(&sc.src_idx, (size_t)slab * sizeof(uint32_t)));
@@ -2865,11 +2656,7 @@ extern "C" int ise_index_remove_ids_host(ise_index_t* h, const int64_t* ids, int
     std::vector<long long> v;
     std::vector<RemoveRun> runs;
     try {
-        v.reserve((size_t)n_ids);
-        for (int64_t i = 0; i < n_ids; i++)
-            if (ids[i] >= 0) v.push_back(ids[i]);
-        std::sort(v.begin(), v.end());
-        v.erase(std::unique(v.begin(), v.end()), v.end());
+        v = remove_plan_ids(ids, n_ids);
     } catch (const std::bad_alloc&) {
         return fail(ISE_E_NOMEM, "remove_ids: host allocation failed");
     }
@@ -2877,12 +2664,7 @@ extern "C" int ise_index_remove_ids_host(ise_index_t* h, const int64_t* ids, int
     std::lock_guard<std::mutex> lk(h->mu_);
     long long removed = 0;
     try {
-        for (long long id : v) {
-            if (id >= h->n) break;  // sorted: the rest does not exist either
-            if (!runs.empty() && runs.back().start + runs.back().len == id) runs.back().len++;
-            else runs.push_back(RemoveRun{id, 1});
-            removed++;
-        }
+        removed = remove_plan_runs(v, h->n, &runs);
     } catch (const std::bad_alloc&) {
         return fail(ISE_E_NOMEM, "remove_ids: host allocation failed");
     }

@@ -1,5 +1,6 @@
-"""A numpy restatement of the removal source map and slab schedule of csrc/ise_remove.hpp (test infrastructure, not
-a kernel path).
+"""A numpy restatement of the removal planning of csrc/ise_remove_plan.hpp (ids -> runs -> the g / cend tables) and of
+the source map and slab schedule the kernels of csrc/ise_remove.hpp run from them (test infrastructure, not a kernel
+path).  tests/native/remove_plan_check.cpp checks the same header natively.
 
 ``runs``: the removed rows as sorted, disjoint (start, len) pairs inside [0, n).  ``source_map(n, runs)`` -> src, the
 row that ends up at every destination row [0, n_new).  ``slab_schedule(n, runs, slab)`` -> the launches of the

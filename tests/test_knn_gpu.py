@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import knn_oracle as ko
-from tests.knn_checks import assert_knn_matches, load_fixture
+from tests.knn_checks import assert_exact_range, assert_knn_identical, assert_knn_matches, int_data, load_fixture
 
 pytestmark = pytest.mark.gpu
 
@@ -423,6 +423,19 @@ def test_shape_sweep_against_oracle(faiss):
             assert_knn_matches(D, I, D_ref, I_ref, xb, xq, metric, gap=ko.kth_gap(xb, xq, k, metric))
         except AssertionError as e:
             raise AssertionError(f"n={n} d={d} nq={nq} k={k} metric={metric}: {e}")
+
+
+def test_host_search_of_more_than_one_staging_batch(faiss):
+    """A host search stages 4096 queries at a time (k <= 26) through its context's device buffers: 4100 queries are two
+    batches, and the second one's queries and results sit at an offset in the caller's arrays.  Integer data, so the
+    oracle's answer is the only correct one, bit for bit."""
+    rng = np.random.default_rng(4100)
+    xb, xq = int_data("small", rng, 2000, 32), int_data("small", rng, 4100, 32)
+    assert_exact_range(xb, xq)
+    index = faiss.IndexFlatL2(32)
+    index.add(xb)
+    D, I = index.search(xq, 5)
+    assert_knn_identical(D, I, *ko.knn_exact(xb, xq, 5, L2), "nq=4100")
 
 
 @pytest.mark.parametrize("nq,k", [(40, 100), (20, 33), (50, 70)])

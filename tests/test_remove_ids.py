@@ -1,5 +1,6 @@
-"""CPU tests of remove_ids: the numpy restatement of the source map and slab schedule (tests/remove_ref.py), the id
-selectors against brute-force sets, the IndexIDMap file layout and engine.remove_images over a fake index."""
+"""CPU tests of remove_ids: the numpy restatement of the source map and slab schedule (tests/remove_ref.py), the host
+planning itself (csrc/ise_remove_plan.hpp) in a stand-alone sanitized program, the id selectors against brute-force
+sets, the IndexIDMap file layout and engine.remove_images over a fake index."""
 import json
 
 import numpy as np
@@ -66,6 +67,27 @@ def test_slab_schedule_never_reads_an_overwritten_row(slab):
         assert n_new == len(keep) and np.array_equal(got[:n_new], keep) and not got[n_new:].any()
         first = runs[0][0] if runs else n
         assert int(written.sum()) == n_new - min(first, n_new)  # rows moved
+
+
+def test_remove_planning_standalone(tmp_path):
+    """csrc/ise_remove_plan.hpp (ids -> runs -> g / cend tables, the slab rule: what tests/remove_ref.py restates) in a
+    stand-alone host program with its own main, against a brute-force erase, under the address and undefined-behaviour
+    sanitizers (linked statically: the program then runs whatever else the environment loads first).  A missing
+    compiler or sanitizer runtime fails the test."""
+    import os
+    import shutil
+    import subprocess
+
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build the stand-alone check (it is a tool of the build, not hardware)"
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "remove_plan_check.cpp")
+    exe = str(tmp_path / "remove_plan_check")
+    r = subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-o", exe, src],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, "the sanitized build failed (no unsanitized fallback):\n" + r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
 
 
 # ------------------------------------------------------------------------------------------------ selectors

@@ -1,7 +1,7 @@
-"""GPU tests of remove_ids (csrc/ise_remove.hpp).  The yardstick everywhere: after remove_ids the index must be
-indistinguishable from a FRESH index built with add(x[keep]) from the original float32 rows -- ntotal, reconstruct_n,
-search and range_search bit for bit.  Results do not depend on the shift vector or on the path, so no
-comparison here has a tolerance."""
+"""GPU tests of remove_ids (csrc/ise_remove.hpp; its host planning: csrc/ise_remove_plan.hpp).  The yardstick
+everywhere: after remove_ids the index must be indistinguishable from a FRESH index built with add(x[keep]) from the
+original float32 rows -- ntotal, reconstruct_n, search and range_search bit for bit.  Results do not depend on the shift
+vector or on the path, so no comparison here has a tolerance."""
 import ctypes
 import threading
 

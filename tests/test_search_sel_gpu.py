@@ -8,7 +8,8 @@ import pytest
 
 from image_search_engine_amd import _native
 from image_search_engine_amd import faiss_compat as faiss
-from tests.knn_checks import assert_knn_identical, int_data, plant_ties, poison
+from oracle import knn_oracle as ko
+from tests.knn_checks import assert_exact_range, assert_knn_identical, int_data, plant_ties, poison
 from tests.range_ref import assert_range_identical, assert_range_shape
 from tests.sel_ref import IP, L2, filter_range, filter_ranking, pad_value, selector_census, sub_index_search
 
@@ -302,6 +303,18 @@ def test_device_selector_lifetime():
     assert_knn_identical(*idx.search(xq, 10), *full, "unfiltered search after failed calls")
     with pytest.raises(_native.IseError):
         idx.search(xq, 4000, params=P(sel))  # k out of range
+
+
+def test_host_search_of_more_than_one_staging_batch():
+    """A filtered host search stages 1024 queries at a time through its context's device buffers: 1030 queries are two
+    batches, and the second one's queries and results sit at an offset in the caller's arrays.  Integer data, so the
+    oracle's answer over the selected rows is the only correct one, bit for bit."""
+    rng = np.random.default_rng(1030)
+    xb, xq = int_data("small", rng, 2000, 32), int_data("small", rng, 1030, 32)
+    assert_exact_range(xb, xq)
+    idx = make_index(xb, L2, "f32")
+    D, I = idx.search(xq, 5, params=P(faiss.IDSelectorRange(100, 1500)))
+    assert_knn_identical(D, I, *ko.knn_exact(xb[100:1500], xq, 5, L2, id_offset=100), "nq=1030")
 
 
 def test_threads_mixed_with_unfiltered():
