@@ -75,6 +75,70 @@ def _default_device() -> int:
     return torch.cuda.current_device() if torch.cuda.is_available() else 0
 
 
+# ---------------------------------------------------------------- what the index kinds share
+class _AbiFamily:
+    """An object behind one family of entry points of include/ise_knn.h: ``_ABI`` is the family's prefix, ``_fn(name)``
+    looks ``<prefix>_<name>`` up.  For removal, statistics, selector and range paths; the search paths name their entry
+    point outright (no string lookup per call)."""
+
+    _ABI = ""
+
+    def _fn(self, name: str):
+        return getattr(_n.lib, f"{self._ABI}_{name}")
+
+
+class _IndexHandle(_AbiFamily):
+    """The lifetime of an index's library handle ``_h``."""
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                self._fn("destroy")(h)
+            except Exception:  # interpreter shutdown: module globals may already be gone
+                pass
+            h.value = None
+
+
+def _counters(fn, h, keys: tuple) -> dict:
+    """``len(keys)`` uint64 counters from the statistics entry point ``fn(handle, out)``, by name."""
+    out = (ctypes.c_uint64 * len(keys))()
+    _n.check(fn(h, out))
+    return {key: int(v) for key, v in zip(keys, out)}
+
+
+def _read_range_result(res, d_dtype, get, destroy):
+    """A ``*_range_result`` handle -> (lims uint64 (nq + 1,), D ``d_dtype``, I int64) as fresh arrays; the handle is
+    destroyed, also when reading it fails."""
+    try:
+        n = ctypes.c_int64()
+        lp, dp_, ip = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        _n.check(get(res, ctypes.byref(n), ctypes.byref(lp), ctypes.byref(dp_), ctypes.byref(ip)))
+        lims = np.ctypeslib.as_array(ctypes.cast(lp, ctypes.POINTER(ctypes.c_int64)), (n.value + 1,))
+        lims = lims.astype(np.uint64)
+        total = int(lims[-1])
+        D = np.empty(total, dtype=d_dtype)
+        I = np.empty(total, dtype=np.int64)
+        if total:
+            ctypes.memmove(D.ctypes.data, dp_.value, D.nbytes)
+            ctypes.memmove(I.ctypes.data, ip.value, I.nbytes)
+    finally:
+        destroy(res)
+    return lims, D, I
+
+
+def _torch_io(x, dtype, width: int, k: int, d_dtype):
+    """The check-and-allocate step of the torch paths: ``x`` is a CUDA (n, width) tensor of ``dtype`` -> (x contiguous,
+    D ``d_dtype`` (n, k), I int64 (n, k), the handle of x's device's current stream); D and I are uninitialised."""
+    import torch
+
+    assert x.is_cuda and x.dtype == dtype and x.dim() == 2 and x.shape[1] == width
+    x = x.contiguous()
+    D = torch.empty((x.shape[0], k), dtype=d_dtype, device=x.device)
+    I = torch.empty((x.shape[0], k), dtype=torch.int64, device=x.device)
+    return x, D, I, torch.cuda.current_stream(x.device).cuda_stream
+
+
 # ---------------------------------------------------------------- id selectors (faiss.IDSelector*)
 def _ids_array(ids) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
@@ -208,15 +272,12 @@ def lower_selector(sel: IDSelector, ntotal: int):
     return ("bitmap", _bitmap_words(sel.members(np.arange(int(ntotal), dtype=np.int64))))
 
 
-class DeviceSelector:
+class DeviceSelector(_AbiFamily):
     """A selector on an index's device (``IndexFlat.make_selector``; an extension, Faiss has no counterpart): the
     bitmap, its row window and counts.  Valid while the index keeps its rows: after ``add``, ``remove_ids`` or
     ``reset`` a search with it raises ``IseError``."""
 
-    _ABI = "ise_selector"  # the family of entry points (include/ise_knn.h); "tiles" of ``info`` are 16-row tiles
-
-    def _fn(self, name: str):
-        return getattr(_n.lib, f"{self._ABI}_{name}")
+    _ABI = "ise_selector"  # "tiles" of ``info`` are 16-row tiles
 
     def __init__(self, index, lowered):
         self.index = index
@@ -263,7 +324,69 @@ def _runs_to_ids(runs: np.ndarray) -> np.ndarray:
     return np.concatenate([np.arange(a, a + m, dtype=np.int64) for a, m in runs])
 
 
-class IndexFlat:
+class _RemovableIndex(_IndexHandle):
+    """What ``IndexFlat`` and ``IndexBinaryFlat`` share above their handles: ``reset``, ``remove_ids`` and the selector
+    plumbing of ``params=``.  A subclass names its family of entry points (``_ABI``), the class of its device selectors
+    (``_SELECTOR``) and what it says to a selector of another family (``_FOREIGN_SELECTOR``)."""
+
+    _SELECTOR = DeviceSelector
+    _FOREIGN_SELECTOR = ""
+
+    def reset(self) -> None:
+        _n.check(self._fn("reset")(self._h))
+
+    def remove_ids(self, sel) -> int:
+        """faiss ``index.remove_ids``: remove the rows an ``IDSelector`` names -- or an int64 array-like, taken as an
+        ``IDSelectorBatch`` as the Faiss wrapper does -- and return how many went.  The other rows keep their order
+        and are renumbered densely (``IndexIDMap`` / ``IndexBinaryIDMap`` keep external ids).  In place on the device:
+        the rows and what is kept beside them (a float index's norms and shadows) move, nothing is re-uploaded
+        (include/ise_knn.h, ise_index_remove_ids_host / ise_binary_index_remove_ids_host)."""
+        out = ctypes.c_int64(0)
+        if isinstance(sel, IDSelectorRange):
+            _n.check(self._fn("remove_range")(self._h, sel.imin, sel.imax, ctypes.byref(out)))
+            return int(out.value)
+        if isinstance(sel, IDSelectorBatch):
+            ids = sel.ids
+        elif isinstance(sel, IDSelector):  # Not, or a user's selector: complemented / evaluated against ntotal here
+            ids = _runs_to_ids(sel.runs(self.ntotal))
+        else:
+            ids = _ids_array(sel)
+        if ids.size:
+            _n.check(self._fn("remove_ids_host")(self._h, ids.ctypes.data, ids.size, ctypes.byref(out)))
+        return int(out.value)
+
+    def remove_stats(self) -> dict:
+        """Removals since the index was created (include/ise_knn.h, ise_index_remove_stats /
+        ise_binary_index_remove_stats): calls that removed something, rows removed, rows that moved to a new
+        position."""
+        return _counters(self._fn("remove_stats"), self._h, ("remove_calls", "rows_removed", "rows_moved"))
+
+    # -- selector-filtered search (faiss.SearchParameters(sel=...))
+    def make_selector(self, sel) -> DeviceSelector:
+        """Extension (not in Faiss): ``sel`` lowered to a device object that can be reused across ``search``,
+        ``range_search`` and ``search_torch`` calls through ``SearchParameters(sel=...)`` until the index changes."""
+        return self._SELECTOR(self, lower_selector(sel, self.ntotal))
+
+    def _with_selector(self, sel, fn):
+        """``fn(handle)`` with the device selector of ``sel``; one built here is destroyed before returning.  A device
+        selector of another family of entry points is refused by its type, before any handle is touched."""
+        if isinstance(sel, DeviceSelector):
+            if sel._ABI != self._SELECTOR._ABI:
+                raise TypeError(self._FOREIGN_SELECTOR)
+            return fn(sel._s)
+        ds = self.make_selector(sel)
+        try:
+            return fn(ds._s)
+        finally:
+            ds.close()
+
+    def sel_stats(self) -> dict:
+        """Filtered search batches, masked passes launched (a binary index: one per 16 queries and per 32 results),
+        filtered range batches (include/ise_knn.h, ise_index_sel_stats / ise_binary_index_sel_stats)."""
+        return _counters(self._fn("sel_stats"), self._h, ("sel_batches", "sel_passes", "sel_range_batches"))
+
+
+class IndexFlat(_RemovableIndex):
     """Exhaustive-search index owning a device copy of its rows.
 
     Mirrors faiss.IndexFlat as the reference touches it: ``d``, ``ntotal``,
@@ -272,6 +395,9 @@ class IndexFlat:
     request threads, backend/engine.py:137; joblib threads,
     backend/descriptors.py:125); the GIL is released while the device works.
     """
+
+    _ABI = "ise_index"
+    _FOREIGN_SELECTOR = "a binary index's selector cannot filter a float index"
 
     def __init__(self, d: int, metric: int = METRIC_L2, device: int | None = None, storage: str = "f32"):
         """``storage="bf16"`` (extension, not a Faiss IndexFlat feature) keeps rows as bf16 and
@@ -286,67 +412,43 @@ class IndexFlat:
         store = {"f32": _n.STORE_F32, "bf16": _n.STORE_BF16}[storage]
         _n.check(_n.lib.ise_index_create_ex(ctypes.byref(self._h), self.d, self.metric_type, self.device, store))
 
-    # -- lifetime
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _n.lib.ise_index_destroy(h)
-            except Exception:  # interpreter shutdown: module globals may already be gone
-                pass
-            h.value = None
-
     @property
     def ntotal(self) -> int:
         n = ctypes.c_int64(0)
         _n.check(_n.lib.ise_index_info(self._h, None, None, ctypes.byref(n), None))
         return int(n.value)
 
-    def reset(self) -> None:
-        _n.check(_n.lib.ise_index_reset(self._h))
-
     def exact_stats(self) -> dict:
         """Counters of the exact float32 L2 path (include/ise_knn.h, ise_index_stats): queries
         re-ranked, queries the certificate sent to the exact direct-difference scan, refreshes of the
         shift vector."""
-        out = (ctypes.c_uint64 * 4)()
-        _n.check(_n.lib.ise_index_stats(self._h, out))
-        return {"reranked": int(out[0]), "exact_scan": int(out[1]), "shift_updates": int(out[2]),
-                "gemm_chunks": int(out[3])}
+        return _counters(_n.lib.ise_index_stats, self._h, ("reranked", "exact_scan", "shift_updates", "gemm_chunks"))
 
     def host_stats(self) -> dict:
         """Combining of concurrent ``search`` calls (include/ise_knn.h, ise_index_host_stats): how many
         shared batches ran and how many calls they served; and how many queries the direct small-batch
         scan answered (float32 L2, at most 4 queries, k <= 32)."""
-        out = (ctypes.c_uint64 * 3)()
-        _n.check(_n.lib.ise_index_host_stats(self._h, out))
-        return {"combined_batches": int(out[0]), "combined_calls": int(out[1]), "direct_queries": int(out[2])}
+        return _counters(_n.lib.ise_index_host_stats, self._h, ("combined_batches", "combined_calls", "direct_queries"))
 
     def short_stats(self) -> dict:
         """Batches scanned by the short-index kernel (include/ise_knn.h, ise_index_short_stats)."""
-        out = (ctypes.c_uint64 * 1)()
-        _n.check(_n.lib.ise_index_short_stats(self._h, out))
-        return {"short_batches": int(out[0])}
+        return _counters(_n.lib.ise_index_short_stats, self._h, ("short_batches",))
 
     def half_stats(self) -> dict:
         """Batches whose filter read shadow rows, fp16 or byte (include/ise_knn.h, ise_index_half_stats)."""
-        out = (ctypes.c_uint64 * 1)()
-        _n.check(_n.lib.ise_index_half_stats(self._h, out))
-        return {"half_batches": int(out[0])}
+        return _counters(_n.lib.ise_index_half_stats, self._h, ("half_batches",))
 
     def byte_stats(self) -> dict:
         """Batches whose filter read the byte shadow rows, and whether the index's byte route is open (include/ise_knn.h,
         ise_index_byte_stats)."""
-        out = (ctypes.c_uint64 * 2)()
-        _n.check(_n.lib.ise_index_byte_stats(self._h, out))
-        return {"byte_batches": int(out[0]), "byte_route": bool(out[1])}
+        c = _counters(_n.lib.ise_index_byte_stats, self._h, ("byte_batches", "byte_route"))
+        c["byte_route"] = bool(c["byte_route"])
+        return c
 
     def depth_stats(self) -> dict:
         """Byte-shadow batches scanned with the isolated plan and with a deep one (include/ise_knn.h,
         ise_index_depth_stats)."""
-        out = (ctypes.c_uint64 * 2)()
-        _n.check(_n.lib.ise_index_depth_stats(self._h, out))
-        return {"isolated_batches": int(out[0]), "deep_batches": int(out[1])}
+        return _counters(_n.lib.ise_index_depth_stats, self._h, ("isolated_batches", "deep_batches"))
 
     def byte_row(self, i: int) -> tuple:
         """(c_r, e_r) of byte shadow row i (include/ise_knn.h, ise_index_byte_row)."""
@@ -378,9 +480,7 @@ class IndexFlat:
 
     def range_stats(self) -> dict:
         """Range-search batches and those that needed the overflow pass (include/ise_knn.h, ise_index_range_stats)."""
-        out = (ctypes.c_uint64 * 2)()
-        _n.check(_n.lib.ise_index_range_stats(self._h, out))
-        return {"range_batches": int(out[0]), "range_overflow_batches": int(out[1])}
+        return _counters(_n.lib.ise_index_range_stats, self._h, ("range_batches", "range_overflow_batches"))
 
     def reserve(self, nq: int, k: int) -> None:
         """Size every internal workspace for batches of ``nq`` queries / ``k`` results now, so that the
@@ -414,34 +514,9 @@ class IndexFlat:
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
         x = x.contiguous()
         st = torch.cuda.current_stream(x.device).cuda_stream
-        _n.check(_n.lib.ise_index_add_device(self._h, x.data_ptr(), x.shape[0], st))
+        with self._lock:
+            _n.check(_n.lib.ise_index_add_device(self._h, x.data_ptr(), x.shape[0], st))
         torch.cuda.current_stream(x.device).synchronize()  # x may be freed by the caller
-
-    def remove_ids(self, sel) -> int:
-        """faiss ``index.remove_ids``: remove the rows an ``IDSelector`` names -- or an int64 array-like, taken as an
-        ``IDSelectorBatch`` as the Faiss wrapper does -- and return how many went.  The other rows keep their order
-        and are renumbered densely (``IndexIDMap`` keeps external ids).  In place on the device: the rows, their
-        norms and shadows move, nothing is re-uploaded (include/ise_knn.h, ise_index_remove_ids_host)."""
-        out = ctypes.c_int64(0)
-        if isinstance(sel, IDSelectorRange):
-            _n.check(_n.lib.ise_index_remove_range(self._h, sel.imin, sel.imax, ctypes.byref(out)))
-            return int(out.value)
-        if isinstance(sel, IDSelectorBatch):
-            ids = sel.ids
-        elif isinstance(sel, IDSelector):  # Not, or a user's selector: complemented / evaluated against ntotal here
-            ids = _runs_to_ids(sel.runs(self.ntotal))
-        else:
-            ids = _ids_array(sel)
-        if ids.size:
-            _n.check(_n.lib.ise_index_remove_ids_host(self._h, ids.ctypes.data, ids.size, ctypes.byref(out)))
-        return int(out.value)
-
-    def remove_stats(self) -> dict:
-        """Removals since the index was created (include/ise_knn.h, ise_index_remove_stats): calls that removed
-        something, rows removed, rows that moved to a new position."""
-        out = (ctypes.c_uint64 * 3)()
-        _n.check(_n.lib.ise_index_remove_stats(self._h, out))
-        return {"remove_calls": int(out[0]), "rows_removed": int(out[1]), "rows_moved": int(out[2])}
 
     def remove_last_timing(self) -> tuple:
         """(milliseconds, bytes) of the last removal's slab launches (include/ise_knn.h, ise_index_remove_last_timing)."""
@@ -452,7 +527,7 @@ class IndexFlat:
     def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
         n = self.ntotal - i0 if n is None else n
         out = np.empty((n, self.d), dtype=np.float32)
-        _n.check(_n.lib.ise_index_reconstruct_host(self._h, i0, n, out.ctypes.data))
+        _n.check(_n.lib.ise_index_reconstruct_host(self._h, int(i0), int(n), out.ctypes.data))
         return out
 
     # -- query side
@@ -468,39 +543,9 @@ class IndexFlat:
         Returns CUDA (D float32 (n, 1), I int64 (n, 1))."""
         import torch
 
-        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
-        x = x.contiguous()
-        n = x.shape[0]
-        D = torch.empty((n, 1), dtype=torch.float32, device=x.device)
-        I = torch.empty((n, 1), dtype=torch.int64, device=x.device)
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        _n.check(_n.lib.ise_index_assign_device(self._h, x.data_ptr(), n, D.data_ptr(), I.data_ptr(), st))
+        x, D, I, st = _torch_io(x, torch.float32, self.d, 1, torch.float32)
+        _n.check(_n.lib.ise_index_assign_device(self._h, x.data_ptr(), x.shape[0], D.data_ptr(), I.data_ptr(), st))
         return D, I
-
-    # -- selector-filtered search (faiss.SearchParameters(sel=...))
-    def make_selector(self, sel) -> DeviceSelector:
-        """Extension (not in Faiss): ``sel`` lowered to a device object that can be reused across ``search``,
-        ``range_search`` and ``search_torch`` calls through ``SearchParameters(sel=...)`` until the index changes."""
-        return DeviceSelector(self, lower_selector(sel, self.ntotal))
-
-    def _with_selector(self, sel, fn):
-        """``fn(handle)`` with the device selector of ``sel``; one built here is destroyed before returning."""
-        if isinstance(sel, BinaryDeviceSelector):
-            raise TypeError("a binary index's selector cannot filter a float index")
-        if isinstance(sel, DeviceSelector):
-            return fn(sel._s)
-        ds = self.make_selector(sel)
-        try:
-            return fn(ds._s)
-        finally:
-            ds.close()
-
-    def sel_stats(self) -> dict:
-        """Filtered search batches, masked passes launched, filtered range batches (include/ise_knn.h,
-        ise_index_sel_stats)."""
-        out = (ctypes.c_uint64 * 3)()
-        _n.check(_n.lib.ise_index_sel_stats(self._h, out))
-        return {"sel_batches": int(out[0]), "sel_passes": int(out[1]), "sel_range_batches": int(out[2])}
 
     def search(self, x, k: int, params=None):
         """(D float32 (nq,k), I int64 (nq,k)), fresh arrays.  L2: squared distance
@@ -548,22 +593,7 @@ class IndexFlat:
         else:
             _n.check(_n.lib.ise_index_range_search_host(self._h, x.ctypes.data, nq, ctypes.c_float(float(radius)),
                                                         ctypes.byref(res)))
-        try:
-            n = ctypes.c_int64()
-            lp, dp_, ip = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-            _n.check(_n.lib.ise_range_result_get(res, ctypes.byref(n), ctypes.byref(lp), ctypes.byref(dp_),
-                                                 ctypes.byref(ip)))
-            lims = np.ctypeslib.as_array(ctypes.cast(lp, ctypes.POINTER(ctypes.c_int64)), (n.value + 1,))
-            lims = lims.astype(np.uint64)
-            total = int(lims[-1])
-            D = np.empty(total, dtype=np.float32)
-            I = np.empty(total, dtype=np.int64)
-            if total:
-                ctypes.memmove(D.ctypes.data, dp_.value, total * 4)
-                ctypes.memmove(I.ctypes.data, ip.value, total * 8)
-        finally:
-            _n.lib.ise_range_result_destroy(res)
-        return lims, D, I
+        return _read_range_result(res, np.float32, _n.lib.ise_range_result_get, _n.lib.ise_range_result_destroy)
 
     def search_torch(self, xq, k: int, params=None):
         """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out, enqueued on
@@ -571,6 +601,8 @@ class IndexFlat:
         selector that is not a ``DeviceSelector`` is built and destroyed here, which waits for the device."""
         import torch
 
+        # written out, not through _torch_io, here and in search_keys_torch: a latency path (DESIGN.md 4.1, host call
+        # overhead) keeps its number of Python-level calls
         assert xq.is_cuda and xq.dtype == torch.float32 and xq.dim() == 2 and xq.shape[1] == self.d
         xq = xq.contiguous()
         nq = xq.shape[0]
@@ -662,27 +694,30 @@ class _RowMask(IDSelector):
         return out
 
 
-class IndexIDMap:
-    """faiss.IndexIDMap over a flat index: rows carry the caller's 64-bit ids, which survive ``remove_ids`` (the
-    sub-index renumbers its rows; ``id_map[row]`` follows).  The mapping is host numpy, off the hot path."""
+class _IDMapBase:
+    """Faiss's id-mapping wrapper over a flat index of either kind: rows carry the caller's 64-bit ids, which survive
+    ``remove_ids`` (the sub-index renumbers its rows; ``id_map[row]`` follows).  The mapping is host numpy, off the hot
+    path.  Selectors -- in ``remove_ids`` and in ``params=`` -- are over EXTERNAL ids.  A subclass says how rows are
+    coerced (``_rows``) and forwards what its sub-index has beyond ``d``, ``is_trained`` and ``ntotal``; the messages
+    carry its name."""
 
-    def __init__(self, index: IndexFlat):
-        if isinstance(index, IndexIVFFlat):
-            raise NotImplementedError("IndexIDMap over an IndexIVFFlat is not provided")
-        assert index.ntotal == 0, "IndexIDMap wraps an empty index (Faiss: index is empty on input)"
+    def __init__(self, index):
+        assert index.ntotal == 0, f"{type(self).__name__} wraps an empty index (Faiss: index is empty on input)"
         self.index = index
         self.id_map = np.zeros(0, dtype=np.int64)
 
     d = property(lambda self: self.index.d)
-    metric_type = property(lambda self: self.index.metric_type)
     is_trained = property(lambda self: self.index.is_trained)
     ntotal = property(lambda self: self.index.ntotal)
 
+    def _rows(self, x) -> np.ndarray:
+        raise NotImplementedError
+
     def add(self, x) -> None:
-        raise RuntimeError("add does not work with IndexIDMap, call add_with_ids")  # Faiss throws the same
+        raise RuntimeError(f"add does not work with {type(self).__name__}, call add_with_ids")  # Faiss throws the same
 
     def add_with_ids(self, x, ids) -> None:
-        x = _as_rows(x, self.index.d)
+        x = self._rows(x)
         ids = _ids_array(ids)
         assert ids.shape[0] == x.shape[0], "one id per row"
         self.index.add(x)
@@ -700,7 +735,8 @@ class IndexIDMap:
         if sel is None:
             return None
         if isinstance(sel, DeviceSelector):
-            raise TypeError("IndexIDMap takes an IDSelector over external ids, not a DeviceSelector over rows")
+            raise TypeError(f"{type(self).__name__} takes an IDSelector over external ids, not a DeviceSelector over "
+                            "rows")
         return SearchParameters(sel=_RowMask(sel.members(self.id_map)))
 
     def search(self, x, k: int, params=None):
@@ -727,6 +763,20 @@ class IndexIDMap:
     def reset(self) -> None:
         self.index.reset()
         self.id_map = np.zeros(0, dtype=np.int64)
+
+
+class IndexIDMap(_IDMapBase):
+    """faiss.IndexIDMap over an ``IndexFlat``."""
+
+    def __init__(self, index: IndexFlat):
+        if isinstance(index, IndexIVFFlat):
+            raise NotImplementedError("IndexIDMap over an IndexIVFFlat is not provided")
+        super().__init__(index)
+
+    metric_type = property(lambda self: self.index.metric_type)
+
+    def _rows(self, x) -> np.ndarray:
+        return _as_rows(x, self.index.d)
 
 
 def merge_keys_torch(keys, metric: int):
@@ -790,12 +840,30 @@ def serialize_flat(d: int, metric: int, xb: np.ndarray) -> bytes:
     return head + struct.pack("<Q", n * d) + xb.tobytes()
 
 
-def serialize_idmap(d: int, metric: int, xb: np.ndarray, ids) -> bytes:
+def _pack_id_vector(ids, n: int) -> bytes:
+    """The tail of both id-map files: uint64 count (= ntotal), count int64."""
     ids = np.ascontiguousarray(ids, dtype="<i8").reshape(-1)
-    n = xb.shape[0] if np.size(xb) else 0
     assert ids.size == n, "one id per row"
+    return struct.pack("<Q", n) + ids.tobytes()
+
+
+def _parse_id_vector(buf: bytes, off: int, n: int, truncated: str, miscounted: str) -> np.ndarray:
+    """The ``n`` ids at ``buf[off:]``; RuntimeError(``truncated``) when bytes are missing, RuntimeError(``miscounted``)
+    when the count is not ``n``."""
+    if len(buf) < off + 8:
+        raise RuntimeError(truncated)
+    (count,) = struct.unpack_from("<Q", buf, off)
+    if count != n:
+        raise RuntimeError(miscounted)
+    if len(buf) < off + 8 + 8 * count:
+        raise RuntimeError(truncated)
+    return np.frombuffer(buf, dtype="<i8", count=count, offset=off + 8).astype(np.int64)
+
+
+def serialize_idmap(d: int, metric: int, xb: np.ndarray, ids) -> bytes:
+    n = xb.shape[0] if np.size(xb) else 0
     head = _HDR.pack(_FOURCC_IDMAP, d, n, 1 << 20, 1 << 20, 1, metric)
-    return head + serialize_flat(d, metric, xb) + struct.pack("<Q", n) + ids.tobytes()
+    return head + serialize_flat(d, metric, xb) + _pack_id_vector(ids, n)
 
 
 def parse_idmap(buf: bytes):
@@ -809,14 +877,8 @@ def parse_idmap(buf: bytes):
     d2, metric, xb = parse_flat(sub)
     if d2 != d or xb.shape[0] != n:
         raise RuntimeError("corrupt IndexIDMap: the sub-index does not match the header")
-    off = 2 * _HDR.size + 8 + 4 * n * d
-    if len(buf) < off + 8:
-        raise RuntimeError("truncated IndexIDMap id vector")
-    (count,) = struct.unpack_from("<Q", buf, off)
-    if count != n or len(buf) < off + 8 + 8 * count:
-        raise RuntimeError("truncated IndexIDMap id vector")
-    ids = np.frombuffer(buf, dtype="<i8", count=count, offset=off + 8).astype(np.int64)
-    return d, metric, xb, ids
+    truncated = "truncated IndexIDMap id vector"  # also what this format says to a count that is not ntotal
+    return d, metric, xb, _parse_id_vector(buf, 2 * _HDR.size + 8 + 4 * n * d, n, truncated, truncated)
 
 
 def parse_flat(buf: bytes):
@@ -884,11 +946,15 @@ def _as_codes(x, code_size=None) -> np.ndarray:
     return x
 
 
-class IndexBinaryFlat:
+class IndexBinaryFlat(_RemovableIndex):
     """faiss.IndexBinaryFlat(d): exact brute-force search over ``d``-bit codes (uint8 rows of ``d / 8`` bytes) under the
     Hamming distance, on the device (include/ise_knn.h, ise_binary_index_*).  Distances are int32, ascending; ties go
     by ascending id, always (Faiss promises no order among equal distances); unfilled slots are -1 / INT32_MAX.  No
     CPU path: the constructor raises without a GPU."""
+
+    _ABI = "ise_binary_index"
+    _SELECTOR = BinaryDeviceSelector
+    _FOREIGN_SELECTOR = "a float index's selector cannot filter a binary index"
 
     def __init__(self, d: int, device: int | None = None):
         self.d = int(d)
@@ -899,30 +965,16 @@ class IndexBinaryFlat:
         self._lock = threading.Lock()
         _n.check(_n.lib.ise_binary_index_create(ctypes.byref(self._h), self.d, self.device))
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _n.lib.ise_binary_index_destroy(h)
-            except Exception:  # interpreter shutdown: module globals may already be gone
-                pass
-            h.value = None
-
     @property
     def ntotal(self) -> int:
         n = ctypes.c_int64(0)
         _n.check(_n.lib.ise_binary_index_info(self._h, None, ctypes.byref(n), None))
         return int(n.value)
 
-    def reset(self) -> None:
-        _n.check(_n.lib.ise_binary_index_reset(self._h))
-
     def binary_stats(self) -> dict:
         """Search batches, scan passes launched (one per 16 queries and per 32 results), range batches
         (include/ise_knn.h, ise_binary_index_stats)."""
-        out = (ctypes.c_uint64 * 3)()
-        _n.check(_n.lib.ise_binary_index_stats(self._h, out))
-        return {"search_batches": int(out[0]), "scan_passes": int(out[1]), "range_batches": int(out[2])}
+        return _counters(_n.lib.ise_binary_index_stats, self._h, ("search_batches", "scan_passes", "range_batches"))
 
     def add(self, x) -> None:
         """Append codes (copied): uint8 (n, d / 8)."""
@@ -949,56 +1001,8 @@ class IndexBinaryFlat:
     def reconstruct(self, i: int) -> np.ndarray:
         return self.reconstruct_n(int(i), 1)[0]
 
-    def remove_ids(self, sel) -> int:
-        """faiss ``index.remove_ids``, with the arguments of ``IndexFlat.remove_ids``: an ``IDSelector`` or an int64
-        array-like taken as a batch; returns how many rows went.  The other rows keep their order and are renumbered
-        densely (``IndexBinaryIDMap`` keeps external ids).  In place on the device (include/ise_knn.h,
-        ise_binary_index_remove_ids_host)."""
-        out = ctypes.c_int64(0)
-        if isinstance(sel, IDSelectorRange):
-            _n.check(_n.lib.ise_binary_index_remove_range(self._h, sel.imin, sel.imax, ctypes.byref(out)))
-            return int(out.value)
-        if isinstance(sel, IDSelectorBatch):
-            ids = sel.ids
-        elif isinstance(sel, IDSelector):  # Not, or a user's selector: complemented / evaluated against ntotal here
-            ids = _runs_to_ids(sel.runs(self.ntotal))
-        else:
-            ids = _ids_array(sel)
-        if ids.size:
-            _n.check(_n.lib.ise_binary_index_remove_ids_host(self._h, ids.ctypes.data, ids.size, ctypes.byref(out)))
-        return int(out.value)
-
-    def remove_stats(self) -> dict:
-        """Removals since the index was created (include/ise_knn.h, ise_binary_index_remove_stats): calls that removed
-        something, rows removed, rows that moved to a new position."""
-        out = (ctypes.c_uint64 * 3)()
-        _n.check(_n.lib.ise_binary_index_remove_stats(self._h, out))
-        return {"remove_calls": int(out[0]), "rows_removed": int(out[1]), "rows_moved": int(out[2])}
-
-    # -- selector-filtered search (faiss.SearchParameters(sel=...))
-    def make_selector(self, sel) -> BinaryDeviceSelector:
-        """Extension (not in Faiss): ``sel`` lowered to a device object that can be reused across ``search``,
-        ``range_search`` and ``search_torch`` calls through ``SearchParameters(sel=...)`` until the index changes."""
-        return BinaryDeviceSelector(self, lower_selector(sel, self.ntotal))
-
-    def _with_selector(self, sel, fn):
-        """``fn(handle)`` with the device selector of ``sel``; one built here is destroyed before returning."""
-        if isinstance(sel, BinaryDeviceSelector):
-            return fn(sel._s)
-        if isinstance(sel, DeviceSelector):
-            raise TypeError("a float index's selector cannot filter a binary index")
-        ds = self.make_selector(sel)
-        try:
-            return fn(ds._s)
-        finally:
-            ds.close()
-
-    def sel_stats(self) -> dict:
-        """Filtered search batches, masked passes launched (one per 16 queries and per 32 results), filtered range
-        batches (include/ise_knn.h, ise_binary_index_sel_stats)."""
-        out = (ctypes.c_uint64 * 3)()
-        _n.check(_n.lib.ise_binary_index_sel_stats(self._h, out))
-        return {"sel_batches": int(out[0]), "sel_passes": int(out[1]), "sel_range_batches": int(out[2])}
+    def make_selector(self, sel) -> BinaryDeviceSelector:  # the shared method, with this index's return type
+        return super().make_selector(sel)
 
     def search(self, x, k: int, params=None):
         """(D int32 (nq, k), I int64 (nq, k)), fresh arrays: Hamming distance ascending, ties by ascending id.
@@ -1023,12 +1027,8 @@ class IndexBinaryFlat:
         not a ``BinaryDeviceSelector`` is built and destroyed here, which waits for the device."""
         import torch
 
-        assert xq.is_cuda and xq.dtype == torch.uint8 and xq.dim() == 2 and xq.shape[1] == self.code_size
-        xq = xq.contiguous()
+        xq, D, I, st = _torch_io(xq, torch.uint8, self.code_size, int(k), torch.int32)
         nq = xq.shape[0]
-        D = torch.empty((nq, int(k)), dtype=torch.int32, device=xq.device)
-        I = torch.empty((nq, int(k)), dtype=torch.int64, device=xq.device)
-        st = torch.cuda.current_stream(xq.device).cuda_stream
         sel = _params_sel(params)
         if sel is not None:
             def run(s):
@@ -1057,22 +1057,8 @@ class IndexBinaryFlat:
         else:
             _n.check(_n.lib.ise_binary_index_range_search_host(self._h, x.ctypes.data, nq, int(radius),
                                                                ctypes.byref(res)))
-        try:
-            n = ctypes.c_int64()
-            lp, dp_, ip = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-            _n.check(_n.lib.ise_binary_range_result_get(res, ctypes.byref(n), ctypes.byref(lp), ctypes.byref(dp_),
-                                                        ctypes.byref(ip)))
-            lims = np.ctypeslib.as_array(ctypes.cast(lp, ctypes.POINTER(ctypes.c_int64)), (n.value + 1,))
-            lims = lims.astype(np.uint64)
-            total = int(lims[-1])
-            D = np.empty(total, dtype=np.int32)
-            I = np.empty(total, dtype=np.int64)
-            if total:
-                ctypes.memmove(D.ctypes.data, dp_.value, total * 4)
-                ctypes.memmove(I.ctypes.data, ip.value, total * 8)
-        finally:
-            _n.lib.ise_binary_range_result_destroy(res)
-        return lims, D, I
+        return _read_range_result(res, np.int32, _n.lib.ise_binary_range_result_get,
+                                  _n.lib.ise_binary_range_result_destroy)
 
 
 # Faiss on-disk IndexBinaryFlat layout [upstream-faiss index_write.cpp write_index_binary, restated from the published
@@ -1110,70 +1096,20 @@ def parse_binary_flat(buf: bytes):
     return d, xb
 
 
-class IndexBinaryIDMap:
-    """faiss.IndexBinaryIDMap over a binary flat index: rows carry the caller's 64-bit ids, which survive ``remove_ids``
-    (the sub-index renumbers its rows; ``id_map[row]`` follows).  The mapping is host numpy, off the hot path.
-    Selectors -- in ``remove_ids`` and in ``params=`` -- are over EXTERNAL ids."""
+class IndexBinaryIDMap(_IDMapBase):
+    """faiss.IndexBinaryIDMap over an ``IndexBinaryFlat``."""
 
+    # two shared methods under this class's own annotations: the sub-index's type, a radius that is a Hamming distance
     def __init__(self, index: IndexBinaryFlat):
-        assert index.ntotal == 0, "IndexBinaryIDMap wraps an empty index (Faiss: index is empty on input)"
-        self.index = index
-        self.id_map = np.zeros(0, dtype=np.int64)
-
-    d = property(lambda self: self.index.d)
-    code_size = property(lambda self: self.index.code_size)
-    is_trained = property(lambda self: self.index.is_trained)
-    ntotal = property(lambda self: self.index.ntotal)
-
-    def add(self, x) -> None:
-        raise RuntimeError("add does not work with IndexBinaryIDMap, call add_with_ids")  # Faiss throws the same
-
-    def add_with_ids(self, x, ids) -> None:
-        x = _as_codes(x, self.index.code_size)
-        ids = _ids_array(ids)
-        assert ids.shape[0] == x.shape[0], "one id per row"
-        self.index.add(x)
-        self.id_map = np.concatenate((self.id_map, ids))
-
-    def _map(self, I: np.ndarray) -> np.ndarray:
-        out = np.full(I.shape, -1, dtype=np.int64)
-        ok = I >= 0
-        out[ok] = self.id_map[I[ok]]
-        return out
-
-    def _row_params(self, params):
-        """A selector over EXTERNAL ids -> one over rows (a bitmap from ``sel.members(id_map)``)."""
-        sel = _params_sel(params)
-        if sel is None:
-            return None
-        if isinstance(sel, DeviceSelector):
-            raise TypeError("IndexBinaryIDMap takes an IDSelector over external ids, not a DeviceSelector over rows")
-        return SearchParameters(sel=_RowMask(sel.members(self.id_map)))
-
-    def search(self, x, k: int, params=None):
-        D, I = self.index.search(x, k, params=self._row_params(params))
-        return D, self._map(I)
+        super().__init__(index)
 
     def range_search(self, x, radius: int, params=None):
-        lims, D, I = self.index.range_search(x, radius, params=self._row_params(params))
-        return lims, D, self._map(I)
+        return super().range_search(x, radius, params)
 
-    def remove_ids(self, sel) -> int:
-        """``sel`` selects EXTERNAL ids (a selector, or an int64 array-like taken as a batch)."""
-        if not isinstance(sel, IDSelector):
-            sel = IDSelectorBatch(sel)
-        gone = sel.members(self.id_map)
-        rows = np.flatnonzero(gone).astype(np.int64)
-        if rows.size == 0:
-            return 0
-        n = self.index.remove_ids(rows)
-        assert n == rows.size
-        self.id_map = self.id_map[~gone]
-        return n
+    code_size = property(lambda self: self.index.code_size)
 
-    def reset(self) -> None:
-        self.index.reset()
-        self.id_map = np.zeros(0, dtype=np.int64)
+    def _rows(self, x) -> np.ndarray:
+        return _as_codes(x, self.index.code_size)
 
 
 # IndexBinaryIDMap [upstream-faiss index_write.cpp write_index_binary, restated from memory of the published format and
@@ -1186,9 +1122,7 @@ _FOURCC_BINARY_IDMAP = b"IBMp"
 def serialize_binary_idmap(d: int, xb, ids) -> bytes:
     sub = serialize_binary_flat(d, xb)
     _, _, cs, n, _, _ = _BHDR.unpack_from(sub, 0)
-    ids = np.ascontiguousarray(ids, dtype="<i8").reshape(-1)
-    assert ids.size == n, "one id per row"
-    return _BHDR.pack(_FOURCC_BINARY_IDMAP, int(d), cs, n, 1, 1) + sub + struct.pack("<Q", n) + ids.tobytes()
+    return _BHDR.pack(_FOURCC_BINARY_IDMAP, int(d), cs, n, 1, 1) + sub + _pack_id_vector(ids, n)
 
 
 def parse_binary_idmap(buf: bytes):
@@ -1201,15 +1135,8 @@ def parse_binary_idmap(buf: bytes):
     d2, xb = parse_binary_flat(buf[_BHDR.size:])
     if d2 != d or xb.shape[1] != cs or xb.shape[0] != n:
         raise RuntimeError("corrupt IndexBinaryIDMap: the sub-index does not match the header")
-    off = 2 * _BHDR.size + 8 + n * cs
-    if len(buf) < off + 8:
-        raise RuntimeError("truncated IndexBinaryIDMap id vector")
-    (count,) = struct.unpack_from("<Q", buf, off)
-    if count != n:
-        raise RuntimeError("corrupt IndexBinaryIDMap: the id vector does not have one id per row")
-    if len(buf) < off + 8 + 8 * count:
-        raise RuntimeError("truncated IndexBinaryIDMap id vector")
-    ids = np.frombuffer(buf, dtype="<i8", count=count, offset=off + 8).astype(np.int64)
+    ids = _parse_id_vector(buf, 2 * _BHDR.size + 8 + n * cs, n, "truncated IndexBinaryIDMap id vector",
+                           "corrupt IndexBinaryIDMap: the id vector does not have one id per row")
     return d, xb, ids
 
 
@@ -1340,7 +1267,7 @@ class ClusteringParameters:
         self.seed = int(seed)
 
 
-class IndexIVFFlat:
+class IndexIVFFlat(_IndexHandle):
     """faiss.IndexIVFFlat: a coarse quantiser (an ``IndexFlat`` of ``nlist`` centroids, the caller's object) in front of
     uncompressed float32 rows.  ``add`` puts every row into the inverted list of its nearest centroid; ``search`` visits
     the ``nprobe`` lists whose centroids are nearest to the query and returns the exact k best among THEIR rows -- D has
@@ -1354,6 +1281,8 @@ class IndexIVFFlat:
     after an ``add`` rebuilds the lists, which moves the whole index once.  Not provided (they raise
     ``NotImplementedError``): ``range_search``, ``remove_ids``, ``params=``, ``write_index`` / ``read_index`` and
     ``IndexIDMap`` over this type."""
+
+    _ABI = "ise_ivf"
 
     def __init__(self, quantizer: IndexFlat, d: int, nlist: int, metric: int = METRIC_L2):
         assert isinstance(quantizer, IndexFlat), "the coarse quantiser is an IndexFlat"
@@ -1369,15 +1298,6 @@ class IndexIVFFlat:
         self._lock = threading.Lock()
         _n.check(_n.lib.ise_ivf_create(ctypes.byref(self._h), self.d, self.metric_type, self.nlist, self.device))
         self.is_trained = quantizer.ntotal == self.nlist
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _n.lib.ise_ivf_destroy(h)
-            except Exception:  # interpreter shutdown: module globals may already be gone
-                pass
-            h.value = None
 
     @property
     def ntotal(self) -> int:
@@ -1461,9 +1381,7 @@ class IndexIVFFlat:
     def ivf_stats(self) -> dict:
         """Search batches, scan passes launched, 16-row tiles of list rows the passes loaded (include/ise_knn.h,
         ise_ivf_stats).  Waits for the device."""
-        out = (ctypes.c_uint64 * 3)()
-        _n.check(_n.lib.ise_ivf_stats(self._h, out))
-        return {"batches": int(out[0]), "passes": int(out[1]), "tiles_loaded": int(out[2])}
+        return _counters(_n.lib.ise_ivf_stats, self._h, ("batches", "passes", "tiles_loaded"))
 
     # -- query side
     def _nprobe(self) -> int:
@@ -1505,15 +1423,12 @@ class IndexIVFFlat:
             raise NotImplementedError("search parameters are not provided on IndexIVFFlat: set index.nprobe")
         if not self.is_trained:
             raise RuntimeError("IndexIVFFlat.search before train")
-        assert xq.is_cuda and xq.dtype == torch.float32 and xq.dim() == 2 and xq.shape[1] == self.d
-        xq = xq.contiguous()
-        nq, k = xq.shape[0], int(k)
-        D = torch.empty((nq, k), dtype=torch.float32, device=xq.device)
-        I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
+        k = int(k)
+        xq, D, I, st = _torch_io(xq, torch.float32, self.d, k, torch.float32)
+        nq = xq.shape[0]
         if nq == 0:
             return D, I
         probes = self.quantizer.search_torch(xq, self._nprobe())[1].contiguous()
-        st = torch.cuda.current_stream(xq.device).cuda_stream
         with self._lock:
             _n.check(_n.lib.ise_ivf_search_device(self._h, xq.data_ptr(), nq, k, probes.data_ptr(), probes.shape[1],
                                                   D.data_ptr(), I.data_ptr(), st))
