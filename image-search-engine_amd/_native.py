@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("ISE_KNN_LIB") or os.path.join(_HERE, "csrc", "libise_
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
 MAX_K = 2048
+PQ_MAX_M = 64
 STORE_F32, STORE_BF16 = 0, 1
 
 E_INVALID, E_HIP, E_NOMEM, E_NODEVICE = -1, -2, -3, -4
@@ -118,6 +119,24 @@ PROTOTYPES = [
     ("ise_ivf_search_device", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp]),
     ("ise_ivf_search_host", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp]),
     ("ise_ivf_stats", _int, [_vp, _u64p]),
+    ("ise_pq_create", _int, [ctypes.POINTER(_vp), _int, _int, _int, _int, _int]),
+    ("ise_pq_destroy", _int, [_vp]),
+    ("ise_pq_reset", _int, [_vp]),
+    ("ise_pq_info", _int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), _i64p,
+                           ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    ("ise_pq_set_centroids_host", _int, [_vp, _vp]),
+    ("ise_pq_get_centroids_host", _int, [_vp, _vp]),
+    ("ise_pq_encode_host", _int, [_vp, _vp, _i64, _vp]),
+    ("ise_pq_encode_device", _int, [_vp, _vp, _i64, _vp, _vp]),
+    ("ise_pq_decode_host", _int, [_vp, _vp, _i64, _vp]),
+    ("ise_pq_add_host", _int, [_vp, _vp, _i64]),
+    ("ise_pq_add_device", _int, [_vp, _vp, _i64, _vp]),
+    ("ise_pq_add_codes_host", _int, [_vp, _vp, _i64]),
+    ("ise_pq_codes_host", _int, [_vp, _i64, _i64, _vp]),
+    ("ise_pq_reconstruct_host", _int, [_vp, _i64, _i64, _vp]),
+    ("ise_pq_search_host", _int, [_vp, _vp, _i64, _int, _vp, _vp]),
+    ("ise_pq_search_device", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
+    ("ise_pq_stats", _int, [_vp, _u64p]),
     ("ise_refresh_env_knobs", _int, []),
     ("ise_comm_precheck", _int, [_int]),
     ("ise_comm_unique_id", _int, [_vp]),

@@ -37,6 +37,13 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          backend/utils.py:312 points to): ``train`` / ``add`` / ``search`` with ``nprobe`` /
                                          ``search_preassigned``; rows scattered into inverted lists on the device, one
                                          pass over the probed lists only (csrc/ise_ivf.hpp); never called by the reference
+    IndexPQ(d, M, nbits=8)               Faiss's product-quantised index: rows kept as M code bytes, one of 256 centroids per
+                                         sub-vector; ``train`` (one k-means per sub-quantiser) / ``add`` / ``search`` by
+                                         lookup tables over the codes (csrc/ise_pq.hpp), ``reconstruct_n``, ``sa_encode`` /
+                                         ``sa_decode``, ``index.pq`` (``centroids``, ``set_centroids``, ``compute_codes``,
+                                         ``decode``), ``write_index`` / ``read_index`` ("IxPq"); the compression half of
+                                         the reference's "cell-probe" index (backend/utils.py:311-325), which itself
+                                         (IndexIVFPQ) is still not provided
     write_index_binary / read_index_binary   Faiss's names for IndexBinaryFlat ("IBxF") and IndexBinaryIDMap ("IBMp") files
 
 All arithmetic runs on the MI355X through ``include/ise_knn.h``; there is no
@@ -771,6 +778,8 @@ class IndexIDMap(_IDMapBase):
     def __init__(self, index: IndexFlat):
         if isinstance(index, IndexIVFFlat):
             raise NotImplementedError("IndexIDMap over an IndexIVFFlat is not provided")
+        if isinstance(index, IndexPQ):
+            raise NotImplementedError("IndexIDMap over an IndexPQ is not provided")
         super().__init__(index)
 
     metric_type = property(lambda self: self.index.metric_type)
@@ -899,11 +908,67 @@ def parse_flat(buf: bytes):
     return d, metric, xb
 
 
+# IndexPQ [upstream-faiss index_write.cpp write_index / write_ProductQuantizer, restated from memory of the published
+# format and UNPINNED like the four layouts here: there is no sample file]:
+#   fourcc "IxPq"; the index header (d, ntotal, 1<<20, 1<<20, is_trained, metric_type); the product quantiser: int64 d;
+#   int64 M; int64 nbits; the centroid vector: uint64 count (= M * 256 * dsub), count float32; the code vector: uint64
+#   count (= ntotal * M), count uint8; then the polysemous fields: int32 search_type (0, "exhaustive ADC search"),
+#   uint8 encode_signs (0), int32 polysemous_ht (0).
+_FOURCC_PQ = b"IxPq"
+_PQ_DIMS = struct.Struct("<qqq")
+_PQ_TAIL = struct.Struct("<iBi")
+
+
+def serialize_pq(d: int, metric: int, centroids, codes) -> bytes:
+    """``centroids`` float32 (M, 256, dsub), ``codes`` uint8 (n, M) (any n, also 0)."""
+    c = np.ascontiguousarray(centroids, dtype="<f4")
+    assert c.ndim == 3 and c.shape[1] == 256 and c.shape[0] * c.shape[2] == int(d), "centroids are (M, 256, d / M)"
+    M = c.shape[0]
+    codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, M)
+    n = codes.shape[0]
+    head = _HDR.pack(_FOURCC_PQ, int(d), n, 1 << 20, 1 << 20, 1, int(metric))
+    return (head + _PQ_DIMS.pack(int(d), M, 8) + struct.pack("<Q", c.size) + c.tobytes()
+            + struct.pack("<Q", n * M) + codes.tobytes() + _PQ_TAIL.pack(0, 0, 0))
+
+
+def parse_pq(buf: bytes):
+    """-> (d, M, nbits, metric, centroids float32 (M, 256, dsub), codes uint8 (n, M)); raises RuntimeError on a foreign,
+    truncated or miscounted file."""
+    if len(buf) >= 4 and buf[:4] != _FOURCC_PQ:
+        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexPQ")
+    off = _HDR.size
+    if len(buf) < off + _PQ_DIMS.size + 8:
+        raise RuntimeError("truncated IndexPQ file")
+    _, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
+    d2, M, nbits = _PQ_DIMS.unpack_from(buf, off)
+    off += _PQ_DIMS.size
+    if d <= 0 or d2 != d or M <= 0 or d % M != 0 or nbits != 8 or n < 0:
+        raise RuntimeError("corrupt IndexPQ header (only 8-bit product quantisers are readable)")
+    (count,) = struct.unpack_from("<Q", buf, off)
+    off += 8
+    if count != 256 * d:
+        raise RuntimeError("corrupt IndexPQ: the centroid vector does not hold M * 256 * dsub floats")
+    if len(buf) < off + 4 * count + 8:
+        raise RuntimeError("truncated IndexPQ centroids")
+    centroids = np.frombuffer(buf, dtype="<f4", count=count, offset=off).reshape(M, 256, d // M).astype(np.float32)
+    off += 4 * count
+    (ncodes,) = struct.unpack_from("<Q", buf, off)
+    off += 8
+    if ncodes != n * M:
+        raise RuntimeError("corrupt IndexPQ: the code vector does not hold ntotal * M bytes")
+    if len(buf) < off + ncodes + _PQ_TAIL.size:
+        raise RuntimeError("truncated IndexPQ codes")
+    codes = np.frombuffer(buf, dtype=np.uint8, count=ncodes, offset=off).reshape(n, M).copy()
+    return d, M, nbits, metric, centroids, codes
+
+
 def write_index(index, path) -> None:
     if isinstance(index, IndexIVFFlat):
         raise NotImplementedError("write_index of an IndexIVFFlat is not provided")
     with open(str(path), "wb") as f:
-        if isinstance(index, IndexIDMap):
+        if isinstance(index, IndexPQ):
+            f.write(serialize_pq(index.d, index.metric_type, index.pq.centroids, index.codes))
+        elif isinstance(index, IndexIDMap):
             sub = index.index
             f.write(serialize_idmap(sub.d, sub.metric_type, sub.reconstruct_n(0, sub.ntotal), index.id_map))
         else:
@@ -911,10 +976,16 @@ def write_index(index, path) -> None:
 
 
 def read_index(path, device: int | None = None):
-    """-> IndexFlat, or IndexIDMap for a file written from one."""
+    """-> IndexFlat, IndexIDMap or IndexPQ, as the file was written."""
     with open(str(path), "rb") as f:
         buf = f.read()
     ids = None
+    if buf[:4] == _FOURCC_PQ:
+        d, M, nbits, metric, centroids, codes = parse_pq(buf)
+        index = IndexPQ(d, M, nbits, metric, device)
+        index.pq.set_centroids(centroids)
+        index._add_codes(codes)  # as stored: nothing is encoded again
+        return index
     if buf[:4] in (b"IwFl", b"IwF2"):  # Faiss's fourccs of IndexIVFFlat files
         raise NotImplementedError("read_index of an IndexIVFFlat file is not provided")
     if buf[:4] == _FOURCC_IDMAP:
@@ -1168,7 +1239,7 @@ def read_index_binary(path, device: int | None = None):
     return index
 
 
-class IndexIVFPQ:  # backend/utils.py:323 ("cell-probe"): approximate, out of scope
+class IndexIVFPQ:  # backend/utils.py:323 ("cell-probe"): IndexIVFFlat's lists over IndexPQ's codes, not composed yet
     def __init__(self, *a, **kw):
         raise NotImplementedError("IndexIVFPQ ('cell-probe') is outside the exact brute-force hot path")
 
@@ -1439,3 +1510,217 @@ class IndexIVFFlat(_IndexHandle):
 
     def remove_ids(self, *a, **kw):
         raise NotImplementedError("remove_ids is not provided on IndexIVFFlat")
+
+
+# ---------------------------------------------------------------- product quantisation (faiss.IndexPQ)
+class ProductQuantizer:
+    """``index.pq``: the view of an ``IndexPQ``'s codec that faiss.ProductQuantizer gives -- ``d``, ``M``, ``nbits``,
+    ``dsub``, ``ksub``, ``code_size``, ``centroids`` (a float32 (M, 256, dsub) copy), ``compute_codes`` and ``decode``.
+    ``set_centroids`` is an extension, in place of Faiss's ``copy_array_to_vector(c, pq.centroids)`` followed by
+    ``index.is_trained = True``."""
+
+    def __init__(self, index):
+        self._index = index
+        self.d, self.M, self.nbits = index.d, index.M, 8
+        self.dsub, self.ksub, self.code_size = index.d // index.M, 256, index.M
+
+    @property
+    def centroids(self) -> np.ndarray:
+        out = np.empty((self.M, self.ksub, self.dsub), dtype=np.float32)
+        _n.check(_n.lib.ise_pq_get_centroids_host(self._index._h, out.ctypes.data))
+        return out
+
+    def set_centroids(self, c) -> None:
+        """float32 (M, 256, dsub), finite; refused while the index holds rows (their codes belong to the centroids in
+        place).  Marks the index trained."""
+        c = np.ascontiguousarray(np.asarray(c), dtype=np.float32)
+        assert c.shape == (self.M, self.ksub, self.dsub), f"centroids are {(self.M, self.ksub, self.dsub)}, got {c.shape}"
+        if not np.isfinite(c).all():
+            raise ValueError("a centroid has a NaN or inf entry")
+        if self._index.ntotal > 0:
+            raise RuntimeError("set_centroids on an index that holds rows: reset() first")
+        _n.check(_n.lib.ise_pq_set_centroids_host(self._index._h, c.ctypes.data))
+        self._index.is_trained = True
+
+    def compute_codes(self, x) -> np.ndarray:
+        return self._index.sa_encode(x)
+
+    def decode(self, codes) -> np.ndarray:
+        return self._index.sa_decode(codes)
+
+
+class IndexPQ(_IndexHandle):
+    """faiss.IndexPQ(d, M, nbits=8, metric): every row is kept as ``M`` bytes, byte m the number of the centroid (of 256,
+    trained per sub-quantiser) nearest to the row's m-th sub-vector of ``d / M`` entries in squared L2, the lowest number
+    among equals -- for inner-product indexes too, as in Faiss.  ``search`` scores a row from per-query lookup tables
+    (asymmetric distance computation): D is the squared L2 distance or inner product of the query and the DECODED row
+    (``reconstruct_n``), float32; L2 ascending, inner product descending, ties by ascending id, unfilled slots
+    -1 / +-FLT_MAX.
+
+    For a given codebook everything here is determined; Faiss's own training (its seeding, its iteration count) is
+    unpinned.  On the device (include/ise_knn.h, ise_pq_*).  Not provided (they raise
+    ``NotImplementedError``): ``nbits != 8``, ``range_search``, ``remove_ids``, ``params=``, polysemous search and
+    ``IndexIDMap`` over this type."""
+
+    _ABI = "ise_pq"
+    TRAIN_MAX_ROWS = 256 * 256  # Faiss's max_points_per_centroid x ksub
+
+    def __init__(self, d: int, M: int, nbits: int = 8, metric: int = METRIC_L2, device: int | None = None):
+        if int(nbits) != 8:
+            raise NotImplementedError(f"IndexPQ with nbits = {nbits}: only 8-bit sub-quantisers are provided")
+        self.d, self.M = int(d), int(M)
+        self.metric_type = int(metric)
+        self.code_size = self.M
+        self.is_trained = False
+        self.cp = ClusteringParameters(niter=25)
+        self.device = _default_device() if device is None else int(device)
+        self._h = ctypes.c_void_p()
+        self._lock = threading.Lock()
+        _n.check(_n.lib.ise_pq_create(ctypes.byref(self._h), self.d, self.M, 8, self.metric_type, self.device))
+        self.pq = ProductQuantizer(self)
+
+    @property
+    def ntotal(self) -> int:
+        n = ctypes.c_int64(0)
+        _n.check(_n.lib.ise_pq_info(self._h, None, None, None, None, ctypes.byref(n), None, None))
+        return int(n.value)
+
+    def reset(self) -> None:
+        """Drop the rows; the codebook (and ``is_trained``) stay."""
+        _n.check(_n.lib.ise_pq_reset(self._h))
+
+    def pq_stats(self) -> dict:
+        """Search batches, scan passes (one per QT(M) queries and 32 results), table builds (one per 64 queries), bytes
+        of code storage allocated on the device (include/ise_knn.h, ise_pq_stats)."""
+        return _counters(_n.lib.ise_pq_stats, self._h, ("search_batches", "scan_passes", "table_builds", "code_bytes"))
+
+    # -- build side
+    def train(self, x) -> None:
+        """A no-op when trained.  Otherwise one ``Kmeans(dsub, 256)`` per sub-quantiser on its columns of ``x`` (at most
+        ``256 * 256`` rows, drawn with a generator seeded by ``cp.seed``), ``niter`` and ``seed`` from ``self.cp`` -- L2
+        k-means for inner-product indexes too, as in Faiss.  ``cp.niter`` defaults to 25, Faiss's default for a product
+        quantiser's clustering as restated from memory: unpinned, like the seeding of ``Kmeans`` itself."""
+        if self.is_trained:
+            return
+        x = _as_rows(x, self.d)
+        if x.shape[0] < 256:
+            raise RuntimeError(f"{x.shape[0]} training rows for 256 centroids per sub-quantiser")
+        if x.shape[0] > self.TRAIN_MAX_ROWS:
+            pick = np.random.default_rng(self.cp.seed).choice(x.shape[0], self.TRAIN_MAX_ROWS, replace=False)
+            x = x[np.sort(pick)]
+        dsub = self.d // self.M
+        c = np.empty((self.M, 256, dsub), dtype=np.float32)
+        for m in range(self.M):
+            km = Kmeans(dsub, 256, niter=self.cp.niter, seed=self.cp.seed)
+            km.train(np.ascontiguousarray(x[:, m * dsub:(m + 1) * dsub]))
+            c[m] = km.centroids
+        self.pq.set_centroids(c)
+
+    def _require_trained(self, what: str) -> None:
+        if not self.is_trained:
+            raise RuntimeError(f"IndexPQ.{what} before train")
+
+    @staticmethod
+    def _check_rows(rc: int) -> None:
+        """The library's answer to rows with a NaN or inf entry is a ValueError here, as ``IndexIVFFlat.add`` gives."""
+        if rc == _n.E_INVALID and b"NaN or inf" in _n.lib.ise_last_error():
+            raise ValueError(_n.lib.ise_last_error().decode("utf-8", "replace"))
+        _n.check(rc)
+
+    def add(self, x) -> None:
+        """Encode and append rows; a row with a NaN or inf entry raises ``ValueError`` and nothing of the call is
+        added."""
+        self._require_trained("add")
+        x = _as_rows(x, self.d)
+        self._check_rows(_n.lib.ise_pq_add_host(self._h, x.ctypes.data, x.shape[0]))
+
+    def add_torch(self, x) -> None:
+        """``add`` from a CUDA float32 tensor on this index's device (no host hop for the rows; the call waits for the
+        encoder's verdict on non-finite entries)."""
+        import torch
+
+        self._require_trained("add")
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
+        x = x.contiguous()
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        with self._lock:
+            self._check_rows(_n.lib.ise_pq_add_device(self._h, x.data_ptr(), x.shape[0], st))
+
+    def _add_codes(self, codes: np.ndarray) -> None:
+        codes = _as_codes(codes, self.M)
+        _n.check(_n.lib.ise_pq_add_codes_host(self._h, codes.ctypes.data, codes.shape[0]))
+
+    # -- readback and codec
+    @property
+    def codes(self) -> np.ndarray:
+        """uint8 (ntotal, M), a copy."""
+        out = np.empty((self.ntotal, self.M), dtype=np.uint8)
+        _n.check(_n.lib.ise_pq_codes_host(self._h, 0, out.shape[0], out.ctypes.data))
+        return out
+
+    def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
+        n = self.ntotal - i0 if n is None else n
+        out = np.empty((n, self.d), dtype=np.float32)
+        _n.check(_n.lib.ise_pq_reconstruct_host(self._h, int(i0), int(n), out.ctypes.data))
+        return out
+
+    def reconstruct(self, i: int) -> np.ndarray:
+        return self.reconstruct_n(int(i), 1)[0]
+
+    def sa_code_size(self) -> int:
+        return self.code_size
+
+    def sa_encode(self, x) -> np.ndarray:
+        """uint8 (n, M): the codes ``add`` would store."""
+        self._require_trained("sa_encode")
+        x = _as_rows(x, self.d)
+        out = np.empty((x.shape[0], self.M), dtype=np.uint8)
+        self._check_rows(_n.lib.ise_pq_encode_host(self._h, x.ctypes.data, x.shape[0], out.ctypes.data))
+        return out
+
+    def sa_decode(self, codes) -> np.ndarray:
+        """float32 (n, d): row i is the concatenation of the centroids its code names."""
+        self._require_trained("sa_decode")
+        codes = _as_codes(codes, self.M)
+        out = np.empty((codes.shape[0], self.d), dtype=np.float32)
+        _n.check(_n.lib.ise_pq_decode_host(self._h, codes.ctypes.data, codes.shape[0], out.ctypes.data))
+        return out
+
+    # -- query side
+    def search(self, x, k: int, params=None):
+        """(D float32 (nq,k), I int64 (nq,k)), fresh arrays."""
+        if params is not None:
+            raise NotImplementedError("search parameters (selectors, polysemous search) are not provided on IndexPQ")
+        self._require_trained("search")
+        x = _as_rows(x, self.d)
+        k = int(k)
+        assert k > 0
+        nq = x.shape[0]
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        if nq:
+            _n.check(_n.lib.ise_pq_search_host(self._h, x.ctypes.data, nq, k, D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def search_torch(self, xq, k: int, params=None):
+        """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out, enqueued on the current torch stream (no
+        host synchronisation)."""
+        import torch
+
+        if params is not None:
+            raise NotImplementedError("search parameters (selectors, polysemous search) are not provided on IndexPQ")
+        self._require_trained("search")
+        k = int(k)
+        xq, D, I, st = _torch_io(xq, torch.float32, self.d, k, torch.float32)
+        nq = xq.shape[0]
+        if nq == 0:
+            return D, I
+        with self._lock:
+            _n.check(_n.lib.ise_pq_search_device(self._h, xq.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(), st))
+        return D, I
+
+    def range_search(self, *a, **kw):
+        raise NotImplementedError("range_search is not provided on IndexPQ")
+
+    def remove_ids(self, *a, **kw):
+        raise NotImplementedError("remove_ids is not provided on IndexPQ")

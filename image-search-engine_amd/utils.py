@@ -77,7 +77,8 @@ def create_search_index(data_array, index_type="cosine"):
     PLACE in the caller's array (quirk 5.9-6); 'l2' -> IndexFlatL2; then add.
     'cell-probe' (IndexIVFPQ) is approximate and outside the scoped path; 'cell-probe-flat' is that branch
     (backend/utils.py:311-325) without the product quantiser: IndexIVFFlat over an L2 coarse quantiser with the
-    reference's 8 centroids and nprobe = 5, trained on the data, then add."""
+    reference's 8 centroids and nprobe = 5, trained on the data, then add.  'pq' is that branch's product quantiser
+    without the lists: IndexPQ with the reference's m = 16 codes of 8 bits, trained on the data, then add."""
     num_features = data_array.shape[1]
     if index_type == "cosine":
         index = faiss.IndexFlatIP(num_features)
@@ -91,6 +92,10 @@ def create_search_index(data_array, index_type="cosine"):
         coarse_quantizer = faiss.IndexFlatL2(num_features)
         index = faiss.IndexIVFFlat(coarse_quantizer, num_features, ncentroids)
         index.nprobe = 5  # find n most similar clusters
+        index.train(data_array)
+    elif index_type == "pq":
+        m = 16  # number of bytes per vector
+        index = faiss.IndexPQ(num_features, m, 8)
         index.train(data_array)
     else:
         raise ValueError(f"unknown index_type {index_type!r}")

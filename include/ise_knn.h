@@ -52,6 +52,7 @@ extern "C" {
 #define ISE_E_NODEVICE -4 /* no usable gfx950 device */
 
 #define ISE_MAX_K 2048 /* largest k accepted by the search entry points */
+#define ISE_PQ_MAX_M 64 /* most sub-quantisers of a product-quantised index (ise_pq_*): what its scan's LDS holds */
 
 typedef struct ise_index ise_index_t;
 
@@ -403,6 +404,60 @@ int ise_ivf_search_device(ise_ivf_t* h, const float* q_dev, int64_t nq, int k, c
 int ise_ivf_search_host(ise_ivf_t* h, const float* q, int64_t nq, int k, const int64_t* probes, int nprobe, float* D,
                         int64_t* I);
 int ise_ivf_stats(ise_ivf_t* h, uint64_t* out3);
+
+/* Product quantisation: faiss.IndexPQ with 8-bit sub-quantisers (csrc/ise_pq.hpp; the compression half of the
+ * reference's "cell-probe" branch, backend/utils.py:311-325, m = 16 codes of 8 bits; composing it with the inverted
+ * lists above is not built).  An ise_pq_t keeps a codebook and, per row, M code bytes -- never the floats.  All the
+ * conventions at the top of this header hold.  Calls on one handle run one at a time; *_device calls on different
+ * streams are ordered one behind the other on the device (one set of workspaces per handle).
+ *   create        d > 0, 1 <= M <= ISE_PQ_MAX_M, d a multiple of M (dsub = d / M), nbits == 8 (256 centroids per
+ *                 sub-quantiser, code_size = M bytes), one of the two metrics; anything else, and a NULL out, is
+ *                 ISE_E_INVALID before the device is touched.  The index is untrained until the centroids are set
+ *   centroids     float32 [M][256][dsub].  set refuses (ISE_E_INVALID) a NaN or inf entry and an index that holds
+ *                 rows (their codes belong to the centroids in place: reset first); it marks the index trained.
+ *                 Every entry point below except reset / info / stats is ISE_E_INVALID on an untrained index
+ *   encode        byte m of a row's code = the j whose centroid C[m][j] is nearest to the row's m-th sub-vector in
+ *                 squared L2 (float32, the direct difference), the lowest j among equals -- for both metrics.  A row
+ *                 with a NaN or inf entry makes the call ISE_E_INVALID ("NaN or inf" in the message).  Both forms
+ *                 block: the flag is read back.  codes: n x M bytes, row-major
+ *   decode        row i = the concatenation of C[m][code[i][m]]
+ *   add           encode and append; a row with a NaN or inf entry makes the call ISE_E_INVALID and NOTHING of that
+ *                 call is added.  Both forms block.  add_codes appends ready-made codes as they are.  A row's id is
+ *                 its insertion number; fewer than 2^32 rows
+ *   codes /       rows [i0, i0 + n) as row-major n x M bytes / decoded n x d floats (the device keeps a row's M bytes
+ *   reconstruct   in a stride of M rounded up to 16)
+ *   search        asymmetric distance computation: score(x, i) = sum over m of T[m][code[i][m]] with T[m][j] =
+ *                 |x_m - C[m][j]|^2 (L2) or the inner product of x_m and C[m][j], each table entry and the sum over
+ *                 ascending m accumulated in float32 from +0 -- the L2 distance / inner product of the query and the
+ *                 DECODED row.  L2 ascending, inner product descending, ties by ascending id; a score enters only if
+ *                 strictly better than +-FLT_MAX (NaN never); unfilled slots are id -1 with +-FLT_MAX.  k in
+ *                 1 .. ISE_MAX_K.  The tables are built per 64 queries; a scan pass serves QT queries and 32 results:
+ *                     QT(M) = 16 for M <= 5, 8 for M <= 15, 4 for M <= 35, 2 for M <= 64
+ *                 (a pass keeps QT x M KiB of tables and QT x 4 KiB of selection buffers in the CU's 160 KiB of LDS),
+ *                 so a call makes ceil(nq / 64) table builds and ceil(nq / QT) x ceil(k / 32) passes; an empty index
+ *                 fills the padding without either.  search_device only enqueues (it waits on the host only where a
+ *                 workspace has to be replaced by a larger one); search_host works through 4096 queries at a time
+ *   stats         out4[0] = search batches (a device call with nq > 0; the host form: one per 4096 queries), out4[1] =
+ *                 scan passes, out4[2] = table builds, out4[3] = bytes of code storage allocated on the device */
+typedef struct ise_pq ise_pq_t;
+int ise_pq_create(ise_pq_t** out, int d, int M, int nbits, int metric, int device);
+int ise_pq_destroy(ise_pq_t* h); /* NULL is a no-op */
+int ise_pq_reset(ise_pq_t* h);   /* drop all rows, keep the codebook */
+int ise_pq_info(const ise_pq_t* h, int* d, int* M, int* nbits, int* metric, int64_t* ntotal, int* is_trained, int* device);
+int ise_pq_set_centroids_host(ise_pq_t* h, const float* c /* [M][256][dsub] */);
+int ise_pq_get_centroids_host(ise_pq_t* h, float* c);
+int ise_pq_encode_host(ise_pq_t* h, const float* x, int64_t n, uint8_t* codes);
+int ise_pq_encode_device(ise_pq_t* h, const float* x_dev, int64_t n, uint8_t* codes_dev, void* stream);
+int ise_pq_decode_host(ise_pq_t* h, const uint8_t* codes, int64_t n, float* x);
+int ise_pq_add_host(ise_pq_t* h, const float* x, int64_t n);
+int ise_pq_add_device(ise_pq_t* h, const float* x_dev, int64_t n, void* stream);
+int ise_pq_add_codes_host(ise_pq_t* h, const uint8_t* codes, int64_t n);
+int ise_pq_codes_host(ise_pq_t* h, int64_t i0, int64_t n, uint8_t* codes);
+int ise_pq_reconstruct_host(ise_pq_t* h, int64_t i0, int64_t n, float* x);
+/* q: nq x d; D: nq x k float32; I: nq x k int64 */
+int ise_pq_search_host(ise_pq_t* h, const float* q, int64_t nq, int k, float* D, int64_t* I);
+int ise_pq_search_device(ise_pq_t* h, const float* q_dev, int64_t nq, int k, float* D_dev, int64_t* I_dev, void* stream);
+int ise_pq_stats(ise_pq_t* h, uint64_t* out4);
 
 /* Shard-local search for the multi-GPU path: writes nq x k
  * packed candidates, sorted best-first, suitable for one all-gather:

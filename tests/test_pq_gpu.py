@@ -1,0 +1,251 @@
+"""GPU tests of IndexPQ (include/ise_knn.h, ise_pq_*; csrc/ise_pq.hpp).  On integer data every comparison is bit for
+bit against a float64 brute force over the decoded rows (tests/pq_ref.py); on real data the project's own tolerance."""
+import numpy as np
+import pytest
+
+from image_search_engine_amd import faiss_compat as faiss
+from tests import pq_ref
+from tests.knn_checks import assert_exact_range, assert_knn_identical, assert_knn_matches, brute_knn, int_data
+from tests.sel_ref import IP, L2, pad_value
+
+pytestmark = pytest.mark.gpu
+
+CHUNKS = [250, 1, 349]  # the three add calls
+SHAPES = [(1, 4, "small", 600), (8, 4, "small", 600), (8, 4, "binary", 600), (12, 2, "signed", 600),
+          (16, 8, "signed", 600), (64, 2, "signed", 600), (16, 128, "signed", 300)]
+
+
+def integer_index(M, dsub, kind, n, metric, seed, nq=41, chunks=None):
+    rng = np.random.default_rng(seed)
+    d = M * dsub
+    C = int_data(kind, rng, M * 256, dsub).reshape(M, 256, dsub)
+    xb, xq = int_data(kind, rng, n, d), int_data(kind, rng, nq, d)
+    index = faiss.IndexPQ(d, M, 8, metric)
+    assert not index.is_trained and index.ntotal == 0 and index.code_size == M and index.sa_code_size() == M
+    index.pq.set_centroids(C)
+    assert index.is_trained
+    if chunks is None:
+        chunks = [c for c in CHUNKS] if n == sum(CHUNKS) else [n]
+    i0 = 0
+    for c in chunks:
+        index.add(xb[i0:i0 + c])
+        i0 += c
+        assert index.ntotal == i0
+    return index, C, xb, xq
+
+
+def passes_of(M, nq, k):
+    return -(-nq // pq_ref.qt_of(M)) * -(-k // 32)
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+@pytest.mark.parametrize("M,dsub,kind,n", SHAPES)
+def test_exact_sweep(M, dsub, kind, n, metric):
+    index, C, xb, xq = integer_index(M, dsub, kind, n, metric, 1000 + 7 * M + dsub)
+    pq = index.pq
+    assert (pq.d, pq.M, pq.nbits, pq.dsub, pq.ksub, pq.code_size) == (M * dsub, M, 8, dsub, 256, M)
+    assert np.array_equal(pq.centroids.view(np.uint32), C.view(np.uint32))
+    codes = pq_ref.encode(xb, C)
+    dec = pq_ref.decode(codes, C)
+    got = index.codes
+    assert got.dtype == np.uint8 and got.shape == (n, M) and np.array_equal(got, codes)
+    assert np.array_equal(index.sa_encode(xb[:70]), codes[:70]) and np.array_equal(pq.compute_codes(xb[:3]), codes[:3])
+    rec = index.reconstruct_n()
+    assert rec.dtype == np.float32 and np.array_equal(rec.view(np.uint32), dec.view(np.uint32))
+    assert np.array_equal(index.reconstruct(n - 1).view(np.uint32), dec[n - 1].view(np.uint32))
+    assert np.array_equal(index.reconstruct_n(3, 5).view(np.uint32), dec[3:8].view(np.uint32))
+    assert np.array_equal(index.sa_decode(codes[:70]).view(np.uint32), dec[:70].view(np.uint32))
+    assert np.array_equal(pq.decode(codes[:3]).view(np.uint32), dec[:3].view(np.uint32))
+    assert_exact_range(rec, xq)
+    qt = pq_ref.qt_of(M)
+    Dw, Iw = pq_ref.adc_expected(xq, C, codes, 70, metric)  # computed once: smaller nq and k are its corners
+    for nq in sorted({1, 16, 17, 40, qt, qt + 1}):
+        for k in (1, 10, 33, 70):
+            before = index.pq_stats()
+            D, I = index.search(xq[:nq], k)
+            after = index.pq_stats()
+            assert_knn_identical(D, I, Dw[:nq, :k], Iw[:nq, :k], f"nq={nq} k={k}")
+            assert after["search_batches"] - before["search_batches"] == 1
+            assert after["scan_passes"] - before["scan_passes"] == passes_of(M, nq, k)
+            assert after["table_builds"] - before["table_builds"] == -(-nq // 64)
+    assert index.pq_stats()["code_bytes"] >= n * M
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_large_k_and_padding(metric):
+    index, C, xb, xq = integer_index(8, 4, "small", 3000, metric, 77, nq=3)
+    codes = pq_ref.encode(xb, C)
+    assert np.array_equal(index.codes, codes)
+    assert_exact_range(index.reconstruct_n(), xq)
+    before = index.pq_stats()
+    assert_knn_identical(*index.search(xq, 2048), *pq_ref.adc_expected(xq, C, codes, 2048, metric), "k=2048")
+    assert index.pq_stats()["scan_passes"] - before["scan_passes"] == 64
+    # k > ntotal: the tail is padding
+    small, C2, xb2, xq2 = integer_index(8, 4, "small", 50, metric, 78, nq=5)
+    D, I = small.search(xq2, 70)
+    assert_knn_identical(D, I, *pq_ref.adc_expected(xq2, C2, pq_ref.encode(xb2, C2), 70, metric), "k > ntotal")
+    assert (I[:, 50:] == -1).all() and (D[:, 50:] == pad_value(metric)).all()
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+@pytest.mark.parametrize("n", [0, 1, 64, 65])
+def test_tile_edges(n, metric):
+    index, C, xb, xq = integer_index(12, 2, "signed", n, metric, 90 + n, nq=9)
+    codes = pq_ref.encode(xb, C)
+    before = index.pq_stats()
+    for k in (1, 5, 66):
+        assert_knn_identical(*index.search(xq, k), *pq_ref.adc_expected(xq, C, codes, k, metric), f"n={n} k={k}")
+    after = index.pq_stats()
+    assert after["search_batches"] - before["search_batches"] == 3
+    if n == 0:  # an empty index: padding, no table, no pass
+        assert after["scan_passes"] == before["scan_passes"] and after["table_builds"] == before["table_builds"]
+        assert index.codes.shape == (0, 12) and index.reconstruct_n().shape == (0, 24)
+    D, I = index.search(xq[:0], 4)
+    assert D.shape == (0, 4) and I.shape == (0, 4) and D.dtype == np.float32 and I.dtype == np.int64
+    index.reset()
+    assert index.ntotal == 0 and index.is_trained
+    index.add(xb[:1] if n else xq[:1])
+    assert index.ntotal == 1
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_gates(metric):
+    index, C, xb, xq = integer_index(8, 4, "small", 600, metric, 5)
+    bad = xq[:3].copy()
+    bad[1, 5] = np.nan
+    D, I = index.search(bad, 4)
+    assert (I[1] == -1).all() and (D[1] == pad_value(metric)).all() and (I[[0, 2]] >= 0).all()
+    if metric == L2:
+        bad[1, 5] = np.inf
+        D, I = index.search(bad, 4)
+        assert (I[1] == -1).all() and (D[1] == pad_value(L2)).all() and (I[[0, 2]] >= 0).all()
+    for poison in (np.nan, np.inf, -np.inf):
+        block = xb[:130].copy()
+        block[77, 9] = poison
+        with pytest.raises(ValueError):
+            index.add(block)
+        assert index.ntotal == 600
+        with pytest.raises(ValueError):
+            index.sa_encode(block)
+    assert np.array_equal(index.codes, pq_ref.encode(xb, C))  # nothing of the refused calls stayed
+    index.add(xb[:2])
+    assert index.ntotal == 602
+    Cbad = C.copy()
+    Cbad[3, 100, 1] = np.nan
+    fresh = faiss.IndexPQ(32, 8, 8, metric)
+    with pytest.raises(ValueError):
+        fresh.pq.set_centroids(Cbad)
+    assert not fresh.is_trained
+    with pytest.raises(RuntimeError):
+        fresh.search(xq[:1], 1)
+    with pytest.raises(RuntimeError):
+        fresh.add(xb[:1])
+    with pytest.raises(RuntimeError):
+        index.pq.set_centroids(C)  # the index holds rows
+    with pytest.raises(NotImplementedError):
+        index.search(xq[:1], 1, params=faiss.SearchParameters())
+    with pytest.raises(NotImplementedError):
+        faiss.IndexIDMap(fresh)
+
+
+def gaussian(n, d, seed):
+    return np.random.default_rng(seed).standard_normal((n, d)).astype(np.float32)
+
+
+def trained(xb, M, metric, niter):
+    index = faiss.IndexPQ(xb.shape[1], M, 8, metric)
+    assert index.cp.niter == 25
+    index.cp.niter = niter
+    index.train(xb)
+    assert index.is_trained
+    index.train(xb[:10])  # a no-op once trained
+    return index
+
+
+def test_training_and_encoding_on_real_data():
+    n, d, M = 4096, 32, 8
+    dsub = d // M
+    xb = gaussian(n, d, 3)
+    err = {}
+    for niter in (5, 0):
+        index = trained(xb, M, L2, niter)
+        index.add(xb)
+        rec = index.reconstruct_n()
+        err[niter] = float(((xb.astype(np.float64) - rec.astype(np.float64)) ** 2).sum(1).mean())
+        if niter == 5:
+            C, codes = index.pq.centroids, index.codes
+            assert np.array_equal(rec.view(np.uint32), pq_ref.decode(codes, C).view(np.uint32))
+            # every code is a true near-nearest: within the rounding bound of either scoring form
+            for m in range(M):
+                dist = pq_ref.sub_distances(xb, C, m)
+                chosen = dist[np.arange(n), codes[:, m]]
+                xn = np.linalg.norm(xb[:, m * dsub:(m + 1) * dsub].astype(np.float64), axis=1)
+                cn = np.linalg.norm(C[m].astype(np.float64), axis=1).max()
+                bound = 4 * (dsub + 2) * 2.0 ** -24 * (xn + cn) ** 2
+                assert (chosen - dist.min(1) <= bound).all(), f"sub-quantiser {m}"
+    print(f"mean reconstruction error: niter=5 {err[5]:.6f}, niter=0 {err[0]:.6f}")
+    assert err[5] <= err[0] * (1 + 1e-5)
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_search_on_real_data(metric):
+    import torch
+
+    n, d, M, nq, k = 4096, 32, 8, 40, 10
+    xb, xq = gaussian(n, d, 3), gaussian(nq, d, 4)
+    index = trained(xb, M, metric, 5)
+    index.add(xb)
+    rec = index.reconstruct_n()
+    D, I = index.search(xq, k)
+    Dw, Iw = brute_knn(rec, xq, k, metric)
+    assert_knn_matches(D, I, Dw, Iw, rec, xq, metric)
+    # the torch forms give the bits of the host forms
+    dev = torch.device("cuda", index.device)
+    Dt, It = index.search_torch(torch.from_numpy(xq).to(dev), k)
+    assert_knn_identical(Dt.cpu().numpy(), It.cpu().numpy(), D, I, "search_torch")
+    twin = faiss.IndexPQ(d, M, 8, metric)
+    twin.pq.set_centroids(index.pq.centroids)
+    twin.add_torch(torch.from_numpy(xb[:1000]).to(dev))
+    twin.add_torch(torch.from_numpy(xb[1000:]).to(dev))
+    assert twin.ntotal == n and np.array_equal(twin.codes, index.codes)
+    with pytest.raises(ValueError):
+        twin.add_torch(torch.full((3, d), float("nan"), device=dev))
+    assert twin.ntotal == n
+    assert_knn_identical(*twin.search(xq, k), D, I, "add_torch")
+    Dz, Iz = index.search_torch(torch.empty((0, d), device=dev), 3)
+    assert Dz.shape == (0, 3) and Iz.shape == (0, 3)
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_write_and_read_index(metric, tmp_path):
+    index, C, xb, xq = integer_index(12, 2, "signed", 600, metric, 31)
+    path = str(tmp_path / "pq.index")
+    faiss.write_index(index, path)
+    back = faiss.read_index(path)
+    assert isinstance(back, faiss.IndexPQ) and back.is_trained and back.ntotal == 600
+    assert (back.d, back.M, back.metric_type) == (24, 12, metric)
+    assert np.array_equal(back.pq.centroids.view(np.uint32), C.view(np.uint32))
+    assert np.array_equal(back.codes, index.codes)
+    for k in (1, 40):
+        assert_knn_identical(*back.search(xq, k), *index.search(xq, k), f"k={k}")
+    empty = faiss.IndexPQ(24, 12, 8, metric)
+    empty.pq.set_centroids(C)
+    faiss.write_index(empty, path)
+    back = faiss.read_index(path)
+    assert isinstance(back, faiss.IndexPQ) and back.is_trained and back.ntotal == 0
+
+
+def test_create_search_index():
+    from image_search_engine_amd.utils import create_search_index
+
+    x = gaussian(512, 64, 8)
+    index = create_search_index(x, "pq")
+    assert isinstance(index, faiss.IndexPQ) and index.is_trained and index.ntotal == 512
+    assert (index.M, index.code_size, index.pq.nbits, index.metric_type) == (16, 16, 8, L2)
+    flat = faiss.IndexFlatL2(64)
+    flat.add(index.reconstruct_n())
+    top = index.search(x[:5], 1)[1][:, 0]
+    near = flat.search(x[:5], 3)[1]
+    assert all(top[i] in near[i] for i in range(5))
+    with pytest.raises(RuntimeError):
+        create_search_index(gaussian(100, 64, 9), "pq")  # fewer than 256 training rows
