@@ -83,6 +83,11 @@ PROTOTYPES = [
     ("ise_index_search_sel_host", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
     ("ise_index_range_search_sel_host", _int, [_vp, _vp, _i64, ctypes.c_float, _vp, ctypes.POINTER(_vp)]),
     ("ise_index_sel_stats", _int, [_vp, _u64p]),
+    ("ise_index_search_subset_device", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp]),
+    ("ise_index_search_subset_host", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp]),
+    ("ise_index_distance_subset_device", _int, [_vp, _vp, _i64, _vp, _int, _vp, _vp]),
+    ("ise_index_distance_subset_host", _int, [_vp, _vp, _i64, _vp, _int, _vp]),
+    ("ise_index_subset_stats", _int, [_vp, _u64p]),
     ("ise_binary_index_create", _int, [ctypes.POINTER(_vp), _int, _int]),
     ("ise_binary_index_destroy", _int, [_vp]),
     ("ise_binary_index_reset", _int, [_vp]),

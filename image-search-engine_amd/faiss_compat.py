@@ -44,6 +44,14 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          ``decode``), ``write_index`` / ``read_index`` ("IxPq"); the compression half of
                                          the reference's "cell-probe" index (backend/utils.py:311-325), which itself
                                          (IndexIVFPQ) is still not provided
+    IndexRefineFlat(base_index)          Faiss's exact re-ranking of an approximate index: ``search`` asks ``base_index`` (an
+                                         ``IndexPQ``, an ``IndexIVFFlat`` or an ``IndexFlat`` of either storage) for
+                                         ``k * k_factor`` labels and returns the k best of them by their exact distance to
+                                         float32 rows kept beside it (csrc/ise_subset.hpp: a gather-and-score pass spread
+                                         over the device, then one sort per query); ``IndexRefine(base, refine_index)``,
+                                         ``IndexRefineSearchParameters(k_factor=, base_index_params=)``,
+                                         ``IndexFlat.search_subset`` / ``compute_distance_subset`` (the pass on its own),
+                                         ``write_index`` / ``read_index`` ("IxRF"); never called by the reference
     write_index_binary / read_index_binary   Faiss's names for IndexBinaryFlat ("IBxF") and IndexBinaryIDMap ("IBMp") files
 
 All arithmetic runs on the MI355X through ``include/ise_knn.h``; there is no
@@ -253,6 +261,18 @@ def _params_sel(params):
     if not isinstance(params, SearchParameters):
         raise TypeError(f"params must be a SearchParameters, not {type(params).__name__}")
     return params.sel
+
+
+class IndexRefineSearchParameters(SearchParameters):
+    """faiss.IndexRefineSearchParameters: ``k_factor`` replaces the index's own for one ``IndexRefine.search`` call,
+    ``base_index_params`` goes to the base index's ``search``."""
+
+    def __init__(self, k_factor: float = 1.0, base_index_params=None):
+        super().__init__()
+        if not float(k_factor) >= 1.0:
+            raise ValueError(f"k_factor must be >= 1, got {k_factor!r}")
+        self.k_factor = float(k_factor)
+        self.base_index_params = base_index_params
 
 
 def _bitmap_words(members: np.ndarray) -> np.ndarray:
@@ -629,6 +649,75 @@ class IndexFlat(_RemovableIndex):
                                                     I.data_ptr(), st))
         return D, I
 
+    # -- subset scoring (include/ise_knn.h, ise_index_search_subset_* / ise_index_distance_subset_*)
+    @staticmethod
+    def _subset_ids(ids, nq: int) -> np.ndarray:
+        ids = np.ascontiguousarray(np.asarray(ids), dtype=np.int64)
+        assert ids.ndim == 2 and ids.shape[0] == nq, f"ids are (nq, kc) = ({nq}, kc), got {ids.shape}"
+        return ids
+
+    def search_subset(self, x, k: int, ids):
+        """The exact k best among the rows ``ids[q]`` names for query q -> (D float32 (nq,k), I int64 (nq,k)), with the
+        D bits ``search`` reports for the same (query, row) pair.  ``ids``: int64 (nq, kc), kc <= 2048; entries outside
+        [0, ntotal) (Faiss's -1 padding) are ignored, an id named twice counts once.  Float32 storage only."""
+        x = _as_rows(x, self.d)
+        k = int(k)
+        nq = x.shape[0]
+        ids = self._subset_ids(ids, nq)
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        _n.check(_n.lib.ise_index_search_subset_host(self._h, x.ctypes.data, nq, k, ids.ctypes.data, ids.shape[1],
+                                                     D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def search_subset_torch(self, xq, k: int, ids):
+        """``search_subset`` on CUDA tensors (``ids`` int64 (nq, kc)), enqueued on the current torch stream (no host
+        synchronisation)."""
+        import torch
+
+        k = int(k)
+        xq, D, I, st = _torch_io(xq, torch.float32, self.d, k, torch.float32)
+        nq = xq.shape[0]
+        assert ids.is_cuda and ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[0] == nq
+        ids = ids.contiguous()
+        with self._lock:
+            _n.check(_n.lib.ise_index_search_subset_device(self._h, xq.data_ptr(), nq, k, ids.data_ptr(), ids.shape[1],
+                                                           D.data_ptr(), I.data_ptr(), st))
+        return D, I
+
+    def compute_distance_subset(self, x, ids) -> np.ndarray:
+        """Faiss's ``compute_distance_subset``: float32 shaped like ``ids``, entry (q, j) the score of query q and row
+        ``ids[q, j]`` as ``search`` reports it (a NaN stays a NaN); +FLT_MAX (L2) / -FLT_MAX (inner product) for an
+        entry outside [0, ntotal)."""
+        x = _as_rows(x, self.d)
+        nq = x.shape[0]
+        ids = self._subset_ids(ids, nq)
+        out = np.empty(ids.shape, dtype=np.float32)
+        _n.check(_n.lib.ise_index_distance_subset_host(self._h, x.ctypes.data, nq, ids.ctypes.data, ids.shape[1],
+                                                       out.ctypes.data))
+        return out
+
+    def compute_distance_subset_torch(self, xq, ids):
+        """``compute_distance_subset`` on CUDA tensors, enqueued on the current torch stream."""
+        import torch
+
+        assert xq.is_cuda and xq.dtype == torch.float32 and xq.dim() == 2 and xq.shape[1] == self.d
+        xq = xq.contiguous()
+        nq = xq.shape[0]
+        assert ids.is_cuda and ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[0] == nq
+        ids = ids.contiguous()
+        out = torch.empty(ids.shape, dtype=torch.float32, device=xq.device)
+        st = torch.cuda.current_stream(xq.device).cuda_stream
+        with self._lock:
+            _n.check(_n.lib.ise_index_distance_subset_device(self._h, xq.data_ptr(), nq, ids.data_ptr(), ids.shape[1],
+                                                             out.data_ptr(), st))
+        return out
+
+    def subset_stats(self) -> dict:
+        """Subset batches, score launches, candidate entries inside [0, ntotal) that were scored (include/ise_knn.h,
+        ise_index_subset_stats).  Waits for the device."""
+        return _counters(_n.lib.ise_index_subset_stats, self._h, ("subset_batches", "score_launches", "rows_scored"))
+
     # -- allocation-free forms for latency-critical loops (bench.py, sharded search): the caller owns
     # every buffer and names the stream; nothing is checked beyond what the C ABI checks
     def search_into(self, xq, k: int, D, I, stream: int) -> None:
@@ -780,6 +869,8 @@ class IndexIDMap(_IDMapBase):
             raise NotImplementedError("IndexIDMap over an IndexIVFFlat is not provided")
         if isinstance(index, IndexPQ):
             raise NotImplementedError("IndexIDMap over an IndexPQ is not provided")
+        if isinstance(index, IndexRefine):
+            raise NotImplementedError("IndexIDMap over an IndexRefine is not provided")
         super().__init__(index)
 
     metric_type = property(lambda self: self.index.metric_type)
@@ -962,9 +1053,101 @@ def parse_pq(buf: bytes):
     return d, M, nbits, metric, centroids, codes
 
 
+# IndexRefineFlat [upstream-faiss index_write.cpp, restated from memory of the published format and UNPINNED like the
+# layouts above: there is no sample file]:
+#   fourcc "IxRF"; the index header (d, ntotal, 1<<20, 1<<20, is_trained, metric_type); the base index as its own file
+#   image; the refine index as an "IxF2" / "IxFI" image; float32 k_factor.
+_FOURCC_REFINE = b"IxRF"
+_TRUNCATED_REFINE = "truncated IndexRefineFlat file"
+
+
+def _flat_image_size(buf: bytes, off: int) -> int:
+    """Bytes of the flat-index image that starts at ``buf[off:]`` (``parse_flat`` reads a whole buffer)."""
+    if len(buf) < off + _HDR.size + 8:
+        raise RuntimeError(_TRUNCATED_REFINE)
+    (count,) = struct.unpack_from("<Q", buf, off + _HDR.size)
+    return _HDR.size + 8 + 4 * count
+
+
+def _pq_image_size(buf: bytes, off: int) -> int:
+    """Bytes of the IndexPQ image that starts at ``buf[off:]`` (``parse_pq`` reads a whole buffer)."""
+    at = off + _HDR.size + _PQ_DIMS.size
+    if len(buf) < at + 8:
+        raise RuntimeError(_TRUNCATED_REFINE)
+    (count,) = struct.unpack_from("<Q", buf, at)
+    at += 8 + 4 * count
+    if len(buf) < at + 8:
+        raise RuntimeError(_TRUNCATED_REFINE)
+    (ncodes,) = struct.unpack_from("<Q", buf, at)
+    return at + 8 + ncodes + _PQ_TAIL.size - off
+
+
+def _sub_image(buf: bytes, off: int):
+    """-> (kind "flat" | "pq", the sub-index image at ``buf[off:]`` cut to its own length)."""
+    if len(buf) < off + 4:
+        raise RuntimeError(_TRUNCATED_REFINE)
+    fourcc = bytes(buf[off:off + 4])
+    if fourcc in (b"IxF2", b"IxFI"):
+        kind, size = "flat", _flat_image_size(buf, off)
+    elif fourcc == _FOURCC_PQ:
+        kind, size = "pq", _pq_image_size(buf, off)
+    else:
+        raise RuntimeError(f"unsupported sub-index type {fourcc!r} in an IndexRefineFlat file")
+    if len(buf) < off + size:
+        raise RuntimeError(_TRUNCATED_REFINE)
+    return kind, buf[off:off + size]
+
+
+def serialize_refine(base_image: bytes, d: int, metric: int, xb: np.ndarray, k_factor: float) -> bytes:
+    """``base_image``: the base index as ``serialize_flat`` or ``serialize_pq`` writes it; ``xb`` float32 (n, d): the
+    refine index's rows."""
+    n = xb.shape[0] if np.size(xb) else 0
+    head = _HDR.pack(_FOURCC_REFINE, int(d), n, 1 << 20, 1 << 20, 1, int(metric))
+    return head + bytes(base_image) + serialize_flat(int(d), int(metric), xb) + struct.pack("<f", float(k_factor))
+
+
+def parse_refine(buf: bytes):
+    """-> (d, metric, base_kind "flat" | "pq", base as ``parse_flat`` / ``parse_pq`` return it, xb float32 (n, d),
+    k_factor); raises RuntimeError on a foreign, truncated or inconsistent file."""
+    if len(buf) >= 4 and buf[:4] != _FOURCC_REFINE:
+        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexRefineFlat")
+    if len(buf) < _HDR.size:
+        raise RuntimeError(_TRUNCATED_REFINE)
+    _, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
+    off = _HDR.size
+    kind, image = _sub_image(buf, off)
+    off += len(image)
+    base = parse_flat(image) if kind == "flat" else parse_pq(image)
+    rkind, image = _sub_image(buf, off)
+    off += len(image)
+    if rkind != "flat":
+        raise RuntimeError("corrupt IndexRefineFlat: the refine index is not a flat index")
+    d2, metric2, xb = parse_flat(image)
+    base_n = base[2].shape[0] if kind == "flat" else base[5].shape[0]
+    if d2 != d or base[0] != d or xb.shape[0] != n or base_n != n or metric2 != metric:
+        raise RuntimeError("corrupt IndexRefineFlat: the sub-indexes do not match the header")
+    if len(buf) < off + 4:
+        raise RuntimeError(_TRUNCATED_REFINE)
+    (k_factor,) = struct.unpack_from("<f", buf, off)
+    return d, metric, kind, base, xb, float(k_factor)
+
+
 def write_index(index, path) -> None:
     if isinstance(index, IndexIVFFlat):
         raise NotImplementedError("write_index of an IndexIVFFlat is not provided")
+    if isinstance(index, IndexRefine):
+        base = index.base_index
+        if isinstance(base, IndexPQ):
+            image = serialize_pq(base.d, base.metric_type, base.pq.centroids, base.codes)
+        elif type(base) in (IndexFlat, IndexFlatL2, IndexFlatIP) and base.storage == "f32":
+            image = serialize_flat(base.d, base.metric_type, base.reconstruct_n(0, base.ntotal))
+        else:
+            raise NotImplementedError(f"write_index of an IndexRefine over {type(base).__name__} is not provided "
+                                      "(float32 IndexFlat and IndexPQ bases are)")
+        rf = index.refine_index
+        with open(str(path), "wb") as f:
+            f.write(serialize_refine(image, index.d, index.metric_type, rf.reconstruct_n(0, rf.ntotal), index.k_factor))
+        return
     with open(str(path), "wb") as f:
         if isinstance(index, IndexPQ):
             f.write(serialize_pq(index.d, index.metric_type, index.pq.centroids, index.codes))
@@ -976,10 +1159,27 @@ def write_index(index, path) -> None:
 
 
 def read_index(path, device: int | None = None):
-    """-> IndexFlat, IndexIDMap or IndexPQ, as the file was written."""
+    """-> IndexFlat, IndexIDMap, IndexPQ or IndexRefineFlat, as the file was written."""
     with open(str(path), "rb") as f:
         buf = f.read()
     ids = None
+    if buf[:4] == _FOURCC_REFINE:
+        d, metric, kind, base_parts, xb, k_factor = parse_refine(buf)
+        if kind == "pq":
+            _, M, nbits, bmetric, centroids, codes = base_parts
+            base = IndexPQ(d, M, nbits, bmetric, device)
+            base.pq.set_centroids(centroids)
+        else:
+            base = IndexFlat(d, base_parts[1], device)
+        index = IndexRefineFlat(base)
+        index.k_factor = k_factor
+        if xb.shape[0]:  # each side as stored: nothing is encoded again
+            if kind == "pq":
+                base._add_codes(codes)
+            else:
+                base.add(base_parts[2])
+            index.refine_index.add(xb)
+        return index
     if buf[:4] == _FOURCC_PQ:
         d, M, nbits, metric, centroids, codes = parse_pq(buf)
         index = IndexPQ(d, M, nbits, metric, device)
@@ -1724,3 +1924,114 @@ class IndexPQ(_IndexHandle):
 
     def remove_ids(self, *a, **kw):
         raise NotImplementedError("remove_ids is not provided on IndexPQ")
+
+
+# ---------------------------------------------------------------- exact re-ranking (faiss.IndexRefine / IndexRefineFlat)
+class IndexRefine:
+    """faiss.IndexRefine(base_index, refine_index): ``search`` asks ``base_index`` -- an ``IndexFlat`` of either storage,
+    an ``IndexPQ`` or an ``IndexIVFFlat`` -- for ``int(k * k_factor)`` labels and returns the k best of them by the exact
+    score ``refine_index`` (a float32 ``IndexFlat`` that holds the same rows) computes: D has the bits
+    ``refine_index.search`` reports for the same (query, row) pair, ties go by ascending id, unfilled slots are
+    -1 / +-FLT_MAX; -1 labels of the base are ignored.  With ``k * k_factor >= ntotal`` the result is
+    ``refine_index.search`` itself.  ``k_factor`` defaults to 1 as in Faiss: the base's own id set in exact order.
+
+    The re-ranking is one gather-and-score pass over the candidate rows and one sort per query on the device
+    (``IndexFlat.search_subset``, csrc/ise_subset.hpp).  Not provided (they raise
+    ``NotImplementedError``): ``range_search``, ``remove_ids`` and ``IndexIDMap`` over this type."""
+
+    def __init__(self, base_index, refine_index):
+        assert isinstance(base_index, (IndexFlat, IndexPQ, IndexIVFFlat)), \
+            "the base index is an IndexFlat, an IndexPQ or an IndexIVFFlat"
+        assert base_index.ntotal == 0, f"{type(self).__name__} wraps an empty index (Faiss: index is empty on input)"
+        assert isinstance(refine_index, IndexFlat) and refine_index.storage == "f32", \
+            "the refine index is a float32 IndexFlat"
+        assert refine_index.d == base_index.d, f"dimension mismatch: base d={base_index.d}, refine d={refine_index.d}"
+        assert refine_index.metric_type == base_index.metric_type, "the two indexes have different metrics"
+        assert refine_index.device == base_index.device, "the two indexes live on different devices"
+        assert refine_index.ntotal == base_index.ntotal, "the two indexes hold different numbers of rows"
+        self.base_index = base_index
+        self.refine_index = refine_index
+        self.k_factor = 1.0
+        self.d = base_index.d
+        self.metric_type = base_index.metric_type
+        self.device = base_index.device
+
+    is_trained = property(lambda self: self.base_index.is_trained)
+    ntotal = property(lambda self: self.refine_index.ntotal)
+
+    # -- build side
+    def train(self, x) -> None:
+        if hasattr(self.base_index, "train"):  # an IndexFlat has nothing to train
+            self.base_index.train(x)
+
+    def add(self, x) -> None:
+        """To the base first, then to the refine index: if the base refuses the rows (a NaN row on an ``IndexPQ`` base
+        raises ``ValueError``) nothing is added anywhere."""
+        x = _as_rows(x, self.d)
+        self.base_index.add(x)
+        self.refine_index.add(x)
+
+    def add_torch(self, x) -> None:
+        self.base_index.add_torch(x)
+        self.refine_index.add_torch(x)
+
+    def reset(self) -> None:
+        self.base_index.reset()
+        self.refine_index.reset()
+
+    def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
+        return self.refine_index.reconstruct_n(i0, n)
+
+    def reconstruct(self, i: int) -> np.ndarray:
+        return self.refine_index.reconstruct_n(int(i), 1)[0]
+
+    # -- query side
+    def _plan(self, k: int, params):
+        """-> (k_base, the base index's params) of one search call, after the checks both forms share."""
+        k_factor, base_params = self.k_factor, None
+        if params is not None:
+            if not isinstance(params, IndexRefineSearchParameters):
+                raise TypeError(f"params must be an IndexRefineSearchParameters, not {type(params).__name__}")
+            k_factor, base_params = params.k_factor, params.base_index_params
+        if not float(k_factor) >= 1.0:
+            raise ValueError(f"k_factor must be >= 1, got {k_factor!r}")
+        k_base = int(k * k_factor)
+        if k_base > _n.MAX_K:
+            raise ValueError(f"k * k_factor = {k_base} candidates per query: at most {_n.MAX_K}")
+        if self.base_index.ntotal != self.refine_index.ntotal:
+            raise RuntimeError(f"the base index holds {self.base_index.ntotal} rows, the refine index "
+                               f"{self.refine_index.ntotal}: rows were added to one of them alone")
+        return k_base, base_params
+
+    def search(self, x, k: int, params=None):
+        """(D float32 (nq,k), I int64 (nq,k)), fresh arrays.  ``params=IndexRefineSearchParameters(k_factor=...,
+        base_index_params=...)`` replaces ``self.k_factor`` for this call."""
+        k = int(k)
+        assert k > 0
+        k_base, base_params = self._plan(k, params)
+        x = _as_rows(x, self.d)
+        labels = self.base_index.search(x, k_base, params=base_params)[1]
+        return self.refine_index.search_subset(x, k, labels)
+
+    def search_torch(self, xq, k: int, params=None):
+        """Device-resident search: the base index's ``search_torch`` and the re-ranking are enqueued on the current
+        torch stream; this method makes no host synchronisation of its own."""
+        k = int(k)
+        assert k > 0
+        k_base, base_params = self._plan(k, params)
+        labels = self.base_index.search_torch(xq, k_base, params=base_params)[1]
+        return self.refine_index.search_subset_torch(xq, k, labels)
+
+    def range_search(self, *a, **kw):
+        raise NotImplementedError("range_search is not provided on IndexRefine")
+
+    def remove_ids(self, *a, **kw):
+        raise NotImplementedError("remove_ids is not provided on IndexRefine")
+
+
+class IndexRefineFlat(IndexRefine):
+    """faiss.IndexRefineFlat(base_index): ``IndexRefine`` with a float32 ``IndexFlat`` of its own, of the base's ``d``
+    and metric and on the base's device."""
+
+    def __init__(self, base_index):
+        super().__init__(base_index, IndexFlat(base_index.d, base_index.metric_type, device=base_index.device))

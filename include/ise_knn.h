@@ -257,6 +257,44 @@ int ise_index_range_search_sel_host(ise_index_t* h, const float* q, int64_t nq, 
                                     ise_range_result_t** out);
 int ise_index_sel_stats(ise_index_t* h, uint64_t* out3);
 
+/* Subset scoring on the flat float32 index (csrc/ise_subset.hpp): the exact scores of a PER-QUERY LIST of row ids and
+ * the k best of them -- what faiss.IndexRefineFlat does with the labels of its base index, and Faiss's
+ * compute_distance_subset (faiss_compat.IndexRefineFlat; the reference never refines: its "cell-probe" index,
+ * backend/utils.py:311-325, returns the product quantiser's order as it is).  All the conventions at the top of this
+ * header hold (0 / ISE_E_* returns, *_host blocks, *_device only enqueues on the given stream; it waits on the host only
+ * where the key workspace has to be replaced by a larger one).  cand: nq x kc int64 row ids.
+ *   candidates       an entry that is -1 or otherwise outside [0, ntotal) is ignored; an id named twice in a row of
+ *                    cand delivers its row once
+ *   search_subset    the exact k best among the query's candidate rows: D has the bits ise_index_search_* reports for
+ *                    the same (query, row) pair -- float32 L2: the direct-difference value of exact_l2_rows
+ *                    (csrc/ise_exact.hpp); inner product: the scan's two-chain MFMA dot product (range_tile_dots,
+ *                    csrc/ise_range.hpp), the k-steps in the same order, lane (c, g) reading row cand[c] where the scan
+ *                    reads row 16 tile + c.  L2 ascending, inner product descending, ties by ascending id; a score
+ *                    enters only if it is strictly better than +-FLT_MAX (NaN never); unfilled slots are id -1 with
+ *                    +-FLT_MAX.  k in 1 .. ISE_MAX_K and may exceed kc
+ *   distance_subset  dist[q][j] = the same value for candidate j, in candidate order: the raw value, so a NaN stays a
+ *                    NaN; for an ignored entry +FLT_MAX (L2) / -FLT_MAX (inner product).  Faiss's
+ *                    compute_distance_subset, with invalid entries given a defined value
+ *   limits           kc in 1 .. ISE_MAX_K; anything else, NULL buffers and a handle with bf16 storage are ISE_E_INVALID
+ *   empty cases      nq = 0 returns at once; an empty index fills the padding without a score launch
+ *   work             per 4096 queries one score launch spread over the device by candidate (a wave per 4 rows for L2,
+ *                    per tile of 16 gathered rows for inner product; keys ord(score) << 32 | id into a
+ *                    [nq][pow2(kc)] workspace) and one select launch (a block per query sorts the keys, drops adjacent
+ *                    duplicates, writes k); distance_subset makes the score launch only.  One key workspace per handle:
+ *                    calls on different streams are ordered one behind the other on the device.  The host forms work
+ *                    through 4096 queries at a time
+ *   stats            out3[0] = batches (device calls with nq > 0; the host forms: one per 4096 queries), out3[1] =
+ *                    score launches, out3[2] = candidate entries inside [0, ntotal) that were scored (counted on the
+ *                    device; the call waits for the device) */
+int ise_index_search_subset_device(ise_index_t* h, const float* q_dev, int64_t nq, int k, const int64_t* cand_dev, int kc,
+                                   float* D_dev, int64_t* I_dev, void* stream);
+int ise_index_search_subset_host(ise_index_t* h, const float* q, int64_t nq, int k, const int64_t* cand, int kc, float* D,
+                                 int64_t* I);
+int ise_index_distance_subset_device(ise_index_t* h, const float* q_dev, int64_t nq, const int64_t* cand_dev, int kc,
+                                     float* dist_dev, void* stream);
+int ise_index_distance_subset_host(ise_index_t* h, const float* q, int64_t nq, const int64_t* cand, int kc, float* dist);
+int ise_index_subset_stats(ise_index_t* h, uint64_t* out3);
+
 /* Binary flat index: faiss.IndexBinaryFlat(d_bits) -- exact brute-force kNN and range search over bit codes under
  * the HAMMING distance (csrc/ise_binary_scan.hpp).  The reference's DHASH method keeps 64-bit difference hashes
  * (backend/indexer.py:39-49) and answers a query with a dict lookup that finds bit-identical hashes only
