@@ -116,6 +116,35 @@ def test_reference_agrees_with_the_table_sum(metric):
     assert_knn_identical(*pq_ref.adc_expected(xq, C, codes, k, metric), D, I)
 
 
+@pytest.mark.parametrize("metric", [L2, IP])
+@pytest.mark.parametrize("M", [4, 20])
+def test_table_lookup_reference_agrees_with_the_brute_force(M, metric):
+    """adc_topk(adc_scores(...)), the reference of the long-index GPU tests, gives adc_expected's bits on integer data."""
+    rng = np.random.default_rng(40 + M)
+    dsub, n, nq = 2, 600, 9
+    C = int_data("signed", rng, M * 256, dsub).reshape(M, 256, dsub)
+    xq = int_data("signed", rng, nq, M * dsub)
+    codes = rng.integers(0, 256, (n, M)).astype(np.uint8)
+    codes[[7, 300, 599]] = codes[2]  # one tie group for every query
+    T = pq_ref.adc_tables(xq, C, metric)
+    assert T.dtype == np.float64 and T.shape == (nq, M, 256)
+    scores = pq_ref.adc_scores(xq, C, codes, metric)
+    assert scores.dtype == np.float64 and scores.shape == (nq, n)
+    assert np.array_equal(scores[:, 11], sum(T[:, m, codes[11, m]] for m in range(M)))
+    for k in (1, 33, 70, 600, 650):  # 650: padding behind the 600 rows
+        D, I = pq_ref.adc_topk(scores, k, metric)
+        assert_knn_identical(D, I, *pq_ref.adc_expected(xq, C, codes, k, metric), f"k={k}")
+    # the gate: a NaN and an overflowing score never enter; an infinite inner product enters first
+    s = scores[:1].copy()
+    s[0, 5], s[0, 9] = np.nan, (np.inf if metric == L2 else -np.inf)
+    s[0, 11] = 2.0 ** 128 if metric == L2 else -2.0 ** 128
+    s[0, 13] = 3.4e38 if metric == L2 else np.inf  # below FLT_MAX: enters last | +inf: enters first
+    D, I = pq_ref.adc_topk(s, n, metric)
+    assert (I[0, -3:] == -1).all() and not np.isin([5, 9, 11], I[0]).any()
+    assert (D[0, -3:] == (np.float32(3.4028235e38) if metric == L2 else -np.float32(3.4028235e38))).all()
+    assert I[0, n - 4 if metric == L2 else 0] == 13
+
+
 def test_reference_encode_takes_the_lowest_of_equal_centroids():
     rng = np.random.default_rng(6)
     C = int_data("small", rng, 2 * 256, 3).reshape(2, 256, 3)
