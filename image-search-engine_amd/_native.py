@@ -22,6 +22,8 @@ METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
 MAX_K = 2048
 PQ_MAX_M = 64
+SQ_MAX_D = 2048
+SQ_8BIT, SQ_8BIT_UNIFORM = 0, 2
 STORE_F32, STORE_BF16 = 0, 1
 
 E_INVALID, E_HIP, E_NOMEM, E_NODEVICE = -1, -2, -3, -4
@@ -142,6 +144,24 @@ PROTOTYPES = [
     ("ise_pq_search_host", _int, [_vp, _vp, _i64, _int, _vp, _vp]),
     ("ise_pq_search_device", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
     ("ise_pq_stats", _int, [_vp, _u64p]),
+    ("ise_sq_create", _int, [ctypes.POINTER(_vp), _int, _int, _int, _int]),
+    ("ise_sq_destroy", _int, [_vp]),
+    ("ise_sq_reset", _int, [_vp]),
+    ("ise_sq_info", _int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), _i64p, ctypes.POINTER(_int),
+                           ctypes.POINTER(_int)]),
+    ("ise_sq_set_trained_host", _int, [_vp, _vp]),
+    ("ise_sq_get_trained_host", _int, [_vp, _vp]),
+    ("ise_sq_encode_host", _int, [_vp, _vp, _i64, _vp]),
+    ("ise_sq_encode_device", _int, [_vp, _vp, _i64, _vp, _vp]),
+    ("ise_sq_decode_host", _int, [_vp, _vp, _i64, _vp]),
+    ("ise_sq_add_host", _int, [_vp, _vp, _i64]),
+    ("ise_sq_add_device", _int, [_vp, _vp, _i64, _vp]),
+    ("ise_sq_add_codes_host", _int, [_vp, _vp, _i64]),
+    ("ise_sq_codes_host", _int, [_vp, _i64, _i64, _vp]),
+    ("ise_sq_reconstruct_host", _int, [_vp, _i64, _i64, _vp]),
+    ("ise_sq_search_host", _int, [_vp, _vp, _i64, _int, _vp, _vp]),
+    ("ise_sq_search_device", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
+    ("ise_sq_stats", _int, [_vp, _u64p]),
     ("ise_refresh_env_knobs", _int, []),
     ("ise_comm_precheck", _int, [_int]),
     ("ise_comm_unique_id", _int, [_vp]),

@@ -44,8 +44,16 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          ``decode``), ``write_index`` / ``read_index`` ("IxPq"); the compression half of
                                          the reference's "cell-probe" index (backend/utils.py:311-325), which itself
                                          (IndexIVFPQ) is still not provided
+    IndexScalarQuantizer(d, qtype)       Faiss's scalar-quantised index with ``ScalarQuantizer.QT_8bit`` / ``QT_8bit_uniform``:
+                                         rows kept as one byte per entry (a quarter of float32) between a trained
+                                         per-dimension (or single) minimum and maximum; ``train`` (min / max) / ``add`` /
+                                         ``search`` by a byte-row scan on the matrix cores (csrc/ise_sq.hpp),
+                                         ``reconstruct_n``, ``sa_encode`` / ``sa_decode``, ``index.sq`` (``trained``,
+                                         ``set_trained``, ``compute_codes``, ``decode``), ``write_index`` / ``read_index``
+                                         ("IxSQ"); the other quantiser types raise; never called by the reference
     IndexRefineFlat(base_index)          Faiss's exact re-ranking of an approximate index: ``search`` asks ``base_index`` (an
-                                         ``IndexPQ``, an ``IndexIVFFlat`` or an ``IndexFlat`` of either storage) for
+                                         ``IndexPQ``, an ``IndexScalarQuantizer``, an ``IndexIVFFlat`` or an ``IndexFlat`` of
+                                         either storage) for
                                          ``k * k_factor`` labels and returns the k best of them by their exact distance to
                                          float32 rows kept beside it (csrc/ise_subset.hpp: a gather-and-score pass spread
                                          over the device, then one sort per query); ``IndexRefine(base, refine_index)``,
@@ -869,6 +877,8 @@ class IndexIDMap(_IDMapBase):
             raise NotImplementedError("IndexIDMap over an IndexIVFFlat is not provided")
         if isinstance(index, IndexPQ):
             raise NotImplementedError("IndexIDMap over an IndexPQ is not provided")
+        if isinstance(index, IndexScalarQuantizer):
+            raise NotImplementedError("IndexIDMap over an IndexScalarQuantizer is not provided")
         if isinstance(index, IndexRefine):
             raise NotImplementedError("IndexIDMap over an IndexRefine is not provided")
         super().__init__(index)
@@ -1053,6 +1063,62 @@ def parse_pq(buf: bytes):
     return d, M, nbits, metric, centroids, codes
 
 
+# IndexScalarQuantizer [upstream-faiss index_write.cpp write_index / write_ScalarQuantizer, restated from memory of the
+# published format and UNPINNED like the layouts above: there is no sample file]:
+#   fourcc "IxSQ"; the index header (d, ntotal, 1<<20, 1<<20, is_trained, metric_type); the scalar quantiser: int32
+#   qtype; int32 rangestat; float32 rangestat_arg; uint64 d; uint64 code_size; the trained vector: uint64 count (= 2 d,
+#   or 2 for the uniform type), count float32; then the code vector: uint64 count (= ntotal * code_size), count uint8.
+_FOURCC_SQ = b"IxSQ"
+_SQ_HEAD = struct.Struct("<iifQQ")
+_SQ_QTYPES = (0, 2)  # QT_8bit, QT_8bit_uniform: the types that are readable
+
+
+def serialize_sq(d: int, metric: int, qtype: int, trained, codes, rangestat: int = 0, rangestat_arg: float = 0.0) -> bytes:
+    """``trained`` float32 (2 d,) or (2,) for the uniform type, ``codes`` uint8 (n, d) (any n, also 0)."""
+    d, qtype = int(d), int(qtype)
+    assert qtype in _SQ_QTYPES, "only QT_8bit and QT_8bit_uniform are written"
+    t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
+    assert t.size == (2 if qtype == 2 else 2 * d), "the trained vector is [vmin.., vdiff..]"
+    codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, d)
+    n = codes.shape[0]
+    head = _HDR.pack(_FOURCC_SQ, d, n, 1 << 20, 1 << 20, 1, int(metric))
+    return (head + _SQ_HEAD.pack(qtype, int(rangestat), float(rangestat_arg), d, d) + struct.pack("<Q", t.size) + t.tobytes()
+            + struct.pack("<Q", n * d) + codes.tobytes())
+
+
+def parse_sq(buf: bytes):
+    """-> (d, metric, qtype, rangestat, rangestat_arg, trained float32, codes uint8 (n, d)); raises RuntimeError on a
+    foreign, truncated or miscounted file and on a quantiser type other than the two 8-bit ones."""
+    if len(buf) >= 4 and buf[:4] != _FOURCC_SQ:
+        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexScalarQuantizer")
+    off = _HDR.size
+    if len(buf) < off + _SQ_HEAD.size + 8:
+        raise RuntimeError("truncated IndexScalarQuantizer file")
+    _, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
+    qtype, rangestat, rangestat_arg, d2, code_size = _SQ_HEAD.unpack_from(buf, off)
+    off += _SQ_HEAD.size
+    if qtype not in _SQ_QTYPES:
+        raise RuntimeError(f"unsupported scalar quantiser type {qtype}: only QT_8bit (0) and QT_8bit_uniform (2) are readable")
+    if d <= 0 or d2 != d or code_size != d or n < 0:
+        raise RuntimeError("corrupt IndexScalarQuantizer header")
+    (count,) = struct.unpack_from("<Q", buf, off)
+    off += 8
+    if count != (2 if qtype == 2 else 2 * d):
+        raise RuntimeError("corrupt IndexScalarQuantizer: the trained vector does not hold vmin and vdiff")
+    if len(buf) < off + 4 * count + 8:
+        raise RuntimeError("truncated IndexScalarQuantizer trained vector")
+    trained = np.frombuffer(buf, dtype="<f4", count=count, offset=off).astype(np.float32)
+    off += 4 * count
+    (ncodes,) = struct.unpack_from("<Q", buf, off)
+    off += 8
+    if ncodes != n * d:
+        raise RuntimeError("corrupt IndexScalarQuantizer: the code vector does not hold ntotal * d bytes")
+    if len(buf) < off + ncodes:
+        raise RuntimeError("truncated IndexScalarQuantizer codes")
+    codes = np.frombuffer(buf, dtype=np.uint8, count=ncodes, offset=off).reshape(n, d).copy()
+    return d, metric, qtype, rangestat, float(rangestat_arg), trained, codes
+
+
 # IndexRefineFlat [upstream-faiss index_write.cpp, restated from memory of the published format and UNPINNED like the
 # layouts above: there is no sample file]:
 #   fourcc "IxRF"; the index header (d, ntotal, 1<<20, 1<<20, is_trained, metric_type); the base index as its own file
@@ -1082,8 +1148,21 @@ def _pq_image_size(buf: bytes, off: int) -> int:
     return at + 8 + ncodes + _PQ_TAIL.size - off
 
 
+def _sq_image_size(buf: bytes, off: int) -> int:
+    """Bytes of the IndexScalarQuantizer image that starts at ``buf[off:]`` (``parse_sq`` reads a whole buffer)."""
+    at = off + _HDR.size + _SQ_HEAD.size
+    if len(buf) < at + 8:
+        raise RuntimeError(_TRUNCATED_REFINE)
+    (count,) = struct.unpack_from("<Q", buf, at)
+    at += 8 + 4 * count
+    if len(buf) < at + 8:
+        raise RuntimeError(_TRUNCATED_REFINE)
+    (ncodes,) = struct.unpack_from("<Q", buf, at)
+    return at + 8 + ncodes - off
+
+
 def _sub_image(buf: bytes, off: int):
-    """-> (kind "flat" | "pq", the sub-index image at ``buf[off:]`` cut to its own length)."""
+    """-> (kind "flat" | "pq" | "sq", the sub-index image at ``buf[off:]`` cut to its own length)."""
     if len(buf) < off + 4:
         raise RuntimeError(_TRUNCATED_REFINE)
     fourcc = bytes(buf[off:off + 4])
@@ -1091,6 +1170,8 @@ def _sub_image(buf: bytes, off: int):
         kind, size = "flat", _flat_image_size(buf, off)
     elif fourcc == _FOURCC_PQ:
         kind, size = "pq", _pq_image_size(buf, off)
+    elif fourcc == _FOURCC_SQ:
+        kind, size = "sq", _sq_image_size(buf, off)
     else:
         raise RuntimeError(f"unsupported sub-index type {fourcc!r} in an IndexRefineFlat file")
     if len(buf) < off + size:
@@ -1099,7 +1180,7 @@ def _sub_image(buf: bytes, off: int):
 
 
 def serialize_refine(base_image: bytes, d: int, metric: int, xb: np.ndarray, k_factor: float) -> bytes:
-    """``base_image``: the base index as ``serialize_flat`` or ``serialize_pq`` writes it; ``xb`` float32 (n, d): the
+    """``base_image``: the base index as ``serialize_flat``, ``serialize_pq`` or ``serialize_sq`` writes it; ``xb`` float32 (n, d): the
     refine index's rows."""
     n = xb.shape[0] if np.size(xb) else 0
     head = _HDR.pack(_FOURCC_REFINE, int(d), n, 1 << 20, 1 << 20, 1, int(metric))
@@ -1107,7 +1188,7 @@ def serialize_refine(base_image: bytes, d: int, metric: int, xb: np.ndarray, k_f
 
 
 def parse_refine(buf: bytes):
-    """-> (d, metric, base_kind "flat" | "pq", base as ``parse_flat`` / ``parse_pq`` return it, xb float32 (n, d),
+    """-> (d, metric, base_kind "flat" | "pq" | "sq", base as ``parse_flat`` / ``parse_pq`` / ``parse_sq`` return it, xb float32 (n, d),
     k_factor); raises RuntimeError on a foreign, truncated or inconsistent file."""
     if len(buf) >= 4 and buf[:4] != _FOURCC_REFINE:
         raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexRefineFlat")
@@ -1117,13 +1198,13 @@ def parse_refine(buf: bytes):
     off = _HDR.size
     kind, image = _sub_image(buf, off)
     off += len(image)
-    base = parse_flat(image) if kind == "flat" else parse_pq(image)
+    base = parse_flat(image) if kind == "flat" else parse_pq(image) if kind == "pq" else parse_sq(image)
     rkind, image = _sub_image(buf, off)
     off += len(image)
     if rkind != "flat":
         raise RuntimeError("corrupt IndexRefineFlat: the refine index is not a flat index")
     d2, metric2, xb = parse_flat(image)
-    base_n = base[2].shape[0] if kind == "flat" else base[5].shape[0]
+    base_n = base[{"flat": 2, "pq": 5, "sq": 6}[kind]].shape[0]
     if d2 != d or base[0] != d or xb.shape[0] != n or base_n != n or metric2 != metric:
         raise RuntimeError("corrupt IndexRefineFlat: the sub-indexes do not match the header")
     if len(buf) < off + 4:
@@ -1139,11 +1220,13 @@ def write_index(index, path) -> None:
         base = index.base_index
         if isinstance(base, IndexPQ):
             image = serialize_pq(base.d, base.metric_type, base.pq.centroids, base.codes)
+        elif isinstance(base, IndexScalarQuantizer):
+            image = base._image()
         elif type(base) in (IndexFlat, IndexFlatL2, IndexFlatIP) and base.storage == "f32":
             image = serialize_flat(base.d, base.metric_type, base.reconstruct_n(0, base.ntotal))
         else:
             raise NotImplementedError(f"write_index of an IndexRefine over {type(base).__name__} is not provided "
-                                      "(float32 IndexFlat and IndexPQ bases are)")
+                                      "(float32 IndexFlat, IndexPQ and IndexScalarQuantizer bases are)")
         rf = index.refine_index
         with open(str(path), "wb") as f:
             f.write(serialize_refine(image, index.d, index.metric_type, rf.reconstruct_n(0, rf.ntotal), index.k_factor))
@@ -1151,6 +1234,8 @@ def write_index(index, path) -> None:
     with open(str(path), "wb") as f:
         if isinstance(index, IndexPQ):
             f.write(serialize_pq(index.d, index.metric_type, index.pq.centroids, index.codes))
+        elif isinstance(index, IndexScalarQuantizer):
+            f.write(index._image())
         elif isinstance(index, IndexIDMap):
             sub = index.index
             f.write(serialize_idmap(sub.d, sub.metric_type, sub.reconstruct_n(0, sub.ntotal), index.id_map))
@@ -1159,7 +1244,7 @@ def write_index(index, path) -> None:
 
 
 def read_index(path, device: int | None = None):
-    """-> IndexFlat, IndexIDMap, IndexPQ or IndexRefineFlat, as the file was written."""
+    """-> IndexFlat, IndexIDMap, IndexPQ, IndexScalarQuantizer or IndexRefineFlat, as the file was written."""
     with open(str(path), "rb") as f:
         buf = f.read()
     ids = None
@@ -1169,12 +1254,15 @@ def read_index(path, device: int | None = None):
             _, M, nbits, bmetric, centroids, codes = base_parts
             base = IndexPQ(d, M, nbits, bmetric, device)
             base.pq.set_centroids(centroids)
+        elif kind == "sq":
+            base = IndexScalarQuantizer._from_parts(base_parts, device, add_codes=False)
+            codes = base_parts[6]
         else:
             base = IndexFlat(d, base_parts[1], device)
         index = IndexRefineFlat(base)
         index.k_factor = k_factor
         if xb.shape[0]:  # each side as stored: nothing is encoded again
-            if kind == "pq":
+            if kind in ("pq", "sq"):
                 base._add_codes(codes)
             else:
                 base.add(base_parts[2])
@@ -1186,6 +1274,8 @@ def read_index(path, device: int | None = None):
         index.pq.set_centroids(centroids)
         index._add_codes(codes)  # as stored: nothing is encoded again
         return index
+    if buf[:4] == _FOURCC_SQ:
+        return IndexScalarQuantizer._from_parts(parse_sq(buf), device)  # as stored: nothing is encoded again
     if buf[:4] in (b"IwFl", b"IwF2"):  # Faiss's fourccs of IndexIVFFlat files
         raise NotImplementedError("read_index of an IndexIVFFlat file is not provided")
     if buf[:4] == _FOURCC_IDMAP:
@@ -1926,10 +2016,251 @@ class IndexPQ(_IndexHandle):
         raise NotImplementedError("remove_ids is not provided on IndexPQ")
 
 
+# ---------------------------------------------------------------- scalar quantisation (faiss.IndexScalarQuantizer)
+class ScalarQuantizer:
+    """``index.sq``: the view of an ``IndexScalarQuantizer``'s codec that faiss.ScalarQuantizer gives -- ``d``, ``qtype``,
+    ``code_size``, ``trained`` (a float32 copy: ``[vmin_0.., vdiff_0..]``, or ``[vmin, vdiff]`` for the uniform type),
+    ``rangestat`` / ``rangestat_arg`` (only Faiss's ``RS_minmax`` with argument 0 trains), ``compute_codes`` and
+    ``decode``.  The constants carry Faiss's enum values as restated from memory (unpinned, like the file layouts).
+    ``set_trained`` is an extension, named like ``ProductQuantizer.set_centroids``."""
+
+    QT_8bit, QT_4bit, QT_8bit_uniform, QT_4bit_uniform, QT_fp16, QT_8bit_direct, QT_6bit, QT_bf16, \
+        QT_8bit_direct_signed = range(9)
+    RS_minmax, RS_meanstd, RS_quantiles, RS_optim = range(4)
+    _PROVIDED = (0, 2)
+
+    def __init__(self, index):
+        self._index = index
+        self.d, self.qtype, self.code_size = index.d, index.qtype, index.d
+        self.rangestat, self.rangestat_arg = self.RS_minmax, 0.0
+
+    @property
+    def _trained_size(self) -> int:
+        return 2 if self.qtype == self.QT_8bit_uniform else 2 * self.d
+
+    @property
+    def trained(self) -> np.ndarray:
+        if not self._index.is_trained:
+            return np.zeros(0, dtype=np.float32)
+        out = np.empty(self._trained_size, dtype=np.float32)
+        _n.check(_n.lib.ise_sq_get_trained_host(self._index._h, out.ctypes.data))
+        return out
+
+    def set_trained(self, t) -> None:
+        """float32 ``[vmin.., vdiff..]``, finite, no negative ``vdiff``; refused while the index holds rows (their codes
+        belong to the state in place).  Marks the index trained."""
+        t = np.ascontiguousarray(np.asarray(t), dtype=np.float32).reshape(-1)
+        assert t.size == self._trained_size, f"the trained vector holds {self._trained_size} floats, got {t.size}"
+        if not np.isfinite(t).all():
+            raise ValueError("the trained state has a NaN or inf entry")
+        if (t[t.size // 2:] < 0).any():
+            raise ValueError("the trained state has a negative vdiff")
+        if self._index.ntotal > 0:
+            raise RuntimeError("set_trained on an index that holds rows: reset() first")
+        _n.check(_n.lib.ise_sq_set_trained_host(self._index._h, t.ctypes.data))
+        self._index.is_trained = True
+
+    def compute_codes(self, x) -> np.ndarray:
+        return self._index.sa_encode(x)
+
+    def decode(self, codes) -> np.ndarray:
+        return self._index.sa_decode(codes)
+
+
+class IndexScalarQuantizer(_IndexHandle):
+    """faiss.IndexScalarQuantizer(d, qtype, metric) for ``ScalarQuantizer.QT_8bit`` (a minimum and a range per dimension)
+    and ``QT_8bit_uniform`` (one of each for all): every row is kept as ``d`` bytes, byte j =
+    ``min(255, max(0, floor((x_j - vmin_j) / s_j)))`` with the step ``s_j = vdiff_j / 255`` (0 where the step is 0), all in
+    float32 and for both metrics; it decodes to ``fmaf(c_j + 0.5, s_j, vmin_j)``.  ``search`` scores the query against
+    the DECODED row (``reconstruct_n``): D is their squared L2 distance or inner product in float32, within
+    ``1e-4 * max(1, |D|)`` of the float64 value and exact on integer data; L2 ascending, inner product descending, ties
+    by ascending id, unfilled slots -1 / +-FLT_MAX; a query with a NaN or inf entry gets padding only.
+
+    On the device (include/ise_knn.h, ise_sq_*).  Not provided (they raise ``NotImplementedError``):
+    the other quantiser types, range statistics other than ``RS_minmax`` with argument 0, ``range_search``,
+    ``remove_ids``, ``params=`` and ``IndexIDMap`` over this type."""
+
+    _ABI = "ise_sq"
+
+    def __init__(self, d: int, qtype: int = ScalarQuantizer.QT_8bit, metric: int = METRIC_L2, device: int | None = None):
+        if int(qtype) not in ScalarQuantizer._PROVIDED:
+            raise NotImplementedError(f"IndexScalarQuantizer with qtype = {qtype}: only QT_8bit and QT_8bit_uniform are "
+                                      "provided (IndexFlat(storage=\"bf16\") is the 2-byte route)")
+        self.d, self.qtype = int(d), int(qtype)
+        self.metric_type = int(metric)
+        self.code_size = self.d
+        self.is_trained = False
+        self.device = _default_device() if device is None else int(device)
+        self._h = ctypes.c_void_p()
+        self._lock = threading.Lock()
+        _n.check(_n.lib.ise_sq_create(ctypes.byref(self._h), self.d, self.qtype, self.metric_type, self.device))
+        self.sq = ScalarQuantizer(self)
+
+    @classmethod
+    def _from_parts(cls, parts, device, add_codes: bool = True):
+        """The index a parsed "IxSQ" image describes (``parse_sq``); the stored codes are added as they are."""
+        d, metric, qtype, rangestat, rangestat_arg, trained, codes = parts
+        index = cls(d, qtype, metric, device)
+        index.sq.rangestat, index.sq.rangestat_arg = rangestat, rangestat_arg
+        index.sq.set_trained(trained)
+        if add_codes:
+            index._add_codes(codes)
+        return index
+
+    def _image(self) -> bytes:
+        self._require_trained("write_index")
+        return serialize_sq(self.d, self.metric_type, self.qtype, self.sq.trained, self.codes, self.sq.rangestat,
+                            self.sq.rangestat_arg)
+
+    @property
+    def ntotal(self) -> int:
+        n = ctypes.c_int64(0)
+        _n.check(_n.lib.ise_sq_info(self._h, None, None, None, ctypes.byref(n), None, None))
+        return int(n.value)
+
+    def reset(self) -> None:
+        """Drop the rows; the trained state (and ``is_trained``) stay."""
+        _n.check(_n.lib.ise_sq_reset(self._h))
+
+    def sq_stats(self) -> dict:
+        """Search batches, scan passes (one per QT(d) queries and 32 results), bytes of code storage allocated on the
+        device (include/ise_knn.h, ise_sq_stats)."""
+        return _counters(_n.lib.ise_sq_stats, self._h, ("search_batches", "scan_passes", "code_bytes"))
+
+    # -- build side
+    def train(self, x) -> None:
+        """A no-op when trained.  Otherwise vmin = the minimum and vdiff = maximum - minimum of the training rows, per
+        dimension or (uniform) over everything: Faiss's ``RS_minmax`` with ``rangestat_arg = 0``; any other setting of
+        ``sq.rangestat`` / ``sq.rangestat_arg`` raises ``NotImplementedError``.  A NaN or inf entry raises
+        ``ValueError``."""
+        if self.is_trained:
+            return
+        if self.sq.rangestat != ScalarQuantizer.RS_minmax or float(self.sq.rangestat_arg) != 0.0:
+            raise NotImplementedError("only rangestat = RS_minmax with rangestat_arg = 0 is provided")
+        x = _as_rows(x, self.d)
+        if x.shape[0] == 0:
+            raise RuntimeError("no training rows")
+        if not np.isfinite(x).all():
+            raise ValueError("a training row has a NaN or inf entry")
+        if self.qtype == ScalarQuantizer.QT_8bit_uniform:
+            vmin, vmax = np.float32(x.min()), np.float32(x.max())
+            t = np.array([vmin, vmax - vmin], dtype=np.float32)
+        else:
+            vmin = x.min(axis=0)
+            t = np.concatenate([vmin, x.max(axis=0) - vmin]).astype(np.float32)
+        if not np.isfinite(t).all():
+            raise ValueError("the range of the training rows overflows float32")
+        self.sq.set_trained(t)
+
+    def _require_trained(self, what: str) -> None:
+        if not self.is_trained:
+            raise RuntimeError(f"IndexScalarQuantizer.{what} before train")
+
+    _check_rows = staticmethod(IndexPQ._check_rows)
+
+    def add(self, x) -> None:
+        """Encode and append rows; a row with a NaN or inf entry raises ``ValueError`` and nothing of the call is
+        added."""
+        self._require_trained("add")
+        x = _as_rows(x, self.d)
+        self._check_rows(_n.lib.ise_sq_add_host(self._h, x.ctypes.data, x.shape[0]))
+
+    def add_torch(self, x) -> None:
+        """``add`` from a CUDA float32 tensor on this index's device (no host hop for the rows; the call waits for the
+        encoder's verdict on non-finite entries)."""
+        import torch
+
+        self._require_trained("add")
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
+        x = x.contiguous()
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        with self._lock:
+            self._check_rows(_n.lib.ise_sq_add_device(self._h, x.data_ptr(), x.shape[0], st))
+
+    def _add_codes(self, codes: np.ndarray) -> None:
+        codes = _as_codes(codes, self.d)
+        _n.check(_n.lib.ise_sq_add_codes_host(self._h, codes.ctypes.data, codes.shape[0]))
+
+    # -- readback and codec
+    @property
+    def codes(self) -> np.ndarray:
+        """uint8 (ntotal, d), a copy."""
+        out = np.empty((self.ntotal, self.d), dtype=np.uint8)
+        _n.check(_n.lib.ise_sq_codes_host(self._h, 0, out.shape[0], out.ctypes.data))
+        return out
+
+    def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
+        n = self.ntotal - i0 if n is None else n
+        out = np.empty((n, self.d), dtype=np.float32)
+        _n.check(_n.lib.ise_sq_reconstruct_host(self._h, int(i0), int(n), out.ctypes.data))
+        return out
+
+    def reconstruct(self, i: int) -> np.ndarray:
+        return self.reconstruct_n(int(i), 1)[0]
+
+    def sa_code_size(self) -> int:
+        return self.code_size
+
+    def sa_encode(self, x) -> np.ndarray:
+        """uint8 (n, d): the codes ``add`` would store."""
+        self._require_trained("sa_encode")
+        x = _as_rows(x, self.d)
+        out = np.empty((x.shape[0], self.d), dtype=np.uint8)
+        self._check_rows(_n.lib.ise_sq_encode_host(self._h, x.ctypes.data, x.shape[0], out.ctypes.data))
+        return out
+
+    def sa_decode(self, codes) -> np.ndarray:
+        """float32 (n, d): entry j of row i is ``fmaf(codes[i, j] + 0.5, s_j, vmin_j)``."""
+        self._require_trained("sa_decode")
+        codes = _as_codes(codes, self.d)
+        out = np.empty((codes.shape[0], self.d), dtype=np.float32)
+        _n.check(_n.lib.ise_sq_decode_host(self._h, codes.ctypes.data, codes.shape[0], out.ctypes.data))
+        return out
+
+    # -- query side
+    def search(self, x, k: int, params=None):
+        """(D float32 (nq,k), I int64 (nq,k)), fresh arrays."""
+        if params is not None:
+            raise NotImplementedError("search parameters (selectors) are not provided on IndexScalarQuantizer")
+        self._require_trained("search")
+        x = _as_rows(x, self.d)
+        k = int(k)
+        assert k > 0
+        nq = x.shape[0]
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        if nq:
+            _n.check(_n.lib.ise_sq_search_host(self._h, x.ctypes.data, nq, k, D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def search_torch(self, xq, k: int, params=None):
+        """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out, enqueued on the current torch stream (no
+        host synchronisation)."""
+        import torch
+
+        if params is not None:
+            raise NotImplementedError("search parameters (selectors) are not provided on IndexScalarQuantizer")
+        self._require_trained("search")
+        k = int(k)
+        xq, D, I, st = _torch_io(xq, torch.float32, self.d, k, torch.float32)
+        nq = xq.shape[0]
+        if nq == 0:
+            return D, I
+        with self._lock:
+            _n.check(_n.lib.ise_sq_search_device(self._h, xq.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(), st))
+        return D, I
+
+    def range_search(self, *a, **kw):
+        raise NotImplementedError("range_search is not provided on IndexScalarQuantizer")
+
+    def remove_ids(self, *a, **kw):
+        raise NotImplementedError("remove_ids is not provided on IndexScalarQuantizer")
+
+
 # ---------------------------------------------------------------- exact re-ranking (faiss.IndexRefine / IndexRefineFlat)
 class IndexRefine:
     """faiss.IndexRefine(base_index, refine_index): ``search`` asks ``base_index`` -- an ``IndexFlat`` of either storage,
-    an ``IndexPQ`` or an ``IndexIVFFlat`` -- for ``int(k * k_factor)`` labels and returns the k best of them by the exact
+    an ``IndexPQ``, an ``IndexScalarQuantizer`` or an ``IndexIVFFlat`` -- for ``int(k * k_factor)`` labels and returns the k best of them by the exact
     score ``refine_index`` (a float32 ``IndexFlat`` that holds the same rows) computes: D has the bits
     ``refine_index.search`` reports for the same (query, row) pair, ties go by ascending id, unfilled slots are
     -1 / +-FLT_MAX; -1 labels of the base are ignored.  With ``k * k_factor >= ntotal`` the result is
@@ -1940,8 +2271,8 @@ class IndexRefine:
     ``NotImplementedError``): ``range_search``, ``remove_ids`` and ``IndexIDMap`` over this type."""
 
     def __init__(self, base_index, refine_index):
-        assert isinstance(base_index, (IndexFlat, IndexPQ, IndexIVFFlat)), \
-            "the base index is an IndexFlat, an IndexPQ or an IndexIVFFlat"
+        assert isinstance(base_index, (IndexFlat, IndexPQ, IndexScalarQuantizer, IndexIVFFlat)), \
+            "the base index is an IndexFlat, an IndexPQ, an IndexScalarQuantizer or an IndexIVFFlat"
         assert base_index.ntotal == 0, f"{type(self).__name__} wraps an empty index (Faiss: index is empty on input)"
         assert isinstance(refine_index, IndexFlat) and refine_index.storage == "f32", \
             "the refine index is a float32 IndexFlat"

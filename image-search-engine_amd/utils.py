@@ -79,7 +79,9 @@ def create_search_index(data_array, index_type="cosine"):
     (backend/utils.py:311-325) without the product quantiser: IndexIVFFlat over an L2 coarse quantiser with the
     reference's 8 centroids and nprobe = 5, trained on the data, then add.  'pq' is that branch's product quantiser
     without the lists: IndexPQ with the reference's m = 16 codes of 8 bits, trained on the data, then add.
-    'pq-refine' is that index under IndexRefineFlat: its k * 16 best rows re-ranked by their exact float32 distance."""
+    'pq-refine' is that index under IndexRefineFlat: its k * 16 best rows re-ranked by their exact float32 distance.
+    'sq8' is IndexScalarQuantizer with QT_8bit: one byte per entry between the data's per-dimension minimum and maximum,
+    trained on the data, then add."""
     num_features = data_array.shape[1]
     if index_type == "cosine":
         index = faiss.IndexFlatIP(num_features)
@@ -102,6 +104,9 @@ def create_search_index(data_array, index_type="cosine"):
         index = faiss.IndexRefineFlat(faiss.IndexPQ(num_features, 16, 8))
         # a choice, not a tuned value: the reference's k = 20 then asks the product quantiser for 320 candidates
         index.k_factor = 16
+        index.train(data_array)
+    elif index_type == "sq8":
+        index = faiss.IndexScalarQuantizer(num_features, faiss.ScalarQuantizer.QT_8bit)
         index.train(data_array)
     else:
         raise ValueError(f"unknown index_type {index_type!r}")

@@ -52,6 +52,7 @@ extern "C" {
 #define ISE_E_NODEVICE -4 /* no usable gfx950 device */
 
 #define ISE_MAX_K 2048 /* largest k accepted by the search entry points */
+#define ISE_SQ_MAX_D 2048 /* longest row of a scalar-quantised index (ise_sq_*): what its scan's LDS holds of 8 queries */
 #define ISE_PQ_MAX_M 64 /* most sub-quantisers of a product-quantised index (ise_pq_*): what its scan's LDS holds */
 
 typedef struct ise_index ise_index_t;
@@ -496,6 +497,62 @@ int ise_pq_reconstruct_host(ise_pq_t* h, int64_t i0, int64_t n, float* x);
 int ise_pq_search_host(ise_pq_t* h, const float* q, int64_t nq, int k, float* D, int64_t* I);
 int ise_pq_search_device(ise_pq_t* h, const float* q_dev, int64_t nq, int k, float* D_dev, int64_t* I_dev, void* stream);
 int ise_pq_stats(ise_pq_t* h, uint64_t* out4);
+
+/* Scalar quantisation: faiss.IndexScalarQuantizer with the 8-bit types (csrc/ise_sq.hpp).  An ise_sq_t keeps a
+ * per-dimension (ISE_SQ_8BIT) or a single (ISE_SQ_8BIT_UNIFORM) vmin / vdiff and, per row, d code bytes plus one
+ * float64 -- never the floats.  All the conventions at the top of this header hold; calls, streams and workspaces as
+ * for ise_pq_*.
+ *   create        1 <= d <= ISE_SQ_MAX_D, one of the two types (Faiss's enum values), one of the two metrics;
+ *                 anything else, and a NULL out, is ISE_E_INVALID before the device is touched.  The index is
+ *                 untrained until the trained state is set
+ *   trained       float32 in Faiss's layout: [vmin_0 .. vmin_{d-1}, vdiff_0 .. vdiff_{d-1}], or [vmin, vdiff] for the
+ *                 uniform type.  set refuses (ISE_E_INVALID) a NaN or inf entry, a negative vdiff and an index that
+ *                 holds rows (reset first); it takes the step s_j = vdiff_j / 255.0f (one float32 division) and marks
+ *                 the index trained.  Every entry point below except reset / info / stats is ISE_E_INVALID on an
+ *                 untrained index
+ *   encode        c_j = 0 if s_j == 0, else min(255, max(0, floor((x_j - vmin_j) / s_j))) in float32, for both
+ *                 metrics.  A row with a NaN or inf entry makes the call ISE_E_INVALID ("NaN or inf" in the message).
+ *                 Both forms block: the flag is read back.  codes: n x d bytes, row-major
+ *   decode        y_j = fmaf((float)c_j + 0.5f, s_j, vmin_j)
+ *   add           encode and append; a row with a NaN or inf entry makes the call ISE_E_INVALID and NOTHING of that
+ *                 call is added.  Both forms block.  add_codes appends ready-made codes as they are.  A row's id is
+ *                 its insertion number; fewer than 2^32 rows
+ *   codes /       rows [i0, i0 + n) as row-major n x d bytes / decoded n x d floats (the device keeps a row's d bytes
+ *   reconstruct   in a stride of d rounded up to 64, and one float64 row term beside it)
+ *   search        the squared L2 distance / inner product of the query and the DECODED row in float32, expanded about
+ *                 o_j = vmin_j + s_j / 2 with float64 outer terms (csrc/ise_sq.hpp): within 1e-4 max(1, |score|) of the float64 value, exact
+ *                 where every partial sum is an exactly representable integer, an L2 score never negative, a zero
+ *                 +0, and the bits of a (query, row) pair independent of nq, k and the query's place in the batch.
+ *                 L2 ascending, inner product descending, ties by ascending id; a score enters only if strictly better
+ *                 than +-FLT_MAX (NaN never; a query with a NaN or inf entry gets padding only); unfilled slots are
+ *                 id -1 with +-FLT_MAX.  k in 1 .. ISE_MAX_K.  A scan pass serves QT queries and 32 results, QT = 16
+ *                 for d <= 1472 and 8 above (the CU's 160 KiB of LDS), so a call makes ceil(nq / QT) x ceil(k / 32)
+ *                 passes; an empty index fills the padding without one.  search_device only enqueues (it waits on
+ *                 the host only where a workspace has to be replaced by a larger one); search_host works through 4096
+ *                 queries at a time
+ *   stats         out3[0] = search batches (a device call with nq > 0; the host form: one per 4096 queries), out3[1] =
+ *                 scan passes, out3[2] = bytes of code storage allocated on the device */
+#define ISE_SQ_8BIT 0
+#define ISE_SQ_8BIT_UNIFORM 2
+typedef struct ise_sq ise_sq_t;
+int ise_sq_create(ise_sq_t** out, int d, int qtype, int metric, int device);
+int ise_sq_destroy(ise_sq_t* h); /* NULL is a no-op */
+int ise_sq_reset(ise_sq_t* h);   /* drop all rows, keep the trained state */
+int ise_sq_info(const ise_sq_t* h, int* d, int* qtype, int* metric, int64_t* ntotal, int* is_trained, int* device);
+int ise_sq_set_trained_host(ise_sq_t* h, const float* t /* 2 d floats, or 2 for the uniform type */);
+int ise_sq_get_trained_host(ise_sq_t* h, float* t);
+int ise_sq_encode_host(ise_sq_t* h, const float* x, int64_t n, uint8_t* codes);
+int ise_sq_encode_device(ise_sq_t* h, const float* x_dev, int64_t n, uint8_t* codes_dev, void* stream);
+int ise_sq_decode_host(ise_sq_t* h, const uint8_t* codes, int64_t n, float* x);
+int ise_sq_add_host(ise_sq_t* h, const float* x, int64_t n);
+int ise_sq_add_device(ise_sq_t* h, const float* x_dev, int64_t n, void* stream);
+int ise_sq_add_codes_host(ise_sq_t* h, const uint8_t* codes, int64_t n);
+int ise_sq_codes_host(ise_sq_t* h, int64_t i0, int64_t n, uint8_t* codes);
+int ise_sq_reconstruct_host(ise_sq_t* h, int64_t i0, int64_t n, float* x);
+/* q: nq x d; D: nq x k float32; I: nq x k int64 */
+int ise_sq_search_host(ise_sq_t* h, const float* q, int64_t nq, int k, float* D, int64_t* I);
+int ise_sq_search_device(ise_sq_t* h, const float* q_dev, int64_t nq, int k, float* D_dev, int64_t* I_dev, void* stream);
+int ise_sq_stats(ise_sq_t* h, uint64_t* out3);
 
 /* Shard-local search for the multi-GPU path: writes nq x k
  * packed candidates, sorted best-first, suitable for one all-gather:

@@ -1,0 +1,370 @@
+"""GPU tests of IndexScalarQuantizer (include/ise_knn.h, ise_sq_*; csrc/ise_sq.hpp).  On the integer construction of
+tests/sq_ref.py every comparison is bit for bit against a float64 brute force over the decoded rows; on real data the
+project's own tolerance (tests/knn_checks.py, RTOL)."""
+import numpy as np
+import pytest
+
+from image_search_engine_amd import faiss_compat as faiss
+from tests import sq_ref
+from tests.knn_checks import (assert_exact_range, assert_knn_identical, assert_knn_matches, brute_knn, int_data,
+                              plant_ties)
+from tests.sel_ref import IP, L2, pad_value
+
+pytestmark = pytest.mark.gpu
+
+SQ = faiss.ScalarQuantizer
+CHUNKS = [250, 1, 349]  # the three add calls
+QTYPES = [SQ.QT_8bit, SQ.QT_8bit_uniform]
+
+
+def integer_index(d, qtype, metric, n, seed, nq=41, kind="small", qkind="small", chunks=None, ties=None):
+    rng = np.random.default_rng(seed)
+    t, m, s = sq_ref.integer_trained(rng, d, qtype)
+    xb, base = sq_ref.integer_rows(rng, n, d, m, s, kind)
+    if ties is not None and n:
+        plant_ties(xb, ties[0], ties[1:])
+        plant_ties(base, ties[0], ties[1:])
+    xq = int_data(qkind, rng, nq, d)
+    index = faiss.IndexScalarQuantizer(d, qtype, metric)
+    assert not index.is_trained and index.ntotal == 0 and index.code_size == d and index.sa_code_size() == d
+    assert index.sq.trained.size == 0
+    index.sq.set_trained(t)
+    assert index.is_trained
+    if chunks is None:
+        chunks = list(CHUNKS) if n == sum(CHUNKS) else [n]
+    i0 = 0
+    for c in chunks:
+        index.add(xb[i0:i0 + c])
+        i0 += c
+        assert index.ntotal == i0
+    return index, t, xb, base, xq
+
+
+def check_searches(index, xq, dec, metric, nqs, ks, d):
+    kmax = max(ks)
+    Dw, Iw = sq_ref.expected(xq, dec, kmax, metric)  # computed once: smaller nq and k are its corners
+    for nq in nqs:
+        for k in ks:
+            before = index.sq_stats()
+            D, I = index.search(xq[:nq], k)
+            after = index.sq_stats()
+            assert_knn_identical(D, I, Dw[:nq, :k], Iw[:nq, :k], f"nq={nq} k={k}")
+            assert after["search_batches"] - before["search_batches"] == 1
+            assert after["scan_passes"] - before["scan_passes"] == (sq_ref.passes_of(d, nq, k) if index.ntotal else 0)
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+@pytest.mark.parametrize("qtype", QTYPES)
+@pytest.mark.parametrize("d", [1, 3, 17, 64, 100, 512])
+def test_exact_sweep(d, qtype, metric):
+    n = 600
+    index, t, xb, base, xq = integer_index(d, qtype, metric, n, 1000 + 7 * d + qtype)
+    sq = index.sq
+    assert (sq.d, sq.qtype, sq.code_size, sq.rangestat, sq.rangestat_arg) == (d, qtype, d, SQ.RS_minmax, 0.0)
+    assert np.array_equal(sq.trained.view(np.uint32), t.view(np.uint32))
+    vmin, vdiff = sq_ref.expand(t, d, qtype)
+    codes = sq_ref.encode(xb, vmin, vdiff)
+    dec = sq_ref.decode(codes, vmin, vdiff)
+    assert np.array_equal(codes, base) and np.array_equal(dec, xb)
+    got = index.codes
+    assert got.dtype == np.uint8 and got.shape == (n, d) and np.array_equal(got, codes)
+    assert np.array_equal(index.sa_encode(xb[:70]), codes[:70]) and np.array_equal(sq.compute_codes(xb[:3]), codes[:3])
+    rec = index.reconstruct_n()
+    assert rec.dtype == np.float32 and np.array_equal(rec.view(np.uint32), dec.view(np.uint32))
+    assert np.array_equal(index.reconstruct(n - 1).view(np.uint32), dec[n - 1].view(np.uint32))
+    assert np.array_equal(index.reconstruct_n(3, 5).view(np.uint32), dec[3:8].view(np.uint32))
+    assert np.array_equal(index.sa_decode(codes[:70]).view(np.uint32), dec[:70].view(np.uint32))
+    assert np.array_equal(sq.decode(codes[:3]).view(np.uint32), dec[:3].view(np.uint32))
+    assert_exact_range(rec, xq)
+    check_searches(index, xq, dec, metric, (1, 16, 17, 40), (1, 10, 33, 70), d)
+    assert index.sq_stats()["code_bytes"] >= n * d
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_exact_widest_rows(metric):
+    """d = 2048 (8 queries per pass): "binary" bases and binary queries keep every sum exact."""
+    d, n = 2048, 300
+    assert sq_ref.qt_of(d) == 8
+    index, t, xb, base, xq = integer_index(d, SQ.QT_8bit, metric, n, 2048, nq=18, kind="binary", qkind="binary")
+    assert np.array_equal(index.codes, base)
+    rec = index.reconstruct_n()
+    assert np.array_equal(rec, xb)
+    assert_exact_range(rec, xq)
+    check_searches(index, xq, rec, metric, (1, 8, 9, 17), (1, 33), d)
+    with pytest.raises(RuntimeError):
+        faiss.IndexScalarQuantizer(d + 1, SQ.QT_8bit, metric)
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_large_k_and_padding(metric):
+    index, t, xb, base, xq = integer_index(8, SQ.QT_8bit, metric, 3000, 77, nq=3)
+    before = index.sq_stats()
+    assert_knn_identical(*index.search(xq, 2048), *sq_ref.expected(xq, xb, 2048, metric), "k=2048")
+    assert index.sq_stats()["scan_passes"] - before["scan_passes"] == 64
+    # k > ntotal: the tail is padding
+    small, t2, xb2, base2, xq2 = integer_index(8, SQ.QT_8bit, metric, 50, 78, nq=5)
+    D, I = small.search(xq2, 70)
+    assert_knn_identical(D, I, *sq_ref.expected(xq2, xb2, 70, metric), "k > ntotal")
+    assert (I[:, 50:] == -1).all() and (D[:, 50:] == pad_value(metric)).all()
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65])
+def test_tile_edges(n, metric):
+    d = 24
+    index, t, xb, base, xq = integer_index(d, SQ.QT_8bit, metric, n, 90 + n, nq=9)
+    before = index.sq_stats()
+    for k in (1, 5, 66):
+        assert_knn_identical(*index.search(xq, k), *sq_ref.expected(xq, xb, k, metric), f"n={n} k={k}")
+    after = index.sq_stats()
+    assert after["search_batches"] - before["search_batches"] == 3
+    if n == 0:  # an empty index: padding, no pass
+        assert after["scan_passes"] == before["scan_passes"]
+        assert index.codes.shape == (0, d) and index.reconstruct_n().shape == (0, d)
+    D, I = index.search(xq[:0], 4)
+    assert D.shape == (0, 4) and I.shape == (0, 4) and D.dtype == np.float32 and I.dtype == np.int64
+    index.reset()
+    assert index.ntotal == 0 and index.is_trained
+    assert np.array_equal(index.sq.trained.view(np.uint32), t.view(np.uint32))
+    index.add(xb[:1] if n else xq[:1])
+    assert index.ntotal == 1
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_blocks_and_tie_groups(metric):
+    """Two blocks and a ragged last tile; one tie group that straddles a tile edge, a block edge and the last row."""
+    n = sq_ref.BLOCK_ROWS + sq_ref.TILE_ROWS + 7
+    half = sq_ref.BLOCK_ROWS // 2  # tiles go to the blocks four at a time: rows [256, 512) are the second block's
+    ties = [sq_ref.TILE_ROWS - 1, sq_ref.TILE_ROWS, half - 1, half, sq_ref.BLOCK_ROWS - 1, sq_ref.BLOCK_ROWS, n - 1]
+    index, t, xb, base, xq = integer_index(17, SQ.QT_8bit, metric, n, 55, nq=20, ties=ties)
+    rng = np.random.default_rng(56)
+    xq[:4] = xb[ties[0]] + int_data("signed", rng, 4, 17) * (np.arange(17) < 2)  # queries near the tie group
+    assert_exact_range(xb, xq)
+    for k in (1, 7, 40):
+        D, I = index.search(xq, k)
+        assert_knn_identical(D, I, *sq_ref.expected(xq, xb, k, metric), f"k={k}")
+    if metric == L2:
+        D, I = index.search(xb[ties[:1]], 7)
+        assert I[0].tolist() == sorted(ties) and (D[0] == 0).all() and not np.signbit(D[0]).any()
+
+
+def real_rows(kind, n, d, seed):
+    rng = np.random.default_rng(seed)
+    if kind == "gauss":
+        return (3 + rng.standard_normal((n, d))).astype(np.float32)
+    return rng.random((n, d), dtype=np.float32)
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+@pytest.mark.parametrize("qtype", QTYPES)
+@pytest.mark.parametrize("kind,n,d", [("gauss", 2000, 64), ("uniform", 2000, 64), ("gauss", 1000, 512),
+                                      ("uniform", 1000, 512)])
+def test_real_data(kind, n, d, qtype, metric):
+    nq, k = 40, 10
+    xb, xq = real_rows(kind, n, d, 3), real_rows(kind, nq, d, 4)
+    index = faiss.IndexScalarQuantizer(d, qtype, metric)
+    with pytest.raises(RuntimeError):
+        index.add(xb[:1])
+    with pytest.raises(RuntimeError):
+        index.search(xq[:1], 1)
+    index.train(xb)
+    assert index.is_trained
+    t = index.sq.trained
+    assert np.array_equal(t.view(np.uint32), sq_ref.train_minmax(xb, qtype).view(np.uint32))
+    index.train(xb[:10])  # a no-op once trained
+    assert np.array_equal(index.sq.trained.view(np.uint32), t.view(np.uint32))
+    index.add(xb)
+    vmin, vdiff = sq_ref.expand(t, d, qtype)
+    # codes: the float64 reference's, but for +-1 where its quotient lies within 1e-3 of an integer
+    codes = index.codes
+    t64 = sq_ref.encode_t64(xb, vmin, vdiff)
+    diff = codes.astype(np.int64) - sq_ref.encode(xb, vmin, vdiff, np.float64).astype(np.int64)
+    band = np.abs(t64 - np.rint(t64)) <= 1e-3
+    assert (diff[~band] == 0).all() and (np.abs(diff) <= 1).all()
+    rec = index.reconstruct_n()
+    assert np.array_equal(rec.view(np.uint32), sq_ref.decode(codes, vmin, vdiff).view(np.uint32))
+    s = sq_ref.step_of(vdiff).astype(np.float64)
+    assert (np.abs(rec.astype(np.float64) - xb) <= 0.5 * s[None, :] * (1 + 1e-3)).all()
+    D, I = index.search(xq, k)
+    Dw, Iw = brute_knn(rec, xq, k, metric)
+    err = np.abs(D.astype(np.float64) - Dw) / np.maximum(1.0, np.abs(Dw))
+    print(f"{kind} {n}x{d} qtype={qtype} metric={metric}: largest |D - D64| / max(1, |D64|) = {err.max():.3e}")
+    assert_knn_matches(D, I, Dw, Iw, rec, xq, metric)
+    if metric == L2:
+        assert (D >= 0).all()
+        flat = faiss.IndexFlatL2(d)
+        flat.add(xb)
+        If = flat.search(xq, k)[1]
+        recall = np.mean([len(set(I[q]) & set(If[q])) / k for q in range(nq)])
+        print(f"{kind} {n}x{d} qtype={qtype}: recall@10 against IndexFlatL2 = {recall:.3f}")
+    # the bits of a (query, row) pair do not depend on the batch or on k
+    D1, I1 = index.search(xq[23:24], k)
+    assert_knn_identical(D1, I1, D[23:24], I[23:24], "alone vs position 23 of 40")
+    D3, I3 = index.search(xq[20:27], 3)
+    assert_knn_identical(D3, I3, D[20:27, :3], I[20:27, :3], "another batch and k")
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_nonfinite_and_clamping(metric):
+    import torch
+
+    index, t, xb, base, xq = integer_index(24, SQ.QT_8bit, metric, 600, 5)
+    dev = torch.device("cuda", index.device)
+    bad = xq[:3].copy()
+    bad[1, 5] = np.nan
+    D, I = index.search(bad, 4)
+    assert (I[1] == -1).all() and (D[1] == pad_value(metric)).all() and (I[[0, 2]] >= 0).all()
+    for poison in (np.nan, np.inf, -np.inf):
+        block = xb[:130].copy()
+        block[77, 9] = poison
+        with pytest.raises(ValueError):
+            index.add(block)
+        assert index.ntotal == 600
+        with pytest.raises(ValueError):
+            index.add_torch(torch.from_numpy(block).to(dev))
+        assert index.ntotal == 600
+        with pytest.raises(ValueError):
+            index.sa_encode(block)
+    assert np.array_equal(index.codes, base)  # nothing of the refused calls stayed
+    # rows far outside the trained range clamp to 0 / 255 and are searched as their decoded selves
+    far = xb[:4].copy()
+    far[0], far[1], far[2, ::2], far[3, 1::2] = -1e6, 1e6, 1e30, -1e30
+    index.add(far)
+    assert index.ntotal == 604
+    vmin, vdiff = sq_ref.expand(t, 24, SQ.QT_8bit)
+    want = sq_ref.encode(far, vmin, vdiff)
+    assert (want[0] == 0).all() and (want[1] == 255).all() and (want[2, ::2] == 255).all() and (want[3, 1::2] == 0).all()
+    assert np.array_equal(index.codes[600:], want)
+    rec = index.reconstruct_n()
+    assert np.array_equal(rec[600:].view(np.uint32), sq_ref.decode(want, vmin, vdiff).view(np.uint32))
+    assert_exact_range(rec, xq)
+    for k in (5, 604):
+        assert_knn_identical(*index.search(xq[:7], k), *sq_ref.expected(xq[:7], rec, k, metric), f"clamped rows, k={k}")
+    with pytest.raises(RuntimeError):
+        index.sq.set_trained(t)  # the index holds rows
+    fresh = faiss.IndexScalarQuantizer(24, SQ.QT_8bit, metric)
+    for poisoned, at in ((np.nan, 3), (np.inf, 30), (-1.0, 30)):
+        tb = t.copy()
+        tb[at] = poisoned
+        with pytest.raises(ValueError):
+            fresh.sq.set_trained(tb)
+    assert not fresh.is_trained
+    with pytest.raises(ValueError):
+        fresh.train(bad)
+    fresh.sq.rangestat = SQ.RS_meanstd
+    with pytest.raises(NotImplementedError):
+        fresh.train(xb)
+    fresh.sq.rangestat, fresh.sq.rangestat_arg = SQ.RS_minmax, 0.1
+    with pytest.raises(NotImplementedError):
+        fresh.train(xb)
+    assert not fresh.is_trained
+    with pytest.raises(NotImplementedError):
+        index.search(xq[:1], 1, params=faiss.SearchParameters())
+    with pytest.raises(NotImplementedError):
+        faiss.IndexIDMap(fresh)
+
+
+def test_zero_step_dimensions():
+    """A constant training column: step 0, code 0, decoded to vmin, and scored as such."""
+    rng = np.random.default_rng(12)
+    xb = int_data("small", rng, 200, 10)
+    xb[:, 3], xb[:, 7] = 2.0, -1.0
+    xb[0], xb[1] = 0.0, 15.0
+    xb[:2, 3], xb[:2, 7] = 2.0, -1.0
+    index = faiss.IndexScalarQuantizer(10, SQ.QT_8bit, L2)
+    index.train(xb)
+    vmin, vdiff = sq_ref.expand(index.sq.trained, 10, SQ.QT_8bit)
+    assert vdiff[3] == 0 and vdiff[7] == 0 and (vdiff[[0, 1, 2, 4, 5, 6, 8, 9]] == 15).all()
+    index.add(xb)
+    codes = index.codes
+    assert (codes[:, 3] == 0).all() and (codes[:, 7] == 0).all()
+    rec = index.reconstruct_n()
+    assert (rec[:, 3] == 2.0).all() and (rec[:, 7] == -1.0).all()
+    assert np.array_equal(rec.view(np.uint32), sq_ref.decode(codes, vmin, vdiff).view(np.uint32))
+    xq = int_data("small", rng, 5, 10)
+    D, I = index.search(xq, 10)
+    Dw, Iw = brute_knn(rec, xq, 10, L2)
+    assert_knn_matches(D, I, Dw, Iw, rec, xq, L2)
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_torch_forms(metric):
+    import torch
+
+    index, t, xb, base, xq = integer_index(100, SQ.QT_8bit_uniform, metric, 600, 21)
+    dev = torch.device("cuda", index.device)
+    D, I = index.search(xq, 40)
+    Dt, It = index.search_torch(torch.from_numpy(xq).to(dev), 40)
+    assert_knn_identical(Dt.cpu().numpy(), It.cpu().numpy(), D, I, "search_torch")
+    twin = faiss.IndexScalarQuantizer(100, SQ.QT_8bit_uniform, metric)
+    twin.sq.set_trained(t)
+    twin.add_torch(torch.from_numpy(xb[:250]).to(dev))
+    twin.add_torch(torch.from_numpy(xb[250:]).to(dev))
+    assert twin.ntotal == 600 and np.array_equal(twin.codes, index.codes)
+    assert_knn_identical(*twin.search(xq, 40), D, I, "add_torch")
+    Dz, Iz = index.search_torch(torch.empty((0, 100), device=dev), 3)
+    assert Dz.shape == (0, 3) and Iz.shape == (0, 3)
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+@pytest.mark.parametrize("qtype", QTYPES)
+def test_write_and_read_index(qtype, metric, tmp_path):
+    rng = np.random.default_rng(31)
+    xb = (3 + rng.standard_normal((600, 40))).astype(np.float32)
+    xq = (3 + rng.standard_normal((20, 40))).astype(np.float32)
+    index = faiss.IndexScalarQuantizer(40, qtype, metric)
+    index.train(xb)
+    index.add(xb)
+    path = str(tmp_path / "sq.index")
+    faiss.write_index(index, path)
+    back = faiss.read_index(path)
+    assert isinstance(back, faiss.IndexScalarQuantizer) and back.is_trained and back.ntotal == 600
+    assert (back.d, back.qtype, back.metric_type, back.code_size) == (40, qtype, metric, 40)
+    assert np.array_equal(back.sq.trained.view(np.uint32), index.sq.trained.view(np.uint32))
+    assert np.array_equal(back.codes, index.codes)
+    for k in (1, 40):
+        assert_knn_identical(*back.search(xq, k), *index.search(xq, k), f"k={k}")
+    empty = faiss.IndexScalarQuantizer(40, qtype, metric)
+    empty.sq.set_trained(index.sq.trained)
+    faiss.write_index(empty, path)
+    back = faiss.read_index(path)
+    assert isinstance(back, faiss.IndexScalarQuantizer) and back.is_trained and back.ntotal == 0
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_refine_over_scalar_quantiser(metric, tmp_path):
+    rng = np.random.default_rng(41)
+    n, d, nq, k = 300, 32, 12, 10
+    xb = rng.standard_normal((n, d)).astype(np.float32)
+    xq = rng.standard_normal((nq, d)).astype(np.float32)
+    index = faiss.IndexRefineFlat(faiss.IndexScalarQuantizer(d, SQ.QT_8bit, metric))
+    assert not index.is_trained
+    index.train(xb)
+    index.add(xb[:100])
+    index.add(xb[100:])
+    assert index.is_trained and index.ntotal == n and index.base_index.ntotal == n
+    flat = faiss.IndexFlat(d, metric)
+    flat.add(xb)
+    index.k_factor = 30  # k * k_factor >= ntotal: the exact index's own answer
+    assert_knn_identical(*index.search(xq, k), *flat.search(xq, k), "refine, every row a candidate")
+    index.k_factor = 2
+    D2, I2 = index.search(xq, k)
+    Df, If = flat.search(xq, k)
+    print(f"recall@10 of IndexRefineFlat(SQ8), k_factor 2: {np.mean([len(set(I2[q]) & set(If[q])) / k for q in range(nq)]):.3f}")
+    path = str(tmp_path / "rf.index")
+    faiss.write_index(index, path)
+    back = faiss.read_index(path)
+    assert isinstance(back, faiss.IndexRefineFlat) and isinstance(back.base_index, faiss.IndexScalarQuantizer)
+    assert back.ntotal == n and back.k_factor == 2 and np.array_equal(back.base_index.codes, index.base_index.codes)
+    assert_knn_identical(*back.search(xq, k), D2, I2, "IxRF round trip")
+
+
+def test_create_search_index():
+    from image_search_engine_amd.utils import create_search_index
+
+    x = np.random.default_rng(8).standard_normal((512, 64)).astype(np.float32)
+    index = create_search_index(x, "sq8")
+    assert isinstance(index, faiss.IndexScalarQuantizer) and index.is_trained and index.ntotal == 512
+    assert (index.qtype, index.code_size, index.metric_type) == (SQ.QT_8bit, 64, L2)
+    top = index.search(x[:5], 1)[1][:, 0]
+    assert top.tolist() == [0, 1, 2, 3, 4]
