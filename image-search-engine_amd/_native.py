@@ -67,6 +67,7 @@ PROTOTYPES = [
     ("ise_index_byte_stats", _int, [_vp, _u64p]),
     ("ise_index_depth_stats", _int, [_vp, _u64p]),
     ("ise_index_byte_row", _int, [_vp, _i64, _f32p]),
+    ("ise_index_byte_row_codes", _int, [_vp, _i64, _vp]),
     ("ise_index_stage_query_debug", _int, [_vp, _vp, _int, _vp, _i64, _f32p, ctypes.POINTER(ctypes.c_int32)]),
     ("ise_index_range_search_host", _int, [_vp, _vp, _i64, ctypes.c_float, ctypes.POINTER(_vp)]),
     ("ise_range_result_get", _int, [_vp, _i64p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),

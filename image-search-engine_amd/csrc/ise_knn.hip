@@ -13,6 +13,7 @@
 //   xh     [cap][dph] fp16 shadow rows of LONG float32 L2 indexes: 2^-s_r fp16(2^s_r (y - mu)), what the
 //   hmeta  [3][cap]   scan's filter reads instead of xb; |u~|^2, e_r, s_r per row (ise_rows.hpp)
 //   xq8    [cap][dpb] int8 shadow rows beside xh: rint((y - mu) / c_r), what the filter of batches with k <= 10 reads;
+//          stored tile-blocked [cap/16][dpb/64][4][16][16 B] (ise_byte_layout.hpp);
 //   bmeta  [cap]      c_r (bf16) | e_r / c_r (fp16) per row (ise_rows.hpp, byte_rows_kernel)
 //   part   [nqt][nb][16 T][k] u64  per-block sorted candidate lists (workspace slot)
 //
@@ -89,7 +90,7 @@ struct ise_index {
     int dph = 0;               // padded shadow row length (whole 64-byte k-steps)
     bool shadow_off = false;   // its allocation failed: the float32 filter serves (no retry until reset)
     // ... and its byte image (ise_scan.hpp BYTE), kept with the fp16 shadow: set only while xh is
-    void* xq8 = nullptr;       // [cap][dpb] int8
+    void* xq8 = nullptr;       // [cap][dpb] int8, tile-blocked (ise_byte_layout.hpp)
     uint32_t* bmeta = nullptr; // [cap]: c_r | e_r / c_r
     int dpb = 0;               // padded byte row length (whole 64-byte k-steps)
     bool byte_off = false;     // its allocation failed: the fp16 shadow serves (no retry until reset)
@@ -441,6 +442,7 @@ static int reserve_rows(ise_index* h, long long need, hipStream_t st) {
     long long want = need;
     if (cap > 0 && want < cap + cap / 2) want = cap + cap / 2;  // geometric growth on re-add
     want = (want + 15) / 16 * 16;
+    static_assert(BYTE_TILE_ROWS == 16, "capacities are whole row tiles: the byte rows are stored and copied by the tile");
     const size_t rb = row_bytes(h);
     char* nx = nullptr;
     float* nn = nullptr;
@@ -484,8 +486,11 @@ static int reserve_rows(ise_index* h, long long need, hipStream_t st) {
             if (nxq) (void)hipFree(nxq);
             nxq = nullptr;
         } else {
-            HIP_TRY(hipMemcpyAsync(nxq, h->xq8, (size_t)h->n * qb, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemsetAsync(nxq + (size_t)h->n * qb, 0, (size_t)(want - h->n) * qb, st));
+            // tile-blocked rows (ise_byte_layout.hpp): whole tiles are copied -- the last one's rows at or beyond n
+            // read zero in the source -- and whole tiles are cleared; both capacities are multiples of the tile
+            const long long nt = (h->n + BYTE_TILE_ROWS - 1) / BYTE_TILE_ROWS * BYTE_TILE_ROWS;
+            HIP_TRY(hipMemcpyAsync(nxq, h->xq8, (size_t)nt * qb, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemsetAsync(nxq + (size_t)nt * qb, 0, (size_t)(want - nt) * qb, st));
             HIP_TRY(hipMemsetAsync(nbm, 0, (size_t)want * sizeof(uint32_t), st));
             HIP_TRY(hipMemcpyAsync(nbm, h->bmeta, (size_t)h->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         }
@@ -2783,7 +2788,6 @@ static int remove_runs_locked(ise_index* h, const std::vector<RemoveRun>& runs, 
                                (const uint32_t*)sc.cend, (int)T, (uint32_t)a, (uint32_t)m, sc.src_idx);
             remove_move_rows(h, h->xb, rb, a, m, sc, st);
             if (mv_h) remove_move_rows(h, h->xh, hb, a, m, sc, st);
-            if (mv_q) remove_move_rows(h, h->xq8, qb, a, m, sc, st);
             if (meta) {  // the 4-byte arrays: plane p of the bounce buffer is [p * m, (p + 1) * m)
                 RemovePlanes gp{}, cp{};
                 int np = 0;
@@ -2799,7 +2803,6 @@ static int remove_runs_locked(ise_index* h, const std::vector<RemoveRun>& runs, 
                 plane(h->norms);
                 if (mv_h)
                     for (int i = 0; i < 3; i++) plane(h->hmeta + (size_t)i * h->cap);
-                if (mv_q) plane(h->bmeta);
                 hipLaunchKernelGGL(remove_words_kernel<true>, dim3(gw, np), dim3(256), 0, st, gp,
                                    (const uint32_t*)sc.src_idx, (uint32_t)m);
                 hipLaunchKernelGGL(remove_words_kernel<false>, dim3(gw, np), dim3(256), 0, st, cp,
@@ -2807,6 +2810,12 @@ static int remove_runs_locked(ise_index* h, const std::vector<RemoveRun>& runs, 
             }
             HIP_TRY(hipGetLastError());
         }
+        // the byte rows are tile-blocked (ise_byte_layout.hpp) and do not move: codes and bmeta are functions of the
+        // row and mu, so the destination rows are built again from the float32 rows that have just arrived -- the
+        // same bits a move would have brought (4 B read per element where a move copied 1 B twice)
+        if (mv_q)
+            hipLaunchKernelGGL(byte_rows_kernel, dim3((unsigned)((moved + 3) / 4)), dim3(256), 0, st, (const float*)h->xb,
+                               first, moved, h->d, h->dp, (const float*)h->mu, (int8_t*)h->xq8, h->dpb, h->bmeta);
         HIP_TRY(hipEventRecord(sc.ev1, st));
     }
     // the tail [n_new, n_old) of every array reads zeros again (reserve_rows' invariant: pad rows zero, their norms
@@ -2819,7 +2828,17 @@ static int remove_runs_locked(ise_index* h, const std::vector<RemoveRun>& runs, 
             HIP_TRY(hipMemsetAsync(h->hmeta + (size_t)i * h->cap + n_new, 0, (size_t)removed * sizeof(float), st));
     }
     if (h->xq8) {
-        HIP_TRY(hipMemsetAsync(static_cast<char*>(h->xq8) + (size_t)n_new * qb, 0, (size_t)removed * qb, st));
+        // tile-blocked: the rows of n_new's tile that are no longer rows go through the address map, the whole tiles
+        // behind it are contiguous (rows at or beyond n_old were zero already; cap is whole tiles)
+        const long long upr = (long long)(qb / 16);
+        const long long t_new = (n_new + BYTE_TILE_ROWS - 1) / BYTE_TILE_ROWS * BYTE_TILE_ROWS;
+        const long long t_old = (n_old + BYTE_TILE_ROWS - 1) / BYTE_TILE_ROWS * BYTE_TILE_ROWS;
+        const long long z1 = std::min(t_new, n_old);
+        if (z1 > n_new)
+            hipLaunchKernelGGL(byte_rows_zero_kernel, dim3((unsigned)(((z1 - n_new) * upr + 255) / 256)), dim3(256), 0, st,
+                               (int8_t*)h->xq8, n_new, z1, (int)upr);
+        if (t_old > t_new)
+            HIP_TRY(hipMemsetAsync(static_cast<char*>(h->xq8) + (size_t)t_new * qb, 0, (size_t)(t_old - t_new) * qb, st));
         HIP_TRY(hipMemsetAsync(h->bmeta + n_new, 0, (size_t)removed * sizeof(uint32_t), st));
     }
     h->n = n_new;
@@ -2957,6 +2976,27 @@ extern "C" int ise_index_byte_row(ise_index_t* h, int64_t i, float* out2) {
     const _Float16 eh = __builtin_bit_cast(_Float16, (unsigned short)eb);
     out2[0] = cr;
     out2[1] = cr * (float)eh;  // exact: 8 x 11 significant bits
+    return ISE_OK;
+}
+
+extern "C" int ise_index_byte_row_codes(ise_index_t* h, int64_t i, int8_t* out_dpb) {
+    if (!h || !out_dpb) return fail(ISE_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    DeviceGuard gd(h->device);
+    int rc = prepare_shift_locked(h, h->stream);
+    if (rc) return rc;
+    if (!h->xq8) return fail(ISE_E_INVALID, "this index has no byte shadow rows");
+    // allocated rows at or beyond n can be read too (they read zero: the partial-tile invariant)
+    if (i < 0 || i >= h->cap) return fail(ISE_E_INVALID, "row out of range");
+    HIP_TRY(hipDeviceSynchronize());
+    u32x4* tmp = nullptr;
+    HIP_TRY(hipMalloc(&tmp, (size_t)h->dpb));
+    hipLaunchKernelGGL(byte_row_read_kernel, dim3(1), dim3(64), 0, h->stream, (const int8_t*)h->xq8, (long long)i,
+                       (int)(h->dpb / 16), tmp);
+    hipError_t e = hipMemcpyAsync(out_dpb, tmp, (size_t)h->dpb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(tmp);
+    HIP_TRY(e);
     return ISE_OK;
 }
 

@@ -1,6 +1,7 @@
 // ise_rows.hpp -- wave-per-row helper kernels: norms, padding / conversion, normalize_L2, shift vector.
 #pragma once
 #include "ise_common.hpp"
+#include "ise_byte_layout.hpp"
 
 // ---------------------------------------------------------------- row helpers
 // |y|^2 per row, wave per row, fixed summation order (lanes stride float4, then
@@ -112,12 +113,22 @@ __global__ __launch_bounds__(256) void byte_rows_kernel(const float* __restrict_
     uint32_t cb = __float_as_uint(cf);
     if (cb & 0xFFFFu) cb = (cb + 0x10000u) & 0xFFFF0000u;  // bf16, rounded up: |a| / c_r <= 127
     const double cr = (double)__uint_as_float(cb);
-    int8_t* qr = xq + (size_t)r * dpb;
+    const int upr = dpb >> 4;  // 16-byte units per row; dpb is a multiple of 64, so every pass has all 64 lanes
     double nu = 0.0, e2 = 0.0;
     for (int j = lane; j < dpb; j += 64) {
         const double a = (j < d && !bad) ? (double)xr[j] - (double)mu[j] : 0.0;
         const double q = cr > 0.0 ? fmin(fmax(rint(a / cr), -127.0), 127.0) : 0.0;
-        qr[j] = (int8_t)q;
+        // the 16 codes of lanes 16g .. 16g + 15 are unit j / 16 of the row: gathered into lane 16g (bytes, then
+        // dwords) and stored as one 16-byte unit where ise_byte_layout.hpp puts it
+        const uint32_t b = (uint32_t)(uint8_t)(int8_t)q;
+        const uint32_t w4 = b | (__shfl_down(b, 1) << 8) | (__shfl_down(b, 2) << 16) | (__shfl_down(b, 3) << 24);
+        u32x4 unit;
+        unit[0] = w4;
+        unit[1] = __shfl_down(w4, 4);
+        unit[2] = __shfl_down(w4, 8);
+        unit[3] = __shfl_down(w4, 12);
+        if ((lane & 15) == 0)
+            *reinterpret_cast<u32x4*>(xq + (byte_unit_index(r, j >> 4, upr) << 4)) = unit;
         const double res = a - cr * q;  // cr q is exact (8 + 7 significant bits)
         nu = fma(a, a, nu);
         e2 = fma(res, res, e2);
@@ -136,6 +147,24 @@ __global__ __launch_bounds__(256) void byte_rows_kernel(const float* __restrict_
         if ((float)__builtin_bit_cast(_Float16, hb) < ef) hb++;  // fp16, rounded up (eps <= sqrt(d) / 2 + margins)
         bm[r] = (cb >> 16) | ((uint32_t)hb << 16);
     }
+}
+
+// Rows [row0, row1) of the tile-blocked byte rows read zero again (remove_ids: the rows of a last, partial tile that
+// are no longer rows; whole tiles behind it are cleared with a memset).  One thread per (row, unit).
+__global__ __launch_bounds__(256) void byte_rows_zero_kernel(int8_t* __restrict__ xq, long long row0, long long row1,
+                                                             int upr) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long row = row0 + i / upr;
+    if (row >= row1) return;
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    *reinterpret_cast<u32x4*>(xq + (byte_unit_index(row, (int)(i % upr), upr) << 4)) = z;
+}
+
+// Debug read (ise_index_byte_row_codes): the upr units of one row, gathered into out[upr] in column order.
+__global__ __launch_bounds__(64) void byte_row_read_kernel(const int8_t* __restrict__ xq, long long row, int upr,
+                                                           u32x4* __restrict__ out) {
+    for (int u = threadIdx.x; u < upr; u += 64)
+        out[u] = *reinterpret_cast<const u32x4*>(xq + (byte_unit_index(row, u, upr) << 4));
 }
 
 // The byte route's index statistic (ise_knn.hip, byte_rel_ok): mean e_r / |y - mu| over the rows with a finite,

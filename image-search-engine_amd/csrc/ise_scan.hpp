@@ -2,6 +2,7 @@
 #pragma once
 #include "ise_common.hpp"
 #include "ise_scan_params.hpp"
+#include "ise_byte_layout.hpp"
 #include "ise_select.hpp"
 #include "ise_stage.hpp"
 
@@ -148,15 +149,28 @@ __global__ __launch_bounds__(W * 64, T == 1 ? W / 2 : (W / 4 > 0 ? W / 4 : 1)) v
     STAMP(0);
 
     auto load_chunk = [&](f32x4(&a)[CH], int tile, int s0) {
+        // byte shadow rows are tile-blocked (ise_byte_layout.hpp): lane (c, g) wants unit 4 s + g of row 16 tile + c,
+        // byte_unit_index(16 tile + c, 4 s + g, row_slots) = tile * 16 * row_slots + s * 64 + lane -- the
+        // wave-uniform part is inlined here, a k-step is 1 KB contiguous per wave instruction
+        // Loads: fp16 and float32 rows are row-major, a wave load covers 16 rows x 64 B, half lines whose other half
+        // the next load wants from L2, and non-temporal loads lose with that shape (float32: 369 vs 343 us; byte rows
+        // row-major: step 107.6 vs 91.4 us) -- plain loads.  Blocked byte rows, whole lines: the scan that runs alone
+        // (ROWS_I8) is faster non-temporal (isolated 96.6 vs 105.9 us), the one-request kernel of the deep plan
+        // (ROWS_I8_ONE), which always shares the device with its neighbour's scan, is faster plain (step 88.9 vs
+        // 89.9 us) -- DESIGN.md 5.0g.  Compile-time: the one-tile kernels have no register to spare for a branch.
+        constexpr bool BLOCKED = BYTE;
+        constexpr bool NT = RM == ROWS_I8;
+        constexpr int STEP = BLOCKED ? 1024 : 64;  // bytes from one k-step of a lane to the next
         const char* base = static_cast<const char*>(p.xb) +
-                           ((((size_t)tile * 16 + c) * p.row_slots + 4 * s0 + g) << 4);
+                           (BLOCKED ? (((size_t)tile * 16 * p.row_slots + (size_t)s0 * 64 + lane) << 4)
+                                    : ((((size_t)tile * 16 + c) * p.row_slots + 4 * s0 + g) << 4));
         if (ABL(32)) base = static_cast<const char*>(p.xb) + (((size_t)c * p.row_slots + g) << 4);  // dev: L1-hot
-        // plain loads on purpose: non-temporal loads stream a pure read faster (7.1 vs 6.2 TB/s,
-        // scripts/microbench/read_bw.hip) but lose here (369 vs 343 us) -- a wave load covers 16 rows x
-        // 64 B, half lines whose other half the next load wants from L2
         if (ABL(128)) return;  // dev: no index loads at all (registers keep whatever they hold)
 #pragma unroll
-        for (int s = 0; s < CH; s++) a[s] = *reinterpret_cast<const f32x4*>(base + 64 * s);
+        for (int s = 0; s < CH; s++) {
+            const f32x4* src = reinterpret_cast<const f32x4*>(base + STEP * s);
+            a[s] = NT ? __builtin_nontemporal_load(src) : *src;
+        }
     };
     auto load_norms = [&](int tile) -> f32x4 {
         return *reinterpret_cast<const f32x4*>(p.norms + (size_t)tile * 16 + 4 * g);

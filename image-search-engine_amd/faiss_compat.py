@@ -491,6 +491,14 @@ class IndexFlat(_RemovableIndex):
         _n.check(_n.lib.ise_index_byte_row(self._h, int(i), out))
         return float(out[0]), float(out[1])
 
+    def byte_row_codes(self, i: int):
+        """The int8 codes of byte shadow row i in column order, its dpb padded columns (include/ise_knn.h,
+        ise_index_byte_row_codes)."""
+        steps = (self.d + 63) // 64  # dpb as the library pads it: whole 64-byte k-steps, in fours beyond four
+        out = np.zeros((steps if steps <= 4 else (steps + 3) // 4 * 4) * 64, dtype=np.int8)
+        _n.check(_n.lib.ise_index_byte_row_codes(self._h, int(i), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
     def shadow_row(self, i: int) -> tuple:
         """(|u~|^2, e_r, s_r) of shadow row i (include/ise_knn.h, ise_index_shadow_row)."""
         out = (ctypes.c_float * 3)()

@@ -113,8 +113,11 @@ int ise_index_short_stats(ise_index_t* h, uint64_t* out1);
  * read shadow rows of either kind.  ise_index_byte_stats: out2[0] = those of them that read the byte shadow, out2[1] = 1
  * when the index's byte route is open (the byte shadow exists and its build-time statistics admit it).
  * ise_index_shadow_row: out3 = (|u~|^2, e_r, s_r) of fp16 shadow row i, e_r >= |(y - mu) - u~|.
- * ise_index_byte_row: out2 = (c_r, e_r) of byte shadow row i, e_r >= |(y - mu) - c_r q|.  Both ISE_E_INVALID when the
- * index has no such shadow. */
+ * ise_index_byte_row: out2 = (c_r, e_r) of byte shadow row i, e_r >= |(y - mu) - c_r q|.
+ * ise_index_byte_row_codes (debug): the codes q of byte shadow row i in column order, out_dpb[0 .. dpb), dpb = d rounded
+ * up to whole 64-column k-steps, and to a multiple of four of them beyond four (pad columns read zero); the rows are stored tile-blocked and this read goes through the same
+ * address map as the scan.  i may also name an allocated row at or beyond n (below the capacity): it reads zero.  All three
+ * ISE_E_INVALID when the index has no such shadow. */
 int ise_index_half_stats(ise_index_t* h, uint64_t* out1);
 int ise_index_byte_stats(ise_index_t* h, uint64_t* out2);
 /* The byte-shadow scan has two plans.  A batch enqueued on another stream than the index's previous search has
@@ -127,6 +130,7 @@ int ise_index_byte_stats(ise_index_t* h, uint64_t* out2);
 int ise_index_depth_stats(ise_index_t* h, uint64_t* out2);
 int ise_index_shadow_row(ise_index_t* h, int64_t i, float* out3);
 int ise_index_byte_row(ise_index_t* h, int64_t i, float* out2);
+int ise_index_byte_row_codes(ise_index_t* h, int64_t i, int8_t* out_dpb);
 
 /* Tests only (nothing on the search path calls it): one float32 query (device pointer, d floats) through the query
  * staging of a shadow filter (csrc/ise_stage.hpp, the device functions the scan kernel runs) in a one-block kernel.
