@@ -163,6 +163,21 @@ PROTOTYPES = [
     ("ise_sq_search_host", _int, [_vp, _vp, _i64, _int, _vp, _vp]),
     ("ise_sq_search_device", _int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
     ("ise_sq_stats", _int, [_vp, _u64p]),
+    ("ise_ivfsq_create", _int, [ctypes.POINTER(_vp), _int, _int, _int, _int, _int]),
+    ("ise_ivfsq_destroy", _int, [_vp]),
+    ("ise_ivfsq_reset", _int, [_vp]),
+    ("ise_ivfsq_info", _int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), _i64p,
+                              ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    ("ise_ivfsq_set_trained_host", _int, [_vp, _vp]),
+    ("ise_ivfsq_get_trained_host", _int, [_vp, _vp]),
+    ("ise_ivfsq_add_host", _int, [_vp, _vp, _vp, _i64]),
+    ("ise_ivfsq_add_device", _int, [_vp, _vp, _vp, _i64, _vp]),
+    ("ise_ivfsq_add_codes_host", _int, [_vp, _vp, _vp, _i64]),
+    ("ise_ivfsq_list_sizes_host", _int, [_vp, _vp]),
+    ("ise_ivfsq_list_host", _int, [_vp, _int, _vp, _vp]),
+    ("ise_ivfsq_search_host", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp]),
+    ("ise_ivfsq_search_device", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp]),
+    ("ise_ivfsq_stats", _int, [_vp, _u64p]),
     ("ise_refresh_env_knobs", _int, []),
     ("ise_comm_precheck", _int, [_int]),
     ("ise_comm_unique_id", _int, [_vp]),

@@ -1,0 +1,133 @@
+// ise_ivfsq.hpp -- kernels of IndexIVFScalarQuantizer: inverted lists over the 8-bit rows of ise_sq.hpp and the pass
+// that scans only the probed ones (include/ise_knn.h, ise_ivfsq_*).  Host side: ise_ivfsq.hip.
+//
+// Layout.  All lists live in ONE array: codes [slots][stride] (stride = d rounded up to 64, pad bytes zero), rterm
+// [slots] float64 (ise_sq.hpp's row term) and ids [slots] uint32 (the row's insertion number).  List l owns the 64-row
+// tiles [list_tile0[l], list_tile0[l + 1]) -- SQ_TILE rows, a wave's unit in the byte scan; inside a list the slots are
+// in ascending id order, the slots behind list_size[l] rows are zero rows with id 0xFFFFFFFF, masked by position.
+//
+// A pass serves one group of QT = sq_qt(d) queries and 32 results:
+//   masks      ivfsq_mask_kernel turns the probe table [nq][nprobe] into one query mask per (group of QT, list); -1 and
+//              out-of-range entries set nothing, a duplicate sets its bit twice.
+//   work list  ivfsq_offsets_kernel scans the lists' tile counts under "mask != 0" into an offset per (group, list) and
+//              a count per group; ivfsq_work_kernel, parallel over all tiles, writes for every tile of a probed list
+//              the entry (tile, valid rows in it, the list's mask) at offset[list] + tile - list_tile0[list]: slot order,
+//              so the list is the same whatever the launch does.
+//   scan       ivfsq_scan_kernel is sq_scan_body (ise_sq.hpp) walking the entries instead of the tiles: wave w of block
+//              b takes entries b SQ_WAVES + w + j gridDim.x SQ_WAVES.  The key is ord(score) << 32 | ids[slot]; keys are
+//              unique and compared in full, so ties go by ascending id however the lists order the ids.
+// The staging record, the selection, sq_merge_kernel and the floor-keyed repeat for k > 32 are ise_sq.hpp's.
+#pragma once
+#include "ise_sq.hpp"
+
+struct SqIvfScanParams {
+    const uint8_t* codes;   // [tiles * 64][stride]
+    const double* rterm;    // [tiles * 64]
+    const uint32_t* ids;    // [tiles * 64]
+    int d, stride;
+    const unsigned char* qrec;  // the group's first query's staged record, nqt of them
+    int nqt, kp;
+    int ip;
+    const u64* lo;          // [nqt] floors, or null in the first pass
+    u64* lists;             // [grid][QT][SQ_KPASS]
+    const u32x4* work;      // the group's entries: (tile, valid rows, query mask, 0)
+    const uint32_t* count;  // [1] entries of the group
+    unsigned long long* tiles_loaded;  // += the entries this pass visits
+};
+
+template <int QT>
+__global__ __launch_bounds__(SQ_WAVES * 64) void ivfsq_scan_kernel(const SqIvfScanParams p) {
+    sq_scan_body<QT, true>(p);
+}
+
+// probes [nq][nprobe] (int64) -> masks [groups of 1 << qshift queries][nlist]; the masks are zero on entry
+static __global__ __launch_bounds__(256) void ivfsq_mask_kernel(const long long* probes, long long total, int nprobe, int nlist,
+                                                                int qshift, uint32_t* masks) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long l = probes[i];
+    if (l < 0 || l >= nlist) return;
+    const long long q = i / nprobe;
+    atomicOr(masks + (size_t)(q >> qshift) * nlist + l, 1u << (q & ((1 << qshift) - 1)));
+}
+
+// one block per group: offs[group][l] = the tiles of the probed lists before l, count[group] = their total.  Thread t
+// owns the lists [t per, (t + 1) per); the 256 partial sums are scanned in LDS
+static __global__ __launch_bounds__(256) void ivfsq_offsets_kernel(const uint32_t* masks, const uint32_t* list_tile0, int nlist,
+                                                                   uint32_t* offs, uint32_t* count) {
+    __shared__ uint32_t part[256];
+    const int t = threadIdx.x, grp = blockIdx.x;
+    const uint32_t* gm = masks + (size_t)grp * nlist;
+    uint32_t* go = offs + (size_t)grp * nlist;
+    const int per = (nlist + 255) / 256;
+    const int l0 = min(nlist, t * per), l1 = min(nlist, l0 + per);
+    uint32_t s = 0;
+    for (int l = l0; l < l1; l++) s += gm[l] ? list_tile0[l + 1] - list_tile0[l] : 0u;
+    part[t] = s;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {  // inclusive scan
+        const uint32_t v = t >= o ? part[t - o] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - s;
+    for (int l = l0; l < l1; l++) {
+        go[l] = run;
+        run += gm[l] ? list_tile0[l + 1] - list_tile0[l] : 0u;
+    }
+    if (t == 255) count[grp] = part[255];
+}
+
+// thread per (tile, group = blockIdx.y): the entry of a probed list's tile.  work: [groups][tiles]
+static __global__ __launch_bounds__(256) void ivfsq_work_kernel(const uint32_t* masks, const uint32_t* offs,
+                                                                const uint32_t* list_tile0, const uint32_t* list_size,
+                                                                const uint32_t* tile_list, int nlist, uint32_t tiles,
+                                                                u32x4* work) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= tiles) return;
+    const size_t grp = blockIdx.y;
+    const uint32_t l = tile_list[t];
+    const uint32_t m = masks[grp * nlist + l];
+    if (!m) return;
+    const uint32_t in_list = t - list_tile0[l];
+    const uint32_t left = list_size[l] - in_list * SQ_TILE;  // >= 1: a list has no tile without a row
+    work[grp * tiles + offs[grp * nlist + l] + in_list] = u32x4{t, left < SQ_TILE ? left : (uint32_t)SQ_TILE, m, 0u};
+}
+
+// ---------------------------------------------------------------- rebuild (ise_ivfsq.hip)
+// one block per OLD tile: the tile moves, whole, to where its list now starts (row terms, ids and pad slots with it)
+static __global__ __launch_bounds__(256) void ivfsq_move_tiles_kernel(const uint8_t* src, const double* src_rterm,
+                                                                      const uint32_t* src_ids, const uint32_t* old_tile_list,
+                                                                      const uint32_t* old_tile0, const uint32_t* new_tile0,
+                                                                      int stride, uint8_t* dst, double* dst_rterm,
+                                                                      uint32_t* dst_ids) {
+    const size_t t = blockIdx.x;
+    const uint32_t l = old_tile_list[t];
+    const size_t nt = (size_t)new_tile0[l] + (t - old_tile0[l]);
+    const u32x4* s = reinterpret_cast<const u32x4*>(src + t * SQ_TILE * stride);
+    u32x4* o = reinterpret_cast<u32x4*>(dst + nt * SQ_TILE * stride);
+    for (int i = threadIdx.x; i < SQ_TILE * stride / 16; i += 256) o[i] = s[i];
+    if (threadIdx.x < SQ_TILE) {
+        dst_rterm[nt * SQ_TILE + threadIdx.x] = src_rterm[t * SQ_TILE + threadIdx.x];
+        dst_ids[nt * SQ_TILE + threadIdx.x] = src_ids[t * SQ_TILE + threadIdx.x];
+    }
+}
+
+// wave per pending row i: to slot dest[i], with id id0 + i
+static __global__ __launch_bounds__(256) void ivfsq_scatter_rows_kernel(const uint8_t* pend, const double* pend_rterm,
+                                                                        long long m, const uint32_t* dest, uint32_t id0,
+                                                                        int stride, uint8_t* dst, double* dst_rterm,
+                                                                        uint32_t* dst_ids) {
+    const int lane = threadIdx.x & 63;
+    const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= m) return;
+    const size_t slot = dest[i];
+    const u32x4* s = reinterpret_cast<const u32x4*>(pend + (size_t)i * stride);
+    u32x4* o = reinterpret_cast<u32x4*>(dst + slot * stride);
+    for (int j = lane; j < stride / 16; j += 64) o[j] = s[j];
+    if (lane == 0) {
+        dst_rterm[slot] = pend_rterm[i];
+        dst_ids[slot] = id0 + (uint32_t)i;
+    }
+}

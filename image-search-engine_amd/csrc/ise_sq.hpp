@@ -34,6 +34,9 @@
 // LDS per pass: QT x (two limb images of 2 dpad + 16 bytes, dpad = d rounded up to 64; the 16 bytes stagger the
 // queries over the banks) + QT x 4 KiB of selection buffers + QT x 16 bytes; QT = 16 while that fits 160 KiB
 // (d <= 1472), else 8 (sq_qt).
+//
+// The scan's body (sq_scan_body) also serves the inverted lists over these rows (ise_ivfsq.hpp), which
+// walk a work list of tiles instead of the whole array; this file's kernels do not depend on that one.
 #pragma once
 #include "ise_common.hpp"
 #include "ise_merge.hpp"
@@ -226,14 +229,29 @@ static __global__ __launch_bounds__(64) void sq_stage_kernel(const SqStageParams
     }
 }
 
-template <int QT>
-__global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanParams p) {
+// The scan of one pass, for both layouts (IVF false: the flat index's rows [0, n), sq_scan_kernel; IVF true: the work
+// list of an inverted-list pass, P = SqIvfScanParams, ise_ivfsq.hpp).  What differs stands under `if constexpr (IVF)`:
+// which tile a wave's next unit names, the row mask (row < n | position < valid rows and the query's mask bit) and the
+// key's low word (row | ids[slot]).  The record copy-in, the byte -> fp16 MFMA step, the float64 assembly, the cuts and
+// the block's final selection exist once.
+template <int QT, bool IVF, class P>
+__device__ __forceinline__ void sq_scan_body(const P& p) {
     extern __shared__ __align__(16) unsigned char smem_sq[];
     const int dpad = sq_dpad(p.d);
     const int qrow = 2 * dpad + 16;  // bytes of one limb image
     const int rec = 2 * qrow + 16;   // bytes of one query's record
     u64* buf = reinterpret_cast<u64*>(smem_sq + QT * rec);  // [SQ_WAVES][QT][SQ_CAP]
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    long long nent = 0;  // IVF: entries of the group's work list
+    if constexpr (IVF) {
+        nent = (long long)__builtin_amdgcn_readfirstlane((int)*p.count);
+        if (blockIdx.x == 0 && threadIdx.x == 0 && nent) atomicAdd(p.tiles_loaded, (unsigned long long)nent);
+        if ((long long)blockIdx.x * SQ_WAVES >= nent) {  // no entry for this block: its lists are padding
+            for (int i = threadIdx.x; i < p.nqt * SQ_KPASS; i += SQ_WAVES * 64)
+                p.lists[(size_t)blockIdx.x * QT * SQ_KPASS + i] = KEY_PAD;
+            return;
+        }
+    }
     {  // the pass's records, zeros behind the last: every 16-byte load is independent
         const u32x4* src = reinterpret_cast<const u32x4*>(p.qrec);
         u32x4* dst = reinterpret_cast<u32x4*>(smem_sq);
@@ -269,7 +287,9 @@ __global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanPara
         }
     };
 
-    const long long ntiles = (p.n + SQ_TILE - 1) / SQ_TILE;
+    long long ntiles;  // units of the pass: the index's tiles | the work list's entries
+    if constexpr (IVF) ntiles = nent;
+    else ntiles = (p.n + SQ_TILE - 1) / SQ_TILE;
     const long long tstep = (long long)gridDim.x * SQ_WAVES;
     const int nsteps = dpad >> 6;  // 64 entries per step: lane group g takes bytes [64 S + 16 g, + 16) of its row
     const unsigned char* bh = smem_sq + qsrc * rec + 32 * g;
@@ -281,12 +301,15 @@ __global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanPara
 #pragma unroll
         for (int rt = 0; rt < SQ_RT; rt++) {
             long long r = t * SQ_TILE + rt * 16 + c16;
-            r = r < p.n ? r : p.n - 1;
+            if constexpr (!IVF) r = r < p.n ? r : p.n - 1;  // (the lists' slots are whole tiles)
             a[rt] = *reinterpret_cast<const u32x4*>(p.codes + (size_t)r * p.stride + kb);
         }
     };
     // the lane holds query c16 against rows t * 64 + 16 rt + 4 g + reg: score, gate, append; then the cuts
-    auto epilogue = [&](long long t, const f32x4(&acc0)[SQ_RT], const f32x4(&acc1)[SQ_RT], const double2(&rr)[SQ_RT][2]) {
+    // IVF: valid = rows of the tile that belong to its list, qm = the list's query mask, idv = the lane's rows' ids
+    auto epilogue = [&](long long t, const f32x4(&acc0)[SQ_RT], const f32x4(&acc1)[SQ_RT], const double2(&rr)[SQ_RT][2], int valid,
+                        uint32_t qm, const u32x4(&idv)[SQ_RT]) {
+        const bool probes = (qm >> c16) & 1u;
 #pragma unroll
         for (int rt = 0; rt < SQ_RT; rt++) {
             const long long rbase = t * SQ_TILE + rt * 16 + 4 * g;
@@ -299,8 +322,15 @@ __global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanPara
                 if (!p.ip) sc = sc < 0.f ? 0.f : sc;  // NaN stays NaN
                 sc += 0.f;                            // a zero is +0
                 const float s = p.ip ? -sc : sc;
-                const u64 key = ((u64)ord_f32(s) << 32) | (uint32_t)row;
-                const bool c = row < p.n && s < FLT_MAX && key >= lo_v && key < thr_v;
+                u64 key;
+                bool c;
+                if constexpr (IVF) {
+                    key = ((u64)ord_f32(s) << 32) | idv[rt][reg];
+                    c = rt * 16 + 4 * g + reg < valid && probes && s < FLT_MAX && key >= lo_v && key < thr_v;
+                } else {
+                    key = ((u64)ord_f32(s) << 32) | (uint32_t)row;
+                    c = row < p.n && s < FLT_MAX && key >= lo_v && key < thr_v;
+                }
                 const u64 mk = __ballot(c);
                 if (mk) {
                     const u64 col = (mk >> c16) & 0x0001000100010001ull;  // my column's four lanes
@@ -323,11 +353,31 @@ __global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanPara
     const long long t0 = (long long)blockIdx.x * SQ_WAVES + w;
     long long lt = t0, ct = t0;  // the tile being requested | computed
     int lS = 0, cS = 0;          // and the step in it
+    // IVF: lt / ct count ENTRIES; an entry is (tile, valid rows, query mask, 0).  The entry behind the one in use is
+    // fetched a tile ahead on either side (wave-uniform loads), so no code-byte request waits for the entry it has just
+    // asked for.  Behind the wave's last entry: the list's last entry again -- a valid tile, unused
+    [[maybe_unused]] auto entry_at = [&](long long e) {
+        if constexpr (IVF) return p.work[e < nent ? e : nent - 1];
+        else return u32x4{0u, 0u, 0u, 0u};
+    };
+    [[maybe_unused]] uint32_t ltile = 0, lnext = 0;
+    [[maybe_unused]] u32x4 cent = {0u, 0u, 0u, 0u}, cnext = {0u, 0u, 0u, 0u};
+    if constexpr (IVF) {
+        ltile = entry_at(lt)[0];
+        lnext = entry_at(lt + tstep)[0];
+        cent = entry_at(ct);
+        cnext = entry_at(ct + tstep);
+    }
     auto request = [&](u32x4(&a)[SQ_RT]) {
-        load_step(a, lt < ntiles ? lt : ntiles - 1, lS);  // behind the wave's last tile: the index's last tile again, unused
+        if constexpr (IVF) load_step(a, (long long)ltile, lS);
+        else load_step(a, lt < ntiles ? lt : ntiles - 1, lS);  // behind the wave's last tile: the index's last tile again, unused
         if (++lS == nsteps) {
             lS = 0;
             lt += tstep;
+            if constexpr (IVF) {
+                ltile = lnext;
+                lnext = entry_at(lt + tstep)[0];
+            }
         }
     };
     u32x4 ring[SQ_RING][SQ_RT];
@@ -337,6 +387,7 @@ __global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanPara
 #pragma unroll
     for (int rt = 0; rt < SQ_RT; rt++) acc0[rt] = acc1[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
     double2 rr[SQ_RT][2];  // the row terms of the tile being computed (the inner product never uses them)
+    [[maybe_unused]] u32x4 idv[SQ_RT] = {};  // IVF: and the ids in its slots
     bool done = ct >= ntiles;
     while (!done) {
 #pragma unroll
@@ -345,11 +396,18 @@ __global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanPara
                 // the tile's row terms are requested ahead of the younger code bytes: the epilogue's wait for them
                 // does not drain the ring
                 if (cS == 0) {
+                    long long tile = ct;
+                    if constexpr (IVF) tile = (long long)cent[0];
 #pragma unroll
                     for (int rt = 0; rt < SQ_RT; rt++)
 #pragma unroll
                         for (int h2 = 0; h2 < 2; h2++)
-                            rr[rt][h2] = *reinterpret_cast<const double2*>(p.rterm + ct * SQ_TILE + rt * 16 + 4 * g + 2 * h2);
+                            rr[rt][h2] = *reinterpret_cast<const double2*>(p.rterm + tile * SQ_TILE + rt * 16 + 4 * g + 2 * h2);
+                    if constexpr (IVF) {
+#pragma unroll
+                        for (int rt = 0; rt < SQ_RT; rt++)
+                            idv[rt] = *reinterpret_cast<const u32x4*>(p.ids + tile * SQ_TILE + rt * 16 + 4 * g);
+                    }
                 }
                 request(ring[(j + SQ_RING - 1) % SQ_RING]);
                 const f16x8 bh0 = *reinterpret_cast<const f16x8*>(bh + 128 * cS);
@@ -366,12 +424,17 @@ __global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanPara
                     acc1[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bl1, acc1[rt], 0, 0, 0);
                 }
                 if (++cS == nsteps) {
-                    epilogue(ct, acc0, acc1, rr);
+                    if constexpr (IVF) epilogue((long long)cent[0], acc0, acc1, rr, (int)cent[1], cent[2], idv);
+                    else epilogue(ct, acc0, acc1, rr, 0, 0u, idv);
 #pragma unroll
                     for (int rt = 0; rt < SQ_RT; rt++) acc0[rt] = acc1[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
                     cS = 0;
                     ct += tstep;
                     done = ct >= ntiles;
+                    if constexpr (IVF) {
+                        cent = cnext;
+                        cnext = entry_at(ct + tstep);
+                    }
                 }
             }
         }
@@ -395,6 +458,11 @@ __global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanPara
         const int nw = wave_select<2 * SQ_WAVES>(kk, SQ_WAVES * SQ_CAP, kp, dst, &kth_unused);
         for (int i = nw + lane; i < kp; i += 64) dst[i] = KEY_PAD;
     }
+}
+
+template <int QT>
+__global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanParams p) {
+    sq_scan_body<QT, false>(p);
 }
 
 // One block per query of the pass: the k-way walk over the blocks' lists (merge_waves), then positions

@@ -51,8 +51,18 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          ``reconstruct_n``, ``sa_encode`` / ``sa_decode``, ``index.sq`` (``trained``,
                                          ``set_trained``, ``compute_codes``, ``decode``), ``write_index`` / ``read_index``
                                          ("IxSQ"); the other quantiser types raise; never called by the reference
+    IndexIVFScalarQuantizer(quantizer, d, nlist, qtype, metric, by_residual=False)
+                                         Faiss's cell-probe index over scalar-quantised rows: ``IndexIVFFlat``'s lists holding
+                                         ``IndexScalarQuantizer``'s bytes (the same codec for the same ``sq.trained``);
+                                         ``train`` (k-means, then min / max) / ``add`` / ``search`` with ``nprobe`` /
+                                         ``search_preassigned`` / ``search_torch``, ``get_list``, ``index.sq``,
+                                         ``write_index`` / ``read_index`` ("IwSq"); a pass reads the 64-row tiles of the
+                                         probed lists only (csrc/ise_ivfsq.hpp) and D has ``IndexScalarQuantizer``'s bits;
+                                         ``by_residual=True`` (Faiss's default) raises; the compressed cell-probe index
+                                         this package has (the reference's own, IndexIVFPQ, is still not provided)
     IndexRefineFlat(base_index)          Faiss's exact re-ranking of an approximate index: ``search`` asks ``base_index`` (an
-                                         ``IndexPQ``, an ``IndexScalarQuantizer``, an ``IndexIVFFlat`` or an ``IndexFlat`` of
+                                         ``IndexPQ``, an ``IndexScalarQuantizer``, an ``IndexIVFFlat``, an
+                                         ``IndexIVFScalarQuantizer`` or an ``IndexFlat`` of
                                          either storage) for
                                          ``k * k_factor`` labels and returns the k best of them by their exact distance to
                                          float32 rows kept beside it (csrc/ise_subset.hpp: a gather-and-score pass spread
@@ -881,8 +891,8 @@ class IndexIDMap(_IDMapBase):
     """faiss.IndexIDMap over an ``IndexFlat``."""
 
     def __init__(self, index: IndexFlat):
-        if isinstance(index, IndexIVFFlat):
-            raise NotImplementedError("IndexIDMap over an IndexIVFFlat is not provided")
+        if isinstance(index, _IndexIVF):
+            raise NotImplementedError(f"IndexIDMap over an {type(index).__name__} is not provided")
         if isinstance(index, IndexPQ):
             raise NotImplementedError("IndexIDMap over an IndexPQ is not provided")
         if isinstance(index, IndexScalarQuantizer):
@@ -1127,6 +1137,135 @@ def parse_sq(buf: bytes):
     return d, metric, qtype, rangestat, float(rangestat_arg), trained, codes
 
 
+# IndexIVFScalarQuantizer [upstream-faiss index_write.cpp write_index / write_ivf_header / write_InvertedLists, restated
+# from memory of the published format and UNPINNED like the layouts above: there is no sample file]:
+#   fourcc "IwSq"; the index header (d, ntotal, 1<<20, 1<<20, is_trained, metric_type); uint64 nlist; uint64 nprobe; the
+#   quantiser as its own "IxF2" / "IxFI" image; the direct map, empty: uint8 type (0, none), uint64 count (0); the scalar
+#   quantiser block of "IxSQ": int32 qtype; int32 rangestat; float32 rangestat_arg; uint64 d; uint64 code_size; uint64
+#   count (= 2 d, or 2 for the uniform type), count float32; then uint64 code_size; uint8 by_residual; the inverted lists:
+#   fourcc "ilar"; uint64 nlist; uint64 code_size; the sizes -- fourcc "full", uint64 count (= nlist), count uint64 (what is
+#   written here), or fourcc "sprs", uint64 count (= 2 x the lists that hold rows), count uint64 as (list, size) pairs
+#   (Faiss writes it when fewer than half of the lists hold rows; readable) -- then, per list that holds rows: size x
+#   code_size uint8, size int64 ids.
+_FOURCC_IVFSQ = b"IwSq"
+_IVF_DIMS = struct.Struct("<QQ")
+_TRUNCATED_IVFSQ = "truncated IndexIVFScalarQuantizer file"
+
+
+def serialize_ivfsq(d: int, metric: int, nlist: int, nprobe: int, qmetric: int, centroids, qtype: int, trained, lists,
+                    rangestat: int = 0, rangestat_arg: float = 0.0, by_residual: bool = False) -> bytes:
+    """``centroids`` float32 (nlist, d) (or (0, d): an untrained quantiser) under the quantiser's metric ``qmetric``;
+    ``trained`` as for ``serialize_sq``; ``lists``: ``nlist`` pairs (ids int64 (m,), codes uint8 (m, d)), any m, also 0."""
+    d, qtype, nlist = int(d), int(qtype), int(nlist)
+    assert qtype in _SQ_QTYPES, "only QT_8bit and QT_8bit_uniform are written"
+    t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
+    assert t.size == (2 if qtype == 2 else 2 * d), "the trained vector is [vmin.., vdiff..]"
+    assert len(lists) == nlist, "one (ids, codes) pair per list"
+    pairs = [(np.ascontiguousarray(ids, dtype="<i8").reshape(-1), np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, d))
+             for ids, codes in lists]
+    assert all(ids.size == codes.shape[0] for ids, codes in pairs), "one id per code row"
+    sizes = np.array([ids.size for ids, _ in pairs], dtype="<u8")
+    out = [_HDR.pack(_FOURCC_IVFSQ, d, int(sizes.sum()), 1 << 20, 1 << 20, 1, int(metric)), _IVF_DIMS.pack(nlist, int(nprobe)),
+           serialize_flat(d, int(qmetric), np.asarray(centroids, dtype=np.float32).reshape(-1, d)), struct.pack("<BQ", 0, 0),
+           _SQ_HEAD.pack(qtype, int(rangestat), float(rangestat_arg), d, d), struct.pack("<Q", t.size), t.tobytes(),
+           struct.pack("<QB", d, 1 if by_residual else 0), b"ilar", _IVF_DIMS.pack(nlist, d), b"full",
+           struct.pack("<Q", nlist), sizes.tobytes()]
+    for ids, codes in pairs:
+        if ids.size:
+            out += [codes.tobytes(), ids.tobytes()]
+    return b"".join(out)
+
+
+def parse_ivfsq(buf: bytes):
+    """-> (d, metric, nlist, nprobe, qmetric, centroids float32 (nlist or 0, d), qtype, trained float32, lists [(ids int64
+    (m,), codes uint8 (m, d))] * nlist, rangestat, rangestat_arg, by_residual): ``serialize_ivfsq``'s arguments.  Raises
+    RuntimeError on a foreign, truncated or miscounted file and on a quantiser type other than the two 8-bit ones."""
+    if len(buf) >= 4 and buf[:4] != _FOURCC_IVFSQ:
+        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexIVFScalarQuantizer")
+
+    def need(off: int, size: int) -> None:
+        if len(buf) < off + size:
+            raise RuntimeError(_TRUNCATED_IVFSQ)
+
+    off = _HDR.size
+    need(off, _IVF_DIMS.size + 4)
+    _, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
+    nlist, nprobe = _IVF_DIMS.unpack_from(buf, off)
+    off += _IVF_DIMS.size
+    if d <= 0 or n < 0 or nlist <= 0:
+        raise RuntimeError("corrupt IndexIVFScalarQuantizer header")
+    if bytes(buf[off:off + 4]) not in (b"IxF2", b"IxFI"):
+        raise RuntimeError(f"unsupported quantiser type {bytes(buf[off:off + 4])!r} in an IndexIVFScalarQuantizer file: "
+                           "only flat quantisers are readable")
+    need(off, _HDR.size + 8)
+    (count,) = struct.unpack_from("<Q", buf, off + _HDR.size)
+    need(off, _HDR.size + 8 + 4 * count)
+    d2, qmetric, centroids = parse_flat(buf[off:off + _HDR.size + 8 + 4 * count])
+    off += _HDR.size + 8 + 4 * count
+    if d2 != d or centroids.shape[0] not in (0, nlist):
+        raise RuntimeError("corrupt IndexIVFScalarQuantizer: the quantiser does not hold nlist centroids of dimension d")
+    need(off, 9)
+    dm_type, dm_count = struct.unpack_from("<BQ", buf, off)
+    off += 9
+    if dm_type != 0 or dm_count != 0:
+        raise RuntimeError("an IndexIVFScalarQuantizer file with a direct map is not readable")
+    need(off, _SQ_HEAD.size + 8)
+    qtype, rangestat, rangestat_arg, d2, code_size = _SQ_HEAD.unpack_from(buf, off)
+    off += _SQ_HEAD.size
+    if qtype not in _SQ_QTYPES:
+        raise RuntimeError(f"unsupported scalar quantiser type {qtype}: only QT_8bit (0) and QT_8bit_uniform (2) are readable")
+    if d2 != d or code_size != d:
+        raise RuntimeError("corrupt IndexIVFScalarQuantizer: the scalar quantiser does not match the header")
+    (count,) = struct.unpack_from("<Q", buf, off)
+    off += 8
+    if count != (2 if qtype == 2 else 2 * d):
+        raise RuntimeError("corrupt IndexIVFScalarQuantizer: the trained vector does not hold vmin and vdiff")
+    need(off, 4 * count)
+    trained = np.frombuffer(buf, dtype="<f4", count=count, offset=off).astype(np.float32)
+    off += 4 * count
+    need(off, 9 + 4 + _IVF_DIMS.size + 4 + 8)
+    code_size, by_residual = struct.unpack_from("<QB", buf, off)
+    off += 9
+    if bytes(buf[off:off + 4]) != b"ilar":
+        raise RuntimeError(f"unsupported inverted lists {bytes(buf[off:off + 4])!r}: only array lists (\"ilar\") are readable")
+    off += 4
+    nlist2, code_size2 = _IVF_DIMS.unpack_from(buf, off)
+    off += _IVF_DIMS.size
+    if code_size != d or nlist2 != nlist or code_size2 != d:
+        raise RuntimeError("corrupt IndexIVFScalarQuantizer: the inverted lists do not match the header")
+    form = bytes(buf[off:off + 4])
+    (count,) = struct.unpack_from("<Q", buf, off + 4)
+    off += 12
+    sizes = np.zeros(nlist, dtype=np.int64)
+    if form == b"full":
+        if count != nlist:
+            raise RuntimeError("corrupt IndexIVFScalarQuantizer: the size vector does not hold nlist entries")
+        need(off, 8 * count)
+        sizes[:] = np.frombuffer(buf, dtype="<u8", count=count, offset=off).astype(np.int64)
+    elif form == b"sprs":
+        if count % 2 or count > 2 * nlist:
+            raise RuntimeError("corrupt IndexIVFScalarQuantizer: the sparse size vector does not hold (list, size) pairs")
+        need(off, 8 * count)
+        pairs = np.frombuffer(buf, dtype="<u8", count=count, offset=off).astype(np.int64).reshape(-1, 2)
+        if pairs.size and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= nlist):
+            raise RuntimeError("corrupt IndexIVFScalarQuantizer: a list number outside [0, nlist)")
+        sizes[pairs[:, 0]] = pairs[:, 1]
+    else:
+        raise RuntimeError(f"unsupported list size form {form!r} in an IndexIVFScalarQuantizer file")
+    off += 8 * count
+    if sizes.min() < 0 or int(sizes.sum()) != n:
+        raise RuntimeError("corrupt IndexIVFScalarQuantizer: the list sizes do not add up to ntotal")
+    lists = []
+    for m in (int(s) for s in sizes):
+        need(off, m * d + 8 * m)
+        codes = np.frombuffer(buf, dtype=np.uint8, count=m * d, offset=off).reshape(m, d).copy()
+        ids = np.frombuffer(buf, dtype="<i8", count=m, offset=off + m * d).astype(np.int64)
+        off += m * d + 8 * m
+        lists.append((ids, codes))
+    return (d, metric, int(nlist), int(nprobe), qmetric, centroids, qtype, trained, lists, rangestat, float(rangestat_arg),
+            bool(by_residual))
+
+
 # IndexRefineFlat [upstream-faiss index_write.cpp, restated from memory of the published format and UNPINNED like the
 # layouts above: there is no sample file]:
 #   fourcc "IxRF"; the index header (d, ntotal, 1<<20, 1<<20, is_trained, metric_type); the base index as its own file
@@ -1222,6 +1361,11 @@ def parse_refine(buf: bytes):
 
 
 def write_index(index, path) -> None:
+    if isinstance(index, IndexIVFScalarQuantizer):  # before its sibling: the two share a base class, not each other
+        image = index._image()  # raises on an untrained index before a file is made
+        with open(str(path), "wb") as f:
+            f.write(image)
+        return
     if isinstance(index, IndexIVFFlat):
         raise NotImplementedError("write_index of an IndexIVFFlat is not provided")
     if isinstance(index, IndexRefine):
@@ -1252,7 +1396,8 @@ def write_index(index, path) -> None:
 
 
 def read_index(path, device: int | None = None):
-    """-> IndexFlat, IndexIDMap, IndexPQ, IndexScalarQuantizer or IndexRefineFlat, as the file was written."""
+    """-> IndexFlat, IndexIDMap, IndexPQ, IndexScalarQuantizer, IndexIVFScalarQuantizer or IndexRefineFlat, as the file
+    was written."""
     with open(str(path), "rb") as f:
         buf = f.read()
     ids = None
@@ -1284,6 +1429,8 @@ def read_index(path, device: int | None = None):
         return index
     if buf[:4] == _FOURCC_SQ:
         return IndexScalarQuantizer._from_parts(parse_sq(buf), device)  # as stored: nothing is encoded again
+    if buf[:4] == _FOURCC_IVFSQ:
+        return IndexIVFScalarQuantizer._from_parts(parse_ivfsq(buf), device)  # as stored: nothing is encoded again
     if buf[:4] in (b"IwFl", b"IwF2"):  # Faiss's fourccs of IndexIVFFlat files
         raise NotImplementedError("read_index of an IndexIVFFlat file is not provided")
     if buf[:4] == _FOURCC_IDMAP:
@@ -1636,7 +1783,115 @@ class ClusteringParameters:
         self.seed = int(seed)
 
 
-class IndexIVFFlat(_IndexHandle):
+class _IndexIVF(_IndexHandle):
+    """What the inverted-list indexes share: the caller's coarse quantiser (an ``IndexFlat`` of ``nlist`` centroids),
+    its clustering in ``train``, the assignment of rows to lists, ``nprobe`` and ``search`` as ``search_preassigned`` of
+    the quantiser's answer.  A subclass creates its handle, sets ``is_trained`` and provides ``search_preassigned`` and
+    the device call of ``search_torch`` (``_search_device``)."""
+
+    def _init_ivf(self, quantizer: IndexFlat, d: int, nlist: int, metric: int) -> None:
+        assert isinstance(quantizer, IndexFlat), "the coarse quantiser is an IndexFlat"
+        assert quantizer.d == int(d), f"dimension mismatch: quantizer has d={quantizer.d}, index d={d}"
+        self.quantizer = quantizer
+        self.d = int(d)
+        self.nlist = int(nlist)
+        self.nprobe = 1
+        self.metric_type = int(metric)
+        self.cp = ClusteringParameters()
+        self.device = quantizer.device
+        self._h = ctypes.c_void_p()
+        self._lock = threading.Lock()
+
+    def _train_quantizer(self, x) -> None:
+        """Nothing when the quantiser already holds ``nlist`` centroids.  With an empty quantiser: ``Kmeans(d, nlist)``
+        on ``x`` (spherical when the quantiser is an inner-product index), ``niter`` and ``seed`` from ``self.cp``, and
+        the centroids are added to the quantiser."""
+        if self.quantizer.ntotal == self.nlist:
+            return
+        if self.quantizer.ntotal != 0:
+            raise RuntimeError(f"the quantizer holds {self.quantizer.ntotal} centroids, neither 0 nor nlist = {self.nlist}")
+        x = _as_rows(x, self.d)
+        if x.shape[0] < self.nlist:
+            raise RuntimeError(f"{x.shape[0]} training rows for nlist = {self.nlist} centroids")
+        km = Kmeans(self.d, self.nlist, niter=self.cp.niter, seed=self.cp.seed,
+                    spherical=self.quantizer.metric_type == METRIC_INNER_PRODUCT)
+        km.train(x)
+        self.quantizer.add(km.centroids)
+
+    def _require_trained(self, what: str) -> None:
+        if not self.is_trained:
+            raise RuntimeError(f"{type(self).__name__}.{what} before train")
+
+    def _check_assignment(self, lists: np.ndarray) -> None:
+        bad = np.flatnonzero(lists < 0)
+        if bad.size:
+            raise ValueError(f"row {int(bad[0])} has no nearest centroid (a NaN or inf entry?): nothing was added")
+
+    def _assign(self, x: np.ndarray) -> np.ndarray:
+        """int64 (n,): the list of every row, ``quantizer.search(x, 1)[1]``, checked."""
+        lists = np.ascontiguousarray(self.quantizer.search(x, 1)[1].reshape(-1), dtype=np.int64)
+        self._check_assignment(lists)
+        return lists
+
+    def _assign_torch(self, x):
+        """The same on the device: the route ``quantizer.search(x, 1)`` takes for this many rows, so that the ids are the
+        same; the list numbers are read back to be checked."""
+        qz = self.quantizer
+        n = x.shape[0]
+        lists = (qz.assign_torch(x) if qz._assign_applies(n, 1) else qz.search_torch(x, 1))[1].reshape(-1).contiguous()
+        self._check_assignment(lists.cpu().numpy())
+        return lists
+
+    def list_size(self, l: int) -> int:
+        sizes = np.zeros(self.nlist, dtype=np.int64)
+        _n.check(self._fn("list_sizes_host")(self._h, sizes.ctypes.data))
+        return int(sizes[int(l)])
+
+    # -- query side
+    def _nprobe(self) -> int:
+        return max(1, min(int(self.nprobe), self.nlist))
+
+    def _no_params(self, params) -> None:
+        if params is not None:
+            raise NotImplementedError(f"search parameters are not provided on {type(self).__name__}: set index.nprobe")
+
+    def search(self, x, k: int, params=None):
+        """(D float32 (nq,k), I int64 (nq,k)), fresh arrays: the k best among the rows of the ``nprobe`` lists nearest
+        to each query (``quantizer.search(x, min(nprobe, nlist))[1]``)."""
+        self._no_params(params)
+        self._require_trained("search")
+        x = _as_rows(x, self.d)
+        if x.shape[0] == 0:
+            return np.empty((0, int(k)), dtype=np.float32), np.empty((0, int(k)), dtype=np.int64)
+        return self.search_preassigned(x, k, self.quantizer.search(x, self._nprobe())[1])
+
+    def search_torch(self, xq, k: int, params=None):
+        """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out; the quantiser's search and the scan are
+        enqueued on the current torch stream.  No host synchronisation, except that the first search after an ``add``
+        rebuilds the lists and waits for that."""
+        import torch
+
+        self._no_params(params)
+        self._require_trained("search")
+        k = int(k)
+        xq, D, I, st = _torch_io(xq, torch.float32, self.d, k, torch.float32)
+        nq = xq.shape[0]
+        if nq == 0:
+            return D, I
+        probes = self.quantizer.search_torch(xq, self._nprobe())[1].contiguous()
+        with self._lock:
+            _n.check(self._search_device(self._h, xq.data_ptr(), nq, k, probes.data_ptr(), probes.shape[1], D.data_ptr(),
+                                         I.data_ptr(), st))
+        return D, I
+
+    def range_search(self, *a, **kw):
+        raise NotImplementedError(f"range_search is not provided on {type(self).__name__}")
+
+    def remove_ids(self, *a, **kw):
+        raise NotImplementedError(f"remove_ids is not provided on {type(self).__name__}")
+
+
+class IndexIVFFlat(_IndexIVF):
     """faiss.IndexIVFFlat: a coarse quantiser (an ``IndexFlat`` of ``nlist`` centroids, the caller's object) in front of
     uncompressed float32 rows.  ``add`` puts every row into the inverted list of its nearest centroid; ``search`` visits
     the ``nprobe`` lists whose centroids are nearest to the query and returns the exact k best among THEIR rows -- D has
@@ -1652,19 +1907,10 @@ class IndexIVFFlat(_IndexHandle):
     ``IndexIDMap`` over this type."""
 
     _ABI = "ise_ivf"
+    _search_device = staticmethod(_n.lib.ise_ivf_search_device)
 
     def __init__(self, quantizer: IndexFlat, d: int, nlist: int, metric: int = METRIC_L2):
-        assert isinstance(quantizer, IndexFlat), "the coarse quantiser is an IndexFlat"
-        assert quantizer.d == int(d), f"dimension mismatch: quantizer has d={quantizer.d}, index d={d}"
-        self.quantizer = quantizer
-        self.d = int(d)
-        self.nlist = int(nlist)
-        self.nprobe = 1
-        self.metric_type = int(metric)
-        self.cp = ClusteringParameters()
-        self.device = quantizer.device
-        self._h = ctypes.c_void_p()
-        self._lock = threading.Lock()
+        self._init_ivf(quantizer, d, nlist, metric)
         _n.check(_n.lib.ise_ivf_create(ctypes.byref(self._h), self.d, self.metric_type, self.nlist, self.device))
         self.is_trained = quantizer.ntotal == self.nlist
 
@@ -1684,34 +1930,16 @@ class IndexIVFFlat(_IndexHandle):
         on ``x`` (spherical when the quantiser is an inner-product index), ``niter`` and ``seed`` from ``self.cp``, and
         the centroids are added to the quantiser.  ``cp.niter`` defaults to 10, Faiss's default for an IVF's clustering
         as restated from memory: unpinned, like the seeding of ``Kmeans`` itself."""
-        if self.quantizer.ntotal == self.nlist:
-            self.is_trained = True
-            return
-        if self.quantizer.ntotal != 0:
-            raise RuntimeError(f"the quantizer holds {self.quantizer.ntotal} centroids, neither 0 nor nlist = {self.nlist}")
-        x = _as_rows(x, self.d)
-        if x.shape[0] < self.nlist:
-            raise RuntimeError(f"{x.shape[0]} training rows for nlist = {self.nlist} centroids")
-        km = Kmeans(self.d, self.nlist, niter=self.cp.niter, seed=self.cp.seed,
-                    spherical=self.quantizer.metric_type == METRIC_INNER_PRODUCT)
-        km.train(x)
-        self.quantizer.add(km.centroids)
+        self._train_quantizer(x)
         self.is_trained = True
-
-    def _check_assignment(self, lists: np.ndarray) -> None:
-        bad = np.flatnonzero(lists < 0)
-        if bad.size:
-            raise ValueError(f"row {int(bad[0])} has no nearest centroid (a NaN or inf entry?): nothing was added")
 
     def add(self, x) -> None:
         """Append rows (copied); row i of the call goes to list ``quantizer.search(x, 1)[1][i]``."""
-        if not self.is_trained:
-            raise RuntimeError("IndexIVFFlat.add before train")
+        self._require_trained("add")
         x = _as_rows(x, self.d)
         if x.shape[0] == 0:
             return
-        lists = np.ascontiguousarray(self.quantizer.search(x, 1)[1].reshape(-1), dtype=np.int64)
-        self._check_assignment(lists)
+        lists = self._assign(x)
         _n.check(_n.lib.ise_ivf_add_host(self._h, x.ctypes.data, lists.ctypes.data, x.shape[0]))
 
     def add_torch(self, x) -> None:
@@ -1719,26 +1947,17 @@ class IndexIVFFlat(_IndexHandle):
         are read back to be checked)."""
         import torch
 
-        if not self.is_trained:
-            raise RuntimeError("IndexIVFFlat.add before train")
+        self._require_trained("add")
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
         x = x.contiguous()
         n = x.shape[0]
         if n == 0:
             return
-        # the route quantizer.search(x, 1) takes for this many rows, so that the ids are the same
-        qz = self.quantizer
-        lists = (qz.assign_torch(x) if qz._assign_applies(n, 1) else qz.search_torch(x, 1))[1].reshape(-1).contiguous()
-        self._check_assignment(lists.cpu().numpy())
+        lists = self._assign_torch(x)
         st = torch.cuda.current_stream(x.device).cuda_stream
         _n.check(_n.lib.ise_ivf_add_device(self._h, x.data_ptr(), lists.data_ptr(), n, st))
 
     # -- lists
-    def list_size(self, l: int) -> int:
-        sizes = np.zeros(self.nlist, dtype=np.int64)
-        _n.check(_n.lib.ise_ivf_list_sizes_host(self._h, sizes.ctypes.data))
-        return int(sizes[int(l)])
-
     def get_list(self, l: int):
         """(ids int64 (m,), rows float32 (m, d)) of list ``l``, in list order (ascending ids)."""
         m = self.list_size(l)
@@ -1753,9 +1972,6 @@ class IndexIVFFlat(_IndexHandle):
         return _counters(_n.lib.ise_ivf_stats, self._h, ("batches", "passes", "tiles_loaded"))
 
     # -- query side
-    def _nprobe(self) -> int:
-        return max(1, min(int(self.nprobe), self.nlist))
-
     def search_preassigned(self, x, k: int, probes):
         """``search`` with the probed lists given: ``probes`` int64 (nq, nprobe); -1 entries are ignored."""
         x = _as_rows(x, self.d)
@@ -1769,45 +1985,6 @@ class IndexIVFFlat(_IndexHandle):
         _n.check(_n.lib.ise_ivf_search_host(self._h, x.ctypes.data, nq, k, probes.ctypes.data, probes.shape[1],
                                             D.ctypes.data, I.ctypes.data))
         return D, I
-
-    def search(self, x, k: int, params=None):
-        """(D float32 (nq,k), I int64 (nq,k)), fresh arrays: the k best among the rows of the ``nprobe`` lists nearest
-        to each query (``quantizer.search(x, min(nprobe, nlist))[1]``)."""
-        if params is not None:
-            raise NotImplementedError("search parameters are not provided on IndexIVFFlat: set index.nprobe")
-        if not self.is_trained:
-            raise RuntimeError("IndexIVFFlat.search before train")
-        x = _as_rows(x, self.d)
-        if x.shape[0] == 0:
-            return np.empty((0, int(k)), dtype=np.float32), np.empty((0, int(k)), dtype=np.int64)
-        return self.search_preassigned(x, k, self.quantizer.search(x, self._nprobe())[1])
-
-    def search_torch(self, xq, k: int, params=None):
-        """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out; the quantiser's search and the scan are
-        enqueued on the current torch stream.  No host synchronisation, except that the first search after an ``add``
-        rebuilds the lists and waits for that."""
-        import torch
-
-        if params is not None:
-            raise NotImplementedError("search parameters are not provided on IndexIVFFlat: set index.nprobe")
-        if not self.is_trained:
-            raise RuntimeError("IndexIVFFlat.search before train")
-        k = int(k)
-        xq, D, I, st = _torch_io(xq, torch.float32, self.d, k, torch.float32)
-        nq = xq.shape[0]
-        if nq == 0:
-            return D, I
-        probes = self.quantizer.search_torch(xq, self._nprobe())[1].contiguous()
-        with self._lock:
-            _n.check(_n.lib.ise_ivf_search_device(self._h, xq.data_ptr(), nq, k, probes.data_ptr(), probes.shape[1],
-                                                  D.data_ptr(), I.data_ptr(), st))
-        return D, I
-
-    def range_search(self, *a, **kw):
-        raise NotImplementedError("range_search is not provided on IndexIVFFlat")
-
-    def remove_ids(self, *a, **kw):
-        raise NotImplementedError("remove_ids is not provided on IndexIVFFlat")
 
 
 # ---------------------------------------------------------------- product quantisation (faiss.IndexPQ)
@@ -2026,7 +2203,7 @@ class IndexPQ(_IndexHandle):
 
 # ---------------------------------------------------------------- scalar quantisation (faiss.IndexScalarQuantizer)
 class ScalarQuantizer:
-    """``index.sq``: the view of an ``IndexScalarQuantizer``'s codec that faiss.ScalarQuantizer gives -- ``d``, ``qtype``,
+    """``index.sq``: the view of an ``IndexScalarQuantizer``'s (or ``IndexIVFScalarQuantizer``'s) codec that faiss.ScalarQuantizer gives -- ``d``, ``qtype``,
     ``code_size``, ``trained`` (a float32 copy: ``[vmin_0.., vdiff_0..]``, or ``[vmin, vdiff]`` for the uniform type),
     ``rangestat`` / ``rangestat_arg`` (only Faiss's ``RS_minmax`` with argument 0 trains), ``compute_codes`` and
     ``decode``.  The constants carry Faiss's enum values as restated from memory (unpinned, like the file layouts).
@@ -2048,10 +2225,10 @@ class ScalarQuantizer:
 
     @property
     def trained(self) -> np.ndarray:
-        if not self._index.is_trained:
+        if not getattr(self._index, "_sq_trained", self._index.is_trained):  # (an IVF index is trained with its quantiser)
             return np.zeros(0, dtype=np.float32)
         out = np.empty(self._trained_size, dtype=np.float32)
-        _n.check(_n.lib.ise_sq_get_trained_host(self._index._h, out.ctypes.data))
+        _n.check(self._index._fn("get_trained_host")(self._index._h, out.ctypes.data))
         return out
 
     def set_trained(self, t) -> None:
@@ -2065,8 +2242,8 @@ class ScalarQuantizer:
             raise ValueError("the trained state has a negative vdiff")
         if self._index.ntotal > 0:
             raise RuntimeError("set_trained on an index that holds rows: reset() first")
-        _n.check(_n.lib.ise_sq_set_trained_host(self._index._h, t.ctypes.data))
-        self._index.is_trained = True
+        _n.check(self._index._fn("set_trained_host")(self._index._h, t.ctypes.data))
+        self._index._trained_set()
 
     def compute_codes(self, x) -> np.ndarray:
         return self._index.sa_encode(x)
@@ -2103,6 +2280,9 @@ class IndexScalarQuantizer(_IndexHandle):
         self._lock = threading.Lock()
         _n.check(_n.lib.ise_sq_create(ctypes.byref(self._h), self.d, self.qtype, self.metric_type, self.device))
         self.sq = ScalarQuantizer(self)
+
+    def _trained_set(self) -> None:  # ScalarQuantizer.set_trained has set the state
+        self.is_trained = True
 
     @classmethod
     def _from_parts(cls, parts, device, add_codes: bool = True):
@@ -2265,10 +2445,196 @@ class IndexScalarQuantizer(_IndexHandle):
         raise NotImplementedError("remove_ids is not provided on IndexScalarQuantizer")
 
 
+# ---------------------------------------------------------------- inverted lists over 8-bit rows (faiss.IndexIVFScalarQuantizer)
+class IndexIVFScalarQuantizer(_IndexIVF):
+    """faiss.IndexIVFScalarQuantizer(quantizer, d, nlist, qtype, metric, by_residual) for ``ScalarQuantizer.QT_8bit`` and
+    ``QT_8bit_uniform`` with ``by_residual=False``: ``IndexIVFFlat``'s lists holding ``IndexScalarQuantizer``'s rows.  The
+    codec is that index's -- the same trained state, code bytes and decoded rows for the same ``sq.trained``.  ``add``
+    files row i under ``quantizer.search(x, 1)[1][i]``; ``search`` visits the ``nprobe`` lists nearest each query and
+    returns the exact k best among their rows by the score against the DECODED row: D has the bits
+    ``IndexScalarQuantizer.search`` reports for the same (query, row) pair, ties go by ascending id, unfilled slots are
+    -1 / +-FLT_MAX, a query with a NaN or inf entry gets padding only.  With ``nprobe == nlist`` the result is
+    ``IndexScalarQuantizer.search`` itself.
+
+    ``by_residual=True`` -- Faiss's default, and this constructor's -- raises ``NotImplementedError``: a residual code
+    makes the scan's operand differ per (query, list), which the byte-row pass does not provide.  Pass
+    ``by_residual=False``.
+
+    On the device (include/ise_knn.h, ise_ivfsq_*): ``add`` encodes into a pending buffer, the first
+    search after an ``add`` rebuilds the lists.  Not provided (they raise ``NotImplementedError``): the other quantiser
+    types, ``range_search``, ``remove_ids``, ``params=`` and ``IndexIDMap`` over this type."""
+
+    _ABI = "ise_ivfsq"
+    _search_device = staticmethod(_n.lib.ise_ivfsq_search_device)
+
+    def __init__(self, quantizer: IndexFlat, d: int, nlist: int, qtype: int = ScalarQuantizer.QT_8bit, metric: int = METRIC_L2,
+                 by_residual: bool = True):
+        if by_residual:
+            raise NotImplementedError("IndexIVFScalarQuantizer with by_residual = True (Faiss's default) is not provided: "
+                                      "pass by_residual=False (codes of the rows themselves, not of their residuals)")
+        if int(qtype) not in ScalarQuantizer._PROVIDED:
+            raise NotImplementedError(f"IndexIVFScalarQuantizer with qtype = {qtype}: only QT_8bit and QT_8bit_uniform are "
+                                      "provided")
+        self._init_ivf(quantizer, d, nlist, metric)
+        self.qtype = int(qtype)
+        self.by_residual = False
+        self.code_size = self.d
+        self._sq_trained = False
+        self._codec = None
+        _n.check(_n.lib.ise_ivfsq_create(ctypes.byref(self._h), self.d, self.qtype, self.metric_type, self.nlist, self.device))
+        self.sq = ScalarQuantizer(self)
+
+    @property
+    def is_trained(self) -> bool:
+        return self._sq_trained and self.quantizer.ntotal == self.nlist
+
+    def _trained_set(self) -> None:  # ScalarQuantizer.set_trained has set the state
+        self._sq_trained = True
+        self._codec = None
+
+    @property
+    def ntotal(self) -> int:
+        n = ctypes.c_int64(0)
+        _n.check(_n.lib.ise_ivfsq_info(self._h, None, None, None, None, ctypes.byref(n), None, None))
+        return int(n.value)
+
+    def reset(self) -> None:
+        """Drop the rows; the quantiser and the trained state (and ``is_trained``) stay."""
+        _n.check(_n.lib.ise_ivfsq_reset(self._h))
+
+    # -- build side
+    def train(self, x) -> None:
+        """The quantiser's k-means as ``IndexIVFFlat.train`` (nothing when it holds ``nlist`` centroids), then vmin /
+        vdiff from the rows' minimum and maximum as ``IndexScalarQuantizer.train`` (nothing when the state is set)."""
+        self._train_quantizer(x)
+        if not self._sq_trained:
+            IndexScalarQuantizer.train(self, x)
+
+    _check_rows = staticmethod(IndexPQ._check_rows)
+
+    def add(self, x) -> None:
+        """Encode and append rows; row i of the call goes to list ``quantizer.search(x, 1)[1][i]``.  A row with a NaN or
+        inf entry raises ``ValueError`` and nothing of the call is added."""
+        self._require_trained("add")
+        x = _as_rows(x, self.d)
+        if x.shape[0] == 0:
+            return
+        lists = self._assign(x)
+        self._check_rows(_n.lib.ise_ivfsq_add_host(self._h, x.ctypes.data, lists.ctypes.data, x.shape[0]))
+
+    def add_torch(self, x) -> None:
+        """``add`` from a CUDA float32 tensor on this index's device (no host hop for the rows; the list numbers are
+        read back to be checked and the call waits for the encoder's verdict on non-finite entries)."""
+        import torch
+
+        self._require_trained("add")
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
+        x = x.contiguous()
+        n = x.shape[0]
+        if n == 0:
+            return
+        lists = self._assign_torch(x)
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        with self._lock:
+            self._check_rows(_n.lib.ise_ivfsq_add_device(self._h, x.data_ptr(), lists.data_ptr(), n, st))
+
+    def _add_codes(self, codes: np.ndarray, lists: np.ndarray) -> None:
+        codes = _as_codes(codes, self.d)
+        lists = np.ascontiguousarray(lists, dtype=np.int64).reshape(-1)
+        assert lists.size == codes.shape[0], "one list number per code row"
+        _n.check(_n.lib.ise_ivfsq_add_codes_host(self._h, codes.ctypes.data, lists.ctypes.data, codes.shape[0]))
+
+    # -- the codec: an empty IndexScalarQuantizer with the same trained state (ise_ivfsq_* has no encode / decode entry)
+    def _codec_index(self):
+        if not self._sq_trained:
+            raise RuntimeError("IndexIVFScalarQuantizer's codec before train")
+        if self._codec is None:
+            codec = IndexScalarQuantizer(self.d, self.qtype, self.metric_type, self.device)
+            codec.sq.set_trained(self.sq.trained)
+            self._codec = codec
+        return self._codec
+
+    def sa_code_size(self) -> int:
+        return self.code_size
+
+    def sa_encode(self, x) -> np.ndarray:
+        """uint8 (n, d): the codes ``add`` would store."""
+        return self._codec_index().sa_encode(x)
+
+    def sa_decode(self, codes) -> np.ndarray:
+        return self._codec_index().sa_decode(codes)
+
+    # -- lists and statistics
+    def get_list(self, l: int):
+        """(ids int64 (m,), codes uint8 (m, d)) of list ``l``, in list order (ascending ids)."""
+        m = self.list_size(l)
+        ids = np.empty(m, dtype=np.int64)
+        codes = np.empty((m, self.d), dtype=np.uint8)
+        if self._sq_trained:
+            _n.check(_n.lib.ise_ivfsq_list_host(self._h, int(l), ids.ctypes.data, codes.ctypes.data))
+        return ids, codes
+
+    def ivfsq_stats(self) -> dict:
+        """Search batches, scan passes (one per QT(d) queries and 32 results), 64-row tiles of list rows the passes
+        visited (include/ise_knn.h, ise_ivfsq_stats).  Waits for the device."""
+        return _counters(_n.lib.ise_ivfsq_stats, self._h, ("batches", "passes", "tiles_loaded"))
+
+    # -- files
+    def _image(self) -> bytes:
+        self._require_trained("write_index")
+        qz = self.quantizer
+        lists = [self.get_list(l) for l in range(self.nlist)]
+        return serialize_ivfsq(self.d, self.metric_type, self.nlist, int(self.nprobe), qz.metric_type,
+                               qz.reconstruct_n(0, qz.ntotal), self.qtype, self.sq.trained, lists, self.sq.rangestat,
+                               self.sq.rangestat_arg, False)
+
+    @classmethod
+    def _from_parts(cls, parts, device):
+        """The index a parsed "IwSq" image describes (``parse_ivfsq``); the stored codes are added as they are, in the
+        order of their ids, which have to be the insertion numbers 0 .. ntotal - 1."""
+        d, metric, nlist, nprobe, qmetric, centroids, qtype, trained, lists, rangestat, rangestat_arg, by_residual = parts
+        if by_residual:
+            raise NotImplementedError("read_index of an IndexIVFScalarQuantizer file with by_residual = true is not provided")
+        quantizer = IndexFlat(d, qmetric, device)
+        if centroids.shape[0]:
+            quantizer.add(centroids)
+        index = cls(quantizer, d, nlist, qtype, metric, by_residual=False)
+        index.nprobe = nprobe
+        index.sq.rangestat, index.sq.rangestat_arg = rangestat, rangestat_arg
+        index.sq.set_trained(trained)
+        ids = np.concatenate([ids for ids, _ in lists]) if lists else np.zeros(0, np.int64)
+        if ids.size:
+            order = np.argsort(ids, kind="stable")
+            if not np.array_equal(ids[order], np.arange(ids.size)):
+                raise RuntimeError("an IndexIVFScalarQuantizer file whose ids are not the insertion numbers 0 .. ntotal - 1 "
+                                   "is not readable")
+            codes = np.concatenate([codes for _, codes in lists])
+            list_no = np.repeat(np.arange(nlist, dtype=np.int64), [len(ids) for ids, _ in lists])
+            index._add_codes(codes[order], list_no[order])
+        return index
+
+    # -- query side
+    def search_preassigned(self, x, k: int, probes):
+        """``search`` with the probed lists given: ``probes`` int64 (nq, nprobe); -1 entries are ignored."""
+        self._require_trained("search")
+        x = _as_rows(x, self.d)
+        k = int(k)
+        assert k > 0
+        nq = x.shape[0]
+        probes = np.ascontiguousarray(np.asarray(probes), dtype=np.int64)
+        assert probes.ndim == 2 and probes.shape[0] == nq and probes.shape[1] >= 1
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        if nq:
+            _n.check(_n.lib.ise_ivfsq_search_host(self._h, x.ctypes.data, nq, k, probes.ctypes.data, probes.shape[1],
+                                                  D.ctypes.data, I.ctypes.data))
+        return D, I
+
+
 # ---------------------------------------------------------------- exact re-ranking (faiss.IndexRefine / IndexRefineFlat)
 class IndexRefine:
     """faiss.IndexRefine(base_index, refine_index): ``search`` asks ``base_index`` -- an ``IndexFlat`` of either storage,
-    an ``IndexPQ``, an ``IndexScalarQuantizer`` or an ``IndexIVFFlat`` -- for ``int(k * k_factor)`` labels and returns the k best of them by the exact
+    an ``IndexPQ``, an ``IndexScalarQuantizer``, an ``IndexIVFFlat`` or an ``IndexIVFScalarQuantizer`` -- for ``int(k * k_factor)`` labels and returns the k best of them by the exact
     score ``refine_index`` (a float32 ``IndexFlat`` that holds the same rows) computes: D has the bits
     ``refine_index.search`` reports for the same (query, row) pair, ties go by ascending id, unfilled slots are
     -1 / +-FLT_MAX; -1 labels of the base are ignored.  With ``k * k_factor >= ntotal`` the result is
@@ -2279,8 +2645,8 @@ class IndexRefine:
     ``NotImplementedError``): ``range_search``, ``remove_ids`` and ``IndexIDMap`` over this type."""
 
     def __init__(self, base_index, refine_index):
-        assert isinstance(base_index, (IndexFlat, IndexPQ, IndexScalarQuantizer, IndexIVFFlat)), \
-            "the base index is an IndexFlat, an IndexPQ, an IndexScalarQuantizer or an IndexIVFFlat"
+        assert isinstance(base_index, (IndexFlat, IndexPQ, IndexScalarQuantizer, _IndexIVF)), \
+            "the base index is an IndexFlat, an IndexPQ, an IndexScalarQuantizer, an IndexIVFFlat or an IndexIVFScalarQuantizer"
         assert base_index.ntotal == 0, f"{type(self).__name__} wraps an empty index (Faiss: index is empty on input)"
         assert isinstance(refine_index, IndexFlat) and refine_index.storage == "f32", \
             "the refine index is a float32 IndexFlat"

@@ -81,7 +81,9 @@ def create_search_index(data_array, index_type="cosine"):
     without the lists: IndexPQ with the reference's m = 16 codes of 8 bits, trained on the data, then add.
     'pq-refine' is that index under IndexRefineFlat: its k * 16 best rows re-ranked by their exact float32 distance.
     'sq8' is IndexScalarQuantizer with QT_8bit: one byte per entry between the data's per-dimension minimum and maximum,
-    trained on the data, then add."""
+    trained on the data, then add.  'cell-probe-sq8' is the cell-probe branch with that quantiser in place of the product
+    quantiser: IndexIVFScalarQuantizer (QT_8bit, by_residual=False) over an L2 coarse quantiser with the reference's 8
+    centroids and nprobe = 5, trained on the data, then add."""
     num_features = data_array.shape[1]
     if index_type == "cosine":
         index = faiss.IndexFlatIP(num_features)
@@ -107,6 +109,13 @@ def create_search_index(data_array, index_type="cosine"):
         index.train(data_array)
     elif index_type == "sq8":
         index = faiss.IndexScalarQuantizer(num_features, faiss.ScalarQuantizer.QT_8bit)
+        index.train(data_array)
+    elif index_type == "cell-probe-sq8":
+        ncentroids = 8
+        coarse_quantizer = faiss.IndexFlatL2(num_features)
+        index = faiss.IndexIVFScalarQuantizer(coarse_quantizer, num_features, ncentroids, faiss.ScalarQuantizer.QT_8bit,
+                                              faiss.METRIC_L2, by_residual=False)
+        index.nprobe = 5  # find n most similar clusters
         index.train(data_array)
     else:
         raise ValueError(f"unknown index_type {index_type!r}")

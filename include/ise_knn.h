@@ -558,6 +558,51 @@ int ise_sq_search_host(ise_sq_t* h, const float* q, int64_t nq, int k, float* D,
 int ise_sq_search_device(ise_sq_t* h, const float* q_dev, int64_t nq, int k, float* D_dev, int64_t* I_dev, void* stream);
 int ise_sq_stats(ise_sq_t* h, uint64_t* out3);
 
+/* Inverted lists over scalar-quantised rows: faiss.IndexIVFScalarQuantizer with by_residual = false and the two 8-bit
+ * types (csrc/ise_ivfsq.hpp).  An ise_ivfsq_t is ise_ivf_t's lists holding ise_sq_t's rows: nlist lists of d code bytes
+ * plus one float64 per row, NO centroids (the coarse quantiser is the caller's; rows come with their list numbers,
+ * searches with their probe tables, as for ise_ivf_*), and the codec, trained state, code bytes and scores of ise_sq_*
+ * for the same trained vector.  Calls, streams and workspaces as for ise_ivf_*.
+ *   create        1 <= d <= ISE_SQ_MAX_D, nlist >= 1, one of the two types, one of the two metrics; anything else is
+ *                 ISE_E_INVALID before the device is touched.  Untrained until the trained state is set; every entry
+ *                 point below except reset / info / list_sizes / stats is then ISE_E_INVALID
+ *   trained       as ise_sq_set_trained_host / ise_sq_get_trained_host
+ *   add           list_no[i] in [0, nlist) is the list of row i; a number outside makes the call ISE_E_INVALID and
+ *                 nothing is added.  The rows are encoded at once into a pending buffer of codes and row terms; a row
+ *                 with a NaN or inf entry makes the call ISE_E_INVALID ("NaN or inf" in the message) and NOTHING of that
+ *                 call is added.  All forms block.  add_codes takes ready-made codes (n x d bytes).  A row's id is its
+ *                 insertion number; fewer than 2^32 rows.  The first search or list_host after an add rebuilds the lists
+ *                 (64-row tiles; one rebuild moves the whole index)
+ *   list_sizes    rows per list, pending ones included
+ *   list          ids (ascending) and codes (m x d bytes) of one list, in list order; either may be NULL
+ *   search        probes: nq x nprobe list numbers; -1 and numbers outside [0, nlist) name nothing, a list named twice
+ *                 counts once.  The k best among the rows of a query's probed lists, scored as ise_sq_search_* scores
+ *                 the same (query, row) pair; ties by ascending id; unfilled slots are id -1 with +-FLT_MAX; a query with
+ *                 a NaN or inf entry gets padding only.  A pass serves QT queries and 32 results (QT as for ise_sq_*) and
+ *                 reads the 64-row tiles of the lists that at least one of its queries probes, and no others; a call
+ *                 makes ceil(nq / QT) x ceil(k / 32) passes, none on an empty index.  search_device only enqueues, unless
+ *                 rows are pending or a workspace has to grow; search_host works through 4096 queries at a time
+ *   stats         out3[0] = search batches, out3[1] = scan passes, out3[2] = 64-row tiles the passes visited.  Waits
+ *                 for the device */
+typedef struct ise_ivfsq ise_ivfsq_t;
+int ise_ivfsq_create(ise_ivfsq_t** out, int d, int qtype, int metric, int nlist, int device);
+int ise_ivfsq_destroy(ise_ivfsq_t* h); /* NULL is a no-op */
+int ise_ivfsq_reset(ise_ivfsq_t* h);   /* drop all rows, keep the trained state */
+int ise_ivfsq_info(const ise_ivfsq_t* h, int* d, int* qtype, int* metric, int* nlist, int64_t* ntotal, int* is_trained,
+                   int* device);
+int ise_ivfsq_set_trained_host(ise_ivfsq_t* h, const float* t /* 2 d floats, or 2 for the uniform type */);
+int ise_ivfsq_get_trained_host(ise_ivfsq_t* h, float* t);
+int ise_ivfsq_add_host(ise_ivfsq_t* h, const float* x, const int64_t* list_no, int64_t n);
+int ise_ivfsq_add_device(ise_ivfsq_t* h, const float* x_dev, const int64_t* list_no_dev, int64_t n, void* stream);
+int ise_ivfsq_add_codes_host(ise_ivfsq_t* h, const uint8_t* codes, const int64_t* list_no, int64_t n);
+int ise_ivfsq_list_sizes_host(ise_ivfsq_t* h, int64_t* sizes /* nlist */);
+int ise_ivfsq_list_host(ise_ivfsq_t* h, int list, int64_t* ids, uint8_t* codes);
+int ise_ivfsq_search_host(ise_ivfsq_t* h, const float* q, int64_t nq, int k, const int64_t* probes, int nprobe, float* D,
+                          int64_t* I);
+int ise_ivfsq_search_device(ise_ivfsq_t* h, const float* q_dev, int64_t nq, int k, const int64_t* probes_dev, int nprobe,
+                            float* D_dev, int64_t* I_dev, void* stream);
+int ise_ivfsq_stats(ise_ivfsq_t* h, uint64_t* out3);
+
 /* Shard-local search for the multi-GPU path: writes nq x k
  * packed candidates, sorted best-first, suitable for one all-gather:
  *   key = (order-preserving uint32 image of the score) << 32 | (row + id_base)
