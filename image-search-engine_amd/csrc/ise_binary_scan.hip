@@ -3,9 +3,9 @@
 // range search; the reference's DHASH method (backend/engine.py:82-91) asks it for "every image within r bits".
 //
 // Calls on one handle run one at a time (a mutex; the host forms hold it until their results are back, the device
-// forms while they enqueue).  The handle has ONE set of workspaces: work enqueued on another stream than the previous
-// call's waits for that call through an event, and a workspace that has to grow is replaced only after the device
-// has drained.
+// forms while they enqueue).  The handle has ONE set of workspaces: every call that touches them waits for the call
+// before and marks its own end (CallOrder, ise_host.hpp), and a workspace that has to grow is replaced by the drained
+// rule (grow_drained, ise_host.hpp).
 //
 // Selectors and removal mirror the float index (ise_knn.hip): a selector is a device bitmap bound to
 // the handle, its ntotal and its ROW EPOCH (bumped by whatever removes rows: a reset of a non-empty index, a removal
@@ -21,32 +21,12 @@
 #define BIN_RANGE_NQ_CHUNK 256 /* queries per range batch: one host synchronisation each */
 static_assert(BIN_RANGE_NQ_CHUNK <= 256, "binary_lims_kernel scans a batch's totals in one block of 256 threads");
 
-namespace {
-// rule: device-wide drain before a free (any stream may still use the handle's ONE set), and half again on top so growth drains rarely
-template <class T>
-int bin_grow(DevBuf<T>& b, size_t need) {
-    if (b.p && need <= b.n) return ISE_OK;
-    if (b.p) {
-        HIP_TRY(hipDeviceSynchronize());  // work in flight on any stream may still use the old one
-        (void)hipFree(b.p);
-    }
-    b.p = nullptr;
-    b.n = 0;
-    const size_t want = std::max<size_t>(need + need / 2, 16);
-    HIP_TRY(hipMalloc((void**)&b.p, want * sizeof(T)));
-    b.n = want;
-    return ISE_OK;
-}
-}  // namespace
-
 struct ise_binary_index {
     int d_bits = 0, code_size = 0, ws = 0, device = 0, num_cu = 256;
     long long n = 0, cap = 0;
     u64* codes = nullptr;  // [cap][ws]; bytes past code_size of every row are zero
     hipStream_t stream = nullptr;
-    hipEvent_t last = nullptr;  // the end of the previous call's device work
-    hipStream_t last_stream = nullptr;
-    bool last_valid = false;
+    CallOrder order;
     mutable std::mutex mu;
     DevBuf<uint8_t> raw;       // host forms: the queries as passed
     DevBuf<u64> qpad, lo, lists;
@@ -71,18 +51,6 @@ struct ise_binary_range_result {
 namespace {
 int bin_wt(const ise_binary_index* h) { return h->ws == 1 ? 1 : h->ws == 2 ? 2 : 0; }
 size_t bin_query_lds(const ise_binary_index* h) { return bin_wt(h) == 0 ? (size_t)BIN_QT * h->ws * 8 : 0; }
-
-// order this call's device work behind the previous call's, and mark its own end
-int bin_begin(ise_binary_index* h, hipStream_t st) {
-    if (h->last_valid && h->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->last, 0));
-    return ISE_OK;
-}
-int bin_end(ise_binary_index* h, hipStream_t st) {
-    HIP_TRY(hipEventRecord(h->last, st));
-    h->last_stream = st;
-    h->last_valid = true;
-    return ISE_OK;
-}
 
 // mk: the selector's mask and window (the masked kernels), or null
 void launch_scan(int wt, unsigned grid, size_t lds, hipStream_t st, const BinScanParams& sp, const BinMask* mk) {
@@ -159,7 +127,7 @@ int reserve_codes(ise_binary_index* h, long long need, hipStream_t st) {
     if (e == hipSuccess && h->codes) e = hipDeviceSynchronize();  // searches in flight still read the old storage
     if (e != hipSuccess) {
         (void)hipFree(nx);
-        return ise_fail_(ISE_E_HIP, std::string("growing the code storage: ") + hipGetErrorString(e));
+        return ise_fail_(e == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP, std::string("growing the code storage: ") + hipGetErrorString(e));
     }
     if (h->codes) (void)hipFree(h->codes);
     h->codes = nx;
@@ -175,21 +143,21 @@ void pad_rows(const uint8_t* src_dev, int code_size, u64* dst, int ws, long long
 
 int add_device_locked(ise_binary_index* h, const uint8_t* x_dev, long long n, hipStream_t st) {
     if (h->n + n >= (1ll << 32)) return ise_fail_(ISE_E_INVALID, "a binary index holds fewer than 2^32 rows");
-    int rc = bin_begin(h, st);
+    int rc = h->order.wait(st);
     if (rc) return rc;
     rc = reserve_codes(h, h->n + n, st);
     if (rc) return rc;
     pad_rows(x_dev, h->code_size, h->codes + (size_t)h->n * h->ws, h->ws, n, st);
     HIP_TRY(hipGetLastError());
     h->n += n;
-    return bin_end(h, st);
+    return h->order.mark(st);
 }
 
 // q_dev: nq x code_size bytes on the device; D_dev / I_dev: nq x k.  sel: among the selector's rows only (checked by
 // the caller; the masked kernels over its window), or null
 int search_enqueue(ise_binary_index* h, const uint8_t* q_dev, long long nq, int k, int* D_dev, long long* I_dev,
                    hipStream_t st, const ise_binary_selector* sel = nullptr) {
-    int rc = bin_begin(h, st);
+    int rc = h->order.wait(st);
     if (rc) return rc;
     uint64_t& st_batches = sel ? h->st_sel : h->st_search;
     uint64_t& st_pass = sel ? h->st_sel_passes : h->st_passes;
@@ -198,15 +166,15 @@ int search_enqueue(ise_binary_index* h, const uint8_t* q_dev, long long nq, int 
         const long long cnt = nq * k;
         hipLaunchKernelGGL(binary_fill_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, cnt);
         HIP_TRY(hipGetLastError());
-        return bin_end(h, st);
+        return h->order.mark(st);
     }
     BinMask mk{};
     if (sel) mk = selector_mask(sel);
     const unsigned grid = sel ? bin_grid_tiles(h, mk.tile1 - mk.tile0) : bin_grid(h);
     const long long nq16 = (nq + BIN_QT - 1) / BIN_QT * BIN_QT;
-    if ((rc = bin_grow(h->qpad, (size_t)nq16 * h->ws))) return rc;
-    if ((rc = bin_grow(h->lo, (size_t)nq16))) return rc;
-    if ((rc = bin_grow(h->lists, (size_t)grid * BIN_QT * BIN_KPASS))) return rc;
+    if ((rc = grow_drained(h->qpad, (size_t)nq16 * h->ws))) return rc;
+    if ((rc = grow_drained(h->lo, (size_t)nq16))) return rc;
+    if ((rc = grow_drained(h->lists, (size_t)grid * BIN_QT * BIN_KPASS))) return rc;
     st_batches++;  // counted once the batch is certain to be enqueued
     pad_rows(q_dev, h->code_size, h->qpad.p, h->ws, nq, st);
     const int wt = bin_wt(h);
@@ -244,18 +212,14 @@ int search_enqueue(ise_binary_index* h, const uint8_t* q_dev, long long nq, int 
         }
     }
     HIP_TRY(hipGetLastError());
-    return bin_end(h, st);
+    return h->order.mark(st);
 }
 
 int check_handle(const ise_binary_index* h) { return h ? ISE_OK : ise_fail_(ISE_E_INVALID, "binary index handle is NULL"); }
 
-int check_search_args(const ise_binary_index* h, const void* q, long long nq, int k) {
+int check_search_args(const ise_binary_index* h, const void* q, long long nq, int k, const void* D, const void* I) {
     if (check_handle(h)) return ISE_E_INVALID;
-    if (nq < 0) return ise_fail_(ISE_E_INVALID, "nq must be >= 0");
-    if (k < 1 || k > ISE_MAX_K) return ise_fail_(ISE_E_INVALID, "k must be in [1, ISE_MAX_K]");
-    if (nq > 0 && !q) return ise_fail_(ISE_E_INVALID, "query pointer is NULL");
-    if (nq * (long long)k >= (1ll << 40)) return ise_fail_(ISE_E_INVALID, "nq * k is too large");
-    return ISE_OK;
+    return check_knn_args(q, nq, k, D, I);
 }
 
 // one batch of m <= BIN_RANGE_NQ_CHUNK queries (host pointer) appended to the result.  sel: the segments cut the
@@ -272,12 +236,12 @@ int range_batch(ise_binary_index* h, hipStream_t st, const uint8_t* q, long long
     long long seg_rows = ((sel ? (mkv.tile1 - mkv.tile0) * 64 : h->n) + S - 1) / S;
     seg_rows = (seg_rows + 63) / 64 * 64;
     const long long M = m * S;
-    if ((rc = bin_grow(h->raw, (size_t)m * h->code_size))) return rc;
-    if ((rc = bin_grow(h->qpad, (size_t)m16 * h->ws))) return rc;
-    if ((rc = bin_grow(h->counts, (size_t)M))) return rc;
-    if ((rc = bin_grow(h->offs, (size_t)M))) return rc;
-    if ((rc = bin_grow(h->lims, (size_t)m + 1))) return rc;
-    if ((rc = bin_grow(h->totals, (size_t)m))) return rc;
+    if ((rc = grow_drained(h->raw, (size_t)m * h->code_size))) return rc;
+    if ((rc = grow_drained(h->qpad, (size_t)m16 * h->ws))) return rc;
+    if ((rc = grow_drained(h->counts, (size_t)M))) return rc;
+    if ((rc = grow_drained(h->offs, (size_t)M))) return rc;
+    if ((rc = grow_drained(h->lims, (size_t)m + 1))) return rc;
+    if ((rc = grow_drained(h->totals, (size_t)m))) return rc;
     HIP_TRY(hipMemcpyAsync(h->raw.p, q, (size_t)m * h->code_size, hipMemcpyHostToDevice, st));
     pad_rows(h->raw.p, h->code_size, h->qpad.p, h->ws, m, st);
     const int wt = bin_wt(h);
@@ -306,8 +270,8 @@ int range_batch(ise_binary_index* h, hipStream_t st, const uint8_t* q, long long
     const size_t at = res->D.size();
     for (long long i = 1; i <= m; i++) res->lims.push_back((int64_t)at + lims[(size_t)i]);
     if (total == 0) return ISE_OK;
-    if ((rc = bin_grow(h->rD, (size_t)total))) return rc;
-    if ((rc = bin_grow(h->rI, (size_t)total))) return rc;
+    if ((rc = grow_drained(h->rD, (size_t)total))) return rc;
+    if ((rc = grow_drained(h->rI, (size_t)total))) return rc;
     rp.D = h->rD.p;
     rp.I = h->rI.p;
     for (long long q0 = 0; q0 < m; q0 += BIN_QT) {
@@ -344,14 +308,9 @@ extern "C" int ise_binary_index_create(ise_binary_index_t** out, int d_bits, int
     *out = nullptr;
     if (d_bits <= 0 || d_bits % 8 != 0 || d_bits > ISE_BINARY_MAX_BITS)
         return ise_fail_(ISE_E_INVALID, "d_bits must be a positive multiple of 8, at most ISE_BINARY_MAX_BITS");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return ise_fail_(ISE_E_NODEVICE, "no HIP device visible: the kNN path needs an MI355X (gfx950) GPU");
-    if (device < 0 || device >= ndev) return ise_fail_(ISE_E_INVALID, "device out of range");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return ise_fail_(ISE_E_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    int num_cu = 0;
+    const int rc = device_gate(device, &num_cu);
+    if (rc) return rc;
     ise_binary_index* h = new (std::nothrow) ise_binary_index();
     if (!h) return ise_fail_(ISE_E_NOMEM, "host allocation failed");
     h->d_bits = d_bits;
@@ -359,14 +318,14 @@ extern "C" int ise_binary_index_create(ise_binary_index_t** out, int d_bits, int
     const int w = (h->code_size + 7) / 8;
     h->ws = w == 1 ? 1 : (w + 1) / 2 * 2;
     h->device = device;
-    h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    h->num_cu = num_cu;
     DeviceGuard gd(device);
     if (!gd.ok) {
         delete h;
         return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     }
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->last, hipEventDisableTiming);
+    if (e == hipSuccess) e = h->order.create();
     if (e != hipSuccess) {
         if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
@@ -382,7 +341,7 @@ extern "C" int ise_binary_index_destroy(ise_binary_index_t* h) {
         DeviceGuard gd(h->device);
         (void)hipDeviceSynchronize();
         free_buffers(h);
-        if (h->last) (void)hipEventDestroy(h->last);
+        h->order.destroy();
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
     delete h;
@@ -423,10 +382,10 @@ extern "C" int ise_binary_index_add_host(ise_binary_index_t* h, const uint8_t* c
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(h->mu);
-    const long long step = std::max<long long>(1, (1ll << 28) / h->code_size);  // 256 MiB of codes per upload
+    const long long step = upload_step((size_t)h->code_size);
     for (long long i0 = 0; i0 < n; i0 += step) {
         const long long m = std::min<long long>(step, n - i0);
-        int rc = bin_grow(h->raw, (size_t)m * h->code_size);
+        int rc = grow_drained(h->raw, (size_t)m * h->code_size);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(h->raw.p, codes + (size_t)i0 * h->code_size, (size_t)m * h->code_size, hipMemcpyHostToDevice,
                                h->stream));
@@ -445,21 +404,20 @@ extern "C" int ise_binary_index_reconstruct_host(ise_binary_index_t* h, int64_t 
     if (!out) return ise_fail_(ISE_E_INVALID, "out is NULL");
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
-    int rc = bin_begin(h, h->stream);
+    int rc = h->order.wait(h->stream);
     if (rc) return rc;
     HIP_TRY(hipMemcpy2DAsync(out, (size_t)h->code_size, h->codes + (size_t)i0 * h->ws, (size_t)h->ws * 8, (size_t)h->code_size,
                              (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if ((rc = bin_end(h, h->stream))) return rc;
+    if ((rc = h->order.mark(h->stream))) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ISE_OK;
 }
 
 extern "C" int ise_binary_index_search_device(ise_binary_index_t* h, const uint8_t* q_dev, int64_t nq, int k, int32_t* D_dev,
                                               int64_t* I_dev, void* stream) {
-    int rc = check_search_args(h, q_dev, nq, k);
+    int rc = check_search_args(h, q_dev, nq, k, D_dev, I_dev);
     if (rc) return rc;
     if (nq == 0) return ISE_OK;
-    if (!D_dev || !I_dev) return ise_fail_(ISE_E_INVALID, "output pointer is NULL");
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(h->mu);
@@ -468,18 +426,17 @@ extern "C" int ise_binary_index_search_device(ise_binary_index_t* h, const uint8
 
 extern "C" int ise_binary_index_search_host(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int k, int32_t* D,
                                             int64_t* I) {
-    int rc = check_search_args(h, q, nq, k);
+    int rc = check_search_args(h, q, nq, k, D, I);
     if (rc) return rc;
     if (nq == 0) return ISE_OK;
-    if (!D || !I) return ise_fail_(ISE_E_INVALID, "output pointer is NULL");
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(h->mu);
     const size_t cnt = (size_t)nq * k;
-    if ((rc = bin_grow(h->raw, (size_t)nq * h->code_size))) return rc;
-    if ((rc = bin_grow(h->oD, cnt))) return rc;
-    if ((rc = bin_grow(h->oI, cnt))) return rc;
-    if ((rc = bin_begin(h, h->stream))) return rc;
+    if ((rc = grow_drained(h->raw, (size_t)nq * h->code_size))) return rc;
+    if ((rc = grow_drained(h->oD, cnt))) return rc;
+    if ((rc = grow_drained(h->oI, cnt))) return rc;
+    if ((rc = h->order.wait(h->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(h->raw.p, q, (size_t)nq * h->code_size, hipMemcpyHostToDevice, h->stream));
     if ((rc = search_enqueue(h, h->raw.p, nq, k, h->oD.p, h->oI.p, h->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(D, h->oD.p, cnt * 4, hipMemcpyDeviceToHost, h->stream));
@@ -509,13 +466,13 @@ static int range_search_impl(ise_binary_index_t* h, const uint8_t* q, int64_t nq
         if (!rc && (h->n == 0 || radius <= 0 || (filtered && sel->count == 0))) {
             res->lims.resize((size_t)nq + 1, 0);  // nothing can match: no pass
         } else if (!rc) {
-            rc = bin_begin(h, h->stream);
+            rc = h->order.wait(h->stream);
             for (long long q0 = 0; q0 < nq && !rc; q0 += BIN_RANGE_NQ_CHUNK) {
                 const long long m = std::min<long long>(BIN_RANGE_NQ_CHUNK, nq - q0);
                 (filtered ? h->st_sel_range : h->st_range)++;
                 rc = range_batch(h, h->stream, q + (size_t)q0 * h->code_size, m, radius, res, sel);
             }
-            if (!rc) rc = bin_end(h, h->stream);  // the workspaces' last user, as after every other call
+            if (!rc) rc = h->order.mark(h->stream);  // the workspaces' last user, as after every other call
         }
     } catch (const std::bad_alloc&) {
         rc = ise_fail_(ISE_E_NOMEM, "host allocation of the range result failed");
@@ -630,10 +587,9 @@ extern "C" int ise_binary_selector_destroy(ise_binary_selector_t* sel) {
 extern "C" int ise_binary_index_search_sel_device(ise_binary_index_t* h, const uint8_t* q_dev, int64_t nq, int k,
                                                   const ise_binary_selector_t* sel, int32_t* D_dev, int64_t* I_dev,
                                                   void* stream) {
-    int rc = check_search_args(h, q_dev, nq, k);
+    int rc = check_search_args(h, q_dev, nq, k, D_dev, I_dev);
     if (rc) return rc;
     if (!sel) return ise_fail_(ISE_E_INVALID, "selector is NULL");
-    if (nq > 0 && (!D_dev || !I_dev)) return ise_fail_(ISE_E_INVALID, "output pointer is NULL");
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(h->mu);
@@ -644,20 +600,19 @@ extern "C" int ise_binary_index_search_sel_device(ise_binary_index_t* h, const u
 
 extern "C" int ise_binary_index_search_sel_host(ise_binary_index_t* h, const uint8_t* q, int64_t nq, int k,
                                                 const ise_binary_selector_t* sel, int32_t* D, int64_t* I) {
-    int rc = check_search_args(h, q, nq, k);
+    int rc = check_search_args(h, q, nq, k, D, I);
     if (rc) return rc;
     if (!sel) return ise_fail_(ISE_E_INVALID, "selector is NULL");
-    if (nq > 0 && (!D || !I)) return ise_fail_(ISE_E_INVALID, "output pointer is NULL");
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(h->mu);
     if ((rc = selector_check_locked(h, sel))) return rc;
     if (nq == 0) return ISE_OK;
     const size_t cnt = (size_t)nq * k;
-    if ((rc = bin_grow(h->raw, (size_t)nq * h->code_size))) return rc;
-    if ((rc = bin_grow(h->oD, cnt))) return rc;
-    if ((rc = bin_grow(h->oI, cnt))) return rc;
-    if ((rc = bin_begin(h, h->stream))) return rc;
+    if ((rc = grow_drained(h->raw, (size_t)nq * h->code_size))) return rc;
+    if ((rc = grow_drained(h->oD, cnt))) return rc;
+    if ((rc = grow_drained(h->oI, cnt))) return rc;
+    if ((rc = h->order.wait(h->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(h->raw.p, q, (size_t)nq * h->code_size, hipMemcpyHostToDevice, h->stream));
     if ((rc = search_enqueue(h, h->raw.p, nq, k, h->oD.p, h->oI.p, h->stream, sel))) return rc;
     HIP_TRY(hipMemcpyAsync(D, h->oD.p, cnt * 4, hipMemcpyDeviceToHost, h->stream));
@@ -741,7 +696,7 @@ int remove_runs_locked(ise_binary_index* h, const std::vector<RemoveRun>& runs, 
     // the tail [n_new, n_old) keeps its stale rows: masked by row number, like the rows a reset leaves behind
     h->n = n_new;
     h->row_epoch++;  // rows were renumbered: selectors made before are stale
-    h->last_valid = false;  // the device has drained: nothing to order the next call behind
+    h->order.forget();  // the device has drained
     h->st_rm_calls++;
     h->st_rm_rows += (uint64_t)removed;
     h->st_rm_moved += (uint64_t)moved;

@@ -1,6 +1,9 @@
-// ise_ivf_plan.hpp -- the host bookkeeping of an inverted-list rebuild (ise_ivf.hip): a stable counting sort of the
-// pending rows' list numbers.  Plain C++ with no device call, so a stand-alone program can run it under a sanitizer.
+// ise_ivf_plan.hpp -- the host bookkeeping of the inverted lists (ise_ivf.hip, ise_ivfsq.hip; their device side is
+// ise_ivf_lists.hpp): the plan of a rebuild (a stable counting sort of the pending rows' list numbers), the table the
+// kernels read built from it, the check of list numbers, and the counts a handle keeps between rebuilds.  Plain C++
+// with no device call, so a stand-alone program can run it under a sanitizer.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -40,3 +43,65 @@ inline bool ivf_plan_rebuild(const std::vector<long long>& old_size, const int32
     }
     return true;
 }
+
+// the table the kernels read, the ONE place that knows its layout: list_tile0 [nlist + 1] | list_size [nlist] |
+// tile_list [tiles]
+inline size_t ivf_meta_size_at(size_t nlist) { return nlist + 1; }
+inline size_t ivf_meta_tile_list_at(size_t nlist) { return 2 * nlist + 1; }
+inline std::vector<uint32_t> ivf_plan_meta(const IvfPlan& pl) {
+    const size_t nlist = pl.size.size();
+    std::vector<uint32_t> meta(ivf_meta_tile_list_at(nlist) + pl.tile_list.size());
+    std::copy(pl.tile0.begin(), pl.tile0.end(), meta.begin());
+    for (size_t l = 0; l < nlist; l++) meta[ivf_meta_size_at(nlist) + l] = (uint32_t)pl.size[l];
+    std::copy(pl.tile_list.begin(), pl.tile_list.end(), meta.begin() + ivf_meta_tile_list_at(nlist));
+    return meta;
+}
+
+// the first row whose list number is not one of the nlist lists, or -1
+inline long long ivf_first_bad_list(const int64_t* list_no, long long n, int nlist) {
+    for (long long i = 0; i < n; i++)
+        if (list_no[i] < 0 || list_no[i] >= nlist) return i;
+    return -1;
+}
+
+// what a handle knows of its lists on the host (its mutex held)
+struct IvfBook {
+    int nlist = 0;
+    long long n = 0;      // rows in all, the pending ones included
+    long long tiles = 0;  // of the sorted array
+    std::vector<long long> size;      // [nlist] rows per list in the sorted array
+    std::vector<long long> size_all;  // ... with the pending rows
+    std::vector<uint32_t> tile0;      // [nlist + 1] first tile of every list in the sorted array
+    // rows added since the last rebuild, in insertion order
+    long long pend_n = 0;
+    std::vector<int32_t> pend_list;
+
+    // no rows, sorted or pending
+    void clear() {
+        n = tiles = pend_n = 0;
+        pend_list.clear();
+        size.assign((size_t)nlist, 0);
+        size_all.assign((size_t)nlist, 0);
+        tile0.assign((size_t)nlist + 1, 0u);
+    }
+    // m more rows are in the pending buffer (list numbers checked): book them
+    void add(const int64_t* list_no, long long m) {
+        pend_list.reserve(pend_list.size() + (size_t)m);
+        for (long long i = 0; i < m; i++) {
+            pend_list.push_back((int32_t)list_no[i]);
+            size_all[(size_t)list_no[i]]++;
+        }
+        pend_n += m;
+        n += m;
+    }
+    bool plan(IvfPlan* pl, int tile_rows) const { return ivf_plan_rebuild(size, pend_list.data(), pend_n, pl, tile_rows); }
+    // the arrays of a finished plan are in place: nothing is pending any more
+    void take_over(const IvfPlan& pl) {
+        pend_n = 0;
+        pend_list.clear();
+        pend_list.shrink_to_fit();
+        tiles = pl.tile0[size.size()];
+        size = pl.size;
+        tile0 = pl.tile0;
+    }
+};

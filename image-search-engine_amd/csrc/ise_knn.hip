@@ -29,7 +29,7 @@
 //   selectors      ise_sel_scan.hpp  search / range search among the rows a device bitmap names: one masked pass per 16 queries
 //
 // Host headers shared with the other index kinds (ise_binary_scan.hip, ise_ivf.hip)
-//   ise_host.hpp         ise_fail_ (defined here), HIP_TRY, DevBuf
+//   ise_host.hpp         ise_fail_ (defined here), HIP_TRY, the device gate of every *_create, DevBuf
 //   ise_selector.hpp     the selector object: allocate, fill, census, info, free
 //   ise_remove_plan.hpp  remove_ids planning without a device call: ids -> runs -> g / cend tables, slab size
 //
@@ -287,15 +287,9 @@ extern "C" int ise_index_create_ex(ise_index_t** out, int d, int metric, int dev
         return fail(ISE_E_INVALID, "storage must be ISE_STORE_F32 or ISE_STORE_BF16");
     if (metric != ISE_METRIC_L2 && metric != ISE_METRIC_INNER_PRODUCT)
         return fail(ISE_E_INVALID, "metric must be ISE_METRIC_L2 or ISE_METRIC_INNER_PRODUCT");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(ISE_E_NODEVICE, "no HIP device visible: the kNN path needs an MI355X (gfx950) GPU");
-    if (device < 0 || device >= ndev) return fail(ISE_E_INVALID, "device out of range");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(ISE_E_NODEVICE, std::string("device is ") + prop.gcnArchName +
-                                        ", this library is built for gfx950 only");
+    int num_cu = 0;
+    const int rc = device_gate(device, &num_cu);
+    if (rc) return rc;
     ise_index* h = new (std::nothrow) ise_index();
     if (!h) return fail(ISE_E_NOMEM, "host allocation failed");
     h->d = d;
@@ -305,7 +299,7 @@ extern "C" int ise_index_create_ex(ise_index_t** out, int d, int metric, int dev
     h->dpb = pad_bytes(d);
     h->metric = metric;
     h->device = device;
-    h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    h->num_cu = num_cu;
     DeviceGuard gd(device);
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc(&h->mu, (size_t)h->dp * sizeof(float));

@@ -4,31 +4,13 @@
 // only, search builds the queries' lookup tables and scans the codes.
 //
 // Calls on one handle run one at a time (a mutex; the host forms hold it until their results are back, the device
-// forms while they enqueue).  The handle has ONE set of workspaces: work enqueued on another stream than the previous
-// call's waits for that call through an event, and a workspace that has to grow is replaced only after the device
-// has drained.
+// forms while they enqueue).  The handle has ONE set of workspaces: every call that touches them waits for the call
+// before and marks its own end (CallOrder, ise_host.hpp), and a workspace that has to grow is replaced by the drained
+// rule (grow_drained, ise_host.hpp).
 #include <cmath>
 
 #include "ise_host.hpp"
 #include "ise_pq.hpp"
-
-namespace {
-// rule: device-wide drain before a free (any stream may still use the handle's ONE set), and half again on top so growth drains rarely
-template <class T>
-int pq_grow(DevBuf<T>& b, size_t need) {
-    if (b.p && need <= b.n) return ISE_OK;
-    if (b.p) {
-        HIP_TRY(hipDeviceSynchronize());  // work in flight on any stream may still use the old one
-        (void)hipFree(b.p);
-    }
-    b.p = nullptr;
-    b.n = 0;
-    const size_t want = std::max<size_t>(need + need / 2, 16);
-    HIP_TRY(hipMalloc((void**)&b.p, want * sizeof(T)));
-    b.n = want;
-    return ISE_OK;
-}
-}  // namespace
 
 struct ise_pq {
     int d = 0, M = 0, dsub = 0, stride = 0, qt = 0, metric = ISE_METRIC_L2, device = 0, num_cu = 256;
@@ -36,11 +18,9 @@ struct ise_pq {
     long long n = 0, cap = 0;
     uint8_t* codes = nullptr;  // [cap][stride]; bytes [M, stride) of every row are zero
     float* cb = nullptr;       // [M][256][dsub]
-    unsigned int* bad = nullptr;  // [1] set by an encode that met a NaN or inf entry
+    BadFlag bad;               // set by an encode that met a NaN or inf entry
     hipStream_t stream = nullptr;
-    hipEvent_t last = nullptr;  // the end of the previous call's device work
-    hipStream_t last_stream = nullptr;
-    bool last_valid = false;
+    CallOrder order;
     mutable std::mutex mu;
     DevBuf<float> xraw, tab, oD;  // host forms: rows or queries as passed | one chunk's tables | results
     DevBuf<uint8_t> craw;         // host forms: codes as passed or to hand back, packed [n][M]
@@ -50,20 +30,6 @@ struct ise_pq {
 };
 
 namespace {
-const char* const NONFINITE_MSG = "a row has a NaN or inf entry: nothing was encoded or added";
-
-// order this call's device work behind the previous call's, and mark its own end
-int pq_begin(ise_pq* h, hipStream_t st) {
-    if (h->last_valid && h->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->last, 0));
-    return ISE_OK;
-}
-int pq_end(ise_pq* h, hipStream_t st) {
-    HIP_TRY(hipEventRecord(h->last, st));
-    h->last_stream = st;
-    h->last_valid = true;
-    return ISE_OK;
-}
-
 int check_handle(const ise_pq* h) { return h ? ISE_OK : ise_fail_(ISE_E_INVALID, "product-quantiser index handle is NULL"); }
 int check_trained(const ise_pq* h) {
     return h->trained ? ISE_OK : ise_fail_(ISE_E_INVALID, "the index is not trained: set the centroids first");
@@ -106,7 +72,7 @@ int reserve_codes(ise_pq* h, long long need, hipStream_t st) {
     if (e == hipSuccess && h->codes) e = hipDeviceSynchronize();  // searches in flight still read the old storage
     if (e != hipSuccess) {
         (void)hipFree(nx);
-        return ise_fail_(ISE_E_HIP, std::string("growing the code storage: ") + hipGetErrorString(e));
+        return ise_fail_(e == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP, std::string("growing the code storage: ") + hipGetErrorString(e));
     }
     if (h->codes) (void)hipFree(h->codes);
     h->codes = nx;
@@ -114,39 +80,24 @@ int reserve_codes(ise_pq* h, long long need, hipStream_t st) {
     return ISE_OK;
 }
 
-// byte m of rows [0, n) of dst (row stride `stride`) <- the code of x's rows; sets *h->bad on a non-finite entry
+// byte m of rows [0, n) of dst (row stride `stride`) <- the code of x's rows; sets the bad flag on a non-finite entry
 void encode_launch(ise_pq* h, const float* x_dev, long long n, uint8_t* dst, int stride, hipStream_t st) {
     static LdsAttrOnce attr;
     const dim3 grid((unsigned)((n + PQ_ENC_ROWS - 1) / PQ_ENC_ROWS), (unsigned)h->M);
     if (h->dsub <= PQ_ENC_LDS_DSUB) {
         attr.ensure(reinterpret_cast<const void*>(pq_encode_kernel<true>), PQ_ENC_LDS_DSUB * PQ_KSUB * 4);
         hipLaunchKernelGGL(pq_encode_kernel<true>, grid, dim3(PQ_WAVES * 64), (size_t)h->dsub * PQ_KSUB * 4, st, x_dev, n, h->d,
-                           h->M, (const float*)h->cb, dst, stride, h->bad);
+                           h->M, (const float*)h->cb, dst, stride, h->bad.p);
     } else {
         hipLaunchKernelGGL(pq_encode_kernel<false>, grid, dim3(PQ_WAVES * 64), 0, st, x_dev, n, h->d, h->M,
-                           (const float*)h->cb, dst, stride, h->bad);
+                           (const float*)h->cb, dst, stride, h->bad.p);
     }
-}
-
-// waits for st; ISE_E_INVALID when an encode since bad_clear met a non-finite entry
-int bad_clear(ise_pq* h, hipStream_t st) {
-    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(unsigned int), st));
-    return ISE_OK;
-}
-int bad_check(ise_pq* h, hipStream_t st) {
-    unsigned int flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, h->bad, sizeof(flag), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return flag ? ise_fail_(ISE_E_INVALID, NONFINITE_MSG) : ISE_OK;
 }
 
 int check_rows_fit(const ise_pq* h, long long n) {
     if (h->n + n >= (1ll << 32)) return ise_fail_(ISE_E_INVALID, "a product-quantiser index holds fewer than 2^32 rows");
     return ISE_OK;
 }
-
-// rows of `step` at most so that one upload is 256 MiB at most
-long long upload_step(size_t row_bytes) { return std::max<long long>(1, (1ll << 28) / (long long)row_bytes); }
 
 void decode_launch(const ise_pq* h, const uint8_t* codes, int stride, long long n, float* x_dev, hipStream_t st) {
     const long long tot = n * h->d;
@@ -156,7 +107,7 @@ void decode_launch(const ise_pq* h, const uint8_t* codes, int stride, long long 
 
 // q_dev: nq x d floats on the device; D_dev / I_dev: nq x k.  mu held, the index trained
 int search_enqueue(ise_pq* h, const float* q_dev, long long nq, int k, float* D_dev, long long* I_dev, hipStream_t st) {
-    int rc = pq_begin(h, st);
+    int rc = h->order.wait(st);
     if (rc) return rc;
     const int ip = h->metric == ISE_METRIC_INNER_PRODUCT;
     if (h->n == 0) {  // nothing to rank: a fill, no table, no pass
@@ -164,14 +115,14 @@ int search_enqueue(ise_pq* h, const float* q_dev, long long nq, int k, float* D_
         const long long cnt = nq * k;
         hipLaunchKernelGGL(pq_fill_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, cnt, ip);
         HIP_TRY(hipGetLastError());
-        return pq_end(h, st);
+        return h->order.mark(st);
     }
     const int qt = h->qt;
     const unsigned grid = pq_grid(h);
     const size_t tab_q = (size_t)h->M * PQ_KSUB;  // floats of one query's tables
-    if ((rc = pq_grow(h->tab, (size_t)std::min<long long>((nq + qt - 1) / qt * qt, PQ_TAB_CHUNK) * tab_q))) return rc;
-    if ((rc = pq_grow(h->lo, (size_t)PQ_TAB_CHUNK))) return rc;
-    if ((rc = pq_grow(h->lists, (size_t)grid * qt * PQ_KPASS))) return rc;
+    if ((rc = grow_drained(h->tab, (size_t)std::min<long long>((nq + qt - 1) / qt * qt, PQ_TAB_CHUNK) * tab_q))) return rc;
+    if ((rc = grow_drained(h->lo, (size_t)PQ_TAB_CHUNK))) return rc;
+    if ((rc = grow_drained(h->lists, (size_t)grid * qt * PQ_KPASS))) return rc;
     h->st_search++;  // counted once the batch is certain to be enqueued
     const size_t lds = pq_lds_bytes(h->M, qt);
     for (long long c0 = 0; c0 < nq; c0 += PQ_TAB_CHUNK) {
@@ -218,16 +169,12 @@ int search_enqueue(ise_pq* h, const float* q_dev, long long nq, int k, float* D_
         }
     }
     HIP_TRY(hipGetLastError());
-    return pq_end(h, st);
+    return h->order.mark(st);
 }
 
 int check_search_args(const ise_pq* h, const void* q, long long nq, int k, const void* D, const void* I) {
-    if (nq < 0) return ise_fail_(ISE_E_INVALID, "nq must be >= 0");
-    if (k < 1 || k > ISE_MAX_K) return ise_fail_(ISE_E_INVALID, "k must be in [1, ISE_MAX_K]");
-    if (nq > 0 && !q) return ise_fail_(ISE_E_INVALID, "query pointer is NULL");
-    if (nq > 0 && (!D || !I)) return ise_fail_(ISE_E_INVALID, "output pointer is NULL");
-    if (nq * (long long)k >= (1ll << 40)) return ise_fail_(ISE_E_INVALID, "nq * k is too large");
-    return check_handle(h);
+    const int rc = check_knn_args(q, nq, k, D, I);
+    return rc ? rc : check_handle(h);
 }
 
 // mu held, trained, n > 0 rows at x_dev: encode them behind the stored rows and, if every entry was finite, count
@@ -235,20 +182,20 @@ int check_search_args(const ise_pq* h, const void* q, long long nq, int k, const
 int add_device_locked(ise_pq* h, const float* x_dev, long long n, hipStream_t st) {
     int rc = check_rows_fit(h, n);
     if (rc) return rc;
-    if ((rc = pq_begin(h, st))) return rc;
+    if ((rc = h->order.wait(st))) return rc;
     if ((rc = reserve_codes(h, h->n + n, st))) return rc;
-    if ((rc = bad_clear(h, st))) return rc;
+    if ((rc = h->bad.clear(st))) return rc;
     encode_launch(h, x_dev, n, h->codes + (size_t)h->n * h->stride, h->stride, st);
     HIP_TRY(hipGetLastError());
-    if ((rc = pq_end(h, st))) return rc;
-    if ((rc = bad_check(h, st))) return rc;
+    if ((rc = h->order.mark(st))) return rc;
+    if ((rc = h->bad.check(st))) return rc;
     h->n += n;
     return ISE_OK;
 }
 
 void free_buffers(ise_pq* h) {
     for (void* p : {(void*)h->xraw.p, (void*)h->tab.p, (void*)h->oD.p, (void*)h->craw.p, (void*)h->lo.p, (void*)h->lists.p,
-                    (void*)h->oI.p, (void*)h->codes, (void*)h->cb, (void*)h->bad})
+                    (void*)h->oI.p, (void*)h->codes, (void*)h->cb, (void*)h->bad.p})
         if (p) (void)hipFree(p);
 }
 }  // namespace
@@ -263,14 +210,9 @@ extern "C" int ise_pq_create(ise_pq_t** out, int d, int M, int nbits, int metric
     if (nbits != 8) return ise_fail_(ISE_E_INVALID, "nbits must be 8: only 8-bit sub-quantisers are provided");
     if (metric != ISE_METRIC_L2 && metric != ISE_METRIC_INNER_PRODUCT)
         return ise_fail_(ISE_E_INVALID, "metric must be ISE_METRIC_L2 or ISE_METRIC_INNER_PRODUCT");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return ise_fail_(ISE_E_NODEVICE, "no HIP device visible: the kNN path needs an MI355X (gfx950) GPU");
-    if (device < 0 || device >= ndev) return ise_fail_(ISE_E_INVALID, "device out of range");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return ise_fail_(ISE_E_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    int num_cu = 0;
+    const int rc = device_gate(device, &num_cu);
+    if (rc) return rc;
     ise_pq* h = new (std::nothrow) ise_pq();
     if (!h) return ise_fail_(ISE_E_NOMEM, "host allocation failed");
     h->d = d;
@@ -280,16 +222,16 @@ extern "C" int ise_pq_create(ise_pq_t** out, int d, int M, int nbits, int metric
     h->qt = pq_qt(M);
     h->metric = metric;
     h->device = device;
-    h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    h->num_cu = num_cu;
     DeviceGuard gd(device);
     hipError_t e = gd.ok ? hipSuccess : hipErrorInvalidDevice;
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->last, hipEventDisableTiming);
+    if (e == hipSuccess) e = h->order.create();
     if (e == hipSuccess) e = hipMalloc((void**)&h->cb, (size_t)M * PQ_KSUB * h->dsub * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->bad, sizeof(unsigned int));
+    if (e == hipSuccess) e = h->bad.create();
     if (e != hipSuccess) {
         free_buffers(h);
-        if (h->last) (void)hipEventDestroy(h->last);
+        h->order.destroy();
         if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return ise_fail_(ISE_E_HIP, std::string("product-quantiser index setup: ") + hipGetErrorString(e));
@@ -304,7 +246,7 @@ extern "C" int ise_pq_destroy(ise_pq_t* h) {
         DeviceGuard gd(h->device);
         (void)hipDeviceSynchronize();
         free_buffers(h);
-        if (h->last) (void)hipEventDestroy(h->last);
+        h->order.destroy();
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
     delete h;
@@ -369,13 +311,13 @@ extern "C" int ise_pq_encode_device(ise_pq_t* h, const float* x_dev, int64_t n, 
     if (n == 0) return ISE_OK;
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
-    int rc = pq_begin(h, st);
+    int rc = h->order.wait(st);
     if (rc) return rc;
-    if ((rc = bad_clear(h, st))) return rc;
+    if ((rc = h->bad.clear(st))) return rc;
     encode_launch(h, x_dev, n, codes_dev, h->M, st);
     HIP_TRY(hipGetLastError());
-    if ((rc = pq_end(h, st))) return rc;
-    return bad_check(h, st);
+    if ((rc = h->order.mark(st))) return rc;
+    return h->bad.check(st);
 }
 
 extern "C" int ise_pq_encode_host(ise_pq_t* h, const float* x, int64_t n, uint8_t* codes) {
@@ -389,19 +331,19 @@ extern "C" int ise_pq_encode_host(ise_pq_t* h, const float* x, int64_t n, uint8_
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     hipStream_t st = h->stream;
     const long long step = upload_step((size_t)h->d * sizeof(float));
-    int rc = pq_begin(h, st);
+    int rc = h->order.wait(st);
     if (rc) return rc;
     for (long long i0 = 0; i0 < n; i0 += step) {
         const long long m = std::min<long long>(step, n - i0);
-        if ((rc = pq_grow(h->xraw, (size_t)m * h->d))) return rc;
-        if ((rc = pq_grow(h->craw, (size_t)m * h->M))) return rc;
+        if ((rc = grow_drained(h->xraw, (size_t)m * h->d))) return rc;
+        if ((rc = grow_drained(h->craw, (size_t)m * h->M))) return rc;
         HIP_TRY(hipMemcpyAsync(h->xraw.p, x + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice, st));
-        if ((rc = bad_clear(h, st))) return rc;
+        if ((rc = h->bad.clear(st))) return rc;
         encode_launch(h, h->xraw.p, m, h->craw.p, h->M, st);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(codes + (size_t)i0 * h->M, h->craw.p, (size_t)m * h->M, hipMemcpyDeviceToHost, st));
-        if ((rc = pq_end(h, st))) return rc;
-        if ((rc = bad_check(h, st))) return rc;
+        if ((rc = h->order.mark(st))) return rc;
+        if ((rc = h->bad.check(st))) return rc;
     }
     return ISE_OK;
 }
@@ -417,17 +359,17 @@ extern "C" int ise_pq_decode_host(ise_pq_t* h, const uint8_t* codes, int64_t n, 
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     hipStream_t st = h->stream;
     const long long step = upload_step((size_t)h->d * sizeof(float));
-    int rc = pq_begin(h, st);
+    int rc = h->order.wait(st);
     if (rc) return rc;
     for (long long i0 = 0; i0 < n; i0 += step) {
         const long long m = std::min<long long>(step, n - i0);
-        if ((rc = pq_grow(h->xraw, (size_t)m * h->d))) return rc;
-        if ((rc = pq_grow(h->craw, (size_t)m * h->M))) return rc;
+        if ((rc = grow_drained(h->xraw, (size_t)m * h->d))) return rc;
+        if ((rc = grow_drained(h->craw, (size_t)m * h->M))) return rc;
         HIP_TRY(hipMemcpyAsync(h->craw.p, codes + (size_t)i0 * h->M, (size_t)m * h->M, hipMemcpyHostToDevice, st));
         decode_launch(h, h->craw.p, h->M, m, h->xraw.p, st);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(x + (size_t)i0 * h->d, h->xraw.p, (size_t)m * h->d * sizeof(float), hipMemcpyDeviceToHost, st));
-        if ((rc = pq_end(h, st))) return rc;
+        if ((rc = h->order.mark(st))) return rc;
         HIP_TRY(hipStreamSynchronize(st));
     }
     return ISE_OK;
@@ -468,7 +410,7 @@ extern "C" int ise_pq_add_host(ise_pq_t* h, const float* x, int64_t n) {
     if ((rc = reserve_codes(h, h->n + n, h->stream))) return rc;
     for (long long i0 = 0; i0 < n; i0 += step) {
         const long long m = std::min<long long>(step, n - i0);
-        if ((rc = pq_grow(h->xraw, (size_t)m * h->d))) return rc;
+        if ((rc = grow_drained(h->xraw, (size_t)m * h->d))) return rc;
         HIP_TRY(hipMemcpyAsync(h->xraw.p, x + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice,
                                h->stream));
         if ((rc = add_device_locked(h, h->xraw.p, m, h->stream))) return rc;
@@ -489,12 +431,12 @@ extern "C" int ise_pq_add_codes_host(ise_pq_t* h, const uint8_t* codes, int64_t 
     hipStream_t st = h->stream;
     int rc = check_rows_fit(h, n);
     if (rc) return rc;
-    if ((rc = pq_begin(h, st))) return rc;
+    if ((rc = h->order.wait(st))) return rc;
     if ((rc = reserve_codes(h, h->n + n, st))) return rc;
     // the pad bytes of the fresh rows are zero already (reserve_codes); only bytes below M are ever written
     HIP_TRY(hipMemcpy2DAsync(h->codes + (size_t)h->n * h->stride, (size_t)h->stride, codes, (size_t)h->M, (size_t)h->M, (size_t)n,
                              hipMemcpyHostToDevice, st));
-    if ((rc = pq_end(h, st))) return rc;
+    if ((rc = h->order.mark(st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     h->n += n;
     return ISE_OK;
@@ -509,11 +451,11 @@ extern "C" int ise_pq_codes_host(ise_pq_t* h, int64_t i0, int64_t n, uint8_t* co
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     hipStream_t st = h->stream;
-    int rc = pq_begin(h, st);
+    int rc = h->order.wait(st);
     if (rc) return rc;
     HIP_TRY(hipMemcpy2DAsync(codes, (size_t)h->M, h->codes + (size_t)i0 * h->stride, (size_t)h->stride, (size_t)h->M, (size_t)n,
                              hipMemcpyDeviceToHost, st));
-    if ((rc = pq_end(h, st))) return rc;
+    if ((rc = h->order.mark(st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return ISE_OK;
 }
@@ -528,15 +470,15 @@ extern "C" int ise_pq_reconstruct_host(ise_pq_t* h, int64_t i0, int64_t n, float
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     hipStream_t st = h->stream;
     const long long step = upload_step((size_t)h->d * sizeof(float));
-    int rc = pq_begin(h, st);
+    int rc = h->order.wait(st);
     if (rc) return rc;
     for (long long j0 = 0; j0 < n; j0 += step) {
         const long long m = std::min<long long>(step, n - j0);
-        if ((rc = pq_grow(h->xraw, (size_t)m * h->d))) return rc;
+        if ((rc = grow_drained(h->xraw, (size_t)m * h->d))) return rc;
         decode_launch(h, h->codes + (size_t)(i0 + j0) * h->stride, h->stride, m, h->xraw.p, st);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(x + (size_t)j0 * h->d, h->xraw.p, (size_t)m * h->d * sizeof(float), hipMemcpyDeviceToHost, st));
-        if ((rc = pq_end(h, st))) return rc;
+        if ((rc = h->order.mark(st))) return rc;
         HIP_TRY(hipStreamSynchronize(st));
     }
     return ISE_OK;
@@ -564,12 +506,12 @@ extern "C" int ise_pq_search_host(ise_pq_t* h, const float* q, int64_t nq, int k
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     hipStream_t st = h->stream;
     const long long batch = std::min<long long>(nq, 4096);
-    if ((rc = pq_grow(h->xraw, (size_t)batch * h->d))) return rc;
-    if ((rc = pq_grow(h->oD, (size_t)batch * k))) return rc;
-    if ((rc = pq_grow(h->oI, (size_t)batch * k))) return rc;
+    if ((rc = grow_drained(h->xraw, (size_t)batch * h->d))) return rc;
+    if ((rc = grow_drained(h->oD, (size_t)batch * k))) return rc;
+    if ((rc = grow_drained(h->oI, (size_t)batch * k))) return rc;
     for (long long i0 = 0; i0 < nq; i0 += batch) {
         const long long m = std::min<long long>(batch, nq - i0);
-        if ((rc = pq_begin(h, st))) return rc;
+        if ((rc = h->order.wait(st))) return rc;
         HIP_TRY(hipMemcpyAsync(h->xraw.p, q + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice, st));
         if ((rc = search_enqueue(h, h->xraw.p, m, k, h->oD.p, h->oI.p, st))) return rc;
         HIP_TRY(hipMemcpyAsync(D + (size_t)i0 * k, h->oD.p, (size_t)m * k * sizeof(float), hipMemcpyDeviceToHost, st));

@@ -1,10 +1,12 @@
 // Stand-alone check of the inverted lists' rebuild bookkeeping (csrc/ise_ivf_plan.hpp): random cases against a
-// naive stable grouping.  Built and run by tests/test_ivf.py, with the host sanitizers where the compiler has them.
+// naive stable grouping, then the table, the list check and the counts against values written out by hand
+// (ivf_book_check.hpp).  Built and run by tests/test_ivf.py, with the host sanitizers where the compiler has them.
 #include <algorithm>
 #include <cstdio>
 #include <random>
 
 #include "../../image-search-engine_amd/csrc/ise_ivf_plan.hpp"
+#include "ivf_book_check.hpp"
 
 static int check(const std::vector<long long>& old_size, const std::vector<int32_t>& pend) {
     IvfPlan pl;
@@ -54,6 +56,9 @@ int main() {
         std::printf("FAIL: 2^32 slots accepted\n");
         return 1;
     }
+    // the table, the list check and the counts (ivf_book_check.hpp)
+    if (!ivf_book_check()) return 1;
+    cases++;
     std::printf("ok %d cases\n", cases);
     return 0;
 }

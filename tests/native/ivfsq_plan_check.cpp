@@ -1,12 +1,13 @@
 // Stand-alone check of the rebuild bookkeeping (csrc/ise_ivf_plan.hpp) with the 64-row tiles of the inverted lists
 // over 8-bit rows (csrc/ise_ivfsq.hip): the list sizes at a tile's edge, stable order, old rows keeping their
-// positions, the 2^32 slot refusal, and the default of 16 rows left as it was.  Built and run by tests/test_ivfsq.py
-// under the host sanitizers.
+// positions, the 2^32 slot refusal, the default of 16 rows left as it was, and the table, the list check and the counts
+// (ivf_book_check.hpp).  Built and run by tests/test_ivfsq.py under the host sanitizers.
 #include <algorithm>
 #include <cstdio>
 #include <random>
 
 #include "../../image-search-engine_amd/csrc/ise_ivf_plan.hpp"
+#include "ivf_book_check.hpp"
 
 static const int ROWS = 64;
 
@@ -97,6 +98,9 @@ int main() {
         std::printf("FAIL: the default tile is not 16 rows\n");
         return 1;
     }
+    // the table, the list check and the counts (ivf_book_check.hpp)
+    if (!ivf_book_check()) return 1;
+    cases++;
     std::printf("ok %d cases\n", cases);
     return 0;
 }

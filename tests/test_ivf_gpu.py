@@ -255,6 +255,43 @@ def test_torch_preassigned_and_odd_probes():
         untrained.train(xb[:3])  # fewer rows than lists
 
 
+def test_one_handle_from_two_streams():
+    """Adds and searches on one handle from the default stream and a side stream, nothing waited for in between: the
+    side stream's search (two chunks of two k-passes, more queries and a larger k than the call before) has to grow
+    every workspace while the first search may still be in flight.  Every result is the host form's, bit for bit."""
+    import torch
+
+    d, n, nlist = 40, 900, 6
+    rng = np.random.default_rng(31)
+    xb, xq = int_data("small", rng, n, d), int_data("small", rng, 70, d)
+    cent = xb[[1, 2, 3, 5, 8, 13]]
+    qz, ivf = build(cent, xb, L2, L2, chunks=[n])
+    qz2, twin = build(cent, xb[:0], L2, L2, chunks=[])
+    ivf.nprobe = twin.nprobe = 3
+    want = {(nq, k): ivf.search(xq[:nq], k) for nq, k in ((3, 10), (70, 33))}
+    dev = torch.device("cuda", twin.device)
+    side = torch.cuda.Stream(device=dev)
+    xb_t, xq_t = torch.from_numpy(xb).to(dev), torch.from_numpy(xq).to(dev)
+    torch.cuda.synchronize(dev)
+    twin.add_torch(xb_t[:300])
+    with torch.cuda.stream(side):
+        twin.add_torch(xb_t[300:])
+    assert twin.ntotal == n and [twin.list_size(l) for l in range(nlist)] == [ivf.list_size(l) for l in range(nlist)]
+    first = twin.search_torch(xq_t[:3], 10)  # rebuilds the lists
+    with torch.cuda.stream(side):
+        second = twin.search_torch(xq_t, 33)
+    third = twin.search_torch(xq_t[:3], 10)
+    torch.cuda.synchronize(dev)
+    for name, got, key in (("first", first, (3, 10)), ("side stream", second, (70, 33)), ("third", third, (3, 10))):
+        assert_knn_identical(got[0].cpu().numpy(), got[1].cpu().numpy(), *want[key], name)
+    for key, (D, I) in want.items():
+        assert_knn_identical(*twin.search(xq[:key[0]], key[1]), D, I, f"the twin's host form {key}")
+    assert twin.ntotal == n
+    for l in range(nlist):
+        (ids, rows), (ids2, rows2) = ivf.get_list(l), twin.get_list(l)
+        assert np.array_equal(ids, ids2) and np.array_equal(rows.view(np.uint32), rows2.view(np.uint32))
+
+
 def test_work_is_proportional_to_the_probes():
     d = 20
     cent, plan, xb, xq = clustered(d, 3)

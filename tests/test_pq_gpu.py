@@ -148,6 +148,37 @@ def test_gates(metric):
         faiss.IndexIDMap(fresh)
 
 
+def test_one_handle_from_two_streams():
+    """Adds and searches on one handle from the default stream and a side stream, nothing waited for in between: the
+    side stream's search (two k-passes, more queries and a larger k than the call before) has to grow every workspace
+    while the first search may still be in flight.  Every result is the host form's, bit for bit."""
+    import torch
+
+    M, dsub, n = 8, 5, 900
+    index, C, xb, xq = integer_index(M, dsub, "small", n, L2, 31, nq=70, chunks=[n])
+    want = {(nq, k): index.search(xq[:nq], k) for nq, k in ((3, 10), (70, 33))}
+    twin = faiss.IndexPQ(M * dsub, M, 8, L2)
+    twin.pq.set_centroids(C)
+    dev = torch.device("cuda", twin.device)
+    side = torch.cuda.Stream(device=dev)
+    xb_t, xq_t = torch.from_numpy(xb).to(dev), torch.from_numpy(xq).to(dev)
+    torch.cuda.synchronize(dev)
+    twin.add_torch(xb_t[:300])
+    with torch.cuda.stream(side):
+        twin.add_torch(xb_t[300:])
+    assert twin.ntotal == n and np.array_equal(twin.codes, index.codes)
+    first = twin.search_torch(xq_t[:3], 10)
+    with torch.cuda.stream(side):
+        second = twin.search_torch(xq_t, 33)
+    third = twin.search_torch(xq_t[:3], 10)
+    torch.cuda.synchronize(dev)
+    for name, got, key in (("first", first, (3, 10)), ("side stream", second, (70, 33)), ("third", third, (3, 10))):
+        assert_knn_identical(got[0].cpu().numpy(), got[1].cpu().numpy(), *want[key], name)
+    for key, (D, I) in want.items():
+        assert_knn_identical(*twin.search(xq[:key[0]], key[1]), D, I, f"the twin's host form {key}")
+    assert twin.ntotal == n and np.array_equal(twin.codes, index.codes)
+
+
 def gaussian(n, d, seed):
     return np.random.default_rng(seed).standard_normal((n, d)).astype(np.float32)
 

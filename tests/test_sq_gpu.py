@@ -306,6 +306,37 @@ def test_torch_forms(metric):
     assert Dz.shape == (0, 3) and Iz.shape == (0, 3)
 
 
+def test_one_handle_from_two_streams():
+    """Adds and searches on one handle from the default stream and a side stream, nothing waited for in between: the
+    side stream's search (two k-passes, more queries and a larger k than the call before) has to grow every workspace
+    while the first search may still be in flight.  Every result is the host form's, bit for bit."""
+    import torch
+
+    d, n = 40, 900
+    index, t, xb, base, xq = integer_index(d, SQ.QT_8bit, L2, n, 31, nq=70, chunks=[n])
+    want = {(nq, k): index.search(xq[:nq], k) for nq, k in ((3, 10), (70, 33))}
+    twin = faiss.IndexScalarQuantizer(d, SQ.QT_8bit, L2)
+    twin.sq.set_trained(t)
+    dev = torch.device("cuda", twin.device)
+    side = torch.cuda.Stream(device=dev)
+    xb_t, xq_t = torch.from_numpy(xb).to(dev), torch.from_numpy(xq).to(dev)
+    torch.cuda.synchronize(dev)
+    twin.add_torch(xb_t[:300])
+    with torch.cuda.stream(side):
+        twin.add_torch(xb_t[300:])
+    assert twin.ntotal == n and np.array_equal(twin.codes, index.codes)
+    first = twin.search_torch(xq_t[:3], 10)
+    with torch.cuda.stream(side):
+        second = twin.search_torch(xq_t, 33)
+    third = twin.search_torch(xq_t[:3], 10)
+    torch.cuda.synchronize(dev)
+    for name, got, key in (("first", first, (3, 10)), ("side stream", second, (70, 33)), ("third", third, (3, 10))):
+        assert_knn_identical(got[0].cpu().numpy(), got[1].cpu().numpy(), *want[key], name)
+    for key, (D, I) in want.items():
+        assert_knn_identical(*twin.search(xq[:key[0]], key[1]), D, I, f"the twin's host form {key}")
+    assert twin.ntotal == n and np.array_equal(twin.codes, index.codes)
+
+
 @pytest.mark.parametrize("metric", [L2, IP])
 @pytest.mark.parametrize("qtype", QTYPES)
 def test_write_and_read_index(qtype, metric, tmp_path):
