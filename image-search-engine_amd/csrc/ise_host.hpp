@@ -1,7 +1,8 @@
 // ise_host.hpp -- host plumbing every translation unit of libise_knn.so shares: the error path into
-// ise_last_error(), the device gate of every *_create, the lazily grown device buffer with its two grow rules, the
-// call order of a handle with ONE set of workspaces, the non-finite flag of the encoders, the kNN argument checks and
-// the small helpers, and the one knob another translation unit reads.  Plain structs and inline functions; no kernels.
+// ise_last_error(), the device gate of every *_create, the lazily grown buffer (device or page-locked) with every grow
+// rule of the library, the call order of a handle with ONE set of workspaces and the hand-out of workspace slots, the
+// non-finite flag of the encoders, the kNN argument checks and the small helpers, and the one knob another translation
+// unit reads.  Plain structs and inline functions; no kernels.
 #pragma once
 #include "ise_common.hpp"
 
@@ -32,30 +33,58 @@ inline int device_gate(int device, int* num_cu) {
     return ISE_OK;
 }
 
-// ---- a buffer grown lazily, contents not kept.  What has to be waited for before the old one is freed is the grow
-// rule, and a handle's kind picks one: grow_drained (the flat kinds: product-quantised, scalar-quantised, binary) or
-// grow_after_event (the inverted-list kinds).  They block differently, so they stay two functions.  The float index's
-// range_grow and subset_grow (ise_knn.hip) are its own: pinned memory, and a drain with the exact size.
-template <class T>
+// ---- a buffer grown lazily, contents not kept: device memory, page-locked host memory, or page-locked host memory
+// the device addresses too (`dev`).  buf_realloc is the one way such a buffer comes to hold memory and buf_free the one
+// way it lets go of it; what decides a replacement is a grow rule below.  Each rule answers three questions: is the
+// buffer already enough, what is waited for before the free, and how much is asked for.  A handle's kind picks its
+// rule; the rules block differently, so each stays a function of its own.
+enum MemKind { MEM_DEVICE, MEM_PINNED, MEM_MAPPED };
+template <class T, MemKind K = MEM_DEVICE>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
 };
+template <class T>
+struct DevBuf<T, MEM_MAPPED> {
+    T* p = nullptr;
+    size_t n = 0;
+    T* dev = nullptr;  // p as the device addresses it
+};
+
+template <class T, MemKind K>
+void buf_free(DevBuf<T, K>& b) {
+    if (b.p) (void)(K == MEM_DEVICE ? hipFree(b.p) : hipHostFree(b.p));
+    b = DevBuf<T, K>();
+}
+template <class... B>
+void buf_free(B&... b) {
+    (buf_free(b), ...);
+}
+// frees what b holds, allocates `want` elements and records the size
+template <class T, MemKind K>
+int buf_realloc(DevBuf<T, K>& b, size_t want) {
+    buf_free(b);
+    if constexpr (K == MEM_DEVICE) HIP_TRY(hipMalloc((void**)&b.p, want * sizeof(T)));
+    else HIP_TRY(hipHostMalloc((void**)&b.p, want * sizeof(T), K == MEM_MAPPED ? hipHostMallocMapped : hipHostMallocDefault));
+    if constexpr (K == MEM_MAPPED) HIP_TRY(hipHostGetDevicePointer((void**)&b.dev, b.p, 0));
+    b.n = want;
+    return ISE_OK;
+}
 
 // rule: device-wide drain before a free (any stream may still use the handle's ONE set), and half again on top so growth drains rarely
 template <class T>
 int grow_drained(DevBuf<T>& b, size_t need) {
     if (b.p && need <= b.n) return ISE_OK;
-    if (b.p) {
-        HIP_TRY(hipDeviceSynchronize());  // work in flight on any stream may still use the old one
-        (void)hipFree(b.p);
-    }
-    b.p = nullptr;
-    b.n = 0;
-    const size_t want = std::max<size_t>(need + need / 2, 16);
-    HIP_TRY(hipMalloc((void**)&b.p, want * sizeof(T)));
-    b.n = want;
-    return ISE_OK;
+    if (b.p) HIP_TRY(hipDeviceSynchronize());  // work in flight on any stream may still use the old one
+    return buf_realloc(b, std::max<size_t>(need + need / 2, 16));
+}
+
+// rule: device-wide drain before a free (work in flight on any stream may still use the handle's ONE set); exact size
+template <class T>
+int grow_drained_exact(DevBuf<T>& b, size_t need) {
+    if (b.p && need <= b.n) return ISE_OK;
+    if (b.p) HIP_TRY(hipDeviceSynchronize());
+    return buf_realloc(b, std::max<size_t>(need, 16));
 }
 
 // busy: the event behind the last pass that used the workspaces (CallOrder::busy), or null -- waited for only when the
@@ -65,12 +94,22 @@ template <class T>
 int grow_after_event(DevBuf<T>& b, size_t need, hipEvent_t busy) {
     if (need <= b.n) return ISE_OK;
     if (b.p && busy) HIP_TRY(hipEventSynchronize(busy));
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.n = 0;
-    HIP_TRY(hipMalloc((void**)&b.p, need * sizeof(T)));
-    b.n = need;
-    return ISE_OK;
+    return buf_realloc(b, need);
+}
+
+// rule: no wait before a free -- range search owns its workspace (rg_mu) and drains it per batch, a SelSlot's other user was waited for, a host context is its caller's; exact size, `floor` at least
+template <class T, MemKind K>
+int grow_owned(DevBuf<T, K>& b, size_t need, size_t floor = 1) {
+    if (b.p && need <= b.n) return ISE_OK;
+    return buf_realloc(b, std::max(need, floor));
+}
+
+// rule: no wait of its own -- hipFree waits for outstanding work; exact size; *changed: something was allocated (the caller fills and drains once)
+template <class T>
+int grow_slot(DevBuf<T>& b, size_t need, bool* changed) {
+    if (need <= b.n) return ISE_OK;
+    *changed = true;
+    return buf_realloc(b, need);
 }
 
 // ---- the call order of a handle with ONE set of workspaces (its mutex held): device work enqueued on another stream
@@ -111,6 +150,24 @@ struct CallOrder {
         }
     };
 };
+
+// ---- slots of workspaces, each with a CallOrder `order` (the handle's mutex held): a stream keeps the slot it used
+// last (stream order is all the ordering that needs); a stream without one takes a fresh slot, or the least recently
+// taken one behind an event wait.  *waited (optional): the slot's last user was another stream.  The caller marks the
+// slot's end through a CallOrder::Scope
+template <class Slot, int N>
+int take_slot(Slot (&slots)[N], unsigned* next, hipStream_t st, Slot** out, bool* waited) {
+    Slot* w = nullptr;
+    for (auto& s : slots)
+        if (s.order.valid && s.order.last_stream == st) { w = &s; break; }
+    if (!w)
+        for (auto& s : slots)
+            if (!s.order.valid) { w = &s; break; }
+    if (!w) w = &slots[(*next)++ % N];
+    if (waited) *waited = w->order.valid && w->order.last_stream != st;
+    *out = w;
+    return w->order.wait(st);
+}
 
 // ---- the encoders' non-finite flag: [1] on the device, set by an encode that met a NaN or inf entry
 struct BadFlag {

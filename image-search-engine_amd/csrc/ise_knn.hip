@@ -29,9 +29,20 @@
 //   selectors      ise_sel_scan.hpp  search / range search among the rows a device bitmap names: one masked pass per 16 queries
 //
 // Host headers shared with the other index kinds (ise_binary_scan.hip, ise_ivf.hip)
-//   ise_host.hpp         ise_fail_ (defined here), HIP_TRY, the device gate of every *_create, DevBuf
+//   ise_host.hpp         ise_fail_ (defined here), HIP_TRY, the device gate of every *_create, DevBuf and every grow
+//                        rule, CallOrder, take_slot
 //   ise_selector.hpp     the selector object: allocate, fill, census, info, free
 //   ise_remove_plan.hpp  remove_ids planning without a device call: ids -> runs -> g / cend tables, slab size
+//
+// The float index's translation units (ise_flat.hpp: the handle, its workspaces, and what the units call in each other)
+//   ise_knn.hip          this file: the error path, device queries, create / destroy / reset, add / reconstruct, shift
+//                        and shadows, plans (make_plan), the search paths (host and device) and their stats; and what
+//                        launches from ise_rows.hpp, whose kernels one unit only can hold: remove_ids with its stats
+//                        and timing, the row-inspection ABI, normalize_rows, the BoVW histogram (with assign and
+//                        merge_keys beside them)
+//   ise_flat_range.hip   range search, plain and masked
+//   ise_flat_sel.hip     the selector objects and the selector-filtered search
+//   ise_flat_subset.hip  subset scoring
 //
 // Candidate order: a 64-bit key = ord(score) << 32 | row id, where ord() is the
 // order-preserving map float -> uint32 and score = squared L2 (or -inner product).
@@ -39,10 +50,9 @@
 // ascending id), and keys are unique, so every selection is deterministic and
 // independent of the grid shape.
 //
-// This file: the host side and the C ABI (include/ise_knn.h).
+// This file: the core of the host side and of the C ABI (include/ise_knn.h).
 
-#include "ise_host.hpp"
-#include "ise_geometry.hpp"
+#include "ise_flat.hpp"
 #include "ise_scan_params.hpp"
 #include "ise_assign.hpp"
 #include "ise_exact.hpp"
@@ -52,13 +62,9 @@
 #include "ise_gemm_bf16.hpp"
 #include "ise_rows.hpp"
 #include "ise_short_scan.hpp"
-#include "ise_range.hpp"
-#include "ise_sel_scan.hpp"
 #include "ise_stage.hpp"
 #include "ise_remove.hpp"
 #include "ise_remove_plan.hpp"
-#include "ise_selector.hpp"
-#include "ise_subset.hpp"
 
 // ---------------------------------------------------------------- host side
 static thread_local std::string g_err;
@@ -66,188 +72,12 @@ int ise_fail_(int code, const std::string& msg) {  // ise_host.hpp: every transl
     g_err = msg;
     return code;
 }
-static int fail(int code, const std::string& msg) { return ise_fail_(code, msg); }
-
-struct ise_index {
-    int d = 0, dp = 0, metric = ISE_METRIC_L2, device = 0;
-    int storage = ISE_STORE_F32;  // element type of xb
-    long long n = 0, cap = 0;
-    void* xb = nullptr;
-    float* norms = nullptr;
-    // float32 L2 indexes: shift vector mu [dp] = column mean of the rows, (re)computed lazily at the
-    // first search after the index has grown by a quarter since the last time (or pinned by
-    // ise_index_set_shift); norms [0, norms_rows) are |y - mu|^2 for the current mu.  mu only
-    // decides how tight the scan's lower bounds are -- results are exact for any mu (ise_exact.hpp)
-    float* mu = nullptr;
-    bool shift_pinned = false;
-    long long mu_rows = 0;     // rows mu was computed from (0 = not yet)
-    long long norms_rows = 0;  // rows whose norm is valid
-    // fp16 shadow of the centred rows (float32 L2 indexes of more than SHADOW_MIN_ROWS rows): the scan's filter
-    // streams it instead of xb (ise_scan.hpp HALF).  Built at the first search past the threshold, then kept
-    // with the norms: valid for rows [0, norms_rows) whenever xh is set (launch_norms writes both)
-    void* xh = nullptr;        // [cap][dph] fp16
-    float* hmeta = nullptr;    // [3][cap]: |u~|^2, e_r, s_r
-    int dph = 0;               // padded shadow row length (whole 64-byte k-steps)
-    bool shadow_off = false;   // its allocation failed: the float32 filter serves (no retry until reset)
-    // ... and its byte image (ise_scan.hpp BYTE), kept with the fp16 shadow: set only while xh is
-    void* xq8 = nullptr;       // [cap][dpb] int8, tile-blocked (ise_byte_layout.hpp)
-    uint32_t* bmeta = nullptr; // [cap]: c_r | e_r / c_r
-    int dpb = 0;               // padded byte row length (whole 64-byte k-steps)
-    bool byte_off = false;     // its allocation failed: the fp16 shadow serves (no retry until reset)
-    double byte_rel = 0.0;     // mean e_r / |y - mu| when the byte shadow was last built over all rows (byte_rel_ok)
-    double byte_rho = 1.0;     // ... and the sample rows' mean nearest-neighbour over mean pair distance (byte_rel_ok)
-    unsigned long long half_batches = 0;  // batches whose filter read shadow rows, fp16 or byte (under mu_)
-    unsigned long long byte_batches = 0;  // ... of them, those that read the byte shadow rows (under mu_)
-    unsigned long long byte_deep_batches = 0;  // ... of those, the ones scanned with a deep plan (make_plan, depth > 1)
-    // the stream of the index's previous search (search_enqueue, under mu_): a batch on another one is pipelined
-    hipStream_t prev_stream = nullptr;
-    bool prev_search = false;
-    unsigned long long* stats_dev = nullptr;  // [4]: reranked queries, exact-scan queries
-    unsigned long long mu_updates = 0;
-    unsigned long long gemm_chunks = 0;  // query chunks that took the large-batch path
-    // workspaces (grown lazily, guarded by mu): NWS slots, so searches on different streams
-    // may be in flight together.  A stream keeps the slot it used last (stream order is all
-    // the ordering that needs); a stream without one takes a fresh slot, or the least
-    // recently taken one behind an event wait.  Six slots on purpose: a server that issues
-    // batches round-robin on more streams than that (bench.py: 16) gets at most six scans in
-    // flight, chained slot to slot on the GPU, with the next ones already queued -- measured
-    // best at 1M x 512 (303 us per batch against 328 with 4 streams and 319 with 16 slots)
-    // With the byte route's deep plan (make_plan, depth 2) a scan fills half the block slots, so two of
-    // the six slots' scans are resident together and the other four are the queue behind them.
-    struct WorkSlot {
-        u64* part = nullptr;
-        size_t part_elems = 0;
-        u64* keys_tmp = nullptr;  // multi-pass k scratch
-        size_t keys_tmp_elems = 0;
-        u64* xchg = nullptr;      // threshold-exchange entries of the scan kernel, tagged by xchg_seq
-        size_t xchg_elems = 0;
-        uint32_t xchg_seq = 0;    // bumped per scan launch: entries of older launches never match
-        // large-batch path (ise_gemm_scan.hpp): one allocation holding qprep | xn | tau | ccnt | sample keys | cand
-        char* gemm = nullptr;
-        size_t gemm_bytes = 0;
-        u64* fl_state = nullptr;  // exact path: launch seq << 32 | number of queries on the fallback list
-        int* fl_list = nullptr;   // [fl_elems] the listed queries
-        size_t fl_elems = 0;
-        uint32_t fl_seq = 0;      // bumped per rerank launch, never reset while fl_state lives
-        hipEvent_t done = nullptr;
-        bool used = false;
-        hipStream_t last_stream = nullptr;  // valid when used
-    };
-    static constexpr int NWS = 6;
-    WorkSlot ws[NWS];
-    unsigned ws_next = 0;
-    hipStream_t stream = nullptr;  // add / reconstruct / shift maintenance
-    // host-API search contexts: a caller owns one for the duration of its call
-    struct HostCtx {
-        hipStream_t stream = nullptr;
-        float* q_dev = nullptr;  size_t q_elems = 0;
-        float* D_dev = nullptr;  long long* I_dev = nullptr;  size_t out_elems = 0;
-        // page-locked staging of a combined batch (queries in, results out)
-        float* q_pin = nullptr;  size_t q_pin_elems = 0;
-        float* D_pin = nullptr;  long long* I_pin = nullptr;  size_t out_pin_elems = 0;
-        float* D_pin_dev = nullptr;  long long* I_pin_dev = nullptr;  // the same buffers as the device addresses them
-        bool busy = false;
-    };
-    static constexpr int NHC = 4;
-    HostCtx hc[NHC];
-    std::mutex hc_mu;
-    std::condition_variable hc_cv;
-    // combining of concurrent host searches (ise_index_search_host): callers queue their request; one
-    // of them -- at most CQ_LEADERS at a time -- takes the requests at the head of the queue that ask
-    // for the same k, runs them as ONE batch and hands the results out
-    struct HostReq {
-        const float* q; long long nq; int k; float* D; long long* I;
-        int rc = 0; std::string err; bool done = false;
-        std::condition_variable cv;
-    };
-    static constexpr int CQ_LEADERS = 2;
-    std::mutex cq_mu;
-    std::deque<HostReq*> cq;
-    int cq_leaders = 0;
-    unsigned long long cq_batches = 0, cq_requests = 0;
-    unsigned long long direct_queries = 0;  // queries answered by the direct small-batch scan (under mu_)
-    unsigned long long short_batches = 0;   // batches whose scan was the short-index kernel (under mu_)
-    int num_cu = 256;
-    std::mutex mu_;
-    // range search (ise_range.hpp): a workspace of its own, grown lazily and held by one call at a time (rg_mu,
-    // taken before mu_); the WorkSlot rotation of search is never touched
-    struct RangeWs {
-        DevBuf<float> q;                        // [m][dp] padded queries
-        DevBuf<unsigned> cnt;                   // [m][nseg] hits per segment
-        DevBuf<long long> segoff;               // [m][nseg] offset of a segment within its query
-        DevBuf<float> sD;                       // [m][nseg][cap] staged distances
-        DevBuf<uint32_t> sI;                    // [m][nseg][cap] staged row ids
-        DevBuf<long long> tot, lims;            // [m], [m + 1]
-        DevBuf<unsigned> flag;                  // overflow flag
-        DevBuf<float> D;                        // [total]
-        DevBuf<long long> I;                    // [total]
-        DevBuf<float> q_pin;                    // page-locked staging
-        DevBuf<long long> lims_pin;             // [m + 1] lims, then the overflow flag
-        DevBuf<float> D_pin;
-        DevBuf<long long> I_pin;
-    };
-    RangeWs rg;
-    std::mutex rg_mu;
-    unsigned long long range_batches = 0, range_overflows = 0;  // under rg_mu
-    // remove_ids (ise_remove.hpp): calls that removed something, rows removed, rows moved (under mu_); and the last
-    // such call's slab launches as HIP events timed them, with the bytes they moved (each counted once)
-    unsigned long long remove_calls = 0, remove_rows = 0, remove_moved = 0;
-    float remove_last_ms = 0.f;
-    unsigned long long remove_last_bytes = 0;
-    // selectors (ise_sel_scan.hpp).  row_epoch: bumped by whatever removes rows (reset, remove_ids, remove_range), never
-    // by add; a selector made at another epoch or ntotal is refused (under mu_).  The masked pass has a slot scheme
-    // of its own, NSS slots handed out like the WorkSlots (a stream keeps its slot; another stream takes a fresh one,
-    // or the least recently taken one behind an event wait), so filtered searches of several threads and streams
-    // run beside unfiltered ones and beside each other
-    unsigned long long row_epoch = 0;
-    struct SelSlot {
-        DevBuf<float> q;      // [chunk][dp] padded queries
-        DevBuf<u64> part;     // [groups][blocks][16][kpass]
-        DevBuf<u64> keys;     // [chunk][32] one pass's merged keys (k > 32) | [chunk] floors
-        hipEvent_t done = nullptr;
-        bool used = false;
-        hipStream_t last_stream = nullptr;
-    };
-    static constexpr int NSS = 4;
-    SelSlot ss[NSS];
-    unsigned ss_next = 0;
-    unsigned long long sel_batches = 0, sel_passes = 0;  // under mu_
-    unsigned long long sel_range_batches = 0;            // under rg_mu
-    // subset scoring (ise_subset.hpp): ONE key workspace per handle (under mu_).  A call on another stream than the
-    // previous subset call's waits for that call through `last`; a workspace that has to grow is replaced only after
-    // the device has drained.  The host forms stage through buffers of their own, held by one call at a time (mu,
-    // taken before mu_)
-    struct SubsetWs {
-        DevBuf<u64> keys;                 // [chunk][n2]
-        unsigned long long* valid = nullptr;  // [1] device counter: candidate entries inside [0, ntotal)
-        hipEvent_t last = nullptr;
-        hipStream_t last_stream = nullptr;
-        bool last_valid = false;
-        unsigned long long batches = 0, launches = 0;
-        std::mutex mu;
-        DevBuf<float> q, out;             // host forms: [chunk][d] queries | [chunk][k] D or [chunk][kc] scores
-        DevBuf<long long> cand, I;        // host forms: [chunk][kc] | [chunk][k]
-    };
-    SubsetWs sub;
-};
 
 // byte rows (the int8 shadow): 64 values per k-step, padded as above
 static int pad_bytes(int d) {
     const int steps = (d + 63) / 64;
     return (steps > 4 ? (steps + 3) / 4 * 4 : steps) * 64;
 }
-static size_t row_bytes(const ise_index* h) { return (size_t)h->dp * elem_size(h->storage); }
-static size_t shadow_row_bytes(const ise_index* h) { return (size_t)h->dph * 2; }
-static size_t byte_row_bytes(const ise_index* h) { return (size_t)h->dpb; }
-static int chunk_steps(const ise_index* h) { return chunk_steps_rb(row_bytes(h)); }
-static int qs_stride_for(const ise_index* h) { return qs_stride_units((int)(row_bytes(h) / 4)); }
-// the shadow-row kernel's query row: fp16 hi halves | lo halves, dph each
-static int qs_stride_half(const ise_index* h) { return qs_stride_units(h->dph); }
-// the byte shadow-row kernel's query row: int8 hi limbs | lo limbs, dpb each
-static int qs_stride_byte(const ise_index* h) { return qs_stride_units(h->dpb / 2); }
-#define KPASS_MAX 36 /* most keys per query one scan pass selects: k = 32 with the exact path's 4 spare candidates still is
-                        ONE pass (k = 29..32 took two: 730 us instead of 355 at 1M x 512); more: floor-keyed passes */
-#define XPASS_MAX 32 /* most results per query of one exact-scan pass, of the direct scan and of the large-batch paths */
 static size_t scan_lds_bytes(const ise_index* h, int waves, int T, int kb) {
     return scan_lds_layout(qs_stride_for(h), waves, T, kb);
 }
@@ -335,53 +165,11 @@ static void free_all(ise_index* h) {
     if (h->xb) (void)hipFree(h->xb);
     if (h->norms) (void)hipFree(h->norms);
     free_shadow(h);
-    for (auto& w : h->ws) {
-        if (w.part) (void)hipFree(w.part);
-        if (w.keys_tmp) (void)hipFree(w.keys_tmp);
-        if (w.xchg) (void)hipFree(w.xchg);
-        if (w.gemm) (void)hipFree(w.gemm);
-        if (w.fl_state) (void)hipFree(w.fl_state);
-        if (w.fl_list) (void)hipFree(w.fl_list);
-        if (w.done) (void)hipEventDestroy(w.done);
-        w = ise_index::WorkSlot();
-    }
-    for (auto& c : h->hc) {
-        if (c.q_dev) (void)hipFree(c.q_dev);
-        if (c.D_dev) (void)hipFree(c.D_dev);
-        if (c.I_dev) (void)hipFree(c.I_dev);
-        if (c.q_pin) (void)hipHostFree(c.q_pin);
-        if (c.D_pin) (void)hipHostFree(c.D_pin);
-        if (c.I_pin) (void)hipHostFree(c.I_pin);
-        if (c.stream) (void)hipStreamDestroy(c.stream);
-        c = ise_index::HostCtx();
-    }
-    {
-        auto& r = h->rg;
-        for (void* p : {(void*)r.q.p, (void*)r.cnt.p, (void*)r.segoff.p, (void*)r.sD.p, (void*)r.sI.p, (void*)r.tot.p,
-                        (void*)r.lims.p, (void*)r.flag.p, (void*)r.D.p, (void*)r.I.p})
-            if (p) (void)hipFree(p);
-        for (void* p : {(void*)r.q_pin.p, (void*)r.lims_pin.p, (void*)r.D_pin.p, (void*)r.I_pin.p})
-            if (p) (void)hipHostFree(p);
-        r = ise_index::RangeWs();
-    }
-    for (auto& sl : h->ss) {
-        for (void* p : {(void*)sl.q.p, (void*)sl.part.p, (void*)sl.keys.p})
-            if (p) (void)hipFree(p);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        sl = ise_index::SelSlot();
-    }
-    {
-        auto& sb = h->sub;
-        for (void* p : {(void*)sb.keys.p, (void*)sb.valid, (void*)sb.q.p, (void*)sb.out.p, (void*)sb.cand.p, (void*)sb.I.p})
-            if (p) (void)hipFree(p);
-        if (sb.last) (void)hipEventDestroy(sb.last);
-        sb.keys = DevBuf<u64>();
-        sb.q = sb.out = DevBuf<float>();
-        sb.cand = sb.I = DevBuf<long long>();
-        sb.valid = nullptr;
-        sb.last = nullptr;
-        sb.last_valid = false;
-    }
+    for (auto& w : h->ws) w.release();
+    for (auto& c : h->hc) c.release();
+    h->rg.release();
+    for (auto& sl : h->ss) sl.release();
+    h->sub.release();
     h->xb = h->norms = nullptr;
     h->n = h->cap = 0;
 }
@@ -512,14 +300,6 @@ static int reserve_rows(ise_index* h, long long need, hipStream_t st) {
 // true when float32 rows can be copied verbatim into the index layout
 static bool rows_copy_verbatim(const ise_index* h) { return h->storage == ISE_STORE_F32 && h->dp == h->d; }
 
-static bool uses_shift(const ise_index* h) { return h->storage == ISE_STORE_F32 && h->metric == ISE_METRIC_L2; }
-
-// float32 L2 indexes: bring mu and the norms up to date with the rows (called with the handle
-// locked, before a search / assignment reads them).  mu = column mean of ALL rows, recomputed when
-// the index has grown by a quarter since it was last taken (amortised O(1) per row); a new mu
-// means new norms for every row.  Rare and blocking: other streams' searches read mu and norms.
-static int prepare_shift_locked(ise_index* h, hipStream_t st);
-
 static void launch_shadow(ise_index* h, long long row0, long long n, hipStream_t st) {
     const long long nblk = (n + 3) / 4;
     if (nblk > 0)
@@ -633,7 +413,11 @@ static int alloc_shadow(ise_index* h) {
     return ISE_OK;
 }
 
-static int prepare_shift_locked(ise_index* h, hipStream_t st) {
+// float32 L2 indexes: bring mu and the norms up to date with the rows (called with the handle
+// locked, before a search / assignment reads them).  mu = column mean of ALL rows, recomputed when
+// the index has grown by a quarter since it was last taken (amortised O(1) per row); a new mu
+// means new norms for every row.  Rare and blocking: other streams' searches read mu and norms.
+int prepare_shift_locked(ise_index* h, hipStream_t st) {
     if (!uses_shift(h) || h->n == 0) return ISE_OK;
     const bool need_mu = !h->shift_pinned && (h->mu_rows == 0 || h->n >= h->mu_rows + h->mu_rows / 4 + 1);
     const bool need_shadow = shadow_wanted(h);
@@ -856,9 +640,6 @@ static int exact_extra(int k) {
     (void)k;
     return forced > 0 && forced <= 16 ? forced : 4;
 }
-// relative width of the scan's lower bound: every rounding between the stored floats and the keyed
-// value, in units of u = 2^-24 times (|x-mu|^2 + |y-mu|^2) (derivation: DESIGN.md section 4.1)
-static float exact_beta(const ise_index* h) { return exact_beta_dp(h->dp); }
 // the shadow-row filter's beta: the f16 MFMA dot of 2 dph exact products in any accumulation order, twice the
 // worst-case n u, plus the roundings of |u~|^2, |v~|^2 and the expanded form, relative to |u~|^2 + |v~|^2 (DESIGN.md
 // 4.1); and the factor that takes its square below the float32 direct-difference value (fmaf chains of dp / 64
@@ -869,38 +650,8 @@ static float half_lo_shrink(const ise_index* h) { return 1.f - ((float)h->dp / 1
 // the difference), of the float32 norm (dp / 64 + 9), of the dot (two: 256 A_hi + A_lo, times c_r; the integer
 // sums are exact) and of the expression, relative to tt, with a wide margin: none of them matters beside e_r
 static float byte_beta(const ise_index* h) { return ((float)h->dp / 8.f + 64.f) * 5.9604645e-8f * 1.02f; }
-// Test / rehearsal knobs that may change while the process runs: read from the environment when the library
-// is first used and again whenever ise_refresh_env_knobs() is called (the tests call it after changing the
-// environment) -- never inside a search, where another thread's setenv would race with getenv.
-struct EnvKnobs {
-    std::atomic<int> force_exact{0};    // ISE_FORCE_EXACT=1: fail every certificate (exercises the exact scan)
-    std::atomic<int> no_direct{0};      // ISE_NO_DIRECT=1: one-query batches take the filtered path as well
-    std::atomic<int> no_short{0};       // ISE_NO_SHORT=1: short indexes take the streaming kernel + merge launches
-    std::atomic<int> short_tpb_max{0};  // ISE_SHORT_TPB_MAX: most row tiles per block the short-index kernel takes
-    std::atomic<int> direct_short_max_tiles{0};  // ISE_DIRECT_SHORT_MAX_TILES: longest SHORT index (16-row tiles) whose one-query batches take the direct scan
-    std::atomic<int> range_stage_cap{0};  // ISE_RANGE_STAGE_CAP: staging entries per range-search segment (tests: force the overflow pass)
-    std::atomic<int> no_half{0};        // ISE_NO_HALF_FILTER=1: long float32 L2 indexes keep the float32 filter (A/B, tests)
-    std::atomic<int> no_byte{0};        // ISE_NO_BYTE_FILTER=1: ... filter through the fp16 shadow, never the byte one
-    std::atomic<int> fail_byte_alloc{0};  // ISE_FAIL_BYTE_ALLOC=1: the byte shadow's allocation fails as out of memory (tests)
-    std::atomic<int> remove_slab_rows{0};  // ISE_REMOVE_SLAB_ROWS: destination rows per slab of a removal (tests: cross many slabs)
-    std::atomic<int> scan_depth{0};     // ISE_SCAN_DEPTH: 0 = by the stream rule of search_enqueue, 1 = isolated plan, N >= 2 = depth N
-    void refresh() {
-        auto flag = [](const char* name) { const char* e = getenv(name); return (e && e[0] == '1') ? 1 : 0; };
-        auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
-        force_exact.store(flag("ISE_FORCE_EXACT"));
-        no_direct.store(flag("ISE_NO_DIRECT"));
-        no_short.store(flag("ISE_NO_SHORT"));
-        short_tpb_max.store(num("ISE_SHORT_TPB_MAX"));
-        direct_short_max_tiles.store(num("ISE_DIRECT_SHORT_MAX_TILES"));
-        range_stage_cap.store(num("ISE_RANGE_STAGE_CAP"));
-        no_half.store(flag("ISE_NO_HALF_FILTER"));
-        no_byte.store(flag("ISE_NO_BYTE_FILTER"));
-        fail_byte_alloc.store(flag("ISE_FAIL_BYTE_ALLOC"));
-        remove_slab_rows.store(num("ISE_REMOVE_SLAB_ROWS"));
-        scan_depth.store(std::max(0, num("ISE_SCAN_DEPTH")));
-    }
-};
-static EnvKnobs& knobs() {
+// (EnvKnobs: ise_flat.hpp)
+EnvKnobs& knobs() {
     static EnvKnobs k;
     static std::once_flag once;
     std::call_once(once, [] { k.refresh(); });
@@ -1108,72 +859,30 @@ static int make_plan(const ise_index* h, long long nq, int k, ScanPlan* pl, bool
 // keys_tmp = keys_all [nq][kc] | floor [nq] | pass_keys [nq][kpass] | exact floor [nq] | exact pass keys [nq][32];
 // exact path: the fallback list
 static int ensure_workspace(ise_index::WorkSlot* w, const ScanPlan& pl, long long nq, bool* changed) {
-    if (!w->done) HIP_TRY(hipEventCreateWithFlags(&w->done, hipEventDisableTiming));
+    if (!w->order.ev) HIP_TRY(w->order.create());
     // at least what the direct one-query scan can ask for (direct_applies): MERGE_LISTS_MAX lists of XPASS_MAX keys
     // (fb_nblocks: the depth-1 grid, never smaller than the deep plan's -- make_plan checks -- so that a slot sized
     // once serves both plans and nothing is allocated when a stream's batches change plan)
     const size_t need = std::max<size_t>((size_t)pl.nqt * pl.fb_nblocks * (16 * pl.T) * pl.kpass, (size_t)MERGE_LISTS_MAX * XPASS_MAX);
-    if (need > w->part_elems) {
-        if (w->part) (void)hipFree(w->part);  // hipFree waits for outstanding work
-        w->part = nullptr;
-        w->part_elems = 0;
-        HIP_TRY(hipMalloc(&w->part, need * sizeof(u64)));
-        w->part_elems = need;
-        *changed = true;
-    }
+    int rc = grow_slot(w->part, need, changed);
     const size_t needx = (size_t)pl.nqt * (16 * pl.T) * pl.fb_nblocks;
-    if (needx > w->xchg_elems) {
-        if (w->xchg) (void)hipFree(w->xchg);
-        w->xchg = nullptr;
-        w->xchg_elems = 0;
-        HIP_TRY(hipMalloc(&w->xchg, needx * sizeof(u64)));
-        HIP_TRY(hipMemset(w->xchg, 0xFF, needx * sizeof(u64)));  // tag 0xFFFFFFFF is never issued
-        w->xchg_elems = needx;
+    if (!rc && needx > w->xchg.n) {
+        if ((rc = grow_slot(w->xchg, needx, changed))) return rc;
+        HIP_TRY(hipMemset(w->xchg.p, 0xFF, needx * sizeof(u64)));  // tag 0xFFFFFFFF is never issued
         w->xchg_seq = 0;
         if (const char* e = getenv("ISE_XCHG_SEQ_START"))  // test knob: start near the tag wrap
             w->xchg_seq = (uint32_t)strtoul(e, nullptr, 0);
-        *changed = true;
     }
-    if (pl.kc > pl.kpass) {
-        const size_t need2 = (size_t)nq * ((size_t)pl.kc + 2 + pl.kpass + XPASS_MAX);
-        if (need2 > w->keys_tmp_elems) {
-            if (w->keys_tmp) (void)hipFree(w->keys_tmp);
-            w->keys_tmp = nullptr;
-            w->keys_tmp_elems = 0;
-            HIP_TRY(hipMalloc(&w->keys_tmp, need2 * sizeof(u64)));
-            w->keys_tmp_elems = need2;
-            *changed = true;
-        }
+    if (!rc && pl.kc > pl.kpass) rc = grow_slot(w->keys_tmp, (size_t)nq * ((size_t)pl.kc + 2 + pl.kpass + XPASS_MAX), changed);
+    if (!rc && pl.gemm) rc = grow_slot(w->gemm, pl.gemm_bytes, changed);
+    if (!rc && pl.exact && !w->fl_state.p) {
+        if ((rc = grow_slot(w->fl_state, 2, changed))) return rc;  // [0] the list's state, [1] the exact scan's arrival counter
+        HIP_TRY(hipMemset(w->fl_state.p, 0, 2 * sizeof(u64)));  // tag 0 is never issued
+        w->fl_seq = 0;
+        if (const char* e = getenv("ISE_XCHG_SEQ_START")) w->fl_seq = (uint32_t)strtoul(e, nullptr, 0);
     }
-    if (pl.gemm) {
-        const size_t needg = pl.gemm_bytes;
-        if (needg > w->gemm_bytes) {
-            if (w->gemm) (void)hipFree(w->gemm);
-            w->gemm = nullptr;
-            w->gemm_bytes = 0;
-            HIP_TRY(hipMalloc(&w->gemm, needg));
-            w->gemm_bytes = needg;
-            *changed = true;
-        }
-    }
-    if (pl.exact) {
-        if (!w->fl_state) {
-            HIP_TRY(hipMalloc(&w->fl_state, 2 * sizeof(u64)));  // [0] the list's state, [1] the exact scan's arrival counter
-            HIP_TRY(hipMemset(w->fl_state, 0, 2 * sizeof(u64)));  // tag 0 is never issued
-            w->fl_seq = 0;
-            if (const char* e = getenv("ISE_XCHG_SEQ_START")) w->fl_seq = (uint32_t)strtoul(e, nullptr, 0);
-            *changed = true;
-        }
-        if ((size_t)nq > w->fl_elems) {
-            if (w->fl_list) (void)hipFree(w->fl_list);
-            w->fl_list = nullptr;
-            w->fl_elems = 0;
-            HIP_TRY(hipMalloc(&w->fl_list, (size_t)nq * sizeof(int)));
-            w->fl_elems = (size_t)nq;
-            *changed = true;
-        }
-    }
-    return ISE_OK;
+    if (!rc && pl.exact) rc = grow_slot(w->fl_list, (size_t)nq, changed);
+    return rc;
 }
 
 // Every slot is sized for the plan at once (nothing is allocated, filled or synchronised on a later
@@ -1226,7 +935,7 @@ struct TimedOut {
 // (one stream, or an event wait), so no two of them write the buffer at once.
 static int next_xchg_seq(ise_index::WorkSlot* w, hipStream_t st, uint32_t* seq) {
     if (w->xchg_seq >= 0xFFFFFFF0u) {  // wrap: wipe the tags (stream-ordered behind the slot's last use)
-        HIP_TRY(hipMemsetAsync(w->xchg, 0xFF, w->xchg_elems * sizeof(u64), st));
+        HIP_TRY(hipMemsetAsync(w->xchg.p, 0xFF, w->xchg.n * sizeof(u64), st));
         w->xchg_seq = 0;
     }
     *seq = ++w->xchg_seq;
@@ -1234,7 +943,7 @@ static int next_xchg_seq(ise_index::WorkSlot* w, hipStream_t st, uint32_t* seq) 
 }
 static int next_fl_seq(ise_index::WorkSlot* w, hipStream_t st, uint32_t* seq) {
     if (w->fl_seq >= 0xFFFFFFF0u) {
-        HIP_TRY(hipMemsetAsync(w->fl_state, 0, sizeof(u64), st));
+        HIP_TRY(hipMemsetAsync(w->fl_state.p, 0, sizeof(u64), st));
         w->fl_seq = 0;
     }
     *seq = ++w->fl_seq;
@@ -1254,16 +963,16 @@ static int enqueue_exact_fallback(ise_index* h, ise_index::WorkSlot* w, const Sc
                                   long long nq, hipStream_t st) {
     ExactScanParams xs;
     xs.xb = (const float*)h->xb; xs.q = xp.q; xs.n = h->n; xs.d = h->d; xs.dp = h->dp;
-    xs.id_base = xp.id_base; xs.fl_state = w->fl_state; xs.fl_list = w->fl_list; xs.seq = xp.seq;
-    xs.part = w->part;  // the filter's lists are dead: [position][nblocks][kp] fits (kp <= kpass, positions <= nq)
+    xs.id_base = xp.id_base; xs.fl_state = w->fl_state.p; xs.fl_list = w->fl_list.p; xs.seq = xp.seq;
+    xs.part = w->part.p;  // the filter's lists are dead: [position][nblocks][kp] fits (kp <= kpass, positions <= nq)
     // (the depth-1 grid whatever plan the filter ran with: adversarial data is not scanned at half occupancy)
     xs.rows_per_block = (long long)pl.fb_tiles_per_block * 16;
-    xs.arrive = reinterpret_cast<unsigned int*>(w->fl_state + 1);
+    xs.arrive = reinterpret_cast<unsigned int*>(w->fl_state.p + 1);
     xs.direct_n = 0;
     const size_t lds = (size_t)XQ * h->dp * 4 + (size_t)XQ * 4 * 32 * 8;
     MergeParams mp;  // the per-block lists are merged by the scan's last block
-    mp.lists = w->part; mp.qt = 1; mp.n_lists = pl.fb_nblocks; mp.nq = (int)nq; mp.metric = h->metric;
-    mp.fl_state = w->fl_state; mp.fl_list = w->fl_list; mp.seq = xp.seq; mp.dbg = nullptr; mp.gate = nullptr;
+    mp.lists = w->part.p; mp.qt = 1; mp.n_lists = pl.fb_nblocks; mp.nq = (int)nq; mp.metric = h->metric;
+    mp.fl_state = w->fl_state.p; mp.fl_list = w->fl_list.p; mp.seq = xp.seq; mp.dbg = nullptr; mp.gate = nullptr;
     const int k = xp.k;
     if (k <= XPASS_MAX) {
         xs.kpass = k; xs.floor_keys = nullptr;
@@ -1273,7 +982,7 @@ static int enqueue_exact_fallback(ise_index* h, ise_index::WorkSlot* w, const Sc
         HIP_TRY(hipGetLastError());
         return ISE_OK;
     }
-    u64* fb_floor = w->keys_tmp + (size_t)nq * ((size_t)pl.kc + 1 + pl.kpass);  // [nq]
+    u64* fb_floor = w->keys_tmp.p + (size_t)nq * ((size_t)pl.kc + 1 + pl.kpass);  // [nq]
     u64* fb_pass = fb_floor + nq;                                             // [nq][XPASS_MAX]
     const int kp = XPASS_MAX;
     for (int off = 0; off < k; off += kp) {
@@ -1300,7 +1009,7 @@ static bool direct_applies(const ise_index* h, const ise_index::WorkSlot* w, con
                            int* blocks_out) {
     // one query only: two to four queries are VALU-bound here (380-520 us) and faster through the filter (356 us)
     // (ISE_FORCE_EXACT asks for the filtered path's fallback to be exercised: it implies the filtered path)
-    if (!pl.exact || nq != 1 || k > XPASS_MAX || h->n <= 0 || !w->fl_state || no_direct() || force_exact()) return false;
+    if (!pl.exact || nq != 1 || k > XPASS_MAX || h->n <= 0 || !w->fl_state.p || no_direct() || force_exact()) return false;
     // One query against a short index: up to ~2k rows the direct scan -- ONE launch, no merge, no gate -- has the
     // lower latency, by a microsecond (1000 x 512: 20.6 against 22.1 us per call; 3000: 22.2 against 22.5; 4000:
     // 23.6 against 22.3; 16000: 30.9 against 23.7, scripts/direct_crossover_probe.py): its time grows with the rows
@@ -1319,7 +1028,7 @@ static bool direct_applies(const ise_index* h, const ise_index::WorkSlot* w, con
     long long blocks = std::min<long long>(MERGE_LISTS_MAX, (h->n + min_rows - 1) / min_rows);
     static const long long per_cu = [] { const char* e = getenv("ISE_DIRECT_BLOCKS_PER_CU"); const int v = e ? atoi(e) : 0; return (long long)(v > 0 ? v : 2); }();
     blocks = std::min<long long>(blocks, (long long)h->num_cu * per_cu);
-    if ((size_t)nq * blocks * k > w->part_elems) return false;  // the slot's lists are sized for the filter's plan
+    if ((size_t)nq * blocks * k > w->part.n) return false;  // the slot's lists are sized for the filter's plan
     *blocks_out = (int)blocks;
     return true;
 }
@@ -1328,14 +1037,14 @@ static int direct_small_enqueue(ise_index* h, ise_index::WorkSlot* w, int blocks
                                 TimedOut* tm) {
     ExactScanParams xs;
     xs.xb = (const float*)h->xb; xs.q = q_dev; xs.n = h->n; xs.d = h->d; xs.dp = h->dp;
-    xs.kpass = k; xs.id_base = id_base; xs.fl_state = w->fl_state; xs.fl_list = w->fl_list; xs.seq = 0;
-    xs.floor_keys = nullptr; xs.part = w->part;
+    xs.kpass = k; xs.id_base = id_base; xs.fl_state = w->fl_state.p; xs.fl_list = w->fl_list.p; xs.seq = 0;
+    xs.floor_keys = nullptr; xs.part = w->part.p;
     xs.rows_per_block = (h->n + blocks - 1) / blocks;
-    xs.arrive = reinterpret_cast<unsigned int*>(w->fl_state + 1);
+    xs.arrive = reinterpret_cast<unsigned int*>(w->fl_state.p + 1);
     xs.direct_n = (int)nq;
     MergeParams mp;
-    mp.lists = w->part; mp.qt = 1; mp.n_lists = blocks; mp.nq = (int)nq; mp.metric = h->metric;
-    mp.fl_state = w->fl_state; mp.fl_list = w->fl_list; mp.seq = 0; mp.dbg = nullptr; mp.gate = nullptr;
+    mp.lists = w->part.p; mp.qt = 1; mp.n_lists = blocks; mp.nq = (int)nq; mp.metric = h->metric;
+    mp.fl_state = w->fl_state.p; mp.fl_list = w->fl_list.p; mp.seq = 0; mp.dbg = nullptr; mp.gate = nullptr;
     mp.k = k; mp.stride_list = k; mp.stride_qtile = (long long)blocks * k;
     mp.D = D_dev; mp.I = I_dev; mp.keys_out = keys_out; mp.out_by_pos = 0;
     if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e0, st));
@@ -1432,7 +1141,7 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
                              TimedOut* tm, const unsigned int* gate) {
     int rc;
     ScanParams sp;
-    sp.xb = h->xb; sp.norms = h->norms; sp.q = q_dev; sp.mu = h->mu; sp.floor_keys = nullptr; sp.part = w->part;
+    sp.xb = h->xb; sp.norms = h->norms; sp.q = q_dev; sp.mu = h->mu; sp.floor_keys = nullptr; sp.part = w->part.p;
     sp.n = h->n; sp.d = h->d; sp.dp = h->dp; sp.qs_stride = qs_stride_for(h);
     sp.row_slots = (int)(row_bytes(h) / 16);
     sp.nq = (int)nq; sp.k = pl.kpass; sp.kb = pl.kb; sp.metric = h->metric; sp.id_base = id_base;
@@ -1451,7 +1160,7 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
         h->half_batches++;
     }
     sp.tiles_total = pl.tiles_total; sp.tiles_per_block = pl.tiles_per_block;
-    sp.xchg = xchg_enabled() ? w->xchg : nullptr;
+    sp.xchg = xchg_enabled() ? w->xchg.p : nullptr;
     sp.xchg_seq = 0;
     sp.gate = gate;
     sp.ablate = 0;
@@ -1463,7 +1172,7 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
 
     MergeParams mp;
     const int NQ = 16 * pl.T;
-    mp.lists = w->part; mp.stride_list = (long long)NQ * pl.kpass;
+    mp.lists = w->part.p; mp.stride_list = (long long)NQ * pl.kpass;
     mp.stride_qtile = (long long)pl.nblocks * NQ * pl.kpass; mp.qt = NQ;
     mp.n_lists = pl.nblocks; mp.nq = (int)nq; mp.k = pl.kpass; mp.metric = h->metric;
     mp.fl_state = nullptr; mp.fl_list = nullptr; mp.seq = 0; mp.out_by_pos = 0;
@@ -1473,7 +1182,7 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
     ExactParams xp;  // used on the exact path only
     xp.xb = (const float*)h->xb; xp.q = q_dev; xp.n = h->n; xp.d = h->d; xp.dp = h->dp; xp.nq = (int)nq;
     xp.k = k; xp.kc = pl.kc; xp.id_base = id_base; xp.D = D_dev; xp.I = I_dev; xp.keys_out = keys_out;
-    xp.fl_state = w->fl_state; xp.fl_list = w->fl_list; xp.seq = 0; xp.stats = h->stats_dev;
+    xp.fl_state = w->fl_state.p; xp.fl_list = w->fl_list.p; xp.seq = 0; xp.stats = h->stats_dev;
     xp.force_fail = force_exact() ? 1 : 0;
     xp.tau_bound = nullptr;
 
@@ -1526,8 +1235,8 @@ static int scan_path_enqueue(ise_index* h, ise_index::WorkSlot* w, const ScanPla
     // kc > KPASS_MAX: passes of KPASS_MAX; a pass only admits keys above the
     // previous pass's last key (keys are totally ordered and unique)
     const int kc = pl.kc;
-    u64* keys_all = (!pl.exact && keys_out) ? keys_out : w->keys_tmp;  // [nq][kc]
-    u64* floor_dev = w->keys_tmp + (size_t)nq * kc;                    // [nq]
+    u64* keys_all = (!pl.exact && keys_out) ? keys_out : w->keys_tmp.p;  // [nq][kc]
+    u64* floor_dev = w->keys_tmp.p + (size_t)nq * kc;                    // [nq]
     u64* pass_keys = floor_dev + nq;                                   // [nq][kpass]
     if (tm && tm->on) HIP_TRY(hipEventRecord(tm->e0, st));
     for (int off = 0; off < kc; off += pl.kpass) {
@@ -1630,12 +1339,12 @@ static int search_large_chunk(ise_index* h, ise_index::WorkSlot* w, const float*
     const int S = qs_stride_for(h);
     const GemmLayout gl = gemm_layout(h);
     h->gemm_chunks++;
-    float* qprep = reinterpret_cast<float*>(w->gemm + gl.qprep);
-    float* xn = reinterpret_cast<float*>(w->gemm + gl.xn);
-    float* tau = reinterpret_cast<float*>(w->gemm + gl.tau);
-    unsigned int* ccnt = reinterpret_cast<unsigned int*>(w->gemm + gl.ccnt);
-    float* dump = reinterpret_cast<float*>(w->gemm + gl.dump);
-    u64* cand = reinterpret_cast<u64*>(w->gemm + gl.cand);
+    float* qprep = reinterpret_cast<float*>(w->gemm.p + gl.qprep);
+    float* xn = reinterpret_cast<float*>(w->gemm.p + gl.xn);
+    float* tau = reinterpret_cast<float*>(w->gemm.p + gl.tau);
+    unsigned int* ccnt = reinterpret_cast<unsigned int*>(w->gemm.p + gl.ccnt);
+    float* dump = reinterpret_cast<float*>(w->gemm.p + gl.dump);
+    u64* cand = reinterpret_cast<u64*>(w->gemm.p + gl.cand);
     const int nq_pad = (int)((nq + fl.gq - 1) / fl.gq * fl.gq);
     auto launch = [&](bool sample, int grid, const GemmScanParams& gp) {
         if (fl.bf16) return sample ? launch_gemm_bf16<true>(fl.ns, grid, fl.lds, st, gp) : launch_gemm_bf16<false>(fl.ns, grid, fl.lds, st, gp);
@@ -1656,7 +1365,7 @@ static int search_large_chunk(ise_index* h, ise_index::WorkSlot* w, const float*
     gp.xb = (const float*)h->xb; gp.norms = h->norms; gp.mu = fl.mu; gp.n = h->n; gp.rows16 = (h->n + 15) / 16 * 16;
     gp.dp = h->dp; gp.S = S; gp.qprep = qprep; gp.xn = xn; gp.tau = tau; gp.nq = (int)nq; gp.nq_pad = nq_pad;
     gp.beta = fl.beta; gp.id_base = id_base; gp.metric = h->metric;
-    gp.wbuf = reinterpret_cast<u32x4*>(w->gemm + gl.wbuf); gp.wcnt = reinterpret_cast<unsigned int*>(w->gemm + gl.wcnt);
+    gp.wbuf = reinterpret_cast<u32x4*>(w->gemm.p + gl.wbuf); gp.wcnt = reinterpret_cast<unsigned int*>(w->gemm.p + gl.wcnt);
     gp.capw = GEMM_CAPW;
     gp.ablate = 0;
 #ifdef ISE_ABLATE
@@ -1698,7 +1407,7 @@ static int search_large_chunk(ise_index* h, ise_index::WorkSlot* w, const float*
         ExactParams xp;
         xp.xb = (const float*)h->xb; xp.q = q_dev; xp.n = h->n; xp.d = h->d; xp.dp = h->dp; xp.nq = (int)nq;
         xp.k = k; xp.kc = fl.kth; xp.id_base = id_base; xp.D = D_dev; xp.I = I_dev; xp.keys_out = keys_out;
-        xp.fl_state = w->fl_state; xp.fl_list = w->fl_list; xp.seq = 0; xp.stats = h->stats_dev;
+        xp.fl_state = w->fl_state.p; xp.fl_list = w->fl_list.p; xp.seq = 0; xp.stats = h->stats_dev;
         xp.force_fail = force_exact() ? 1 : 0;
         xp.tau_bound = tau;
         if ((rc = next_fl_seq(w, st, &xp.seq))) return rc;
@@ -1722,34 +1431,6 @@ static int search_large_chunk(ise_index* h, ise_index::WorkSlot* w, const float*
     return ISE_OK;
 }
 
-// Slot hand-out of the WorkSlots and the SelSlots (mu_ held): a stream keeps the slot it used last (stream order is
-// all the ordering that needs); a stream without one takes a fresh slot, or the least recently taken one behind an
-// event wait.  *waited (optional): the slot's last user was another stream.
-template <class Slot, int N>
-static int take_slot(Slot (&slots)[N], unsigned* next, hipStream_t st, Slot** out, bool* waited) {
-    Slot* w = nullptr;
-    bool same_stream = false;
-    for (auto& s : slots)
-        if (s.used && s.last_stream == st) { w = &s; same_stream = true; break; }
-    if (!w)
-        for (auto& s : slots)
-            if (!s.used) { w = &s; break; }
-    if (!w) w = &slots[(*next)++ % N];
-    const bool other = w->used && !same_stream;
-    if (other) HIP_TRY(hipStreamWaitEvent(st, w->done, 0));
-    if (waited) *waited = other;
-    *out = w;
-    return ISE_OK;
-}
-template <class Slot>
-struct SlotRelease {  // whatever path returns, a later user on another stream waits for this call
-    Slot* w;
-    hipStream_t st;
-    ~SlotRelease() {
-        if (hipEventRecord(w->done, st) == hipSuccess) { w->used = true; w->last_stream = st; }
-    }
-};
-
 // enqueue one search batch; outputs (D, I) and/or keys.  Nothing here blocks once the slots are
 // sized (first batch of a shape) and the shift is current (first batch after rows were added).
 static int search_enqueue(ise_index* h, const float* q_dev, long long nq, int k, uint32_t id_base, float* D_dev,
@@ -1772,7 +1453,7 @@ static int search_enqueue(ise_index* h, const float* q_dev, long long nq, int k,
     if (rc) return rc;
     ise_index::WorkSlot* w = nullptr;
     if ((rc = take_slot(h->ws, &h->ws_next, st, &w, nullptr))) return rc;
-    SlotRelease<ise_index::WorkSlot> release{w, st};
+    CallOrder::Scope release{w->order, st};
 
     if (pl.gemm) {  // float32 L2 or bf16 rows, nq >= 256: GEMM-shaped pass, GEMM_NQ_MAX queries at a time
         for (long long q0 = 0; q0 < nq; q0 += GEMM_NQ_MAX) {
@@ -1791,7 +1472,7 @@ static int search_enqueue(ise_index* h, const float* q_dev, long long nq, int k,
     return scan_path_enqueue(h, w, pl, q_dev, nq, k, id_base, D_dev, I_dev, keys_out, st, tm, nullptr);
 }
 
-static int check_search_args(const ise_index* h, const void* q, long long nq, int k) {
+int check_search_args(const ise_index* h, const void* q, long long nq, int k) {
     if (!h) return fail(ISE_E_INVALID, "handle is NULL");
     if (nq < 0 || (nq > 0 && !q)) return fail(ISE_E_INVALID, "bad query argument");
     if (k <= 0 || k > ISE_MAX_K) return fail(ISE_E_INVALID, "k must be in [1, 2048]");
@@ -1858,71 +1539,10 @@ extern "C" int ise_index_search_timed_device(ise_index_t* h, const float* q_dev,
     return ISE_OK;
 }
 
-// Host-API searches run on a small pool of contexts (stream + staging buffers), and hold the handle
-// lock only while their kernels are enqueued: concurrent callers (Flask request threads,
-// backend/engine.py:137; joblib threads, backend/descriptors.py:125) overlap their copies and
-// their scans instead of queueing behind one stream.
-static ise_index::HostCtx* acquire_ctx(ise_index* h) {
-    std::unique_lock<std::mutex> lk(h->hc_mu);
-    for (;;) {
-        for (auto& c : h->hc)
-            if (!c.busy) { c.busy = true; return &c; }
-        h->hc_cv.wait(lk);
-    }
-}
-static void release_ctx(ise_index* h, ise_index::HostCtx* c) {
-    { std::lock_guard<std::mutex> lk(h->hc_mu); c->busy = false; }
-    h->hc_cv.notify_one();
-}
-
-// The staging loop of the plain and the filtered host search, on one of the host contexts: `batch` queries at a time
-// (bounds the workspace; larger calls loop) are copied in, enqueued by enqueue(c, m) under mu_, copied out, waited for
-template <class Enqueue>
-static int search_host_staged(ise_index* h, const float* q, long long nq, int k, long long batch, float* D, long long* I,
-                              Enqueue enqueue) {
-    DeviceGuard gd(h->device);
-    ise_index::HostCtx* c = acquire_ctx(h);
-    struct Rel { ise_index* h; ise_index::HostCtx* c; ~Rel() { release_ctx(h, c); } } rel{h, c};
-    if (!c->stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    const size_t qe = (size_t)std::min<long long>(nq, batch) * h->d;
-    const size_t oe = (size_t)std::min<long long>(nq, batch) * k;
-    if (qe > c->q_elems) {
-        if (c->q_dev) (void)hipFree(c->q_dev);
-        c->q_dev = nullptr; c->q_elems = 0;
-        HIP_TRY(hipMalloc(&c->q_dev, qe * sizeof(float)));
-        c->q_elems = qe;
-    }
-    if (oe > c->out_elems) {
-        if (c->D_dev) (void)hipFree(c->D_dev);
-        if (c->I_dev) (void)hipFree(c->I_dev);
-        c->D_dev = nullptr; c->I_dev = nullptr; c->out_elems = 0;
-        HIP_TRY(hipMalloc(&c->D_dev, oe * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->I_dev, oe * sizeof(long long)));
-        c->out_elems = oe;
-    }
-    for (long long i0 = 0; i0 < nq; i0 += batch) {
-        const long long m = std::min<long long>(batch, nq - i0);
-        HIP_TRY(hipMemcpyAsync(c->q_dev, q + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice,
-                               c->stream));
-        int rc;
-        {
-            std::lock_guard<std::mutex> lk(h->mu_);
-            rc = enqueue(c, m);
-        }
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(D + (size_t)i0 * k, c->D_dev, (size_t)m * k * sizeof(float), hipMemcpyDeviceToHost,
-                               c->stream));
-        HIP_TRY(hipMemcpyAsync(I + (size_t)i0 * k, c->I_dev, (size_t)m * k * sizeof(long long), hipMemcpyDeviceToHost,
-                               c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return ISE_OK;
-}
-
 // one caller, one scan: queries straight from the caller's memory, results straight into it
 static int search_host_direct(ise_index* h, const float* q, long long nq, int k, float* D, long long* I) {
     return search_host_staged(h, q, nq, k, k + 6 <= XPASS_MAX ? 4096 : 1024, D, I, [&](ise_index::HostCtx* c, long long m) {
-        return search_enqueue(h, c->q_dev, m, k, 0u, c->D_dev, c->I_dev, nullptr, c->stream, nullptr);
+        return search_enqueue(h, c->q_dev.p, m, k, 0u, c->D_dev.p, c->I_dev.p, nullptr, c->stream, nullptr);
     });
 }
 
@@ -1942,61 +1562,34 @@ static long long host_combine_max() {
 // the requests of one combined batch (same k): gather -> one upload -> one search -> one download -> scatter
 static int run_combined(ise_index* h, const std::vector<ise_index::HostReq*>& batch, long long total, int k) {
     DeviceGuard gd(h->device);
-    ise_index::HostCtx* c = acquire_ctx(h);
-    struct Rel { ise_index* h; ise_index::HostCtx* c; ~Rel() { release_ctx(h, c); } } rel{h, c};
-    if (!c->stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    CtxLease lease(h);
+    ise_index::HostCtx* c = lease.c;
     const size_t qe = (size_t)total * h->d, oe = (size_t)total * k;
-    if (qe > c->q_elems) {
-        if (c->q_dev) (void)hipFree(c->q_dev);
-        c->q_dev = nullptr; c->q_elems = 0;
-        HIP_TRY(hipMalloc(&c->q_dev, qe * sizeof(float)));
-        c->q_elems = qe;
-    }
-    if (oe > c->out_elems) {
-        if (c->D_dev) (void)hipFree(c->D_dev);
-        if (c->I_dev) (void)hipFree(c->I_dev);
-        c->D_dev = nullptr; c->I_dev = nullptr; c->out_elems = 0;
-        HIP_TRY(hipMalloc(&c->D_dev, oe * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->I_dev, oe * sizeof(long long)));
-        c->out_elems = oe;
-    }
-    if (qe > c->q_pin_elems) {
-        if (c->q_pin) (void)hipHostFree(c->q_pin);
-        c->q_pin = nullptr; c->q_pin_elems = 0;
-        const size_t want = std::max<size_t>(qe, (size_t)std::max<long long>(host_combine_max(), 1) * h->d);
-        HIP_TRY(hipHostMalloc(&c->q_pin, want * sizeof(float), hipHostMallocDefault));
-        c->q_pin_elems = want;
-    }
-    if (oe > c->out_pin_elems) {
-        if (c->D_pin) (void)hipHostFree(c->D_pin);
-        if (c->I_pin) (void)hipHostFree(c->I_pin);
-        c->D_pin = nullptr; c->I_pin = nullptr; c->out_pin_elems = 0;
-        const size_t want = std::max<size_t>(oe, (size_t)std::max<long long>(host_combine_max(), 1) * k);
-        HIP_TRY(hipHostMalloc(&c->D_pin, want * sizeof(float), hipHostMallocMapped));
-        HIP_TRY(hipHostMalloc(&c->I_pin, want * sizeof(long long), hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer((void**)&c->D_pin_dev, c->D_pin, 0));
-        HIP_TRY(hipHostGetDevicePointer((void**)&c->I_pin_dev, c->I_pin, 0));
-        c->out_pin_elems = want;
-    }
+    const size_t rows = (size_t)std::max<long long>(host_combine_max(), 1);  // the page-locked part never holds less
+    int rc = lease.stream();
+    if (!rc) rc = c->stage(qe, oe);
+    if (!rc) rc = grow_owned(c->q_pin, qe, rows * h->d);
+    if (!rc) rc = grow_owned(c->D_pin, oe, rows * k);
+    if (!rc) rc = grow_owned(c->I_pin, oe, rows * k);
+    if (rc) return rc;
     size_t off = 0;
     for (const auto* r : batch) {
-        memcpy(c->q_pin + off * h->d, r->q, (size_t)r->nq * h->d * sizeof(float));
+        memcpy(c->q_pin.p + off * h->d, r->q, (size_t)r->nq * h->d * sizeof(float));
         off += (size_t)r->nq;
     }
-    HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, qe * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    int rc;
+    HIP_TRY(hipMemcpyAsync(c->q_dev.p, c->q_pin.p, qe * sizeof(float), hipMemcpyHostToDevice, c->stream));
     {
         std::lock_guard<std::mutex> lk(h->mu_);
         // results go straight into the pinned host buffers (mapped, coherent: the last kernel's few hundred bytes
         // travel as posted writes and are visible when the stream has drained) -- two copy launches less per call
-        rc = search_enqueue(h, c->q_dev, total, k, 0u, c->D_pin_dev, c->I_pin_dev, nullptr, c->stream, nullptr);
+        rc = search_enqueue(h, c->q_dev.p, total, k, 0u, c->D_pin.dev, c->I_pin.dev, nullptr, c->stream, nullptr);
     }
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     off = 0;
     for (auto* r : batch) {
-        memcpy(r->D, c->D_pin + off * k, (size_t)r->nq * k * sizeof(float));
-        memcpy(r->I, c->I_pin + off * k, (size_t)r->nq * k * sizeof(long long));
+        memcpy(r->D, c->D_pin.p + off * k, (size_t)r->nq * k * sizeof(float));
+        memcpy(r->I, c->I_pin.p + off * k, (size_t)r->nq * k * sizeof(long long));
         off += (size_t)r->nq;
     }
     return ISE_OK;
@@ -2050,671 +1643,15 @@ extern "C" int ise_index_search_host(ise_index_t* h, const float* q, int64_t nq,
     return ISE_OK;
 }
 
-// ---- range search (ise_range.hpp): index.range_search(x, radius) -> (lims, D, I)
-struct ise_range_result {
-    std::vector<int64_t> lims;
-    std::vector<float> D;
-    std::vector<int64_t> I;
-};
-
-#define RANGE_NQ_CHUNK 256          /* queries per batch: one host synchronisation (and 16 passes over the index) each */
-#define RANGE_STAGE_CAP 16          /* default staging entries per (query, wave segment) */
-#define RANGE_STAGE_MAX (1ll << 23) /* most staged entries per batch (64 MiB): a smaller capacity beyond that */
-
-// grow a device (or, pinned, page-locked host) buffer to at least `need` elements; contents are not kept
-// rule: no wait before a free -- range search owns its workspace (rg_mu) and drains it per batch, a SelSlot's other user was waited for
-template <class T>
-static int range_grow(DevBuf<T>& b, size_t need, bool pinned = false) {
-    if (b.p && need <= b.n) return ISE_OK;
-    if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
-    b.p = nullptr;
-    b.n = 0;
-    const size_t want = std::max<size_t>(need, 1);
-    if (pinned) HIP_TRY(hipHostMalloc((void**)&b.p, want * sizeof(T), hipHostMallocDefault));
-    else HIP_TRY(hipMalloc((void**)&b.p, want * sizeof(T)));
-    b.n = want;
-    return ISE_OK;
-}
-
-template <bool BF16, bool SHIFT>
-static void launch_range_v(int ch, dim3 grid, size_t lds, hipStream_t st, const RangeParams& rp) {
-    static LdsAttrOnce attr[3];
-    auto go = [&](auto kern, LdsAttrOnce& a) {
-        a.ensure(reinterpret_cast<const void*>(kern), LDS_LIMIT);
-        hipLaunchKernelGGL(kern, grid, dim3(RANGE_W * 64), lds, st, rp);
-    };
-    if (ch >= 4) go(range_scan_kernel<4, BF16, SHIFT>, attr[0]);
-    else if (ch == 2) go(range_scan_kernel<2, BF16, SHIFT>, attr[1]);
-    else go(range_scan_kernel<1, BF16, SHIFT>, attr[2]);
-}
-static void launch_range(const ise_index* h, int ch, dim3 grid, size_t lds, hipStream_t st, const RangeParams& rp) {
-    if (h->storage == ISE_STORE_BF16) launch_range_v<true, false>(ch, grid, lds, st, rp);
-    else if (uses_shift(h)) launch_range_v<false, true>(ch, grid, lds, st, rp);
-    else launch_range_v<false, false>(ch, grid, lds, st, rp);
-}
-
-// the index as the range kernels read it (mu_ held, shift prepared)
-static void range_params_index(const ise_index* h, RangeParams* rp) {
-    rp->xb = h->xb;
-    rp->norms = h->norms;
-    rp->mu = h->mu;
-    rp->d = h->d;
-    rp->dp = h->dp;
-    rp->qs_stride = qs_stride_for(h);
-    rp->row_slots = (int)(row_bytes(h) / 16);
-    rp->metric = h->metric;
-    rp->beta = uses_shift(h) ? exact_beta(h) : 0.f;
-}
-
-// ---- selectors (ise_sel_scan.hpp): a device bitmap over the rows of ONE index at ONE (ntotal, row epoch)
-struct ise_selector : SelectorBase {};  // bits: ceil(ntotal / 32) words + zero padding (pad rows of the last tile and word: zero bits)
-
-// mu_ held.  A selector is good for the handle it was made from while ntotal and the row epoch stand
-static int selector_check_locked(const ise_index* h, const ise_selector* sel) {
-    if (!sel) return fail(ISE_E_INVALID, "selector is NULL");
-    if (sel->owner != h) return fail(ISE_E_INVALID, "the selector was made for another index");
-    if (sel->epoch != h->row_epoch)
-        return fail(ISE_E_INVALID, "stale selector: rows were removed from the index (row epoch changed) since it was made");
-    if (sel->ntotal != h->n)
-        return fail(ISE_E_INVALID, "stale selector: ntotal changed (" + std::to_string(sel->ntotal) + " -> " +
-                                       std::to_string(h->n) + ") since it was made");
-    return ISE_OK;
-}
-
 // the streaming kernel's query staging for this index (the bits of |x|^2 for bf16 L2): threads per query row from
 // the waves of its one-tile plan, the vector path where the rows allow it (padded queries are 16-byte aligned)
-static int range_staging(const ise_index* h, int qs_stride, int* tpr, int* vec_q) {
+int range_staging(const ise_index* h, int qs_stride, int* tpr, int* vec_q) {
     ScanPlan pl;
     const int rc = make_plan(h, 16, 1, &pl, false, false);
     if (rc) return rc;
     range_staging_rule(pl.waves, h->storage == ISE_STORE_BF16, h->d, qs_stride, tpr, vec_q);
     return ISE_OK;
 }
-
-// one batch of m <= RANGE_NQ_CHUNK queries, appended to r (rg_mu held).  sel: restricted to a selector's window and
-// mask (the MASK instantiations), or null
-static int range_batch(ise_index* h, hipStream_t st, const float* q, long long m, float radius, const ise_selector* sel,
-                       ise_range_result* r) {
-    auto& ws = h->rg;
-    const int dp = h->dp, d = h->d;
-    // queries zero padded to dp: the staging reads them per row, the direct difference as exact_l2_rows does
-    int rc = range_grow(ws.q_pin, (size_t)m * dp, true);
-    if (!rc) rc = range_grow(ws.q, (size_t)m * dp);
-    if (rc) return rc;
-    for (long long i = 0; i < m; i++) {
-        memcpy(ws.q_pin.p + (size_t)i * dp, q + (size_t)i * d, (size_t)d * sizeof(float));
-        memset(ws.q_pin.p + (size_t)i * dp + d, 0, (size_t)(dp - d) * sizeof(float));
-    }
-    HIP_TRY(hipMemcpyAsync(ws.q.p, ws.q_pin.p, (size_t)m * dp * sizeof(float), hipMemcpyHostToDevice, st));
-
-    RangeParams rp{};
-    dim3 grid;
-    size_t lds = 0;
-    int ch = 1;
-    long long n0 = 0;
-    {
-        std::lock_guard<std::mutex> lk(h->mu_);
-        rc = prepare_shift_locked(h, st);
-        if (rc) return rc;
-        n0 = h->n;
-        if (n0 == 0) {  // an empty index (a reset since the caller looked): every list is empty
-            r->lims.resize(r->lims.size() + (size_t)m, r->lims.back());
-            return ISE_OK;
-        }
-        if (sel) {
-            rc = selector_check_locked(h, sel);
-            if (rc) return rc;
-            if (sel->count == 0) {  // an empty selection: every list is empty
-                r->lims.resize(r->lims.size() + (size_t)m, r->lims.back());
-                h->sel_range_batches++;
-                return ISE_OK;
-            }
-        }
-        range_params_index(h, &rp);
-        rc = range_staging(h, rp.qs_stride, &rp.tpr, &rp.vec_q);
-        if (rc) return rc;
-        ch = std::min(chunk_steps(h), 4);
-        // blocks own contiguous slabs of row tiles (of the selector's window), up to 4 blocks per CU
-        rp.tile0 = sel ? (int)(sel->r0 / 16) : 0;
-        rp.bits = sel ? sel->bits : nullptr;
-        rp.tiles_total = sel ? (int)((sel->r1 + 15) / 16) : (int)((n0 + 15) / 16);
-        const int span = rp.tiles_total - rp.tile0;
-        int nb = std::max(1, std::min(span, 4 * h->num_cu));
-        rp.tiles_per_block = (span + nb - 1) / nb;
-        nb = (span + rp.tiles_per_block - 1) / rp.tiles_per_block;
-        rp.nseg = nb * RANGE_W;
-        rp.n = n0;
-        rp.nq = (int)m;
-        rp.radius = radius;
-        int cap = knobs().range_stage_cap.load(std::memory_order_relaxed);
-        if (cap <= 0) cap = RANGE_STAGE_CAP;
-        rp.cap = (int)std::max<long long>(1, std::min<long long>(cap, RANGE_STAGE_MAX / (m * rp.nseg)));
-        const size_t segs = (size_t)m * rp.nseg;
-        rc = range_grow(ws.cnt, segs);
-        if (!rc) rc = range_grow(ws.segoff, segs);
-        if (!rc) rc = range_grow(ws.sD, segs * rp.cap);
-        if (!rc) rc = range_grow(ws.sI, segs * rp.cap);
-        if (!rc) rc = range_grow(ws.tot, (size_t)m);
-        if (!rc) rc = range_grow(ws.lims, (size_t)m + 1);
-        if (!rc) rc = range_grow(ws.flag, 1);
-        if (!rc) rc = range_grow(ws.lims_pin, (size_t)m + 2, true);
-        if (rc) return rc;
-        rp.q = ws.q.p;
-        rp.cnt = ws.cnt.p;
-        rp.sD = ws.sD.p;
-        rp.sI = ws.sI.p;
-        rp.mode = 0;
-        rp.g0 = 0;
-        grid = dim3((unsigned)nb, (unsigned)((m + 15) / 16));
-        lds = range_lds_bytes(rp.qs_stride);
-        HIP_TRY(hipMemsetAsync(ws.flag.p, 0, sizeof(unsigned), st));
-        if (sel) ise_launch_range_masked(h->storage == ISE_STORE_BF16, uses_shift(h), ch, grid, lds, st, rp);
-        else launch_range(h, ch, grid, lds, st, rp);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(range_offsets_kernel, dim3((unsigned)m), dim3(256), 0, st, ws.cnt.p, rp.nseg, rp.cap,
-                       ws.segoff.p, ws.tot.p, ws.flag.p);
-    hipLaunchKernelGGL(range_lims_kernel, dim3(1), dim3(1024), 0, st, ws.tot.p, (int)m, ws.lims.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(ws.lims_pin.p, ws.lims.p, (size_t)(m + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(ws.lims_pin.p + m + 1, ws.flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));  // the one synchronisation: the total sizes the output
-    const long long total = ws.lims_pin.p[m];
-    const bool overflow = *reinterpret_cast<const unsigned*>(ws.lims_pin.p + m + 1) != 0;
-    if (total > 0) {
-        rc = range_grow(ws.D, (size_t)total);
-        if (!rc) rc = range_grow(ws.I, (size_t)total);
-        if (!rc) rc = range_grow(ws.D_pin, (size_t)total, true);
-        if (!rc) rc = range_grow(ws.I_pin, (size_t)total, true);
-        if (rc) return rc;
-        if (overflow) {  // a segment overflowed: read the index once more, every hit straight to its exact offset
-            std::lock_guard<std::mutex> lk(h->mu_);
-            rc = prepare_shift_locked(h, st);
-            if (rc) return rc;
-            if (h->n < n0 || !h->xb) return fail(ISE_E_INVALID, "the index was reset during range_search");
-            if (sel) {  // an add since the first pass: the selector no longer names this index's rows
-                rc = selector_check_locked(h, sel);
-                if (rc) return rc;
-            }
-            range_params_index(h, &rp);
-            rp.mode = 1;
-            rp.lims = ws.lims.p;
-            rp.segoff = ws.segoff.p;
-            rp.D = ws.D.p;
-            rp.I = ws.I.p;
-            if (sel) ise_launch_range_masked(h->storage == ISE_STORE_BF16, uses_shift(h), ch, grid, lds, st, rp);
-            else launch_range(h, ch, grid, lds, st, rp);
-            HIP_TRY(hipGetLastError());
-        } else {
-            hipLaunchKernelGGL(range_compact_kernel, dim3((unsigned)((rp.nseg + 3) / 4), (unsigned)m), dim3(256), 0,
-                               st, ws.cnt.p, ws.sD.p, ws.sI.p, ws.lims.p, ws.segoff.p, rp.nseg, rp.cap, ws.D.p, ws.I.p);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemcpyAsync(ws.D_pin.p, ws.D.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(ws.I_pin.p, ws.I.p, (size_t)total * sizeof(long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        r->D.insert(r->D.end(), ws.D_pin.p, ws.D_pin.p + total);
-        r->I.insert(r->I.end(), ws.I_pin.p, ws.I_pin.p + total);
-    }
-    const int64_t base = r->lims.back();
-    for (long long i = 1; i <= m; i++) r->lims.push_back(base + ws.lims_pin.p[i]);
-    if (sel) h->sel_range_batches++;
-    else h->range_batches++;
-    if (overflow) h->range_overflows++;
-    return ISE_OK;
-}
-
-static int range_search_host(ise_index_t* h, const float* q, int64_t nq, float radius, const ise_selector* sel,
-                             ise_range_result_t** out) {
-    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
-    if (!out) return fail(ISE_E_INVALID, "output pointer is NULL");
-    *out = nullptr;
-    if (nq < 0 || (nq > 0 && !q)) return fail(ISE_E_INVALID, "bad query argument");
-    ise_range_result* r = new (std::nothrow) ise_range_result;
-    if (!r) return fail(ISE_E_NOMEM, "range result");
-    try {
-        r->lims.reserve((size_t)nq + 1);
-        r->lims.push_back(0);
-        if (nq > 0 && h->n > 0) {
-            DeviceGuard gd(h->device);
-            ise_index::HostCtx* c = acquire_ctx(h);
-            struct Rel { ise_index* h; ise_index::HostCtx* c; ~Rel() { release_ctx(h, c); } } rel{h, c};
-            if (!c->stream) {
-                const hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-                if (e != hipSuccess) {
-                    delete r;
-                    return fail(ISE_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-                }
-            }
-            std::lock_guard<std::mutex> lk(h->rg_mu);
-            for (long long i0 = 0; i0 < nq; i0 += RANGE_NQ_CHUNK) {
-                const long long m = std::min<long long>(RANGE_NQ_CHUNK, nq - i0);
-                const int rc = range_batch(h, c->stream, q + (size_t)i0 * h->d, m, radius, sel, r);
-                if (rc) {
-                    delete r;
-                    return rc;
-                }
-            }
-        }
-        r->lims.resize((size_t)nq + 1, r->lims.back());  // an empty index: every list is empty
-    } catch (const std::bad_alloc&) {
-        delete r;
-        return fail(ISE_E_NOMEM, "range result: host allocation failed");
-    }
-    *out = r;
-    return ISE_OK;
-}
-
-extern "C" int ise_index_range_search_host(ise_index_t* h, const float* q, int64_t nq, float radius,
-                                           ise_range_result_t** out) {
-    return range_search_host(h, q, nq, radius, nullptr, out);
-}
-
-extern "C" int ise_index_range_search_sel_host(ise_index_t* h, const float* q, int64_t nq, float radius,
-                                               const ise_selector_t* sel, ise_range_result_t** out) {
-    if (out) *out = nullptr;
-    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
-    if (!sel) return fail(ISE_E_INVALID, "selector is NULL");
-    {
-        std::lock_guard<std::mutex> lk(h->mu_);
-        const int rc = selector_check_locked(h, sel);  // also when the index is empty or nq == 0
-        if (rc) return rc;
-    }
-    return range_search_host(h, q, nq, radius, sel, out);
-}
-
-extern "C" int ise_range_result_get(const ise_range_result_t* r, int64_t* nq, const int64_t** lims, const float** D,
-                                    const int64_t** I) {
-    if (!r) return fail(ISE_E_INVALID, "result is NULL");
-    if (nq) *nq = (int64_t)r->lims.size() - 1;
-    if (lims) *lims = r->lims.data();
-    if (D) *D = r->D.data();
-    if (I) *I = r->I.data();
-    return ISE_OK;
-}
-
-extern "C" int ise_range_result_destroy(ise_range_result_t* r) {
-    delete r;
-    return ISE_OK;
-}
-
-// ---- selector objects and the selector-filtered search (ise_sel_scan.hpp)
-#define SEL_NQ_CHUNK 64 /* queries per masked launch (4 groups of 16): bounds the per-block lists of a slot */
-
-// a new selector for h as it stands (mu_ held): ceil(n / 32) words and a word of padding, so that the half-word of
-// every tile below the capacity's last one is there to read, zero
-static SelectorFor selector_for(const ise_index* h) {
-    return SelectorFor{h, h->device, h->n, h->row_epoch, h->stream, (h->n + 31) / 32 + 1};
-}
-static void selector_census_launch(SelectorBase* s, hipStream_t st, unsigned long long* out4) {
-    hipLaunchKernelGGL(sel_census_kernel, dim3((unsigned)((s->nwords + 255) / 256)), dim3(256), 0, st, s->bits, s->nwords,
-                       s->ntotal, out4);
-}
-
-extern "C" int ise_selector_create_range(ise_index_t* h, int64_t i0, int64_t i1, ise_selector_t** out) {
-    if (!out) return fail(ISE_E_INVALID, "output pointer is NULL");
-    *out = nullptr;
-    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
-    std::lock_guard<std::mutex> lk(h->mu_);
-    DeviceGuard gd(h->device);
-    const long long a = std::max<long long>(i0, 0), b = std::min<long long>(i1, h->n);
-    return selector_create(selector_for(h), [&](SelectorBase* s) { return selector_fill_range(s, h->stream, a, b); },
-                           selector_census_launch, out);
-}
-
-extern "C" int ise_selector_create_ids(ise_index_t* h, const int64_t* ids, int64_t n_ids, int invert, ise_selector_t** out) {
-    if (!out) return fail(ISE_E_INVALID, "output pointer is NULL");
-    *out = nullptr;
-    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(ISE_E_INVALID, "ids is NULL");
-    std::lock_guard<std::mutex> lk(h->mu_);
-    DeviceGuard gd(h->device);
-    DevFree ids_dev;
-    return selector_create(selector_for(h),
-                           [&](SelectorBase* s) { return selector_scatter_ids(s, h->stream, ids, n_ids, invert, &ids_dev); },
-                           selector_census_launch, out);
-}
-
-extern "C" int ise_selector_create_bitmap(ise_index_t* h, const uint32_t* words, int64_t n_words, ise_selector_t** out) {
-    if (!out) return fail(ISE_E_INVALID, "output pointer is NULL");
-    *out = nullptr;
-    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
-    if (n_words < 0 || (n_words > 0 && !words)) return fail(ISE_E_INVALID, "words is NULL");
-    std::lock_guard<std::mutex> lk(h->mu_);
-    if (n_words != (h->n + 31) / 32)
-        return fail(ISE_E_INVALID, "the bitmap must have ceil(ntotal / 32) = " + std::to_string((h->n + 31) / 32) + " words");
-    DeviceGuard gd(h->device);
-    return selector_create(selector_for(h), [&](SelectorBase* s) { return selector_copy_bitmap(s, h->stream, words, n_words); },
-                           selector_census_launch, out);  // the census clears the bits at or beyond ntotal
-}
-
-extern "C" int ise_selector_info(const ise_selector_t* sel, int64_t* out5) { return selector_info(sel, out5); }
-
-extern "C" int ise_selector_destroy(ise_selector_t* sel) {
-    if (sel) selector_free(sel);  // waits for the device: a masked pass still in flight has finished reading the bitmap
-    return ISE_OK;
-}
-
-// one chunk of m <= SEL_NQ_CHUNK queries (mu_ held, the selector checked, the shift prepared): pad the queries, then
-// per 32 results one masked pass + the merge of its per-block lists
-static int sel_chunk_enqueue(ise_index* h, ise_index::SelSlot* sl, const ise_selector* sel, const float* q_dev, long long m,
-                             int k, float* D_dev, long long* I_dev, hipStream_t st) {
-    SelScanParams sp{};
-    sp.xb = h->xb; sp.norms = h->norms; sp.mu = h->mu; sp.bits = sel->bits;
-    sp.n = h->n; sp.d = h->d; sp.dp = h->dp;
-    sp.qs_stride = qs_stride_for(h);
-    sp.row_slots = (int)(row_bytes(h) / 16);
-    sp.nq = (int)m; sp.metric = h->metric;
-    sp.beta = uses_shift(h) ? exact_beta(h) : 0.f;
-    int rc = range_staging(h, sp.qs_stride, &sp.tpr, &sp.vec_q);
-    if (rc) return rc;
-    const int ch = std::min(chunk_steps(h), 4);
-    // the grid comes from the window's tiles, not from the index: at least a tile per wave, at most two blocks per CU
-    // (what their LDS lets a CU hold) and the merge's list count
-    sp.tile0 = (int)(sel->r0 / 16);
-    sp.tile1 = (int)((sel->r1 + 15) / 16);
-    const int span = sp.tile1 - sp.tile0;
-    int nb = std::max(1, std::min({(span + SEL_W - 1) / SEL_W, 2 * h->num_cu, MERGE_LISTS_MAX}));
-    sp.tiles_per_block = (span + nb - 1) / nb;
-    nb = (span + sp.tiles_per_block - 1) / sp.tiles_per_block;
-    const int groups = (int)((m + 15) / 16);
-    // results per pass: XPASS_MAX, or what the wave lists' LDS holds beside long query rows (d = 2048: 19)
-    static_assert(XPASS_MAX == SEL_KPASS_MAX, "one masked pass yields what one exact pass yields");
-    const long long lds_left = (long long)LDS_LIMIT - (long long)range_lds_bytes(sp.qs_stride);
-    const int kp = (int)std::min<long long>(std::min(k, XPASS_MAX), lds_left / (SEL_W * 16 * 8));
-    if (kp < 1) return fail(ISE_E_INVALID, "rows too long for the selector-filtered search");
-    rc = range_grow(sl->q, (size_t)m * h->dp);
-    if (!rc) rc = range_grow(sl->part, (size_t)groups * nb * 16 * kp);
-    if (!rc && k > kp) rc = range_grow(sl->keys, (size_t)m * kp + (size_t)m);
-    if (rc) return rc;
-    const long long qtot = m * h->dp;
-    hipLaunchKernelGGL(sel_pad_queries_kernel, dim3((unsigned)((qtot + 255) / 256)), dim3(256), 0, st, q_dev, h->d, h->dp,
-                       qtot, sl->q.p);
-    sp.q = sl->q.p;
-    sp.part = sl->part.p;
-    sp.kpass = kp;
-    MergeParams mp{};
-    mp.lists = sl->part.p; mp.qt = 16; mp.n_lists = nb; mp.nq = (int)m; mp.k = kp; mp.metric = h->metric;
-    mp.stride_list = 16ll * kp; mp.stride_qtile = (long long)nb * 16 * kp;
-    const ExactParams xp{};
-    const dim3 grid((unsigned)nb, (unsigned)groups);
-    const size_t lds = sel_lds_bytes(sp.qs_stride, kp);
-    const int bf16 = h->storage == ISE_STORE_BF16, shift = uses_shift(h);
-    if (k <= kp) {
-        sp.floor_keys = nullptr;
-        ise_launch_sel_scan(bf16, shift, ch, grid, lds, st, sp);
-        mp.D = D_dev; mp.I = I_dev;
-        launch_merge<false>((unsigned)m, 0, st, mp, xp);
-        h->sel_passes++;
-    } else {
-        u64* pass_keys = sl->keys.p;
-        u64* floors = pass_keys + (size_t)m * kp;
-        for (int off = 0; off < k; off += kp) {
-            sp.floor_keys = off ? floors : nullptr;
-            ise_launch_sel_scan(bf16, shift, ch, grid, lds, st, sp);
-            mp.keys_out = pass_keys;
-            launch_merge<false>((unsigned)m, 0, st, mp, xp);
-            const long long tot = m * kp;
-            hipLaunchKernelGGL(sel_scatter_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st,
-                               (const u64*)pass_keys, (int)m, kp, off, k, h->metric, D_dev, I_dev, floors);
-            h->sel_passes++;
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return ISE_OK;
-}
-
-// mu_ held.  Enqueues only
-static int search_sel_enqueue(ise_index* h, const ise_selector* sel, const float* q_dev, long long nq, int k, float* D_dev,
-                              long long* I_dev, hipStream_t st) {
-    int rc = selector_check_locked(h, sel);
-    if (rc) return rc;
-    h->sel_batches++;
-    if (sel->count == 0) {  // an empty window: padding, no pass
-        const long long tot = nq * k;
-        hipLaunchKernelGGL(sel_fill_pad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, tot,
-                           h->metric);
-        HIP_TRY(hipGetLastError());
-        return ISE_OK;
-    }
-    rc = prepare_shift_locked(h, st);
-    if (rc) return rc;
-    ise_index::SelSlot* sl = nullptr;
-    bool waited = false;
-    if ((rc = take_slot(h->ss, &h->ss_next, st, &sl, &waited))) return rc;
-    if (!sl->done) HIP_TRY(hipEventCreateWithFlags(&sl->done, hipEventDisableTiming));  // a slot never used: nothing was waited for
-    // its buffers may grow (free + allocate) below: the other stream's passes have to be through with them
-    if (waited) HIP_TRY(hipEventSynchronize(sl->done));
-    SlotRelease<ise_index::SelSlot> release{sl, st};
-    for (long long i0 = 0; i0 < nq; i0 += SEL_NQ_CHUNK) {
-        const long long m = std::min<long long>(SEL_NQ_CHUNK, nq - i0);
-        rc = sel_chunk_enqueue(h, sl, sel, q_dev + (size_t)i0 * h->d, m, k, D_dev + (size_t)i0 * k, I_dev + (size_t)i0 * k, st);
-        if (rc) return rc;
-    }
-    return ISE_OK;
-}
-
-extern "C" int ise_index_search_sel_device(ise_index_t* h, const float* q_dev, int64_t nq, int k, const ise_selector_t* sel,
-                                           float* D_dev, int64_t* I_dev, void* stream) {
-    int rc = check_search_args(h, q_dev, nq, k);
-    if (rc) return rc;
-    if (!sel) return fail(ISE_E_INVALID, "selector is NULL");
-    if (nq > 0 && (!D_dev || !I_dev)) return fail(ISE_E_INVALID, "output pointer is NULL");
-    std::lock_guard<std::mutex> lk(h->mu_);
-    if (nq == 0) return selector_check_locked(h, sel);
-    DeviceGuard gd(h->device);
-    return search_sel_enqueue(h, sel, q_dev, nq, k, D_dev, (long long*)I_dev, (hipStream_t)stream);
-}
-
-// blocks; on one of the host contexts, never through the request combiner: a filtered call is not merged with others
-extern "C" int ise_index_search_sel_host(ise_index_t* h, const float* q, int64_t nq, int k, const ise_selector_t* sel,
-                                         float* D, int64_t* I) {
-    int rc = check_search_args(h, q, nq, k);
-    if (rc) return rc;
-    if (!sel) return fail(ISE_E_INVALID, "selector is NULL");
-    if (nq > 0 && (!D || !I)) return fail(ISE_E_INVALID, "output pointer is NULL");
-    if (nq == 0) {
-        std::lock_guard<std::mutex> lk(h->mu_);
-        return selector_check_locked(h, sel);
-    }
-    return search_host_staged(h, q, nq, k, 1024, D, (long long*)I, [&](ise_index::HostCtx* c, long long m) {
-        return search_sel_enqueue(h, sel, c->q_dev, m, k, c->D_dev, c->I_dev, c->stream);
-    });
-}
-
-extern "C" int ise_index_sel_stats(ise_index_t* h, uint64_t* out3) {
-    if (!h || !out3) return fail(ISE_E_INVALID, "NULL argument");
-    {
-        std::lock_guard<std::mutex> lk(h->mu_);
-        out3[0] = h->sel_batches;
-        out3[1] = h->sel_passes;
-    }
-    std::lock_guard<std::mutex> lk(h->rg_mu);
-    out3[2] = h->sel_range_batches;
-    return ISE_OK;
-}
-
-// ---- subset scoring (ise_subset.hpp): exact scores of per-query candidate lists, and their k best
-#define SUBSET_NQ_CHUNK 4096 /* queries per pair of launches (grid.y) and per staging round of the host forms */
-
-// rule: device-wide drain before a free (work in flight on any stream may still use the handle's ONE set)
-template <class T>
-static int subset_grow(DevBuf<T>& b, size_t need) {
-    if (b.p && need <= b.n) return ISE_OK;
-    if (b.p) {
-        HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(b.p);
-    }
-    b.p = nullptr;
-    b.n = 0;
-    const size_t want = std::max<size_t>(need, 16);
-    HIP_TRY(hipMalloc((void**)&b.p, want * sizeof(T)));
-    b.n = want;
-    return ISE_OK;
-}
-
-static int check_subset_args(const ise_index* h, const void* q, long long nq, const void* cand, int kc) {
-    if (!h) return fail(ISE_E_INVALID, "handle is NULL");
-    if (h->storage != ISE_STORE_F32) return fail(ISE_E_INVALID, "subset scoring needs float32 rows (this index keeps bf16)");
-    if (nq < 0 || nq > (1ll << 20)) return fail(ISE_E_INVALID, "nq must be in [0, 2^20]");
-    if (kc < 1 || kc > ISE_MAX_K) return fail(ISE_E_INVALID, "kc (candidates per query) must be in [1, 2048]");
-    if (nq > 0 && (!q || !cand)) return fail(ISE_E_INVALID, "query or candidate pointer is NULL");
-    return ISE_OK;
-}
-
-// mu_ held.  Enqueues only (it waits on the host only where the key workspace has to grow, and once for the counter's
-// allocation).  D_dev / I_dev ([nq][k]) and / or dist_dev ([nq][kc])
-static int subset_enqueue(ise_index* h, const float* q_dev, long long nq, int k, const long long* cand_dev, int kc,
-                          float* D_dev, long long* I_dev, float* dist_dev, hipStream_t st) {
-    auto& sb = h->sub;
-    const int ip = h->metric == ISE_METRIC_INNER_PRODUCT;
-    if (!sb.last) HIP_TRY(hipEventCreateWithFlags(&sb.last, hipEventDisableTiming));
-    if (sb.last_valid && sb.last_stream != st) HIP_TRY(hipStreamWaitEvent(st, sb.last, 0));
-    if (h->n == 0) {  // nothing to score: padding, no score launch
-        sb.batches++;
-        if (D_dev) {
-            const long long tot = nq * k;
-            hipLaunchKernelGGL(sel_fill_pad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, tot,
-                               h->metric);
-        }
-        if (dist_dev) {
-            const long long tot = nq * kc;
-            hipLaunchKernelGGL(subset_fill_dist_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, dist_dev, tot, ip);
-        }
-    } else {
-        const int n2 = rerank_pow2(kc);
-        const long long chunk = std::min<long long>(nq, SUBSET_NQ_CHUNK);
-        int rc = D_dev ? subset_grow(sb.keys, (size_t)chunk * n2) : ISE_OK;
-        if (rc) return rc;
-        if (!sb.valid) {
-            HIP_TRY(hipMalloc((void**)&sb.valid, sizeof(unsigned long long)));
-            // on the call's stream: a plain hipMemset of device memory may return before it has run, and this stream
-            // does not wait for the null stream
-            HIP_TRY(hipMemsetAsync(sb.valid, 0, sizeof(unsigned long long), st));
-        }
-        sb.batches++;  // counted once the batch is certain to be enqueued
-        SubsetParams sp{};
-        sp.xb = static_cast<const float*>(h->xb);
-        sp.n = h->n; sp.d = h->d; sp.dp = h->dp; sp.kc = kc; sp.n2 = n2; sp.ip = ip;
-        sp.valid = sb.valid;
-        const unsigned gx = (unsigned)((n2 + SUB_CPB - 1) / SUB_CPB);
-        const size_t lds = (size_t)h->dp * sizeof(float);  // at most 8 KiB + padding for d <= 2048; far below the default limit
-        const int sort_threads = std::min(SUB_SORT_MAX_THREADS, std::max(64, n2 / 2));
-        for (long long i0 = 0; i0 < nq; i0 += SUBSET_NQ_CHUNK) {
-            const long long m = std::min<long long>(SUBSET_NQ_CHUNK, nq - i0);
-            sp.q = q_dev + (size_t)i0 * h->d;
-            sp.cand = cand_dev + (size_t)i0 * kc;
-            sp.keys = D_dev ? sb.keys.p : nullptr;
-            sp.dist = dist_dev ? dist_dev + (size_t)i0 * kc : nullptr;
-            const dim3 grid(gx, (unsigned)m);
-            if (ip) hipLaunchKernelGGL(subset_score_ip_kernel, grid, dim3(64), lds, st, sp);
-            else hipLaunchKernelGGL(subset_score_l2_kernel, grid, dim3(SUB_W * 64), lds, st, sp);
-            sb.launches++;
-            if (D_dev)
-                hipLaunchKernelGGL(subset_select_kernel, dim3((unsigned)m), dim3(sort_threads), subset_select_lds_bytes(n2), st,
-                                   (const u64*)sb.keys.p, n2, k, ip, D_dev + (size_t)i0 * k, I_dev + (size_t)i0 * k);
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sb.last, st));
-    sb.last_stream = st;
-    sb.last_valid = true;
-    return ISE_OK;
-}
-
-extern "C" int ise_index_search_subset_device(ise_index_t* h, const float* q_dev, int64_t nq, int k, const int64_t* cand_dev,
-                                              int kc, float* D_dev, int64_t* I_dev, void* stream) {
-    int rc = check_subset_args(h, q_dev, nq, cand_dev, kc);
-    if (rc) return rc;
-    if (k < 1 || k > ISE_MAX_K) return fail(ISE_E_INVALID, "k must be in [1, 2048]");
-    if (nq > 0 && (!D_dev || !I_dev)) return fail(ISE_E_INVALID, "output pointer is NULL");
-    if (nq == 0) return ISE_OK;
-    std::lock_guard<std::mutex> lk(h->mu_);
-    DeviceGuard gd(h->device);
-    return subset_enqueue(h, q_dev, nq, k, (const long long*)cand_dev, kc, D_dev, (long long*)I_dev, nullptr,
-                          (hipStream_t)stream);
-}
-
-extern "C" int ise_index_distance_subset_device(ise_index_t* h, const float* q_dev, int64_t nq, const int64_t* cand_dev, int kc,
-                                                float* dist_dev, void* stream) {
-    int rc = check_subset_args(h, q_dev, nq, cand_dev, kc);
-    if (rc) return rc;
-    if (nq > 0 && !dist_dev) return fail(ISE_E_INVALID, "output pointer is NULL");
-    if (nq == 0) return ISE_OK;
-    std::lock_guard<std::mutex> lk(h->mu_);
-    DeviceGuard gd(h->device);
-    return subset_enqueue(h, q_dev, nq, 0, (const long long*)cand_dev, kc, nullptr, nullptr, dist_dev, (hipStream_t)stream);
-}
-
-// the host forms: SUBSET_NQ_CHUNK queries at a time are copied in, enqueued under mu_, copied out and waited for.
-// k == 0: the scores (dist [nq][kc]); else D / I [nq][k]
-static int subset_host(ise_index* h, const float* q, long long nq, int k, const long long* cand, int kc, float* D,
-                       long long* I, float* dist) {
-    std::lock_guard<std::mutex> lk(h->sub.mu);
-    DeviceGuard gd(h->device);
-    auto& sb = h->sub;
-    hipStream_t st = h->stream;
-    const long long batch = std::min<long long>(nq, SUBSET_NQ_CHUNK);
-    const int width = dist ? kc : k;
-    int rc = subset_grow(sb.q, (size_t)batch * h->d);
-    if (!rc) rc = subset_grow(sb.cand, (size_t)batch * kc);
-    if (!rc) rc = subset_grow(sb.out, (size_t)batch * width);
-    if (!rc && !dist) rc = subset_grow(sb.I, (size_t)batch * k);
-    if (rc) return rc;
-    for (long long i0 = 0; i0 < nq; i0 += batch) {
-        const long long m = std::min<long long>(batch, nq - i0);
-        HIP_TRY(hipMemcpyAsync(sb.q.p, q + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(sb.cand.p, cand + (size_t)i0 * kc, (size_t)m * kc * sizeof(long long), hipMemcpyHostToDevice, st));
-        {
-            std::lock_guard<std::mutex> lk2(h->mu_);
-            rc = subset_enqueue(h, sb.q.p, m, k, sb.cand.p, kc, dist ? nullptr : sb.out.p, dist ? nullptr : sb.I.p,
-                                dist ? sb.out.p : nullptr, st);
-        }
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync((dist ? dist : D) + (size_t)i0 * width, sb.out.p, (size_t)m * width * sizeof(float),
-                               hipMemcpyDeviceToHost, st));
-        if (!dist)
-            HIP_TRY(hipMemcpyAsync(I + (size_t)i0 * k, sb.I.p, (size_t)m * k * sizeof(long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return ISE_OK;
-}
-
-extern "C" int ise_index_search_subset_host(ise_index_t* h, const float* q, int64_t nq, int k, const int64_t* cand, int kc,
-                                            float* D, int64_t* I) {
-    int rc = check_subset_args(h, q, nq, cand, kc);
-    if (rc) return rc;
-    if (k < 1 || k > ISE_MAX_K) return fail(ISE_E_INVALID, "k must be in [1, 2048]");
-    if (nq > 0 && (!D || !I)) return fail(ISE_E_INVALID, "output pointer is NULL");
-    if (nq == 0) return ISE_OK;
-    return subset_host(h, q, nq, k, (const long long*)cand, kc, D, (long long*)I, nullptr);
-}
-
-extern "C" int ise_index_distance_subset_host(ise_index_t* h, const float* q, int64_t nq, const int64_t* cand, int kc,
-                                              float* dist) {
-    int rc = check_subset_args(h, q, nq, cand, kc);
-    if (rc) return rc;
-    if (nq > 0 && !dist) return fail(ISE_E_INVALID, "output pointer is NULL");
-    if (nq == 0) return ISE_OK;
-    return subset_host(h, q, nq, 0, (const long long*)cand, kc, nullptr, nullptr, dist);
-}
-
-extern "C" int ise_index_subset_stats(ise_index_t* h, uint64_t* out3) {
-    if (!h || !out3) return fail(ISE_E_INVALID, "NULL argument");
-    std::lock_guard<std::mutex> lk(h->mu_);
-    out3[0] = h->sub.batches;
-    out3[1] = h->sub.launches;
-    out3[2] = 0;
-    if (h->sub.valid) {  // counted on the device: wait for the passes in flight
-        DeviceGuard gd(h->device);
-        HIP_TRY(hipDeviceSynchronize());
-        unsigned long long v = 0;
-        HIP_TRY(hipMemcpy(&v, h->sub.valid, sizeof(v), hipMemcpyDeviceToHost));
-        out3[2] = v;
-    }
-    return ISE_OK;
-}
-
 // ---- remove_ids: stable in-place compaction (ise_remove.hpp)
 // everything a removal allocates for the duration of the call
 struct RemoveScratch {
@@ -2912,14 +1849,6 @@ extern "C" int ise_index_remove_last_timing(ise_index_t* h, float* ms, uint64_t*
     std::lock_guard<std::mutex> lk(h->mu_);
     *ms = h->remove_last_ms;
     *bytes = h->remove_last_bytes;
-    return ISE_OK;
-}
-
-extern "C" int ise_index_range_stats(ise_index_t* h, uint64_t* out2) {
-    if (!h || !out2) return fail(ISE_E_INVALID, "NULL argument");
-    std::lock_guard<std::mutex> lk(h->rg_mu);
-    out2[0] = h->range_batches;
-    out2[1] = h->range_overflows;
     return ISE_OK;
 }
 

@@ -1,4 +1,4 @@
-// ise_selector.hpp -- the selector object of the float and the binary index (ise_knn.hip, ise_binary_scan.hip): a
+// ise_selector.hpp -- the selector object of the float and the binary index (ise_flat_sel.hip, ise_binary_scan.hip): a
 // device bitmap over the rows of ONE index at ONE (ntotal, row epoch), with its census.  Host code only; the fill and
 // scatter kernels are those of ise_sel_scan.hpp, the census kernel is the index kind's own (the word layouts differ)
 // and comes in as the launch `census(s, stream, out4)`.  The index's lock is held by every caller that names an index.
@@ -15,6 +15,10 @@ struct SelectorBase {
     unsigned long long epoch = 0;
     long long count = 0, r0 = 0, r1 = 0, tiles = 0;  // selected rows, window [r0, r1), non-empty tiles
 };
+
+// the float index's (ise_flat_range.hip, ise_flat_sel.hip).  bits: ceil(ntotal / 32) words + zero padding (pad rows of
+// the last tile and word: zero bits)
+struct ise_selector : SelectorBase {};
 
 // the index a selector is made for, as it stands
 struct SelectorFor {

@@ -122,7 +122,7 @@ def lower_bounds(xb: np.ndarray, xq: np.ndarray, mu: np.ndarray) -> np.ndarray:
 
 
 def float32_filter_bounds(xb: np.ndarray, xq: np.ndarray, mu: np.ndarray) -> np.ndarray:
-    """The float32 filter's key for comparison (ise_common.hpp l2_lower_bound, beta of ise_knn.hip exact_beta), in
+    """The float32 filter's key for comparison (ise_common.hpp l2_lower_bound, beta of ise_flat.hpp exact_beta), in
     float64: |x-mu|^2 + |y-mu|^2 - 2 (x-mu).(y-mu) - beta (|x-mu|^2 + |y-mu|^2)."""
     beta = (0.5625 * dp_for(xb.shape[1]) + 256.0) * U * 1.02
     a = xb.astype(np.float64) - np.asarray(mu, np.float32).astype(np.float64)

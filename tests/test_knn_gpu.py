@@ -438,6 +438,40 @@ def test_host_search_of_more_than_one_staging_batch(faiss):
     assert_knn_identical(D, I, *ko.knn_exact(xb, xq, 5, L2), "nq=4100")
 
 
+def test_host_contexts_that_grow(faiss):
+    """A host search above the request combiner's 16 queries stages through one of four host contexts, whose device
+    buffers grow with the call: four threads, each with 20 queries at k = 5, then 300 at k = 40, then 20 at k = 5 again.
+    All twelve results have the bits of a single-threaded run."""
+    rng = np.random.default_rng(900)
+    n, d = 900, 20
+    xb = int_data("small", rng, n, d)
+    index = faiss.IndexFlatL2(d)
+    index.add(xb)
+    calls = [(20, 5), (300, 40), (20, 5)]
+    qs = [[int_data("small", rng, nq, d) for nq, _ in calls] for _ in range(4)]
+    for xq in (q for per_thread in qs for q in per_thread):
+        assert_exact_range(xb, xq)
+    out = [[None] * len(calls) for _ in range(4)]
+    errs = []
+    gate = threading.Barrier(4)
+
+    def work(t):
+        try:
+            gate.wait()
+            for j, (_, k) in enumerate(calls):
+                out[t][j] = index.search(qs[t][j], k)
+        except Exception as e:  # noqa: BLE001
+            errs.append(e)
+
+    th = [threading.Thread(target=work, args=(t,)) for t in range(4)]
+    [t.start() for t in th]
+    [t.join() for t in th]
+    assert not errs, errs
+    for t in range(4):
+        for j, (nq, k) in enumerate(calls):
+            assert_knn_identical(*out[t][j], *index.search(qs[t][j], k), f"thread {t} call {j}: nq={nq} k={k}")
+
+
 @pytest.mark.parametrize("nq,k", [(40, 100), (20, 33), (50, 70)])
 def test_large_k_with_several_query_tiles(faiss, nq, k):
     """k > 32 (floor-keyed passes) combined with 2 and 3 query tiles per pass."""

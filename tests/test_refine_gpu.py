@@ -182,6 +182,41 @@ def test_errors_stats_and_the_empty_index():
         assert empty.subset_stats() == {"subset_batches": 2, "score_launches": 0, "rows_scored": 0}
 
 
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_one_handle_from_two_streams(metric):
+    """Subset scoring keeps ONE key workspace per handle: a call on another stream than the previous call's waits for
+    it through an event, and a workspace that has to grow (here from 3 x 8 to 17 x 64 keys) is replaced behind a drain.
+    Four calls on two streams with nothing waited for in between; every result has the bits of the host form."""
+    import torch
+
+    rng = np.random.default_rng(300)
+    n, d = 300, 20
+    xb = int_data("small", rng, n, d)
+    index = flat_index(xb, metric)
+    dev = torch.device("cuda", index.device)
+    shapes = {"small": (3, 5, 5), "large": (17, 37, 10)}
+    host, cuda = {}, {}
+    for name, (nq, kc, _) in shapes.items():
+        host[name] = (int_data("small", rng, nq, d), candidate_table(rng, n, nq, kc))
+        assert_exact_range(xb, host[name][0])
+        cuda[name] = tuple(torch.from_numpy(a).to(dev) for a in host[name])
+    torch.cuda.synchronize(dev)  # the inputs are there: from here on no stream waits for another through torch
+    side = torch.cuda.Stream(device=dev)
+    first = index.search_subset_torch(cuda["small"][0], shapes["small"][2], cuda["small"][1])
+    with torch.cuda.stream(side):
+        grown = index.search_subset_torch(cuda["large"][0], shapes["large"][2], cuda["large"][1])
+        dist = index.compute_distance_subset_torch(*cuda["large"])
+    again = index.search_subset_torch(cuda["small"][0], shapes["small"][2], cuda["small"][1])
+    torch.cuda.synchronize(dev)
+    assert index.subset_stats()["subset_batches"] == 4
+    want_small = index.search_subset(host["small"][0], shapes["small"][2], host["small"][1])
+    want_large = index.search_subset(host["large"][0], shapes["large"][2], host["large"][1])
+    for got, want, what in ((first, want_small, "default stream"), (grown, want_large, "side stream"),
+                            (again, want_small, "default stream again")):
+        assert_knn_identical(got[0].cpu().numpy(), got[1].cpu().numpy(), *want, what)
+    assert np.array_equal(dist.cpu().numpy().view(np.uint32), index.compute_distance_subset(*host["large"]).view(np.uint32))
+
+
 # ------------------------------------------------------------------ IndexRefineFlat
 def refine_over_pq(n, metric, seed, nq=9):
     rng = np.random.default_rng(seed)

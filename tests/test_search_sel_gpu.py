@@ -305,6 +305,35 @@ def test_device_selector_lifetime():
         idx.search(xq, 4000, params=P(sel))  # k out of range
 
 
+def test_five_streams_share_four_slots():
+    """The masked pass has four workspace slots: a stream keeps its slot, and the fifth stream takes the least recently
+    taken one behind its event and grows it.  Five streams, growing batches (the last two need two passes and so the
+    keys buffer), the first stream once more, nothing waited for in between; every result has the bits of the host
+    search with the same selector."""
+    import torch
+
+    rng = np.random.default_rng(900)
+    n, d = 900, 20
+    xb = int_data("small", rng, n, d)
+    idx = make_index(xb, L2, "f32")
+    ds = idx.make_selector(faiss.IDSelectorRange(5, 777))  # cuts a tile at both ends
+    dev = torch.device("cuda", idx.device)
+    pairs = [(2, 3), (5, 10), (9, 10), (17, 33), (40, 40)]
+    xqs = [int_data("small", rng, nq, d) for nq, _ in pairs]
+    for xq in xqs:
+        assert_exact_range(xb, xq)
+    xts = [torch.from_numpy(xq).to(dev) for xq in xqs]
+    torch.cuda.synchronize(dev)  # the inputs are there: no stream waits for another through torch
+    streams = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(device=dev) for _ in range(4)]
+    got = []
+    for st, xt, (_, k) in zip(streams + streams[:1], xts + xts[:1], pairs + pairs[:1]):
+        with torch.cuda.stream(st):
+            got.append(idx.search_torch(xt, k, params=P(ds)))
+    torch.cuda.synchronize(dev)
+    for j, ((Dt, It), xq, (nq, k)) in enumerate(zip(got, xqs + xqs[:1], pairs + pairs[:1])):
+        assert_knn_identical(Dt.cpu().numpy(), It.cpu().numpy(), *idx.search(xq, k, params=P(ds)), f"call {j}: nq={nq} k={k}")
+
+
 def test_host_search_of_more_than_one_staging_batch():
     """A filtered host search stages 1024 queries at a time through its context's device buffers: 1030 queries are two
     batches, and the second one's queries and results sit at an offset in the caller's arrays.  Integer data, so the
