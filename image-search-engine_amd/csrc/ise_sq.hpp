@@ -19,7 +19,12 @@
 // mfma_f32_16x16x32_f16.  A centred code byte is exact in fp16 (1024 + c by a byte permute into 0x64cc, one packed
 // subtract of 1152); the weights are staged in LDS, scaled by the query's own power of two 2^sh (max |w| 2^sh in
 // [2^14, 2^15)), as fp16 hi + lo limbs w~ (22 bits of a weight); hi and lo feed two float32 accumulator chains.
-// Centring keeps what the float32 accumulators hold at the size of the score itself; the large terms that cancel --
+// Centring halves what the float32 accumulators hold: partial sums of w_j c'_j, up to 128 sum_j |w_j|.  Where a query
+// sits near the middle of the trained range the w_j change sign and that is the size of the score itself; where rows and
+// queries sit together near one end of a range that an outlier stretched, w_j and c'_j keep one sign over all j and
+// the accumulators hold orders of magnitude more than an L2 distance -- its error is bounded by 128 sum_j |w_j|
+// (2^-22 of the limbs, 2^-24 per accumulation), not by the score (DESIGN.md 4.15 has the bound and what was measured).
+// The large terms that cancel outside the sum --
 // the bracket (per query, of the limbs w~ themselves, so the identity is exact; sq_stage_kernel builds it and the limb
 // images once per call, the scan's blocks copy them in), R_i and the assembly -- are float64,
 // and the result is rounded to float32 once.  On integer data every term is an integer and the result exact.

@@ -2257,8 +2257,10 @@ class IndexScalarQuantizer(_IndexHandle):
     and ``QT_8bit_uniform`` (one of each for all): every row is kept as ``d`` bytes, byte j =
     ``min(255, max(0, floor((x_j - vmin_j) / s_j)))`` with the step ``s_j = vdiff_j / 255`` (0 where the step is 0), all in
     float32 and for both metrics; it decodes to ``fmaf(c_j + 0.5, s_j, vmin_j)``.  ``search`` scores the query against
-    the DECODED row (``reconstruct_n``): D is their squared L2 distance or inner product in float32, within
-    ``1e-4 * max(1, |D|)`` of the float64 value and exact on integer data; L2 ascending, inner product descending, ties
+    the DECODED row (``reconstruct_n``): D is their squared L2 distance or inner product in float32, exact on integer
+    data and within ``1e-4 * max(1, |D|)`` of the float64 value where the data fill their trained range (min/max
+    training on the added rows, no outlier that stretches it; otherwise the error is bounded by the weights' sum, not
+    by D: include/ise_knn.h); L2 ascending, inner product descending, ties
     by ascending id, unfilled slots -1 / +-FLT_MAX; a query with a NaN or inf entry gets padding only.
 
     On the device (include/ise_knn.h, ise_sq_*).  Not provided (they raise ``NotImplementedError``):

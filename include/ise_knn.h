@@ -524,7 +524,17 @@ int ise_pq_stats(ise_pq_t* h, uint64_t* out4);
  *   codes /       rows [i0, i0 + n) as row-major n x d bytes / decoded n x d floats (the device keeps a row's d bytes
  *   reconstruct   in a stride of d rounded up to 64, and one float64 row term beside it)
  *   search        the squared L2 distance / inner product of the query and the DECODED row in float32, expanded about
- *                 o_j = vmin_j + s_j / 2 with float64 outer terms (csrc/ise_sq.hpp): within 1e-4 max(1, |score|) of the float64 value, exact
+ *                 o_j = vmin_j + s_j / 2 with float64 outer terms (csrc/ise_sq.hpp).  The float32 accumulators hold
+ *                 sums of size 128 W, W = sum_j |s_j (x_j - o_j)| (L2) or sum_j |s_j x_j| (inner product), so the
+ *                 error against the float64 score over the decoded rows is bounded in terms of W, not of the score:
+ *                 at most 128 W (3 * 2^-22 + 2 ceil(d / 64) 2^-24 (1 + 2^-9)) for the inner product and twice that
+ *                 for L2, plus float32's rounding of the result, of x_j - o_j and of o_j (DESIGN.md 4.15 derives
+ *                 every term; tests/sq_ref.py, score_bound).  That is within 1e-4 max(1, |score|) where the data
+ *                 fill their trained range, as min/max training on the added rows gives unless outliers stretch it.
+ *                 Where a training outlier stretches the range and rows and queries sit together near one end of
+ *                 it, W is orders of magnitude above an L2 distance, which then loses its digits from the second
+ *                 on (measured: 5e-2 to 1e-1 relative at d = 512 on rows N(900, 1) with one all-zero training row);
+ *                 the inner product stays below 1e-6 relative there.  Exact
  *                 where every partial sum is an exactly representable integer, an L2 score never negative, a zero
  *                 +0, and the bits of a (query, row) pair independent of nq, k and the query's place in the batch.
  *                 L2 ascending, inner product descending, ties by ascending id; a score enters only if strictly better

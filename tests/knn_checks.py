@@ -21,13 +21,15 @@ def true_scores(xb, xq, ids, metric):
 ATOL_UNIFORM = 1e-4  # north_star's absolute bound, asserted where it is attainable: uniform[0,1) data
 
 
-def assert_knn_matches(D, I, D_ref, I_ref, xb, xq, metric, gap=None, rtol=RTOL, atol=None):
+def assert_knn_matches(D, I, D_ref, I_ref, xb, xq, metric, gap=None, rtol=RTOL, atol=None, near=None):
     """Bit-exact ids wherever the float64 ranking is unambiguous; where two
     consecutive oracle ranks are closer than float32 can resolve, the returned
     row must still be a true near-tie at that rank.  Distances always within
     rtol * max(1, |D_ref|); with ``atol`` additionally within that ABSOLUTE bound
     (north_star: 1e-4 -- used on uniform[0,1) data, where |D| ~ d/6 keeps it above
-    float32 rounding)."""
+    float32 rounding).  ``near`` (a scalar or one value per query) replaces the float32 margin of a near-tie where
+    the caller has raised ``rtol`` / ``atol`` to a derived error bound e of the scores: scores within e of the
+    truth put a row at rank r whose true score lies within 2 e of the reference's at that rank."""
     assert D.dtype == np.float32 and I.dtype == np.int64
     assert D.shape == D_ref.shape and I.shape == I_ref.shape
     pad = I_ref < 0
@@ -45,8 +47,10 @@ def assert_knn_matches(D, I, D_ref, I_ref, xb, xq, metric, gap=None, rtol=RTOL, 
     if mism.any():
         ts = true_scores(xb, xq, I, metric)
         ref = D_ref.astype(np.float64)
-        near = np.abs(ts - ref) <= 2e-6 * np.maximum(1.0, np.abs(ref)) + 1e-6
-        bad = mism & ~near
+        margin = 2e-6 * np.maximum(1.0, np.abs(ref)) + 1e-6
+        if near is not None:
+            margin = np.broadcast_to(np.asarray(near, np.float64).reshape(-1, 1), ref.shape)
+        bad = mism & ~(np.abs(ts - ref) <= margin)
         assert not bad.any(), (
             f"{bad.sum()} id mismatches that are not float32 near-ties, e.g. q={np.argwhere(bad)[0]}")
         if gap is not None:

@@ -11,6 +11,7 @@ from image_search_engine_amd import faiss_compat as faiss
 from tests import ivf_ref, ivfsq_ref, sq_ref
 from tests.knn_checks import RTOL, assert_exact_range, assert_knn_identical, assert_knn_matches, int_data
 from tests.sel_ref import IP, L2, pad_value
+from tests.sq_ref import exact_top
 
 pytestmark = pytest.mark.gpu
 
@@ -316,19 +317,6 @@ def pass_blocks(tiles, d, device):
     qt = sq_ref.qt_of(d)
     lds = qt * (2 * (2 * dpad + 16) + 4 * 128 * 8 + 16)
     return max(1, min(-(-tiles // 8), max(1, sq_ref.LDS_LIMIT // lds) * cu, 1024))
-
-
-def exact_top(xb64, norms, x, ids, k, metric):
-    """The k best of rows ``ids`` for one query on integer data (float64 is exact), ties by ascending id."""
-    dots = xb64[ids] @ x if len(ids) < len(xb64) else xb64 @ x
-    s = (norms[ids] + x @ x - 2.0 * dots) if metric == L2 else dots
-    key = s if metric == L2 else -s
-    if len(ids) > k:
-        cand = np.flatnonzero(key <= np.partition(key, k - 1)[k - 1])
-    else:
-        cand = np.arange(len(ids))
-    order = cand[np.lexsort((ids[cand], key[cand]))][:k]
-    return s[order].astype(np.float32) + np.float32(0.0), ids[order]
 
 
 @pytest.mark.parametrize("metric", [L2, IP])

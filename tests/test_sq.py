@@ -150,6 +150,66 @@ def test_wide_integer_construction_stays_exact():
     assert_exact_range((s[None, :] * base).astype(np.float32), (xq - m[None, :]).astype(np.float32))
 
 
+@pytest.mark.parametrize("metric", [L2, IP])
+@pytest.mark.parametrize("qtype", [sq_ref.QT_8BIT, sq_ref.QT_8BIT_UNIFORM])
+@pytest.mark.parametrize("d,kind", [(1, "small"), (17, "small"), (130, "small"), (320, "small"), (576, "small"),
+                                    (1473, "binary")])
+def test_scan_emulation_is_exact_on_integer_construction(d, kind, qtype, metric):
+    """``sq_ref.emulate_scores`` -- the scan's arithmetic in numpy -- gives the exact score, bit for bit, where the
+    scan's own condition holds: 128 sum |w_j| < 2^24, so every accumulator holds an integer times 2^sh."""
+    rng = np.random.default_rng(300 + d + qtype)
+    t, m, s = sq_ref.integer_trained(rng, d, qtype)
+    vmin, vdiff = sq_ref.expand(t, d, qtype)
+    assert np.array_equal(sq_ref.offset_of(vmin, vdiff), m)
+    xb, base = sq_ref.integer_rows(rng, 150, d, m, s, kind)
+    xq = int_data(kind, rng, 7, d)
+    xq[3] = 0.0  # the all-zero query: sh = 0 for the inner product
+    xq[4] = xb[11]  # a zero distance
+    assert_exact_range(xb, xq)
+    w = s[None, :] * (xq - m[None, :] if metric == L2 else xq)
+    assert 128.0 * np.abs(w.astype(np.float64)).sum(1).max() < 1 << 24
+    x64, y64 = xq.astype(np.float64), xb.astype(np.float64)
+    want = ((x64[:, None, :] - y64[None]) ** 2).sum(2) if metric == L2 else x64 @ y64.T
+    got = sq_ref.emulate_scores(xq, base, vmin, vdiff, metric)
+    assert got.dtype == np.float32 and got.shape == (7, 150)
+    assert np.array_equal(got.view(np.uint32), (want.astype(np.float32) + np.float32(0)).view(np.uint32))
+    assert not np.signbit(got[got == 0]).any()
+    # the same scores through the BLAS form the long-index test uses, and its top-k against the brute force
+    assert np.array_equal(sq_ref.scores_from_codes(base, m, s, xq, metric, chunk=64), want.T)
+    D, I = sq_ref.expected(xq, xb, 20, metric)
+    for q in range(7):
+        Dq, Iq = sq_ref.top_of_scores(want[q], np.arange(150, dtype=np.int64), 20, metric)
+        assert_knn_identical(Dq[None, :], Iq[None, :], D[q:q + 1], I[q:q + 1], f"q={q}")
+    # exact scores: the bound has nothing but the reference's own rounding terms to cover
+    E, parts = sq_ref.score_bound(xq, base, vmin, vdiff, metric)
+    assert E.shape == (7,) and (E >= 0).all() and all(v.shape == (7,) for v in parts.values())
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+@pytest.mark.parametrize("qtype", [sq_ref.QT_8BIT, sq_ref.QT_8BIT_UNIFORM])
+@pytest.mark.parametrize("family", [3, 30, 900, "offset", "relu"])
+@pytest.mark.parametrize("d", [64, 512])
+def test_scan_emulation_stays_within_the_derived_bound(d, family, qtype, metric):
+    """The emulation's error against float64 over the decoded rows lies under ``sq_ref.score_bound`` on every family the
+    GPU test uses (the emulation is a lower estimate of the device's error: a bound it broke would be wrong)."""
+    train, xb, xq = sq_ref.stretched_case(family, d, qtype)
+    vmin, vdiff = sq_ref.expand(sq_ref.train_minmax(train, qtype), d, qtype)
+    codes = sq_ref.encode(xb, vmin, vdiff)
+    dec = sq_ref.decode(codes, vmin, vdiff).astype(np.float64)
+    x64 = xq.astype(np.float64)
+    want = ((x64[:, None, :] - dec[None]) ** 2).sum(2) if metric == L2 else x64 @ dec.T
+    got = sq_ref.emulate_scores(xq, codes, vmin, vdiff, metric).astype(np.float64)
+    E, parts = sq_ref.score_bound(xq, codes, vmin, vdiff, metric)
+    bound = E[:, None] * (1 + sq_ref.U) + sq_ref.U * np.abs(want)
+    err = np.abs(got - want)
+    rel = err / np.maximum(1.0, np.abs(want))
+    print(f"d={d} family={family} qtype={qtype} metric={metric}: largest |D - D64| / max(1, |D64|) = {rel.max():.3e}, "
+          f"largest error / bound = {(err / bound).max():.3e}")
+    assert (err <= bound).all()
+    if family == 3:  # data that fill their trained range: the 1e-4 of the real-data tests holds with room
+        assert rel.max() < 2e-5
+
+
 @pytest.mark.parametrize("qtype", [sq_ref.QT_8BIT, sq_ref.QT_8BIT_UNIFORM])
 def test_encode_and_decode_on_real_data(qtype):
     rng = np.random.default_rng(7)
