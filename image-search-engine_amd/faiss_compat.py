@@ -81,6 +81,7 @@ from __future__ import annotations
 import ctypes
 import struct
 import threading
+from collections import namedtuple
 
 import numpy as np
 
@@ -138,6 +139,19 @@ def _counters(fn, h, keys: tuple) -> dict:
     out = (ctypes.c_uint64 * len(keys))()
     _n.check(fn(h, out))
     return {key: int(v) for key, v in zip(keys, out)}
+
+
+def _ntotal_property(info, nargs: int, pos: int) -> property:
+    """``ntotal`` over a family's ``*_info`` entry point: ``nargs`` arguments, the handle first, the ``pos``-th (from 0)
+    the ``int64_t*`` that receives the row count; the others are passed as NULL."""
+    before, after = (None,) * (pos - 1), (None,) * (nargs - pos - 1)
+
+    def ntotal(self) -> int:
+        n = ctypes.c_int64(0)
+        _n.check(info(self._h, *before, ctypes.byref(n), *after))
+        return int(n.value)
+
+    return property(ntotal)
 
 
 def _read_range_result(res, d_dtype, get, destroy):
@@ -457,11 +471,7 @@ class IndexFlat(_RemovableIndex):
         store = {"f32": _n.STORE_F32, "bf16": _n.STORE_BF16}[storage]
         _n.check(_n.lib.ise_index_create_ex(ctypes.byref(self._h), self.d, self.metric_type, self.device, store))
 
-    @property
-    def ntotal(self) -> int:
-        n = ctypes.c_int64(0)
-        _n.check(_n.lib.ise_index_info(self._h, None, None, ctypes.byref(n), None))
-        return int(n.value)
+    ntotal = _ntotal_property(_n.lib.ise_index_info, 5, 3)
 
     def exact_stats(self) -> dict:
         """Counters of the exact float32 L2 path (include/ise_knn.h, ise_index_stats): queries
@@ -582,6 +592,14 @@ class IndexFlat(_RemovableIndex):
         out = np.empty((n, self.d), dtype=np.float32)
         _n.check(_n.lib.ise_index_reconstruct_host(self._h, int(i0), int(n), out.ctypes.data))
         return out
+
+    @staticmethod
+    def _from_parts(parts, device):
+        """The index a parsed "IxF2" / "IxFI" image describes (``parse_flat``)."""
+        index = IndexFlat(parts.d, parts.metric, device)
+        if parts.xb.shape[0]:
+            index.add(parts.xb)
+        return index
 
     # -- query side
     ASSIGN_MIN_NQ = 2048  # k = 1 searches with at least this many rows use the assignment kernel
@@ -906,6 +924,18 @@ class IndexIDMap(_IDMapBase):
     def _rows(self, x) -> np.ndarray:
         return _as_rows(x, self.index.d)
 
+    def _image(self) -> bytes:
+        sub = self.index
+        return serialize_idmap(sub.d, sub.metric_type, sub.reconstruct_n(0, sub.ntotal), self.id_map)
+
+    @classmethod
+    def _from_parts(cls, parts, device):
+        """The index a parsed "IxMp" image describes (``parse_idmap``)."""
+        index = cls(IndexFlat(parts.d, parts.metric, device))
+        if parts.xb.shape[0]:
+            index.add_with_ids(parts.xb, parts.ids)
+        return index
+
 
 def merge_keys_torch(keys, metric: int):
     """Merge all-gathered candidate lists: ``keys`` int64 CUDA (n_lists, nq, k) ->
@@ -947,6 +977,63 @@ def normalize_L2(x) -> None:
 
 
 # ---------------------------------------------------------------- persistence
+class _Cursor:
+    """A read position in a file image, for the ``_parse_*_at`` readers below: each reads the image that starts at the
+    cursor and leaves the cursor behind it, so that an image inside another file is read where it lies.  An operation
+    names the message of the RuntimeError it raises when bytes are missing; ``truncated``, where the cursor was made
+    with one, replaces them all (an image inside an "IwSq" or "IxRF" file is cut short with its file)."""
+
+    _COUNT = struct.Struct("<Q")
+
+    def __init__(self, buf, truncated: str | None = None):
+        self.buf, self.off, self.truncated = buf, 0, truncated
+
+    def _advance(self, size: int, missing) -> int:
+        at = self.off
+        if len(self.buf) < at + size:
+            raise RuntimeError(self.truncated or missing)
+        self.off = at + size
+        return at
+
+    def take(self, st: struct.Struct, missing=None) -> tuple:
+        return st.unpack_from(self.buf, self._advance(st.size, missing))
+
+    def fourcc(self, missing=None) -> bytes:
+        at = self._advance(4, missing)
+        return bytes(self.buf[at:at + 4])
+
+    def peek(self, missing=None) -> bytes:
+        """The fourcc at the cursor, which stays there."""
+        fourcc = self.fourcc(missing)
+        self.off -= 4
+        return fourcc
+
+    def expect(self, fourcc: bytes, what: str) -> None:
+        """A whole fourcc at the cursor that is not ``fourcc`` is a foreign file."""
+        got = bytes(self.buf[self.off:self.off + 4])
+        if len(got) == 4 and got != fourcc:
+            raise RuntimeError(f"unsupported index type {got!r}: not an {what}")
+
+    def array(self, dtype, count: int, missing=None) -> np.ndarray:
+        """``count`` little-endian items of ``dtype``, as a fresh array."""
+        dtype = np.dtype(dtype)
+        at = self._advance(count * dtype.itemsize, missing)
+        return np.frombuffer(self.buf, dtype=dtype.newbyteorder("<"), count=count, offset=at).astype(dtype)
+
+    def vector(self, dtype, expect, miscounted: str, missing=None, count_missing=None) -> np.ndarray:
+        """A counted vector: uint64 count, then count items.  RuntimeError(``miscounted``) when the count is not
+        ``expect`` (a number, or a predicate); ``count_missing`` where the count's own bytes have another message."""
+        (count,) = self.take(self._COUNT, count_missing or missing)
+        if not (expect(count) if callable(expect) else count == expect):
+            raise RuntimeError(miscounted)
+        return self.array(dtype, count, missing)
+
+
+def _pack_vector(a: np.ndarray) -> bytes:
+    """A counted vector as every layout here writes it: uint64 count, then the items."""
+    return struct.pack("<Q", a.size) + a.tobytes()
+
+
 # Faiss on-disk IndexFlat layout [upstream-faiss index_write.cpp, restated from
 # the published format; no sample .faiss file exists in the reference, so byte
 # compatibility with real Faiss files is UNPINNED (SURVEY.md 8f-1)]:
@@ -959,6 +1046,8 @@ def normalize_L2(x) -> None:
 _FOURCC = {METRIC_L2: b"IxF2", METRIC_INNER_PRODUCT: b"IxFI"}
 _FOURCC_IDMAP = b"IxMp"
 _HDR = struct.Struct("<4siqqqBi")
+_FlatParts = namedtuple("_FlatParts", "d metric xb")
+_IDMapParts = namedtuple("_IDMapParts", "d metric xb ids")
 
 
 def serialize_flat(d: int, metric: int, xb: np.ndarray) -> bytes:
@@ -972,20 +1061,7 @@ def _pack_id_vector(ids, n: int) -> bytes:
     """The tail of both id-map files: uint64 count (= ntotal), count int64."""
     ids = np.ascontiguousarray(ids, dtype="<i8").reshape(-1)
     assert ids.size == n, "one id per row"
-    return struct.pack("<Q", n) + ids.tobytes()
-
-
-def _parse_id_vector(buf: bytes, off: int, n: int, truncated: str, miscounted: str) -> np.ndarray:
-    """The ``n`` ids at ``buf[off:]``; RuntimeError(``truncated``) when bytes are missing, RuntimeError(``miscounted``)
-    when the count is not ``n``."""
-    if len(buf) < off + 8:
-        raise RuntimeError(truncated)
-    (count,) = struct.unpack_from("<Q", buf, off)
-    if count != n:
-        raise RuntimeError(miscounted)
-    if len(buf) < off + 8 + 8 * count:
-        raise RuntimeError(truncated)
-    return np.frombuffer(buf, dtype="<i8", count=count, offset=off + 8).astype(np.int64)
+    return _pack_vector(ids)
 
 
 def serialize_idmap(d: int, metric: int, xb: np.ndarray, ids) -> bytes:
@@ -994,37 +1070,42 @@ def serialize_idmap(d: int, metric: int, xb: np.ndarray, ids) -> bytes:
     return head + serialize_flat(d, metric, xb) + _pack_id_vector(ids, n)
 
 
-def parse_idmap(buf: bytes):
-    """-> (d, metric, xb float32 (n, d), ids int64 (n,)); raises RuntimeError on a foreign or truncated file."""
-    if len(buf) < _HDR.size:
-        raise RuntimeError("truncated index file")
-    fourcc, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
+def _parse_idmap_at(cur: _Cursor) -> _IDMapParts:
+    fourcc, d, n, _, _, _, metric = cur.take(_HDR, "truncated index file")
     if fourcc != _FOURCC_IDMAP:
         raise RuntimeError(f"unsupported index type {fourcc!r}: not an IndexIDMap")
-    sub = buf[_HDR.size:]
-    d2, metric, xb = parse_flat(sub)
+    d2, metric, xb = _parse_flat_at(cur)
     if d2 != d or xb.shape[0] != n:
         raise RuntimeError("corrupt IndexIDMap: the sub-index does not match the header")
     truncated = "truncated IndexIDMap id vector"  # also what this format says to a count that is not ntotal
-    return d, metric, xb, _parse_id_vector(buf, 2 * _HDR.size + 8 + 4 * n * d, n, truncated, truncated)
+    return _IDMapParts(d, metric, xb, cur.vector(np.int64, n, truncated, truncated))
 
 
-def parse_flat(buf: bytes):
-    """-> (d, metric, xb float32 (n, d)); raises RuntimeError on a foreign file."""
-    if len(buf) < _HDR.size + 8:
-        raise RuntimeError("truncated index file")
-    fourcc, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
+def parse_idmap(buf: bytes):
+    """-> (d, metric, xb float32 (n, d), ids int64 (n,)); raises RuntimeError on a foreign or truncated file."""
+    return tuple(_parse_idmap_at(_Cursor(buf)))
+
+
+def _flat_image(index) -> bytes:
+    """An ``IndexFlat`` -- or whatever has its ``d``, ``metric_type``, ``ntotal`` and ``reconstruct_n`` -- as a file."""
+    return serialize_flat(index.d, index.metric_type, index.reconstruct_n(0, index.ntotal))
+
+
+def _parse_flat_at(cur: _Cursor) -> _FlatParts:
+    fourcc, d, n, _, _, _, metric = cur.take(_HDR, "truncated index file")
     if fourcc not in (b"IxF2", b"IxFI", b"IxFl"):
         raise RuntimeError(f"unsupported index type {fourcc!r}: only flat indexes are readable")
     if fourcc == b"IxF2":
         metric = METRIC_L2
     elif fourcc == b"IxFI":
         metric = METRIC_INNER_PRODUCT
-    (count,) = struct.unpack_from("<Q", buf, _HDR.size)
-    if count != n * d or len(buf) < _HDR.size + 8 + 4 * count:
-        raise RuntimeError("corrupt flat index payload")
-    xb = np.frombuffer(buf, dtype="<f4", count=count, offset=_HDR.size + 8).reshape(n, d).astype(np.float32)
-    return d, metric, xb
+    corrupt = "corrupt flat index payload"  # also what this format says to missing rows
+    return _FlatParts(d, metric, cur.vector(np.float32, n * d, corrupt, corrupt, "truncated index file").reshape(n, d))
+
+
+def parse_flat(buf: bytes):
+    """-> (d, metric, xb float32 (n, d)); raises RuntimeError on a foreign file."""
+    return tuple(_parse_flat_at(_Cursor(buf)))
 
 
 # IndexPQ [upstream-faiss index_write.cpp write_index / write_ProductQuantizer, restated from memory of the published
@@ -1036,6 +1117,7 @@ def parse_flat(buf: bytes):
 _FOURCC_PQ = b"IxPq"
 _PQ_DIMS = struct.Struct("<qqq")
 _PQ_TAIL = struct.Struct("<iBi")
+_PQParts = namedtuple("_PQParts", "d M nbits metric centroids codes")
 
 
 def serialize_pq(d: int, metric: int, centroids, codes) -> bytes:
@@ -1044,41 +1126,28 @@ def serialize_pq(d: int, metric: int, centroids, codes) -> bytes:
     assert c.ndim == 3 and c.shape[1] == 256 and c.shape[0] * c.shape[2] == int(d), "centroids are (M, 256, d / M)"
     M = c.shape[0]
     codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, M)
-    n = codes.shape[0]
-    head = _HDR.pack(_FOURCC_PQ, int(d), n, 1 << 20, 1 << 20, 1, int(metric))
-    return (head + _PQ_DIMS.pack(int(d), M, 8) + struct.pack("<Q", c.size) + c.tobytes()
-            + struct.pack("<Q", n * M) + codes.tobytes() + _PQ_TAIL.pack(0, 0, 0))
+    head = _HDR.pack(_FOURCC_PQ, int(d), codes.shape[0], 1 << 20, 1 << 20, 1, int(metric))
+    return head + _PQ_DIMS.pack(int(d), M, 8) + _pack_vector(c) + _pack_vector(codes) + _PQ_TAIL.pack(0, 0, 0)
+
+
+def _parse_pq_at(cur: _Cursor) -> _PQParts:
+    cur.expect(_FOURCC_PQ, "IndexPQ")
+    _, d, n, _, _, _, metric = cur.take(_HDR, "truncated IndexPQ file")
+    d2, M, nbits = cur.take(_PQ_DIMS, "truncated IndexPQ file")
+    if d <= 0 or d2 != d or M <= 0 or d % M != 0 or nbits != 8 or n < 0:
+        raise RuntimeError("corrupt IndexPQ header (only 8-bit product quantisers are readable)")
+    centroids = cur.vector(np.float32, 256 * d, "corrupt IndexPQ: the centroid vector does not hold M * 256 * dsub floats",
+                           "truncated IndexPQ centroids", "truncated IndexPQ file").reshape(M, 256, d // M)
+    codes = cur.vector(np.uint8, n * M, "corrupt IndexPQ: the code vector does not hold ntotal * M bytes",
+                       "truncated IndexPQ codes", "truncated IndexPQ centroids").reshape(n, M)
+    cur.take(_PQ_TAIL, "truncated IndexPQ codes")
+    return _PQParts(d, M, nbits, metric, centroids, codes)
 
 
 def parse_pq(buf: bytes):
     """-> (d, M, nbits, metric, centroids float32 (M, 256, dsub), codes uint8 (n, M)); raises RuntimeError on a foreign,
     truncated or miscounted file."""
-    if len(buf) >= 4 and buf[:4] != _FOURCC_PQ:
-        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexPQ")
-    off = _HDR.size
-    if len(buf) < off + _PQ_DIMS.size + 8:
-        raise RuntimeError("truncated IndexPQ file")
-    _, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
-    d2, M, nbits = _PQ_DIMS.unpack_from(buf, off)
-    off += _PQ_DIMS.size
-    if d <= 0 or d2 != d or M <= 0 or d % M != 0 or nbits != 8 or n < 0:
-        raise RuntimeError("corrupt IndexPQ header (only 8-bit product quantisers are readable)")
-    (count,) = struct.unpack_from("<Q", buf, off)
-    off += 8
-    if count != 256 * d:
-        raise RuntimeError("corrupt IndexPQ: the centroid vector does not hold M * 256 * dsub floats")
-    if len(buf) < off + 4 * count + 8:
-        raise RuntimeError("truncated IndexPQ centroids")
-    centroids = np.frombuffer(buf, dtype="<f4", count=count, offset=off).reshape(M, 256, d // M).astype(np.float32)
-    off += 4 * count
-    (ncodes,) = struct.unpack_from("<Q", buf, off)
-    off += 8
-    if ncodes != n * M:
-        raise RuntimeError("corrupt IndexPQ: the code vector does not hold ntotal * M bytes")
-    if len(buf) < off + ncodes + _PQ_TAIL.size:
-        raise RuntimeError("truncated IndexPQ codes")
-    codes = np.frombuffer(buf, dtype=np.uint8, count=ncodes, offset=off).reshape(n, M).copy()
-    return d, M, nbits, metric, centroids, codes
+    return tuple(_parse_pq_at(_Cursor(buf)))
 
 
 # IndexScalarQuantizer [upstream-faiss index_write.cpp write_index / write_ScalarQuantizer, restated from memory of the
@@ -1089,52 +1158,55 @@ def parse_pq(buf: bytes):
 _FOURCC_SQ = b"IxSQ"
 _SQ_HEAD = struct.Struct("<iifQQ")
 _SQ_QTYPES = (0, 2)  # QT_8bit, QT_8bit_uniform: the types that are readable
+_SQParts = namedtuple("_SQParts", "d metric qtype rangestat rangestat_arg trained codes")
+
+
+def _pack_sq_block(d: int, qtype: int, trained, rangestat: int, rangestat_arg: float) -> bytes:
+    """The scalar quantiser block of "IxSQ" and "IwSq": ``_SQ_HEAD``, then the trained vector."""
+    assert qtype in _SQ_QTYPES, "only QT_8bit and QT_8bit_uniform are written"
+    t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
+    assert t.size == (2 if qtype == 2 else 2 * d), "the trained vector is [vmin.., vdiff..]"
+    return _SQ_HEAD.pack(qtype, int(rangestat), float(rangestat_arg), d, d) + _pack_vector(t)
+
+
+def _parse_sq_block_at(cur: _Cursor, d: int, what: str, mismatch: str, missing=None, missing_trained=None):
+    """-> (qtype, rangestat, rangestat_arg, trained) of the block at the cursor, in a file of a ``what``."""
+    qtype, rangestat, rangestat_arg, d2, code_size = cur.take(_SQ_HEAD, missing)
+    if qtype not in _SQ_QTYPES:
+        raise RuntimeError(f"unsupported scalar quantiser type {qtype}: only QT_8bit (0) and QT_8bit_uniform (2) are readable")
+    if d2 != d or code_size != d:
+        raise RuntimeError(mismatch)
+    trained = cur.vector(np.float32, 2 if qtype == 2 else 2 * d,
+                         f"corrupt {what}: the trained vector does not hold vmin and vdiff", missing_trained, missing)
+    return qtype, rangestat, float(rangestat_arg), trained
 
 
 def serialize_sq(d: int, metric: int, qtype: int, trained, codes, rangestat: int = 0, rangestat_arg: float = 0.0) -> bytes:
     """``trained`` float32 (2 d,) or (2,) for the uniform type, ``codes`` uint8 (n, d) (any n, also 0)."""
     d, qtype = int(d), int(qtype)
-    assert qtype in _SQ_QTYPES, "only QT_8bit and QT_8bit_uniform are written"
-    t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
-    assert t.size == (2 if qtype == 2 else 2 * d), "the trained vector is [vmin.., vdiff..]"
+    block = _pack_sq_block(d, qtype, trained, rangestat, rangestat_arg)
     codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, d)
-    n = codes.shape[0]
-    head = _HDR.pack(_FOURCC_SQ, d, n, 1 << 20, 1 << 20, 1, int(metric))
-    return (head + _SQ_HEAD.pack(qtype, int(rangestat), float(rangestat_arg), d, d) + struct.pack("<Q", t.size) + t.tobytes()
-            + struct.pack("<Q", n * d) + codes.tobytes())
+    return _HDR.pack(_FOURCC_SQ, d, codes.shape[0], 1 << 20, 1 << 20, 1, int(metric)) + block + _pack_vector(codes)
+
+
+def _parse_sq_at(cur: _Cursor) -> _SQParts:
+    cur.expect(_FOURCC_SQ, "IndexScalarQuantizer")
+    corrupt = "corrupt IndexScalarQuantizer header"
+    _, d, n, _, _, _, metric = cur.take(_HDR, "truncated IndexScalarQuantizer file")
+    qtype, rangestat, rangestat_arg, trained = _parse_sq_block_at(
+        cur, d, "IndexScalarQuantizer", corrupt, "truncated IndexScalarQuantizer file",
+        "truncated IndexScalarQuantizer trained vector")
+    if d <= 0 or n < 0:
+        raise RuntimeError(corrupt)
+    codes = cur.vector(np.uint8, n * d, "corrupt IndexScalarQuantizer: the code vector does not hold ntotal * d bytes",
+                       "truncated IndexScalarQuantizer codes", "truncated IndexScalarQuantizer trained vector").reshape(n, d)
+    return _SQParts(d, metric, qtype, rangestat, rangestat_arg, trained, codes)
 
 
 def parse_sq(buf: bytes):
     """-> (d, metric, qtype, rangestat, rangestat_arg, trained float32, codes uint8 (n, d)); raises RuntimeError on a
     foreign, truncated or miscounted file and on a quantiser type other than the two 8-bit ones."""
-    if len(buf) >= 4 and buf[:4] != _FOURCC_SQ:
-        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexScalarQuantizer")
-    off = _HDR.size
-    if len(buf) < off + _SQ_HEAD.size + 8:
-        raise RuntimeError("truncated IndexScalarQuantizer file")
-    _, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
-    qtype, rangestat, rangestat_arg, d2, code_size = _SQ_HEAD.unpack_from(buf, off)
-    off += _SQ_HEAD.size
-    if qtype not in _SQ_QTYPES:
-        raise RuntimeError(f"unsupported scalar quantiser type {qtype}: only QT_8bit (0) and QT_8bit_uniform (2) are readable")
-    if d <= 0 or d2 != d or code_size != d or n < 0:
-        raise RuntimeError("corrupt IndexScalarQuantizer header")
-    (count,) = struct.unpack_from("<Q", buf, off)
-    off += 8
-    if count != (2 if qtype == 2 else 2 * d):
-        raise RuntimeError("corrupt IndexScalarQuantizer: the trained vector does not hold vmin and vdiff")
-    if len(buf) < off + 4 * count + 8:
-        raise RuntimeError("truncated IndexScalarQuantizer trained vector")
-    trained = np.frombuffer(buf, dtype="<f4", count=count, offset=off).astype(np.float32)
-    off += 4 * count
-    (ncodes,) = struct.unpack_from("<Q", buf, off)
-    off += 8
-    if ncodes != n * d:
-        raise RuntimeError("corrupt IndexScalarQuantizer: the code vector does not hold ntotal * d bytes")
-    if len(buf) < off + ncodes:
-        raise RuntimeError("truncated IndexScalarQuantizer codes")
-    codes = np.frombuffer(buf, dtype=np.uint8, count=ncodes, offset=off).reshape(n, d).copy()
-    return d, metric, qtype, rangestat, float(rangestat_arg), trained, codes
+    return tuple(_parse_sq_at(_Cursor(buf)))
 
 
 # IndexIVFScalarQuantizer [upstream-faiss index_write.cpp write_index / write_ivf_header / write_InvertedLists, restated
@@ -1149,7 +1221,11 @@ def parse_sq(buf: bytes):
 #   code_size uint8, size int64 ids.
 _FOURCC_IVFSQ = b"IwSq"
 _IVF_DIMS = struct.Struct("<QQ")
+_IVF_DIRECT_MAP = struct.Struct("<BQ")
+_IVF_CODE = struct.Struct("<QB")
 _TRUNCATED_IVFSQ = "truncated IndexIVFScalarQuantizer file"
+_IVFSQParts = namedtuple("_IVFSQParts", "d metric nlist nprobe qmetric centroids qtype trained lists rangestat "
+                                        "rangestat_arg by_residual")
 
 
 def serialize_ivfsq(d: int, metric: int, nlist: int, nprobe: int, qmetric: int, centroids, qtype: int, trained, lists,
@@ -1157,113 +1233,73 @@ def serialize_ivfsq(d: int, metric: int, nlist: int, nprobe: int, qmetric: int, 
     """``centroids`` float32 (nlist, d) (or (0, d): an untrained quantiser) under the quantiser's metric ``qmetric``;
     ``trained`` as for ``serialize_sq``; ``lists``: ``nlist`` pairs (ids int64 (m,), codes uint8 (m, d)), any m, also 0."""
     d, qtype, nlist = int(d), int(qtype), int(nlist)
-    assert qtype in _SQ_QTYPES, "only QT_8bit and QT_8bit_uniform are written"
-    t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
-    assert t.size == (2 if qtype == 2 else 2 * d), "the trained vector is [vmin.., vdiff..]"
+    block = _pack_sq_block(d, qtype, trained, rangestat, rangestat_arg)
     assert len(lists) == nlist, "one (ids, codes) pair per list"
     pairs = [(np.ascontiguousarray(ids, dtype="<i8").reshape(-1), np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, d))
              for ids, codes in lists]
     assert all(ids.size == codes.shape[0] for ids, codes in pairs), "one id per code row"
     sizes = np.array([ids.size for ids, _ in pairs], dtype="<u8")
     out = [_HDR.pack(_FOURCC_IVFSQ, d, int(sizes.sum()), 1 << 20, 1 << 20, 1, int(metric)), _IVF_DIMS.pack(nlist, int(nprobe)),
-           serialize_flat(d, int(qmetric), np.asarray(centroids, dtype=np.float32).reshape(-1, d)), struct.pack("<BQ", 0, 0),
-           _SQ_HEAD.pack(qtype, int(rangestat), float(rangestat_arg), d, d), struct.pack("<Q", t.size), t.tobytes(),
-           struct.pack("<QB", d, 1 if by_residual else 0), b"ilar", _IVF_DIMS.pack(nlist, d), b"full",
-           struct.pack("<Q", nlist), sizes.tobytes()]
+           serialize_flat(d, int(qmetric), np.asarray(centroids, dtype=np.float32).reshape(-1, d)), _IVF_DIRECT_MAP.pack(0, 0),
+           block, _IVF_CODE.pack(d, 1 if by_residual else 0), b"ilar", _IVF_DIMS.pack(nlist, d), b"full", _pack_vector(sizes)]
     for ids, codes in pairs:
         if ids.size:
             out += [codes.tobytes(), ids.tobytes()]
     return b"".join(out)
 
 
+def _parse_ivfsq_at(cur: _Cursor) -> _IVFSQParts:
+    """(Every missing byte is ``_TRUNCATED_IVFSQ``: the cursor is made with it.)"""
+    corrupt = "corrupt IndexIVFScalarQuantizer: "
+    cur.expect(_FOURCC_IVFSQ, "IndexIVFScalarQuantizer")
+    _, d, n, _, _, _, metric = cur.take(_HDR)
+    nlist, nprobe = cur.take(_IVF_DIMS)
+    if d <= 0 or n < 0 or nlist <= 0:
+        raise RuntimeError("corrupt IndexIVFScalarQuantizer header")
+    quantizer = cur.peek()
+    if quantizer not in (b"IxF2", b"IxFI"):
+        raise RuntimeError(f"unsupported quantiser type {quantizer!r} in an IndexIVFScalarQuantizer file: "
+                           "only flat quantisers are readable")
+    d2, qmetric, centroids = _parse_flat_at(cur)
+    if d2 != d or centroids.shape[0] not in (0, nlist):
+        raise RuntimeError(corrupt + "the quantiser does not hold nlist centroids of dimension d")
+    if cur.take(_IVF_DIRECT_MAP) != (0, 0):
+        raise RuntimeError("an IndexIVFScalarQuantizer file with a direct map is not readable")
+    qtype, rangestat, rangestat_arg, trained = _parse_sq_block_at(
+        cur, d, "IndexIVFScalarQuantizer", corrupt + "the scalar quantiser does not match the header")
+    code_size, by_residual = cur.take(_IVF_CODE)
+    lists = cur.fourcc()
+    if lists != b"ilar":
+        raise RuntimeError(f"unsupported inverted lists {lists!r}: only array lists (\"ilar\") are readable")
+    if (code_size,) + cur.take(_IVF_DIMS) != (d, nlist, d):
+        raise RuntimeError(corrupt + "the inverted lists do not match the header")
+    form = cur.fourcc()
+    sizes = np.zeros(nlist, dtype=np.int64)
+    if form == b"full":
+        sizes[:] = cur.vector(np.uint64, nlist, corrupt + "the size vector does not hold nlist entries").astype(np.int64)
+    elif form == b"sprs":
+        pairs = cur.vector(np.uint64, lambda count: count % 2 == 0 and count <= 2 * nlist,
+                           corrupt + "the sparse size vector does not hold (list, size) pairs").astype(np.int64).reshape(-1, 2)
+        if pairs.size and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= nlist):
+            raise RuntimeError(corrupt + "a list number outside [0, nlist)")
+        sizes[pairs[:, 0]] = pairs[:, 1]
+    else:
+        raise RuntimeError(f"unsupported list size form {form!r} in an IndexIVFScalarQuantizer file")
+    if sizes.min() < 0 or int(sizes.sum()) != n:
+        raise RuntimeError(corrupt + "the list sizes do not add up to ntotal")
+    lists = []
+    for m in (int(s) for s in sizes):
+        codes = cur.array(np.uint8, m * d).reshape(m, d)
+        lists.append((cur.array(np.int64, m), codes))
+    return _IVFSQParts(d, metric, int(nlist), int(nprobe), qmetric, centroids, qtype, trained, lists, rangestat,
+                       rangestat_arg, bool(by_residual))
+
+
 def parse_ivfsq(buf: bytes):
     """-> (d, metric, nlist, nprobe, qmetric, centroids float32 (nlist or 0, d), qtype, trained float32, lists [(ids int64
     (m,), codes uint8 (m, d))] * nlist, rangestat, rangestat_arg, by_residual): ``serialize_ivfsq``'s arguments.  Raises
     RuntimeError on a foreign, truncated or miscounted file and on a quantiser type other than the two 8-bit ones."""
-    if len(buf) >= 4 and buf[:4] != _FOURCC_IVFSQ:
-        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexIVFScalarQuantizer")
-
-    def need(off: int, size: int) -> None:
-        if len(buf) < off + size:
-            raise RuntimeError(_TRUNCATED_IVFSQ)
-
-    off = _HDR.size
-    need(off, _IVF_DIMS.size + 4)
-    _, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
-    nlist, nprobe = _IVF_DIMS.unpack_from(buf, off)
-    off += _IVF_DIMS.size
-    if d <= 0 or n < 0 or nlist <= 0:
-        raise RuntimeError("corrupt IndexIVFScalarQuantizer header")
-    if bytes(buf[off:off + 4]) not in (b"IxF2", b"IxFI"):
-        raise RuntimeError(f"unsupported quantiser type {bytes(buf[off:off + 4])!r} in an IndexIVFScalarQuantizer file: "
-                           "only flat quantisers are readable")
-    need(off, _HDR.size + 8)
-    (count,) = struct.unpack_from("<Q", buf, off + _HDR.size)
-    need(off, _HDR.size + 8 + 4 * count)
-    d2, qmetric, centroids = parse_flat(buf[off:off + _HDR.size + 8 + 4 * count])
-    off += _HDR.size + 8 + 4 * count
-    if d2 != d or centroids.shape[0] not in (0, nlist):
-        raise RuntimeError("corrupt IndexIVFScalarQuantizer: the quantiser does not hold nlist centroids of dimension d")
-    need(off, 9)
-    dm_type, dm_count = struct.unpack_from("<BQ", buf, off)
-    off += 9
-    if dm_type != 0 or dm_count != 0:
-        raise RuntimeError("an IndexIVFScalarQuantizer file with a direct map is not readable")
-    need(off, _SQ_HEAD.size + 8)
-    qtype, rangestat, rangestat_arg, d2, code_size = _SQ_HEAD.unpack_from(buf, off)
-    off += _SQ_HEAD.size
-    if qtype not in _SQ_QTYPES:
-        raise RuntimeError(f"unsupported scalar quantiser type {qtype}: only QT_8bit (0) and QT_8bit_uniform (2) are readable")
-    if d2 != d or code_size != d:
-        raise RuntimeError("corrupt IndexIVFScalarQuantizer: the scalar quantiser does not match the header")
-    (count,) = struct.unpack_from("<Q", buf, off)
-    off += 8
-    if count != (2 if qtype == 2 else 2 * d):
-        raise RuntimeError("corrupt IndexIVFScalarQuantizer: the trained vector does not hold vmin and vdiff")
-    need(off, 4 * count)
-    trained = np.frombuffer(buf, dtype="<f4", count=count, offset=off).astype(np.float32)
-    off += 4 * count
-    need(off, 9 + 4 + _IVF_DIMS.size + 4 + 8)
-    code_size, by_residual = struct.unpack_from("<QB", buf, off)
-    off += 9
-    if bytes(buf[off:off + 4]) != b"ilar":
-        raise RuntimeError(f"unsupported inverted lists {bytes(buf[off:off + 4])!r}: only array lists (\"ilar\") are readable")
-    off += 4
-    nlist2, code_size2 = _IVF_DIMS.unpack_from(buf, off)
-    off += _IVF_DIMS.size
-    if code_size != d or nlist2 != nlist or code_size2 != d:
-        raise RuntimeError("corrupt IndexIVFScalarQuantizer: the inverted lists do not match the header")
-    form = bytes(buf[off:off + 4])
-    (count,) = struct.unpack_from("<Q", buf, off + 4)
-    off += 12
-    sizes = np.zeros(nlist, dtype=np.int64)
-    if form == b"full":
-        if count != nlist:
-            raise RuntimeError("corrupt IndexIVFScalarQuantizer: the size vector does not hold nlist entries")
-        need(off, 8 * count)
-        sizes[:] = np.frombuffer(buf, dtype="<u8", count=count, offset=off).astype(np.int64)
-    elif form == b"sprs":
-        if count % 2 or count > 2 * nlist:
-            raise RuntimeError("corrupt IndexIVFScalarQuantizer: the sparse size vector does not hold (list, size) pairs")
-        need(off, 8 * count)
-        pairs = np.frombuffer(buf, dtype="<u8", count=count, offset=off).astype(np.int64).reshape(-1, 2)
-        if pairs.size and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= nlist):
-            raise RuntimeError("corrupt IndexIVFScalarQuantizer: a list number outside [0, nlist)")
-        sizes[pairs[:, 0]] = pairs[:, 1]
-    else:
-        raise RuntimeError(f"unsupported list size form {form!r} in an IndexIVFScalarQuantizer file")
-    off += 8 * count
-    if sizes.min() < 0 or int(sizes.sum()) != n:
-        raise RuntimeError("corrupt IndexIVFScalarQuantizer: the list sizes do not add up to ntotal")
-    lists = []
-    for m in (int(s) for s in sizes):
-        need(off, m * d + 8 * m)
-        codes = np.frombuffer(buf, dtype=np.uint8, count=m * d, offset=off).reshape(m, d).copy()
-        ids = np.frombuffer(buf, dtype="<i8", count=m, offset=off + m * d).astype(np.int64)
-        off += m * d + 8 * m
-        lists.append((ids, codes))
-    return (d, metric, int(nlist), int(nprobe), qmetric, centroids, qtype, trained, lists, rangestat, float(rangestat_arg),
-            bool(by_residual))
+    return tuple(_parse_ivfsq_at(_Cursor(buf, _TRUNCATED_IVFSQ)))
 
 
 # IndexRefineFlat [upstream-faiss index_write.cpp, restated from memory of the published format and UNPINNED like the
@@ -1272,58 +1308,18 @@ def parse_ivfsq(buf: bytes):
 #   image; the refine index as an "IxF2" / "IxFI" image; float32 k_factor.
 _FOURCC_REFINE = b"IxRF"
 _TRUNCATED_REFINE = "truncated IndexRefineFlat file"
+_RefineParts = namedtuple("_RefineParts", "d metric base_kind base xb k_factor")
+_K_FACTOR = struct.Struct("<f")
+_SUB_IMAGES = {b"IxF2": ("flat", _parse_flat_at), b"IxFI": ("flat", _parse_flat_at), _FOURCC_PQ: ("pq", _parse_pq_at),
+               _FOURCC_SQ: ("sq", _parse_sq_at)}
 
 
-def _flat_image_size(buf: bytes, off: int) -> int:
-    """Bytes of the flat-index image that starts at ``buf[off:]`` (``parse_flat`` reads a whole buffer)."""
-    if len(buf) < off + _HDR.size + 8:
-        raise RuntimeError(_TRUNCATED_REFINE)
-    (count,) = struct.unpack_from("<Q", buf, off + _HDR.size)
-    return _HDR.size + 8 + 4 * count
-
-
-def _pq_image_size(buf: bytes, off: int) -> int:
-    """Bytes of the IndexPQ image that starts at ``buf[off:]`` (``parse_pq`` reads a whole buffer)."""
-    at = off + _HDR.size + _PQ_DIMS.size
-    if len(buf) < at + 8:
-        raise RuntimeError(_TRUNCATED_REFINE)
-    (count,) = struct.unpack_from("<Q", buf, at)
-    at += 8 + 4 * count
-    if len(buf) < at + 8:
-        raise RuntimeError(_TRUNCATED_REFINE)
-    (ncodes,) = struct.unpack_from("<Q", buf, at)
-    return at + 8 + ncodes + _PQ_TAIL.size - off
-
-
-def _sq_image_size(buf: bytes, off: int) -> int:
-    """Bytes of the IndexScalarQuantizer image that starts at ``buf[off:]`` (``parse_sq`` reads a whole buffer)."""
-    at = off + _HDR.size + _SQ_HEAD.size
-    if len(buf) < at + 8:
-        raise RuntimeError(_TRUNCATED_REFINE)
-    (count,) = struct.unpack_from("<Q", buf, at)
-    at += 8 + 4 * count
-    if len(buf) < at + 8:
-        raise RuntimeError(_TRUNCATED_REFINE)
-    (ncodes,) = struct.unpack_from("<Q", buf, at)
-    return at + 8 + ncodes - off
-
-
-def _sub_image(buf: bytes, off: int):
-    """-> (kind "flat" | "pq" | "sq", the sub-index image at ``buf[off:]`` cut to its own length)."""
-    if len(buf) < off + 4:
-        raise RuntimeError(_TRUNCATED_REFINE)
-    fourcc = bytes(buf[off:off + 4])
-    if fourcc in (b"IxF2", b"IxFI"):
-        kind, size = "flat", _flat_image_size(buf, off)
-    elif fourcc == _FOURCC_PQ:
-        kind, size = "pq", _pq_image_size(buf, off)
-    elif fourcc == _FOURCC_SQ:
-        kind, size = "sq", _sq_image_size(buf, off)
-    else:
+def _sub_image(cur: _Cursor):
+    """-> (kind "flat" | "pq" | "sq", the reader of the sub-index image at the cursor)."""
+    fourcc = cur.peek(_TRUNCATED_REFINE)
+    if fourcc not in _SUB_IMAGES:
         raise RuntimeError(f"unsupported sub-index type {fourcc!r} in an IndexRefineFlat file")
-    if len(buf) < off + size:
-        raise RuntimeError(_TRUNCATED_REFINE)
-    return kind, buf[off:off + size]
+    return _SUB_IMAGES[fourcc]
 
 
 def serialize_refine(base_image: bytes, d: int, metric: int, xb: np.ndarray, k_factor: float) -> bytes:
@@ -1331,121 +1327,60 @@ def serialize_refine(base_image: bytes, d: int, metric: int, xb: np.ndarray, k_f
     refine index's rows."""
     n = xb.shape[0] if np.size(xb) else 0
     head = _HDR.pack(_FOURCC_REFINE, int(d), n, 1 << 20, 1 << 20, 1, int(metric))
-    return head + bytes(base_image) + serialize_flat(int(d), int(metric), xb) + struct.pack("<f", float(k_factor))
+    return head + bytes(base_image) + serialize_flat(int(d), int(metric), xb) + _K_FACTOR.pack(float(k_factor))
+
+
+def _parse_refine_at(cur: _Cursor) -> _RefineParts:
+    """(Every missing byte is ``_TRUNCATED_REFINE``: the cursor is made with it.)"""
+    cur.expect(_FOURCC_REFINE, "IndexRefineFlat")
+    _, d, n, _, _, _, metric = cur.take(_HDR)
+    kind, read = _sub_image(cur)
+    base = read(cur)
+    rkind, read = _sub_image(cur)
+    if rkind != "flat":
+        raise RuntimeError("corrupt IndexRefineFlat: the refine index is not a flat index")
+    d2, metric2, xb = read(cur)
+    base_n = (base.xb if kind == "flat" else base.codes).shape[0]
+    if d2 != d or base.d != d or xb.shape[0] != n or base_n != n or metric2 != metric:
+        raise RuntimeError("corrupt IndexRefineFlat: the sub-indexes do not match the header")
+    (k_factor,) = cur.take(_K_FACTOR)
+    return _RefineParts(d, metric, kind, base, xb, float(k_factor))
 
 
 def parse_refine(buf: bytes):
     """-> (d, metric, base_kind "flat" | "pq" | "sq", base as ``parse_flat`` / ``parse_pq`` / ``parse_sq`` return it, xb float32 (n, d),
     k_factor); raises RuntimeError on a foreign, truncated or inconsistent file."""
-    if len(buf) >= 4 and buf[:4] != _FOURCC_REFINE:
-        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexRefineFlat")
-    if len(buf) < _HDR.size:
-        raise RuntimeError(_TRUNCATED_REFINE)
-    _, d, n, _, _, _, metric = _HDR.unpack_from(buf, 0)
-    off = _HDR.size
-    kind, image = _sub_image(buf, off)
-    off += len(image)
-    base = parse_flat(image) if kind == "flat" else parse_pq(image) if kind == "pq" else parse_sq(image)
-    rkind, image = _sub_image(buf, off)
-    off += len(image)
-    if rkind != "flat":
-        raise RuntimeError("corrupt IndexRefineFlat: the refine index is not a flat index")
-    d2, metric2, xb = parse_flat(image)
-    base_n = base[{"flat": 2, "pq": 5, "sq": 6}[kind]].shape[0]
-    if d2 != d or base[0] != d or xb.shape[0] != n or base_n != n or metric2 != metric:
-        raise RuntimeError("corrupt IndexRefineFlat: the sub-indexes do not match the header")
-    if len(buf) < off + 4:
-        raise RuntimeError(_TRUNCATED_REFINE)
-    (k_factor,) = struct.unpack_from("<f", buf, off)
-    return d, metric, kind, base, xb, float(k_factor)
+    parts = _parse_refine_at(_Cursor(buf, _TRUNCATED_REFINE))
+    return tuple(parts._replace(base=tuple(parts.base)))
 
 
 def write_index(index, path) -> None:
-    if isinstance(index, IndexIVFScalarQuantizer):  # before its sibling: the two share a base class, not each other
-        image = index._image()  # raises on an untrained index before a file is made
-        with open(str(path), "wb") as f:
-            f.write(image)
-        return
     if isinstance(index, IndexIVFFlat):
         raise NotImplementedError("write_index of an IndexIVFFlat is not provided")
-    if isinstance(index, IndexRefine):
-        base = index.base_index
-        if isinstance(base, IndexPQ):
-            image = serialize_pq(base.d, base.metric_type, base.pq.centroids, base.codes)
-        elif isinstance(base, IndexScalarQuantizer):
-            image = base._image()
-        elif type(base) in (IndexFlat, IndexFlatL2, IndexFlatIP) and base.storage == "f32":
-            image = serialize_flat(base.d, base.metric_type, base.reconstruct_n(0, base.ntotal))
-        else:
-            raise NotImplementedError(f"write_index of an IndexRefine over {type(base).__name__} is not provided "
-                                      "(float32 IndexFlat, IndexPQ and IndexScalarQuantizer bases are)")
-        rf = index.refine_index
-        with open(str(path), "wb") as f:
-            f.write(serialize_refine(image, index.d, index.metric_type, rf.reconstruct_n(0, rf.ntotal), index.k_factor))
-        return
+    # the image first: a kind that refuses (an untrained index) leaves what is at ``path`` as it is
+    image = index._image() if isinstance(index, (_CodedIndex, _IndexIVF, IndexRefine, IndexIDMap)) else _flat_image(index)
     with open(str(path), "wb") as f:
-        if isinstance(index, IndexPQ):
-            f.write(serialize_pq(index.d, index.metric_type, index.pq.centroids, index.codes))
-        elif isinstance(index, IndexScalarQuantizer):
-            f.write(index._image())
-        elif isinstance(index, IndexIDMap):
-            sub = index.index
-            f.write(serialize_idmap(sub.d, sub.metric_type, sub.reconstruct_n(0, sub.ntotal), index.id_map))
-        else:
-            f.write(serialize_flat(index.d, index.metric_type, index.reconstruct_n(0, index.ntotal)))
+        f.write(image)
 
 
 def read_index(path, device: int | None = None):
     """-> IndexFlat, IndexIDMap, IndexPQ, IndexScalarQuantizer, IndexIVFScalarQuantizer or IndexRefineFlat, as the file
-    was written."""
+    was written; the stored rows and codes are added as they are, nothing is encoded again."""
     with open(str(path), "rb") as f:
         buf = f.read()
-    ids = None
-    if buf[:4] == _FOURCC_REFINE:
-        d, metric, kind, base_parts, xb, k_factor = parse_refine(buf)
-        if kind == "pq":
-            _, M, nbits, bmetric, centroids, codes = base_parts
-            base = IndexPQ(d, M, nbits, bmetric, device)
-            base.pq.set_centroids(centroids)
-        elif kind == "sq":
-            base = IndexScalarQuantizer._from_parts(base_parts, device, add_codes=False)
-            codes = base_parts[6]
-        else:
-            base = IndexFlat(d, base_parts[1], device)
-        index = IndexRefineFlat(base)
-        index.k_factor = k_factor
-        if xb.shape[0]:  # each side as stored: nothing is encoded again
-            if kind in ("pq", "sq"):
-                base._add_codes(codes)
-            else:
-                base.add(base_parts[2])
-            index.refine_index.add(xb)
-        return index
-    if buf[:4] == _FOURCC_PQ:
-        d, M, nbits, metric, centroids, codes = parse_pq(buf)
-        index = IndexPQ(d, M, nbits, metric, device)
-        index.pq.set_centroids(centroids)
-        index._add_codes(codes)  # as stored: nothing is encoded again
-        return index
-    if buf[:4] == _FOURCC_SQ:
-        return IndexScalarQuantizer._from_parts(parse_sq(buf), device)  # as stored: nothing is encoded again
-    if buf[:4] == _FOURCC_IVFSQ:
-        return IndexIVFScalarQuantizer._from_parts(parse_ivfsq(buf), device)  # as stored: nothing is encoded again
     if buf[:4] in (b"IwFl", b"IwF2"):  # Faiss's fourccs of IndexIVFFlat files
         raise NotImplementedError("read_index of an IndexIVFFlat file is not provided")
-    if buf[:4] == _FOURCC_IDMAP:
-        d, metric, xb, ids = parse_idmap(buf)
-    else:
-        d, metric, xb = parse_flat(buf)
-    index = IndexFlat(d, metric, device)
-    if ids is not None:
-        index = IndexIDMap(index)
-        if xb.shape[0]:
-            index.add_with_ids(xb, ids)
-    elif xb.shape[0]:
-        index.add(xb)
-    return index
+    cls, read, truncated = _INDEX_FILES.get(bytes(buf[:4]), _FLAT_FILE)  # (a foreign file is the flat reader's to refuse)
+    return cls()._from_parts(read(_Cursor(buf, truncated)), device)
 
+
+# fourcc -> (the class of its index, late: the classes follow; the reader of its image; the cursor's message)
+_FLAT_FILE = (lambda: IndexFlat, _parse_flat_at, None)
+_INDEX_FILES = {_FOURCC_IDMAP: (lambda: IndexIDMap, _parse_idmap_at, None),
+                _FOURCC_PQ: (lambda: IndexPQ, _parse_pq_at, None),
+                _FOURCC_SQ: (lambda: IndexScalarQuantizer, _parse_sq_at, None),
+                _FOURCC_IVFSQ: (lambda: IndexIVFScalarQuantizer, _parse_ivfsq_at, _TRUNCATED_IVFSQ),
+                _FOURCC_REFINE: (lambda: IndexRefineFlat, _parse_refine_at, _TRUNCATED_REFINE)}
 
 # ---------------------------------------------------------------- binary flat index (faiss.IndexBinaryFlat)
 _INT32_MAX = int(np.iinfo(np.int32).max)
@@ -1481,11 +1416,7 @@ class IndexBinaryFlat(_RemovableIndex):
         self._lock = threading.Lock()
         _n.check(_n.lib.ise_binary_index_create(ctypes.byref(self._h), self.d, self.device))
 
-    @property
-    def ntotal(self) -> int:
-        n = ctypes.c_int64(0)
-        _n.check(_n.lib.ise_binary_index_info(self._h, None, ctypes.byref(n), None))
-        return int(n.value)
+    ntotal = _ntotal_property(_n.lib.ise_binary_index_info, 4, 2)
 
     def binary_stats(self) -> dict:
         """Search batches, scan passes launched (one per 16 queries and per 32 results), range batches
@@ -1584,6 +1515,8 @@ class IndexBinaryFlat(_RemovableIndex):
 #   (= ntotal * code_size); count bytes.
 _FOURCC_BINARY = b"IBxF"
 _BHDR = struct.Struct("<4siiqBi")
+_BinaryFlatParts = namedtuple("_BinaryFlatParts", "d xb")
+_BinaryIDMapParts = namedtuple("_BinaryIDMapParts", "d xb ids")
 
 
 def serialize_binary_flat(d: int, xb) -> bytes:
@@ -1592,24 +1525,22 @@ def serialize_binary_flat(d: int, xb) -> bytes:
     cs = d // 8
     xb = np.asarray(xb, dtype=np.uint8)
     xb = _as_codes(xb.reshape(-1, cs), cs)
-    n = xb.shape[0]
-    return _BHDR.pack(_FOURCC_BINARY, d, cs, n, 1, 1) + struct.pack("<Q", n * cs) + xb.tobytes()
+    return _BHDR.pack(_FOURCC_BINARY, d, cs, xb.shape[0], 1, 1) + _pack_vector(xb)
+
+
+def _parse_binary_flat_at(cur: _Cursor) -> _BinaryFlatParts:
+    cur.expect(_FOURCC_BINARY, "IndexBinaryFlat")
+    _, d, cs, n, _, _ = cur.take(_BHDR, "truncated binary index file")
+    # the count is part of the header check: a header that is wrong in itself has no right count
+    expect = n * cs if d > 0 and d % 8 == 0 and cs == d // 8 and n >= 0 else -1
+    xb = cur.vector(np.uint8, expect, "corrupt binary flat index header", "truncated binary flat index payload",
+                    "truncated binary index file")
+    return _BinaryFlatParts(d, xb.reshape(n, cs))
 
 
 def parse_binary_flat(buf: bytes):
     """-> (d, xb uint8 (n, d / 8)); raises RuntimeError on a foreign or truncated file."""
-    if len(buf) >= 4 and buf[:4] != _FOURCC_BINARY:
-        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexBinaryFlat")
-    if len(buf) < _BHDR.size + 8:
-        raise RuntimeError("truncated binary index file")
-    _, d, cs, n, _, _ = _BHDR.unpack_from(buf, 0)
-    (count,) = struct.unpack_from("<Q", buf, _BHDR.size)
-    if d <= 0 or d % 8 != 0 or cs != d // 8 or n < 0 or count != n * cs:
-        raise RuntimeError("corrupt binary flat index header")
-    if len(buf) < _BHDR.size + 8 + count:
-        raise RuntimeError("truncated binary flat index payload")
-    xb = np.frombuffer(buf, dtype=np.uint8, count=count, offset=_BHDR.size + 8).reshape(n, cs).copy()
-    return d, xb
+    return tuple(_parse_binary_flat_at(_Cursor(buf)))
 
 
 class IndexBinaryIDMap(_IDMapBase):
@@ -1641,45 +1572,45 @@ def serialize_binary_idmap(d: int, xb, ids) -> bytes:
     return _BHDR.pack(_FOURCC_BINARY_IDMAP, int(d), cs, n, 1, 1) + sub + _pack_id_vector(ids, n)
 
 
-def parse_binary_idmap(buf: bytes):
-    """-> (d, xb uint8 (n, d / 8), ids int64 (n,)); raises RuntimeError on a foreign or truncated file."""
-    if len(buf) >= 4 and buf[:4] != _FOURCC_BINARY_IDMAP:
-        raise RuntimeError(f"unsupported index type {bytes(buf[:4])!r}: not an IndexBinaryIDMap")
-    if len(buf) < _BHDR.size:
-        raise RuntimeError("truncated binary index file")
-    _, d, cs, n, _, _ = _BHDR.unpack_from(buf, 0)
-    d2, xb = parse_binary_flat(buf[_BHDR.size:])
+def _parse_binary_idmap_at(cur: _Cursor) -> _BinaryIDMapParts:
+    cur.expect(_FOURCC_BINARY_IDMAP, "IndexBinaryIDMap")
+    _, d, cs, n, _, _ = cur.take(_BHDR, "truncated binary index file")
+    d2, xb = _parse_binary_flat_at(cur)
     if d2 != d or xb.shape[1] != cs or xb.shape[0] != n:
         raise RuntimeError("corrupt IndexBinaryIDMap: the sub-index does not match the header")
-    ids = _parse_id_vector(buf, 2 * _BHDR.size + 8 + n * cs, n, "truncated IndexBinaryIDMap id vector",
-                           "corrupt IndexBinaryIDMap: the id vector does not have one id per row")
-    return d, xb, ids
+    ids = cur.vector(np.int64, n, "corrupt IndexBinaryIDMap: the id vector does not have one id per row",
+                     "truncated IndexBinaryIDMap id vector")
+    return _BinaryIDMapParts(d, xb, ids)
+
+
+def parse_binary_idmap(buf: bytes):
+    """-> (d, xb uint8 (n, d / 8), ids int64 (n,)); raises RuntimeError on a foreign or truncated file."""
+    return tuple(_parse_binary_idmap_at(_Cursor(buf)))
 
 
 def write_index_binary(index, path) -> None:
-    with open(str(path), "wb") as f:
-        if isinstance(index, IndexBinaryIDMap):
-            sub = index.index
-            f.write(serialize_binary_idmap(sub.d, sub.reconstruct_n(0, sub.ntotal), index.id_map))
-        else:
-            f.write(serialize_binary_flat(index.d, index.reconstruct_n(0, index.ntotal)))
+    if isinstance(index, IndexBinaryIDMap):
+        sub = index.index
+        image = serialize_binary_idmap(sub.d, sub.reconstruct_n(0, sub.ntotal), index.id_map)
+    else:
+        image = serialize_binary_flat(index.d, index.reconstruct_n(0, index.ntotal))
+    with open(str(path), "wb") as f:  # after the image, as ``write_index``
+        f.write(image)
 
 
 def read_index_binary(path, device: int | None = None):
     """-> IndexBinaryFlat, or IndexBinaryIDMap for a file written from one."""
     with open(str(path), "rb") as f:
         buf = f.read()
-    ids = None
     if buf[:4] == _FOURCC_BINARY_IDMAP:
-        d, xb, ids = parse_binary_idmap(buf)
-    else:
-        d, xb = parse_binary_flat(buf)
-    index = IndexBinaryFlat(d, device)
-    if ids is not None:
-        index = IndexBinaryIDMap(index)
+        d, xb, ids = _parse_binary_idmap_at(_Cursor(buf))
+        index = IndexBinaryIDMap(IndexBinaryFlat(d, device))
         if xb.shape[0]:
             index.add_with_ids(xb, ids)
-    elif xb.shape[0]:
+        return index
+    d, xb = _parse_binary_flat_at(_Cursor(buf))
+    index = IndexBinaryFlat(d, device)
+    if xb.shape[0]:
         index.add(xb)
     return index
 
@@ -1785,9 +1716,16 @@ class ClusteringParameters:
 
 class _IndexIVF(_IndexHandle):
     """What the inverted-list indexes share: the caller's coarse quantiser (an ``IndexFlat`` of ``nlist`` centroids),
-    its clustering in ``train``, the assignment of rows to lists, ``nprobe`` and ``search`` as ``search_preassigned`` of
-    the quantiser's answer.  A subclass creates its handle, sets ``is_trained`` and provides ``search_preassigned`` and
-    the device call of ``search_torch`` (``_search_device``)."""
+    its clustering in ``train``, the assignment of rows to lists, ``add``, ``get_list``, ``nprobe`` and ``search`` as
+    ``search_preassigned`` of the quantiser's answer.  A subclass creates its handle, says what ``is_trained`` is and
+    names its family of entry points (``_ABI``), the two search calls outright (``_search_host``, ``_search_device``),
+    its ``ntotal``, the dtype of a list's payload of (m, d) entries (``_LIST_DTYPE``) and whether it encodes its rows
+    (``_ENCODES``).  An index that does checks the rows of an ``add`` for NaN / inf entries, needs its training in
+    ``search_preassigned`` too and answers an empty batch there itself, and has no lists to read while its codec is
+    untrained."""
+
+    _LIST_DTYPE = np.float32
+    _ENCODES = False
 
     def _init_ivf(self, quantizer: IndexFlat, d: int, nlist: int, metric: int) -> None:
         assert isinstance(quantizer, IndexFlat), "the coarse quantiser is an IndexFlat"
@@ -1822,6 +1760,13 @@ class _IndexIVF(_IndexHandle):
         if not self.is_trained:
             raise RuntimeError(f"{type(self).__name__}.{what} before train")
 
+    def _codec_trained(self) -> bool:
+        return True
+
+    def reset(self) -> None:
+        """Drop the rows; the quantiser, a codec's trained state (and ``is_trained``) stay."""
+        _n.check(self._fn("reset")(self._h))
+
     def _check_assignment(self, lists: np.ndarray) -> None:
         bad = np.flatnonzero(lists < 0)
         if bad.size:
@@ -1842,10 +1787,52 @@ class _IndexIVF(_IndexHandle):
         self._check_assignment(lists.cpu().numpy())
         return lists
 
+    # -- build side
+    def add(self, x) -> None:
+        """Append rows (copied; encoded by an index that encodes); row i of the call goes to list
+        ``quantizer.search(x, 1)[1][i]``.  On an index that encodes, a row with a NaN or inf entry raises ``ValueError``
+        and nothing of the call is added."""
+        self._require_trained("add")
+        x = _as_rows(x, self.d)
+        if x.shape[0] == 0:
+            return
+        lists = self._assign(x)
+        (_check_rows if self._ENCODES else _n.check)(
+            self._fn("add_host")(self._h, x.ctypes.data, lists.ctypes.data, x.shape[0]))
+
+    def add_torch(self, x) -> None:
+        """``add`` from a CUDA float32 tensor on this index's device (no host hop for the rows; the list numbers are
+        read back to be checked, and an index that encodes waits for the encoder's verdict on non-finite entries).
+        Under the index's lock, like every device call that names a stream."""
+        import torch
+
+        self._require_trained("add")
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
+        x = x.contiguous()
+        n = x.shape[0]
+        if n == 0:
+            return
+        lists = self._assign_torch(x)
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        with self._lock:
+            (_check_rows if self._ENCODES else _n.check)(
+                self._fn("add_device")(self._h, x.data_ptr(), lists.data_ptr(), n, st))
+
+    # -- lists
     def list_size(self, l: int) -> int:
         sizes = np.zeros(self.nlist, dtype=np.int64)
         _n.check(self._fn("list_sizes_host")(self._h, sizes.ctypes.data))
         return int(sizes[int(l)])
+
+    def get_list(self, l: int):
+        """(ids int64 (m,), rows (m, d) -- float32, or the uint8 codes of an index that encodes) of list ``l``, in list
+        order (ascending ids)."""
+        m = self.list_size(l)
+        ids = np.empty(m, dtype=np.int64)
+        rows = np.empty((m, self.d), dtype=self._LIST_DTYPE)
+        if self._codec_trained():
+            _n.check(self._fn("list_host")(self._h, int(l), ids.ctypes.data, rows.ctypes.data))
+        return ids, rows
 
     # -- query side
     def _nprobe(self) -> int:
@@ -1864,6 +1851,23 @@ class _IndexIVF(_IndexHandle):
         if x.shape[0] == 0:
             return np.empty((0, int(k)), dtype=np.float32), np.empty((0, int(k)), dtype=np.int64)
         return self.search_preassigned(x, k, self.quantizer.search(x, self._nprobe())[1])
+
+    def search_preassigned(self, x, k: int, probes):
+        """``search`` with the probed lists given: ``probes`` int64 (nq, nprobe); -1 entries are ignored."""
+        if self._ENCODES:
+            self._require_trained("search")
+        x = _as_rows(x, self.d)
+        k = int(k)
+        assert k > 0
+        nq = x.shape[0]
+        probes = np.ascontiguousarray(np.asarray(probes), dtype=np.int64)
+        assert probes.ndim == 2 and probes.shape[0] == nq and probes.shape[1] >= 1
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        if nq or not self._ENCODES:  # (the float family checks k and the probes of an empty batch too)
+            _n.check(self._search_host(self._h, x.ctypes.data, nq, k, probes.ctypes.data, probes.shape[1],
+                                       D.ctypes.data, I.ctypes.data))
+        return D, I
 
     def search_torch(self, xq, k: int, params=None):
         """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out; the quantiser's search and the scan are
@@ -1907,24 +1911,15 @@ class IndexIVFFlat(_IndexIVF):
     ``IndexIDMap`` over this type."""
 
     _ABI = "ise_ivf"
+    _search_host = staticmethod(_n.lib.ise_ivf_search_host)
     _search_device = staticmethod(_n.lib.ise_ivf_search_device)
+    ntotal = _ntotal_property(_n.lib.ise_ivf_info, 6, 4)
 
     def __init__(self, quantizer: IndexFlat, d: int, nlist: int, metric: int = METRIC_L2):
         self._init_ivf(quantizer, d, nlist, metric)
         _n.check(_n.lib.ise_ivf_create(ctypes.byref(self._h), self.d, self.metric_type, self.nlist, self.device))
         self.is_trained = quantizer.ntotal == self.nlist
 
-    @property
-    def ntotal(self) -> int:
-        n = ctypes.c_int64(0)
-        _n.check(_n.lib.ise_ivf_info(self._h, None, None, None, ctypes.byref(n), None))
-        return int(n.value)
-
-    def reset(self) -> None:
-        """Drop the rows; the quantiser (and ``is_trained``) stay."""
-        _n.check(_n.lib.ise_ivf_reset(self._h))
-
-    # -- build side
     def train(self, x) -> None:
         """A no-op when the quantiser already holds ``nlist`` centroids.  With an empty quantiser: ``Kmeans(d, nlist)``
         on ``x`` (spherical when the quantiser is an inner-product index), ``niter`` and ``seed`` from ``self.cp``, and
@@ -1933,58 +1928,10 @@ class IndexIVFFlat(_IndexIVF):
         self._train_quantizer(x)
         self.is_trained = True
 
-    def add(self, x) -> None:
-        """Append rows (copied); row i of the call goes to list ``quantizer.search(x, 1)[1][i]``."""
-        self._require_trained("add")
-        x = _as_rows(x, self.d)
-        if x.shape[0] == 0:
-            return
-        lists = self._assign(x)
-        _n.check(_n.lib.ise_ivf_add_host(self._h, x.ctypes.data, lists.ctypes.data, x.shape[0]))
-
-    def add_torch(self, x) -> None:
-        """Append rows from a CUDA float32 tensor on this index's device (the rows make no host hop; the list numbers
-        are read back to be checked)."""
-        import torch
-
-        self._require_trained("add")
-        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
-        x = x.contiguous()
-        n = x.shape[0]
-        if n == 0:
-            return
-        lists = self._assign_torch(x)
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        _n.check(_n.lib.ise_ivf_add_device(self._h, x.data_ptr(), lists.data_ptr(), n, st))
-
-    # -- lists
-    def get_list(self, l: int):
-        """(ids int64 (m,), rows float32 (m, d)) of list ``l``, in list order (ascending ids)."""
-        m = self.list_size(l)
-        ids = np.empty(m, dtype=np.int64)
-        rows = np.empty((m, self.d), dtype=np.float32)
-        _n.check(_n.lib.ise_ivf_list_host(self._h, int(l), ids.ctypes.data, rows.ctypes.data))
-        return ids, rows
-
     def ivf_stats(self) -> dict:
         """Search batches, scan passes launched, 16-row tiles of list rows the passes loaded (include/ise_knn.h,
         ise_ivf_stats).  Waits for the device."""
         return _counters(_n.lib.ise_ivf_stats, self._h, ("batches", "passes", "tiles_loaded"))
-
-    # -- query side
-    def search_preassigned(self, x, k: int, probes):
-        """``search`` with the probed lists given: ``probes`` int64 (nq, nprobe); -1 entries are ignored."""
-        x = _as_rows(x, self.d)
-        k = int(k)
-        assert k > 0
-        nq = x.shape[0]
-        probes = np.ascontiguousarray(np.asarray(probes), dtype=np.int64)
-        assert probes.ndim == 2 and probes.shape[0] == nq and probes.shape[1] >= 1
-        D = np.empty((nq, k), dtype=np.float32)
-        I = np.empty((nq, k), dtype=np.int64)
-        _n.check(_n.lib.ise_ivf_search_host(self._h, x.ctypes.data, nq, k, probes.ctypes.data, probes.shape[1],
-                                            D.ctypes.data, I.ctypes.data))
-        return D, I
 
 
 # ---------------------------------------------------------------- product quantisation (faiss.IndexPQ)
@@ -2024,7 +1971,131 @@ class ProductQuantizer:
         return self._index.sa_decode(codes)
 
 
-class IndexPQ(_IndexHandle):
+def _check_rows(rc: int) -> None:
+    """The library's answer to rows with a NaN or inf entry is a ValueError here, as ``IndexIVFFlat.add`` gives."""
+    if rc == _n.E_INVALID and b"NaN or inf" in _n.lib.ise_last_error():
+        raise ValueError(_n.lib.ise_last_error().decode("utf-8", "replace"))
+    _n.check(rc)
+
+
+class _CodedIndex(_IndexHandle):
+    """What ``IndexPQ`` and ``IndexScalarQuantizer`` share above their handles: float32 rows go in, ``code_size`` bytes per
+    row are kept (``M`` for a product quantiser, ``d`` for a scalar one), and everything but ``train`` is the same call
+    into the family of entry points ``_ABI`` names.  A subclass names its two search entry points outright
+    (``_search_host``, ``_search_device``), its ``ntotal`` and what a ``params=`` argument cannot carry."""
+
+    _NO_PARAMS = ""
+
+    def reset(self) -> None:
+        """Drop the rows; the codec's state (and ``is_trained``) stay."""
+        _n.check(self._fn("reset")(self._h))
+
+    def _require_trained(self, what: str) -> None:
+        if not self.is_trained:
+            raise RuntimeError(f"{type(self).__name__}.{what} before train")
+
+    # -- build side
+    def add(self, x) -> None:
+        """Encode and append rows; a row with a NaN or inf entry raises ``ValueError`` and nothing of the call is
+        added."""
+        self._require_trained("add")
+        x = _as_rows(x, self.d)
+        _check_rows(self._fn("add_host")(self._h, x.ctypes.data, x.shape[0]))
+
+    def add_torch(self, x) -> None:
+        """``add`` from a CUDA float32 tensor on this index's device (no host hop for the rows; the call waits for the
+        encoder's verdict on non-finite entries)."""
+        import torch
+
+        self._require_trained("add")
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
+        x = x.contiguous()
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        with self._lock:
+            _check_rows(self._fn("add_device")(self._h, x.data_ptr(), x.shape[0], st))
+
+    def _add_codes(self, codes: np.ndarray) -> None:
+        codes = _as_codes(codes, self.code_size)
+        _n.check(self._fn("add_codes_host")(self._h, codes.ctypes.data, codes.shape[0]))
+
+    # -- readback and codec
+    @property
+    def codes(self) -> np.ndarray:
+        """uint8 (ntotal, code_size), a copy."""
+        out = np.empty((self.ntotal, self.code_size), dtype=np.uint8)
+        _n.check(self._fn("codes_host")(self._h, 0, out.shape[0], out.ctypes.data))
+        return out
+
+    def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
+        n = self.ntotal - i0 if n is None else n
+        out = np.empty((n, self.d), dtype=np.float32)
+        _n.check(self._fn("reconstruct_host")(self._h, int(i0), int(n), out.ctypes.data))
+        return out
+
+    def reconstruct(self, i: int) -> np.ndarray:
+        return self.reconstruct_n(int(i), 1)[0]
+
+    def sa_code_size(self) -> int:
+        return self.code_size
+
+    def sa_encode(self, x) -> np.ndarray:
+        """uint8 (n, code_size): the codes ``add`` would store."""
+        self._require_trained("sa_encode")
+        x = _as_rows(x, self.d)
+        out = np.empty((x.shape[0], self.code_size), dtype=np.uint8)
+        _check_rows(self._fn("encode_host")(self._h, x.ctypes.data, x.shape[0], out.ctypes.data))
+        return out
+
+    def sa_decode(self, codes) -> np.ndarray:
+        """float32 (n, d): the rows the codes stand for -- the concatenation of the centroids a product quantiser's code
+        names; entry j ``fmaf(codes[i, j] + 0.5, s_j, vmin_j)`` for a scalar quantiser."""
+        self._require_trained("sa_decode")
+        codes = _as_codes(codes, self.code_size)
+        out = np.empty((codes.shape[0], self.d), dtype=np.float32)
+        _n.check(self._fn("decode_host")(self._h, codes.ctypes.data, codes.shape[0], out.ctypes.data))
+        return out
+
+    # -- query side
+    def search(self, x, k: int, params=None):
+        """(D float32 (nq,k), I int64 (nq,k)), fresh arrays."""
+        if params is not None:
+            raise NotImplementedError(f"search parameters ({self._NO_PARAMS}) are not provided on {type(self).__name__}")
+        self._require_trained("search")
+        x = _as_rows(x, self.d)
+        k = int(k)
+        assert k > 0
+        nq = x.shape[0]
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        if nq:
+            _n.check(self._search_host(self._h, x.ctypes.data, nq, k, D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def search_torch(self, xq, k: int, params=None):
+        """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out, enqueued on the current torch stream (no
+        host synchronisation)."""
+        import torch
+
+        if params is not None:
+            raise NotImplementedError(f"search parameters ({self._NO_PARAMS}) are not provided on {type(self).__name__}")
+        self._require_trained("search")
+        k = int(k)
+        xq, D, I, st = _torch_io(xq, torch.float32, self.d, k, torch.float32)
+        nq = xq.shape[0]
+        if nq == 0:
+            return D, I
+        with self._lock:
+            _n.check(self._search_device(self._h, xq.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(), st))
+        return D, I
+
+    def range_search(self, *a, **kw):
+        raise NotImplementedError(f"range_search is not provided on {type(self).__name__}")
+
+    def remove_ids(self, *a, **kw):
+        raise NotImplementedError(f"remove_ids is not provided on {type(self).__name__}")
+
+
+class IndexPQ(_CodedIndex):
     """faiss.IndexPQ(d, M, nbits=8, metric): every row is kept as ``M`` bytes, byte m the number of the centroid (of 256,
     trained per sub-quantiser) nearest to the row's m-th sub-vector of ``d / M`` entries in squared L2, the lowest number
     among equals -- for inner-product indexes too, as in Faiss.  ``search`` scores a row from per-query lookup tables
@@ -2039,6 +2110,10 @@ class IndexPQ(_IndexHandle):
 
     _ABI = "ise_pq"
     TRAIN_MAX_ROWS = 256 * 256  # Faiss's max_points_per_centroid x ksub
+    _NO_PARAMS = "selectors, polysemous search"
+    _search_host = staticmethod(_n.lib.ise_pq_search_host)
+    _search_device = staticmethod(_n.lib.ise_pq_search_device)
+    ntotal = _ntotal_property(_n.lib.ise_pq_info, 8, 5)
 
     def __init__(self, d: int, M: int, nbits: int = 8, metric: int = METRIC_L2, device: int | None = None):
         if int(nbits) != 8:
@@ -2054,15 +2129,17 @@ class IndexPQ(_IndexHandle):
         _n.check(_n.lib.ise_pq_create(ctypes.byref(self._h), self.d, self.M, 8, self.metric_type, self.device))
         self.pq = ProductQuantizer(self)
 
-    @property
-    def ntotal(self) -> int:
-        n = ctypes.c_int64(0)
-        _n.check(_n.lib.ise_pq_info(self._h, None, None, None, None, ctypes.byref(n), None, None))
-        return int(n.value)
+    @classmethod
+    def _from_parts(cls, parts, device, add_codes: bool = True):
+        """The index a parsed "IxPq" image describes (``parse_pq``); the stored codes are added as they are."""
+        index = cls(parts.d, parts.M, parts.nbits, parts.metric, device)
+        index.pq.set_centroids(parts.centroids)
+        if add_codes:
+            index._add_codes(parts.codes)
+        return index
 
-    def reset(self) -> None:
-        """Drop the rows; the codebook (and ``is_trained``) stay."""
-        _n.check(_n.lib.ise_pq_reset(self._h))
+    def _image(self) -> bytes:
+        return serialize_pq(self.d, self.metric_type, self.pq.centroids, self.codes)
 
     def pq_stats(self) -> dict:
         """Search batches, scan passes (one per QT(M) queries and 32 results), table builds (one per 64 queries), bytes
@@ -2091,115 +2168,6 @@ class IndexPQ(_IndexHandle):
             c[m] = km.centroids
         self.pq.set_centroids(c)
 
-    def _require_trained(self, what: str) -> None:
-        if not self.is_trained:
-            raise RuntimeError(f"IndexPQ.{what} before train")
-
-    @staticmethod
-    def _check_rows(rc: int) -> None:
-        """The library's answer to rows with a NaN or inf entry is a ValueError here, as ``IndexIVFFlat.add`` gives."""
-        if rc == _n.E_INVALID and b"NaN or inf" in _n.lib.ise_last_error():
-            raise ValueError(_n.lib.ise_last_error().decode("utf-8", "replace"))
-        _n.check(rc)
-
-    def add(self, x) -> None:
-        """Encode and append rows; a row with a NaN or inf entry raises ``ValueError`` and nothing of the call is
-        added."""
-        self._require_trained("add")
-        x = _as_rows(x, self.d)
-        self._check_rows(_n.lib.ise_pq_add_host(self._h, x.ctypes.data, x.shape[0]))
-
-    def add_torch(self, x) -> None:
-        """``add`` from a CUDA float32 tensor on this index's device (no host hop for the rows; the call waits for the
-        encoder's verdict on non-finite entries)."""
-        import torch
-
-        self._require_trained("add")
-        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
-        x = x.contiguous()
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        with self._lock:
-            self._check_rows(_n.lib.ise_pq_add_device(self._h, x.data_ptr(), x.shape[0], st))
-
-    def _add_codes(self, codes: np.ndarray) -> None:
-        codes = _as_codes(codes, self.M)
-        _n.check(_n.lib.ise_pq_add_codes_host(self._h, codes.ctypes.data, codes.shape[0]))
-
-    # -- readback and codec
-    @property
-    def codes(self) -> np.ndarray:
-        """uint8 (ntotal, M), a copy."""
-        out = np.empty((self.ntotal, self.M), dtype=np.uint8)
-        _n.check(_n.lib.ise_pq_codes_host(self._h, 0, out.shape[0], out.ctypes.data))
-        return out
-
-    def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
-        n = self.ntotal - i0 if n is None else n
-        out = np.empty((n, self.d), dtype=np.float32)
-        _n.check(_n.lib.ise_pq_reconstruct_host(self._h, int(i0), int(n), out.ctypes.data))
-        return out
-
-    def reconstruct(self, i: int) -> np.ndarray:
-        return self.reconstruct_n(int(i), 1)[0]
-
-    def sa_code_size(self) -> int:
-        return self.code_size
-
-    def sa_encode(self, x) -> np.ndarray:
-        """uint8 (n, M): the codes ``add`` would store."""
-        self._require_trained("sa_encode")
-        x = _as_rows(x, self.d)
-        out = np.empty((x.shape[0], self.M), dtype=np.uint8)
-        self._check_rows(_n.lib.ise_pq_encode_host(self._h, x.ctypes.data, x.shape[0], out.ctypes.data))
-        return out
-
-    def sa_decode(self, codes) -> np.ndarray:
-        """float32 (n, d): row i is the concatenation of the centroids its code names."""
-        self._require_trained("sa_decode")
-        codes = _as_codes(codes, self.M)
-        out = np.empty((codes.shape[0], self.d), dtype=np.float32)
-        _n.check(_n.lib.ise_pq_decode_host(self._h, codes.ctypes.data, codes.shape[0], out.ctypes.data))
-        return out
-
-    # -- query side
-    def search(self, x, k: int, params=None):
-        """(D float32 (nq,k), I int64 (nq,k)), fresh arrays."""
-        if params is not None:
-            raise NotImplementedError("search parameters (selectors, polysemous search) are not provided on IndexPQ")
-        self._require_trained("search")
-        x = _as_rows(x, self.d)
-        k = int(k)
-        assert k > 0
-        nq = x.shape[0]
-        D = np.empty((nq, k), dtype=np.float32)
-        I = np.empty((nq, k), dtype=np.int64)
-        if nq:
-            _n.check(_n.lib.ise_pq_search_host(self._h, x.ctypes.data, nq, k, D.ctypes.data, I.ctypes.data))
-        return D, I
-
-    def search_torch(self, xq, k: int, params=None):
-        """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out, enqueued on the current torch stream (no
-        host synchronisation)."""
-        import torch
-
-        if params is not None:
-            raise NotImplementedError("search parameters (selectors, polysemous search) are not provided on IndexPQ")
-        self._require_trained("search")
-        k = int(k)
-        xq, D, I, st = _torch_io(xq, torch.float32, self.d, k, torch.float32)
-        nq = xq.shape[0]
-        if nq == 0:
-            return D, I
-        with self._lock:
-            _n.check(_n.lib.ise_pq_search_device(self._h, xq.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(), st))
-        return D, I
-
-    def range_search(self, *a, **kw):
-        raise NotImplementedError("range_search is not provided on IndexPQ")
-
-    def remove_ids(self, *a, **kw):
-        raise NotImplementedError("remove_ids is not provided on IndexPQ")
-
 
 # ---------------------------------------------------------------- scalar quantisation (faiss.IndexScalarQuantizer)
 class ScalarQuantizer:
@@ -2225,11 +2193,35 @@ class ScalarQuantizer:
 
     @property
     def trained(self) -> np.ndarray:
-        if not getattr(self._index, "_sq_trained", self._index.is_trained):  # (an IVF index is trained with its quantiser)
+        if not self._index._codec_trained():
             return np.zeros(0, dtype=np.float32)
         out = np.empty(self._trained_size, dtype=np.float32)
         _n.check(self._index._fn("get_trained_host")(self._index._h, out.ctypes.data))
         return out
+
+    def train(self, x) -> None:
+        """Nothing when the state is set.  Otherwise vmin = the minimum and vdiff = maximum - minimum of the training
+        rows, per dimension or (uniform) over everything: Faiss's ``RS_minmax`` with ``rangestat_arg = 0``; any other
+        setting of ``rangestat`` / ``rangestat_arg`` raises ``NotImplementedError``.  A NaN or inf entry raises
+        ``ValueError``."""
+        if self._index._codec_trained():
+            return
+        if self.rangestat != self.RS_minmax or float(self.rangestat_arg) != 0.0:
+            raise NotImplementedError("only rangestat = RS_minmax with rangestat_arg = 0 is provided")
+        x = _as_rows(x, self.d)
+        if x.shape[0] == 0:
+            raise RuntimeError("no training rows")
+        if not np.isfinite(x).all():
+            raise ValueError("a training row has a NaN or inf entry")
+        if self.qtype == self.QT_8bit_uniform:
+            vmin, vmax = np.float32(x.min()), np.float32(x.max())
+            t = np.array([vmin, vmax - vmin], dtype=np.float32)
+        else:
+            vmin = x.min(axis=0)
+            t = np.concatenate([vmin, x.max(axis=0) - vmin]).astype(np.float32)
+        if not np.isfinite(t).all():
+            raise ValueError("the range of the training rows overflows float32")
+        self.set_trained(t)
 
     def set_trained(self, t) -> None:
         """float32 ``[vmin.., vdiff..]``, finite, no negative ``vdiff``; refused while the index holds rows (their codes
@@ -2252,7 +2244,7 @@ class ScalarQuantizer:
         return self._index.sa_decode(codes)
 
 
-class IndexScalarQuantizer(_IndexHandle):
+class IndexScalarQuantizer(_CodedIndex):
     """faiss.IndexScalarQuantizer(d, qtype, metric) for ``ScalarQuantizer.QT_8bit`` (a minimum and a range per dimension)
     and ``QT_8bit_uniform`` (one of each for all): every row is kept as ``d`` bytes, byte j =
     ``min(255, max(0, floor((x_j - vmin_j) / s_j)))`` with the step ``s_j = vdiff_j / 255`` (0 where the step is 0), all in
@@ -2268,6 +2260,10 @@ class IndexScalarQuantizer(_IndexHandle):
     ``remove_ids``, ``params=`` and ``IndexIDMap`` over this type."""
 
     _ABI = "ise_sq"
+    _NO_PARAMS = "selectors"
+    _search_host = staticmethod(_n.lib.ise_sq_search_host)
+    _search_device = staticmethod(_n.lib.ise_sq_search_device)
+    ntotal = _ntotal_property(_n.lib.ise_sq_info, 7, 4)
 
     def __init__(self, d: int, qtype: int = ScalarQuantizer.QT_8bit, metric: int = METRIC_L2, device: int | None = None):
         if int(qtype) not in ScalarQuantizer._PROVIDED:
@@ -2283,18 +2279,20 @@ class IndexScalarQuantizer(_IndexHandle):
         _n.check(_n.lib.ise_sq_create(ctypes.byref(self._h), self.d, self.qtype, self.metric_type, self.device))
         self.sq = ScalarQuantizer(self)
 
+    def _codec_trained(self) -> bool:  # what ``sq`` asks its owner
+        return self.is_trained
+
     def _trained_set(self) -> None:  # ScalarQuantizer.set_trained has set the state
         self.is_trained = True
 
     @classmethod
     def _from_parts(cls, parts, device, add_codes: bool = True):
         """The index a parsed "IxSQ" image describes (``parse_sq``); the stored codes are added as they are."""
-        d, metric, qtype, rangestat, rangestat_arg, trained, codes = parts
-        index = cls(d, qtype, metric, device)
-        index.sq.rangestat, index.sq.rangestat_arg = rangestat, rangestat_arg
-        index.sq.set_trained(trained)
+        index = cls(parts.d, parts.qtype, parts.metric, device)
+        index.sq.rangestat, index.sq.rangestat_arg = parts.rangestat, parts.rangestat_arg
+        index.sq.set_trained(parts.trained)
         if add_codes:
-            index._add_codes(codes)
+            index._add_codes(parts.codes)
         return index
 
     def _image(self) -> bytes:
@@ -2302,149 +2300,14 @@ class IndexScalarQuantizer(_IndexHandle):
         return serialize_sq(self.d, self.metric_type, self.qtype, self.sq.trained, self.codes, self.sq.rangestat,
                             self.sq.rangestat_arg)
 
-    @property
-    def ntotal(self) -> int:
-        n = ctypes.c_int64(0)
-        _n.check(_n.lib.ise_sq_info(self._h, None, None, None, ctypes.byref(n), None, None))
-        return int(n.value)
-
-    def reset(self) -> None:
-        """Drop the rows; the trained state (and ``is_trained``) stay."""
-        _n.check(_n.lib.ise_sq_reset(self._h))
-
     def sq_stats(self) -> dict:
         """Search batches, scan passes (one per QT(d) queries and 32 results), bytes of code storage allocated on the
         device (include/ise_knn.h, ise_sq_stats)."""
         return _counters(_n.lib.ise_sq_stats, self._h, ("search_batches", "scan_passes", "code_bytes"))
 
-    # -- build side
     def train(self, x) -> None:
-        """A no-op when trained.  Otherwise vmin = the minimum and vdiff = maximum - minimum of the training rows, per
-        dimension or (uniform) over everything: Faiss's ``RS_minmax`` with ``rangestat_arg = 0``; any other setting of
-        ``sq.rangestat`` / ``sq.rangestat_arg`` raises ``NotImplementedError``.  A NaN or inf entry raises
-        ``ValueError``."""
-        if self.is_trained:
-            return
-        if self.sq.rangestat != ScalarQuantizer.RS_minmax or float(self.sq.rangestat_arg) != 0.0:
-            raise NotImplementedError("only rangestat = RS_minmax with rangestat_arg = 0 is provided")
-        x = _as_rows(x, self.d)
-        if x.shape[0] == 0:
-            raise RuntimeError("no training rows")
-        if not np.isfinite(x).all():
-            raise ValueError("a training row has a NaN or inf entry")
-        if self.qtype == ScalarQuantizer.QT_8bit_uniform:
-            vmin, vmax = np.float32(x.min()), np.float32(x.max())
-            t = np.array([vmin, vmax - vmin], dtype=np.float32)
-        else:
-            vmin = x.min(axis=0)
-            t = np.concatenate([vmin, x.max(axis=0) - vmin]).astype(np.float32)
-        if not np.isfinite(t).all():
-            raise ValueError("the range of the training rows overflows float32")
-        self.sq.set_trained(t)
-
-    def _require_trained(self, what: str) -> None:
-        if not self.is_trained:
-            raise RuntimeError(f"IndexScalarQuantizer.{what} before train")
-
-    _check_rows = staticmethod(IndexPQ._check_rows)
-
-    def add(self, x) -> None:
-        """Encode and append rows; a row with a NaN or inf entry raises ``ValueError`` and nothing of the call is
-        added."""
-        self._require_trained("add")
-        x = _as_rows(x, self.d)
-        self._check_rows(_n.lib.ise_sq_add_host(self._h, x.ctypes.data, x.shape[0]))
-
-    def add_torch(self, x) -> None:
-        """``add`` from a CUDA float32 tensor on this index's device (no host hop for the rows; the call waits for the
-        encoder's verdict on non-finite entries)."""
-        import torch
-
-        self._require_trained("add")
-        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
-        x = x.contiguous()
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        with self._lock:
-            self._check_rows(_n.lib.ise_sq_add_device(self._h, x.data_ptr(), x.shape[0], st))
-
-    def _add_codes(self, codes: np.ndarray) -> None:
-        codes = _as_codes(codes, self.d)
-        _n.check(_n.lib.ise_sq_add_codes_host(self._h, codes.ctypes.data, codes.shape[0]))
-
-    # -- readback and codec
-    @property
-    def codes(self) -> np.ndarray:
-        """uint8 (ntotal, d), a copy."""
-        out = np.empty((self.ntotal, self.d), dtype=np.uint8)
-        _n.check(_n.lib.ise_sq_codes_host(self._h, 0, out.shape[0], out.ctypes.data))
-        return out
-
-    def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
-        n = self.ntotal - i0 if n is None else n
-        out = np.empty((n, self.d), dtype=np.float32)
-        _n.check(_n.lib.ise_sq_reconstruct_host(self._h, int(i0), int(n), out.ctypes.data))
-        return out
-
-    def reconstruct(self, i: int) -> np.ndarray:
-        return self.reconstruct_n(int(i), 1)[0]
-
-    def sa_code_size(self) -> int:
-        return self.code_size
-
-    def sa_encode(self, x) -> np.ndarray:
-        """uint8 (n, d): the codes ``add`` would store."""
-        self._require_trained("sa_encode")
-        x = _as_rows(x, self.d)
-        out = np.empty((x.shape[0], self.d), dtype=np.uint8)
-        self._check_rows(_n.lib.ise_sq_encode_host(self._h, x.ctypes.data, x.shape[0], out.ctypes.data))
-        return out
-
-    def sa_decode(self, codes) -> np.ndarray:
-        """float32 (n, d): entry j of row i is ``fmaf(codes[i, j] + 0.5, s_j, vmin_j)``."""
-        self._require_trained("sa_decode")
-        codes = _as_codes(codes, self.d)
-        out = np.empty((codes.shape[0], self.d), dtype=np.float32)
-        _n.check(_n.lib.ise_sq_decode_host(self._h, codes.ctypes.data, codes.shape[0], out.ctypes.data))
-        return out
-
-    # -- query side
-    def search(self, x, k: int, params=None):
-        """(D float32 (nq,k), I int64 (nq,k)), fresh arrays."""
-        if params is not None:
-            raise NotImplementedError("search parameters (selectors) are not provided on IndexScalarQuantizer")
-        self._require_trained("search")
-        x = _as_rows(x, self.d)
-        k = int(k)
-        assert k > 0
-        nq = x.shape[0]
-        D = np.empty((nq, k), dtype=np.float32)
-        I = np.empty((nq, k), dtype=np.int64)
-        if nq:
-            _n.check(_n.lib.ise_sq_search_host(self._h, x.ctypes.data, nq, k, D.ctypes.data, I.ctypes.data))
-        return D, I
-
-    def search_torch(self, xq, k: int, params=None):
-        """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out, enqueued on the current torch stream (no
-        host synchronisation)."""
-        import torch
-
-        if params is not None:
-            raise NotImplementedError("search parameters (selectors) are not provided on IndexScalarQuantizer")
-        self._require_trained("search")
-        k = int(k)
-        xq, D, I, st = _torch_io(xq, torch.float32, self.d, k, torch.float32)
-        nq = xq.shape[0]
-        if nq == 0:
-            return D, I
-        with self._lock:
-            _n.check(_n.lib.ise_sq_search_device(self._h, xq.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(), st))
-        return D, I
-
-    def range_search(self, *a, **kw):
-        raise NotImplementedError("range_search is not provided on IndexScalarQuantizer")
-
-    def remove_ids(self, *a, **kw):
-        raise NotImplementedError("remove_ids is not provided on IndexScalarQuantizer")
+        """A no-op when trained; otherwise ``sq.train``: vmin / vdiff from the rows' minimum and maximum."""
+        self.sq.train(x)
 
 
 # ---------------------------------------------------------------- inverted lists over 8-bit rows (faiss.IndexIVFScalarQuantizer)
@@ -2468,6 +2331,10 @@ class IndexIVFScalarQuantizer(_IndexIVF):
 
     _ABI = "ise_ivfsq"
     _search_device = staticmethod(_n.lib.ise_ivfsq_search_device)
+    _search_host = staticmethod(_n.lib.ise_ivfsq_search_host)
+    _LIST_DTYPE = np.uint8
+    _ENCODES = True
+    ntotal = _ntotal_property(_n.lib.ise_ivfsq_info, 8, 5)
 
     def __init__(self, quantizer: IndexFlat, d: int, nlist: int, qtype: int = ScalarQuantizer.QT_8bit, metric: int = METRIC_L2,
                  by_residual: bool = True):
@@ -2490,55 +2357,19 @@ class IndexIVFScalarQuantizer(_IndexIVF):
     def is_trained(self) -> bool:
         return self._sq_trained and self.quantizer.ntotal == self.nlist
 
+    def _codec_trained(self) -> bool:  # what ``sq`` asks its owner (the index is trained with its quantiser only)
+        return self._sq_trained
+
     def _trained_set(self) -> None:  # ScalarQuantizer.set_trained has set the state
         self._sq_trained = True
         self._codec = None
-
-    @property
-    def ntotal(self) -> int:
-        n = ctypes.c_int64(0)
-        _n.check(_n.lib.ise_ivfsq_info(self._h, None, None, None, None, ctypes.byref(n), None, None))
-        return int(n.value)
-
-    def reset(self) -> None:
-        """Drop the rows; the quantiser and the trained state (and ``is_trained``) stay."""
-        _n.check(_n.lib.ise_ivfsq_reset(self._h))
 
     # -- build side
     def train(self, x) -> None:
         """The quantiser's k-means as ``IndexIVFFlat.train`` (nothing when it holds ``nlist`` centroids), then vmin /
         vdiff from the rows' minimum and maximum as ``IndexScalarQuantizer.train`` (nothing when the state is set)."""
         self._train_quantizer(x)
-        if not self._sq_trained:
-            IndexScalarQuantizer.train(self, x)
-
-    _check_rows = staticmethod(IndexPQ._check_rows)
-
-    def add(self, x) -> None:
-        """Encode and append rows; row i of the call goes to list ``quantizer.search(x, 1)[1][i]``.  A row with a NaN or
-        inf entry raises ``ValueError`` and nothing of the call is added."""
-        self._require_trained("add")
-        x = _as_rows(x, self.d)
-        if x.shape[0] == 0:
-            return
-        lists = self._assign(x)
-        self._check_rows(_n.lib.ise_ivfsq_add_host(self._h, x.ctypes.data, lists.ctypes.data, x.shape[0]))
-
-    def add_torch(self, x) -> None:
-        """``add`` from a CUDA float32 tensor on this index's device (no host hop for the rows; the list numbers are
-        read back to be checked and the call waits for the encoder's verdict on non-finite entries)."""
-        import torch
-
-        self._require_trained("add")
-        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
-        x = x.contiguous()
-        n = x.shape[0]
-        if n == 0:
-            return
-        lists = self._assign_torch(x)
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        with self._lock:
-            self._check_rows(_n.lib.ise_ivfsq_add_device(self._h, x.data_ptr(), lists.data_ptr(), n, st))
+        self.sq.train(x)
 
     def _add_codes(self, codes: np.ndarray, lists: np.ndarray) -> None:
         codes = _as_codes(codes, self.d)
@@ -2565,16 +2396,6 @@ class IndexIVFScalarQuantizer(_IndexIVF):
 
     def sa_decode(self, codes) -> np.ndarray:
         return self._codec_index().sa_decode(codes)
-
-    # -- lists and statistics
-    def get_list(self, l: int):
-        """(ids int64 (m,), codes uint8 (m, d)) of list ``l``, in list order (ascending ids)."""
-        m = self.list_size(l)
-        ids = np.empty(m, dtype=np.int64)
-        codes = np.empty((m, self.d), dtype=np.uint8)
-        if self._sq_trained:
-            _n.check(_n.lib.ise_ivfsq_list_host(self._h, int(l), ids.ctypes.data, codes.ctypes.data))
-        return ids, codes
 
     def ivfsq_stats(self) -> dict:
         """Search batches, scan passes (one per QT(d) queries and 32 results), 64-row tiles of list rows the passes
@@ -2614,23 +2435,6 @@ class IndexIVFScalarQuantizer(_IndexIVF):
             list_no = np.repeat(np.arange(nlist, dtype=np.int64), [len(ids) for ids, _ in lists])
             index._add_codes(codes[order], list_no[order])
         return index
-
-    # -- query side
-    def search_preassigned(self, x, k: int, probes):
-        """``search`` with the probed lists given: ``probes`` int64 (nq, nprobe); -1 entries are ignored."""
-        self._require_trained("search")
-        x = _as_rows(x, self.d)
-        k = int(k)
-        assert k > 0
-        nq = x.shape[0]
-        probes = np.ascontiguousarray(np.asarray(probes), dtype=np.int64)
-        assert probes.ndim == 2 and probes.shape[0] == nq and probes.shape[1] >= 1
-        D = np.empty((nq, k), dtype=np.float32)
-        I = np.empty((nq, k), dtype=np.int64)
-        if nq:
-            _n.check(_n.lib.ise_ivfsq_search_host(self._h, x.ctypes.data, nq, k, probes.ctypes.data, probes.shape[1],
-                                                  D.ctypes.data, I.ctypes.data))
-        return D, I
 
 
 # ---------------------------------------------------------------- exact re-ranking (faiss.IndexRefine / IndexRefineFlat)
@@ -2729,6 +2533,18 @@ class IndexRefine:
         labels = self.base_index.search_torch(xq, k_base, params=base_params)[1]
         return self.refine_index.search_subset_torch(xq, k, labels)
 
+    def _image(self) -> bytes:
+        base = self.base_index
+        if isinstance(base, _CodedIndex):
+            image = base._image()
+        elif type(base) in (IndexFlat, IndexFlatL2, IndexFlatIP) and base.storage == "f32":
+            image = _flat_image(base)
+        else:
+            raise NotImplementedError(f"write_index of an IndexRefine over {type(base).__name__} is not provided "
+                                      "(float32 IndexFlat, IndexPQ and IndexScalarQuantizer bases are)")
+        rf = self.refine_index
+        return serialize_refine(image, self.d, self.metric_type, rf.reconstruct_n(0, rf.ntotal), self.k_factor)
+
     def range_search(self, *a, **kw):
         raise NotImplementedError("range_search is not provided on IndexRefine")
 
@@ -2742,3 +2558,21 @@ class IndexRefineFlat(IndexRefine):
 
     def __init__(self, base_index):
         super().__init__(base_index, IndexFlat(base_index.d, base_index.metric_type, device=base_index.device))
+
+    @classmethod
+    def _from_parts(cls, parts, device):
+        """The index a parsed "IxRF" image describes (``parse_refine``); each side gets what is stored for it."""
+        kind, stored = parts.base_kind, parts.base
+        if kind == "flat":
+            base = IndexFlat(parts.d, stored.metric, device)
+        else:
+            base = {"pq": IndexPQ, "sq": IndexScalarQuantizer}[kind]._from_parts(stored, device, add_codes=False)
+        index = cls(base)
+        index.k_factor = parts.k_factor
+        if parts.xb.shape[0]:
+            if kind == "flat":
+                base.add(stored.xb)
+            else:
+                base._add_codes(stored.codes)
+            index.refine_index.add(parts.xb)
+        return index

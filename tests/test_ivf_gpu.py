@@ -292,6 +292,46 @@ def test_one_handle_from_two_streams():
         assert np.array_equal(ids, ids2) and np.array_equal(rows.view(np.uint32), rows2.view(np.uint32))
 
 
+def test_add_torch_and_search_torch_from_two_threads():
+    """One thread adds the same 16 rows 20 times with ``add_torch``, another searches with ``search_torch`` meanwhile;
+    both go through the index's lock.  Afterwards the index holds 16 * 20 rows and answers as a fresh index that was
+    given them in one call: the lock changes no result."""
+    import threading
+
+    import torch
+
+    d, nlist, n, rounds = 8, 3, 16, 20
+    rng = np.random.default_rng(53)
+    xb, xq = int_data("small", rng, n, d), int_data("small", rng, 5, d)
+    cent = xb[[0, 5, 11]]
+    _, ivf = build(cent, xb[:0], L2, L2, chunks=[])
+    _, fresh = build(cent, np.tile(xb, (rounds, 1)), L2, L2, chunks=[n * rounds])
+    ivf.nprobe = fresh.nprobe = 2
+    dev = torch.device("cuda", ivf.device)
+    xb_t, xq_t = torch.from_numpy(xb).to(dev), torch.from_numpy(xq).to(dev)
+    torch.cuda.synchronize(dev)
+    errors = []
+
+    def run(call):
+        try:
+            for _ in range(rounds):
+                call()
+            torch.cuda.synchronize(dev)
+        except Exception as e:  # reported by the asserting thread
+            errors.append(e)
+
+    threads = [threading.Thread(target=run, args=(lambda: ivf.add_torch(xb_t),)),
+               threading.Thread(target=run, args=(lambda: ivf.search_torch(xq_t, 4),))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    assert ivf.ntotal == n * rounds
+    D, I = ivf.search_torch(xq_t, 10)
+    assert_knn_identical(D.cpu().numpy(), I.cpu().numpy(), *fresh.search(xq, 10), "after the two threads")
+
+
 def test_work_is_proportional_to_the_probes():
     d = 20
     cent, plan, xb, xq = clustered(d, 3)

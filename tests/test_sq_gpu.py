@@ -362,6 +362,24 @@ def test_write_and_read_index(qtype, metric, tmp_path):
     assert isinstance(back, faiss.IndexScalarQuantizer) and back.is_trained and back.ntotal == 0
 
 
+def test_a_refused_write_leaves_the_file_alone(tmp_path):
+    """``write_index`` builds the image before it opens the file: an untrained index raises and what was written to the
+    same path before is still there, byte for byte."""
+    xb = np.array([[1, 2, 3, 4, 5, 6, 7, 8], [8, 7, 6, 5, 4, 3, 2, 1], [0, 0, 0, 0, 0, 0, 0, 0], [2, 2, 2, 2, 9, 9, 9, 9]],
+                  dtype=np.float32)
+    index = faiss.IndexScalarQuantizer(8)
+    index.train(xb)
+    index.add(xb)
+    path = tmp_path / "sq.index"
+    faiss.write_index(index, str(path))
+    written = path.read_bytes()
+    with pytest.raises(RuntimeError, match="IndexScalarQuantizer.write_index before train"):
+        faiss.write_index(faiss.IndexScalarQuantizer(8), str(path))
+    assert path.read_bytes() == written
+    back = faiss.read_index(str(path))
+    assert back.ntotal == 4 and np.array_equal(back.codes, index.codes)
+
+
 @pytest.mark.parametrize("metric", [L2, IP])
 def test_refine_over_scalar_quantiser(metric, tmp_path):
     rng = np.random.default_rng(41)
