@@ -13,7 +13,7 @@
 // holds the mutex from its device-wide synchronisation to the end of its last copy: other calls on the handle run
 // entirely before or entirely after it.
 #include "ise_binary_scan.hpp"
-#include "ise_host.hpp"
+#include "ise_pass_host.hpp"
 #include "ise_remove.hpp"
 #include "ise_remove_plan.hpp"
 #include "ise_selector.hpp"
@@ -84,11 +84,7 @@ void launch_range(int wt, unsigned grid, size_t lds, hipStream_t st, const BinRa
 }
 
 // blocks of a pass over `tiles` 64-row tiles: about two per wave on a short index, at most two blocks per CU
-unsigned bin_grid_tiles(const ise_binary_index* h, long long tiles) {
-    long long g = (tiles + 2 * BIN_WAVES - 1) / (2 * BIN_WAVES);
-    g = std::min<long long>(g, std::min<long long>(2ll * h->num_cu, MERGE_LISTS_MAX));
-    return (unsigned)std::max<long long>(g, 1);
-}
+unsigned bin_grid_tiles(const ise_binary_index* h, long long tiles) { return coded_grid(tiles, 2, BIN_WAVES, 2, h->num_cu); }
 unsigned bin_grid(const ise_binary_index* h) { return bin_grid_tiles(h, (h->n + 63) / 64); }
 
 // mu held.  A selector is good for the handle it was made from while ntotal and the row epoch stand
@@ -112,29 +108,6 @@ BinMask selector_mask(const ise_binary_selector* sel) {
     return mk;
 }
 
-int reserve_codes(ise_binary_index* h, long long need, hipStream_t st) {
-    if (need <= h->cap) return ISE_OK;
-    long long want = need;
-    if (h->cap > 0 && want < h->cap + h->cap / 2) want = h->cap + h->cap / 2;  // geometric growth on re-add
-    want = (want + 63) / 64 * 64;
-    const size_t rb = (size_t)h->ws * 8;
-    u64* nx = nullptr;
-    HIP_TRY(hipMalloc((void**)&nx, (size_t)want * rb));
-    hipError_t e = hipSuccess;
-    if (h->n > 0) e = hipMemcpyAsync(nx, h->codes, (size_t)h->n * rb, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync((char*)nx + (size_t)h->n * rb, 0, (size_t)(want - h->n) * rb, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && h->codes) e = hipDeviceSynchronize();  // searches in flight still read the old storage
-    if (e != hipSuccess) {
-        (void)hipFree(nx);
-        return ise_fail_(e == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP, std::string("growing the code storage: ") + hipGetErrorString(e));
-    }
-    if (h->codes) (void)hipFree(h->codes);
-    h->codes = nx;
-    h->cap = want;
-    return ISE_OK;
-}
-
 void pad_rows(const uint8_t* src_dev, int code_size, u64* dst, int ws, long long n, hipStream_t st) {
     const long long total = n * ws;
     hipLaunchKernelGGL(binary_pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src_dev, code_size, dst,
@@ -145,7 +118,7 @@ int add_device_locked(ise_binary_index* h, const uint8_t* x_dev, long long n, hi
     if (h->n + n >= (1ll << 32)) return ise_fail_(ISE_E_INVALID, "a binary index holds fewer than 2^32 rows");
     int rc = h->order.wait(st);
     if (rc) return rc;
-    rc = reserve_codes(h, h->n + n, st);
+    rc = reserve_code_rows(&h->codes, (size_t)h->ws * 8, h->n, &h->cap, h->n + n, 64, st);
     if (rc) return rc;
     pad_rows(x_dev, h->code_size, h->codes + (size_t)h->n * h->ws, h->ws, n, st);
     HIP_TRY(hipGetLastError());
@@ -163,8 +136,7 @@ int search_enqueue(ise_binary_index* h, const uint8_t* q_dev, long long nq, int 
     uint64_t& st_pass = sel ? h->st_sel_passes : h->st_passes;
     if (h->n == 0 || (sel && sel->count == 0)) {  // nothing to rank: a fill, no pass
         st_batches++;
-        const long long cnt = nq * k;
-        hipLaunchKernelGGL(binary_fill_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, cnt);
+        knn_fill_launch(D_dev, I_dev, nq * k, 0, st);
         HIP_TRY(hipGetLastError());
         return h->order.mark(st);
     }
@@ -193,21 +165,8 @@ int search_enqueue(ise_binary_index* h, const uint8_t* q_dev, long long nq, int 
             sp.lo = off == 0 ? nullptr : h->lo.p + q0;  // the merge of the pass before wrote it
             sp.lists = h->lists.p;
             launch_scan(wt, grid, lds, st, sp, sel ? &mk : nullptr);
-            MergeParams mp{};
-            mp.lists = h->lists.p;
-            mp.stride_list = (long long)BIN_QT * BIN_KPASS;
-            mp.stride_qtile = 0;
-            mp.qt = BIN_QT;
-            mp.n_lists = (int)grid;
-            mp.nq = nqt;
-            mp.k = kp;
-            BinMergeOut mo{};
-            mo.D = D_dev + (size_t)q0 * k;
-            mo.I = I_dev + (size_t)q0 * k;
-            mo.lo = h->lo.p + q0;
-            mo.k = k;
-            mo.off = off;
-            hipLaunchKernelGGL(binary_merge_kernel, dim3((unsigned)nqt), dim3(MERGE_THREADS), 0, st, mp, mo);
+            pass_merge_launch(h->lists.p, BIN_QT, BIN_KPASS, grid, nqt, kp, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k,
+                              h->lo.p + q0, k, off, 0, st);
             st_pass++;
         }
     }

@@ -16,9 +16,12 @@
 // rounds, no sort) keeps between kp and kp + kp / 2 + 4 (at most BIN_CUT_MAX) of them and its cut key becomes the
 // threshold -- a window close to kp, so that the threshold is tight and a wave rarely cuts twice.  At the end the
 // block selects once per query: a wave takes every fourth query, gathers the four waves' buffers (at most 512 keys)
-// and wave_select writes the kp smallest, SORTED, as the block's list.  binary_merge_kernel walks the blocks' lists
+// and wave_select writes the kp smallest, SORTED, as the block's list.  pass_merge_kernel<int> walks the blocks' lists
 // (merge_waves, ise_merge.hpp) and writes int32 D / int64 I.  A pass yields at most BIN_KPASS results per query; a
 // larger k repeats the pass with lo = (last key found) + 1 as the smallest key admitted.
+// The same scheme serves the other coded kinds as CandBuf (ise_cand.hpp); this kernel keeps its own body, with the waves'
+// final counts in LDS (cnts) where CandBuf pads the buffers' tails: measured, the shared body was 0.1 to 0.3 us slower on
+// the masked scan at 16 queries over a 1 % random selection (profiles/cands).
 //
 // Selectors: binary_scan_masked_kernel / binary_range_masked_kernel are the same passes over the tiles
 // of a selector's row window, skipping every 64-row tile whose mask word is zero (BinMask); the unmasked kernels are
@@ -106,8 +109,8 @@ __device__ __forceinline__ void hamming16(const u64* __restrict__ codes, int ws,
 // The candidate key: ascending key = ascending (distance, row).  The distance is stored + 1 so that every real key
 // lies strictly between 0 and KEY_PAD -- what wave_cut and wave_select (ise_select.hpp) require: (distance 0, row 0),
 // a query that is the index's first row, would otherwise be key 0, which wave_cut keeps but does not count.
+// PassOut<int> (ise_merge.hpp) takes the 1 off again.
 __device__ __forceinline__ u64 bin_key(int dist, long long row) { return ((u64)((uint32_t)dist + 1u) << 32) | (uint32_t)row; }
-__device__ __forceinline__ int bin_key_dist(u64 key) { return (int)((uint32_t)(key >> 32) - 1u); }
 
 struct BinScanParams {
     const u64* codes;  // [n][ws]
@@ -223,31 +226,6 @@ __global__ __launch_bounds__(BIN_WAVES * 64) void binary_scan_kernel(const BinSc
 template <int WT>
 __global__ __launch_bounds__(BIN_WAVES * 64) void binary_scan_masked_kernel(const BinScanParams p, const BinMask mk) {
     binary_scan_body<WT, true>(p, mk);
-}
-
-// One block per query of the tile: the k-way walk over the blocks' lists (merge_waves), then positions
-// [off, off + kp) of the query's results as int32 distance / int64 id (unfilled: INT32_MAX / -1) and the floor of
-// the next pass.
-struct BinMergeOut {
-    int* D;         // the tile's first query, [nqt][k]
-    long long* I;
-    u64* lo;        // [nqt]
-    int k, off;
-};
-static __global__ __launch_bounds__(MERGE_THREADS) void binary_merge_kernel(const MergeParams p, const BinMergeOut o) {
-    __shared__ MergeFastScratch fast;
-    __shared__ u64 res[MERGE_FAST_K];
-    const int lq = blockIdx.x;
-    merge_waves(p, p.lists + (size_t)lq * BIN_KPASS, fast, res);
-    const int t = threadIdx.x;
-    if (t < p.k) {
-        const u64 key = res[t];
-        const bool pad = key == KEY_PAD;
-        const size_t at = (size_t)lq * o.k + o.off + t;
-        o.D[at] = pad ? INT_MAX : bin_key_dist(key);
-        o.I[at] = pad ? -1ll : (long long)(uint32_t)key;
-        if (t == p.k - 1) o.lo[lq] = pad ? KEY_PAD : key + 1;
-    }
 }
 
 // ---- range search: every row with dist < radius, per query in ascending row order.  The rows are cut into S
@@ -401,15 +379,6 @@ static __global__ void binary_pad_kernel(const uint8_t* __restrict__ src, int co
         if (j < code_size) v |= (u64)s[j] << (8 * b);
     }
     dst[i] = v;
-}
-
-// unfilled results (an empty index)
-static __global__ void binary_fill_kernel(int* D, long long* I, long long cnt) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cnt) {
-        D[i] = INT_MAX;
-        I[i] = -1ll;
-    }
 }
 
 // ---- selectors: the census of a bitmap, read as one 8-byte word per 64-row tile.  Bits at or beyond n are cleared

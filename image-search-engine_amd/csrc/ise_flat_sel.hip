@@ -1,5 +1,6 @@
 // ise_flat_sel.hip -- the float index's selector objects and its selector-filtered search (ise_sel_scan.hpp; ise_flat.hpp: the handle).
 #include "ise_flat.hpp"
+#include "ise_pass_host.hpp"
 #include "ise_scan_params.hpp"
 #include "ise_selector.hpp"
 
@@ -150,9 +151,7 @@ static int search_sel_enqueue(ise_index* h, const ise_selector* sel, const float
     if (rc) return rc;
     h->sel_batches++;
     if (sel->count == 0) {  // an empty window: padding, no pass
-        const long long tot = nq * k;
-        hipLaunchKernelGGL(sel_fill_pad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, tot,
-                           h->metric);
+        knn_fill_launch(D_dev, I_dev, nq * k, h->metric != ISE_METRIC_L2, st);
         HIP_TRY(hipGetLastError());
         return ISE_OK;
     }

@@ -1,5 +1,6 @@
 // ise_flat_subset.hip -- the float index's subset scoring (ise_subset.hpp; ise_flat.hpp: the handle).
 #include "ise_flat.hpp"
+#include "ise_pass_host.hpp"
 #include "ise_sel_scan.hpp"
 #include "ise_subset.hpp"
 
@@ -27,9 +28,7 @@ static int subset_enqueue(ise_index* h, const float* q_dev, long long nq, int k,
     if (h->n == 0) {  // nothing to score: padding, no score launch
         sb.batches++;
         if (D_dev) {
-            const long long tot = nq * k;
-            hipLaunchKernelGGL(sel_fill_pad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, tot,
-                               h->metric);
+            knn_fill_launch(D_dev, I_dev, nq * k, h->metric != ISE_METRIC_L2, st);
         }
         if (dist_dev) {
             const long long tot = nq * kc;

@@ -19,6 +19,7 @@
 #include "ise_scan_params.hpp"
 #include "ise_ivf.hpp"
 #include "ise_ivf_lists.hpp"
+#include "ise_pass_host.hpp"
 
 #define IVF_NQ_CHUNK 64 /* queries per launch (4 groups of 16): bounds the per-block lists */
 
@@ -319,7 +320,7 @@ static int ivf_chunk_enqueue(ise_ivf* h, const float* q_dev, long long m, int k,
     HIP_TRY(hipMemsetAsync(h->masks.p, 0, (size_t)groups * h->inv.nlist * sizeof(uint32_t), st));
     const long long ptot = m * nprobe;
     hipLaunchKernelGGL(ivf_mask_kernel, dim3((unsigned)((ptot + 255) / 256)), dim3(256), 0, st, probes_dev, ptot, nprobe, h->inv.nlist,
-                       h->masks.p);
+                       4, h->masks.p);
     sp.q = h->q.p;
     sp.masks = h->masks.p;
     sp.part = h->part.p;
@@ -367,8 +368,7 @@ static int ivf_search_enqueue(ise_ivf* h, const float* q_dev, long long nq, int 
     if (rc) return rc;
     if ((rc = ivf_rebuild_locked(h, st))) return rc;
     if (h->inv.tiles == 0) {  // an empty index: padding, no pass
-        const long long tot = nq * k;
-        hipLaunchKernelGGL(sel_fill_pad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, tot, h->metric);
+        knn_fill_launch(D_dev, I_dev, nq * k, h->metric != ISE_METRIC_L2, st);
         HIP_TRY(hipGetLastError());
         return ISE_OK;
     }

@@ -10,8 +10,9 @@
 // ivf_scan_kernel makes one pass per group of 16 queries (grid.y).  It is sel_scan_kernel's loop (ise_sel_scan.hpp)
 // with the selector's half-word replaced by two tests -- "position < list size" and "this query's bit in the list's
 // mask" -- and with these differences:
-//   masks        ivf_mask_kernel turns the probe table [nq][nprobe] into one 16-bit query mask per (group, list);
-//                -1 and out-of-range entries set nothing, a duplicate sets its bit twice.
+//   masks        ivf_mask_kernel (ise_ivf_lists.hpp; groups of 16: qshift 4) turns the probe table [nq][nprobe] into
+//                one 16-bit query mask per (group, list); -1 and out-of-range entries set nothing, a duplicate sets
+//                its bit twice.
 //   work split   the tiles are dealt ROUND-ROBIN: round r gives block b the 8 consecutive tiles from (r blocks + b) 8,
 //                wave w the w-th of them, so the tiles of a probed list spread over all blocks however few lists are
 //                probed.  (sel_scan_kernel's contiguous slabs would leave one probed list to one or two blocks; they
@@ -48,17 +49,6 @@ struct IvfScanParams {
     u64* part;                  // [groups][gridDim.x][16][kpass] sorted keys per block
     unsigned long long* tiles_loaded;  // += the tiles this launch loaded
 };
-
-// probes [nq][nprobe] (int64) -> masks; the masks are zero on entry
-static __global__ __launch_bounds__(256) void ivf_mask_kernel(const long long* probes, long long total, int nprobe, int nlist,
-                                                       uint32_t* masks) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const long long l = probes[i];
-    if (l < 0 || l >= nlist) return;
-    const long long q = i / nprobe;
-    atomicOr(masks + (size_t)(q >> 4) * nlist + l, 1u << (q & 15));
-}
 
 template <int CH, bool SHIFT>
 __global__ __launch_bounds__(SEL_W * 64) void ivf_scan_kernel(const IvfScanParams p) {

@@ -2,10 +2,23 @@
 // the 8-bit lists (ise_ivfsq.hip): the ids and the table of the sorted array beside the host's counts
 // (ise_ivf_plan.hpp), and the staged host form of a search.  What a row IS (float32 rows and norms, or codes and row
 // terms) stays with the index kind: its rebuild allocates and fills the payload, this struct's begin_rebuild /
-// finish_rebuild do the ids, the table and the counts around it.  Host code only; the handle's mutex is held.
+// finish_rebuild do the ids, the table and the counts around it.  Host code (the handle's mutex is held), and the one
+// kernel that reads nothing of a row: the probe table's masks.
 #pragma once
 #include "ise_host.hpp"
 #include "ise_ivf_plan.hpp"
+
+// probes [nq][nprobe] (int64) -> masks [groups of 1 << qshift queries][nlist], bit c: query (group << qshift) + c probes
+// the list; the masks are zero on entry.  -1 and out-of-range entries set nothing, a duplicate sets its bit twice
+static __global__ __launch_bounds__(256) void ivf_mask_kernel(const long long* probes, long long total, int nprobe, int nlist,
+                                                              int qshift, uint32_t* masks) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long l = probes[i];
+    if (l < 0 || l >= nlist) return;
+    const long long q = i / nprobe;
+    atomicOr(masks + (size_t)(q >> qshift) * nlist + l, 1u << (q & ((1 << qshift) - 1)));
+}
 
 struct IvfLists : IvfBook {
     uint32_t* ids = nullptr;   // [tiles * tile rows] the sorted array's row numbers, ~0 in the pad slots

@@ -154,9 +154,7 @@ void launch_scan(int qt, unsigned grid, size_t lds, hipStream_t st, const SqIvfS
 // holds without a wait): about SQ_BLOCK_TILES tiles per wave, at most what the CUs hold at once and the merge's list count
 unsigned pass_grid(const ise_ivfsq* h) {
     const long long per_cu = std::max<long long>(1, (long long)SQ_LDS_LIMIT / (long long)sq_lds_bytes(h->d, h->qt));
-    long long g = (h->inv.tiles + SQ_BLOCK_TILES * SQ_WAVES - 1) / (SQ_BLOCK_TILES * SQ_WAVES);
-    g = std::min<long long>(g, std::min<long long>(per_cu * h->num_cu, MERGE_LISTS_MAX));
-    return (unsigned)std::max<long long>(g, 1);
+    return coded_grid(h->inv.tiles, SQ_BLOCK_TILES, SQ_WAVES, per_cu, h->num_cu);
 }
 
 // mu_ held, trained.  Enqueues only, unless rows are pending (the rebuild blocks) or a workspace has to grow
@@ -171,8 +169,7 @@ int search_enqueue(ise_ivfsq* h, const float* q_dev, long long nq, int k, const 
     const IvfLists& inv = h->inv;
     const int ip = h->metric == ISE_METRIC_INNER_PRODUCT;
     if (inv.tiles == 0) {  // an empty index: padding, no pass
-        const long long cnt = nq * k;
-        hipLaunchKernelGGL(sq_fill_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, cnt, ip);
+        knn_fill_launch(D_dev, I_dev, nq * k, ip, st);
         HIP_TRY(hipGetLastError());
         return ISE_OK;
     }
@@ -196,7 +193,7 @@ int search_enqueue(ise_ivfsq* h, const float* q_dev, long long nq, int k, const 
         h->codec.stage_launch(q_dev + (size_t)c0 * h->d, m, ip, h->qrec.p, st);
         HIP_TRY(hipMemsetAsync(h->masks.p, 0, (size_t)groups * nl * sizeof(uint32_t), st));
         const long long ptot = (long long)m * nprobe;
-        hipLaunchKernelGGL(ivfsq_mask_kernel, dim3((unsigned)((ptot + 255) / 256)), dim3(256), 0, st, probes_dev + (size_t)c0 * nprobe,
+        hipLaunchKernelGGL(ivf_mask_kernel, dim3((unsigned)((ptot + 255) / 256)), dim3(256), 0, st, probes_dev + (size_t)c0 * nprobe,
                            ptot, nprobe, inv.nlist, h->qshift, h->masks.p);
         hipLaunchKernelGGL(ivfsq_offsets_kernel, dim3((unsigned)groups), dim3(256), 0, st, (const uint32_t*)h->masks.p,
                            inv.list_tile0_dev(), inv.nlist, h->offs.p, counts);
@@ -224,7 +221,7 @@ int search_enqueue(ise_ivfsq* h, const float* q_dev, long long nq, int k, const 
                 sp.count = counts + g;
                 sp.tiles_loaded = h->stats_dev;
                 launch_scan(qt, grid, lds, st, sp);
-                sq_merge_launch(h->lists.p, qt, grid, nqt, kp, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, h->lo.p, k, off, ip, st);
+                pass_merge_launch(h->lists.p, qt, SQ_KPASS, grid, nqt, kp, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, h->lo.p, k, off, ip, st);
                 h->passes++;
             }
         }

@@ -7,8 +7,8 @@
 // in ascending id order, the slots behind list_size[l] rows are zero rows with id 0xFFFFFFFF, masked by position.
 //
 // A pass serves one group of QT = sq_qt(d) queries and 32 results:
-//   masks      ivfsq_mask_kernel turns the probe table [nq][nprobe] into one query mask per (group of QT, list); -1 and
-//              out-of-range entries set nothing, a duplicate sets its bit twice.
+//   masks      ivf_mask_kernel (ise_ivf_lists.hpp) turns the probe table [nq][nprobe] into one query mask per (group of
+//              QT, list); -1 and out-of-range entries set nothing, a duplicate sets its bit twice.
 //   work list  ivfsq_offsets_kernel scans the lists' tile counts under "mask != 0" into an offset per (group, list) and
 //              a count per group; ivfsq_work_kernel, parallel over all tiles, writes for every tile of a probed list
 //              the entry (tile, valid rows in it, the list's mask) at offset[list] + tile - list_tile0[list]: slot order,
@@ -16,7 +16,7 @@
 //   scan       ivfsq_scan_kernel is sq_scan_body (ise_sq.hpp) walking the entries instead of the tiles: wave w of block
 //              b takes entries b SQ_WAVES + w + j gridDim.x SQ_WAVES.  The key is ord(score) << 32 | ids[slot]; keys are
 //              unique and compared in full, so ties go by ascending id however the lists order the ids.
-// The staging record, the selection, sq_merge_kernel and the floor-keyed repeat for k > 32 are ise_sq.hpp's.
+// The staging record, the selection (ise_cand.hpp), the pass's merge and the floor-keyed repeat for k > 32 are ise_sq.hpp's.
 #pragma once
 #include "ise_sq.hpp"
 
@@ -38,17 +38,6 @@ struct SqIvfScanParams {
 template <int QT>
 __global__ __launch_bounds__(SQ_WAVES * 64) void ivfsq_scan_kernel(const SqIvfScanParams p) {
     sq_scan_body<QT, true>(p);
-}
-
-// probes [nq][nprobe] (int64) -> masks [groups of 1 << qshift queries][nlist]; the masks are zero on entry
-static __global__ __launch_bounds__(256) void ivfsq_mask_kernel(const long long* probes, long long total, int nprobe, int nlist,
-                                                                int qshift, uint32_t* masks) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const long long l = probes[i];
-    if (l < 0 || l >= nlist) return;
-    const long long q = i / nprobe;
-    atomicOr(masks + (size_t)(q >> qshift) * nlist + l, 1u << (q & ((1 << qshift) - 1)));
 }
 
 // one block per group: offs[group][l] = the tiles of the probed lists before l, count[group] = their total.  Thread t

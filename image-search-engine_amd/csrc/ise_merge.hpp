@@ -1,5 +1,8 @@
 // ise_merge.hpp -- k-way merge of sorted candidate lists.
 #pragma once
+#include <climits>
+#include <type_traits>
+
 #include "ise_common.hpp"
 #include "ise_exact.hpp"
 
@@ -13,6 +16,7 @@ struct MergeParams {
     long long stride_qtile;  // elements between consecutive query tiles
     int qt;                  // queries per tile
     int n_lists, nq, k, metric;
+    int stride_query;  // pass_merge_kernel: elements between a block's lists of consecutive queries
     float* D;        // [nq][k] or null
     long long* I;    // [nq][k] or null
     u64* keys_out;   // [nq][k] or null
@@ -221,6 +225,52 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(const MergeParams 
     } else {
         merge_rounds<MERGE_THREADS, LPT>(p, base, wmin, [&](int r, u64 key) { emit_result(p, (size_t)q * k + r, key); });
     }
+}
+
+// ---------------------------------------------------------------- the merge half of a coded scan's k-pass
+// Where a pass's results go: positions [off, off + kp) of each query's k, as distance / int64 id, and the floor of the
+// next pass.  T = float: the key's high word is ord_f32 of the score (of -score under the inner product), unfilled
+// +-FLT_MAX / -1.  T = int: it is the Hamming distance + 1 (bin_key, ise_binary_scan.hpp), unfilled INT_MAX / -1.
+// knn_fill_kernel uses only D, I and ip (through store); its lo is null and never read.  ip means nothing for T = int.
+template <class T>
+struct PassOut {
+    T* D;  // the pass's first query, [nqt][k]
+    long long* I;
+    u64* lo;  // [nqt]
+    int k, off, ip;
+    __device__ __forceinline__ void store(size_t at, u64 key, bool pad) const {
+        if constexpr (std::is_same_v<T, float>) {
+            const float sc = unord_f32((uint32_t)(key >> 32));
+            D[at] = pad ? (ip ? -FLT_MAX : FLT_MAX) : (ip ? -sc : sc);
+        } else {
+            D[at] = pad ? INT_MAX : (int)((uint32_t)(key >> 32) - 1u);
+        }
+        I[at] = pad ? -1ll : (long long)(uint32_t)key;
+    }
+};
+
+// One block per query of the pass: the k-way walk over the blocks' lists (merge_waves), then the query's results and
+// its floor.
+template <class T>
+__global__ __launch_bounds__(MERGE_THREADS) void pass_merge_kernel(const MergeParams p, const PassOut<T> o) {
+    __shared__ MergeFastScratch fast;
+    __shared__ u64 res[MERGE_FAST_K];
+    const int lq = blockIdx.x;
+    merge_waves(p, p.lists + (size_t)lq * p.stride_query, fast, res);
+    const int t = threadIdx.x;
+    if (t < p.k) {
+        const u64 key = res[t];
+        const bool pad = key == KEY_PAD;
+        o.store((size_t)lq * o.k + o.off + t, key, pad);
+        if (t == p.k - 1) o.lo[lq] = pad ? KEY_PAD : key + 1;
+    }
+}
+
+// unfilled results (nothing to rank)
+template <class T>
+__global__ __launch_bounds__(256) void knn_fill_kernel(const PassOut<T> o, long long cnt) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cnt) o.store((size_t)i, KEY_PAD, true);
 }
 
 // Up to 64 lists (the all-gathered per-rank lists of the multi-GPU path): one wave per query,

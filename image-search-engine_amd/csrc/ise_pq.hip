@@ -9,7 +9,7 @@
 // rule (grow_drained, ise_host.hpp).
 #include <cmath>
 
-#include "ise_host.hpp"
+#include "ise_pass_host.hpp"
 #include "ise_pq.hpp"
 
 struct ise_pq {
@@ -47,37 +47,14 @@ void launch_scan(int qt, unsigned grid, size_t lds, hipStream_t st, const PqScan
     else go(pq_scan_kernel<2>, attr[3]);
 }
 
-// blocks of a pass: about two tiles per wave on a short index, at most what the CUs hold at once (their LDS) and the
-// merge's list count
+// blocks of a pass: about two tiles per wave on a short index, at most what the CUs hold at once (their LDS)
 unsigned pq_grid(const ise_pq* h) {
-    const long long tiles = (h->n + 63) / 64;
     const long long per_cu = std::max<long long>(1, (long long)PQ_LDS_LIMIT / (long long)pq_lds_bytes(h->M, h->qt));
-    long long g = (tiles + 2 * PQ_WAVES - 1) / (2 * PQ_WAVES);
-    g = std::min<long long>(g, std::min<long long>(per_cu * h->num_cu, MERGE_LISTS_MAX));
-    return (unsigned)std::max<long long>(g, 1);
+    return coded_grid((h->n + 63) / 64, 2, PQ_WAVES, per_cu, h->num_cu);
 }
 
-int reserve_codes(ise_pq* h, long long need, hipStream_t st) {
-    if (need <= h->cap) return ISE_OK;
-    long long want = need;
-    if (h->cap > 0 && want < h->cap + h->cap / 2) want = h->cap + h->cap / 2;  // geometric growth on re-add
-    want = (want + 63) / 64 * 64;
-    const size_t rb = (size_t)h->stride;
-    uint8_t* nx = nullptr;
-    HIP_TRY(hipMalloc((void**)&nx, (size_t)want * rb));
-    hipError_t e = hipSuccess;
-    if (h->n > 0) e = hipMemcpyAsync(nx, h->codes, (size_t)h->n * rb, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(nx + (size_t)h->n * rb, 0, (size_t)(want - h->n) * rb, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && h->codes) e = hipDeviceSynchronize();  // searches in flight still read the old storage
-    if (e != hipSuccess) {
-        (void)hipFree(nx);
-        return ise_fail_(e == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP, std::string("growing the code storage: ") + hipGetErrorString(e));
-    }
-    if (h->codes) (void)hipFree(h->codes);
-    h->codes = nx;
-    h->cap = want;
-    return ISE_OK;
+int reserve_rows(ise_pq* h, long long need, hipStream_t st) {
+    return reserve_code_rows(&h->codes, (size_t)h->stride, h->n, &h->cap, need, 64, st);
 }
 
 // byte m of rows [0, n) of dst (row stride `stride`) <- the code of x's rows; sets the bad flag on a non-finite entry
@@ -112,8 +89,7 @@ int search_enqueue(ise_pq* h, const float* q_dev, long long nq, int k, float* D_
     const int ip = h->metric == ISE_METRIC_INNER_PRODUCT;
     if (h->n == 0) {  // nothing to rank: a fill, no table, no pass
         h->st_search++;
-        const long long cnt = nq * k;
-        hipLaunchKernelGGL(pq_fill_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, cnt, ip);
+        knn_fill_launch(D_dev, I_dev, nq * k, ip, st);
         HIP_TRY(hipGetLastError());
         return h->order.mark(st);
     }
@@ -148,22 +124,8 @@ int search_enqueue(ise_pq* h, const float* q_dev, long long nq, int k, float* D_
                 sp.lo = off == 0 ? nullptr : h->lo.p + g * qt;  // the merge of the pass before wrote it
                 sp.lists = h->lists.p;
                 launch_scan(qt, grid, lds, st, sp);
-                MergeParams mp{};
-                mp.lists = h->lists.p;
-                mp.stride_list = (long long)qt * PQ_KPASS;
-                mp.stride_qtile = 0;
-                mp.qt = qt;
-                mp.n_lists = (int)grid;
-                mp.nq = nqt;
-                mp.k = kp;
-                PqMergeOut mo{};
-                mo.D = D_dev + (size_t)q0 * k;
-                mo.I = I_dev + (size_t)q0 * k;
-                mo.lo = h->lo.p + g * qt;
-                mo.k = k;
-                mo.off = off;
-                mo.ip = ip;
-                hipLaunchKernelGGL(pq_merge_kernel, dim3((unsigned)nqt), dim3(MERGE_THREADS), 0, st, mp, mo);
+                pass_merge_launch(h->lists.p, qt, PQ_KPASS, grid, nqt, kp, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k,
+                                  h->lo.p + g * qt, k, off, ip, st);
                 h->st_passes++;
             }
         }
@@ -183,7 +145,7 @@ int add_device_locked(ise_pq* h, const float* x_dev, long long n, hipStream_t st
     int rc = check_rows_fit(h, n);
     if (rc) return rc;
     if ((rc = h->order.wait(st))) return rc;
-    if ((rc = reserve_codes(h, h->n + n, st))) return rc;
+    if ((rc = reserve_rows(h, h->n + n, st))) return rc;
     if ((rc = h->bad.clear(st))) return rc;
     encode_launch(h, x_dev, n, h->codes + (size_t)h->n * h->stride, h->stride, st);
     HIP_TRY(hipGetLastError());
@@ -407,7 +369,7 @@ extern "C" int ise_pq_add_host(ise_pq_t* h, const float* x, int64_t n) {
     const long long step = upload_step((size_t)h->d * sizeof(float));
     int rc = check_rows_fit(h, n);
     if (rc) return rc;
-    if ((rc = reserve_codes(h, h->n + n, h->stream))) return rc;
+    if ((rc = reserve_rows(h, h->n + n, h->stream))) return rc;
     for (long long i0 = 0; i0 < n; i0 += step) {
         const long long m = std::min<long long>(step, n - i0);
         if ((rc = grow_drained(h->xraw, (size_t)m * h->d))) return rc;
@@ -432,8 +394,8 @@ extern "C" int ise_pq_add_codes_host(ise_pq_t* h, const uint8_t* codes, int64_t 
     int rc = check_rows_fit(h, n);
     if (rc) return rc;
     if ((rc = h->order.wait(st))) return rc;
-    if ((rc = reserve_codes(h, h->n + n, st))) return rc;
-    // the pad bytes of the fresh rows are zero already (reserve_codes); only bytes below M are ever written
+    if ((rc = reserve_rows(h, h->n + n, st))) return rc;
+    // the pad bytes of the fresh rows are zero already (reserve_code_rows); only bytes below M are ever written
     HIP_TRY(hipMemcpy2DAsync(h->codes + (size_t)h->n * h->stride, (size_t)h->stride, codes, (size_t)h->M, (size_t)h->M, (size_t)n,
                              hipMemcpyHostToDevice, st));
     if ((rc = h->order.mark(st))) return rc;

@@ -15,21 +15,19 @@
 // (QT >= 4: ds_read_b128; QT = 2: ds_read_b64).
 //
 // Scan (pq_scan_kernel<QT>): the shape of the binary scan (ise_binary_scan.hpp) -- a lane owns a row, a wave a tile of
-// 64 consecutive rows, QT queries per pass, a per-wave and per-query threshold key, candidates ballot-appended to an
-// LDS buffer of PQ_CAP keys, wave_cut when fewer than 64 slots are free, one wave_select per block and query at the
-// end, merge_waves over the blocks' lists (pq_merge_kernel), a pass repeated with a floor key for k > PQ_KPASS.  What
-// is new: the pass's tables sit in LDS ([m][256][QT], copied in by the whole block), and the lane walks the bytes of
-// its code and gathers.  Key = ord_f32(score) << 32 | row (inner product: of -score): ascending key is (best score,
-// ascending id); a score enters only if it is < FLT_MAX (NaN never), so every key lies strictly between 0 and KEY_PAD.
+// 64 consecutive rows, QT queries per pass, the tile's keys ballot-appended per query -- and the k-pass of ise_cand.hpp
+// behind it (CandBuf, query q's state in lane q; pass_merge_kernel<float>), a pass repeated with a floor key for
+// k > PQ_KPASS.  What is new: the pass's tables sit in LDS ([m][256][QT], copied in by the whole block), and the lane
+// walks the bytes of its code and gathers.  Key = ord_f32(score) << 32 | row (inner product: of -score): ascending key
+// is (best score, ascending id); a score enters only if it is < FLT_MAX (NaN never), so every key lies strictly between
+// 0 and KEY_PAD.
 //
-// LDS: QT * (M KiB of tables + 4 KiB of selection buffers: PQ_WAVES * PQ_CAP keys per query), nothing else -- the
-// waves pad their buffers with KEY_PAD at the end instead of keeping counts -- against 160 KiB per CU:
+// LDS: QT * (M KiB of tables + 4 KiB of selection buffers: PQ_WAVES * PQ_CAP keys per query), nothing else, against
+// 160 KiB per CU:
 //   QT(M) = 16 for M <= 5, 8 for M <= 15, 4 for M <= 35, 2 for M <= ISE_PQ_MAX_M = 64   (pq_qt)
 // i.e. the largest power of two with QT * (M + 4) KiB <= 160 KiB; M = 16 takes 80 KiB, two blocks per CU.
 #pragma once
-#include "ise_common.hpp"
-#include "ise_merge.hpp"
-#include "ise_select.hpp"
+#include "ise_cand.hpp"
 
 #define PQ_KSUB 256     /* centroids per sub-quantiser (8 bits) */
 #define PQ_WAVES 4      /* waves per block */
@@ -41,9 +39,8 @@
 #define PQ_COPY_UNROLL 8 /* 16-byte loads in flight per thread while the tables are copied into LDS */
 #define PQ_LDS_LIMIT (160 * 1024)
 
-static_assert(PQ_CUT_MAX + 64 <= PQ_CAP && PQ_KPASS <= PQ_CUT_MAX, "a tile's 64 keys fit behind the kept ones");
-static_assert(PQ_WAVES * PQ_CAP == 512, "the block's selection holds the waves' buffers in eight registers per lane");
-static_assert(PQ_KPASS <= MERGE_FAST_K, "merge_waves serves every pass");
+template <int QT>
+using PqCand = CandBuf<QT, PQ_WAVES, PQ_CAP, 64, PQ_CUT_MAX, PQ_KPASS>;
 
 // queries per pass for M sub-quantisers, and the pass's LDS
 constexpr int pq_qt(int M) { return M <= 5 ? 16 : M <= 15 ? 8 : M <= 35 ? 4 : 2; }
@@ -133,29 +130,11 @@ __global__ __launch_bounds__(PQ_WAVES * 64) void pq_scan_kernel(const PqScanPara
         for (; i < units; i += PQ_WAVES * 64) dst[i] = src[i];
     }
     __syncthreads();
-    u64* mybuf = buf + w * QT * PQ_CAP;
-    const int kp = p.kp;
     // per-query state of the wave, query q in lane q: keys held, threshold (a new key must be below it), floor
-    int cnt_v = 0;
-    u64 thr_v = KEY_PAD;
+    PqCand<QT> cand(buf, w, lane, p.kp);
     const u64 lo_v = lane < p.nqt ? (p.lo ? p.lo[lane] : 0ull) : KEY_PAD;
     const u64 lt_mask = (1ull << lane) - 1ull;
     const uint32_t flip = p.ip ? 0x80000000u : 0u;
-
-    const int kmax = kp + kp / 2 + 4 < PQ_CUT_MAX ? kp + kp / 2 + 4 : PQ_CUT_MAX;
-    auto cut = [&](int q) {
-        const int cnt = __builtin_amdgcn_readlane(cnt_v, q);
-        u64 kk[2];
-#pragma unroll
-        for (int e = 0; e < 2; e++) kk[e] = lane + 64 * e < cnt ? mybuf[q * PQ_CAP + lane + 64 * e] : KEY_PAD;
-        u64 ckey = KEY_PAD;
-        const int nw = wave_cut<2>(kk, PQ_CAP, kp, kmax, mybuf + q * PQ_CAP, &ckey);
-        wave_lds_fence();
-        if (lane == q) {
-            cnt_v = nw;
-            thr_v = ckey;
-        }
-    };
 
     const long long ntiles = (p.n + 63) >> 6;
     const int pieces = p.stride >> 4;
@@ -190,77 +169,18 @@ __global__ __launch_bounds__(PQ_WAVES * 64) void pq_scan_kernel(const PqScanPara
             if (q < p.nqt) {
                 const float s = __uint_as_float(__float_as_uint(acc[q]) ^ flip);
                 const u64 key = ((u64)ord_f32(s) << 32) | (uint32_t)row;
-                const bool c = valid && s < FLT_MAX && key >= readlane_u64(lo_v, q) && key < readlane_u64(thr_v, q);
+                const bool c = valid && s < FLT_MAX && key >= readlane_u64(lo_v, q) && key < readlane_u64(cand.thr, q);
                 const u64 mk = __ballot(c);
                 if (mk) {
-                    const int cnt = __builtin_amdgcn_readlane(cnt_v, q);
-                    if (c) mybuf[q * PQ_CAP + cnt + __popcll(mk & lt_mask)] = key;
-                    if (lane == q) cnt_v += __popcll(mk);
+                    const int cnt = __builtin_amdgcn_readlane(cand.cnt, q);
+                    if (c) cand.keys(q)[cnt + __popcll(mk & lt_mask)] = key;
+                    if (lane == q) cand.cnt += __popcll(mk);
                 }
             }
         }
-        wave_lds_fence();
-        u64 need = __ballot(cnt_v > PQ_CAP - 64);  // the next tile may not fit
-        while (need) {
-            const int q = __ffsll((long long)need) - 1;
-            need &= need - 1;
-            cut(q);
-        }
+        cand.make_room();
     }
-    // the slots behind a buffer's keys read as empty: the block's selection needs no counts
-#pragma unroll
-    for (int q = 0; q < QT; q++) {
-        const int cnt = __builtin_amdgcn_readlane(cnt_v, q);
-#pragma unroll
-        for (int e = 0; e < 2; e++)
-            if (lane + 64 * e >= cnt) mybuf[q * PQ_CAP + lane + 64 * e] = KEY_PAD;
-    }
-    __syncthreads();
-    // the waves' buffers -> the block's sorted list
-    for (int q = w; q < p.nqt; q += PQ_WAVES) {
-        u64 kk[2 * PQ_WAVES];
-#pragma unroll
-        for (int e = 0; e < 2 * PQ_WAVES; e++) kk[e] = buf[((e >> 1) * QT + q) * PQ_CAP + lane + 64 * (e & 1)];
-        u64* dst = p.lists + ((size_t)blockIdx.x * QT + q) * PQ_KPASS;
-        u64 kth_unused = 0;
-        const int nw = wave_select<2 * PQ_WAVES>(kk, PQ_WAVES * PQ_CAP, kp, dst, &kth_unused);
-        for (int i = nw + lane; i < kp; i += 64) dst[i] = KEY_PAD;
-    }
-}
-
-// One block per query of the pass: the k-way walk over the blocks' lists (merge_waves), then positions
-// [off, off + kp) of the query's results as float32 score / int64 id (unfilled: +-FLT_MAX / -1) and the floor of the
-// next pass.
-struct PqMergeOut {
-    float* D;  // the pass's first query, [nqt][k]
-    long long* I;
-    u64* lo;  // [nqt]
-    int k, off, ip;
-};
-static __global__ __launch_bounds__(MERGE_THREADS) void pq_merge_kernel(const MergeParams p, const PqMergeOut o) {
-    __shared__ MergeFastScratch fast;
-    __shared__ u64 res[MERGE_FAST_K];
-    const int lq = blockIdx.x;
-    merge_waves(p, p.lists + (size_t)lq * PQ_KPASS, fast, res);
-    const int t = threadIdx.x;
-    if (t < p.k) {
-        const u64 key = res[t];
-        const bool pad = key == KEY_PAD;
-        const size_t at = (size_t)lq * o.k + o.off + t;
-        const float sc = unord_f32((uint32_t)(key >> 32));
-        o.D[at] = pad ? (o.ip ? -FLT_MAX : FLT_MAX) : (o.ip ? -sc : sc);
-        o.I[at] = pad ? -1ll : (long long)(uint32_t)key;
-        if (t == p.k - 1) o.lo[lq] = pad ? KEY_PAD : key + 1;
-    }
-}
-
-// unfilled results (an empty index)
-static __global__ void pq_fill_kernel(float* D, long long* I, long long cnt, int ip) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cnt) {
-        D[i] = ip ? -FLT_MAX : FLT_MAX;
-        I[i] = -1ll;
-    }
+    cand.fold(p.nqt, p.lists + (size_t)blockIdx.x * QT * PQ_KPASS);
 }
 
 // ---- encoding (build side).  A wave owns a row at a time, block (rows, m) sub-quantiser m = blockIdx.y: lane l holds

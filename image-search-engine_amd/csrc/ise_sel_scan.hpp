@@ -188,14 +188,6 @@ static __global__ __launch_bounds__(256) void sel_scatter_kernel(const u64* pass
     if (r == kp - 1) floor_out[q] = key;
 }
 
-// an empty selection: every slot is padding
-static __global__ __launch_bounds__(256) void sel_fill_pad_kernel(float* D, long long* I, long long total, int metric) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    D[i] = metric == ISE_METRIC_L2 ? FLT_MAX : -FLT_MAX;
-    I[i] = -1ll;
-}
-
 // queries [nq][d] -> [nq][dp], zero padded (the staging and exact_l2_rows read whole padded rows)
 static __global__ __launch_bounds__(256) void sel_pad_queries_kernel(const float* q, int d, int dp, long long total, float* out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -40,43 +40,15 @@ void launch_scan(int qt, unsigned grid, size_t lds, hipStream_t st, const SqScan
     else go(sq_scan_kernel<8>, attr[1]);
 }
 
-// blocks of a pass: about SQ_BLOCK_TILES tiles per wave on a short index, at most what the CUs hold at once (their
-// LDS) and the merge's list count
+// blocks of a pass: about SQ_BLOCK_TILES tiles per wave on a short index, at most what the CUs hold at once (their LDS)
 unsigned sq_grid(const ise_sq* h) {
-    const long long tiles = (h->n + SQ_TILE - 1) / SQ_TILE;
     const long long per_cu = std::max<long long>(1, (long long)SQ_LDS_LIMIT / (long long)sq_lds_bytes(h->d, h->qt));
-    long long g = (tiles + SQ_BLOCK_TILES * SQ_WAVES - 1) / (SQ_BLOCK_TILES * SQ_WAVES);
-    g = std::min<long long>(g, std::min<long long>(per_cu * h->num_cu, MERGE_LISTS_MAX));
-    return (unsigned)std::max<long long>(g, 1);
+    return coded_grid((h->n + SQ_TILE - 1) / SQ_TILE, SQ_BLOCK_TILES, SQ_WAVES, per_cu, h->num_cu);
 }
 
-int reserve_codes(ise_sq* h, long long need, hipStream_t st) {
-    if (need <= h->cap) return ISE_OK;
-    long long want = need;
-    if (h->cap > 0 && want < h->cap + h->cap / 2) want = h->cap + h->cap / 2;  // geometric growth on re-add
-    want = (want + SQ_TILE - 1) / SQ_TILE * SQ_TILE;
-    const size_t rb = (size_t)h->stride;
-    uint8_t* nx = nullptr;
-    double* nr = nullptr;
-    HIP_TRY(hipMalloc((void**)&nx, (size_t)want * rb));
-    hipError_t e = hipMalloc((void**)&nr, (size_t)want * sizeof(double));
-    if (e == hipSuccess && h->n > 0) e = hipMemcpyAsync(nx, h->codes, (size_t)h->n * rb, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && h->n > 0) e = hipMemcpyAsync(nr, h->rterm, (size_t)h->n * sizeof(double), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(nx + (size_t)h->n * rb, 0, (size_t)(want - h->n) * rb, st);
-    if (e == hipSuccess) e = hipMemsetAsync(nr + h->n, 0, (size_t)(want - h->n) * sizeof(double), st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && h->codes) e = hipDeviceSynchronize();  // searches in flight still read the old storage
-    if (e != hipSuccess) {
-        (void)hipFree(nx);
-        if (nr) (void)hipFree(nr);
-        return ise_fail_(e == hipErrorOutOfMemory ? ISE_E_NOMEM : ISE_E_HIP, std::string("growing the code storage: ") + hipGetErrorString(e));
-    }
-    if (h->codes) (void)hipFree(h->codes);
-    if (h->rterm) (void)hipFree(h->rterm);
-    h->codes = nx;
-    h->rterm = nr;
-    h->cap = want;
-    return ISE_OK;
+// the codes and, beside them, the row terms
+int reserve_rows(ise_sq* h, long long need, hipStream_t st) {
+    return reserve_code_rows(&h->codes, (size_t)h->stride, h->n, &h->cap, need, SQ_TILE, st, &h->rterm, sizeof(double));
 }
 
 int check_rows_fit(const ise_sq* h, long long n) {
@@ -91,8 +63,7 @@ int search_enqueue(ise_sq* h, const float* q_dev, long long nq, int k, float* D_
     const int ip = h->metric == ISE_METRIC_INNER_PRODUCT;
     if (h->n == 0) {  // nothing to rank: a fill, no pass
         h->st_search++;
-        const long long cnt = nq * k;
-        hipLaunchKernelGGL(sq_fill_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, D_dev, I_dev, cnt, ip);
+        knn_fill_launch(D_dev, I_dev, nq * k, ip, st);
         HIP_TRY(hipGetLastError());
         return h->order.mark(st);
     }
@@ -124,7 +95,7 @@ int search_enqueue(ise_sq* h, const float* q_dev, long long nq, int k, float* D_
             sp.lo = off == 0 ? nullptr : h->lo.p;  // the merge of the pass before wrote it
             sp.lists = h->lists.p;
             launch_scan(qt, grid, lds, st, sp);
-            sq_merge_launch(h->lists.p, qt, grid, nqt, kp, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, h->lo.p, k, off, ip, st);
+            pass_merge_launch(h->lists.p, qt, SQ_KPASS, grid, nqt, kp, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, h->lo.p, k, off, ip, st);
             h->st_passes++;
         }
     }
@@ -143,7 +114,7 @@ int add_device_locked(ise_sq* h, const float* x_dev, long long n, hipStream_t st
     int rc = check_rows_fit(h, n);
     if (rc) return rc;
     if ((rc = h->order.wait(st))) return rc;
-    if ((rc = reserve_codes(h, h->n + n, st))) return rc;
+    if ((rc = reserve_rows(h, h->n + n, st))) return rc;
     if ((rc = h->codec.bad.clear(st))) return rc;
     h->codec.encode_launch(x_dev, n, h->codes + (size_t)h->n * h->stride, h->stride, h->rterm + h->n, st);
     HIP_TRY(hipGetLastError());
@@ -351,7 +322,7 @@ extern "C" int ise_sq_add_host(ise_sq_t* h, const float* x, int64_t n) {
     const long long step = upload_step((size_t)h->d * sizeof(float));
     int rc = check_rows_fit(h, n);
     if (rc) return rc;
-    if ((rc = reserve_codes(h, h->n + n, h->stream))) return rc;
+    if ((rc = reserve_rows(h, h->n + n, h->stream))) return rc;
     for (long long i0 = 0; i0 < n; i0 += step) {
         const long long m = std::min<long long>(step, n - i0);
         if ((rc = grow_drained(h->xraw, (size_t)m * h->d))) return rc;
@@ -376,8 +347,8 @@ extern "C" int ise_sq_add_codes_host(ise_sq_t* h, const uint8_t* codes, int64_t 
     int rc = check_rows_fit(h, n);
     if (rc) return rc;
     if ((rc = h->order.wait(st))) return rc;
-    if ((rc = reserve_codes(h, h->n + n, st))) return rc;
-    // the pad bytes of the fresh rows are zero already (reserve_codes); only bytes below d are ever written
+    if ((rc = reserve_rows(h, h->n + n, st))) return rc;
+    // the pad bytes of the fresh rows are zero already (reserve_code_rows); only bytes below d are ever written
     uint8_t* dst = h->codes + (size_t)h->n * h->stride;
     HIP_TRY(hipMemcpy2DAsync(dst, (size_t)h->stride, codes, (size_t)h->d, (size_t)h->d, (size_t)n, hipMemcpyHostToDevice, st));
     h->codec.rowterm_launch(dst, h->stride, n, h->rterm + h->n, st);

@@ -30,11 +30,10 @@
 // and the result is rounded to float32 once.  On integer data every term is an integer and the result exact.
 // A query with a NaN or inf entry (or whose weights overflow) scores NaN everywhere and gets padding.
 //
-// Selection is the product-quantised scan's (ise_pq.hpp): per wave and query a buffer of SQ_CAP keys in LDS, appended
-// by ballot, wave_cut when fewer than 64 slots are free, one wave_select per block and query, merge_waves over the
-// blocks' lists, a pass repeated with a floor key for k > SQ_KPASS.  A wave's tile is 64 rows (SQ_RT MFMA row tiles),
-// so a lane ends a tile with 16 scores of ONE query (column = lane & 15) and the per-query state is kept replicated
-// in the four lanes of that column.
+// Selection is the k-pass of ise_cand.hpp (CandBuf; pass_merge_kernel<float>), a pass repeated with a floor key for
+// k > SQ_KPASS.  A wave's tile is 64 rows (SQ_RT MFMA row tiles), so a lane ends a tile with 16 scores of ONE query
+// (column = lane & 15): the per-query state is kept replicated in the four lanes of that column, and a tile's keys are
+// appended at per-column popcount positions.
 //
 // LDS per pass: QT x (two limb images of 2 dpad + 16 bytes, dpad = d rounded up to 64; the 16 bytes stagger the
 // queries over the banks) + QT x 4 KiB of selection buffers + QT x 16 bytes; QT = 16 while that fits 160 KiB
@@ -43,9 +42,7 @@
 // The scan's body (sq_scan_body) also serves the inverted lists over these rows (ise_ivfsq.hpp), which
 // walk a work list of tiles instead of the whole array; this file's kernels do not depend on that one.
 #pragma once
-#include "ise_common.hpp"
-#include "ise_merge.hpp"
-#include "ise_select.hpp"
+#include "ise_cand.hpp"
 
 #define SQ_WAVES 4    /* waves per block */
 #define SQ_RT 4       /* MFMA row tiles (16 rows) of a wave's tile */
@@ -60,9 +57,8 @@
 #define SQ_BLOCK_TILES 2 /* wave tiles per wave a short index's grid is sized for: 2 * SQ_WAVES * SQ_TILE rows per block */
 
 static_assert(SQ_TILE == 64, "a tile adds at most 64 keys per query; the row-term loads are 16-byte aligned");
-static_assert(SQ_CUT_MAX + SQ_TILE <= SQ_CAP && SQ_KPASS <= SQ_CUT_MAX, "a tile's keys fit behind the kept ones");
-static_assert(SQ_WAVES * SQ_CAP == 512, "the block's selection holds the waves' buffers in eight registers per lane");
-static_assert(SQ_KPASS <= MERGE_FAST_K, "merge_waves serves every pass");
+template <int QT>
+using SqCand = CandBuf<QT, SQ_WAVES, SQ_CAP, SQ_TILE, SQ_CUT_MAX, SQ_KPASS>;
 
 constexpr int sq_dpad(int d) { return (d + 63) / 64 * 64; }
 constexpr int sq_stride(int d) { return sq_dpad(d); }
@@ -265,32 +261,14 @@ __device__ __forceinline__ void sq_scan_body(const P& p) {
     }
     __syncthreads();
 
-    u64* mybuf = buf + w * QT * SQ_CAP;
-    const int kp = p.kp;
     const int g = lane >> 4, c16 = lane & 15;
     const int qsrc = c16 & (QT - 1);  // QT = 8: columns 8 .. 15 repeat 0 .. 7 and are never selected from
     // per-query state of the wave, query q in the four lanes of column q: keys held, threshold, floor
-    int cnt_v = 0;
-    u64 thr_v = KEY_PAD;
+    SqCand<QT> cand(buf, w, c16, p.kp);
     const u64 lo_v = c16 < p.nqt ? (p.lo ? p.lo[c16] : 0ull) : KEY_PAD;
     const u64 below_mask = (1ull << (16 * g)) - 1ull;  // the lower lanes of my column
     const double cq = *reinterpret_cast<const double*>(smem_sq + qsrc * rec + 2 * qrow);
     const int shq = *reinterpret_cast<const int*>(smem_sq + qsrc * rec + 2 * qrow + 8);
-
-    const int kmax = kp + kp / 2 + 4 < SQ_CUT_MAX ? kp + kp / 2 + 4 : SQ_CUT_MAX;
-    auto cut = [&](int q) {
-        const int cnt = __builtin_amdgcn_readlane(cnt_v, q);
-        u64 kk[2];
-#pragma unroll
-        for (int e = 0; e < 2; e++) kk[e] = lane + 64 * e < cnt ? mybuf[q * SQ_CAP + lane + 64 * e] : KEY_PAD;
-        u64 ckey = KEY_PAD;
-        const int nw = wave_cut<2>(kk, SQ_CAP, kp, kmax, mybuf + q * SQ_CAP, &ckey);
-        wave_lds_fence();
-        if (c16 == q) {
-            cnt_v = nw;
-            thr_v = ckey;
-        }
-    };
 
     long long ntiles;  // units of the pass: the index's tiles | the work list's entries
     if constexpr (IVF) ntiles = nent;
@@ -331,26 +309,20 @@ __device__ __forceinline__ void sq_scan_body(const P& p) {
                 bool c;
                 if constexpr (IVF) {
                     key = ((u64)ord_f32(s) << 32) | idv[rt][reg];
-                    c = rt * 16 + 4 * g + reg < valid && probes && s < FLT_MAX && key >= lo_v && key < thr_v;
+                    c = rt * 16 + 4 * g + reg < valid && probes && s < FLT_MAX && key >= lo_v && key < cand.thr;
                 } else {
                     key = ((u64)ord_f32(s) << 32) | (uint32_t)row;
-                    c = row < p.n && s < FLT_MAX && key >= lo_v && key < thr_v;
+                    c = row < p.n && s < FLT_MAX && key >= lo_v && key < cand.thr;
                 }
                 const u64 mk = __ballot(c);
                 if (mk) {
                     const u64 col = (mk >> c16) & 0x0001000100010001ull;  // my column's four lanes
-                    if (c) mybuf[c16 * SQ_CAP + cnt_v + __popcll(col & below_mask)] = key;
-                    cnt_v += __popcll(col);
+                    if (c) cand.keys(c16)[cand.cnt + __popcll(col & below_mask)] = key;
+                    cand.cnt += __popcll(col);
                 }
             }
         }
-        wave_lds_fence();
-        u64 need = __ballot(cnt_v > SQ_CAP - SQ_TILE) & 0xFFFFull;  // the next tile may not fit
-        while (need) {
-            const int q = __ffsll((long long)need) - 1;
-            need &= need - 1;
-            cut(q);
-        }
+        cand.make_room();
     };
 
     // ---- main loop: the wave's (tile, step) sequence through a ring of SQ_RING steps' bytes, requested SQ_RING - 1
@@ -444,63 +416,10 @@ __device__ __forceinline__ void sq_scan_body(const P& p) {
             }
         }
     }
-    // the slots behind a buffer's keys read as empty: the block's selection needs no counts
-#pragma unroll
-    for (int q = 0; q < QT; q++) {
-        const int cnt = __builtin_amdgcn_readlane(cnt_v, q);
-#pragma unroll
-        for (int e = 0; e < 2; e++)
-            if (lane + 64 * e >= cnt) mybuf[q * SQ_CAP + lane + 64 * e] = KEY_PAD;
-    }
-    __syncthreads();
-    // the waves' buffers -> the block's sorted list
-    for (int q = w; q < p.nqt; q += SQ_WAVES) {
-        u64 kk[2 * SQ_WAVES];
-#pragma unroll
-        for (int e = 0; e < 2 * SQ_WAVES; e++) kk[e] = buf[((e >> 1) * QT + q) * SQ_CAP + lane + 64 * (e & 1)];
-        u64* dst = p.lists + ((size_t)blockIdx.x * QT + q) * SQ_KPASS;
-        u64 kth_unused = 0;
-        const int nw = wave_select<2 * SQ_WAVES>(kk, SQ_WAVES * SQ_CAP, kp, dst, &kth_unused);
-        for (int i = nw + lane; i < kp; i += 64) dst[i] = KEY_PAD;
-    }
+    cand.fold(p.nqt, p.lists + (size_t)blockIdx.x * QT * SQ_KPASS);
 }
 
 template <int QT>
 __global__ __launch_bounds__(SQ_WAVES * 64) void sq_scan_kernel(const SqScanParams p) {
     sq_scan_body<QT, false>(p);
-}
-
-// One block per query of the pass: the k-way walk over the blocks' lists (merge_waves), then positions
-// [off, off + kp) of the query's results as float32 score / int64 id (unfilled: +-FLT_MAX / -1) and the floor of the
-// next pass.
-struct SqMergeOut {
-    float* D;  // the pass's first query, [nqt][k]
-    long long* I;
-    u64* lo;  // [nqt]
-    int k, off, ip;
-};
-static __global__ __launch_bounds__(MERGE_THREADS) void sq_merge_kernel(const MergeParams p, const SqMergeOut o) {
-    __shared__ MergeFastScratch fast;
-    __shared__ u64 res[MERGE_FAST_K];
-    const int lq = blockIdx.x;
-    merge_waves(p, p.lists + (size_t)lq * SQ_KPASS, fast, res);
-    const int t = threadIdx.x;
-    if (t < p.k) {
-        const u64 key = res[t];
-        const bool pad = key == KEY_PAD;
-        const size_t at = (size_t)lq * o.k + o.off + t;
-        const float sc = unord_f32((uint32_t)(key >> 32));
-        o.D[at] = pad ? (o.ip ? -FLT_MAX : FLT_MAX) : (o.ip ? -sc : sc);
-        o.I[at] = pad ? -1ll : (long long)(uint32_t)key;
-        if (t == p.k - 1) o.lo[lq] = pad ? KEY_PAD : key + 1;
-    }
-}
-
-// unfilled results (an empty index)
-static __global__ void sq_fill_kernel(float* D, long long* I, long long cnt, int ip) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cnt) {
-        D[i] = ip ? -FLT_MAX : FLT_MAX;
-        I[i] = -1ll;
-    }
 }

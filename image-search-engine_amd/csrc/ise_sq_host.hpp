@@ -1,11 +1,11 @@
 // ise_sq_host.hpp -- the host state of the scalar-quantiser codec (kernels and arithmetic: ise_sq.hpp), held once each by
-// the flat index (ise_sq.hip) and the inverted lists over 8-bit rows (ise_ivfsq.hip), and the two launches of a search
-// that do not depend on where the rows lie: the queries' staging and the merge half of a k-pass.  Host code only; the
-// handle's mutex is held.
+// the flat index (ise_sq.hip) and the inverted lists over 8-bit rows (ise_ivfsq.hip), with the launch of a search that
+// does not depend on where the rows lie: the queries' staging (the merge half of a k-pass is ise_pass_host.hpp's).  Host
+// code only; the handle's mutex is held.
 #pragma once
 #include <cmath>
 
-#include "ise_host.hpp"
+#include "ise_pass_host.hpp"
 #include "ise_sq.hpp"
 
 struct SqCodec {
@@ -96,25 +96,3 @@ struct SqCodec {
         hipLaunchKernelGGL(sq_stage_kernel, dim3((unsigned)nq), dim3(64), 0, st, gp);
     }
 };
-
-// the merge half of a k-pass: the `grid` blocks' lists of nqt queries -> positions [off, off + kp) of their k results
-// at D, I and the floor keys of the next pass at lo
-inline void sq_merge_launch(u64* lists, int qt, unsigned grid, int nqt, int kp, float* D, long long* I, u64* lo, int k, int off, int ip,
-                            hipStream_t st) {
-    MergeParams mp{};
-    mp.lists = lists;
-    mp.stride_list = (long long)qt * SQ_KPASS;
-    mp.stride_qtile = 0;
-    mp.qt = qt;
-    mp.n_lists = (int)grid;
-    mp.nq = nqt;
-    mp.k = kp;
-    SqMergeOut mo{};
-    mo.D = D;
-    mo.I = I;
-    mo.lo = lo;
-    mo.k = k;
-    mo.off = off;
-    mo.ip = ip;
-    hipLaunchKernelGGL(sq_merge_kernel, dim3((unsigned)nqt), dim3(MERGE_THREADS), 0, st, mp, mo);
-}

@@ -2,9 +2,11 @@
 include/ise_knn.h states them, the expected kNN (a float64 brute force over the DECODED rows), the kernel's pass rule,
 block size and grid, the integer construction on which every score is exact, an emulation of the scan's arithmetic
 (``emulate_scores``) and the worst-case bound of its error derived in DESIGN.md 4.15 (``score_bound``)."""
+import functools
+
 import numpy as np
 
-from tests.knn_checks import brute_knn, int_data
+from tests.knn_checks import HUGE, assert_exact_range, brute_knn, int_data
 from tests.sel_ref import L2
 
 QT_8BIT, QT_8BIT_UNIFORM = 0, 2
@@ -266,3 +268,30 @@ def stretched_case(family, d, qtype, seed=0, n=600, nq=8):
     xq = (c + rng.standard_normal((nq, d))).astype(np.float32)
     train = xb if family == "offset" else np.concatenate([xb, np.zeros((1, d), np.float32)])
     return train, xb, xq
+
+
+# ---- one block that cuts, then lists that end short (tests/test_sq_scan_gpu.py, tests/test_ivfsq_gpu.py)
+@functools.lru_cache(maxsize=None)
+def one_block_case(d: int, qtype: int = QT_8BIT):
+    """-> (trained, rows, codes, plain queries, queries, D, I): 512 rows of the integer construction -- eight tiles in one
+    block, wave 0 streams tiles 0 and 4 and cuts after the second -- in DESCENDING L2 distance to query 0 (every key of
+    its second tile passes); 16 queries of which the last three get an entry of 2^64 (finite weights, every distance
+    rounds to inf: their lists end without a key); the expected k = 33 results (a floor-keyed second pass).  Computed
+    once, shared, read-only."""
+    n, nq, k, far = 512, 16, 33, [13, 14, 15]
+    rng = np.random.default_rng(9100 + d)
+    t, m, s = integer_trained(rng, d, qtype)
+    xb, base = integer_rows(rng, n, d, m, s, "binary")
+    plain = int_data("binary", rng, nq, d)
+    assert_exact_range(xb, plain)
+    d0 = ((xb.astype(np.float64) - plain[0].astype(np.float64)) ** 2).sum(1)
+    order = np.argsort(-d0, kind="stable")  # query 0: every row beats or ties its predecessors
+    xb, base = np.ascontiguousarray(xb[order]), np.ascontiguousarray(base[order])
+    xq = plain.copy()
+    xq[far, [0, d // 2, d - 1]] = HUGE
+    Dw, Iw = expected(xq, xb, k, L2)
+    assert (Iw[far] == -1).all() and (Iw[:13] >= 0).all() and (np.diff(Dw[0]) >= 0).all()
+    out = (t, xb, base, plain, xq, Dw, Iw)
+    for a in out:
+        a.setflags(write=False)
+    return out

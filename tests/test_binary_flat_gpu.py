@@ -115,6 +115,30 @@ def test_query_equal_to_row_zero_survives_a_cut():
     assert_range_same(index.range_search(q, 2), ref.range_search(xb, q, 2))
 
 
+def one_block_data(code_size):
+    """(xb, xq, dist): 512 rows -- eight tiles in one block, wave 0 streams tiles 0 and 4 and cuts after the second --
+    in DESCENDING distance to query 0, so that every key of its second tile passes; 16 queries."""
+    rng = np.random.default_rng(3000 + code_size)
+    xb = rng.integers(0, 256, (512, code_size), dtype=np.uint8)
+    xq = rng.integers(0, 256, (16, code_size), dtype=np.uint8)
+    xb = xb[np.argsort(-ref.distances(xb, xq[:1])[0], kind="stable")]
+    dist = ref.distances(xb, xq)
+    assert (np.diff(dist[0]) <= 0).all()
+    return xb, xq, dist
+
+
+@pytest.mark.parametrize("code_size", (8, 16, 24))  # one word, two words, the queries in LDS
+def test_one_block_cut_then_short_lists(code_size):
+    """k = 33: the floor-keyed second pass and the merge's floor write behind a pass that cut.  k = 513: sixteen full
+    passes, then one that finds no row above its floor -- every list of the block ends short."""
+    xb, xq, dist = one_block_data(code_size)
+    index = make_index(xb)
+    for k in (KPASS + 1, 513):
+        got = index.search(xq, k)
+        assert_same(got, ref.search(xb, xq, k, dist))
+    assert (got[1][:, 512] == -1).all() and (got[0][:, 512] == ref.INT32_MAX).all() and (got[1][:, :512] >= 0).all()
+
+
 def test_long_index_thresholds_and_worst_case_order():
     """One million rows: the grid is at its cap, so every wave streams several 64-row tiles and most keys are turned
     away by the wave's threshold (at 70 001 rows a wave sees two tiles and cuts once).  The rows are sorted by

@@ -13,7 +13,8 @@ from image_search_engine_amd import faiss_compat as faiss
 from image_search_engine_amd._native import IseError
 from tests import binary_ref as ref
 from tests import binary_sel_ref as sref
-from tests.test_binary_flat_gpu import N_SWEEP, assert_range_same, assert_same, big_data, make_index, sweep_data
+from tests.test_binary_flat_gpu import (N_SWEEP, assert_range_same, assert_same, big_data, make_index, one_block_data,
+                                        sweep_data)
 
 pytestmark = pytest.mark.gpu
 
@@ -99,6 +100,27 @@ def test_masked_search_sweep(code_size):
     if code_size == 8:  # the tie rule is exercised, not assumed: most queries tie at the 10th place
         D, _ = sref.search(xb, xq, 11, sref.members_of(EveryThird(), N_SWEEP), dist)
         assert int((D[:, 9] == D[:, 10]).sum()) == 29
+
+
+@pytest.mark.parametrize("code_size", (8, 16, 24))  # one word, two words, the queries in LDS
+def test_one_block_cut_beside_a_cleared_tile(code_size):
+    """512 rows in one block, in descending distance to query 0: wave 0 streams tiles 0 and 4 and cuts after the second,
+    wave 1 skips its second tile (5), which the selector clears whole.  k = 33: the floor-keyed second pass; k = 513:
+    fourteen full passes over the 448 selected rows, then passes that find nothing -- every list ends short."""
+    xb, xq, dist = one_block_data(code_size)
+    mask = np.ones(512, dtype=bool)
+    mask[5 * 64:6 * 64] = False
+    sel = Mask(mask)
+    members = sref.members_of(sel, 512)
+    index = make_index(xb)
+    ds = index.make_selector(sel)
+    assert ds.info() == sref.census(members) and ds.info()["selected"] == 448
+    for k in (KPASS + 1, 513):
+        got = index.search(xq, k, params=params(ds))
+        assert_same(got, sref.search(xb, xq, k, members, dist))
+    assert (got[1][:, 448:] == -1).all() and (got[0][:, 448:] == ref.INT32_MAX).all() and (got[1][:, :448] >= 0).all()
+    assert not np.isin(got[1], np.arange(5 * 64, 6 * 64)).any()
+    ds.close()
 
 
 def test_ties_among_selected_rows():

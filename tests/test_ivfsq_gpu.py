@@ -356,6 +356,23 @@ def test_many_entries_per_wave(metric):
             assert_knn_identical(D[q:q + 1], I[q:q + 1], Dw[None, :], Iw[None, :], f"two lists k={k} q={q}")
 
 
+@pytest.mark.parametrize("d", [130, 1473])  # QT = 16, 8
+def test_one_block_cut_then_short_lists(d):
+    """``sq_ref.one_block_case``: 512 rows in two lists of four full tiles, every list probed -- eight entries in one
+    block, in row order.  Wave 0 streams entries 0 and 4 and cuts after the second (the rows lie in descending distance
+    to query 0), k = 33 runs the floor-keyed second pass, and the last three queries are far from all rows: their lists
+    end without a key in either pass."""
+    assert sq_ref.qt_of(d) == (16 if d == 130 else 8)
+    t, xb, base, plain, xq, Dw, Iw = sq_ref.one_block_case(d)
+    assign = np.repeat(np.arange(2), 256)
+    qz, index = new_index(d, SQ.QT_8bit, L2, np.random.default_rng(d).standard_normal((2, d)), t)
+    force_add(index, xb, assign)
+    check_lists(index, assign, base)
+    D, I = search_pre(index, xq, 33, np.tile(np.arange(2), (16, 1)))
+    assert_knn_identical(D, I, Dw, Iw, f"d={d}")
+    assert (D[13:] == pad_value(L2)).all()
+
+
 # ---------------------------------------------------------------- 8. real-valued data
 def sq_scores_of(sqi, xq, I):
     """IndexScalarQuantizer's D for the pairs (q, I[q, r]), read out of its own deepest search."""

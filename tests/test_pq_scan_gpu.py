@@ -368,3 +368,42 @@ def test_overflowing_inner_products():
     assert not np.isin(I[1], huge_rows).any() and (I[1, n - nh:] == -1).all() and (D[1, n - nh:] == pad_value(IP)).all()
     assert not np.isin(I[2], edge_rows).any() and (I[2, n - ne:] == -1).all() and (D[2, n - ne:] == pad_value(IP)).all()
     assert (I[2, :n - ne] >= 0).all() and (I[3:] >= 0).all()
+
+
+# ---------------------------------------------------------------- F. one block: a cut, then lists that end short
+@pytest.mark.parametrize("M", [4, 12, 20, 64])  # QT = 16, 8, 4, 2
+def test_one_block_cut_then_short_lists(M):
+    """512 rows are eight tiles in one block: wave 0 streams tiles 0 and 4 and cuts after the second, every wave folds.
+    The rows lie in descending distance to query 0 (every key of the second tile passes), k = 33 runs the floor-keyed
+    second pass and the merge's floor write.  Sub-quantiser 0 has two HUGE centroids: a row coded with one of them is at
+    distance inf from every ordinary query and never enters.  The last three queries are far from all other rows:
+    query 13 sits on centroid 255 (20 rows are finite: a first pass that ends short, a finished second pass), query 15
+    on centroid 254 (exactly 32 rows: a full first pass, then nothing above the floor), query 14 on neither (no row)."""
+    dsub, n, nq, k = 2, 512, 16, 33
+    qt = pq_ref.qt_of(M)
+    assert grid_of(M, n, 256) == 1 and qt == {4: 16, 12: 8, 20: 4, 64: 2}[M]
+    rng = np.random.default_rng(9000 + M)
+    C = int_data("small", rng, M * 256, dsub).reshape(M, 256, dsub)
+    C[0, 255], C[0, 254] = (HUGE, 0), (-HUGE, 0)
+    codes = rng.integers(0, 254, (n, M)).astype(np.uint8)
+    xq = pq_ref.decode(rng.integers(0, 254, (nq, M)).astype(np.uint8), C)
+    assert_exact_range(pq_ref.decode(np.unique(codes, axis=0), C), xq)
+    codes = codes[np.argsort(-pq_ref.adc_scores(xq[:1], C, codes, L2)[0], kind="stable")]
+    on255, on254 = np.arange(7, n, 26)[:20], np.arange(2, n, 16)  # spread over the eight tiles
+    assert len(on255) == 20 and len(on254) == 32 and not np.intersect1d(on255, on254).size
+    codes[on255, 0], codes[on254, 0] = 255, 254
+    xq[13, :2], xq[14, :2], xq[15, :2] = (HUGE, 0), (0, HUGE), (-HUGE, 0)
+    scores = pq_ref.adc_scores(xq, C, codes, L2)
+    fin = scores < FLT_MAX
+    assert (fin[:13].sum(1) == n - 52).all() and fin[13:].sum(1).tolist() == [20, 0, 32]
+    assert (scores[~fin] >= 2.0 ** 127).all() and scores[fin].max() < 2.0 ** 24  # inf in any order | exact in any order
+    plain = np.setdiff1d(np.arange(n), np.union1d(on255, on254))
+    assert (np.diff(scores[0, plain]) <= 0).all()  # query 0: every row beats or ties its predecessors
+    Dw, Iw = pq_ref.adc_topk(scores, k, L2)
+    assert (Iw[13, 20:] == -1).all() and (Iw[14] == -1).all() and Iw[15, 32] == -1 and (Iw[[13, 15], :20] >= 0).all()
+    index = empty_index(C, L2)
+    index._add_codes(codes)
+    assert index.ntotal == n and np.array_equal(index.codes, codes)
+    D, I = search_counted(index, xq, k, M)
+    assert_knn_identical(D, I, Dw, Iw, f"M={M} QT={qt}")
+    assert (D[I < 0] == pad_value(L2)).all()

@@ -245,6 +245,24 @@ def test_long_index_streams_cuts_and_worst_case_order(metric):
         assert_knn_identical(D[:2], I[:2], Dw[:2, :k], Iw[:2, :k], f"lists against the exact top, k={k}")
 
 
+@pytest.mark.parametrize("d", [130, 1473])  # QT = 16, 8
+def test_one_block_cut_then_short_lists(d):
+    """512 rows are eight tiles in one block (``sq_ref.one_block_case``): wave 0 streams tiles 0 and 4 and cuts after the
+    second, every wave folds.  The rows lie in descending distance to query 0 (every key of the second tile passes),
+    k = 33 runs the floor-keyed second pass and the merge's floor write.  The last three queries are far from all rows --
+    an entry of 2^64: finite weights, every distance rounds to inf -- so their lists end without a key in either pass,
+    beside queries whose lists are full.  The same case through two inverted lists: tests/test_ivfsq_gpu.py."""
+    qtype = SQ.QT_8bit
+    assert sq_ref.grid_of(512, d, 256) == 1 and sq_ref.qt_of(d) == (16 if d == 130 else 8)
+    t, xb, base, plain, xq, Dw, Iw = sq_ref.one_block_case(d)
+    assert_scan_exact(plain, t, d, qtype, L2)
+    index = sq_index(d, qtype, L2, t, xb)
+    check_stored(index, t, xb, base)
+    D, I = counted_search(index, xq, 33)
+    assert_knn_identical(D, I, Dw, Iw, f"the flat index, d={d}")
+    assert (D[13:] == pad_value(L2)).all()
+
+
 # ---------------------------------------------------------------- D. a second staging chunk at QT = 8
 @pytest.mark.parametrize("metric", [L2, IP])
 def test_chunk_reuse_at_qt8(metric):
