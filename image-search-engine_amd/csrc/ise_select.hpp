@@ -9,7 +9,9 @@
 // KEY_PAD.  Control flow is wave-uniform (ballot counts in SGPRs).
 
 // Exact: the min(k, #real) smallest keys, written SORTED to dst[0..).  Returns
-// the number written; *kth = the k-th smallest key when k were written.
+// the number written; *kth = the k-th smallest key when k were written, and is
+// left untouched otherwise.  dst slots at or past the returned count are not
+// written (callers pad them; block_topk_part, CandBuf::fold).  k >= 1.
 // Quickselect on the key value, then an all-pairs rank among the <= k winners.
 template <int KPL>
 __device__ __forceinline__ int wave_select(const u64 (&kk)[KPL], int n, int k, u64* dst, u64* kth) {
@@ -85,8 +87,13 @@ __device__ __forceinline__ int wave_select(const u64 (&kk)[KPL], int n, int k, u
 
 // Windowed cut: finds a key P with kmin <= #(keys <= P) <= kmax and writes those
 // keys UNSORTED to dst (all real keys if there are at most kmax).  Returns the
-// count; *cut = P when the count reached kmin.  A valid, cheap threshold: the
-// kmin-th smallest key is <= P.  Window width makes this take a few rounds only.
+// count; *cut = P when the count reached kmin -- P is then the largest key
+// kept -- and is left untouched otherwise (fewer than kmin real keys: all are
+// kept).  The kept keys are the `count` smallest; dst slots at or past the
+// count are not written, and dst may be where kk was loaded from (every key is
+// in registers before the first store).  1 <= kmin <= kmax.  A valid, cheap
+// threshold: the kmin-th smallest key is <= P.  Window width makes this take a
+// few rounds only.
 template <int KPL>
 __device__ __forceinline__ int wave_cut(const u64 (&kk)[KPL], int n, int kmin, int kmax, u64* dst, u64* cut) {
     const int lane = threadIdx.x & 63;
