@@ -136,6 +136,20 @@ __device__ __forceinline__ void rerank_stage_query(const ExactParams& p, int q, 
     for (int j = threadIdx.x; j < p.dp; j += NT) qs[j] = j < p.d ? src[j] : 0.f;
 }
 
+#define RERANK_ROWS 4 /* rows a re-rank wave scores side by side; two steps of them in flight: 8 loads, 32 VGPRs */
+
+// Where a re-rank wave stands in its rows: group g of RERANK_ROWS candidates, column block j of nj.  The loads run two
+// steps ahead of the arithmetic; each keeps one of these.
+struct RerankCursor {
+    int g = 0, j = 0;
+    __device__ __forceinline__ void next(int nj) {
+        if (++j == nj) {
+            j = 0;
+            g++;
+        }
+    }
+};
+
 // Re-rank the kc candidates of query q (kin: ascending lo-keys, KEY_PAD padded, in LDS behind the
 // staged query) by their direct-difference distance; emit the top k; on a failed certificate put q
 // on the fallback list.  Called by all NT threads of the block; smem is the block's dynamic LDS
@@ -153,6 +167,43 @@ __device__ __forceinline__ void rerank_block(const ExactParams& p, int q, unsign
     if (keys_in_global)
         for (int c = tid; c < p.kc; c += NT) kin[c] = keys_in_global[(size_t)q * p.kc + c];
     __syncthreads();
+    // ---- the candidates' rows.  Wave w takes the candidates w, w + NW, .. in groups of RERANK_ROWS; a STEP is one
+    // 256-float column block (16 bytes per lane) of the RERANK_ROWS rows of a group, and the ring holds two steps.
+    // Fetching a row block by block, each used before the next is asked for, made the re-rank a chain of
+    // dependent trips to rows that miss to HBM.  Here a wave asks for its first two steps together, the moment kin
+    // is known (a pad is the largest key and ends the list, so the requests need no count), and for one step more
+    // behind every step it uses: at dp = 512 all the rows of kc <= 32 (8 waves) come in ONE trip, longer rows and
+    // lists go round the ring.  The lanes keep the wave's candidate keys in a register, 64 at a time, so that naming
+    // a row costs a readlane and no trip to LDS.  A request is masked (a pad, a column at or beyond dp: nothing is read
+    // -- and no row exists when the index is empty) and otherwise unconditional, like exact_scan_kernel's.
+    // d() is exact_l2_rows' bit for bit: per lane the fmaf chain over the row's column blocks in ascending order
+    // from 0.f, then wave_sum_f32 (the rows of a group are reduced side by side, each by its own butterfly).
+    const int nj = (p.dp + 255) >> 8;
+    int kb = 0;  // lane i holds the wave's (kb + i)-th candidate: 64 of them at a time
+    auto lane_key = [&]() -> u64 { return (w + NW * (kb + lane)) < p.kc ? kin[w + NW * (kb + lane)] : KEY_PAD; };
+    u64 lanekey = lane_key();
+    f32x4 ring[2][RERANK_ROWS];
+    RerankCursor ld;  // the next step to LOAD
+    auto load_step = [&](f32x4(&y)[RERANK_ROWS]) {  // a slot keeps what it held where nothing is read (never used)
+        const int j = (ld.j << 8) + lane * 4;
+        if (ld.g * RERANK_ROWS - kb >= 64) {  // wave-uniform, once per 64 candidates of the wave
+            kb += 64;
+            lanekey = lane_key();
+        }
+#pragma unroll
+        for (int r = 0; r < RERANK_ROWS; r++) {
+            const u64 key = readlane_u64(lanekey, ld.g * RERANK_ROWS + r - kb);
+            if (key != KEY_PAD && j < p.dp)
+                y[r] = *reinterpret_cast<const f32x4*>(p.xb + (size_t)((uint32_t)key - p.id_base) * p.dp + j);
+        }
+        ld.next(nj);
+    };
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+#pragma unroll
+        for (int r = 0; r < RERANK_ROWS; r++) ring[h][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        load_step(ring[h]);
+    }
     // real entries come first (the list is sorted and pads are the largest key)
     int count = 0;
     for (int c0 = 0; c0 < p.kc; c0 += 64) {
@@ -160,31 +211,55 @@ __device__ __forceinline__ void rerank_block(const ExactParams& p, int q, unsign
         count += __popcll(__ballot(real));
     }
     DBG_STAMP(p.stats ? p.stats + 8 : nullptr, 4);
-    constexpr int R = NW >= 8 ? 2 : 4;  // rows in flight per wave
-    for (int c0 = w * R; c0 < n2; c0 += NW * R) {
-        if (c0 >= count) {  // nothing real from here on (and no row to read when the index is empty)
-            if (lane < R && c0 + lane < n2) kex[c0 + lane] = KEY_PAD;
-            continue;
-        }
-        const float* rows[R];
-        u64 kc_[R];
+    for (int c = count + tid; c < n2; c += NT) kex[c] = KEY_PAD;
+    {
+        const int rows_w = count > w ? (count - w + NW - 1) / NW : 0;  // this wave's real candidates
+        const int T = (rows_w + RERANK_ROWS - 1) / RERANK_ROWS * nj;    // ... and its steps
+        RerankCursor use;  // the step being USED
+        float s[RERANK_ROWS];
 #pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int c = c0 + r;
-            kc_[r] = c < count ? kin[c] : KEY_PAD;
-            const long long row = kc_[r] != KEY_PAD ? (long long)((uint32_t)kc_[r] - p.id_base) : 0ll;
-            rows[r] = p.xb + (size_t)row * p.dp;
-        }
-        float dd[R];
-        exact_l2_rows<R>(rows, qs, p.dp, lane, dd);
-        if (lane == 0) {
+        for (int r = 0; r < RERANK_ROWS; r++) s[r] = 0.f;
+        auto use_step = [&](f32x4(&slot)[RERANK_ROWS]) {
+            f32x4 y[RERANK_ROWS];
 #pragma unroll
-            for (int r = 0; r < R; r++)
-                if (c0 + r < n2)
+            for (int r = 0; r < RERANK_ROWS; r++) y[r] = slot[r];
+            load_step(slot);
+            const int j = (use.j << 8) + lane * 4;
+            if (j < p.dp) {
+                const f32x4 x = *reinterpret_cast<const f32x4*>(qs + j);
+#pragma unroll
+                for (int r = 0; r < RERANK_ROWS; r++) {
+                    const f32x4 t = y[r] - x;
+                    s[r] = fmaf(t[0], t[0], s[r]);
+                    s[r] = fmaf(t[1], t[1], s[r]);
+                    s[r] = fmaf(t[2], t[2], s[r]);
+                    s[r] = fmaf(t[3], t[3], s[r]);
+                }
+            }
+            if (use.j == nj - 1) {  // the group's rows are complete
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {  // wave_sum_f32 of every row, side by side
+                    float t[RERANK_ROWS];
+#pragma unroll
+                    for (int r = 0; r < RERANK_ROWS; r++) t[r] = __shfl_xor(s[r], o);
+#pragma unroll
+                    for (int r = 0; r < RERANK_ROWS; r++) s[r] += t[r];
+                }
+#pragma unroll
+                for (int r = 0; r < RERANK_ROWS; r++) {
+                    const int i = use.g * RERANK_ROWS + r;
                     // Faiss's gate: a distance >= FLT_MAX (a candidate keyed -FLT_MAX for an overflowing norm, or
                     // one whose bound lay just below FLT_MAX) is not a result
-                    kex[c0 + r] = (kc_[r] != KEY_PAD && dd[r] < FLT_MAX) ? (((u64)ord_f32(dd[r]) << 32) | (uint32_t)kc_[r])
-                                                                       : KEY_PAD;
+                    if (lane == 0 && i < rows_w)
+                        kex[w + NW * i] = s[r] < FLT_MAX ? (((u64)ord_f32(s[r]) << 32) | (uint32_t)kin[w + NW * i]) : KEY_PAD;
+                    s[r] = 0.f;
+                }
+            }
+            use.next(nj);
+        };
+        for (int t = 0; t < T; t += 2) {  // two steps per turn: the ring's registers are named statically
+            use_step(ring[0]);
+            if (t + 1 < T) use_step(ring[1]);
         }
     }
     DBG_STAMP(p.stats ? p.stats + 8 : nullptr, 5);

@@ -47,10 +47,110 @@ __device__ __forceinline__ void emit_result(const MergeParams& p, size_t o, u64 
 // them: merge_waves below is fast when no wave holds more than MERGE_PRE of the k winners, and with list t on
 // thread t the 188 lists of a 6000-row index sat on three waves (17 % of the queries took the slow path, the
 // merge 11.8-13.9 us instead of 7.7).
-// Every list keeps its head AND the element behind it in registers, and the element after that is
-// requested the moment a list wins: the round trip to L2 / HBM stays off the round-to-round path.
+// Every list keeps a WINDOW of its next MERGE_WIN keys in registers, win[e][0] the head.  load() requests every
+// window of the thread at once, with no branch between the requests, so the block pays ONE round trip before its
+// first round; a winning list shifts its window and touches memory again only when all MERGE_WIN keys of it have
+// won, and then asks for the next MERGE_WIN together.  A scan block's list holds one or two real keys ahead of its
+// pads, and the k best are spread about two per wave: the pre-rounds of merge_waves, and normally the whole merge,
+// run on that first trip (a key per round, as before, cost one dependent trip per round: the next round reads it).
+// Requests are never predicated: an index at or beyond k is clamped into the list and its value replaced by
+// KEY_PAD, so nothing is read behind a list's k keys -- whatever the stride says lies there.
+#define MERGE_WIN 4
+typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 template <int NT, int LPT>
 struct ListHeads {
+    const u64* lst[LPT];
+    int used[LPT];  // keys of the list that have won
+    u64 win[LPT][MERGE_WIN];
+    bool vec;  // block-uniform: k and the stride are even and the lists 16-byte aligned -- two keys per request
+    // the window of list e: keys [at, at + MERGE_WIN) of it, at a multiple of MERGE_WIN.  request() asks, settle()
+    // waits and mask() replaces what lies at or beyond k (or belongs to a list that does not exist) by KEY_PAD.
+    __device__ __forceinline__ void request(int e, int at, int k) {
+        if (vec) {
+#pragma unroll
+            for (int i = 0; i < MERGE_WIN; i += 2) {
+                const int j = at + i;  // even, as k is: a pair lies inside the list or outside it
+                const u64x2 v = *reinterpret_cast<const u64x2*>(lst[e] + (j < k ? j : k - 2));
+                win[e][i] = v[0];
+                win[e][i + 1] = v[1];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < MERGE_WIN; i++) {
+                const int j = at + i;
+                win[e][i] = lst[e][j < k ? j : k - 1];
+            }
+        }
+    }
+    // The compiler waits for a load at its first use.  Naming the raw window here makes this that use: the wait
+    // stands HERE and not in the round that follows (where every wave would meet it, whether or not it asked for
+    // anything), and the request cannot be folded into the mask's condition (a predicated load per list, each
+    // waited for before the next was issued).
+    __device__ __forceinline__ void settle(int e) {
+#pragma unroll
+        for (int i = 0; i < MERGE_WIN; i++) asm volatile("" : "+v"(win[e][i]));
+    }
+    __device__ __forceinline__ void mask(int e, int at, int k, bool live) {
+#pragma unroll
+        for (int i = 0; i < MERGE_WIN; i++)
+            if (!live || at + i >= k) win[e][i] = KEY_PAD;
+    }
+    // between(): what the caller wants issued behind the requests and ahead of the wait for them
+    template <typename Between>
+    __device__ __forceinline__ void load(const MergeParams& p, const u64* base, Between between) {
+        vec = ((p.k | (int)(p.stride_list & 1)) & 1) == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0;
+        bool live[LPT];
+#pragma unroll
+        for (int e = 0; e < LPT; e++) {
+            constexpr int NW = NT / 64;
+            const int l = ((int)threadIdx.x & 63) * NW + ((int)threadIdx.x >> 6) + e * NT;
+            live[e] = l < p.n_lists;
+            lst[e] = base + (size_t)(live[e] ? l : 0) * p.stride_list;
+            used[e] = 0;
+        }
+#pragma unroll
+        for (int e = 0; e < LPT; e++) request(e, 0, p.k);
+        between();
+#pragma unroll
+        for (int e = 0; e < LPT; e++) settle(e);
+#pragma unroll
+        for (int e = 0; e < LPT; e++) mask(e, 0, p.k, live[e]);
+    }
+    __device__ __forceinline__ void load(const MergeParams& p, const u64* base) {
+        load(p, base, [] {});
+    }
+    __device__ __forceinline__ u64 best() const {
+        u64 m = win[0][0];
+#pragma unroll
+        for (int e = 1; e < LPT; e++) m = min_u64(m, win[e][0]);
+        return m;
+    }
+    // the list whose head is m (if this thread owns it) moves on; true for the owner
+    __device__ __forceinline__ bool advance(u64 m, int k) {
+        bool mine = false;
+#pragma unroll
+        for (int e = 0; e < LPT; e++)
+            if (win[e][0] == m) {
+                mine = true;
+                used[e]++;
+#pragma unroll
+                for (int i = 0; i + 1 < MERGE_WIN; i++) win[e][i] = win[e][i + 1];
+                win[e][MERGE_WIN - 1] = KEY_PAD;
+                if ((used[e] & (MERGE_WIN - 1)) == 0 && used[e] < k) {  // the window ran out and the list goes on
+                    request(e, used[e], k);
+                    settle(e);
+                    mask(e, used[e], k, true);
+                }
+            }
+        return mine;
+    }
+};
+
+// merge_rounds' lists (any k; a block barrier per round): the head AND the key behind it in registers, the key after
+// that requested the moment a list wins -- a list that wins round after round finds its next key already on the way,
+// where a window that refills on demand would stand a bare trip every MERGE_WIN wins on top of the barrier.
+template <int NT, int LPT>
+struct ListHeadsRounds {
     const u64* lst[LPT];
     int pos[LPT];
     u64 cur[LPT], nxt[LPT];
@@ -93,7 +193,7 @@ template <int NT, int LPT, typename Emit>
 __device__ __forceinline__ void merge_rounds(const MergeParams& p, const u64* base, u64 (*wmin)[NT / 64], Emit emit) {
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: a scalar
     const int k = p.k;
-    ListHeads<NT, LPT> h;
+    ListHeadsRounds<NT, LPT> h;
     h.load(p, base);
     for (int r = 0; r < k; r++) {
         u64 m = wave_min_u64(h.best());
@@ -127,12 +227,14 @@ struct MergeFastScratch {
     int rank[64];
     int need_full;
 };
-__device__ __forceinline__ void merge_waves(const MergeParams& p, const u64* base, MergeFastScratch& s, u64* out) {
+template <typename Between>
+__device__ __forceinline__ void merge_waves(const MergeParams& p, const u64* base, MergeFastScratch& s, u64* out,
+                                            Between between) {
     constexpr int NW = MERGE_THREADS / 64, LPT = MERGE_LISTS_MAX / MERGE_THREADS;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: a scalar
     const int k = p.k;
     ListHeads<MERGE_THREADS, LPT> h;
-    h.load(p, base);
+    h.load(p, base, between);
     DBG_STAMP(p.dbg, 1);
     u64 mine = KEY_PAD;  // lane r keeps the wave's r-th smallest key
     const int pre = k < MERGE_PRE ? k : MERGE_PRE;
@@ -194,6 +296,10 @@ __device__ __forceinline__ void merge_waves(const MergeParams& p, const u64* bas
     }
 }
 
+__device__ __forceinline__ void merge_waves(const MergeParams& p, const u64* base, MergeFastScratch& s, u64* out) {
+    merge_waves(p, base, s, out, [] {});
+}
+
 // RERANK (float32 L2 indexes): the k = kc merged keys are lower-bound keys of the scan; they stay in
 // LDS and rerank_block (ise_exact.hpp) turns them into the exact top xp.k.
 template <bool RERANK>
@@ -215,9 +321,13 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(const MergeParams 
     if (RERANK) {
         u64* kin = reinterpret_cast<u64*>(smem_mr + (size_t)xp.dp * 4);
         DBG_STAMP(xp.stats ? xp.stats + 8 : nullptr, 0);
-        rerank_stage_query<MERGE_THREADS>(xp, q, smem_mr);  // its loads fly while the lists are merged
-        if (k <= MERGE_FAST_K) merge_waves(p, base, fast, kin);
-        else merge_rounds<MERGE_THREADS, LPT>(p, base, wmin, [&](int r, u64 key) { kin[r] = key; });
+        // the query is staged behind the requests for the lists' windows: one trip for both
+        if (k <= MERGE_FAST_K) {
+            merge_waves(p, base, fast, kin, [&] { rerank_stage_query<MERGE_THREADS>(xp, q, smem_mr); });
+        } else {
+            rerank_stage_query<MERGE_THREADS>(xp, q, smem_mr);
+            merge_rounds<MERGE_THREADS, LPT>(p, base, wmin, [&](int r, u64 key) { kin[r] = key; });
+        }
         rerank_block<MERGE_THREADS>(xp, q, smem_mr, nullptr);  // starts with a block barrier
     } else if (k <= MERGE_FAST_K) {
         merge_waves(p, base, fast, res);
