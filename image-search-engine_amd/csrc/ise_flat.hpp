@@ -42,7 +42,9 @@ struct ise_index {
     // the stream of the index's previous search (search_enqueue, under mu_): a batch on another one is pipelined
     hipStream_t prev_stream = nullptr;
     bool prev_search = false;
-    unsigned long long* stats_dev = nullptr;  // [4]: reranked queries, exact-scan queries
+    // [32]: 0 reranked queries, 1 exact-scan queries, 2 queries the large-batch path's plain select found incomplete
+    // (ISE_STAT_GEMM_LOST), 8..23 the merge stage's debug stamps
+    unsigned long long* stats_dev = nullptr;
     unsigned long long mu_updates = 0;
     unsigned long long gemm_chunks = 0;  // query chunks that took the large-batch path
     // workspaces (grown lazily, guarded by mu): NWS slots, so searches on different streams

@@ -254,9 +254,11 @@ __global__ __launch_bounds__(512, 2) void gemm_scan_bf16_kernel(const GemmScanPa
 // One block per query: sort its candidates, emit the k best as they are (no re-rank for bf16 rows / inner
 // product).  Incomplete candidates (an overflowed buffer) raise the rerun flag instead: the host has the
 // streaming passes queued behind this kernel, gated on that flag, and they rewrite every query of the chunk.
+// lost_queries: the index's counter of such queries (ise_index_gemm_stats), one add per query that raises the flag.
 // LDS: capq + 320 keys (candidates, selection scratch, the k best).
 __global__ __launch_bounds__(256) void gemm_select_plain_kernel(const u64* cand, const unsigned int* ccnt, int capq,
-                                                                const unsigned int* overflow, unsigned int* rerun, int k,
+                                                                const unsigned int* overflow, unsigned int* rerun,
+                                                                unsigned long long* lost_queries, int k,
                                                                 int metric, float* D, long long* I, u64* keys_out) {
     extern __shared__ __align__(16) unsigned char smem_sp[];
     u64* srt = reinterpret_cast<u64*>(smem_sp);
@@ -272,7 +274,10 @@ __global__ __launch_bounds__(256) void gemm_select_plain_kernel(const u64* cand,
         off[s_ + 1] = off[s_] + (int)min(c_, (unsigned)caps);
     }
     if (lost) {
-        if (tid == 0) *rerun = 1u;
+        if (tid == 0) {
+            *rerun = 1u;
+            if (lost_queries) atomicAdd(lost_queries, 1ull);
+        }
         return;
     }
     const int cnt = off[GEMM_SUBS];

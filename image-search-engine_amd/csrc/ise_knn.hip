@@ -1079,6 +1079,7 @@ static bool gemm_applies(const ise_index* h, long long nq, int k) {
     return k + exact_extra(k) <= XPASS_MAX;                       // the select stage hands at most 32 candidates to the re-rank
 }
 #define GEMM_CAPW 2048 /* entries of a wave's candidate buffer (expected fill: a few hundred) */
+#define ISE_STAT_GEMM_LOST 2 /* slot of stats_dev: queries gemm_select_plain_kernel found incomplete (ise_index_gemm_stats) */
 struct GemmLayout {
     size_t qprep, xn, tau, ccnt, dump, cand, wbuf, wcnt, total;
 };
@@ -1418,8 +1419,8 @@ static int search_large_chunk(ise_index* h, ise_index::WorkSlot* w, const float*
         if ((rc = enqueue_exact_fallback(h, w, pl, xp, nq, st))) return rc;
     } else {
         hipLaunchKernelGGL(gemm_select_plain_kernel, dim3((unsigned)nq), dim3(256), (size_t)(GEMM_CAPQ + 320) * 8, st, (const u64*)cand,
-                           (const unsigned int*)ccnt, GEMM_CAPQ, (const unsigned int*)overflow, rerun, k, h->metric, D_dev, I_dev,
-                           keys_out);
+                           (const unsigned int*)ccnt, GEMM_CAPQ, (const unsigned int*)overflow, rerun,
+                           h->stats_dev + ISE_STAT_GEMM_LOST, k, h->metric, D_dev, I_dev, keys_out);
         HIP_TRY(hipGetLastError());
         // incomplete candidates anywhere in the chunk: the streaming passes answer the whole chunk instead
         rc = make_plan(h, nq, k, &pl, /*allow_short=*/false);  // a gated rerun: the streaming kernels carry the gate
@@ -2018,6 +2019,18 @@ extern "C" int ise_index_stats(ise_index_t* h, uint64_t* out4) {
     out4[1] = tmp[1];
     out4[2] = h->mu_updates;
     out4[3] = h->gemm_chunks;
+    return ISE_OK;
+}
+
+extern "C" int ise_index_gemm_stats(ise_index_t* h, uint64_t* out2) {
+    if (!h || !out2) return fail(ISE_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu_);
+    DeviceGuard gd(h->device);
+    HIP_TRY(hipDeviceSynchronize());
+    unsigned long long lost = 0;
+    HIP_TRY(hipMemcpy(&lost, h->stats_dev + ISE_STAT_GEMM_LOST, sizeof(lost), hipMemcpyDeviceToHost));
+    out2[0] = h->gemm_chunks;
+    out2[1] = lost;
     return ISE_OK;
 }
 

@@ -479,6 +479,12 @@ class IndexFlat(_RemovableIndex):
         shift vector."""
         return _counters(_n.lib.ise_index_stats, self._h, ("reranked", "exact_scan", "shift_updates", "gemm_chunks"))
 
+    def gemm_stats(self) -> dict:
+        """The large-batch path (include/ise_knn.h, ise_index_gemm_stats): query chunks that took it, and queries of
+        the flavours without a re-rank (float32 inner product, bf16 rows) whose candidates it left incomplete, so that
+        the streaming passes rewrote their chunk."""
+        return _counters(_n.lib.ise_index_gemm_stats, self._h, ("gemm_chunks", "gemm_lost_queries"))
+
     def host_stats(self) -> dict:
         """Combining of concurrent ``search`` calls (include/ise_knn.h, ise_index_host_stats): how many
         shared batches ran and how many calls they served; and how many queries the direct small-batch

@@ -96,6 +96,11 @@ int ise_index_get_shift(ise_index_t* h, float* mu_host);
  *   the exact scan, out4[2] refreshes of the shift vector, out4[3] query chunks (<= 1024 queries) that
  *   took the large-batch GEMM-shaped path (nq >= 64).  Blocks. */
 int ise_index_stats(ise_index_t* h, uint64_t* out4);
+/* The large-batch path alone: out2[0] = out4[3] above; out2[1] = queries of the flavours without a re-rank (float32
+ * inner product, bf16 rows) whose candidates the pass left incomplete (a candidate buffer overflowed), so that the
+ * streaming passes queued behind the chunk rewrote it: same results, at the streaming passes' cost.  A float32 L2
+ * query in that state goes to the exact scan and counts in out4[1].  Blocks. */
+int ise_index_gemm_stats(ise_index_t* h, uint64_t* out2);
 
 /* Short indexes (a batch of <= 16 queries, k + spare candidates <= 32, at most 32 row tiles of 16 rows per
  * block of the grid: <= 262k rows on an MI355X) are scanned by short_scan_kernel (csrc/ise_short_scan.hpp: the

@@ -38,6 +38,7 @@ def test_argument_errors_through_abi():
     assert n.lib.ise_index_create(None, 8, n.METRIC_L2, 0) == n.E_INVALID
     assert n.lib.ise_index_destroy(None) == 0
     assert n.lib.ise_index_search_host(None, None, 1, 1, None, None) == n.E_INVALID
+    assert n.lib.ise_index_gemm_stats(None, None) == n.E_INVALID
     assert n.lib.ise_normalize_rows_host(None, 3, 4, 0) == n.E_INVALID
     assert n.lib.ise_merge_keys_device(None, 1, 1, 1, 1, None, None, 0, None) == n.E_INVALID
 

@@ -4,6 +4,7 @@ or kind.  New private names and new intermediate bases are allowed; nothing reco
 
 The fixture was written by ``describe_surface`` below, from the module as it stood before its index kinds began to
 share their Python code:  python -m tests.test_compat_surface > tests/golden/faiss_compat_surface.json
+``gemm_stats`` of the flat index kinds, a reader added since, was recorded in it from the same function's output.
 
 A second fixture, tests/golden/faiss_compat_surface_coded.json, holds the 16 public names of the kinds that came after
 the first was recorded (``_CODED`` below), with the attributes of a class that do not start with ``_`` plus ``__init__``

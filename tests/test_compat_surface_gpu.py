@@ -53,6 +53,7 @@ def test_every_reader_returns_its_keys_and_types():
     assert (flat.ntotal, binary.ntotal, ivf.ntotal) == (200, 200, 200)
 
     _check(flat.exact_stats(), {"reranked": int, "exact_scan": int, "shift_updates": int, "gemm_chunks": int})
+    _check(flat.gemm_stats(), {"gemm_chunks": int, "gemm_lost_queries": int})
     _check(flat.host_stats(), {"combined_batches": int, "combined_calls": int, "direct_queries": int})
     _check(flat.short_stats(), {"short_batches": int})
     _check(flat.half_stats(), {"half_batches": int})

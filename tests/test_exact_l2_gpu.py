@@ -595,6 +595,7 @@ def test_bf16_large_batch_gemm_path(faiss, metric, d, nq, k):
     index.add(xb)
     D, I = index.search(xq, k)
     assert index.exact_stats()["gemm_chunks"] == 1
+    assert index.gemm_stats()["gemm_lost_queries"] == 0, "the pass answered: no rerun through the streaming passes"
     D_ref, I_ref = ko.knn_exact(rb, rq, k, metric)
     assert_knn_matches(D, I, D_ref, I_ref, rb, rq, metric, gap=ko.kth_gap(rb, rq, k, metric))
     if metric == ko.METRIC_INNER_PRODUCT:
@@ -621,6 +622,7 @@ def test_bf16_large_batch_overflow_reruns_through_the_streaming_passes(faiss):
     index.add(xb)
     D, I = index.search(xq, k)
     assert index.exact_stats()["gemm_chunks"] == 1
+    assert index.gemm_stats()["gemm_lost_queries"] >= 1, "the overflow must show as lost queries"
     assert (I == dup[:k][None, :]).all(), "ties must resolve to the lowest ids"
     D_ref, I_ref = ko.knn_exact(rb, rq, k, ko.METRIC_INNER_PRODUCT)
     assert_knn_matches(D, I, D_ref, I_ref, rb, rq, ko.METRIC_INNER_PRODUCT)
@@ -642,6 +644,7 @@ def test_f32_inner_product_large_batch_gemm_path(faiss, d, nq, k):
     index.add(xb)
     D, I = index.search(xq, k)
     assert index.exact_stats()["gemm_chunks"] == (nq + 1023) // 1024
+    assert index.gemm_stats()["gemm_lost_queries"] == 0, "the pass answered: no rerun through the streaming passes"
     D_ref, I_ref = ko.knn_exact(xb, xq, k, IP)
     assert_knn_matches(D, I, D_ref, I_ref, xb, xq, IP, gap=ko.kth_gap(xb, xq, k, IP))
     before = index.exact_stats()["gemm_chunks"]
@@ -665,6 +668,7 @@ def test_f32_inner_product_large_batch_overflow_reruns_through_the_streaming_pas
     index.add(xb)
     D, I = index.search(xq, k)
     assert index.exact_stats()["gemm_chunks"] == 1
+    assert index.gemm_stats()["gemm_lost_queries"] >= 1, "the overflow must show as lost queries"
     assert (I == dup[:k][None, :]).all(), "ties must resolve to the lowest ids"
     D_ref, I_ref = ko.knn_exact(xb, xq, k, IP)
     assert_knn_matches(D, I, D_ref, I_ref, xb, xq, IP)

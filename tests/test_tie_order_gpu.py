@@ -54,7 +54,7 @@ def _ref(xb, xq, k, metric, id_offset=0):
 
 
 def _routes(index):
-    return {**index.exact_stats(), **index.host_stats(), **index.short_stats()}
+    return {**index.exact_stats(), **index.host_stats(), **index.short_stats(), **index.gemm_stats()}
 
 
 def _delta(index, before):
@@ -287,6 +287,8 @@ def test_gemm_path_tie_order(faiss, metric, storage, nq, kind):
     assert dt["gemm_chunks"] == 1
     if kind == "overflow" and metric == L2 and storage == "f32":
         assert dt["exact_scan"] == nq, "an overflowed candidate array must send its query to the exact scan"
+    if not (metric == L2 and storage == "f32"):  # the flavours without a re-rank count the queries they lose
+        assert dt["gemm_lost_queries"] >= 1 if kind == "overflow" else dt["gemm_lost_queries"] == 0, dt
     D_ref, I_ref = _ref(xb, xq, k, metric)
     assert_knn_identical(D, I, D_ref, I_ref, "GEMM path")
     step = 64 if storage == "bf16" else 128
