@@ -97,7 +97,11 @@ static int sel_chunk_enqueue(ise_index* h, ise_index::SelSlot* sl, const ise_sel
     sp.tiles_per_block = (span + nb - 1) / nb;
     nb = (span + sp.tiles_per_block - 1) / sp.tiles_per_block;
     const int groups = (int)((m + 15) / 16);
-    // results per pass: XPASS_MAX, or what the wave lists' LDS holds beside long query rows (d = 2048: 19)
+    // results per pass: XPASS_MAX, or what the wave lists' LDS holds beside long query rows (float32 d = 2048: 23; the
+    // longest rows, float32 d = 2240 and bf16 d = 4480: 10).  The kp < 1 test below is not reachable on this index:
+    // range_staging above has failed with make_plan's "d too large" for every row longer than those, whose stride of
+    // 2248 units still leaves 10 results.  It stays as the guard of this function's own LDS arithmetic
+    // (tests/test_flat_shapes_gpu.py, test_rows_too_long_are_refused_by_the_plan)
     static_assert(XPASS_MAX == SEL_KPASS_MAX, "one masked pass yields what one exact pass yields");
     const long long lds_left = (long long)LDS_LIMIT - (long long)range_lds_bytes(sp.qs_stride);
     const int kp = (int)std::min<long long>(std::min(k, XPASS_MAX), lds_left / (SEL_W * 16 * 8));

@@ -2,7 +2,9 @@
 
 (A) ``filter_ranking``: the complete ranking of an UNFILTERED search (``index.search(x, n)``), with the ids a selector
     rejects dropped on the host, cut at k and padded as ``search`` pads.
-(B) ``sub_index_search``: a fresh index of ``x[members]``, its ids mapped back through ``np.flatnonzero(members)``."""
+(B) ``sub_index_search``: a fresh index of ``x[members]``, its ids mapped back through ``np.flatnonzero(members)``.
+(C) ``knn_of_scores`` / ``masked_knn_brute``: the k best among a member mask straight from float64 brute-force scores
+    (tests/range_ref.py, ``scores_f64``) -- no index takes part, so an error shared by every kernel cannot cancel."""
 import numpy as np
 
 FLT_MAX = np.float32(np.finfo(np.float32).max)
@@ -38,6 +40,28 @@ def sub_index_search(make_index, xb, members, xq, k, metric):
     out = np.full(I.shape, -1, dtype=np.int64)
     out[I >= 0] = rows[I[I >= 0]]
     return D, out
+
+
+def knn_of_scores(S, members, k, metric):
+    """The k best rows among a member mask (bool (n,)) from float64 scores S (nq, n), ties by ascending id, padded as
+    ``search`` pads: (D (nq, k) float32, I (nq, k) int64).  Independent of any index."""
+    S = np.asarray(S, dtype=np.float64)
+    rows = np.flatnonzero(np.asarray(members, dtype=bool))
+    D = np.full((S.shape[0], k), pad_value(metric), dtype=np.float32)
+    I = np.full((S.shape[0], k), -1, dtype=np.int64)
+    for q in range(S.shape[0]):
+        s = S[q, rows]
+        order = np.lexsort((rows, s if metric == L2 else -s))[:k]
+        D[q, :len(order)] = s[order].astype(np.float32)
+        I[q, :len(order)] = rows[order]
+    return D, I
+
+
+def masked_knn_brute(xb, xq, members, k, metric):
+    """knn_of_scores over the float64 brute-force scores of (xb, xq)."""
+    from tests.range_ref import scores_f64
+
+    return knn_of_scores(scores_f64(xb, xq, metric), members, k, metric)
 
 
 def filter_range(res, members):
