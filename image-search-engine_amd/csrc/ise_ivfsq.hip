@@ -117,16 +117,9 @@ int rebuild_locked(ise_ivfsq* h, hipStream_t st) {
     HIP_TRY(hipMalloc((void**)&nr, slots * sizeof(double)));
     int rc = inv.begin_rebuild(pl, SQ_TILE, st, meta_host, &nids, &nmeta, &dest);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(nx, 0, slots * h->stride, st));  // pad slots read as zero rows
-    HIP_TRY(hipMemsetAsync(nr, 0, slots * sizeof(double), st));
-    HIP_TRY(hipMemsetAsync(nids, 0xFF, slots * sizeof(uint32_t), st));
-    if (inv.tiles > 0)
-        hipLaunchKernelGGL(ivfsq_move_tiles_kernel, dim3((unsigned)inv.tiles), dim3(256), 0, st, (const uint8_t*)h->codes,
-                           (const double*)h->rterm, (const uint32_t*)inv.ids, inv.tile_list_dev(), inv.list_tile0_dev(),
-                           (const uint32_t*)nmeta, h->stride, nx, nr, nids);
-    hipLaunchKernelGGL(ivfsq_scatter_rows_kernel, dim3((unsigned)((inv.pend_n + 3) / 4)), dim3(256), 0, st, (const uint8_t*)h->pend,
-                       (const double*)h->pend_rterm, inv.pend_n, (const uint32_t*)dest, (uint32_t)(inv.n - inv.pend_n), h->stride, nx,
-                       nr, nids);
+    HIP_TRY(ivfsq_rebuild_launch(h->codes, h->rterm, inv.ids, inv.meta, inv.tiles, h->pend, h->pend_rterm, inv.pend_n, dest,
+                                 (uint32_t)(inv.n - inv.pend_n), h->stride, inv.nlist, nmeta, (long long)pl.tile0[(size_t)inv.nlist], nx,
+                                 nr, nids, st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     std::swap(h->codes, nx);  // the old arrays go with the guard (hipFree waits for the passes that still read them)
@@ -191,15 +184,8 @@ int search_enqueue(ise_ivfsq* h, const float* q_dev, long long nq, int k, const 
         const int m = (int)std::min<long long>(SQ_STAGE_CHUNK, nq - c0);
         const int groups = (m + qt - 1) / qt;
         h->codec.stage_launch(q_dev + (size_t)c0 * h->d, m, ip, h->qrec.p, st);
-        HIP_TRY(hipMemsetAsync(h->masks.p, 0, (size_t)groups * nl * sizeof(uint32_t), st));
-        const long long ptot = (long long)m * nprobe;
-        hipLaunchKernelGGL(ivf_mask_kernel, dim3((unsigned)((ptot + 255) / 256)), dim3(256), 0, st, probes_dev + (size_t)c0 * nprobe,
-                           ptot, nprobe, inv.nlist, h->qshift, h->masks.p);
-        hipLaunchKernelGGL(ivfsq_offsets_kernel, dim3((unsigned)groups), dim3(256), 0, st, (const uint32_t*)h->masks.p,
-                           inv.list_tile0_dev(), inv.nlist, h->offs.p, counts);
-        hipLaunchKernelGGL(ivfsq_work_kernel, dim3((unsigned)((inv.tiles + 255) / 256), (unsigned)groups), dim3(256), 0, st,
-                           (const uint32_t*)h->masks.p, (const uint32_t*)h->offs.p, inv.list_tile0_dev(), inv.list_size_dev(),
-                           inv.tile_list_dev(), inv.nlist, (uint32_t)inv.tiles, h->work.p);
+        HIP_TRY(ivfsq_work_list_launch(probes_dev + (size_t)c0 * nprobe, m, nprobe, inv.nlist, h->qshift, inv.meta, (uint32_t)inv.tiles,
+                                       h->masks.p, h->offs.p, counts, h->work.p, st));
         for (int g = 0; g < groups; g++) {
             const long long q0 = c0 + (long long)g * qt;
             const int nqt = (int)std::min<long long>(qt, nq - q0);

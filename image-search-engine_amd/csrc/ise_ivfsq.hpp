@@ -17,7 +17,12 @@
 //              b takes entries b SQ_WAVES + w + j gridDim.x SQ_WAVES.  The key is ord(score) << 32 | ids[slot]; keys are
 //              unique and compared in full, so ties go by ascending id however the lists order the ids.
 // The staging record, the selection (ise_cand.hpp), the pass's merge and the floor-keyed repeat for k > 32 are ise_sq.hpp's.
+//
+// The launches of the work list and of the rebuild are the two host functions at the end, ivfsq_work_list_launch and
+// ivfsq_rebuild_launch: ise_ivfsq.hip calls them, and so does the test harness (tests/native/ivfsq_lists_harness.hip),
+// which therefore runs the product's grids and not a copy of them.
 #pragma once
+#include "ise_ivf_lists.hpp"
 #include "ise_sq.hpp"
 
 struct SqIvfScanParams {
@@ -119,4 +124,48 @@ static __global__ __launch_bounds__(256) void ivfsq_scatter_rows_kernel(const ui
         dst_rterm[slot] = pend_rterm[i];
         dst_ids[slot] = id0 + (uint32_t)i;
     }
+}
+
+// ---------------------------------------------------------------- the launches (ise_ivfsq.hip and the test harness)
+// Both enqueue on st and return the first error of a memset; the caller takes hipGetLastError() for the launches.
+// meta: ivf_plan_meta's table (ise_ivf_plan.hpp) of nlist lists.
+//
+// the work lists of m queries' probes [m][nprobe]: masks [groups][nlist] (cleared here), offs [groups][nlist], counts
+// [groups], work [groups][tiles], groups = ceil(m / 2^qshift).  m, nprobe >= 1; without a tile no entry is written
+inline hipError_t ivfsq_work_list_launch(const long long* probes, int m, int nprobe, int nlist, int qshift, const uint32_t* meta,
+                                         uint32_t tiles, uint32_t* masks, uint32_t* offs, uint32_t* counts, u32x4* work,
+                                         hipStream_t st) {
+    const int groups = (m + (1 << qshift) - 1) >> qshift;
+    const hipError_t e = hipMemsetAsync(masks, 0, (size_t)groups * nlist * sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    const long long ptot = (long long)m * nprobe;
+    hipLaunchKernelGGL(ivf_mask_kernel, dim3((unsigned)((ptot + 255) / 256)), dim3(256), 0, st, probes, ptot, nprobe, nlist, qshift,
+                       masks);
+    hipLaunchKernelGGL(ivfsq_offsets_kernel, dim3((unsigned)groups), dim3(256), 0, st, (const uint32_t*)masks, meta, nlist, offs,
+                       counts);
+    if (tiles > 0)
+        hipLaunchKernelGGL(ivfsq_work_kernel, dim3((tiles + 255) / 256, (unsigned)groups), dim3(256), 0, st, (const uint32_t*)masks,
+                           (const uint32_t*)offs, meta, meta + ivf_meta_size_at((size_t)nlist),
+                           meta + ivf_meta_tile_list_at((size_t)nlist), nlist, tiles, work);
+    return hipSuccess;
+}
+
+// the new arrays nx / nr / nids of new_tiles tiles (table nmeta): cleared (pad slots are zero rows with id ~0), the
+// old_tiles old tiles (table meta; not read without an old tile) moved, the pend_n >= 1 pending rows scattered to dest
+// with the ids id0, id0 + 1, ..
+inline hipError_t ivfsq_rebuild_launch(const uint8_t* codes, const double* rterm, const uint32_t* ids, const uint32_t* meta,
+                                       long long old_tiles, const uint8_t* pend, const double* pend_rterm, long long pend_n,
+                                       const uint32_t* dest, uint32_t id0, int stride, int nlist, const uint32_t* nmeta,
+                                       long long new_tiles, uint8_t* nx, double* nr, uint32_t* nids, hipStream_t st) {
+    const size_t slots = (size_t)new_tiles * SQ_TILE;
+    hipError_t e = hipMemsetAsync(nx, 0, slots * stride, st);  // pad slots read as zero rows
+    if (e == hipSuccess) e = hipMemsetAsync(nr, 0, slots * sizeof(double), st);
+    if (e == hipSuccess) e = hipMemsetAsync(nids, 0xFF, slots * sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    if (old_tiles > 0)
+        hipLaunchKernelGGL(ivfsq_move_tiles_kernel, dim3((unsigned)old_tiles), dim3(256), 0, st, codes, rterm, ids,
+                           meta + ivf_meta_tile_list_at((size_t)nlist), meta, nmeta, stride, nx, nr, nids);
+    hipLaunchKernelGGL(ivfsq_scatter_rows_kernel, dim3((unsigned)((pend_n + 3) / 4)), dim3(256), 0, st, pend, pend_rterm, pend_n, dest,
+                       id0, stride, nx, nr, nids);
+    return hipSuccess;
 }

@@ -1,5 +1,5 @@
 """CPU tests of IndexIVFScalarQuantizer's host side: the "IwSq" file image, the numpy reference of the GPU tests, the
-pass rule, what raises before the device is touched, and the rebuild plan with 64-row tiles under the host sanitizers."""
+pass rule, the reference of the work list and of the rebuilt arrays, what raises before the device is touched, and the rebuild plan with 64-row tiles under the host sanitizers."""
 import ctypes
 import struct
 
@@ -169,6 +169,85 @@ def test_pass_rule():
     assert ivfsq_ref.pass_tile_sets(probes, sizes, 2048) == [[0], [5, 6], [1]]
     assert ivfsq_ref.stats_of(probes, sizes, 2048, 64) == {"batches": 1, "passes": 6, "tiles_loaded": 8}
     assert ivfsq_ref.stats_of(probes, sizes, 512, 64) == {"batches": 1, "passes": 4, "tiles_loaded": 8}
+
+
+@pytest.mark.parametrize("d", [24, 2048])  # groups of 16 and of 8 queries
+def test_work_list_reference(d):
+    """``masks_of`` / ``work_list_of`` on random tables against ``pass_tile_sets`` and ``stats_of``: the entries of a
+    group are the tiles of its pass, ascending, each with the rows its list has left and the mask of the queries that
+    name the list; the offsets are the running count, on the unprobed lists too."""
+    qt = sq_ref.qt_of(d)
+    rng = np.random.default_rng(d)
+    for trial in range(30):
+        nlist = int(rng.integers(1, 400))
+        sizes = rng.choice([0, 0, 1, 63, 64, 65, 128, 129, 300], nlist)
+        nq, nprobe = int(rng.integers(1, 70)), int(rng.integers(1, 9))
+        probes = rng.integers(-3, nlist + 3, (nq, nprobe))
+        if trial % 5 == 0:
+            probes[:] = -1
+        masks = ivfsq_ref.masks_of(probes, nlist, qt)
+        assert masks.dtype == np.uint32 and masks.shape == (-(-nq // qt), nlist) and (masks >> qt == 0).all()
+        for q in range(nq):
+            named = {int(l) for l in probes[q] if 0 <= l < nlist}
+            assert set(np.flatnonzero(masks[q // qt] >> (q % qt) & 1).tolist()) == named
+        wl = ivfsq_ref.work_list_of(masks, sizes)
+        sets = ivfsq_ref.pass_tile_sets(probes, sizes, d)
+        t0, meta = ivfsq_ref.tile0_of(sizes), ivfsq_ref.meta_of(sizes)
+        assert np.array_equal(meta[:nlist + 1], t0) and np.array_equal(meta[nlist + 1:2 * nlist + 1], sizes) and len(meta) == 2 * nlist + 1 + t0[-1]
+        assert len(wl) == len(sets) == len(masks)
+        for g, ((offs, count, entries), tiles) in enumerate(zip(wl, sets)):
+            assert offs.dtype == entries.dtype == np.uint32 and entries.shape == (count, 4) and count == len(tiles)
+            assert entries[:, 0].tolist() == tiles and (entries[:, 3] == 0).all()
+            lists = meta[2 * nlist + 1:][entries[:, 0]]
+            assert np.array_equal(entries[:, 2], masks[g][lists]) and (entries[:, 2] != 0).all()
+            assert np.array_equal(entries[:, 1], np.minimum(64, sizes[lists] - 64 * (entries[:, 0] - t0[lists])))
+            assert (entries[:, 1] >= 1).all()
+            run = 0
+            for l in range(nlist):
+                assert offs[l] == run
+                run += int(t0[l + 1] - t0[l]) if masks[g][l] else 0
+            assert run == count
+        for k in (10, 70):
+            assert ivfsq_ref.stats_of(probes, sizes, d, k)["tiles_loaded"] == sum(c for _, c, _ in wl) * -(-k // 32)
+    # hand-counted (test_pass_rule's table): lists 4 and 6 of sizes 65 and 129
+    masks = ivfsq_ref.masks_of(np.array([[4, 4], [0, -1], [7, 6], [-1, -1]]), 7, qt)
+    assert masks.tolist() == [[2, 0, 0, 0, 1, 0, 4]]
+    (offs, count, entries), = ivfsq_ref.work_list_of(masks, [0, 1, 63, 64, 65, 128, 129])
+    assert offs.tolist() == [0, 0, 0, 0, 0, 2, 2] and count == 5
+    assert entries.tolist() == [[3, 64, 1, 0], [4, 1, 1, 0], [7, 64, 4, 0], [8, 64, 4, 0], [9, 1, 4, 0]]
+
+
+def test_rebuilt_reference():
+    """``rebuilt`` in two steps is ``rebuilt`` in one; every list holds its ids ascending, its rows' bytes and terms,
+    and pad slots behind them; ``rebuild_dest`` names the slot each pending row lands in."""
+    rng = np.random.default_rng(77)
+    nlist, stride, n = 23, 32, 1500
+    lists = np.minimum(rng.integers(0, nlist + 8, n), nlist - 1)  # the last list is long
+    lists[lists == 3] = 4                                        # list 3 stays empty
+    codes = rng.integers(0, 256, (n, stride)).astype(np.uint8)
+    terms = rng.random(n)
+    none = (np.zeros(nlist, np.int64), np.zeros(0, np.uint32), np.zeros((0, stride), np.uint8))
+    one = ivfsq_ref.rebuilt(*none, lists, codes, 0, stride, np.zeros(0), terms)
+    cut = 611
+    half = ivfsq_ref.rebuilt(*none, lists[:cut], codes[:cut], 0, stride, np.zeros(0), terms[:cut])
+    two = ivfsq_ref.rebuilt(half[0], half[3], half[1], lists[cut:], codes[cut:], cut, stride, half[2], terms[cut:])
+    for a, b in zip(one, two):
+        assert a.dtype == b.dtype and np.array_equal(a, b)
+    sizes, new_codes, new_terms, ids = one
+    assert sizes.tolist() == np.bincount(lists, minlength=nlist).tolist() and sizes[3] == 0 and sizes[-1] > 128
+    t0 = ivfsq_ref.tile0_of(sizes)
+    assert len(ids) == 64 * t0[-1] and ids.dtype == np.uint32 and new_codes.shape == (len(ids), stride)
+    for l, want in enumerate(ivf_ref.list_members(lists, nlist)):
+        a, m = 64 * t0[l], len(want)
+        assert np.array_equal(ids[a:a + m], want) and np.array_equal(new_codes[a:a + m], codes[want])
+        assert np.array_equal(new_terms[a:a + m], terms[want])
+        pad = slice(a + m, 64 * t0[l + 1])
+        assert (ids[pad] == ivfsq_ref.PAD_ID).all() and not new_codes[pad].any() and not new_terms[pad].any()
+    dest = ivfsq_ref.rebuild_dest(half[0], lists[cut:])
+    assert dest.dtype == np.uint32 and np.array_equal(ids[dest], cut + np.arange(n - cut)) and len(set(dest.tolist())) == n - cut
+    # the default row term: the sum of the squared bytes
+    dflt = ivfsq_ref.rebuilt(*none, lists[:9], codes[:9], 0, stride)
+    assert np.array_equal(dflt[2][dflt[3] != ivfsq_ref.PAD_ID], (codes[:9].astype(np.float64) ** 2).sum(1)[dflt[3][dflt[3] != ivfsq_ref.PAD_ID]])
 
 
 def test_early_raises():
