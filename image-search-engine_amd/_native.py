@@ -23,6 +23,9 @@ METRIC_L2 = 1
 MAX_K = 2048
 PQ_MAX_M = 64
 SQ_MAX_D = 2048
+LINEAR_MAX_D = 4096
+LINEAR_FEW_ROWS = 64  # n <= this: the few-row launch shape of ise_linear_apply_*
+LINEAR_KSEG = 256  # k entries of one fmaf chain of ise_linear_apply_*
 SQ_8BIT, SQ_8BIT_UNIFORM = 0, 2
 STORE_F32, STORE_BF16 = 0, 1
 
@@ -179,6 +182,12 @@ PROTOTYPES = [
     ("ise_ivfsq_search_host", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp]),
     ("ise_ivfsq_search_device", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp]),
     ("ise_ivfsq_stats", _int, [_vp, _u64p]),
+    ("ise_linear_create", _int, [ctypes.POINTER(_vp), _int, _int, _vp, _vp, _int]),
+    ("ise_linear_destroy", _int, [_vp]),
+    ("ise_linear_info", _int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    ("ise_linear_apply_device", _int, [_vp, _vp, _i64, _vp, _vp]),
+    ("ise_linear_apply_host", _int, [_vp, _vp, _i64, _vp]),
+    ("ise_linear_stats", _int, [_vp, _u64p]),
     ("ise_refresh_env_knobs", _int, []),
     ("ise_comm_precheck", _int, [_int]),
     ("ise_comm_unique_id", _int, [_vp]),

@@ -50,7 +50,7 @@ class Config:
 
     # ---- which pipeline, which index
     METHOD = Method.DNN
-    INDEX_TYPE = "l2"                       # "cosine" | "l2" | "cell-probe-flat" (IndexIVFFlat) | "pq" (IndexPQ) | "pq-refine" (IndexRefineFlat over it) | "sq8" (IndexScalarQuantizer, QT_8bit) | "cell-probe-sq8" (IndexIVFScalarQuantizer over it)  ("cell-probe", IndexIVFPQ, is not composed yet)
+    INDEX_TYPE = "l2"                       # "cosine" | "l2" | "cell-probe-flat" (IndexIVFFlat) | "pq" (IndexPQ) | "pq-refine" (IndexRefineFlat over it) | "sq8" (IndexScalarQuantizer, QT_8bit) | "cell-probe-sq8" (IndexIVFScalarQuantizer over it) | "pca256-l2" (IndexPreTransform: PCAMatrix to 256 dimensions, then IndexFlatL2) | "opq-pq" (IndexPreTransform: OPQMatrix, then IndexPQ)  ("cell-probe", IndexIVFPQ, is not composed yet)
 
     # ---- DNN path
     DNN_MODEL = DnnModels.RESNET

@@ -71,6 +71,16 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          ``IndexFlat.search_subset`` / ``compute_distance_subset`` (the pass on its own),
                                          ``write_index`` / ``read_index`` ("IxRF"); never called by the reference
     write_index_binary / read_index_binary   Faiss's names for IndexBinaryFlat ("IBxF") and IndexBinaryIDMap ("IBMp") files
+    IndexPreTransform(ltrans, index)     Faiss's transform chain in front of any index kind here: ``PCAMatrix`` (mean,
+                                         float64 covariance, ``eigen_power`` for whitening), ``OPQMatrix`` (the
+                                         non-parametric OPQ rotation for an ``IndexPQ``), ``RandomRotationMatrix``,
+                                         ``LinearTransform`` (``A``, ``b``), ``NormalizationTransform``,
+                                         ``CenteringTransform``; ``train`` / ``add`` / ``search`` / ``search_torch`` /
+                                         ``reconstruct`` / ``apply_chain``, ``SearchParametersPreTransform``,
+                                         ``write_index`` / ``read_index`` ("IxPT"); y = A x + b is a HIP kernel whose bits
+                                         depend on ``d_in`` alone (csrc/ise_linear.hpp), so a stored row sent as a query is
+                                         at distance 0; ``IndexRefineFlat`` takes one as its base; never called by the
+                                         reference
 
 All arithmetic runs on the MI355X through ``include/ise_knn.h``; there is no
 CPU path here.  Without the HIP library or without a GPU the constructors and
@@ -1364,14 +1374,15 @@ def write_index(index, path) -> None:
     if isinstance(index, IndexIVFFlat):
         raise NotImplementedError("write_index of an IndexIVFFlat is not provided")
     # the image first: a kind that refuses (an untrained index) leaves what is at ``path`` as it is
-    image = index._image() if isinstance(index, (_CodedIndex, _IndexIVF, IndexRefine, IndexIDMap)) else _flat_image(index)
+    image = index._image() if isinstance(index, (_CodedIndex, _IndexIVF, IndexRefine, IndexIDMap, IndexPreTransform)) \
+        else _flat_image(index)
     with open(str(path), "wb") as f:
         f.write(image)
 
 
 def read_index(path, device: int | None = None):
-    """-> IndexFlat, IndexIDMap, IndexPQ, IndexScalarQuantizer, IndexIVFScalarQuantizer or IndexRefineFlat, as the file
-    was written; the stored rows and codes are added as they are, nothing is encoded again."""
+    """-> IndexFlat, IndexIDMap, IndexPQ, IndexScalarQuantizer, IndexIVFScalarQuantizer, IndexRefineFlat or
+    IndexPreTransform, as the file was written; the stored rows and codes are added as they are, nothing is encoded again."""
     with open(str(path), "rb") as f:
         buf = f.read()
     if buf[:4] in (b"IwFl", b"IwF2"):  # Faiss's fourccs of IndexIVFFlat files
@@ -2457,8 +2468,9 @@ class IndexRefine:
     ``NotImplementedError``): ``range_search``, ``remove_ids`` and ``IndexIDMap`` over this type."""
 
     def __init__(self, base_index, refine_index):
-        assert isinstance(base_index, (IndexFlat, IndexPQ, IndexScalarQuantizer, _IndexIVF)), \
-            "the base index is an IndexFlat, an IndexPQ, an IndexScalarQuantizer, an IndexIVFFlat or an IndexIVFScalarQuantizer"
+        assert isinstance(base_index, (IndexFlat, IndexPQ, IndexScalarQuantizer, _IndexIVF, IndexPreTransform)), \
+            "the base index is an IndexFlat, an IndexPQ, an IndexScalarQuantizer, an IndexIVFFlat, an IndexIVFScalarQuantizer " \
+            "or an IndexPreTransform over one of them"
         assert base_index.ntotal == 0, f"{type(self).__name__} wraps an empty index (Faiss: index is empty on input)"
         assert isinstance(refine_index, IndexFlat) and refine_index.storage == "f32", \
             "the refine index is a float32 IndexFlat"
@@ -2582,3 +2594,647 @@ class IndexRefineFlat(IndexRefine):
                 base._add_codes(stored.codes)
             index.refine_index.add(parts.xb)
         return index
+
+
+# ---------------------------------------------------------------- vector transforms (faiss.VectorTransform, IndexPreTransform)
+_U32 = 2.0 ** -24  # the unit roundoff of float32
+# Rows that are orthonormal in exact arithmetic and then stored as float32: every entry moves by at most u |a_jk|, so
+# a dot product of two stored rows (taken in float64) moves by at most sum_k (2 u + u^2) |a_ik a_jk| <= 2 u + u^2
+# (Cauchy-Schwarz over unit rows).  4 u is twice that: the other half is for the float64 arithmetic (QR, eigh, SVD,
+# a product of two rotations: d 2^-53 per entry) that made the rows.
+_ORTHONORMAL_TOL = 4 * _U32
+
+
+class _LinearHandle(_IndexHandle):
+    """An ``ise_linear`` handle: the matrix as the kernels load it, on one device; immutable."""
+
+    _ABI = "ise_linear"
+
+    def __init__(self, A: np.ndarray, b, device: int):
+        self.device = int(device)
+        self._h = ctypes.c_void_p()
+        d_out, d_in = A.shape
+        _n.check(_n.lib.ise_linear_create(ctypes.byref(self._h), d_in, d_out, A.ctypes.data,
+                                          None if b is None else b.ctypes.data, self.device))
+
+
+class VectorTransform:
+    """faiss.VectorTransform: ``d_in`` -> ``d_out``; ``train(x)``, ``apply(x)`` (numpy in, a fresh numpy array out;
+    ``apply_py`` is the same), ``apply_torch(x)`` (CUDA float32 in and out, enqueued on the current torch stream, no host
+    synchronisation), ``reverse_transform(y)`` where the transform has one."""
+
+    _FOURCC = b""
+
+    def __init__(self, d_in: int = 0, d_out: int = 0):
+        self.d_in, self.d_out = int(d_in), int(d_out)
+        self.is_trained = True
+
+    def train(self, x) -> None:
+        pass
+
+    def _require_trained(self, what: str) -> None:
+        if not self.is_trained:
+            raise RuntimeError(f"{type(self).__name__}.{what} before train")
+
+    def apply(self, x) -> np.ndarray:
+        raise NotImplementedError
+
+    def apply_py(self, x) -> np.ndarray:
+        return self.apply(x)
+
+    def apply_torch(self, x):
+        raise NotImplementedError
+
+    def reverse_transform(self, y) -> np.ndarray:
+        raise RuntimeError(f"reverse_transform is not provided on {type(self).__name__}")
+
+    def _record_body(self) -> bytes:
+        return b""
+
+    def _record(self) -> bytes:
+        """This transform as a record of an "IxPT" file."""
+        return self._FOURCC + self._record_body() + _VT_TAIL.pack(self.d_in, self.d_out, 1 if self.is_trained else 0)
+
+
+class LinearTransform(VectorTransform):
+    """faiss.LinearTransform(d_in, d_out, have_bias): y = A x + b with ``A`` float32 (d_out, d_in) and ``b`` float32
+    (d_out,).  Assigning ``A`` (which also marks the transform trained) or ``b`` drops the device handle; the next
+    ``apply`` / ``apply_torch`` makes it again (include/ise_knn.h, ise_linear_*), so everything else here needs no GPU.
+    The bits of y are a function of ``d_in`` alone: a row transforms to the same float32 values alone
+    or in a batch of a million.  ``d_in`` and ``d_out`` are at most 4096."""
+
+    _FOURCC = b"LTra"
+
+    def __init__(self, d_in: int = 0, d_out: int = 0, have_bias: bool = False):
+        super().__init__(d_in, d_out)
+        self.have_bias = bool(have_bias)
+        self.is_trained = False
+        self.is_orthonormal = False
+        self._A = np.zeros((0, 0), dtype=np.float32)
+        self._b = np.zeros(0, dtype=np.float32)
+        self._lh = None
+        self._hlock = threading.Lock()
+
+    @property
+    def A(self) -> np.ndarray:
+        return self._A
+
+    @A.setter
+    def A(self, A) -> None:
+        A = np.ascontiguousarray(np.asarray(A), dtype=np.float32)
+        assert A.shape == (self.d_out, self.d_in), f"A is (d_out, d_in) = ({self.d_out}, {self.d_in}), got {A.shape}"
+        self._A, self._lh = A, None
+        self.is_trained = True
+        self.is_orthonormal = False
+
+    @property
+    def b(self) -> np.ndarray:
+        return self._b
+
+    @b.setter
+    def b(self, b) -> None:
+        b = np.ascontiguousarray(np.asarray(b), dtype=np.float32).reshape(-1)
+        assert b.size in (0, self.d_out), f"b holds d_out = {self.d_out} entries, got {b.size}"
+        self._b, self._lh = b, None
+        self.have_bias = b.size > 0
+
+    def set_is_orthonormal(self) -> None:
+        """``is_orthonormal``: d_out <= d_in and A A^T (in float64) is the identity within 4 * 2^-24 per entry (the
+        derivation stands at ``_ORTHONORMAL_TOL``)."""
+        self._require_trained("set_is_orthonormal")
+        if self.d_out > self.d_in:
+            self.is_orthonormal = False
+            return
+        A = self._A.astype(np.float64)
+        self.is_orthonormal = bool(np.abs(A @ A.T - np.eye(self.d_out)).max() <= _ORTHONORMAL_TOL)
+
+    def _handle(self, device: int) -> _LinearHandle:
+        with self._hlock:
+            lh = self._lh
+            if lh is None or lh.device != device:
+                lh = self._lh = _LinearHandle(self._A, self._b if self.have_bias else None, device)
+            return lh
+
+    def linear_stats(self) -> dict:
+        """Calls, few-row launches and tiled launches of the current handle (include/ise_knn.h, ise_linear_stats)."""
+        lh = self._lh
+        keys = ("calls", "few_row_launches", "tiled_launches")
+        return dict.fromkeys(keys, 0) if lh is None else _counters(_n.lib.ise_linear_stats, lh._h, keys)
+
+    def apply(self, x) -> np.ndarray:
+        self._require_trained("apply")
+        x = _as_rows(x, self.d_in)
+        y = np.empty((x.shape[0], self.d_out), dtype=np.float32)
+        if x.shape[0]:
+            lh = self._handle(_default_device())
+            _n.check(_n.lib.ise_linear_apply_host(lh._h, x.ctypes.data, x.shape[0], y.ctypes.data))
+        return y
+
+    def apply_torch(self, x):
+        import torch
+
+        self._require_trained("apply")
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d_in
+        x = x.contiguous()
+        y = torch.empty((x.shape[0], self.d_out), dtype=torch.float32, device=x.device)
+        if x.shape[0]:
+            lh = self._handle(x.device.index)
+            st = torch.cuda.current_stream(x.device).cuda_stream
+            _n.check(_n.lib.ise_linear_apply_device(lh._h, x.data_ptr(), x.shape[0], y.data_ptr(), st))
+        return y
+
+    def reverse_transform(self, y) -> np.ndarray:
+        """x = (y - b) A on the host (float64, narrowed once): the inverse when the rows of A are orthonormal
+        (``is_orthonormal``; ``set_is_orthonormal`` decides), otherwise a RuntimeError, as in Faiss."""
+        self._require_trained("reverse_transform")
+        if not self.is_orthonormal:
+            raise RuntimeError("reverse transform not implemented for non-orthonormal matrices")
+        y = _as_rows(y, self.d_out).astype(np.float64)
+        if self.have_bias:
+            y = y - self._b.astype(np.float64)[None, :]
+        return (y @ self._A.astype(np.float64)).astype(np.float32)
+
+    def _record_body(self) -> bytes:
+        return struct.pack("<B", 1 if self.have_bias else 0) + _pack_vector(self._A.astype("<f4")) + \
+            _pack_vector((self._b if self.have_bias else self._b[:0]).astype("<f4"))
+
+
+class RandomRotationMatrix(LinearTransform):
+    """faiss.RandomRotationMatrix(d_in, d_out): ``init(seed)`` takes the Q of the QR factorisation of a Gaussian matrix
+    (float64 on the host, numpy's generator: unpinned against Faiss's own); rows orthonormal when d_out <= d_in,
+    columns otherwise.  ``train`` is ``init(12345)``."""
+
+    _FOURCC = b"rrot"
+
+    def __init__(self, d_in: int = 0, d_out: int = 0):
+        super().__init__(d_in, d_out, False)
+
+    def init(self, seed: int) -> None:
+        lo, hi = min(self.d_in, self.d_out), max(self.d_in, self.d_out)
+        q, _ = np.linalg.qr(np.random.default_rng(int(seed)).standard_normal((hi, lo)))  # (hi, lo), orthonormal columns
+        self.A = q.T if self.d_out <= self.d_in else q
+        self.set_is_orthonormal()
+
+    def train(self, x) -> None:
+        self.init(12345)
+
+
+def _moments(x: np.ndarray, gram: bool):
+    """float32 (n, d) -> (mean float64 (d,), the centred (n, n) Gram matrix Xc Xc^T if ``gram`` else the (d, d) scatter
+    matrix Xc^T Xc, float64 on the host); neither is divided by n.  Sums in float64, on the device when there is one
+    (in pieces of 64k rows), else on the host."""
+    import torch
+
+    n, d = x.shape
+    dev = torch.device("cuda", _default_device()) if torch.cuda.is_available() else torch.device("cpu")
+    step = 1 << 16
+    total = torch.zeros(d, dtype=torch.float64, device=dev)
+    for i0 in range(0, n, step):
+        total += torch.from_numpy(x[i0:i0 + step]).to(dev).double().sum(0)
+    mean = total / n
+    if gram:
+        xc = torch.from_numpy(x).to(dev).double() - mean
+        m = xc @ xc.T
+    else:
+        m = torch.zeros((d, d), dtype=torch.float64, device=dev)
+        for i0 in range(0, n, step):
+            xc = torch.from_numpy(x[i0:i0 + step]).to(dev).double() - mean
+            m += xc.T @ xc
+    return mean.cpu(), m.cpu()
+
+
+class PCAMatrix(LinearTransform):
+    """faiss.PCAMatrix(d_in, d_out, eigen_power, random_rotation): ``train`` takes the mean and the covariance (divided
+    by n, as in Faiss) in float64 -- through the (n, n) Gram matrix when n < d_in -- and its eigenvectors by
+    ``torch.linalg.eigh`` on the host in float64, eigenvalues descending: ``mean`` float32 (d_in,), ``eigenvalues``
+    float32 (d_in,) (zeros behind the rank a Gram matrix can show), ``PCAMat`` float32 (r, d_in), eigenvectors as rows (r
+    = d_in, or the Gram matrix's rank).  ``A`` is the first ``d_out`` rows times ``eigenvalue ** eigen_power``
+    (-0.5: whitening), times a random rotation if asked; ``b = -A mean``.  Eigenvector signs, and so Faiss's LAPACK
+    path, are unpinned."""
+
+    _FOURCC = b"PcAm"
+    max_points_per_d = 1000
+
+    def __init__(self, d_in: int = 0, d_out: int = 0, eigen_power: float = 0, random_rotation: bool = False):
+        super().__init__(d_in, d_out, True)
+        self.eigen_power = float(eigen_power)
+        self.random_rotation = bool(random_rotation)
+        self.balanced_bins = 0
+        self.mean = np.zeros(0, dtype=np.float32)
+        self.eigenvalues = np.zeros(0, dtype=np.float32)
+        self.PCAMat = np.zeros((0, self.d_in), dtype=np.float32)
+        self._eig64 = None  # train's float64 results, which prepare_Ab prefers to their float32 copies
+        self._gram = None   # tests: force the Gram (True) or the covariance (False) path; None: Gram when n < d_in
+
+    def train(self, x) -> None:
+        import torch
+
+        x = _as_rows(x, self.d_in)
+        n = x.shape[0]
+        assert n >= 2, "PCA needs at least two rows"
+        gram = n < self.d_in if self._gram is None else self._gram
+        mean, m = _moments(x, gram)
+        lam, vec = torch.linalg.eigh(m / n)
+        lam, vec = lam.flip(0).numpy(), vec.flip(1).numpy()  # descending; eigenvectors in columns
+        if gram:
+            # Xc Xc^T / n = U L U^T  ->  the covariance Xc^T Xc / n has eigenvectors Xc^T u / sqrt(n l) for l > 0
+            keep = lam > lam[0] * n * 2.0 ** -52
+            xc = x.astype(np.float64) - mean.numpy()[None, :]
+            rows = (xc.T @ vec[:, keep] / np.sqrt(n * lam[keep])[None, :]).T
+            lam = np.concatenate((lam[keep], np.zeros(self.d_in - int(keep.sum()))))
+        else:
+            rows = vec.T
+        if rows.shape[0] < self.d_out:
+            raise RuntimeError(f"{n} training rows span {rows.shape[0]} principal directions, d_out = {self.d_out}")
+        self._eig64 = (mean.numpy(), np.maximum(lam, 0.0), rows)
+        self.mean = self._eig64[0].astype(np.float32)
+        self.eigenvalues = self._eig64[1].astype(np.float32)
+        self.PCAMat = np.ascontiguousarray(rows, dtype=np.float32)
+        self.prepare_Ab()
+
+    def prepare_Ab(self) -> None:
+        """``A`` and ``b`` from ``mean``, ``eigenvalues`` and ``PCAMat`` (float64, narrowed once)."""
+        mean, lam, rows = self._eig64 or (self.mean.astype(np.float64), self.eigenvalues.astype(np.float64),
+                                          self.PCAMat.astype(np.float64))
+        assert rows.shape[0] >= self.d_out and rows.shape[1] == self.d_in and mean.size == self.d_in
+        A = rows[:self.d_out]
+        if self.eigen_power != 0:
+            if self.eigen_power < 0 and not (lam[:self.d_out] > 0).all():
+                raise RuntimeError("a zero eigenvalue among the first d_out: a negative eigen_power cannot scale it")
+            A = A * (lam[:self.d_out] ** self.eigen_power)[:, None]
+        if self.random_rotation:
+            r = RandomRotationMatrix(self.d_out, self.d_out)
+            r.init(5)
+            A = r.A.astype(np.float64) @ A
+        self.A = A
+        self.b = -(A @ mean)
+        if self.eigen_power == 0:
+            self.set_is_orthonormal()
+
+    def _record_body(self) -> bytes:
+        head = struct.pack("<fBi", self.eigen_power, 1 if self.random_rotation else 0, int(self.balanced_bins))
+        return head + _pack_vector(self.mean.astype("<f4")) + _pack_vector(self.eigenvalues.astype("<f4")) + \
+            _pack_vector(self.PCAMat.astype("<f4")) + super()._record_body()
+
+
+class OPQMatrix(LinearTransform):
+    """faiss.OPQMatrix(d, M, d2=-1): the non-parametric OPQ of Ge, He, Ke and Sun ("Optimized Product Quantization",
+    2013).  ``train`` starts from a random rotation and repeats ``niter`` times: rotate the rows (``apply_torch``), train
+    a product quantiser on them (one ``Kmeans`` per sub-quantiser of ``niter_pq`` iterations -- ``niter_pq_0`` the first
+    time -- warm-started from the previous round's centroids), encode and decode through a scratch ``IndexPQ``, and take
+    the rotation nearest to mapping the rows onto their decoded images: A^T = U V^T from the SVD of X^T Xhat, float64 on
+    the host.  At most ``max_train_points`` rows, drawn with a seeded generator.  Written to a file as a plain
+    ``LinearTransform`` ("LTra"), as in Faiss."""
+
+    niter, niter_pq, niter_pq_0 = 50, 4, 40  # Faiss's defaults; set on an object before ``train``
+    max_train_points = 256 * 256
+    seed = 1234
+
+    def __init__(self, d: int = 0, M: int = 1, d2: int = -1):
+        super().__init__(d, d if int(d2) < 0 else int(d2), False)
+        self.M = int(M)
+        assert self.d_out <= self.d_in and self.d_out % self.M == 0, "d2 <= d, and M divides d2"
+
+    def train(self, x) -> None:
+        import torch
+
+        x = _as_rows(x, self.d_in)
+        if x.shape[0] < 256:
+            raise RuntimeError(f"{x.shape[0]} training rows for 256 centroids per sub-quantiser")
+        if x.shape[0] > self.max_train_points:
+            pick = np.random.default_rng(self.seed).choice(x.shape[0], self.max_train_points, replace=False)
+            x = x[np.sort(pick)]
+        d2, dsub = self.d_out, self.d_out // self.M
+        x64 = x.astype(np.float64)
+        x_dev = torch.from_numpy(x).to(torch.device("cuda", _default_device()))
+        rot = RandomRotationMatrix(self.d_in, d2)
+        rot.init(self.seed)
+        self.A = rot.A
+        pq = IndexPQ(d2, self.M, 8)
+        centroids = None
+        for it in range(int(self.niter)):
+            xr = self.apply_torch(x_dev).cpu().numpy()
+            c = np.empty((self.M, 256, dsub), dtype=np.float32)
+            for m in range(self.M):
+                km = Kmeans(dsub, 256, niter=self.niter_pq_0 if it == 0 else self.niter_pq, seed=self.seed)
+                km.train(np.ascontiguousarray(xr[:, m * dsub:(m + 1) * dsub]),
+                         init_centroids=None if centroids is None else centroids[m])
+                c[m] = km.centroids
+            centroids = c
+            pq.pq.set_centroids(c)
+            xhat = pq.sa_decode(pq.sa_encode(xr)).astype(np.float64)
+            u, _, vt = np.linalg.svd(x64.T @ xhat, full_matrices=False)  # (d, d2) = u (d, d2) s vt (d2, d2)
+            self.A = (u @ vt).T
+        self.set_is_orthonormal()
+
+
+class NormalizationTransform(VectorTransform):
+    """faiss.NormalizationTransform(d, norm=2.0): every row divided by its L2 norm, zero rows untouched --
+    ``normalize_L2`` on a copy (include/ise_knn.h, ise_normalize_rows_*).  Only norm 2 is provided."""
+
+    _FOURCC = b"VNrm"
+
+    def __init__(self, d: int = 0, norm: float = 2.0):
+        super().__init__(d, d)
+        if float(norm) != 2.0:
+            raise NotImplementedError(f"NormalizationTransform with norm = {norm}: only the L2 norm is provided")
+        self.norm = float(norm)
+
+    def apply(self, x) -> np.ndarray:
+        y = _as_rows(x, self.d_in).copy()
+        if y.shape[0]:
+            normalize_L2(y)
+        return y
+
+    def apply_torch(self, x):
+        import torch
+
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d_in
+        y = x.contiguous().clone()
+        if y.shape[0]:
+            normalize_L2(y)
+        return y
+
+    def reverse_transform(self, y) -> np.ndarray:
+        return _as_rows(y, self.d_out).copy()  # the norm is gone: Faiss hands the rows back as they are
+
+    def _record_body(self) -> bytes:
+        return struct.pack("<f", self.norm)
+
+
+class CenteringTransform(VectorTransform):
+    """faiss.CenteringTransform(d): y = x - mean, ``mean`` from ``train``.  It runs as a ``LinearTransform`` with the
+    identity for A and -mean for b rather than through a kernel of its own: every chain is then x_j exactly (zeros and
+    one product by 1), and the one rounding is that of -mean_j + x_j, the bits of x_j - mean_j.  (A row with an inf
+    entry turns NaN throughout: 0 * inf.)  d is at most 4096."""
+
+    _FOURCC = b"VCnt"
+
+    def __init__(self, d: int = 0):
+        super().__init__(d, d)
+        self.is_trained = False
+        self._mean = np.zeros(0, dtype=np.float32)
+        self._lt = None
+
+    @property
+    def mean(self) -> np.ndarray:
+        return self._mean
+
+    @mean.setter
+    def mean(self, mean) -> None:
+        mean = np.ascontiguousarray(np.asarray(mean), dtype=np.float32).reshape(-1)
+        assert mean.size == self.d_in, f"mean holds d = {self.d_in} entries, got {mean.size}"
+        self._mean, self._lt = mean, None
+        self.is_trained = True
+
+    def train(self, x) -> None:
+        self.mean = _as_rows(x, self.d_in).astype(np.float64).mean(axis=0)
+
+    def _linear(self) -> LinearTransform:
+        self._require_trained("apply")
+        if self._lt is None:
+            lt = LinearTransform(self.d_in, self.d_in, True)
+            lt.A = np.eye(self.d_in, dtype=np.float32)
+            lt.b = -self._mean
+            self._lt = lt
+        return self._lt
+
+    def apply(self, x) -> np.ndarray:
+        return self._linear().apply(x)
+
+    def apply_torch(self, x):
+        return self._linear().apply_torch(x)
+
+    def reverse_transform(self, y) -> np.ndarray:
+        self._require_trained("reverse_transform")
+        return _as_rows(y, self.d_out) + self._mean[None, :]
+
+    def _record_body(self) -> bytes:
+        return _pack_vector(self._mean.astype("<f4"))
+
+
+class SearchParametersPreTransform(SearchParameters):
+    """faiss.SearchParametersPreTransform(index_params=): ``index_params`` goes to the sub-index."""
+
+    def __init__(self, index_params=None):
+        super().__init__()
+        self.index_params = index_params
+
+
+class IndexPreTransform:
+    """faiss.IndexPreTransform(ltrans, index) / IndexPreTransform(index) + ``prepend_transform(vt)``: the rows and the
+    queries pass through ``chain`` (first transform first) before they reach ``index`` -- any index kind of this
+    package with ``add`` and ``search``.  ``train`` trains each untrained transform on the rows as transformed so far,
+    then the sub-index; ``search`` / ``search_torch`` return what the sub-index returns for ``apply_chain(x)``, bit for
+    bit.  ``range_search``, ``remove_ids``, ``add_with_ids`` and ``params=`` (``SearchParametersPreTransform`` is
+    unwrapped) go straight to the sub-index, which raises where it does not provide them; ``reconstruct`` goes back
+    through every ``reverse_transform``."""
+
+    def __init__(self, *args):
+        assert len(args) in (1, 2), "IndexPreTransform(index) or IndexPreTransform(ltrans, index)"
+        self.index = args[-1]
+        assert hasattr(self.index, "search") and hasattr(self.index, "add"), "the sub-index has add and search"
+        self.chain = []
+        if len(args) == 2:
+            self.prepend_transform(args[0])
+
+    d = property(lambda self: self.chain[0].d_in if self.chain else self.index.d)
+    metric_type = property(lambda self: self.index.metric_type)
+    ntotal = property(lambda self: self.index.ntotal)
+    device = property(lambda self: self.index.device)
+    is_trained = property(lambda self: all(t.is_trained for t in self.chain) and bool(self.index.is_trained))
+
+    def prepend_transform(self, vt: VectorTransform) -> None:
+        assert isinstance(vt, VectorTransform), "a VectorTransform"
+        assert vt.d_out == self.d, f"dimension mismatch: the transform gives d_out={vt.d_out}, what follows takes d={self.d}"
+        self.chain.insert(0, vt)
+
+    def apply_chain(self, x):
+        """numpy rows -> numpy rows (``apply``), a CUDA tensor -> a CUDA tensor (``apply_torch``)."""
+        if isinstance(x, np.ndarray) or not hasattr(x, "is_cuda"):
+            x = _as_rows(x, self.d)
+            for t in self.chain:
+                x = t.apply(x)
+            return x
+        assert x.dim() == 2 and x.shape[1] == self.d, f"dimension mismatch: got {tuple(x.shape)}, index has d={self.d}"
+        for t in self.chain:
+            x = t.apply_torch(x)
+        return x
+
+    @staticmethod
+    def _sub_params(params):
+        return params.index_params if isinstance(params, SearchParametersPreTransform) else params
+
+    # -- build side
+    def train(self, x) -> None:
+        x = _as_rows(x, self.d)
+        for t in self.chain:
+            if not t.is_trained:
+                t.train(x)
+            x = t.apply(x)
+        if hasattr(self.index, "train"):
+            self.index.train(x)
+
+    def add(self, x) -> None:
+        self.index.add(self.apply_chain(_as_rows(x, self.d)))
+
+    def add_with_ids(self, x, ids) -> None:
+        self.index.add_with_ids(self.apply_chain(_as_rows(x, self.d)), ids)
+
+    def add_torch(self, x) -> None:
+        self.index.add_torch(self.apply_chain(x))
+
+    def reset(self) -> None:
+        self.index.reset()
+
+    def remove_ids(self, sel) -> int:
+        return self.index.remove_ids(sel)
+
+    def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
+        x = self.index.reconstruct_n(i0, self.ntotal - i0 if n is None else n)
+        for t in reversed(self.chain):
+            x = t.reverse_transform(x)
+        return x
+
+    def reconstruct(self, i: int) -> np.ndarray:
+        return self.reconstruct_n(int(i), 1)[0]
+
+    # -- query side
+    def search(self, x, k: int, params=None):
+        return self.index.search(self.apply_chain(_as_rows(x, self.d)), k, params=self._sub_params(params))
+
+    def search_torch(self, xq, k: int, params=None):
+        """The transforms and the sub-index's ``search_torch``, enqueued on the current torch stream."""
+        return self.index.search_torch(self.apply_chain(xq), k, params=self._sub_params(params))
+
+    def range_search(self, x, radius: float, params=None):
+        return self.index.range_search(self.apply_chain(_as_rows(x, self.d)), radius, params=self._sub_params(params))
+
+    def _image(self) -> bytes:
+        sub = self.index
+        if isinstance(sub, IndexIVFFlat):
+            raise NotImplementedError("write_index of an IndexIVFFlat is not provided")
+        image = sub._image() if hasattr(sub, "_image") else _flat_image(sub)
+        return serialize_pretransform(self.chain, image, self.d, self.metric_type, self.ntotal, self.is_trained)
+
+    @classmethod
+    def _from_parts(cls, parts, device):
+        """The index a parsed "IxPT" image describes (``parse_pretransform``)."""
+        sub_cls, _, _ = _INDEX_FILES.get(parts.sub_fourcc, _FLAT_FILE)
+        index = cls(sub_cls()._from_parts(parts.sub, device))
+        for t in reversed(parts.chain):
+            index.prepend_transform(t)
+        return index
+
+
+# IndexPreTransform [upstream-faiss index_write.cpp write_index / write_VectorTransform, restated from memory of the
+# published format and UNPINNED like the layouts above: there is no sample file]:
+#   fourcc "IxPT"; the index header (d, ntotal, 1<<20, 1<<20, is_trained, metric_type); int32 count; count transform
+#   records, the first to apply first; the sub-index as its own file image.
+#   A transform record: fourcc "rrot" (RandomRotationMatrix), "PcAm" (PCAMatrix), "LTra" (LinearTransform, OPQMatrix),
+#   "VNrm" (NormalizationTransform) or "VCnt" (CenteringTransform); for "PcAm" first: float32 eigen_power, uint8
+#   random_rotation, int32 balanced_bins, the vectors mean, eigenvalues, PCAMat; for the three linear kinds: uint8
+#   have_bias, the vectors A ([d_out][d_in]) and b; for "VNrm": float32 norm; for "VCnt": the vector mean; then for
+#   every kind int32 d_in, int32 d_out, uint8 is_trained.  (A vector: uint64 count, count float32.)
+_FOURCC_PRETRANSFORM = b"IxPT"
+_TRUNCATED_PRETRANSFORM = "truncated IndexPreTransform file"
+_VT_TAIL = struct.Struct("<iiB")
+_VT_COUNT = struct.Struct("<i")
+_VT_PCA_HEAD = struct.Struct("<fBi")
+_VT_BYTE = struct.Struct("<B")
+_VT_FLOAT = struct.Struct("<f")
+_VT_KINDS = {b"rrot": RandomRotationMatrix, b"PcAm": PCAMatrix, b"LTra": LinearTransform, b"VNrm": NormalizationTransform,
+             b"VCnt": CenteringTransform}
+_PreTransformParts = namedtuple("_PreTransformParts", "d metric chain sub_fourcc sub")
+
+
+def serialize_pretransform(chain, sub_image: bytes, d: int, metric: int, ntotal: int, is_trained: bool = True) -> bytes:
+    """``chain``: the ``VectorTransform`` objects, the first to apply first; ``sub_image``: the sub-index as one of the
+    writers here writes it."""
+    head = _HDR.pack(_FOURCC_PRETRANSFORM, int(d), int(ntotal), 1 << 20, 1 << 20, 1 if is_trained else 0, int(metric))
+    return head + _VT_COUNT.pack(len(chain)) + b"".join(t._record() for t in chain) + bytes(sub_image)
+
+
+def _parse_transform_at(cur: _Cursor) -> VectorTransform:
+    corrupt = "corrupt IndexPreTransform: a transform record's sizes do not agree"
+    fourcc = cur.fourcc()
+    if fourcc not in _VT_KINDS:
+        raise RuntimeError(f"unsupported vector transform {fourcc!r} in an IndexPreTransform file")
+
+    def floats():
+        return cur.vector(np.float32, lambda count: True, corrupt)
+
+    pca = lin = norm = mean = None
+    if fourcc == b"PcAm":
+        pca = cur.take(_VT_PCA_HEAD) + (floats(), floats(), floats())
+    if fourcc in (b"rrot", b"PcAm", b"LTra"):
+        lin = cur.take(_VT_BYTE) + (floats(), floats())
+    elif fourcc == b"VNrm":
+        (norm,) = cur.take(_VT_FLOAT)
+    else:
+        mean = floats()
+    d_in, d_out, is_trained = cur.take(_VT_TAIL)
+    if d_in <= 0 or d_out <= 0:
+        raise RuntimeError(corrupt)
+    if lin is not None:
+        have_bias, A, b = lin
+        t = _VT_KINDS[fourcc](d_in, d_out)
+        if A.size not in (0, d_in * d_out) or b.size != (d_out if have_bias and A.size else 0) or bool(A.size) != bool(is_trained):
+            raise RuntimeError(corrupt)
+        if pca is not None:
+            t.eigen_power, t.random_rotation, t.balanced_bins = float(pca[0]), bool(pca[1]), int(pca[2])
+            if A.size and (pca[3].size != d_in or pca[4].size != d_in or pca[5].size % d_in or pca[5].size < d_in * d_out):
+                raise RuntimeError(corrupt)
+            t.mean, t.eigenvalues, t.PCAMat = pca[3], pca[4], pca[5].reshape(-1, d_in)
+        t.have_bias = bool(have_bias)
+        if A.size:
+            t.A = A.reshape(d_out, d_in)
+            if have_bias:
+                t.b = b
+            t.set_is_orthonormal()
+    elif norm is not None:
+        if d_in != d_out or norm != 2.0:
+            raise RuntimeError("unsupported NormalizationTransform in an IndexPreTransform file: only the L2 norm is readable")
+        t = NormalizationTransform(d_in, norm)
+    else:
+        if d_in != d_out or mean.size != (d_in if is_trained else 0):
+            raise RuntimeError(corrupt)
+        t = CenteringTransform(d_in)
+        if is_trained:
+            t.mean = mean
+    return t
+
+
+def _parse_pretransform_at(cur: _Cursor) -> _PreTransformParts:
+    """(Every missing byte is ``_TRUNCATED_PRETRANSFORM``: the cursor is made with it.)"""
+    cur.expect(_FOURCC_PRETRANSFORM, "IndexPreTransform")
+    _, d, n, _, _, _, metric = cur.take(_HDR)
+    (count,) = cur.take(_VT_COUNT)
+    if d <= 0 or n < 0 or not 0 <= count <= 64:
+        raise RuntimeError("corrupt IndexPreTransform header")
+    chain = [_parse_transform_at(cur) for _ in range(count)]
+    for t, after in zip(chain, chain[1:]):
+        if t.d_out != after.d_in:
+            raise RuntimeError("corrupt IndexPreTransform: the transforms do not chain")
+    sub_fourcc = cur.peek()
+    if sub_fourcc in (b"IwFl", b"IwF2"):
+        raise NotImplementedError("read_index of an IndexIVFFlat file is not provided")
+    if sub_fourcc == _FOURCC_PRETRANSFORM:
+        raise RuntimeError("unsupported sub-index type b'IxPT' in an IndexPreTransform file")
+    _, read, _ = _INDEX_FILES.get(sub_fourcc, _FLAT_FILE)
+    sub = read(cur)
+    if cur.off != len(cur.buf):
+        raise RuntimeError("corrupt IndexPreTransform: bytes behind the sub-index")
+    if (chain[0].d_in if chain else sub.d) != d or (chain and chain[-1].d_out != sub.d):
+        raise RuntimeError("corrupt IndexPreTransform: the dimensions do not match the header")
+    return _PreTransformParts(d, metric, chain, sub_fourcc, sub)
+
+
+def parse_pretransform(buf: bytes):
+    """-> (d, metric, chain: the ``VectorTransform`` objects, sub_fourcc, the sub-index as its own parser returns it);
+    raises RuntimeError on a foreign, truncated or inconsistent file."""
+    parts = _parse_pretransform_at(_Cursor(buf, _TRUNCATED_PRETRANSFORM))
+    return tuple(parts._replace(sub=tuple(parts.sub)))
+
+
+_INDEX_FILES[_FOURCC_PRETRANSFORM] = (lambda: IndexPreTransform, _parse_pretransform_at, _TRUNCATED_PRETRANSFORM)

@@ -83,7 +83,9 @@ def create_search_index(data_array, index_type="cosine"):
     'sq8' is IndexScalarQuantizer with QT_8bit: one byte per entry between the data's per-dimension minimum and maximum,
     trained on the data, then add.  'cell-probe-sq8' is the cell-probe branch with that quantiser in place of the product
     quantiser: IndexIVFScalarQuantizer (QT_8bit, by_residual=False) over an L2 coarse quantiser with the reference's 8
-    centroids and nprobe = 5, trained on the data, then add."""
+    centroids and nprobe = 5, trained on the data, then add.  'pca256-l2' is the textbook reduction of a long descriptor:
+    IndexPreTransform(PCAMatrix(d, min(256, d)), IndexFlatL2), trained on the data, then add.  'opq-pq' is the 'pq' index
+    behind an OPQ rotation: IndexPreTransform(OPQMatrix(d, 16), IndexPQ(d, 16, 8)), trained on the data, then add."""
     num_features = data_array.shape[1]
     if index_type == "cosine":
         index = faiss.IndexFlatIP(num_features)
@@ -116,6 +118,13 @@ def create_search_index(data_array, index_type="cosine"):
         index = faiss.IndexIVFScalarQuantizer(coarse_quantizer, num_features, ncentroids, faiss.ScalarQuantizer.QT_8bit,
                                               faiss.METRIC_L2, by_residual=False)
         index.nprobe = 5  # find n most similar clusters
+        index.train(data_array)
+    elif index_type == "pca256-l2":
+        d_out = min(256, num_features)
+        index = faiss.IndexPreTransform(faiss.PCAMatrix(num_features, d_out), faiss.IndexFlatL2(d_out))
+        index.train(data_array)
+    elif index_type == "opq-pq":
+        index = faiss.IndexPreTransform(faiss.OPQMatrix(num_features, 16), faiss.IndexPQ(num_features, 16, 8))
         index.train(data_array)
     else:
         raise ValueError(f"unknown index_type {index_type!r}")

@@ -54,6 +54,9 @@ extern "C" {
 #define ISE_MAX_K 2048 /* largest k accepted by the search entry points */
 #define ISE_SQ_MAX_D 2048 /* longest row of a scalar-quantised index (ise_sq_*): what its scan's LDS holds of 8 queries */
 #define ISE_PQ_MAX_M 64 /* most sub-quantisers of a product-quantised index (ise_pq_*): what its scan's LDS holds */
+#define ISE_LINEAR_MAX_D 4096 /* largest d_in and d_out of a linear transform (ise_linear_*): 16 segments of 256, one
+                                 wave each in the few-row launch shape */
+#define ISE_LINEAR_FEW_ROWS 64 /* ise_linear_apply_*: n <= this takes the few-row launch shape, more the tiled one */
 
 typedef struct ise_index ise_index_t;
 
@@ -671,6 +674,29 @@ int ise_index_assign_device(ise_index_t* h, const float* x_dev, int64_t n, float
  * in-place row L2 normalisation of n x d float32, zero rows untouched. */
 int ise_normalize_rows_device(float* x_dev, int64_t n, int d, int device, void* stream);
 int ise_normalize_rows_host(float* x, int64_t n, int d, int device);
+
+/* faiss.LinearTransform::apply (PCAMatrix, OPQMatrix, RandomRotationMatrix in front of an index):
+ * y = A x + b for n rows, float32.  A handle is immutable: it holds A (host, [d_out][d_in], Faiss's layout), re-packed
+ * once into the panels the kernels load, and b (host, d_out floats, or NULL: none).  1 <= d_in, d_out <=
+ * ISE_LINEAR_MAX_D.
+ *   The arithmetic is a function of d_in only -- not of n, of a row's place in the batch, of the launch shape or of the
+ * stream: k is cut into segments of 256; each segment is a k-ascending float32 fmaf chain from +0, s = fmaf(A[j][k],
+ * x[k], s); y_j = ((b_j + s_0) + s_1) + ... by float32 adds in ascending segment order (b_j = +0 without a bias).  NaN
+ * and inf follow IEEE rules into the outputs of their own row only; subnormals are kept.
+ *   apply_device  x_dev: n x d_in on the device (rows 4-byte aligned; 16-byte loads are used where the pointer and
+ *                 d_in allow), y_dev: n x d_out, not overlapping x_dev; enqueued on `stream`, nothing is waited for
+ *                 and no scratch memory is used, so calls on different streams need no order between them.  n >= 1.
+ *                 n <= ISE_LINEAR_FEW_ROWS spreads the matrix over the device (a wave per segment); more rows take an
+ *                 LDS-tiled kernel; both give the same bits.
+ *   apply_host    the same through the handle's staging buffers, in pieces of 256 MiB at most; one call at a time.
+ *   stats         out3: calls of apply_device / apply_host pieces, few-row launches, tiled launches. */
+typedef struct ise_linear ise_linear_t;
+int ise_linear_create(ise_linear_t** out, int d_in, int d_out, const float* A, const float* b, int device);
+int ise_linear_destroy(ise_linear_t* h);
+int ise_linear_info(const ise_linear_t* h, int* d_in, int* d_out, int* have_bias, int* device);
+int ise_linear_apply_device(ise_linear_t* h, const float* x_dev, int64_t n, float* y_dev, void* stream);
+int ise_linear_apply_host(ise_linear_t* h, const float* x, int64_t n, float* y);
+int ise_linear_stats(ise_linear_t* h, uint64_t* out3);
 
 /* The visual-word histogram of BOVW.transform (backend/bag_of_visual_words.py:98-106): for
  * every image i, np.histogram(labels[offsets[i] : offsets[i+1]], bins=K) -- K equal-width bins
