@@ -1,9 +1,9 @@
-// ise_ivf_lists.hpp -- the device side of the inverted lists' bookkeeping, shared by the float32 lists (ise_ivf.hip) and
-// the 8-bit lists (ise_ivfsq.hip): the ids and the table of the sorted array beside the host's counts
-// (ise_ivf_plan.hpp), and the staged host form of a search.  What a row IS (float32 rows and norms, or codes and row
-// terms) stays with the index kind: its rebuild allocates and fills the payload, this struct's begin_rebuild /
-// finish_rebuild do the ids, the table and the counts around it.  Host code (the handle's mutex is held), and the one
-// kernel that reads nothing of a row: the probe table's masks.
+// ise_ivf_lists.hpp -- the device side of the inverted lists' bookkeeping, shared by the float32 lists (ise_ivf.hip), the
+// 8-bit lists (ise_ivfsq.hip) and the lists over bit codes (ise_binary_ivf.hip): the ids and the table of the sorted
+// array beside the host's counts (ise_ivf_plan.hpp), and the staged host form of a search.  What a row IS (float32 rows
+// and norms, codes and row terms, or bit codes alone) stays with the index kind: its rebuild allocates and fills the
+// payload, this struct's begin_rebuild / finish_rebuild do the ids, the table and the counts around it.  Host code (the
+// handle's mutex is held), and the one kernel that reads nothing of a row: the probe table's masks.
 #pragma once
 #include "ise_host.hpp"
 #include "ise_ivf_plan.hpp"
@@ -90,25 +90,27 @@ inline int check_ivf_knn_args(const void* q, long long nq, int k, const void* pr
 }
 
 // the host form of a search: queries and probes go up in batches of 4096 at most, enqueue(q_dev, m, p_dev, D_dev,
-// I_dev) ranks a batch on st, the results come back before the next one goes up
-template <class Enqueue>
-int ivf_search_staged(int d, hipStream_t st, const float* q, long long nq, int k, const int64_t* probes, int nprobe, float* D,
+// I_dev) ranks a batch on st, the results come back before the next one goes up.  Q: an entry of a query row of d
+// entries (float, or the bytes of a bit code), DT: a distance (float, or the int of a Hamming distance)
+template <class Q, class DT, class Enqueue>
+int ivf_search_staged(int d, hipStream_t st, const Q* q, long long nq, int k, const int64_t* probes, int nprobe, DT* D,
                       int64_t* I, Enqueue enqueue) {
     const long long batch = std::min<long long>(nq, 4096);
-    float *q_dev = nullptr, *D_dev = nullptr;
+    Q* q_dev = nullptr;
+    DT* D_dev = nullptr;
     long long *p_dev = nullptr, *I_dev = nullptr;
     DevFreeList<4> fr{{(void**)&q_dev, (void**)&D_dev, (void**)&p_dev, (void**)&I_dev}};
-    HIP_TRY(hipMalloc((void**)&q_dev, (size_t)batch * d * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&q_dev, (size_t)batch * d * sizeof(Q)));
     HIP_TRY(hipMalloc((void**)&p_dev, (size_t)batch * nprobe * sizeof(long long)));
-    HIP_TRY(hipMalloc((void**)&D_dev, (size_t)batch * k * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&D_dev, (size_t)batch * k * sizeof(DT)));
     HIP_TRY(hipMalloc((void**)&I_dev, (size_t)batch * k * sizeof(long long)));
     for (long long i0 = 0; i0 < nq; i0 += batch) {
         const long long m = std::min<long long>(batch, nq - i0);
-        HIP_TRY(hipMemcpyAsync(q_dev, q + (size_t)i0 * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(q_dev, q + (size_t)i0 * d, (size_t)m * d * sizeof(Q), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(p_dev, probes + (size_t)i0 * nprobe, (size_t)m * nprobe * sizeof(long long), hipMemcpyHostToDevice, st));
-        const int rc = enqueue((const float*)q_dev, m, (const long long*)p_dev, D_dev, I_dev);
+        const int rc = enqueue((const Q*)q_dev, m, (const long long*)p_dev, D_dev, I_dev);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(D + (size_t)i0 * k, D_dev, (size_t)m * k * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(D + (size_t)i0 * k, D_dev, (size_t)m * k * sizeof(DT), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(I + (size_t)i0 * k, I_dev, (size_t)m * k * sizeof(long long), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }

@@ -1,4 +1,4 @@
-// ise_ivf_plan.hpp -- the host bookkeeping of the inverted lists (ise_ivf.hip, ise_ivfsq.hip; their device side is
+// ise_ivf_plan.hpp -- the host bookkeeping of the inverted lists (ise_ivf.hip, ise_ivfsq.hip, ise_binary_ivf.hip; their device side is
 // ise_ivf_lists.hpp): the plan of a rebuild (a stable counting sort of the pending rows' list numbers), the table the
 // kernels read built from it, the check of list numbers, and the counts a handle keeps between rebuilds.  Plain C++
 // with no device call, so a stand-alone program can run it under a sanitizer.

@@ -70,7 +70,16 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          ``IndexRefineSearchParameters(k_factor=, base_index_params=)``,
                                          ``IndexFlat.search_subset`` / ``compute_distance_subset`` (the pass on its own),
                                          ``write_index`` / ``read_index`` ("IxRF"); never called by the reference
-    write_index_binary / read_index_binary   Faiss's names for IndexBinaryFlat ("IBxF") and IndexBinaryIDMap ("IBMp") files
+    write_index_binary / read_index_binary   Faiss's names for IndexBinaryFlat ("IBxF"), IndexBinaryIDMap ("IBMp") and
+                                         IndexBinaryIVF ("IBwF") files
+    IndexBinaryIVF(quantizer, d, nlist)  Faiss's cell-probe index over bit codes: an ``IndexBinaryFlat`` of ``nlist`` centroid
+                                         codes in front of inverted lists of ``d``-bit codes; ``train`` (k-means on the
+                                         bits as +-1, binarised) / ``add`` / ``search`` with ``nprobe`` /
+                                         ``search_preassigned`` / ``search_torch``, ``get_list``; a Hamming pass reads the
+                                         64-row tiles of the probed lists only (csrc/ise_binary_ivf.hpp), and with
+                                         ``nprobe == nlist`` the result is ``IndexBinaryFlat.search``'s bit for bit; what
+                                         near-duplicate search by hash (backend/engine.py:82-91) needs once one
+                                         brute-force pass over the collection is too much; never called by the reference
     IndexPreTransform(ltrans, index)     Faiss's transform chain in front of any index kind here: ``PCAMatrix`` (mean,
                                          float64 covariance, ``eigen_power`` for whitening), ``OPQMatrix`` (the
                                          non-parametric OPQ rotation for an ``IndexPQ``), ``RandomRotationMatrix``,
@@ -1565,6 +1574,8 @@ class IndexBinaryIDMap(_IDMapBase):
 
     # two shared methods under this class's own annotations: the sub-index's type, a radius that is a Hamming distance
     def __init__(self, index: IndexBinaryFlat):
+        if isinstance(index, _IndexIVF):
+            raise NotImplementedError(f"IndexBinaryIDMap over an {type(index).__name__} is not provided")
         super().__init__(index)
 
     def range_search(self, x, radius: int, params=None):
@@ -1605,8 +1616,93 @@ def parse_binary_idmap(buf: bytes):
     return tuple(_parse_binary_idmap_at(_Cursor(buf)))
 
 
+# IndexBinaryIVF [upstream-faiss index_write.cpp write_index_binary / write_binary_ivf_header / write_InvertedLists,
+# restated from memory of the published format and UNPINNED like the layouts above: there is no sample file]:
+#   fourcc "IBwF"; the binary header (int32 d; int32 code_size; int64 ntotal; uint8 is_trained; int32 metric_type);
+#   uint64 nlist; uint64 nprobe; the quantiser as its own "IBxF" image; the direct map, empty: uint8 type (0, none),
+#   uint64 count (0); the inverted lists as in an "IwSq" file with code_size = d / 8 bytes per row: fourcc "ilar"; uint64
+#   nlist; uint64 code_size; the sizes -- fourcc "full", uint64 count (= nlist), count uint64 (what is written here), or
+#   fourcc "sprs", uint64 count, count uint64 as (list, size) pairs (readable) -- then, per list that holds rows: size x
+#   code_size uint8, size int64 ids.
+_FOURCC_BINARY_IVF = b"IBwF"
+_TRUNCATED_BINARY_IVF = "truncated IndexBinaryIVF file"
+_BinaryIVFParts = namedtuple("_BinaryIVFParts", "d nlist nprobe centroids lists")
+
+
+def serialize_binary_ivf(d: int, nlist: int, nprobe: int, centroids, lists) -> bytes:
+    """``centroids`` uint8 (nlist, d / 8) (or (0, d / 8): an untrained quantiser); ``lists``: ``nlist`` pairs (ids int64
+    (m,), codes uint8 (m, d / 8)), any m, also 0."""
+    d, nlist = int(d), int(nlist)
+    assert d > 0 and d % 8 == 0, "d must be a positive multiple of 8"
+    cs = d // 8
+    assert len(lists) == nlist, "one (ids, codes) pair per list"
+    pairs = [(np.ascontiguousarray(ids, dtype="<i8").reshape(-1), np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, cs))
+             for ids, codes in lists]
+    assert all(ids.size == codes.shape[0] for ids, codes in pairs), "one id per code row"
+    sizes = np.array([ids.size for ids, _ in pairs], dtype="<u8")
+    centroids = np.asarray(centroids, dtype=np.uint8).reshape(-1, cs)
+    out = [_BHDR.pack(_FOURCC_BINARY_IVF, d, cs, int(sizes.sum()), 1 if centroids.shape[0] == nlist else 0, 1),
+           _IVF_DIMS.pack(nlist, int(nprobe)), serialize_binary_flat(d, centroids), _IVF_DIRECT_MAP.pack(0, 0), b"ilar",
+           _IVF_DIMS.pack(nlist, cs), b"full", _pack_vector(sizes)]
+    for ids, codes in pairs:
+        if ids.size:
+            out += [codes.tobytes(), ids.tobytes()]
+    return b"".join(out)
+
+
+def _parse_binary_ivf_at(cur: _Cursor) -> _BinaryIVFParts:
+    """(Every missing byte is ``_TRUNCATED_BINARY_IVF``: the cursor is made with it.)"""
+    corrupt = "corrupt IndexBinaryIVF: "
+    cur.expect(_FOURCC_BINARY_IVF, "IndexBinaryIVF")
+    _, d, cs, n, _, _ = cur.take(_BHDR)
+    nlist, nprobe = cur.take(_IVF_DIMS)
+    if d <= 0 or d % 8 != 0 or cs != d // 8 or n < 0 or nlist <= 0:
+        raise RuntimeError("corrupt IndexBinaryIVF header")
+    quantizer = cur.peek()
+    if quantizer != _FOURCC_BINARY:
+        raise RuntimeError(f"unsupported quantiser type {quantizer!r} in an IndexBinaryIVF file: only a flat binary "
+                           "quantiser is readable")
+    d2, centroids = _parse_binary_flat_at(cur)
+    if d2 != d or centroids.shape[0] not in (0, nlist):
+        raise RuntimeError(corrupt + "the quantiser does not hold nlist codes of d bits")
+    if cur.take(_IVF_DIRECT_MAP) != (0, 0):
+        raise RuntimeError("an IndexBinaryIVF file with a direct map is not readable")
+    lists = cur.fourcc()
+    if lists != b"ilar":
+        raise RuntimeError(f"unsupported inverted lists {lists!r}: only array lists (\"ilar\") are readable")
+    if cur.take(_IVF_DIMS) != (nlist, cs):
+        raise RuntimeError(corrupt + "the inverted lists do not match the header")
+    form = cur.fourcc()
+    sizes = np.zeros(nlist, dtype=np.int64)
+    if form == b"full":
+        sizes[:] = cur.vector(np.uint64, nlist, corrupt + "the size vector does not hold nlist entries").astype(np.int64)
+    elif form == b"sprs":
+        pairs = cur.vector(np.uint64, lambda count: count % 2 == 0 and count <= 2 * nlist,
+                           corrupt + "the sparse size vector does not hold (list, size) pairs").astype(np.int64).reshape(-1, 2)
+        if pairs.size and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= nlist):
+            raise RuntimeError(corrupt + "a list number outside [0, nlist)")
+        sizes[pairs[:, 0]] = pairs[:, 1]
+    else:
+        raise RuntimeError(f"unsupported list size form {form!r} in an IndexBinaryIVF file")
+    if sizes.min() < 0 or int(sizes.sum()) != n:
+        raise RuntimeError(corrupt + "the list sizes do not add up to ntotal")
+    lists = []
+    for m in (int(s) for s in sizes):
+        codes = cur.array(np.uint8, m * cs).reshape(m, cs)
+        lists.append((cur.array(np.int64, m), codes))
+    return _BinaryIVFParts(d, int(nlist), int(nprobe), centroids, lists)
+
+
+def parse_binary_ivf(buf: bytes):
+    """-> (d, nlist, nprobe, centroids uint8 (nlist or 0, d / 8), lists [(ids int64 (m,), codes uint8 (m, d / 8))] *
+    nlist): ``serialize_binary_ivf``'s arguments.  Raises RuntimeError on a foreign, truncated or miscounted file."""
+    return tuple(_parse_binary_ivf_at(_Cursor(buf, _TRUNCATED_BINARY_IVF)))
+
+
 def write_index_binary(index, path) -> None:
-    if isinstance(index, IndexBinaryIDMap):
+    if isinstance(index, IndexBinaryIVF):
+        image = index._binary_image()
+    elif isinstance(index, IndexBinaryIDMap):
         sub = index.index
         image = serialize_binary_idmap(sub.d, sub.reconstruct_n(0, sub.ntotal), index.id_map)
     else:
@@ -1616,9 +1712,11 @@ def write_index_binary(index, path) -> None:
 
 
 def read_index_binary(path, device: int | None = None):
-    """-> IndexBinaryFlat, or IndexBinaryIDMap for a file written from one."""
+    """-> IndexBinaryFlat, or IndexBinaryIDMap or IndexBinaryIVF for a file written from one."""
     with open(str(path), "rb") as f:
         buf = f.read()
+    if buf[:4] == _FOURCC_BINARY_IVF:
+        return IndexBinaryIVF._from_parts(_parse_binary_ivf_at(_Cursor(buf, _TRUNCATED_BINARY_IVF)), device)
     if buf[:4] == _FOURCC_BINARY_IDMAP:
         d, xb, ids = _parse_binary_idmap_at(_Cursor(buf))
         index = IndexBinaryIDMap(IndexBinaryFlat(d, device))
@@ -1949,6 +2047,194 @@ class IndexIVFFlat(_IndexIVF):
         """Search batches, scan passes launched, 16-row tiles of list rows the passes loaded (include/ise_knn.h,
         ise_ivf_stats).  Waits for the device."""
         return _counters(_n.lib.ise_ivf_stats, self._h, ("batches", "passes", "tiles_loaded"))
+
+
+# ---------------------------------------------------------------- inverted lists over bit codes (faiss.IndexBinaryIVF)
+def _bits_to_signs(x: np.ndarray, d: int) -> np.ndarray:
+    """uint8 (n, d / 8) -> float32 (n, d) of +-1: bit i of a code is ``(byte[i >> 3] >> (i & 7)) & 1``, a set bit is +1."""
+    bits = np.unpackbits(x, axis=1, bitorder="little")[:, :d]
+    return np.ascontiguousarray(bits.astype(np.float32) * 2.0 - 1.0)
+
+
+def _signs_to_bits(c: np.ndarray) -> np.ndarray:
+    """float32 (n, d) -> uint8 (n, d / 8): a bit is set where the entry is > 0 (the inverse of ``_bits_to_signs``)."""
+    return np.ascontiguousarray(np.packbits(c > 0, axis=1, bitorder="little"))
+
+
+class IndexBinaryIVF(_IndexIVF):
+    """faiss.IndexBinaryIVF(quantizer, d, nlist): a coarse quantiser (an ``IndexBinaryFlat`` of ``nlist`` codes, the
+    caller's object) in front of ``d``-bit codes (uint8 rows of ``d / 8`` bytes).  ``add`` puts every code into the
+    inverted list of its nearest centroid code (``quantizer.search(x, 1)[1]``: Hamming distance, ties by ascending id);
+    ``search`` visits the ``nprobe`` lists whose centroids are nearest to the query and returns the exact k best among
+    THEIR rows: D int32 Hamming distances ascending, ties by ascending id, unfilled slots INT32_MAX / -1.  With ``nprobe ==
+    nlist`` the result is ``IndexBinaryFlat.search`` on the same rows, bit for bit.
+
+    For given centroid codes everything here is determined, and it is checked exactly against this package's own flat
+    binary index; Faiss's own binary IVF (its k-means seeding, its order among equal distances) is unpinned.
+
+    The lists live on the device (include/ise_knn.h, ise_binary_ivf_*): ``add`` appends to a pending
+    buffer, the first search after an ``add`` rebuilds the lists.  Not provided (they raise ``NotImplementedError``):
+    ``range_search``, ``remove_ids``, ``params=`` and ``IndexBinaryIDMap`` over this type."""
+
+    _ABI = "ise_binary_ivf"
+    _search_host = staticmethod(_n.lib.ise_binary_ivf_search_host)
+    _search_device = staticmethod(_n.lib.ise_binary_ivf_search_device)
+    _LIST_DTYPE = np.uint8
+    ntotal = _ntotal_property(_n.lib.ise_binary_ivf_info, 5, 3)
+
+    def __init__(self, quantizer: IndexBinaryFlat, d: int, nlist: int):
+        assert isinstance(quantizer, IndexBinaryFlat), "the coarse quantiser is an IndexBinaryFlat"
+        assert quantizer.d == int(d), f"dimension mismatch: quantizer has d={quantizer.d}, index d={d}"
+        self.quantizer = quantizer
+        self.d = int(d)
+        self.code_size = self.d // 8
+        self.nlist = int(nlist)
+        self.nprobe = 1
+        self.cp = ClusteringParameters()
+        self.device = quantizer.device
+        self._h = ctypes.c_void_p()
+        self._lock = threading.Lock()
+        _n.check(_n.lib.ise_binary_ivf_create(ctypes.byref(self._h), self.d, self.nlist, self.device))
+        self.is_trained = quantizer.ntotal == self.nlist
+
+    # -- build side
+    def train(self, x) -> None:
+        """uint8 (n, d / 8).  A no-op when the quantiser already holds ``nlist`` codes; ``RuntimeError`` when it holds
+        neither 0 nor ``nlist`` codes, or when ``n < nlist``.  Otherwise the bits are expanded to +-1 float32 (bit i of
+        a code is ``(byte[i >> 3] >> (i & 7)) & 1``), ``Kmeans(d, nlist, niter=cp.niter, seed=cp.seed)`` runs on them, a
+        centroid's bit is ``value > 0``, and the ``nlist`` codes are added to the quantiser.
+
+        This is Faiss's scheme for a binary IVF restated from memory: the comparison with Faiss (its seeding, its
+        ``cp.niter`` default, how it binarises) is unpinned, as for ``IndexIVFFlat.train``.
+
+        Two centroids may binarise to the same code.  The quantiser breaks ties by ascending id, so the later of the two
+        lists is never the nearest: it stays empty, and nothing else changes -- an empty list is probed and adds nothing."""
+        if self.quantizer.ntotal != self.nlist:
+            if self.quantizer.ntotal != 0:
+                raise RuntimeError(f"the quantizer holds {self.quantizer.ntotal} codes, neither 0 nor nlist = {self.nlist}")
+            x = _as_codes(x, self.code_size)
+            if x.shape[0] < self.nlist:
+                raise RuntimeError(f"{x.shape[0]} training rows for nlist = {self.nlist} centroids")
+            km = Kmeans(self.d, self.nlist, niter=self.cp.niter, seed=self.cp.seed)
+            km.train(_bits_to_signs(x, self.d))
+            self.quantizer.add(_signs_to_bits(km.centroids))
+        self.is_trained = True
+
+    def add(self, x) -> None:
+        """Append codes (copied): uint8 (n, d / 8); row i of the call goes to list ``quantizer.search(x, 1)[1][i]``."""
+        self._require_trained("add")
+        x = _as_codes(x, self.code_size)
+        if x.shape[0] == 0:
+            return
+        lists = self._assign(x)
+        _n.check(_n.lib.ise_binary_ivf_add_host(self._h, x.ctypes.data, lists.ctypes.data, x.shape[0]))
+
+    def add_torch(self, x) -> None:
+        """``add`` from a CUDA uint8 tensor on this index's device (no host hop for the codes; the list numbers are read
+        back to be checked).  Under the index's lock, like every device call that names a stream."""
+        import torch
+
+        self._require_trained("add")
+        assert x.is_cuda and x.dtype == torch.uint8 and x.dim() == 2 and x.shape[1] == self.code_size
+        x = x.contiguous()
+        n = x.shape[0]
+        if n == 0:
+            return
+        lists = self.quantizer.search_torch(x, 1)[1].reshape(-1).contiguous()
+        self._check_assignment(lists.cpu().numpy())
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        with self._lock:
+            _n.check(_n.lib.ise_binary_ivf_add_device(self._h, x.data_ptr(), lists.data_ptr(), n, st))
+
+    # -- lists
+    def get_list(self, l: int):
+        """(ids int64 (m,), codes uint8 (m, d / 8)) of list ``l``, in list order (ascending ids)."""
+        m = self.list_size(l)
+        ids = np.empty(m, dtype=np.int64)
+        codes = np.empty((m, self.code_size), dtype=np.uint8)
+        _n.check(_n.lib.ise_binary_ivf_list_host(self._h, int(l), ids.ctypes.data, codes.ctypes.data))
+        return ids, codes
+
+    # -- query side
+    def search(self, x, k: int, params=None):
+        """(D int32 (nq, k), I int64 (nq, k)), fresh arrays: the k best among the rows of the ``nprobe`` lists nearest
+        to each query (``quantizer.search(x, min(nprobe, nlist))[1]``), ascending (distance, id); unfilled slots are
+        INT32_MAX / -1."""
+        self._no_params(params)
+        self._require_trained("search")
+        x = _as_codes(x, self.code_size)
+        if x.shape[0] == 0:
+            return np.empty((0, int(k)), dtype=np.int32), np.empty((0, int(k)), dtype=np.int64)
+        return self.search_preassigned(x, k, self.quantizer.search(x, self._nprobe())[1])
+
+    def search_preassigned(self, x, k: int, probes):
+        """``search`` with the probed lists given: ``probes`` int64 (nq, nprobe); -1 and out-of-range entries are
+        ignored, a list named twice counts once."""
+        x = _as_codes(x, self.code_size)
+        k = int(k)
+        assert k > 0
+        nq = x.shape[0]
+        probes = np.ascontiguousarray(np.asarray(probes), dtype=np.int64)
+        assert probes.ndim == 2 and probes.shape[0] == nq and probes.shape[1] >= 1
+        D = np.empty((nq, k), dtype=np.int32)
+        I = np.empty((nq, k), dtype=np.int64)
+        _n.check(self._search_host(self._h, x.ctypes.data, nq, k, probes.ctypes.data, probes.shape[1], D.ctypes.data,
+                                   I.ctypes.data))
+        return D, I
+
+    def search_torch(self, xq, k: int, params=None):
+        """Device-resident search: CUDA uint8 (nq, d / 8) in, CUDA (D int32, I int64) out; the quantiser's search and
+        the scan are enqueued on the current torch stream, under the index's lock.  No host synchronisation, except that
+        the first search after an ``add`` rebuilds the lists and waits for that."""
+        import torch
+
+        self._no_params(params)
+        self._require_trained("search")
+        k = int(k)
+        xq, D, I, st = _torch_io(xq, torch.uint8, self.code_size, k, torch.int32)
+        nq = xq.shape[0]
+        if nq == 0:
+            return D, I
+        probes = self.quantizer.search_torch(xq, self._nprobe())[1].contiguous()
+        with self._lock:
+            _n.check(self._search_device(self._h, xq.data_ptr(), nq, k, probes.data_ptr(), probes.shape[1], D.data_ptr(),
+                                         I.data_ptr(), st))
+        return D, I
+
+    def binary_ivf_stats(self) -> dict:
+        """Search batches, scan passes (one per 16 queries and 32 results), 64-row tiles of list rows the passes visited
+        (include/ise_knn.h, ise_binary_ivf_stats).  Waits for the device."""
+        return _counters(_n.lib.ise_binary_ivf_stats, self._h, ("batches", "passes", "tiles_loaded"))
+
+    # -- files
+    def _image(self) -> bytes:
+        raise NotImplementedError("write_index of an IndexBinaryIVF is not provided: write_index_binary writes binary indexes")
+
+    def _binary_image(self) -> bytes:
+        qz = self.quantizer
+        lists = [self.get_list(l) for l in range(self.nlist)]
+        return serialize_binary_ivf(self.d, self.nlist, int(self.nprobe), qz.reconstruct_n(0, qz.ntotal), lists)
+
+    @classmethod
+    def _from_parts(cls, parts, device):
+        """The index a parsed "IBwF" image describes (``parse_binary_ivf``); the stored codes are added as they are, in
+        the order of their ids, which have to be the insertion numbers 0 .. ntotal - 1."""
+        d, nlist, nprobe, centroids, lists = parts
+        quantizer = IndexBinaryFlat(d, device)
+        if centroids.shape[0]:
+            quantizer.add(centroids)
+        index = cls(quantizer, d, nlist)
+        index.nprobe = nprobe
+        ids = np.concatenate([ids for ids, _ in lists]) if lists else np.zeros(0, np.int64)
+        if ids.size:
+            order = np.argsort(ids, kind="stable")
+            if not np.array_equal(ids[order], np.arange(ids.size)):
+                raise RuntimeError("an IndexBinaryIVF file whose ids are not the insertion numbers 0 .. ntotal - 1 is not "
+                                   "readable")
+            codes = np.ascontiguousarray(np.concatenate([codes for _, codes in lists])[order])
+            list_no = np.ascontiguousarray(np.repeat(np.arange(nlist, dtype=np.int64), [len(ids) for ids, _ in lists])[order])
+            _n.check(_n.lib.ise_binary_ivf_add_host(index._h, codes.ctypes.data, list_no.ctypes.data, codes.shape[0]))
+        return index
 
 
 # ---------------------------------------------------------------- product quantisation (faiss.IndexPQ)

@@ -621,6 +621,43 @@ int ise_ivfsq_search_device(ise_ivfsq_t* h, const float* q_dev, int64_t nq, int 
                             float* D_dev, int64_t* I_dev, void* stream);
 int ise_ivfsq_stats(ise_ivfsq_t* h, uint64_t* out3);
 
+/* Inverted lists over bit codes: faiss.IndexBinaryIVF (csrc/ise_binary_ivf.hpp).  An ise_binary_ivf_t is ise_ivfsq_t's
+ * lists holding ise_binary_index_t's codes: nlist lists of d_bits / 8 code bytes, NO centroids (the coarse quantiser is
+ * the caller's; rows come with their list numbers, searches with their probe tables, as for ise_ivf_*), and the Hamming
+ * distances, keys and tie order of ise_binary_index_search_*.  Calls, streams and workspaces as for ise_ivfsq_*.
+ *   create        d_bits a positive multiple of 8, at most ISE_BINARY_MAX_BITS, nlist >= 1; anything else is
+ *                 ISE_E_INVALID before the device is touched.  There is nothing to train
+ *   add           list_no[i] in [0, nlist) is the list of code i (n x d_bits / 8 bytes); a number outside makes the call
+ *                 ISE_E_INVALID and nothing is added.  The codes go into a pending buffer; both forms block.  A row's id
+ *                 is its insertion number; fewer than 2^32 rows.  The first search or list_host after an add rebuilds the
+ *                 lists (64-row tiles; one rebuild moves the whole index)
+ *   list_sizes    rows per list, pending ones included
+ *   list          ids (ascending) and codes (m x d_bits / 8 bytes) of one list, in list order; either may be NULL
+ *   search        probes: nq x nprobe list numbers; -1 and numbers outside [0, nlist) name nothing, a list named twice
+ *                 counts once.  The k best among the rows of a query's probed lists: D int32 Hamming distances ascending,
+ *                 ties by ascending id, unfilled slots INT32_MAX / -1; k in 1 .. ISE_MAX_K.  A pass serves 16 queries and
+ *                 32 results and reads the 64-row tiles of the lists that at least one of its queries probes, and no
+ *                 others; a call makes ceil(nq / 16) x ceil(k / 32) passes, none on an empty index.  search_device only
+ *                 enqueues, unless rows are pending or a workspace has to grow; search_host works through 4096 queries
+ *                 at a time
+ *   stats         out3[0] = search batches, out3[1] = scan passes, out3[2] = 64-row tiles the passes visited.  Waits
+ *                 for the device */
+typedef struct ise_binary_ivf ise_binary_ivf_t;
+int ise_binary_ivf_create(ise_binary_ivf_t** out, int d_bits, int nlist, int device);
+int ise_binary_ivf_destroy(ise_binary_ivf_t* h); /* NULL is a no-op */
+int ise_binary_ivf_reset(ise_binary_ivf_t* h);   /* drop all rows */
+int ise_binary_ivf_info(const ise_binary_ivf_t* h, int* d_bits, int* nlist, int64_t* ntotal, int* device);
+int ise_binary_ivf_add_host(ise_binary_ivf_t* h, const uint8_t* codes, const int64_t* list_no, int64_t n);
+int ise_binary_ivf_add_device(ise_binary_ivf_t* h, const uint8_t* codes_dev, const int64_t* list_no_dev, int64_t n,
+                              void* stream);
+int ise_binary_ivf_list_sizes_host(ise_binary_ivf_t* h, int64_t* sizes /* nlist */);
+int ise_binary_ivf_list_host(ise_binary_ivf_t* h, int list, int64_t* ids, uint8_t* codes);
+int ise_binary_ivf_search_host(ise_binary_ivf_t* h, const uint8_t* q, int64_t nq, int k, const int64_t* probes, int nprobe,
+                               int32_t* D, int64_t* I);
+int ise_binary_ivf_search_device(ise_binary_ivf_t* h, const uint8_t* q_dev, int64_t nq, int k, const int64_t* probes_dev,
+                                 int nprobe, int32_t* D_dev, int64_t* I_dev, void* stream);
+int ise_binary_ivf_stats(ise_binary_ivf_t* h, uint64_t* out3);
+
 /* Shard-local search for the multi-GPU path: writes nq x k
  * packed candidates, sorted best-first, suitable for one all-gather:
  *   key = (order-preserving uint32 image of the score) << 32 | (row + id_base)
