@@ -116,17 +116,6 @@ int rebuild_locked(ise_binary_ivf* h, hipStream_t st) {
     return ISE_OK;
 }
 
-void launch_scan(int wt, unsigned grid, size_t lds, hipStream_t st, const BinIvfScanParams& sp) {
-    static LdsAttrOnce attr[3];
-    auto go = [&](auto kern, LdsAttrOnce& a) {
-        a.ensure(reinterpret_cast<const void*>(kern), BIN_LDS_MAX);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(BIN_WAVES * 64), lds, st, sp);
-    };
-    if (wt == 1) go(binary_ivf_scan_kernel<1>, attr[0]);
-    else if (wt == 2) go(binary_ivf_scan_kernel<2>, attr[1]);
-    else go(binary_ivf_scan_kernel<0>, attr[2]);
-}
-
 // blocks of a pass: the flat Hamming pass's rule (ise_binary_scan.hip) on the lists' tiles in all (the host does not know
 // how many a group's work list holds without a wait): about two tiles per wave, at most two blocks per CU and the merge's
 // list count
@@ -160,7 +149,6 @@ int search_enqueue(ise_binary_ivf* h, const uint8_t* q_dev, long long nq, int k,
     CallOrder::Scope release{h->order, st};
     uint32_t* counts = h->offs.p + (size_t)gmax * nl;
     const int wt = bin_wt(h);
-    const size_t lds = BIN_BUF_BYTES + BIN_CNT_BYTES + (wt == 0 ? (size_t)BIN_QT * h->ws * 8 : 0);
     for (long long c0 = 0; c0 < nq; c0 += BIN_IVF_CHUNK) {
         // the chunk's padded queries, masks and work lists (in stream order behind the passes that read the last chunk's)
         const int m = (int)std::min<long long>(BIN_IVF_CHUNK, nq - c0);
@@ -188,7 +176,7 @@ int search_enqueue(ise_binary_ivf* h, const uint8_t* q_dev, long long nq, int k,
                 sp.work = h->work.p + (size_t)g * inv.tiles;
                 sp.count = counts + g;
                 sp.tiles_loaded = h->stats_dev;
-                launch_scan(wt, grid, lds, st, sp);
+                binary_ivf_scan_launch(wt, grid, h->ws, st, sp);
                 pass_merge_launch(h->lists.p, BIN_QT, BIN_KPASS, grid, nqt, kp, D_dev + (size_t)q0 * k, I_dev + (size_t)q0 * k, h->lo.p, k,
                                   off, 0, st);
                 h->passes++;

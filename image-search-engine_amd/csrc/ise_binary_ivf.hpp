@@ -1,6 +1,7 @@
 // ise_binary_ivf.hpp -- kernels of IndexBinaryIVF: inverted lists over the bit codes of ise_binary_scan.hpp and the
 // Hamming pass that scans only the probed ones (include/ise_knn.h, ise_binary_ivf_*).  Host side:
-// ise_binary_ivf.hip.
+// ise_binary_ivf.hip.  The launches below (binary_ivf_scan_launch, binary_ivf_rebuild_launch) have a second user:
+// tests/native/binary_ivf_harness.hip hands them crafted work lists and tables (tests/test_binary_ivf_lists_gpu.py).
 //
 // Layout.  All lists live in ONE array: codes [slots][ws] 64-bit words (ws as in ise_binary_scan.hpp: 1, or
 // ceil(code_size / 8) rounded up to an even count; the bytes past code_size zero) and ids [slots] uint32 (the row's
@@ -137,6 +138,20 @@ __global__ __launch_bounds__(BIN_WAVES * 64) void binary_ivf_scan_kernel(const B
         const int nw = wave_select<2 * BIN_WAVES>(kk, BIN_WAVES * BIN_CAP, kp, dst, &kth_unused);
         for (int i = nw + lane; i < kp; i += 64) dst[i] = KEY_PAD;
     }
+}
+
+// One pass's scan on st: grid blocks of the kernel for wt = 1, 2 (ws words a row) or 0 (any longer row, the queries in
+// LDS: [16][ws] words behind the buffers and the counts).  The caller takes hipGetLastError()
+inline void binary_ivf_scan_launch(int wt, unsigned grid, int ws, hipStream_t st, const BinIvfScanParams& sp) {
+    static LdsAttrOnce attr[3];
+    const size_t lds = BIN_BUF_BYTES + BIN_CNT_BYTES + (wt == 0 ? (size_t)BIN_QT * ws * 8 : 0);
+    auto go = [&](auto kern, LdsAttrOnce& a) {
+        a.ensure(reinterpret_cast<const void*>(kern), BIN_LDS_MAX);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(BIN_WAVES * 64), lds, st, sp);
+    };
+    if (wt == 1) go(binary_ivf_scan_kernel<1>, attr[0]);
+    else if (wt == 2) go(binary_ivf_scan_kernel<2>, attr[1]);
+    else go(binary_ivf_scan_kernel<0>, attr[2]);
 }
 
 // ---------------------------------------------------------------- rebuild (ise_binary_ivf.hip)

@@ -242,5 +242,77 @@ def test_reference_probe_tables_and_stats():
     assert binary_ivf_ref.stats_of(table, [0, 1, 64, 65], 70) == {"batches": 1, "passes": 3, "tiles_loaded": 12}
 
 
+# ---------------------------------------------------------------- the reference of one pass (tests/test_binary_ivf_lists_gpu.py)
+def pass_example(rng, cs=9):
+    """Lists of 0 .. 129 rows laid out as a rebuild leaves them, 16 queries (the first the zero code, which every pad slot
+    equals) and a probe table with -1, out-of-range and repeated lists -> what ``block_lists_of`` takes, and the rows."""
+    sizes = np.array([0, 1, 63, 64, 65, 128, 129], np.int64)
+    nlist, n = len(sizes), int(sizes.sum())
+    list_no = rng.permutation(np.repeat(np.arange(nlist), sizes))
+    xb = rng.integers(0, 256, (12, cs), dtype=np.uint8)[rng.integers(0, 12, n)]  # 12 distinct codes: ties everywhere
+    xq = np.concatenate([np.zeros((1, cs), np.uint8), xb[:3], rng.integers(0, 256, (12, cs), dtype=np.uint8)])
+    none = np.zeros(nlist, np.int64), np.zeros(0, np.uint32), np.zeros((0, cs), np.uint8)
+    got_sizes, codes, _, ids = binary_ivf_ref.rebuilt(*none, list_no, xb, 0, cs)
+    assert np.array_equal(got_sizes, sizes) and (ids == binary_ivf_ref.PAD_ID).sum() == len(ids) - n
+    table = rng.integers(-1, nlist + 1, (16, 3))
+    table[1] = (5, 5, -1)
+    table[2] = -1
+    table[3] = (0, nlist, 2 ** 40)  # the empty list and nothing else
+    masks = binary_ivf_ref.masks_of(table, nlist, 16)
+    (offs, count, entries), = binary_ivf_ref.work_list_of(masks, sizes)
+    keys = binary_ivf_ref.tile_keys(codes, ids, xq)
+    return sizes, list_no, xb, xq, table, count, entries, keys
+
+
+def test_block_lists_merge_to_search_preassigned():
+    rng = np.random.default_rng(7)
+    sizes, list_no, xb, xq, table, count, entries, keys = pass_example(rng)
+    nlist = len(sizes)
+    assert count >= 9 and (entries[:, 1] < 64).any() and len(set(entries[:, 2].tolist())) > 3
+    order = rng.permutation(count)  # the result does not depend on the order of the entries, the blocks' lists do
+    for nqt, kp in ((16, 1), (16, 7), (5, 32), (16, 32)):
+        want = binary_ivf_ref.search_preassigned(xb, list_no, xq[:nqt], kp, table[:nqt], nlist)
+        assert (want[1][2] == -1).all() and (want[1][3] == -1).all() and (want[1][1] >= 0).any()
+        for ent in (entries, entries[order]):
+            koe = keys[ent[:, 0]]
+            D, I, lo_out = binary_ivf_ref.pass_of(koe, ent, count, nqt, kp)
+            assert np.array_equal(D, want[0]) and np.array_equal(I, want[1])
+            assert np.array_equal(lo_out == binary_ivf_ref.KEY_PAD, want[1][:, -1] == -1)
+            for grid in (1, 2, 3, -(-count // 4), -(-count // 4) + 1, 64):
+                lists, empty = binary_ivf_ref.block_lists_of(koe, ent, count, grid, nqt, kp)
+                assert lists.shape == (grid, nqt, 32) and empty.sum() == max(0, grid - -(-count // 4))
+                assert (lists[empty] == binary_ivf_ref.KEY_PAD).all() and (lists[:, :, 1:kp] >= lists[:, :, :kp - 1]).all()
+                got = binary_ivf_ref.results_of(binary_ivf_ref.merged_of(lists, kp))
+                assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and np.array_equal(got[2], lo_out)
+    # a floor: the second pass of k = 40 continues where the first ended
+    koe = keys[entries[:, 0]]
+    first = binary_ivf_ref.pass_of(koe, entries, count, 16, 32)
+    second = binary_ivf_ref.pass_of(koe, entries, count, 16, 8, first[2])
+    want = binary_ivf_ref.search_preassigned(xb, list_no, xq, 40, table, nlist)
+    assert np.array_equal(np.concatenate([first[0], second[0]], axis=1), want[0])
+    assert np.array_equal(np.concatenate([first[1], second[1]], axis=1), want[1])
+
+
+def test_blocks_partition_the_work_list_in_slot_order():
+    """``work_list_of`` gives the entries in slot order; ``entries_of_block`` deals them to the blocks four at a time, each
+    to exactly one block, and a block's entries stay in slot order.  A key of an id at or above 2^31 keeps it."""
+    rng = np.random.default_rng(8)
+    sizes, list_no, xb, xq, table, count, entries, keys = pass_example(rng)
+    assert (np.diff(entries[:, 0].astype(np.int64)) > 0).all()
+    for grid in (1, 2, 3, 4, 64):
+        taken = [binary_ivf_ref.entries_of_block(count, grid, b) for b in range(grid)]
+        assert sorted(np.concatenate(taken).tolist()) == list(range(count))
+        for b, mine in enumerate(taken):
+            assert (np.diff(entries[mine, 0].astype(np.int64)) > 0).all()
+            assert all((e // 4) % grid == b for e in mine) and (len(mine) > 0) == (b * 4 < count)
+        assert taken[0][:4].tolist() == list(range(min(4, count)))
+    key = binary_ivf_ref.bin_key(np.array([0, 3]), np.array([0xFFFFFFFE, 2 ** 31], np.uint32))
+    assert key.tolist() == [(1 << 32) | 0xFFFFFFFE, (4 << 32) | 2 ** 31]
+    D, I, lo = binary_ivf_ref.results_of(np.array([[key[0], key[1], binary_ivf_ref.KEY_PAD]], np.uint64))
+    assert D.tolist() == [[0, 3, binary_ref.INT32_MAX]] and I.tolist() == [[0xFFFFFFFE, 2 ** 31, -1]] and lo[0] == binary_ivf_ref.KEY_PAD
+    assert binary_ivf_ref.stats_of(table, sizes, 70, batches=2)["batches"] == 2 and binary_ivf_ref.host_batches(4101) == 2
+    assert binary_ivf_ref.host_batches(4096) == 1
+
+
 if __name__ == "__main__":
     print(json.dumps(describe_binary_ivf_surface(), indent=1, sort_keys=True))
