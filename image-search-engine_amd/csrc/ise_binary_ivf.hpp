@@ -1,19 +1,19 @@
 // ise_binary_ivf.hpp -- kernels of IndexBinaryIVF: inverted lists over the bit codes of ise_binary_scan.hpp and the
 // Hamming pass that scans only the probed ones (include/ise_knn.h, ise_binary_ivf_*).  Host side:
-// ise_binary_ivf.hip.  The launches below (binary_ivf_scan_launch, binary_ivf_rebuild_launch) have a second user:
-// tests/native/binary_ivf_harness.hip hands them crafted work lists and tables (tests/test_binary_ivf_lists_gpu.py).
+// ise_binary_ivf.hip.  The launch below (binary_ivf_scan_launch) has a second user: tests/native/binary_ivf_harness.hip
+// hands it crafted work lists (tests/test_binary_ivf_lists_gpu.py).
 //
 // Layout.  All lists live in ONE array: codes [slots][ws] 64-bit words (ws as in ise_binary_scan.hpp: 1, or
 // ceil(code_size / 8) rounded up to an even count; the bytes past code_size zero) and ids [slots] uint32 (the row's
 // insertion number).  List l owns the 64-row tiles [list_tile0[l], list_tile0[l + 1]) -- a wave's unit in the Hamming
 // scan; inside a list the slots are in ascending id order, the slots behind list_size[l] rows are zero codes with id
-// 0xFFFFFFFF, masked by position.  A code row carries no row term: a rebuild moves words and ids only.
+// 0xFFFFFFFF, masked by position.  A code row carries no row term: a rebuild (ivf_rebuild_launch, ise_ivf_tiles.hpp)
+// moves words and ids only, in 8-byte units -- a row of ws == 1 is half a 16-byte unit, and a slot may be odd.
 //
 // A pass serves one group of BIN_QT = 16 queries and BIN_KPASS = 32 results:
-//   masks, work list   the kernels of the 8-bit lists themselves (ivf_mask_kernel, ise_ivf_lists.hpp; ivfsq_offsets_kernel,
-//                      ivfsq_work_kernel through ivfsq_work_list_launch, ise_ivfsq.hpp) with qshift = 4: per group the
-//                      entries (tile, valid rows, query mask) of the tiles of the lists that a query of the group probes,
-//                      in slot order.
+//   masks, work list   the lists' own kernels (ivf_mask_kernel, ivf_offsets_kernel, ivf_work_kernel through
+//                      ivf_work_list_launch, ise_ivf_tiles.hpp) with qshift = 4: per group the entries (tile, valid
+//                      rows, query mask) of the tiles of the lists that a query of the group probes, in slot order.
 //   scan               binary_ivf_scan_kernel: wave w of block b takes entries b BIN_WAVES + w + j gridDim.x BIN_WAVES,
 //                      lane l owns slot tile * 64 + l (valid while l < valid rows), hamming16 gives its 16 distances, the
 //                      key is bin_key(distance, ids[slot]) -- the id, not the slot, so ties go by ascending id whatever
@@ -29,11 +29,11 @@
 // what a launch changes is which wave meets which key, never which keys survive.
 #pragma once
 #include "ise_binary_scan.hpp"
-#include "ise_ivfsq.hpp"
+#include "ise_ivf_tiles.hpp"
 
-#define BIN_IVF_TILE 64 /* rows of a list tile: a wave's unit, and the work list's (SQ_TILE) */
+#define BIN_IVF_TILE 64 /* rows of a list tile: a wave's unit, and the work list's */
 #define BIN_IVF_CHUNK 64 /* queries whose work lists are built per launch: BIN_IVF_CHUNK / BIN_QT groups */
-static_assert(BIN_IVF_TILE == SQ_TILE, "ivfsq_work_kernel counts a tile's valid rows in units of SQ_TILE");
+static_assert(BIN_IVF_TILE == IVF_WORK_TILE, "ivf_work_kernel counts a tile's valid rows in units of IVF_WORK_TILE");
 static_assert(BIN_IVF_CHUNK % BIN_QT == 0 && (1 << 4) == BIN_QT, "groups of 16 queries: qshift = 4");
 
 struct BinIvfScanParams {
@@ -152,58 +152,4 @@ inline void binary_ivf_scan_launch(int wt, unsigned grid, int ws, hipStream_t st
     if (wt == 1) go(binary_ivf_scan_kernel<1>, attr[0]);
     else if (wt == 2) go(binary_ivf_scan_kernel<2>, attr[1]);
     else go(binary_ivf_scan_kernel<0>, attr[2]);
-}
-
-// ---------------------------------------------------------------- rebuild (ise_binary_ivf.hip)
-// A code row is ws words and nothing else.  Both kernels copy 8-byte words: a row of ws == 1 is half a 16-byte unit,
-// and a pending row's destination slot may be odd.
-//
-// one block per OLD tile: the tile moves, whole, to where its list now starts (ids and pad slots with it)
-static __global__ __launch_bounds__(256) void binary_ivf_move_tiles_kernel(const u64* __restrict__ src,
-                                                                           const uint32_t* __restrict__ src_ids,
-                                                                           const uint32_t* __restrict__ old_tile_list,
-                                                                           const uint32_t* __restrict__ old_tile0,
-                                                                           const uint32_t* __restrict__ new_tile0, int ws,
-                                                                           u64* __restrict__ dst, uint32_t* __restrict__ dst_ids) {
-    const size_t t = blockIdx.x;
-    const uint32_t l = old_tile_list[t];
-    const size_t nt = (size_t)new_tile0[l] + (t - old_tile0[l]);
-    const u64* s = src + t * BIN_IVF_TILE * ws;
-    u64* o = dst + nt * BIN_IVF_TILE * ws;
-    for (int i = threadIdx.x; i < BIN_IVF_TILE * ws; i += 256) o[i] = s[i];
-    if (threadIdx.x < BIN_IVF_TILE) dst_ids[nt * BIN_IVF_TILE + threadIdx.x] = src_ids[t * BIN_IVF_TILE + threadIdx.x];
-}
-
-// wave per pending row i: to slot dest[i], with id id0 + i
-static __global__ __launch_bounds__(256) void binary_ivf_scatter_rows_kernel(const u64* __restrict__ pend, long long m,
-                                                                             const uint32_t* __restrict__ dest, uint32_t id0,
-                                                                             int ws, u64* __restrict__ dst,
-                                                                             uint32_t* __restrict__ dst_ids) {
-    const int lane = threadIdx.x & 63;
-    const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= m) return;
-    const size_t slot = dest[i];
-    const u64* s = pend + (size_t)i * ws;
-    u64* o = dst + slot * ws;
-    for (int j = lane; j < ws; j += 64) o[j] = s[j];
-    if (lane == 0) dst_ids[slot] = id0 + (uint32_t)i;
-}
-
-// the new arrays nx / nids of new_tiles tiles (table nmeta): cleared (pad slots are zero codes with id ~0), the
-// old_tiles old tiles (table meta; not read without an old tile) moved, the pend_n >= 1 pending rows scattered to dest
-// with the ids id0, id0 + 1, ..  Enqueues on st and returns the first error of a memset; the caller takes
-// hipGetLastError() for the launches
-inline hipError_t binary_ivf_rebuild_launch(const u64* codes, const uint32_t* ids, const uint32_t* meta, long long old_tiles,
-                                            const u64* pend, long long pend_n, const uint32_t* dest, uint32_t id0, int ws, int nlist,
-                                            const uint32_t* nmeta, long long new_tiles, u64* nx, uint32_t* nids, hipStream_t st) {
-    const size_t slots = (size_t)new_tiles * BIN_IVF_TILE;
-    hipError_t e = hipMemsetAsync(nx, 0, slots * ws * sizeof(u64), st);
-    if (e == hipSuccess) e = hipMemsetAsync(nids, 0xFF, slots * sizeof(uint32_t), st);
-    if (e != hipSuccess) return e;
-    if (old_tiles > 0)
-        hipLaunchKernelGGL(binary_ivf_move_tiles_kernel, dim3((unsigned)old_tiles), dim3(256), 0, st, codes, ids,
-                           meta + ivf_meta_tile_list_at((size_t)nlist), meta, nmeta, ws, nx, nids);
-    hipLaunchKernelGGL(binary_ivf_scatter_rows_kernel, dim3((unsigned)((pend_n + 3) / 4)), dim3(256), 0, st, pend, pend_n, dest, id0,
-                       ws, nx, nids);
-    return hipSuccess;
 }

@@ -10,7 +10,7 @@
 // ivf_scan_kernel makes one pass per group of 16 queries (grid.y).  It is sel_scan_kernel's loop (ise_sel_scan.hpp)
 // with the selector's half-word replaced by two tests -- "position < list size" and "this query's bit in the list's
 // mask" -- and with these differences:
-//   masks        ivf_mask_kernel (ise_ivf_lists.hpp; groups of 16: qshift 4) turns the probe table [nq][nprobe] into
+//   masks        ivf_mask_kernel (ise_ivf_tiles.hpp; groups of 16: qshift 4) turns the probe table [nq][nprobe] into
 //                one 16-bit query mask per (group, list); -1 and out-of-range entries set nothing, a duplicate sets
 //                its bit twice.
 //   work split   the tiles are dealt ROUND-ROBIN: round r gives block b the 8 consecutive tiles from (r blocks + b) 8,
@@ -186,33 +186,10 @@ __global__ __launch_bounds__(SEL_W * 64) void ivf_scan_kernel(const IvfScanParam
     }
 }
 
-// ---------------------------------------------------------------- rebuild (ise_ivf.hip, ivf_rebuild_locked)
-// one block per OLD tile: the tile moves, whole, to where its list now starts (ids and pad slots with it)
-static __global__ __launch_bounds__(256) void ivf_move_tiles_kernel(const float* src, const uint32_t* src_ids,
-                                                             const uint32_t* old_tile_list, const uint32_t* old_tile0,
-                                                             const uint32_t* new_tile0, int dp, float* dst, uint32_t* dst_ids) {
-    const size_t t = blockIdx.x;
-    const uint32_t l = old_tile_list[t];
-    const size_t nt = (size_t)new_tile0[l] + (t - old_tile0[l]);
-    const f32x4* s = reinterpret_cast<const f32x4*>(src + t * 16 * dp);
-    f32x4* o = reinterpret_cast<f32x4*>(dst + nt * 16 * dp);
-    for (int i = threadIdx.x; i < 4 * dp; i += 256) o[i] = s[i];
-    if (threadIdx.x < 16) dst_ids[nt * 16 + threadIdx.x] = src_ids[t * 16 + threadIdx.x];
-}
-
-// wave per pending row i: to slot dest[i], with id id0 + i
-static __global__ __launch_bounds__(256) void ivf_scatter_rows_kernel(const float* pend, long long m, const uint32_t* dest,
-                                                               uint32_t id0, int dp, float* dst, uint32_t* dst_ids) {
-    const int lane = threadIdx.x & 63;
-    const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= m) return;
-    const size_t slot = dest[i];
-    const f32x4* s = reinterpret_cast<const f32x4*>(pend + (size_t)i * dp);
-    f32x4* o = reinterpret_cast<f32x4*>(dst + slot * dp);
-    for (int j = lane; j < dp / 4; j += 64) o[j] = s[j];
-    if (lane == 0) dst_ids[slot] = id0 + (uint32_t)i;
-}
-
+// ---------------------------------------------------------------- rebuild (ise_ivf.hip)
+// The rows move and scatter with the lists' own kernels (ivf_rebuild_launch, ise_ivf_tiles.hpp: 16-row tiles, 16-byte
+// units); what follows is computed on the new array behind them.
+//
 // column sums of `rows` padded rows in `groups` row groups, then the mean over n real rows (pad slots are zero):
 // fixed order, NaN / inf entries skipped (as the flat index's shift, ise_rows.hpp)
 static __global__ __launch_bounds__(256) void ivf_col_sum_kernel(const float* x, long long rows, int d, int dp, int groups,

@@ -1834,22 +1834,31 @@ class _IndexIVF(_IndexHandle):
     its clustering in ``train``, the assignment of rows to lists, ``add``, ``get_list``, ``nprobe`` and ``search`` as
     ``search_preassigned`` of the quantiser's answer.  A subclass creates its handle, says what ``is_trained`` is and
     names its family of entry points (``_ABI``), the two search calls outright (``_search_host``, ``_search_device``),
-    its ``ntotal``, the dtype of a list's payload of (m, d) entries (``_LIST_DTYPE``) and whether it encodes its rows
-    (``_ENCODES``).  An index that does checks the rows of an ``add`` for NaN / inf entries, needs its training in
+    its ``ntotal``, the dtype of a list's payload of (m, width) entries (``_LIST_DTYPE``) and whether it encodes its
+    rows (``_ENCODES``).  An index that does checks the rows of an ``add`` for NaN / inf entries, needs its training in
     ``search_preassigned`` too and answers an empty batch there itself, and has no lists to read while its codec is
-    untrained."""
+    untrained.  An index over bit codes also names its quantiser's type (``_QUANTIZER``), how rows and queries are
+    coerced (``_COERCE``: ``_as_rows`` or ``_as_codes``, to ``_width`` entries a row) and the dtypes of a row's entries
+    and of a distance (``_ROW_DTYPE``, ``_DIST_DTYPE``: the name numpy and torch share)."""
 
+    _QUANTIZER = IndexFlat
+    _COERCE = staticmethod(_as_rows)
+    _ROW_DTYPE = "float32"
+    _DIST_DTYPE = "float32"
     _LIST_DTYPE = np.float32
     _ENCODES = False
 
-    def _init_ivf(self, quantizer: IndexFlat, d: int, nlist: int, metric: int) -> None:
-        assert isinstance(quantizer, IndexFlat), "the coarse quantiser is an IndexFlat"
+    def _init_ivf(self, quantizer, d: int, nlist: int, metric: int | None, width: int | None = None) -> None:
+        """``metric``: None on an index without a ``metric_type``; ``width``: entries of a row where it is not ``d``."""
+        assert isinstance(quantizer, self._QUANTIZER), f"the coarse quantiser is an {self._QUANTIZER.__name__}"
         assert quantizer.d == int(d), f"dimension mismatch: quantizer has d={quantizer.d}, index d={d}"
         self.quantizer = quantizer
         self.d = int(d)
+        self._width = self.d if width is None else int(width)
         self.nlist = int(nlist)
         self.nprobe = 1
-        self.metric_type = int(metric)
+        if metric is not None:
+            self.metric_type = int(metric)
         self.cp = ClusteringParameters()
         self.device = quantizer.device
         self._h = ctypes.c_void_p()
@@ -1895,10 +1904,10 @@ class _IndexIVF(_IndexHandle):
 
     def _assign_torch(self, x):
         """The same on the device: the route ``quantizer.search(x, 1)`` takes for this many rows, so that the ids are the
-        same; the list numbers are read back to be checked."""
+        same (a quantiser over bit codes has the one route); the list numbers are read back to be checked."""
         qz = self.quantizer
-        n = x.shape[0]
-        lists = (qz.assign_torch(x) if qz._assign_applies(n, 1) else qz.search_torch(x, 1))[1].reshape(-1).contiguous()
+        assign = hasattr(qz, "_assign_applies") and qz._assign_applies(x.shape[0], 1)
+        lists = (qz.assign_torch(x) if assign else qz.search_torch(x, 1))[1].reshape(-1).contiguous()
         self._check_assignment(lists.cpu().numpy())
         return lists
 
@@ -1908,7 +1917,7 @@ class _IndexIVF(_IndexHandle):
         ``quantizer.search(x, 1)[1][i]``.  On an index that encodes, a row with a NaN or inf entry raises ``ValueError``
         and nothing of the call is added."""
         self._require_trained("add")
-        x = _as_rows(x, self.d)
+        x = self._COERCE(x, self._width)
         if x.shape[0] == 0:
             return
         lists = self._assign(x)
@@ -1916,13 +1925,13 @@ class _IndexIVF(_IndexHandle):
             self._fn("add_host")(self._h, x.ctypes.data, lists.ctypes.data, x.shape[0]))
 
     def add_torch(self, x) -> None:
-        """``add`` from a CUDA float32 tensor on this index's device (no host hop for the rows; the list numbers are
-        read back to be checked, and an index that encodes waits for the encoder's verdict on non-finite entries).
-        Under the index's lock, like every device call that names a stream."""
+        """``add`` from a CUDA tensor of the rows' dtype on this index's device (no host hop for the rows; the list
+        numbers are read back to be checked, and an index that encodes waits for the encoder's verdict on non-finite
+        entries).  Under the index's lock, like every device call that names a stream."""
         import torch
 
         self._require_trained("add")
-        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.d
+        assert x.is_cuda and x.dtype == getattr(torch, self._ROW_DTYPE) and x.dim() == 2 and x.shape[1] == self._width
         x = x.contiguous()
         n = x.shape[0]
         if n == 0:
@@ -1940,11 +1949,11 @@ class _IndexIVF(_IndexHandle):
         return int(sizes[int(l)])
 
     def get_list(self, l: int):
-        """(ids int64 (m,), rows (m, d) -- float32, or the uint8 codes of an index that encodes) of list ``l``, in list
-        order (ascending ids)."""
+        """(ids int64 (m,), rows (m, width) -- float32, or the uint8 codes of an index that encodes or holds bit codes)
+        of list ``l``, in list order (ascending ids)."""
         m = self.list_size(l)
         ids = np.empty(m, dtype=np.int64)
-        rows = np.empty((m, self.d), dtype=self._LIST_DTYPE)
+        rows = np.empty((m, self._width), dtype=self._LIST_DTYPE)
         if self._codec_trained():
             _n.check(self._fn("list_host")(self._h, int(l), ids.ctypes.data, rows.ctypes.data))
         return ids, rows
@@ -1958,26 +1967,26 @@ class _IndexIVF(_IndexHandle):
             raise NotImplementedError(f"search parameters are not provided on {type(self).__name__}: set index.nprobe")
 
     def search(self, x, k: int, params=None):
-        """(D float32 (nq,k), I int64 (nq,k)), fresh arrays: the k best among the rows of the ``nprobe`` lists nearest
-        to each query (``quantizer.search(x, min(nprobe, nlist))[1]``)."""
+        """(D (nq,k) float32 -- int32 over bit codes --, I int64 (nq,k)), fresh arrays: the k best among the rows of the
+        ``nprobe`` lists nearest to each query (``quantizer.search(x, min(nprobe, nlist))[1]``)."""
         self._no_params(params)
         self._require_trained("search")
-        x = _as_rows(x, self.d)
+        x = self._COERCE(x, self._width)
         if x.shape[0] == 0:
-            return np.empty((0, int(k)), dtype=np.float32), np.empty((0, int(k)), dtype=np.int64)
+            return np.empty((0, int(k)), dtype=self._DIST_DTYPE), np.empty((0, int(k)), dtype=np.int64)
         return self.search_preassigned(x, k, self.quantizer.search(x, self._nprobe())[1])
 
     def search_preassigned(self, x, k: int, probes):
         """``search`` with the probed lists given: ``probes`` int64 (nq, nprobe); -1 entries are ignored."""
         if self._ENCODES:
             self._require_trained("search")
-        x = _as_rows(x, self.d)
+        x = self._COERCE(x, self._width)
         k = int(k)
         assert k > 0
         nq = x.shape[0]
         probes = np.ascontiguousarray(np.asarray(probes), dtype=np.int64)
         assert probes.ndim == 2 and probes.shape[0] == nq and probes.shape[1] >= 1
-        D = np.empty((nq, k), dtype=np.float32)
+        D = np.empty((nq, k), dtype=self._DIST_DTYPE)
         I = np.empty((nq, k), dtype=np.int64)
         if nq or not self._ENCODES:  # (the float family checks k and the probes of an empty batch too)
             _n.check(self._search_host(self._h, x.ctypes.data, nq, k, probes.ctypes.data, probes.shape[1],
@@ -1985,15 +1994,15 @@ class _IndexIVF(_IndexHandle):
         return D, I
 
     def search_torch(self, xq, k: int, params=None):
-        """Device-resident search: CUDA float32 (nq,d) in, CUDA (D, I) out; the quantiser's search and the scan are
-        enqueued on the current torch stream.  No host synchronisation, except that the first search after an ``add``
-        rebuilds the lists and waits for that."""
+        """Device-resident search: CUDA (nq, width) of the rows' dtype in, CUDA (D, I) out; the quantiser's search and
+        the scan are enqueued on the current torch stream, under the index's lock.  No host synchronisation, except
+        that the first search after an ``add`` rebuilds the lists and waits for that."""
         import torch
 
         self._no_params(params)
         self._require_trained("search")
         k = int(k)
-        xq, D, I, st = _torch_io(xq, torch.float32, self.d, k, torch.float32)
+        xq, D, I, st = _torch_io(xq, getattr(torch, self._ROW_DTYPE), self._width, k, getattr(torch, self._DIST_DTYPE))
         nq = xq.shape[0]
         if nq == 0:
             return D, I
@@ -2072,6 +2081,11 @@ class IndexBinaryIVF(_IndexIVF):
     For given centroid codes everything here is determined, and it is checked exactly against this package's own flat
     binary index; Faiss's own binary IVF (its k-means seeding, its order among equal distances) is unpinned.
 
+    Rows and queries are uint8 (n, d / 8), on the host or, in ``add_torch`` / ``search_torch``, as CUDA tensors; D is int32
+    and I int64 (on the device too), unfilled slots are INT32_MAX / -1; ``get_list`` gives (ids int64 (m,), codes uint8
+    (m, d / 8)).  In ``search_preassigned``'s probes, -1 and out-of-range entries are ignored and a list named twice
+    counts once.
+
     The lists live on the device (include/ise_knn.h, ise_binary_ivf_*): ``add`` appends to a pending
     buffer, the first search after an ``add`` rebuilds the lists.  Not provided (they raise ``NotImplementedError``):
     ``range_search``, ``remove_ids``, ``params=`` and ``IndexBinaryIDMap`` over this type."""
@@ -2079,21 +2093,16 @@ class IndexBinaryIVF(_IndexIVF):
     _ABI = "ise_binary_ivf"
     _search_host = staticmethod(_n.lib.ise_binary_ivf_search_host)
     _search_device = staticmethod(_n.lib.ise_binary_ivf_search_device)
+    _QUANTIZER = IndexBinaryFlat
+    _COERCE = staticmethod(_as_codes)
+    _ROW_DTYPE = "uint8"
+    _DIST_DTYPE = "int32"
     _LIST_DTYPE = np.uint8
     ntotal = _ntotal_property(_n.lib.ise_binary_ivf_info, 5, 3)
 
     def __init__(self, quantizer: IndexBinaryFlat, d: int, nlist: int):
-        assert isinstance(quantizer, IndexBinaryFlat), "the coarse quantiser is an IndexBinaryFlat"
-        assert quantizer.d == int(d), f"dimension mismatch: quantizer has d={quantizer.d}, index d={d}"
-        self.quantizer = quantizer
-        self.d = int(d)
-        self.code_size = self.d // 8
-        self.nlist = int(nlist)
-        self.nprobe = 1
-        self.cp = ClusteringParameters()
-        self.device = quantizer.device
-        self._h = ctypes.c_void_p()
-        self._lock = threading.Lock()
+        self.code_size = int(d) // 8
+        self._init_ivf(quantizer, d, nlist, None, self.code_size)
         _n.check(_n.lib.ise_binary_ivf_create(ctypes.byref(self._h), self.d, self.nlist, self.device))
         self.is_trained = quantizer.ntotal == self.nlist
 
@@ -2119,87 +2128,6 @@ class IndexBinaryIVF(_IndexIVF):
             km.train(_bits_to_signs(x, self.d))
             self.quantizer.add(_signs_to_bits(km.centroids))
         self.is_trained = True
-
-    def add(self, x) -> None:
-        """Append codes (copied): uint8 (n, d / 8); row i of the call goes to list ``quantizer.search(x, 1)[1][i]``."""
-        self._require_trained("add")
-        x = _as_codes(x, self.code_size)
-        if x.shape[0] == 0:
-            return
-        lists = self._assign(x)
-        _n.check(_n.lib.ise_binary_ivf_add_host(self._h, x.ctypes.data, lists.ctypes.data, x.shape[0]))
-
-    def add_torch(self, x) -> None:
-        """``add`` from a CUDA uint8 tensor on this index's device (no host hop for the codes; the list numbers are read
-        back to be checked).  Under the index's lock, like every device call that names a stream."""
-        import torch
-
-        self._require_trained("add")
-        assert x.is_cuda and x.dtype == torch.uint8 and x.dim() == 2 and x.shape[1] == self.code_size
-        x = x.contiguous()
-        n = x.shape[0]
-        if n == 0:
-            return
-        lists = self.quantizer.search_torch(x, 1)[1].reshape(-1).contiguous()
-        self._check_assignment(lists.cpu().numpy())
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        with self._lock:
-            _n.check(_n.lib.ise_binary_ivf_add_device(self._h, x.data_ptr(), lists.data_ptr(), n, st))
-
-    # -- lists
-    def get_list(self, l: int):
-        """(ids int64 (m,), codes uint8 (m, d / 8)) of list ``l``, in list order (ascending ids)."""
-        m = self.list_size(l)
-        ids = np.empty(m, dtype=np.int64)
-        codes = np.empty((m, self.code_size), dtype=np.uint8)
-        _n.check(_n.lib.ise_binary_ivf_list_host(self._h, int(l), ids.ctypes.data, codes.ctypes.data))
-        return ids, codes
-
-    # -- query side
-    def search(self, x, k: int, params=None):
-        """(D int32 (nq, k), I int64 (nq, k)), fresh arrays: the k best among the rows of the ``nprobe`` lists nearest
-        to each query (``quantizer.search(x, min(nprobe, nlist))[1]``), ascending (distance, id); unfilled slots are
-        INT32_MAX / -1."""
-        self._no_params(params)
-        self._require_trained("search")
-        x = _as_codes(x, self.code_size)
-        if x.shape[0] == 0:
-            return np.empty((0, int(k)), dtype=np.int32), np.empty((0, int(k)), dtype=np.int64)
-        return self.search_preassigned(x, k, self.quantizer.search(x, self._nprobe())[1])
-
-    def search_preassigned(self, x, k: int, probes):
-        """``search`` with the probed lists given: ``probes`` int64 (nq, nprobe); -1 and out-of-range entries are
-        ignored, a list named twice counts once."""
-        x = _as_codes(x, self.code_size)
-        k = int(k)
-        assert k > 0
-        nq = x.shape[0]
-        probes = np.ascontiguousarray(np.asarray(probes), dtype=np.int64)
-        assert probes.ndim == 2 and probes.shape[0] == nq and probes.shape[1] >= 1
-        D = np.empty((nq, k), dtype=np.int32)
-        I = np.empty((nq, k), dtype=np.int64)
-        _n.check(self._search_host(self._h, x.ctypes.data, nq, k, probes.ctypes.data, probes.shape[1], D.ctypes.data,
-                                   I.ctypes.data))
-        return D, I
-
-    def search_torch(self, xq, k: int, params=None):
-        """Device-resident search: CUDA uint8 (nq, d / 8) in, CUDA (D int32, I int64) out; the quantiser's search and
-        the scan are enqueued on the current torch stream, under the index's lock.  No host synchronisation, except that
-        the first search after an ``add`` rebuilds the lists and waits for that."""
-        import torch
-
-        self._no_params(params)
-        self._require_trained("search")
-        k = int(k)
-        xq, D, I, st = _torch_io(xq, torch.uint8, self.code_size, k, torch.int32)
-        nq = xq.shape[0]
-        if nq == 0:
-            return D, I
-        probes = self.quantizer.search_torch(xq, self._nprobe())[1].contiguous()
-        with self._lock:
-            _n.check(self._search_device(self._h, xq.data_ptr(), nq, k, probes.data_ptr(), probes.shape[1], D.data_ptr(),
-                                         I.data_ptr(), st))
-        return D, I
 
     def binary_ivf_stats(self) -> dict:
         """Search batches, scan passes (one per 16 queries and 32 results), 64-row tiles of list rows the passes visited

@@ -1,7 +1,9 @@
 """numpy reference of the inverted-list index over 8-bit rows (tests only): which 64-row tiles a pass visits, the
 statistics a search adds, the expected results -- ``sq_ref.expected``'s complete ranking over the decoded rows cut to
 ``ivf_ref.probed_members`` -- and the device side's tables as plain integers: the query masks, the work list and the
-arrays after a rebuild (csrc/ise_ivfsq.hpp; tests/test_ivfsq_lists_gpu.py compares them word for word)."""
+arrays after a rebuild (csrc/ise_ivf_tiles.hpp; tests/test_ivfsq_lists_gpu.py compares them word for word).  The layout
+functions take the rows of a tile (``tile_rows``, 64 unless given): with 16 they are the float32 lists' layout, whose
+rebuild runs the same kernels (tests/test_ivf_rebuild_gpu.py)."""
 import numpy as np
 
 from tests import ivf_ref, sq_ref
@@ -9,14 +11,14 @@ from tests import ivf_ref, sq_ref
 TILE_ROWS = sq_ref.TILE_ROWS  # 64: a wave's unit in the byte scan
 
 
-def tiles_of(sizes) -> int:
-    """Total of ceil(size / 64) over the given list sizes."""
-    return int(sum((int(s) + TILE_ROWS - 1) // TILE_ROWS for s in sizes))
+def tiles_of(sizes, tile_rows: int = TILE_ROWS) -> int:
+    """Total of ceil(size / tile_rows) over the given list sizes."""
+    return int(sum((int(s) + tile_rows - 1) // tile_rows for s in sizes))
 
 
-def tile0_of(sizes) -> np.ndarray:
+def tile0_of(sizes, tile_rows: int = TILE_ROWS) -> np.ndarray:
     """(nlist + 1,) first tile of every list in the one array, and the tiles in all."""
-    return np.concatenate([[0], np.cumsum([(int(s) + TILE_ROWS - 1) // TILE_ROWS for s in sizes])]).astype(np.int64)
+    return np.concatenate([[0], np.cumsum([(int(s) + tile_rows - 1) // tile_rows for s in sizes])]).astype(np.int64)
 
 
 def pass_tile_sets(probes, sizes, d: int) -> list:
@@ -49,15 +51,15 @@ def expected(xq, dec, probes, assign, nlist: int, k: int, metric: int, full=None
     return ivf_ref.expected_from_ranking(full[0], full[1], members, k, metric)
 
 
-# ---- the tables of the device side (csrc/ise_ivfsq.hpp), as plain integers
+# ---- the tables of the device side (csrc/ise_ivf_tiles.hpp), as plain integers
 PAD_ID = 0xFFFFFFFF  # the id of a slot behind a list's rows
 
 
-def meta_of(sizes) -> np.ndarray:
+def meta_of(sizes, tile_rows: int = TILE_ROWS) -> np.ndarray:
     """uint32 table the kernels read (csrc/ise_ivf_plan.hpp, ivf_plan_meta): list_tile0 [nlist + 1] | list_size [nlist]
     | tile_list [tiles]."""
     sizes = np.asarray(sizes, dtype=np.int64)
-    t0 = tile0_of(sizes)
+    t0 = tile0_of(sizes, tile_rows)
     tile_list = np.repeat(np.arange(len(sizes)), np.diff(t0))
     return np.concatenate([t0, sizes, tile_list]).astype(np.uint32)
 
@@ -95,27 +97,28 @@ def work_list_of(masks, sizes) -> list:
     return out
 
 
-def rebuild_dest(old_sizes, pend_lists) -> np.ndarray:
+def rebuild_dest(old_sizes, pend_lists, tile_rows: int = TILE_ROWS) -> np.ndarray:
     """uint32 [m]: the slot of pending row i after the rebuild -- behind the old rows of its list and the pending rows
     of that list that came before it."""
     old_sizes = np.asarray(old_sizes, dtype=np.int64)
     pend_lists = np.asarray(pend_lists, dtype=np.int64).reshape(-1)
     new_sizes = old_sizes + np.bincount(pend_lists, minlength=len(old_sizes))
-    t0 = tile0_of(new_sizes)
+    t0 = tile0_of(new_sizes, tile_rows)
     nxt = old_sizes.copy()
     dest = np.empty(len(pend_lists), np.uint32)
     for i, l in enumerate(pend_lists):
-        dest[i] = t0[l] * TILE_ROWS + nxt[l]
+        dest[i] = t0[l] * tile_rows + nxt[l]
         nxt[l] += 1
     return dest
 
 
-def rebuilt(old_sizes, old_ids, old_codes, pend_lists, pend_codes, id0: int, stride: int, old_rterm=None, pend_rterm=None):
+def rebuilt(old_sizes, old_ids, old_codes, pend_lists, pend_codes, id0: int, stride: int, old_rterm=None, pend_rterm=None,
+            tile_rows: int = TILE_ROWS):
     """-> (new sizes, codes uint8 [slots][stride], rterm float64 [slots], ids uint32 [slots]) after the rebuild.
     old_ids [old slots], old_codes [old slots][stride]: the arrays before it, laid out by ``old_sizes``; pend_lists [m],
     pend_codes [m][stride]: the pending rows in insertion order, row i has id ``id0 + i``.  Every list keeps its old
-    rows in their order and takes its pending rows behind them in theirs; the slots behind a list's rows are zero rows
-    with id 0xFFFFFFFF.  The row terms travel with the rows; left out, a row's term is the sum of its squared bytes."""
+    rows in their order and takes its pending rows behind them in theirs; the slots behind a list's rows (to the end of
+    its last tile of ``tile_rows`` rows) are zero rows with id 0xFFFFFFFF.  The row terms travel with the rows; left out, a row's term is the sum of its squared bytes."""
     old_sizes = np.asarray(old_sizes, dtype=np.int64)
     pend_lists = np.asarray(pend_lists, dtype=np.int64).reshape(-1)
     old_codes = np.asarray(old_codes, np.uint8).reshape(-1, stride)
@@ -124,18 +127,18 @@ def rebuilt(old_sizes, old_ids, old_codes, pend_lists, pend_codes, id0: int, str
         old_rterm = (old_codes.astype(np.float64) ** 2).sum(1)
     if pend_rterm is None:
         pend_rterm = (pend_codes.astype(np.float64) ** 2).sum(1)
-    old_t0 = tile0_of(old_sizes)
-    assert len(old_codes) == len(old_ids) == len(old_rterm) == old_t0[-1] * TILE_ROWS and len(pend_codes) == len(pend_lists)
+    old_t0 = tile0_of(old_sizes, tile_rows)
+    assert len(old_codes) == len(old_ids) == len(old_rterm) == old_t0[-1] * tile_rows and len(pend_codes) == len(pend_lists)
     new_sizes = old_sizes + np.bincount(pend_lists, minlength=len(old_sizes))
-    t0 = tile0_of(new_sizes)
-    slots = int(t0[-1]) * TILE_ROWS
+    t0 = tile0_of(new_sizes, tile_rows)
+    slots = int(t0[-1]) * tile_rows
     codes = np.zeros((slots, stride), np.uint8)
     rterm = np.zeros(slots, np.float64)
     ids = np.full(slots, PAD_ID, np.uint32)
     order = np.argsort(pend_lists, kind="stable")
     first = np.searchsorted(pend_lists[order], np.arange(len(old_sizes) + 1))
     for l in range(len(old_sizes)):
-        a, b, m = int(old_t0[l]) * TILE_ROWS, int(t0[l]) * TILE_ROWS, int(old_sizes[l])
+        a, b, m = int(old_t0[l]) * tile_rows, int(t0[l]) * tile_rows, int(old_sizes[l])
         mine = order[first[l]:first[l + 1]]
         codes[b:b + m], rterm[b:b + m], ids[b:b + m] = old_codes[a:a + m], old_rterm[a:a + m], old_ids[a:a + m]
         b += m

@@ -1,10 +1,10 @@
 // binary_ivf_harness.hip -- test-only launchers around one pass and the rebuild of the inverted lists over bit codes
-// (csrc/ise_binary_ivf.hpp: binary_ivf_scan_kernel, binary_ivf_move_tiles_kernel, binary_ivf_scatter_rows_kernel;
-// csrc/ise_merge.hpp: pass_merge_kernel<int>), so that tests/test_binary_ivf_lists_gpu.py can hand them crafted work
-// lists, floors and list tables and read every word they write.  Built by csrc/Makefile into
+// (csrc/ise_binary_ivf.hpp: binary_ivf_scan_kernel; csrc/ise_ivf_tiles.hpp: ivf_move_tiles_kernel<64, u64>,
+// ivf_scatter_rows_kernel<u64>; csrc/ise_merge.hpp: pass_merge_kernel<int>), so that tests/test_binary_ivf_lists_gpu.py
+// can hand them crafted work lists, floors and list tables and read every word they write.  Built by csrc/Makefile into
 // libise_binary_ivf_check.so; never linked into libise_knn.so.  The headers are included as they are, and the launches
-// are the product's own (binary_ivf_scan_launch, pass_merge_launch<int>, binary_ivf_rebuild_launch): whatever is wrong
-// here is wrong in the product.
+// are the product's own (binary_ivf_scan_launch, pass_merge_launch<int>, ivf_rebuild_launch): whatever is wrong here
+// is wrong in the product.
 //
 // Every launcher takes device pointers, launches on the null stream and returns hipGetLastError() as an int.  The
 // callers validate the sizes of every array against the tables (tests/test_binary_ivf_lists_gpu.py, the wrappers at
@@ -49,7 +49,8 @@ extern "C" int chk_binary_ivf_rebuild(const u64* codes, const uint32_t* ids, con
     if (old_tiles < 0 || pend_n <= 0 || ws < 1 || ws > BIN_MAX_WS || (ws != 1 && ws % 2 != 0) || nlist <= 0 || new_tiles <= 0 ||
         new_tiles >= (1ll << 26) || old_tiles > new_tiles)
         return HARNESS_BAD_ARGS;
-    const hipError_t e = binary_ivf_rebuild_launch(codes, ids, meta, old_tiles, pend, pend_n, dest, id0, ws, nlist, nmeta, new_tiles, nx,
-                                                   nids, nullptr);
+    const hipError_t e = ivf_rebuild_launch(BIN_IVF_TILE, sizeof(u64), (size_t)ws * sizeof(u64), {(void*)codes, nullptr, (uint32_t*)ids},
+                                            meta, old_tiles, {(void*)pend, nullptr, nullptr}, pend_n, dest, id0, nlist, nmeta, new_tiles,
+                                            {nx, nullptr, nids}, nullptr);
     return e != hipSuccess ? (int)e : (int)hipGetLastError();
 }

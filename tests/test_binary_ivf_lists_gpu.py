@@ -1,10 +1,10 @@
 """GPU tests of IndexBinaryIVF's pass and rebuild, called directly and across chunks (csrc/ise_binary_ivf.hpp:
-binary_ivf_scan_kernel, binary_ivf_move_tiles_kernel, binary_ivf_scatter_rows_kernel; csrc/ise_binary_ivf.hip:
-search_enqueue).  tests/test_binary_ivf_gpu.py reaches the kernels through the Python class only: at most 50 queries (one
+binary_ivf_scan_kernel; csrc/ise_ivf_tiles.hpp: ivf_move_tiles_kernel<64, u64>, ivf_scatter_rows_kernel<u64>;
+csrc/ise_binary_ivf.hip: search_enqueue).  tests/test_binary_ivf_gpu.py reaches the kernels through the Python class only: at most 50 queries (one
 chunk of 64), rows of at most 1024 bits, at most two work-list entries per wave below 2^19 rows, ids that are small.
 
 Tests a to e call the kernels through tests/native/binary_ivf_harness.hip, whose launches are the product's own
-(binary_ivf_scan_launch, pass_merge_launch<int>, binary_ivf_rebuild_launch), on crafted work lists, floors and tables,
+(binary_ivf_scan_launch, pass_merge_launch<int>, ivf_rebuild_launch), on crafted work lists, floors and tables,
 and compare every word they write with tests/binary_ivf_ref.py: each block's lists place for place (block b takes the
 entries e with (e // 4) % grid == b), then D, I and the floors.  No input can fault a kernel that is wrong: every tile
 number in the work buffer -- behind ``count`` too -- names a tile that exists, ids and codes cover whole tiles, and the
@@ -396,7 +396,7 @@ def edge_sizes(nlist: int) -> np.ndarray:
 
 
 def rebuild(lib, old_sizes, old_codes, old_ids, pend_lists, pend_codes, id0, ws):
-    """-> (codes uint8 [slots][ws * 8], ids uint32 [slots]) of the new arrays as binary_ivf_rebuild_launch leaves them.
+    """-> (codes uint8 [slots][ws * 8], ids uint32 [slots]) of the new arrays as ivf_rebuild_launch leaves them.
     The slot numbers come from the reference's plan; the new arrays hold SENT words on entry."""
     nlist, cs = len(old_sizes), ws * 8
     old_tiles = ref.tiles_of(old_sizes)

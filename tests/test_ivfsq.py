@@ -250,6 +250,41 @@ def test_rebuilt_reference():
     assert np.array_equal(dflt[2][dflt[3] != ivfsq_ref.PAD_ID], (codes[:9].astype(np.float64) ** 2).sum(1)[dflt[3][dflt[3] != ivfsq_ref.PAD_ID]])
 
 
+def test_rebuilt_reference_with_16_row_tiles():
+    """The layout functions at ``tile_rows = 16``, the float32 lists' tiles: every list starts on a 16-row tile, holds its
+    rows in id order and pad slots to the end of its last tile; the tables are ``ivf_plan_meta``'s; two steps are one."""
+    rng = np.random.default_rng(16)
+    nlist, stride, n = 9, 48, 400
+    lists = rng.integers(0, nlist, n)
+    lists[lists == 4] = 5                # list 4 stays empty
+    lists[:32] = 2                       # list 2 holds at least two tiles
+    codes = rng.integers(0, 256, (n, stride)).astype(np.uint8)
+    none = (np.zeros(nlist, np.int64), np.zeros(0, np.uint32), np.zeros((0, stride), np.uint8))
+    one = ivfsq_ref.rebuilt(*none, lists, codes, 0, stride, tile_rows=16)
+    half = ivfsq_ref.rebuilt(*none, lists[:150], codes[:150], 0, stride, tile_rows=16)
+    two = ivfsq_ref.rebuilt(half[0], half[3], half[1], lists[150:], codes[150:], 150, stride, half[2], tile_rows=16)
+    for a, b in zip(one, two):
+        assert a.dtype == b.dtype and np.array_equal(a, b)
+    sizes, new_codes, _, ids = one
+    t0 = ivfsq_ref.tile0_of(sizes, 16)
+    assert t0[-1] == ivfsq_ref.tiles_of(sizes, 16) == ivf_ref.tiles_of(sizes) > ivfsq_ref.tiles_of(sizes)
+    assert np.diff(t0).tolist() == [-(-int(s) // 16) for s in sizes] and len(ids) == 16 * t0[-1] and sizes[4] == 0
+    for l, want in enumerate(ivf_ref.list_members(lists, nlist)):
+        a, m = 16 * t0[l], len(want)
+        assert np.array_equal(ids[a:a + m], want) and np.array_equal(new_codes[a:a + m], codes[want])
+        pad = slice(a + m, 16 * t0[l + 1])
+        assert (ids[pad] == ivfsq_ref.PAD_ID).all() and not new_codes[pad].any()
+    meta = ivfsq_ref.meta_of(sizes, 16)
+    assert meta.dtype == np.uint32 and len(meta) == 2 * nlist + 1 + t0[-1]
+    assert meta[:nlist + 1].tolist() == t0.tolist() and meta[nlist + 1:2 * nlist + 1].tolist() == sizes.tolist()
+    assert meta[2 * nlist + 1:].tolist() == [l for l in range(nlist) for _ in range(t0[l], t0[l + 1])]
+    dest = ivfsq_ref.rebuild_dest(half[0], lists[150:], 16)
+    assert np.array_equal(ids[dest], 150 + np.arange(n - 150)) and len(set(dest.tolist())) == n - 150
+    # ids near the top of the range keep their bits
+    top = ivfsq_ref.rebuilt(*none, lists[:5], codes[:5], 2 ** 32 - 6, stride, tile_rows=16)
+    assert sorted(top[3][top[3] != ivfsq_ref.PAD_ID].tolist()) == list(range(2 ** 32 - 6, 2 ** 32 - 1))
+
+
 def test_early_raises():
     """by_residual = True (the default) and the unprovided quantiser types raise before anything else is looked at."""
     with pytest.raises(NotImplementedError, match="by_residual"):

@@ -1,11 +1,11 @@
-"""GPU tests of IndexIVFScalarQuantizer's work list and rebuild at many lists (csrc/ise_ivf_lists.hpp: ivf_mask_kernel;
-csrc/ise_ivfsq.hpp: ivfsq_offsets_kernel, ivfsq_work_kernel, ivfsq_move_tiles_kernel, ivfsq_scatter_rows_kernel).
+"""GPU tests of IndexIVFScalarQuantizer's work list and rebuild at many lists (csrc/ise_ivf_tiles.hpp: ivf_mask_kernel,
+ivf_offsets_kernel, ivf_work_kernel, ivf_move_tiles_kernel<64, u32x4>, ivf_scatter_rows_kernel<u32x4>).
 tests/test_ivfsq_gpu.py builds at most 8 lists: every thread of the offsets kernel owns one list or none, the work
 kernel writes a handful of entries and the rebuild maps a handful of tiles.  Here the lists are in the hundreds and
 thousands.
 
 The first two tests call the kernels directly through tests/native/ivfsq_lists_harness.hip, whose launches are the
-product's own (ivfsq_work_list_launch, ivfsq_rebuild_launch), and compare every table they write with
+product's own (ivf_work_list_launch, ivf_rebuild_launch), and compare every table they write with
 tests/ivfsq_ref.py; the others go through the index.  The device tables are plain integers and the data is the integer
 construction of tests/sq_ref.py: every comparison is bit for bit.  The work buffer is never cleared between searches,
 so no test repeats a probe table in consecutive calls.
@@ -37,6 +37,7 @@ _vp, _int, _ll, _u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.
 PROTOTYPES = {
     "chk_ivfsq_work_list": [_vp, _int, _int, _int, _int, _vp, _ll, _vp, _vp, _vp, _vp],
     "chk_ivfsq_rebuild": [_vp, _vp, _vp, _vp, _ll, _vp, _vp, _ll, _vp, _u32, _int, _int, _vp, _ll, _vp, _vp, _vp],
+    "chk_ivf_rebuild": [_int, _int, _ll, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _u32, _int, _vp, _ll, _vp, _vp],  # tests/test_ivf_rebuild_gpu.py
 }
 
 
@@ -107,7 +108,7 @@ def work_list(lib, probes, sizes, qshift):
 
 
 def span_of(nlist: int, t: int):
-    """the lists [l0, l1) thread t of ivfsq_offsets_kernel owns"""
+    """the lists [l0, l1) thread t of ivf_offsets_kernel owns"""
     per = -(-nlist // 256)
     l0 = min(nlist, t * per)
     return l0, min(nlist, l0 + per)
@@ -150,7 +151,7 @@ def test_work_list_kernels(lib, nlist, qshift, groups):
     nq = groups * qt - 3  # not a multiple of QT
     sizes = edge_sizes(nlist)
     tiles = ivfsq_ref.tiles_of(sizes)
-    assert nlist < 257 or tiles > 256  # more than one block of ivfsq_work_kernel in x
+    assert nlist < 257 or tiles > 256  # more than one block of ivf_work_kernel in x
     rng = np.random.default_rng([nlist, qshift, groups])
     failures = []
     for name, probes in probe_tables(rng, nq, nlist, sizes):
@@ -185,7 +186,7 @@ def test_work_list_kernels(lib, nlist, qshift, groups):
 
 # ---------------------------------------------------------------- b. the rebuild kernels, direct
 def rebuild(lib, old_sizes, old, pend_lists, pend_codes, pend_rterm, id0, stride):
-    """-> (codes, rterm, ids) of the new arrays as ivfsq_rebuild_launch leaves them; old = (codes, rterm, ids) laid out
+    """-> (codes, rterm, ids) of the new arrays as ivf_rebuild_launch leaves them; old = (codes, rterm, ids) laid out
     by old_sizes.  The slot numbers come from the reference's plan; the new arrays hold SENT words on entry."""
     nlist = len(old_sizes)
     old_codes, old_rterm, old_ids = old
