@@ -182,6 +182,21 @@ PROTOTYPES = [
     ("ise_ivfsq_search_host", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp]),
     ("ise_ivfsq_search_device", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp]),
     ("ise_ivfsq_stats", _int, [_vp, _u64p]),
+    ("ise_ivfpq_create", _int, [ctypes.POINTER(_vp), _int, _int, _int, _int, _int, _int]),
+    ("ise_ivfpq_destroy", _int, [_vp]),
+    ("ise_ivfpq_reset", _int, [_vp]),
+    ("ise_ivfpq_info", _int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                              ctypes.POINTER(_int), _i64p, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    ("ise_ivfpq_set_centroids_host", _int, [_vp, _vp]),
+    ("ise_ivfpq_get_centroids_host", _int, [_vp, _vp]),
+    ("ise_ivfpq_add_host", _int, [_vp, _vp, _vp, _i64]),
+    ("ise_ivfpq_add_device", _int, [_vp, _vp, _vp, _i64, _vp]),
+    ("ise_ivfpq_add_codes_host", _int, [_vp, _vp, _vp, _i64]),
+    ("ise_ivfpq_list_sizes_host", _int, [_vp, _vp]),
+    ("ise_ivfpq_list_host", _int, [_vp, _int, _vp, _vp]),
+    ("ise_ivfpq_search_host", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp]),
+    ("ise_ivfpq_search_device", _int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp]),
+    ("ise_ivfpq_stats", _int, [_vp, _u64p]),
     ("ise_binary_ivf_create", _int, [ctypes.POINTER(_vp), _int, _int, _int]),
     ("ise_binary_ivf_destroy", _int, [_vp]),
     ("ise_binary_ivf_reset", _int, [_vp]),

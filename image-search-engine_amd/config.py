@@ -50,7 +50,7 @@ class Config:
 
     # ---- which pipeline, which index
     METHOD = Method.DNN
-    INDEX_TYPE = "l2"                       # "cosine" | "l2" | "cell-probe-flat" (IndexIVFFlat) | "pq" (IndexPQ) | "pq-refine" (IndexRefineFlat over it) | "sq8" (IndexScalarQuantizer, QT_8bit) | "cell-probe-sq8" (IndexIVFScalarQuantizer over it) | "pca256-l2" (IndexPreTransform: PCAMatrix to 256 dimensions, then IndexFlatL2) | "opq-pq" (IndexPreTransform: OPQMatrix, then IndexPQ)  ("cell-probe", IndexIVFPQ, is not composed yet)
+    INDEX_TYPE = "l2"                       # "cosine" | "l2" | "cell-probe-flat" (IndexIVFFlat) | "pq" (IndexPQ) | "pq-refine" (IndexRefineFlat over it) | "sq8" (IndexScalarQuantizer, QT_8bit) | "cell-probe-sq8" (IndexIVFScalarQuantizer over it) | "pca256-l2" (IndexPreTransform: PCAMatrix to 256 dimensions, then IndexFlatL2) | "opq-pq" (IndexPreTransform: OPQMatrix, then IndexPQ) | "cell-probe-pq" (IndexIVFPQ, by_residual=False)  ("cell-probe" itself, IndexIVFPQ over residual codes, is not provided)
 
     # ---- DNN path
     DNN_MODEL = DnnModels.RESNET

@@ -1,5 +1,5 @@
 // ise_cand.hpp -- the candidate buffers of a coded scan's k-pass: what the product-quantised and scalar-quantised scans
-// (ise_pq.hpp, ise_sq.hpp and through it ise_ivfsq.hpp) share once a tile's keys exist.  DESIGN.md 4.10 describes the
+// (ise_pq.hpp and ise_sq.hpp, and through them ise_ivfpq.hpp and ise_ivfsq.hpp) share once a tile's keys exist.  DESIGN.md 4.10 describes the
 // scheme.  The binary scan (ise_binary_scan.hpp), where it began, keeps its own body with counts in LDS: measured, this
 // one was slower there on one masked row (profiles/cands).
 //

@@ -1,5 +1,5 @@
-// ise_ivf_lists.hpp -- the host side that the three inverted-list kinds share (float32 rows, ise_ivf.hip; 8-bit rows,
-// ise_ivfsq.hip; bit codes, ise_binary_ivf.hip; the kernels are ise_ivf_tiles.hpp's): the ids and the
+// ise_ivf_lists.hpp -- the host side that the four inverted-list kinds share (float32 rows, ise_ivf.hip; 8-bit rows,
+// ise_ivfsq.hip; product-quantiser codes, ise_ivfpq.hip; bit codes, ise_binary_ivf.hip; the kernels are ise_ivf_tiles.hpp's): the ids and the
 // table of the sorted array beside the host's counts (IvfLists over ise_ivf_plan.hpp), the common part of a handle
 // (IvfCore: the sorted rows and their pending buffer as bytes, the call order, the counters, the stream and the mutex)
 // with its setup, teardown, reset, stats and rebuild, the search shell of the kinds that scan 64-row tiles from a work

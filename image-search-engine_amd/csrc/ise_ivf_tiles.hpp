@@ -1,6 +1,7 @@
 // ise_ivf_tiles.hpp -- the kernels of the inverted lists that read nothing of a row's meaning, and their launches: the
-// probe table's masks, the work list of the kinds that scan 64-row tiles, and the rebuild of all three kinds (float32
-// rows, ise_ivf.hip; 8-bit rows, ise_ivfsq.hip; bit codes, ise_binary_ivf.hip).  A row is `row units`
+// probe table's masks, the work list of the kinds that scan 64-row tiles, and the rebuild of all four kinds (float32
+// rows, ise_ivf.hip; 8-bit rows, ise_ivfsq.hip; product-quantiser codes, ise_ivfpq.hip; bit codes, ise_binary_ivf.hip;
+// DESIGN.md 4.12a).  A row is `row units`
 // copy units of 16 or 8 bytes, a slot may carry an 8-byte side value (the 8-bit rows' row term) and carries a uint32
 // id; list l owns the tiles [list_tile0[l], list_tile0[l + 1]) of ivf_plan_meta's table (ise_ivf_plan.hpp).  The host
 // side is ise_ivf_lists.hpp; the launches have a second user, the test harnesses (tests/native/*_harness.hip), which

@@ -9,16 +9,13 @@
 // rule (grow_drained, ise_host.hpp).
 #include <cmath>
 
-#include "ise_pass_host.hpp"
-#include "ise_pq.hpp"
+#include "ise_pq_host.hpp"
 
 struct ise_pq {
-    int d = 0, M = 0, dsub = 0, stride = 0, qt = 0, metric = ISE_METRIC_L2, device = 0, num_cu = 256;
-    bool trained = false;
+    int metric = ISE_METRIC_L2, device = 0, num_cu = 256;
+    PqCodec codec;  // d, M, dsub, stride, qt, the codebook and the encoders' flag
     long long n = 0, cap = 0;
     uint8_t* codes = nullptr;  // [cap][stride]; bytes [M, stride) of every row are zero
-    float* cb = nullptr;       // [M][256][dsub]
-    BadFlag bad;               // set by an encode that met a NaN or inf entry
     hipStream_t stream = nullptr;
     CallOrder order;
     mutable std::mutex mu;
@@ -31,55 +28,22 @@ struct ise_pq {
 
 namespace {
 int check_handle(const ise_pq* h) { return h ? ISE_OK : ise_fail_(ISE_E_INVALID, "product-quantiser index handle is NULL"); }
-int check_trained(const ise_pq* h) {
-    return h->trained ? ISE_OK : ise_fail_(ISE_E_INVALID, "the index is not trained: set the centroids first");
-}
+int check_trained(const ise_pq* h) { return h->codec.check_trained(); }
 
-void launch_scan(int qt, unsigned grid, size_t lds, hipStream_t st, const PqScanParams& sp) {
-    static LdsAttrOnce attr[4];
-    auto go = [&](auto kern, LdsAttrOnce& a) {
-        a.ensure(reinterpret_cast<const void*>(kern), PQ_LDS_LIMIT);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(PQ_WAVES * 64), lds, st, sp);
-    };
-    if (qt == 16) go(pq_scan_kernel<16>, attr[0]);
-    else if (qt == 8) go(pq_scan_kernel<8>, attr[1]);
-    else if (qt == 4) go(pq_scan_kernel<4>, attr[2]);
-    else go(pq_scan_kernel<2>, attr[3]);
-}
+PqScanLaunch<PqScanParams> launch_scan{{pq_scan_kernel<16>, pq_scan_kernel<8>, pq_scan_kernel<4>, pq_scan_kernel<2>}, {}};
 
 // blocks of a pass: about two tiles per wave on a short index, at most what the CUs hold at once (their LDS)
 unsigned pq_grid(const ise_pq* h) {
-    const long long per_cu = std::max<long long>(1, (long long)PQ_LDS_LIMIT / (long long)pq_lds_bytes(h->M, h->qt));
-    return coded_grid((h->n + 63) / 64, 2, PQ_WAVES, per_cu, h->num_cu);
+    return coded_grid((h->n + 63) / 64, 2, PQ_WAVES, h->codec.blocks_per_cu(), h->num_cu);
 }
 
 int reserve_rows(ise_pq* h, long long need, hipStream_t st) {
-    return reserve_code_rows(&h->codes, (size_t)h->stride, h->n, &h->cap, need, 64, st);
-}
-
-// byte m of rows [0, n) of dst (row stride `stride`) <- the code of x's rows; sets the bad flag on a non-finite entry
-void encode_launch(ise_pq* h, const float* x_dev, long long n, uint8_t* dst, int stride, hipStream_t st) {
-    static LdsAttrOnce attr;
-    const dim3 grid((unsigned)((n + PQ_ENC_ROWS - 1) / PQ_ENC_ROWS), (unsigned)h->M);
-    if (h->dsub <= PQ_ENC_LDS_DSUB) {
-        attr.ensure(reinterpret_cast<const void*>(pq_encode_kernel<true>), PQ_ENC_LDS_DSUB * PQ_KSUB * 4);
-        hipLaunchKernelGGL(pq_encode_kernel<true>, grid, dim3(PQ_WAVES * 64), (size_t)h->dsub * PQ_KSUB * 4, st, x_dev, n, h->d,
-                           h->M, (const float*)h->cb, dst, stride, h->bad.p);
-    } else {
-        hipLaunchKernelGGL(pq_encode_kernel<false>, grid, dim3(PQ_WAVES * 64), 0, st, x_dev, n, h->d, h->M,
-                           (const float*)h->cb, dst, stride, h->bad.p);
-    }
+    return reserve_code_rows(&h->codes, (size_t)h->codec.stride, h->n, &h->cap, need, 64, st);
 }
 
 int check_rows_fit(const ise_pq* h, long long n) {
     if (h->n + n >= (1ll << 32)) return ise_fail_(ISE_E_INVALID, "a product-quantiser index holds fewer than 2^32 rows");
     return ISE_OK;
-}
-
-void decode_launch(const ise_pq* h, const uint8_t* codes, int stride, long long n, float* x_dev, hipStream_t st) {
-    const long long tot = n * h->d;
-    hipLaunchKernelGGL(pq_decode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, codes, stride, n, h->d, h->M,
-                       (const float*)h->cb, x_dev);
 }
 
 // q_dev: nq x d floats on the device; D_dev / I_dev: nq x k.  mu held, the index trained
@@ -93,19 +57,18 @@ int search_enqueue(ise_pq* h, const float* q_dev, long long nq, int k, float* D_
         HIP_TRY(hipGetLastError());
         return h->order.mark(st);
     }
-    const int qt = h->qt;
+    const int qt = h->codec.qt;
     const unsigned grid = pq_grid(h);
-    const size_t tab_q = (size_t)h->M * PQ_KSUB;  // floats of one query's tables
+    const size_t tab_q = h->codec.tab_floats();  // floats of one query's tables
     if ((rc = grow_drained(h->tab, (size_t)std::min<long long>((nq + qt - 1) / qt * qt, PQ_TAB_CHUNK) * tab_q))) return rc;
     if ((rc = grow_drained(h->lo, (size_t)PQ_TAB_CHUNK))) return rc;
     if ((rc = grow_drained(h->lists, (size_t)grid * qt * PQ_KPASS))) return rc;
     h->st_search++;  // counted once the batch is certain to be enqueued
-    const size_t lds = pq_lds_bytes(h->M, qt);
+    const size_t lds = h->codec.lds_bytes();
     for (long long c0 = 0; c0 < nq; c0 += PQ_TAB_CHUNK) {
         const int mc = (int)std::min<long long>(PQ_TAB_CHUNK, nq - c0);
         const int groups = (mc + qt - 1) / qt;
-        hipLaunchKernelGGL(pq_table_kernel, dim3((unsigned)h->M, (unsigned)groups), dim3(PQ_KSUB), 0, st,
-                           q_dev + (size_t)c0 * h->d, mc, h->d, h->M, qt, ip, (const float*)h->cb, h->tab.p);
+        h->codec.table_launch(q_dev + (size_t)c0 * h->codec.d, mc, ip, h->tab.p, st);
         h->st_tables++;
         for (int g = 0; g < groups; g++) {
             const long long q0 = c0 + (long long)g * qt;
@@ -114,8 +77,8 @@ int search_enqueue(ise_pq* h, const float* q_dev, long long nq, int k, float* D_
                 const int kp = std::min(PQ_KPASS, k - off);
                 PqScanParams sp{};
                 sp.codes = h->codes;
-                sp.M = h->M;
-                sp.stride = h->stride;
+                sp.M = h->codec.M;
+                sp.stride = h->codec.stride;
                 sp.n = h->n;
                 sp.tab = h->tab.p + (size_t)g * qt * tab_q;
                 sp.nqt = nqt;
@@ -146,19 +109,20 @@ int add_device_locked(ise_pq* h, const float* x_dev, long long n, hipStream_t st
     if (rc) return rc;
     if ((rc = h->order.wait(st))) return rc;
     if ((rc = reserve_rows(h, h->n + n, st))) return rc;
-    if ((rc = h->bad.clear(st))) return rc;
-    encode_launch(h, x_dev, n, h->codes + (size_t)h->n * h->stride, h->stride, st);
+    if ((rc = h->codec.bad.clear(st))) return rc;
+    h->codec.encode_launch(x_dev, n, h->codes + (size_t)h->n * h->codec.stride, h->codec.stride, st);
     HIP_TRY(hipGetLastError());
     if ((rc = h->order.mark(st))) return rc;
-    if ((rc = h->bad.check(st))) return rc;
+    if ((rc = h->codec.bad.check(st))) return rc;
     h->n += n;
     return ISE_OK;
 }
 
 void free_buffers(ise_pq* h) {
     for (void* p : {(void*)h->xraw.p, (void*)h->tab.p, (void*)h->oD.p, (void*)h->craw.p, (void*)h->lo.p, (void*)h->lists.p,
-                    (void*)h->oI.p, (void*)h->codes, (void*)h->cb, (void*)h->bad.p})
+                    (void*)h->oI.p, (void*)h->codes})
         if (p) (void)hipFree(p);
+    h->codec.destroy();
 }
 }  // namespace
 
@@ -177,11 +141,6 @@ extern "C" int ise_pq_create(ise_pq_t** out, int d, int M, int nbits, int metric
     if (rc) return rc;
     ise_pq* h = new (std::nothrow) ise_pq();
     if (!h) return ise_fail_(ISE_E_NOMEM, "host allocation failed");
-    h->d = d;
-    h->M = M;
-    h->dsub = d / M;
-    h->stride = (M + 15) / 16 * 16;
-    h->qt = pq_qt(M);
     h->metric = metric;
     h->device = device;
     h->num_cu = num_cu;
@@ -189,8 +148,7 @@ extern "C" int ise_pq_create(ise_pq_t** out, int d, int M, int nbits, int metric
     hipError_t e = gd.ok ? hipSuccess : hipErrorInvalidDevice;
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = h->order.create();
-    if (e == hipSuccess) e = hipMalloc((void**)&h->cb, (size_t)M * PQ_KSUB * h->dsub * sizeof(float));
-    if (e == hipSuccess) e = h->bad.create();
+    if (e == hipSuccess) e = h->codec.create(d, M);
     if (e != hipSuccess) {
         free_buffers(h);
         h->order.destroy();
@@ -226,12 +184,12 @@ extern "C" int ise_pq_info(const ise_pq_t* h, int* d, int* M, int* nbits, int* m
                            int* device) {
     if (check_handle(h)) return ISE_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (d) *d = h->d;
-    if (M) *M = h->M;
+    if (d) *d = h->codec.d;
+    if (M) *M = h->codec.M;
     if (nbits) *nbits = 8;
     if (metric) *metric = h->metric;
     if (ntotal) *ntotal = h->n;
-    if (is_trained) *is_trained = h->trained ? 1 : 0;
+    if (is_trained) *is_trained = h->codec.trained ? 1 : 0;
     if (device) *device = h->device;
     return ISE_OK;
 }
@@ -241,26 +199,14 @@ extern "C" int ise_pq_set_centroids_host(ise_pq_t* h, const float* c) {
     if (check_handle(h)) return ISE_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->n > 0) return ise_fail_(ISE_E_INVALID, "the index holds rows: their codes belong to the centroids in place (reset first)");
-    const size_t cnt = (size_t)h->M * PQ_KSUB * h->dsub;
-    for (size_t i = 0; i < cnt; i++)
-        if (!(std::fabs(c[i]) <= FLT_MAX)) return ise_fail_(ISE_E_INVALID, "a centroid has a NaN or inf entry");
-    DeviceGuard gd(h->device);
-    if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
-    HIP_TRY(hipDeviceSynchronize());  // an encode or a table build in flight still reads the old centroids
-    HIP_TRY(hipMemcpy(h->cb, c, cnt * sizeof(float), hipMemcpyHostToDevice));
-    h->trained = true;
-    return ISE_OK;
+    return h->codec.set_centroids(c, h->device);
 }
 
 extern "C" int ise_pq_get_centroids_host(ise_pq_t* h, float* c) {
     if (!c) return ise_fail_(ISE_E_INVALID, "centroid pointer is NULL");
     if (check_handle(h)) return ISE_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (check_trained(h)) return ISE_E_INVALID;
-    DeviceGuard gd(h->device);
-    if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
-    HIP_TRY(hipMemcpy(c, h->cb, (size_t)h->M * PQ_KSUB * h->dsub * sizeof(float), hipMemcpyDeviceToHost));
-    return ISE_OK;
+    return h->codec.get_centroids(c, h->device);
 }
 
 extern "C" int ise_pq_encode_device(ise_pq_t* h, const float* x_dev, int64_t n, uint8_t* codes_dev, void* stream) {
@@ -275,11 +221,11 @@ extern "C" int ise_pq_encode_device(ise_pq_t* h, const float* x_dev, int64_t n, 
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     int rc = h->order.wait(st);
     if (rc) return rc;
-    if ((rc = h->bad.clear(st))) return rc;
-    encode_launch(h, x_dev, n, codes_dev, h->M, st);
+    if ((rc = h->codec.bad.clear(st))) return rc;
+    h->codec.encode_launch(x_dev, n, codes_dev, h->codec.M, st);
     HIP_TRY(hipGetLastError());
     if ((rc = h->order.mark(st))) return rc;
-    return h->bad.check(st);
+    return h->codec.bad.check(st);
 }
 
 extern "C" int ise_pq_encode_host(ise_pq_t* h, const float* x, int64_t n, uint8_t* codes) {
@@ -292,20 +238,20 @@ extern "C" int ise_pq_encode_host(ise_pq_t* h, const float* x, int64_t n, uint8_
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     hipStream_t st = h->stream;
-    const long long step = upload_step((size_t)h->d * sizeof(float));
+    const long long step = upload_step((size_t)h->codec.d * sizeof(float));
     int rc = h->order.wait(st);
     if (rc) return rc;
     for (long long i0 = 0; i0 < n; i0 += step) {
         const long long m = std::min<long long>(step, n - i0);
-        if ((rc = grow_drained(h->xraw, (size_t)m * h->d))) return rc;
-        if ((rc = grow_drained(h->craw, (size_t)m * h->M))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->xraw.p, x + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice, st));
-        if ((rc = h->bad.clear(st))) return rc;
-        encode_launch(h, h->xraw.p, m, h->craw.p, h->M, st);
+        if ((rc = grow_drained(h->xraw, (size_t)m * h->codec.d))) return rc;
+        if ((rc = grow_drained(h->craw, (size_t)m * h->codec.M))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->xraw.p, x + (size_t)i0 * h->codec.d, (size_t)m * h->codec.d * sizeof(float), hipMemcpyHostToDevice, st));
+        if ((rc = h->codec.bad.clear(st))) return rc;
+        h->codec.encode_launch(h->xraw.p, m, h->craw.p, h->codec.M, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(codes + (size_t)i0 * h->M, h->craw.p, (size_t)m * h->M, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(codes + (size_t)i0 * h->codec.M, h->craw.p, (size_t)m * h->codec.M, hipMemcpyDeviceToHost, st));
         if ((rc = h->order.mark(st))) return rc;
-        if ((rc = h->bad.check(st))) return rc;
+        if ((rc = h->codec.bad.check(st))) return rc;
     }
     return ISE_OK;
 }
@@ -320,17 +266,17 @@ extern "C" int ise_pq_decode_host(ise_pq_t* h, const uint8_t* codes, int64_t n, 
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     hipStream_t st = h->stream;
-    const long long step = upload_step((size_t)h->d * sizeof(float));
+    const long long step = upload_step((size_t)h->codec.d * sizeof(float));
     int rc = h->order.wait(st);
     if (rc) return rc;
     for (long long i0 = 0; i0 < n; i0 += step) {
         const long long m = std::min<long long>(step, n - i0);
-        if ((rc = grow_drained(h->xraw, (size_t)m * h->d))) return rc;
-        if ((rc = grow_drained(h->craw, (size_t)m * h->M))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->craw.p, codes + (size_t)i0 * h->M, (size_t)m * h->M, hipMemcpyHostToDevice, st));
-        decode_launch(h, h->craw.p, h->M, m, h->xraw.p, st);
+        if ((rc = grow_drained(h->xraw, (size_t)m * h->codec.d))) return rc;
+        if ((rc = grow_drained(h->craw, (size_t)m * h->codec.M))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->craw.p, codes + (size_t)i0 * h->codec.M, (size_t)m * h->codec.M, hipMemcpyHostToDevice, st));
+        h->codec.decode_launch(h->craw.p, h->codec.M, m, h->xraw.p, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(x + (size_t)i0 * h->d, h->xraw.p, (size_t)m * h->d * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(x + (size_t)i0 * h->codec.d, h->xraw.p, (size_t)m * h->codec.d * sizeof(float), hipMemcpyDeviceToHost, st));
         if ((rc = h->order.mark(st))) return rc;
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -366,14 +312,14 @@ extern "C" int ise_pq_add_host(ise_pq_t* h, const float* x, int64_t n) {
             if (!keep) h->n = n0;
         }
     } undo{h, h->n};
-    const long long step = upload_step((size_t)h->d * sizeof(float));
+    const long long step = upload_step((size_t)h->codec.d * sizeof(float));
     int rc = check_rows_fit(h, n);
     if (rc) return rc;
     if ((rc = reserve_rows(h, h->n + n, h->stream))) return rc;
     for (long long i0 = 0; i0 < n; i0 += step) {
         const long long m = std::min<long long>(step, n - i0);
-        if ((rc = grow_drained(h->xraw, (size_t)m * h->d))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->xraw.p, x + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice,
+        if ((rc = grow_drained(h->xraw, (size_t)m * h->codec.d))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->xraw.p, x + (size_t)i0 * h->codec.d, (size_t)m * h->codec.d * sizeof(float), hipMemcpyHostToDevice,
                                h->stream));
         if ((rc = add_device_locked(h, h->xraw.p, m, h->stream))) return rc;
     }
@@ -396,7 +342,7 @@ extern "C" int ise_pq_add_codes_host(ise_pq_t* h, const uint8_t* codes, int64_t 
     if ((rc = h->order.wait(st))) return rc;
     if ((rc = reserve_rows(h, h->n + n, st))) return rc;
     // the pad bytes of the fresh rows are zero already (reserve_code_rows); only bytes below M are ever written
-    HIP_TRY(hipMemcpy2DAsync(h->codes + (size_t)h->n * h->stride, (size_t)h->stride, codes, (size_t)h->M, (size_t)h->M, (size_t)n,
+    HIP_TRY(hipMemcpy2DAsync(h->codes + (size_t)h->n * h->codec.stride, (size_t)h->codec.stride, codes, (size_t)h->codec.M, (size_t)h->codec.M, (size_t)n,
                              hipMemcpyHostToDevice, st));
     if ((rc = h->order.mark(st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
@@ -415,7 +361,7 @@ extern "C" int ise_pq_codes_host(ise_pq_t* h, int64_t i0, int64_t n, uint8_t* co
     hipStream_t st = h->stream;
     int rc = h->order.wait(st);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy2DAsync(codes, (size_t)h->M, h->codes + (size_t)i0 * h->stride, (size_t)h->stride, (size_t)h->M, (size_t)n,
+    HIP_TRY(hipMemcpy2DAsync(codes, (size_t)h->codec.M, h->codes + (size_t)i0 * h->codec.stride, (size_t)h->codec.stride, (size_t)h->codec.M, (size_t)n,
                              hipMemcpyDeviceToHost, st));
     if ((rc = h->order.mark(st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
@@ -431,15 +377,15 @@ extern "C" int ise_pq_reconstruct_host(ise_pq_t* h, int64_t i0, int64_t n, float
     DeviceGuard gd(h->device);
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     hipStream_t st = h->stream;
-    const long long step = upload_step((size_t)h->d * sizeof(float));
+    const long long step = upload_step((size_t)h->codec.d * sizeof(float));
     int rc = h->order.wait(st);
     if (rc) return rc;
     for (long long j0 = 0; j0 < n; j0 += step) {
         const long long m = std::min<long long>(step, n - j0);
-        if ((rc = grow_drained(h->xraw, (size_t)m * h->d))) return rc;
-        decode_launch(h, h->codes + (size_t)(i0 + j0) * h->stride, h->stride, m, h->xraw.p, st);
+        if ((rc = grow_drained(h->xraw, (size_t)m * h->codec.d))) return rc;
+        h->codec.decode_launch(h->codes + (size_t)(i0 + j0) * h->codec.stride, h->codec.stride, m, h->xraw.p, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(x + (size_t)j0 * h->d, h->xraw.p, (size_t)m * h->d * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(x + (size_t)j0 * h->codec.d, h->xraw.p, (size_t)m * h->codec.d * sizeof(float), hipMemcpyDeviceToHost, st));
         if ((rc = h->order.mark(st))) return rc;
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -468,13 +414,13 @@ extern "C" int ise_pq_search_host(ise_pq_t* h, const float* q, int64_t nq, int k
     if (!gd.ok) return ise_fail_(ISE_E_HIP, "hipSetDevice failed");
     hipStream_t st = h->stream;
     const long long batch = std::min<long long>(nq, 4096);
-    if ((rc = grow_drained(h->xraw, (size_t)batch * h->d))) return rc;
+    if ((rc = grow_drained(h->xraw, (size_t)batch * h->codec.d))) return rc;
     if ((rc = grow_drained(h->oD, (size_t)batch * k))) return rc;
     if ((rc = grow_drained(h->oI, (size_t)batch * k))) return rc;
     for (long long i0 = 0; i0 < nq; i0 += batch) {
         const long long m = std::min<long long>(batch, nq - i0);
         if ((rc = h->order.wait(st))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->xraw.p, q + (size_t)i0 * h->d, (size_t)m * h->d * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(h->xraw.p, q + (size_t)i0 * h->codec.d, (size_t)m * h->codec.d * sizeof(float), hipMemcpyHostToDevice, st));
         if ((rc = search_enqueue(h, h->xraw.p, m, k, h->oD.p, h->oI.p, st))) return rc;
         HIP_TRY(hipMemcpyAsync(D + (size_t)i0 * k, h->oD.p, (size_t)m * k * sizeof(float), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(I + (size_t)i0 * k, h->oI.p, (size_t)m * k * sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -490,6 +436,6 @@ extern "C" int ise_pq_stats(ise_pq_t* h, uint64_t* out4) {
     out4[0] = h->st_search;
     out4[1] = h->st_passes;
     out4[2] = h->st_tables;
-    out4[3] = (uint64_t)h->cap * (uint64_t)h->stride;
+    out4[3] = (uint64_t)h->cap * (uint64_t)h->codec.stride;
     return ISE_OK;
 }

@@ -1,6 +1,6 @@
 // ise_pq.hpp -- kernels of the product-quantised index (include/ise_knn.h, ise_pq_*): faiss.IndexPQ with 8-bit
-// sub-quantisers.  DESIGN.md 4.13.  The table and scan code lives here, apart from the host side (ise_pq.hip), so that
-// an inverted-list composition can include it later.
+// sub-quantisers.  DESIGN.md 4.13.  The table and scan code lives here, apart from the host side (ise_pq.hip): the
+// inverted lists over these codes (ise_ivfpq.hpp) include it, and their pass is pq_scan_body too.
 //
 // Codec: a row of d floats is M sub-vectors of dsub = d / M; byte m of its code is the number j of the centroid
 // C[m][j] (codebook [M][256][dsub], float32) nearest to sub-vector m in squared L2, the lowest j among equals.
@@ -109,12 +109,27 @@ __device__ __forceinline__ void pq_gather(const float* __restrict__ tabs, int m,
     }
 }
 
-template <int QT>
-__global__ __launch_bounds__(PQ_WAVES * 64) void pq_scan_kernel(const PqScanParams p) {
+// The scan of one pass, for both layouts (IVF false: the flat index's rows [0, n), pq_scan_kernel; IVF true: the work
+// list of an inverted-list pass, P = PqIvfScanParams, ise_ivfpq.hpp).  What differs stands under `if constexpr (IVF)`:
+// which tile a wave's next unit names, the row mask (row < n | position < valid rows and the query's mask bit) and the
+// key's low word (row | ids[slot]).  The table copy into LDS, the gathers, the selection buffers and the block's fold
+// exist once.
+template <int QT, bool IVF, class P>
+__device__ __forceinline__ void pq_scan_body(const P& p) {
     extern __shared__ __align__(16) unsigned char smem_pq[];
     float* tabs = reinterpret_cast<float*>(smem_pq);                                 // [M][256][QT]
     u64* buf = reinterpret_cast<u64*>(smem_pq + (size_t)p.M * PQ_KSUB * QT * 4);  // [PQ_WAVES][QT][PQ_CAP]
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    [[maybe_unused]] long long nent = 0;  // IVF: entries of the group's work list
+    if constexpr (IVF) {
+        nent = (long long)__builtin_amdgcn_readfirstlane((int)*p.count);
+        if (blockIdx.x == 0 && threadIdx.x == 0 && nent) atomicAdd(p.tiles_loaded, (unsigned long long)nent);
+        if ((long long)blockIdx.x * PQ_WAVES >= nent) {  // no entry for this block: its lists are padding, no table is copied
+            for (int i = threadIdx.x; i < p.nqt * PQ_KPASS; i += PQ_WAVES * 64)
+                p.lists[(size_t)blockIdx.x * QT * PQ_KPASS + i] = KEY_PAD;
+            return;
+        }
+    }
     {  // the pass's tables, PQ_COPY_UNROLL loads in flight per thread
         const f32x4* src = reinterpret_cast<const f32x4*>(p.tab);
         f32x4* dst = reinterpret_cast<f32x4*>(tabs);
@@ -136,22 +151,14 @@ __global__ __launch_bounds__(PQ_WAVES * 64) void pq_scan_kernel(const PqScanPara
     const u64 lt_mask = (1ull << lane) - 1ull;
     const uint32_t flip = p.ip ? 0x80000000u : 0u;
 
-    const long long ntiles = (p.n + 63) >> 6;
+    long long ntiles;  // units of the pass: the index's tiles | the work list's entries
+    if constexpr (IVF) ntiles = nent;
+    else ntiles = (p.n + 63) >> 6;
     const int pieces = p.stride >> 4;
     const long long tstep = (long long)gridDim.x * PQ_WAVES;
-    // the first 16 bytes of the lane's row in tile t (a lane beyond n reads row 0 and is masked)
-    auto row_piece = [&](long long t) {
-        const long long r = t * 64 + lane;
-        return reinterpret_cast<const u32x4*>(p.codes + (r < p.n ? r : 0ll) * p.stride);
-    };
-    long long t = (long long)blockIdx.x * PQ_WAVES + w;
-    u32x4 ahead = t < ntiles ? *row_piece(t) : u32x4{0u, 0u, 0u, 0u};
-    for (; t < ntiles; t += tstep) {
-        const long long row = t * 64 + lane;
-        const bool valid = row < p.n;
-        const u32x4* rp = row_piece(t);
-        u32x4 cv = ahead;
-        if (t + tstep < ntiles) ahead = *row_piece(t + tstep);  // the next tile's load flies under this tile's gathers
+    // one tile: the lane's row starts at rp, its first piece is cv (loaded a tile ahead); the lane takes part if `valid`
+    // (IVF: and query q if bit q of qmask is set), the key's low word is `low`
+    auto scan_tile = [&](const u32x4* rp, u32x4 cv, bool valid, [[maybe_unused]] uint32_t qmask, uint32_t low) {
         float acc[QT];
 #pragma unroll
         for (int q = 0; q < QT; q++) acc[q] = 0.f;
@@ -168,8 +175,9 @@ __global__ __launch_bounds__(PQ_WAVES * 64) void pq_scan_kernel(const PqScanPara
         for (int q = 0; q < QT; q++) {
             if (q < p.nqt) {
                 const float s = __uint_as_float(__float_as_uint(acc[q]) ^ flip);
-                const u64 key = ((u64)ord_f32(s) << 32) | (uint32_t)row;
-                const bool c = valid && s < FLT_MAX && key >= readlane_u64(lo_v, q) && key < readlane_u64(cand.thr, q);
+                const u64 key = ((u64)ord_f32(s) << 32) | low;
+                bool c = valid && s < FLT_MAX && key >= readlane_u64(lo_v, q) && key < readlane_u64(cand.thr, q);
+                if constexpr (IVF) c = c && ((qmask >> q) & 1u);
                 const u64 mk = __ballot(c);
                 if (mk) {
                     const int cnt = __builtin_amdgcn_readlane(cand.cnt, q);
@@ -179,8 +187,51 @@ __global__ __launch_bounds__(PQ_WAVES * 64) void pq_scan_kernel(const PqScanPara
             }
         }
         cand.make_room();
+    };
+    long long t = (long long)blockIdx.x * PQ_WAVES + w;
+    if constexpr (IVF) {
+        // t counts ENTRIES; an entry is (tile, valid rows, query mask, 0), the lane owns slot tile * 64 + lane.  The entry
+        // two steps on, and the first piece and the id of the next entry's slot, are requested before this tile's
+        // gathers, so no code-byte request waits for the entry it has just asked for.  Behind the wave's last entry: the
+        // list's last entry again -- a valid tile, unused
+        auto entry_at = [&](long long e) { return p.work[e < nent ? e : nent - 1]; };
+        auto slot_of = [&](uint32_t tile) { return (size_t)tile * 64 + lane; };
+        auto slot_piece = [&](uint32_t tile) { return reinterpret_cast<const u32x4*>(p.codes + slot_of(tile) * p.stride); };
+        u32x4 cent = entry_at(t), cnext = entry_at(t + tstep);
+        u32x4 ahead = *slot_piece(cent[0]);
+        uint32_t aid = p.ids[slot_of(cent[0])];
+        for (; t < ntiles; t += tstep) {
+            const u32x4* rp = slot_piece(cent[0]);
+            const u32x4 cv = ahead;
+            const uint32_t id = aid;
+            const u32x4 cafter = entry_at(t + 2 * tstep);
+            ahead = *slot_piece(cnext[0]);
+            aid = p.ids[slot_of(cnext[0])];
+            scan_tile(rp, cv, lane < (int)cent[1], cent[2], id);
+            cent = cnext;
+            cnext = cafter;
+        }
+    } else {
+        // the first 16 bytes of the lane's row in tile t (a lane beyond n reads row 0 and is masked)
+        auto row_piece = [&](long long tt) {
+            const long long r = tt * 64 + lane;
+            return reinterpret_cast<const u32x4*>(p.codes + (r < p.n ? r : 0ll) * p.stride);
+        };
+        u32x4 ahead = t < ntiles ? *row_piece(t) : u32x4{0u, 0u, 0u, 0u};
+        for (; t < ntiles; t += tstep) {
+            const long long row = t * 64 + lane;
+            const u32x4* rp = row_piece(t);
+            const u32x4 cv = ahead;
+            if (t + tstep < ntiles) ahead = *row_piece(t + tstep);  // the next tile's load flies under this tile's gathers
+            scan_tile(rp, cv, row < p.n, 0u, (uint32_t)row);
+        }
     }
     cand.fold(p.nqt, p.lists + (size_t)blockIdx.x * QT * PQ_KPASS);
+}
+
+template <int QT>
+__global__ __launch_bounds__(PQ_WAVES * 64) void pq_scan_kernel(const PqScanParams p) {
+    pq_scan_body<QT, false>(p);
 }
 
 // ---- encoding (build side).  A wave owns a row at a time, block (rows, m) sub-quantiser m = blockIdx.y: lane l holds

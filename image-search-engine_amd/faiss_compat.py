@@ -42,8 +42,7 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          lookup tables over the codes (csrc/ise_pq.hpp), ``reconstruct_n``, ``sa_encode`` /
                                          ``sa_decode``, ``index.pq`` (``centroids``, ``set_centroids``, ``compute_codes``,
                                          ``decode``), ``write_index`` / ``read_index`` ("IxPq"); the compression half of
-                                         the reference's "cell-probe" index (backend/utils.py:311-325), which itself
-                                         (IndexIVFPQ) is still not provided
+                                         the reference's "cell-probe" index (backend/utils.py:311-325), IndexIVFPQ below
     IndexScalarQuantizer(d, qtype)       Faiss's scalar-quantised index with ``ScalarQuantizer.QT_8bit`` / ``QT_8bit_uniform``:
                                          rows kept as one byte per entry (a quarter of float32) between a trained
                                          per-dimension (or single) minimum and maximum; ``train`` (min / max) / ``add`` /
@@ -58,11 +57,19 @@ backend/kmeans_faiss.py:1 and backend/siamese/test_index.py:
                                          ``search_preassigned`` / ``search_torch``, ``get_list``, ``index.sq``,
                                          ``write_index`` / ``read_index`` ("IwSq"); a pass reads the 64-row tiles of the
                                          probed lists only (csrc/ise_ivfsq.hpp) and D has ``IndexScalarQuantizer``'s bits;
-                                         ``by_residual=True`` (Faiss's default) raises; the compressed cell-probe index
-                                         this package has (the reference's own, IndexIVFPQ, is still not provided)
+                                         ``by_residual=True`` (Faiss's default) raises
+    IndexIVFPQ(quantizer, d, nlist, M, nbits=8, metric, by_residual=False)
+                                         the reference's "cell-probe" index (backend/utils.py:311-325) over codes of the rows
+                                         themselves: ``IndexIVFFlat``'s lists holding ``IndexPQ``'s code rows (the same codec
+                                         for the same ``pq.centroids``); ``train`` (k-means, then the codebook) / ``add`` /
+                                         ``search`` with ``nprobe`` / ``search_preassigned`` / ``search_torch``, ``get_list``,
+                                         ``index.pq``, ``sa_encode`` / ``sa_decode``, ``write_index`` / ``read_index``
+                                         ("IwPQ"); a pass gathers from the queries' lookup tables over the 64-row tiles of
+                                         the probed lists only (csrc/ise_ivfpq.hpp) and D has ``IndexPQ``'s bits;
+                                         ``by_residual=True`` (Faiss's default, and the reference's call) raises
     IndexRefineFlat(base_index)          Faiss's exact re-ranking of an approximate index: ``search`` asks ``base_index`` (an
                                          ``IndexPQ``, an ``IndexScalarQuantizer``, an ``IndexIVFFlat``, an
-                                         ``IndexIVFScalarQuantizer`` or an ``IndexFlat`` of
+                                         ``IndexIVFScalarQuantizer``, an ``IndexIVFPQ`` or an ``IndexFlat`` of
                                          either storage) for
                                          ``k * k_factor`` labels and returns the k best of them by their exact distance to
                                          float32 rows kept beside it (csrc/ise_subset.hpp: a gather-and-score pass spread
@@ -1006,7 +1013,7 @@ class _Cursor:
     """A read position in a file image, for the ``_parse_*_at`` readers below: each reads the image that starts at the
     cursor and leaves the cursor behind it, so that an image inside another file is read where it lies.  An operation
     names the message of the RuntimeError it raises when bytes are missing; ``truncated``, where the cursor was made
-    with one, replaces them all (an image inside an "IwSq" or "IxRF" file is cut short with its file)."""
+    with one, replaces them all (an image inside an "IwSq", "IwPQ" or "IxRF" file is cut short with its file)."""
 
     _COUNT = struct.Struct("<Q")
 
@@ -1263,14 +1270,52 @@ def serialize_ivfsq(d: int, metric: int, nlist: int, nprobe: int, qmetric: int, 
     pairs = [(np.ascontiguousarray(ids, dtype="<i8").reshape(-1), np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, d))
              for ids, codes in lists]
     assert all(ids.size == codes.shape[0] for ids, codes in pairs), "one id per code row"
+    head = [_HDR.pack(_FOURCC_IVFSQ, d, sum(ids.size for ids, _ in pairs), 1 << 20, 1 << 20, 1, int(metric)),
+            _IVF_DIMS.pack(nlist, int(nprobe)),
+            serialize_flat(d, int(qmetric), np.asarray(centroids, dtype=np.float32).reshape(-1, d)), _IVF_DIRECT_MAP.pack(0, 0),
+            block, _IVF_CODE.pack(d, 1 if by_residual else 0)]
+    return b"".join(head) + _pack_ivf_lists(pairs, nlist, d)
+
+
+def _pack_ivf_lists(pairs, nlist: int, code_size: int) -> bytes:
+    """The inverted lists of "IwSq" and "IwPQ": fourcc "ilar", nlist, code_size, the sizes in the "full" form, then per
+    list that holds rows its codes and its ids.  ``pairs``: ``nlist`` pairs (ids "<i8" (m,), codes uint8 (m, code_size))."""
     sizes = np.array([ids.size for ids, _ in pairs], dtype="<u8")
-    out = [_HDR.pack(_FOURCC_IVFSQ, d, int(sizes.sum()), 1 << 20, 1 << 20, 1, int(metric)), _IVF_DIMS.pack(nlist, int(nprobe)),
-           serialize_flat(d, int(qmetric), np.asarray(centroids, dtype=np.float32).reshape(-1, d)), _IVF_DIRECT_MAP.pack(0, 0),
-           block, _IVF_CODE.pack(d, 1 if by_residual else 0), b"ilar", _IVF_DIMS.pack(nlist, d), b"full", _pack_vector(sizes)]
+    out = [b"ilar", _IVF_DIMS.pack(nlist, code_size), b"full", _pack_vector(sizes)]
     for ids, codes in pairs:
         if ids.size:
             out += [codes.tobytes(), ids.tobytes()]
     return b"".join(out)
+
+
+def _parse_ivf_lists_at(cur: _Cursor, nlist: int, code_size: int, n: int, what: str) -> list:
+    """-> [(ids int64 (m,), codes uint8 (m, code_size))] * nlist of the inverted lists at the cursor, in a file of a
+    ``what`` whose header says ``nlist`` lists, ``code_size`` bytes a row and ``n`` rows."""
+    corrupt = f"corrupt {what}: "
+    lists = cur.fourcc()
+    if lists != b"ilar":
+        raise RuntimeError(f"unsupported inverted lists {lists!r}: only array lists (\"ilar\") are readable")
+    if cur.take(_IVF_DIMS) != (nlist, code_size):
+        raise RuntimeError(corrupt + "the inverted lists do not match the header")
+    form = cur.fourcc()
+    sizes = np.zeros(nlist, dtype=np.int64)
+    if form == b"full":
+        sizes[:] = cur.vector(np.uint64, nlist, corrupt + "the size vector does not hold nlist entries").astype(np.int64)
+    elif form == b"sprs":
+        pairs = cur.vector(np.uint64, lambda count: count % 2 == 0 and count <= 2 * nlist,
+                           corrupt + "the sparse size vector does not hold (list, size) pairs").astype(np.int64).reshape(-1, 2)
+        if pairs.size and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= nlist):
+            raise RuntimeError(corrupt + "a list number outside [0, nlist)")
+        sizes[pairs[:, 0]] = pairs[:, 1]
+    else:
+        raise RuntimeError(f"unsupported list size form {form!r} in an {what} file")
+    if sizes.min() < 0 or int(sizes.sum()) != n:
+        raise RuntimeError(corrupt + "the list sizes do not add up to ntotal")
+    lists = []
+    for m in (int(s) for s in sizes):
+        codes = cur.array(np.uint8, m * code_size).reshape(m, code_size)
+        lists.append((cur.array(np.int64, m), codes))
+    return lists
 
 
 def _parse_ivfsq_at(cur: _Cursor) -> _IVFSQParts:
@@ -1293,29 +1338,9 @@ def _parse_ivfsq_at(cur: _Cursor) -> _IVFSQParts:
     qtype, rangestat, rangestat_arg, trained = _parse_sq_block_at(
         cur, d, "IndexIVFScalarQuantizer", corrupt + "the scalar quantiser does not match the header")
     code_size, by_residual = cur.take(_IVF_CODE)
-    lists = cur.fourcc()
-    if lists != b"ilar":
-        raise RuntimeError(f"unsupported inverted lists {lists!r}: only array lists (\"ilar\") are readable")
-    if (code_size,) + cur.take(_IVF_DIMS) != (d, nlist, d):
+    if code_size != d:
         raise RuntimeError(corrupt + "the inverted lists do not match the header")
-    form = cur.fourcc()
-    sizes = np.zeros(nlist, dtype=np.int64)
-    if form == b"full":
-        sizes[:] = cur.vector(np.uint64, nlist, corrupt + "the size vector does not hold nlist entries").astype(np.int64)
-    elif form == b"sprs":
-        pairs = cur.vector(np.uint64, lambda count: count % 2 == 0 and count <= 2 * nlist,
-                           corrupt + "the sparse size vector does not hold (list, size) pairs").astype(np.int64).reshape(-1, 2)
-        if pairs.size and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= nlist):
-            raise RuntimeError(corrupt + "a list number outside [0, nlist)")
-        sizes[pairs[:, 0]] = pairs[:, 1]
-    else:
-        raise RuntimeError(f"unsupported list size form {form!r} in an IndexIVFScalarQuantizer file")
-    if sizes.min() < 0 or int(sizes.sum()) != n:
-        raise RuntimeError(corrupt + "the list sizes do not add up to ntotal")
-    lists = []
-    for m in (int(s) for s in sizes):
-        codes = cur.array(np.uint8, m * d).reshape(m, d)
-        lists.append((cur.array(np.int64, m), codes))
+    lists = _parse_ivf_lists_at(cur, nlist, d, n, "IndexIVFScalarQuantizer")
     return _IVFSQParts(d, metric, int(nlist), int(nprobe), qmetric, centroids, qtype, trained, lists, rangestat,
                        rangestat_arg, bool(by_residual))
 
@@ -1327,6 +1352,77 @@ def parse_ivfsq(buf: bytes):
     return tuple(_parse_ivfsq_at(_Cursor(buf, _TRUNCATED_IVFSQ)))
 
 
+# IndexIVFPQ [upstream-faiss index_write.cpp write_index / write_ivf_header / write_ProductQuantizer /
+# write_InvertedLists, restated from memory of the published format and UNPINNED like the layouts above: there is no
+# sample file]:
+#   fourcc "IwPQ"; the IVF header of "IwSq": the index header (d, ntotal, 1<<20, 1<<20, is_trained, metric_type), uint64
+#   nlist, uint64 nprobe, the quantiser as its own "IxF2" / "IxFI" image, the direct map, empty: uint8 type (0), uint64
+#   count (0); then uint8 by_residual; uint64 code_size (= M); the product quantiser block of "IxPq": int64 d, int64 M,
+#   int64 nbits, the centroid vector (uint64 count = M * 256 * dsub, count float32); then the inverted lists as in "IwSq"
+#   with code_size = M.
+_FOURCC_IVFPQ = b"IwPQ"
+_IVFPQ_CODE = struct.Struct("<BQ")
+_TRUNCATED_IVFPQ = "truncated IndexIVFPQ file"
+_IVFPQParts = namedtuple("_IVFPQParts", "d metric nlist nprobe qmetric centroids M nbits pq_centroids lists by_residual")
+
+
+def serialize_ivfpq(d: int, metric: int, nlist: int, nprobe: int, qmetric: int, centroids, pq_centroids, lists,
+                    by_residual: bool = False) -> bytes:
+    """``centroids`` float32 (nlist, d) (or (0, d): an untrained quantiser) under the quantiser's metric ``qmetric``;
+    ``pq_centroids`` float32 (M, 256, d / M); ``lists``: ``nlist`` pairs (ids int64 (m,), codes uint8 (m, M)), any m, also 0."""
+    d, nlist = int(d), int(nlist)
+    c = np.ascontiguousarray(pq_centroids, dtype="<f4")
+    assert c.ndim == 3 and c.shape[1] == 256 and c.shape[0] * c.shape[2] == d, "the codebook is (M, 256, d / M)"
+    M = c.shape[0]
+    assert len(lists) == nlist, "one (ids, codes) pair per list"
+    pairs = [(np.ascontiguousarray(ids, dtype="<i8").reshape(-1), np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, M))
+             for ids, codes in lists]
+    assert all(ids.size == codes.shape[0] for ids, codes in pairs), "one id per code row"
+    head = [_HDR.pack(_FOURCC_IVFPQ, d, sum(ids.size for ids, _ in pairs), 1 << 20, 1 << 20, 1, int(metric)),
+            _IVF_DIMS.pack(nlist, int(nprobe)),
+            serialize_flat(d, int(qmetric), np.asarray(centroids, dtype=np.float32).reshape(-1, d)), _IVF_DIRECT_MAP.pack(0, 0),
+            _IVFPQ_CODE.pack(1 if by_residual else 0, M), _PQ_DIMS.pack(d, M, 8), _pack_vector(c)]
+    return b"".join(head) + _pack_ivf_lists(pairs, nlist, M)
+
+
+def _parse_ivfpq_at(cur: _Cursor) -> _IVFPQParts:
+    """(Every missing byte is ``_TRUNCATED_IVFPQ``: the cursor is made with it.)"""
+    corrupt = "corrupt IndexIVFPQ: "
+    cur.expect(_FOURCC_IVFPQ, "IndexIVFPQ")
+    _, d, n, _, _, _, metric = cur.take(_HDR)
+    nlist, nprobe = cur.take(_IVF_DIMS)
+    if d <= 0 or n < 0 or nlist <= 0:
+        raise RuntimeError("corrupt IndexIVFPQ header")
+    quantizer = cur.peek()
+    if quantizer not in (b"IxF2", b"IxFI"):
+        raise RuntimeError(f"unsupported quantiser type {quantizer!r} in an IndexIVFPQ file: only flat quantisers are readable")
+    d2, qmetric, centroids = _parse_flat_at(cur)
+    if d2 != d or centroids.shape[0] not in (0, nlist):
+        raise RuntimeError(corrupt + "the quantiser does not hold nlist centroids of dimension d")
+    if cur.take(_IVF_DIRECT_MAP) != (0, 0):
+        raise RuntimeError("an IndexIVFPQ file with a direct map is not readable")
+    by_residual, code_size = cur.take(_IVFPQ_CODE)
+    d3, M, nbits = cur.take(_PQ_DIMS)
+    if d3 != d or M <= 0 or d % M != 0 or nbits != 8:
+        raise RuntimeError(corrupt + "the product quantiser does not match the header (only 8-bit product quantisers are "
+                           "readable)")
+    if code_size != M:
+        raise RuntimeError(corrupt + "code_size is not M")
+    pq_centroids = cur.vector(np.float32, 256 * d, corrupt + "the centroid vector does not hold M * 256 * dsub floats"
+                              ).reshape(M, 256, d // M)
+    lists = _parse_ivf_lists_at(cur, nlist, M, n, "IndexIVFPQ")
+    return _IVFPQParts(d, metric, int(nlist), int(nprobe), qmetric, centroids, int(M), int(nbits), pq_centroids, lists,
+                       bool(by_residual))
+
+
+def parse_ivfpq(buf: bytes):
+    """-> (d, metric, nlist, nprobe, qmetric, centroids float32 (nlist or 0, d), M, nbits, pq_centroids float32 (M, 256,
+    d / M), lists [(ids int64 (m,), codes uint8 (m, M))] * nlist, by_residual).  Raises RuntimeError on a foreign,
+    truncated or miscounted file and on sub-quantisers of other than 8 bits; a file with ``by_residual`` set parses (reading
+    it into an index raises)."""
+    return tuple(_parse_ivfpq_at(_Cursor(buf, _TRUNCATED_IVFPQ)))
+
+
 # IndexRefineFlat [upstream-faiss index_write.cpp, restated from memory of the published format and UNPINNED like the
 # layouts above: there is no sample file]:
 #   fourcc "IxRF"; the index header (d, ntotal, 1<<20, 1<<20, is_trained, metric_type); the base index as its own file
@@ -1336,11 +1432,11 @@ _TRUNCATED_REFINE = "truncated IndexRefineFlat file"
 _RefineParts = namedtuple("_RefineParts", "d metric base_kind base xb k_factor")
 _K_FACTOR = struct.Struct("<f")
 _SUB_IMAGES = {b"IxF2": ("flat", _parse_flat_at), b"IxFI": ("flat", _parse_flat_at), _FOURCC_PQ: ("pq", _parse_pq_at),
-               _FOURCC_SQ: ("sq", _parse_sq_at)}
+               _FOURCC_SQ: ("sq", _parse_sq_at), _FOURCC_IVFPQ: ("ivfpq", _parse_ivfpq_at)}
 
 
 def _sub_image(cur: _Cursor):
-    """-> (kind "flat" | "pq" | "sq", the reader of the sub-index image at the cursor)."""
+    """-> (kind "flat" | "pq" | "sq" | "ivfpq", the reader of the sub-index image at the cursor)."""
     fourcc = cur.peek(_TRUNCATED_REFINE)
     if fourcc not in _SUB_IMAGES:
         raise RuntimeError(f"unsupported sub-index type {fourcc!r} in an IndexRefineFlat file")
@@ -1348,8 +1444,8 @@ def _sub_image(cur: _Cursor):
 
 
 def serialize_refine(base_image: bytes, d: int, metric: int, xb: np.ndarray, k_factor: float) -> bytes:
-    """``base_image``: the base index as ``serialize_flat``, ``serialize_pq`` or ``serialize_sq`` writes it; ``xb`` float32 (n, d): the
-    refine index's rows."""
+    """``base_image``: the base index as ``serialize_flat``, ``serialize_pq``, ``serialize_sq`` or ``serialize_ivfpq`` writes it;
+    ``xb`` float32 (n, d): the refine index's rows."""
     n = xb.shape[0] if np.size(xb) else 0
     head = _HDR.pack(_FOURCC_REFINE, int(d), n, 1 << 20, 1 << 20, 1, int(metric))
     return head + bytes(base_image) + serialize_flat(int(d), int(metric), xb) + _K_FACTOR.pack(float(k_factor))
@@ -1365,7 +1461,7 @@ def _parse_refine_at(cur: _Cursor) -> _RefineParts:
     if rkind != "flat":
         raise RuntimeError("corrupt IndexRefineFlat: the refine index is not a flat index")
     d2, metric2, xb = read(cur)
-    base_n = (base.xb if kind == "flat" else base.codes).shape[0]
+    base_n = sum(len(ids) for ids, _ in base.lists) if kind == "ivfpq" else (base.xb if kind == "flat" else base.codes).shape[0]
     if d2 != d or base.d != d or xb.shape[0] != n or base_n != n or metric2 != metric:
         raise RuntimeError("corrupt IndexRefineFlat: the sub-indexes do not match the header")
     (k_factor,) = cur.take(_K_FACTOR)
@@ -1373,8 +1469,8 @@ def _parse_refine_at(cur: _Cursor) -> _RefineParts:
 
 
 def parse_refine(buf: bytes):
-    """-> (d, metric, base_kind "flat" | "pq" | "sq", base as ``parse_flat`` / ``parse_pq`` / ``parse_sq`` return it, xb float32 (n, d),
-    k_factor); raises RuntimeError on a foreign, truncated or inconsistent file."""
+    """-> (d, metric, base_kind "flat" | "pq" | "sq" | "ivfpq", base as ``parse_flat`` / ``parse_pq`` / ``parse_sq`` /
+    ``parse_ivfpq`` return it, xb float32 (n, d), k_factor); raises RuntimeError on a foreign, truncated or inconsistent file."""
     parts = _parse_refine_at(_Cursor(buf, _TRUNCATED_REFINE))
     return tuple(parts._replace(base=tuple(parts.base)))
 
@@ -1390,7 +1486,7 @@ def write_index(index, path) -> None:
 
 
 def read_index(path, device: int | None = None):
-    """-> IndexFlat, IndexIDMap, IndexPQ, IndexScalarQuantizer, IndexIVFScalarQuantizer, IndexRefineFlat or
+    """-> IndexFlat, IndexIDMap, IndexPQ, IndexScalarQuantizer, IndexIVFScalarQuantizer, IndexIVFPQ, IndexRefineFlat or
     IndexPreTransform, as the file was written; the stored rows and codes are added as they are, nothing is encoded again."""
     with open(str(path), "rb") as f:
         buf = f.read()
@@ -1406,6 +1502,7 @@ _INDEX_FILES = {_FOURCC_IDMAP: (lambda: IndexIDMap, _parse_idmap_at, None),
                 _FOURCC_PQ: (lambda: IndexPQ, _parse_pq_at, None),
                 _FOURCC_SQ: (lambda: IndexScalarQuantizer, _parse_sq_at, None),
                 _FOURCC_IVFSQ: (lambda: IndexIVFScalarQuantizer, _parse_ivfsq_at, _TRUNCATED_IVFSQ),
+                _FOURCC_IVFPQ: (lambda: IndexIVFPQ, _parse_ivfpq_at, _TRUNCATED_IVFPQ),
                 _FOURCC_REFINE: (lambda: IndexRefineFlat, _parse_refine_at, _TRUNCATED_REFINE)}
 
 # ---------------------------------------------------------------- binary flat index (faiss.IndexBinaryFlat)
@@ -1730,11 +1827,6 @@ def read_index_binary(path, device: int | None = None):
     return index
 
 
-class IndexIVFPQ:  # backend/utils.py:323 ("cell-probe"): IndexIVFFlat's lists over IndexPQ's codes, not composed yet
-    def __init__(self, *a, **kw):
-        raise NotImplementedError("IndexIVFPQ ('cell-probe') is outside the exact brute-force hot path")
-
-
 class Kmeans:
     """``faiss.Kmeans`` as the reference drives it (backend/kmeans_faiss.py:29-44):
     ``Kmeans(d=, k=, niter=25, nredo=3, seed=42, spherical=True)``, ``.train(x, init_centroids=)``,
@@ -1834,8 +1926,9 @@ class _IndexIVF(_IndexHandle):
     its clustering in ``train``, the assignment of rows to lists, ``add``, ``get_list``, ``nprobe`` and ``search`` as
     ``search_preassigned`` of the quantiser's answer.  A subclass creates its handle, says what ``is_trained`` is and
     names its family of entry points (``_ABI``), the two search calls outright (``_search_host``, ``_search_device``),
-    its ``ntotal``, the dtype of a list's payload of (m, width) entries (``_LIST_DTYPE``) and whether it encodes its
-    rows (``_ENCODES``).  An index that does checks the rows of an ``add`` for NaN / inf entries, needs its training in
+    its ``ntotal``, the dtype of a list's payload of (m, list width) entries (``_LIST_DTYPE``; the list width is the rows'
+    unless ``_init_ivf`` is told another: a product quantiser stores ``M`` bytes for a row of ``d`` floats) and whether it
+    encodes its rows (``_ENCODES``).  An index that does checks the rows of an ``add`` for NaN / inf entries, needs its training in
     ``search_preassigned`` too and answers an empty batch there itself, and has no lists to read while its codec is
     untrained.  An index over bit codes also names its quantiser's type (``_QUANTIZER``), how rows and queries are
     coerced (``_COERCE``: ``_as_rows`` or ``_as_codes``, to ``_width`` entries a row) and the dtypes of a row's entries
@@ -1848,13 +1941,16 @@ class _IndexIVF(_IndexHandle):
     _LIST_DTYPE = np.float32
     _ENCODES = False
 
-    def _init_ivf(self, quantizer, d: int, nlist: int, metric: int | None, width: int | None = None) -> None:
-        """``metric``: None on an index without a ``metric_type``; ``width``: entries of a row where it is not ``d``."""
+    def _init_ivf(self, quantizer, d: int, nlist: int, metric: int | None, width: int | None = None,
+                  list_width: int | None = None) -> None:
+        """``metric``: None on an index without a ``metric_type``; ``width``: entries of a row where it is not ``d``;
+        ``list_width``: entries of a STORED row where it is not ``width``."""
         assert isinstance(quantizer, self._QUANTIZER), f"the coarse quantiser is an {self._QUANTIZER.__name__}"
         assert quantizer.d == int(d), f"dimension mismatch: quantizer has d={quantizer.d}, index d={d}"
         self.quantizer = quantizer
         self.d = int(d)
         self._width = self.d if width is None else int(width)
+        self._list_width = self._width if list_width is None else int(list_width)
         self.nlist = int(nlist)
         self.nprobe = 1
         if metric is not None:
@@ -1949,11 +2045,11 @@ class _IndexIVF(_IndexHandle):
         return int(sizes[int(l)])
 
     def get_list(self, l: int):
-        """(ids int64 (m,), rows (m, width) -- float32, or the uint8 codes of an index that encodes or holds bit codes)
-        of list ``l``, in list order (ascending ids)."""
+        """(ids int64 (m,), rows (m, list width) -- float32, or the uint8 codes of an index that encodes or holds bit
+        codes) of list ``l``, in list order (ascending ids)."""
         m = self.list_size(l)
         ids = np.empty(m, dtype=np.int64)
-        rows = np.empty((m, self._width), dtype=self._LIST_DTYPE)
+        rows = np.empty((m, self._list_width), dtype=self._LIST_DTYPE)
         if self._codec_trained():
             _n.check(self._fn("list_host")(self._h, int(l), ids.ctypes.data, rows.ctypes.data))
         return ids, rows
@@ -2167,21 +2263,42 @@ class IndexBinaryIVF(_IndexIVF):
 
 # ---------------------------------------------------------------- product quantisation (faiss.IndexPQ)
 class ProductQuantizer:
-    """``index.pq``: the view of an ``IndexPQ``'s codec that faiss.ProductQuantizer gives -- ``d``, ``M``, ``nbits``,
-    ``dsub``, ``ksub``, ``code_size``, ``centroids`` (a float32 (M, 256, dsub) copy), ``compute_codes`` and ``decode``.
-    ``set_centroids`` is an extension, in place of Faiss's ``copy_array_to_vector(c, pq.centroids)`` followed by
-    ``index.is_trained = True``."""
+    """``index.pq``: the view of an ``IndexPQ``'s (or ``IndexIVFPQ``'s) codec that faiss.ProductQuantizer gives -- ``d``,
+    ``M``, ``nbits``, ``dsub``, ``ksub``, ``code_size``, ``cp`` (the clustering parameters of ``train``), ``centroids`` (a
+    float32 (M, 256, dsub) copy), ``compute_codes`` and ``decode``.  ``set_centroids`` is an extension, in place of
+    Faiss's ``copy_array_to_vector(c, pq.centroids)`` followed by ``index.is_trained = True``."""
+
+    TRAIN_MAX_ROWS = 256 * 256  # Faiss's max_points_per_centroid x ksub
 
     def __init__(self, index):
         self._index = index
+        self.cp = ClusteringParameters(niter=25)
         self.d, self.M, self.nbits = index.d, index.M, 8
         self.dsub, self.ksub, self.code_size = index.d // index.M, 256, index.M
 
     @property
     def centroids(self) -> np.ndarray:
         out = np.empty((self.M, self.ksub, self.dsub), dtype=np.float32)
-        _n.check(_n.lib.ise_pq_get_centroids_host(self._index._h, out.ctypes.data))
+        _n.check(self._index._fn("get_centroids_host")(self._index._h, out.ctypes.data))
         return out
+
+    def train(self, x, cp=None) -> None:
+        """One ``Kmeans(dsub, 256)`` per sub-quantiser on its columns of ``x`` (at most ``256 * 256`` rows, drawn with a
+        generator seeded by ``cp.seed``), ``niter`` and ``seed`` from ``cp`` (``self.cp`` unless given), then
+        ``set_centroids``."""
+        cp = self.cp if cp is None else cp
+        x = _as_rows(x, self.d)
+        if x.shape[0] < 256:
+            raise RuntimeError(f"{x.shape[0]} training rows for 256 centroids per sub-quantiser")
+        if x.shape[0] > self.TRAIN_MAX_ROWS:
+            pick = np.random.default_rng(cp.seed).choice(x.shape[0], self.TRAIN_MAX_ROWS, replace=False)
+            x = x[np.sort(pick)]
+        c = np.empty((self.M, 256, self.dsub), dtype=np.float32)
+        for m in range(self.M):
+            km = Kmeans(self.dsub, 256, niter=cp.niter, seed=cp.seed)
+            km.train(np.ascontiguousarray(x[:, m * self.dsub:(m + 1) * self.dsub]))
+            c[m] = km.centroids
+        self.set_centroids(c)
 
     def set_centroids(self, c) -> None:
         """float32 (M, 256, dsub), finite; refused while the index holds rows (their codes belong to the centroids in
@@ -2192,8 +2309,8 @@ class ProductQuantizer:
             raise ValueError("a centroid has a NaN or inf entry")
         if self._index.ntotal > 0:
             raise RuntimeError("set_centroids on an index that holds rows: reset() first")
-        _n.check(_n.lib.ise_pq_set_centroids_host(self._index._h, c.ctypes.data))
-        self._index.is_trained = True
+        _n.check(self._index._fn("set_centroids_host")(self._index._h, c.ctypes.data))
+        self._index._trained_set()
 
     def compute_codes(self, x) -> np.ndarray:
         return self._index.sa_encode(x)
@@ -2340,7 +2457,7 @@ class IndexPQ(_CodedIndex):
     ``IndexIDMap`` over this type."""
 
     _ABI = "ise_pq"
-    TRAIN_MAX_ROWS = 256 * 256  # Faiss's max_points_per_centroid x ksub
+    TRAIN_MAX_ROWS = ProductQuantizer.TRAIN_MAX_ROWS
     _NO_PARAMS = "selectors, polysemous search"
     _search_host = staticmethod(_n.lib.ise_pq_search_host)
     _search_device = staticmethod(_n.lib.ise_pq_search_device)
@@ -2359,6 +2476,10 @@ class IndexPQ(_CodedIndex):
         self._lock = threading.Lock()
         _n.check(_n.lib.ise_pq_create(ctypes.byref(self._h), self.d, self.M, 8, self.metric_type, self.device))
         self.pq = ProductQuantizer(self)
+        self.pq.cp = self.cp
+
+    def _trained_set(self) -> None:  # ProductQuantizer.set_centroids has set the codebook
+        self.is_trained = True
 
     @classmethod
     def _from_parts(cls, parts, device, add_codes: bool = True):
@@ -2385,19 +2506,7 @@ class IndexPQ(_CodedIndex):
         quantiser's clustering as restated from memory: unpinned, like the seeding of ``Kmeans`` itself."""
         if self.is_trained:
             return
-        x = _as_rows(x, self.d)
-        if x.shape[0] < 256:
-            raise RuntimeError(f"{x.shape[0]} training rows for 256 centroids per sub-quantiser")
-        if x.shape[0] > self.TRAIN_MAX_ROWS:
-            pick = np.random.default_rng(self.cp.seed).choice(x.shape[0], self.TRAIN_MAX_ROWS, replace=False)
-            x = x[np.sort(pick)]
-        dsub = self.d // self.M
-        c = np.empty((self.M, 256, dsub), dtype=np.float32)
-        for m in range(self.M):
-            km = Kmeans(dsub, 256, niter=self.cp.niter, seed=self.cp.seed)
-            km.train(np.ascontiguousarray(x[:, m * dsub:(m + 1) * dsub]))
-            c[m] = km.centroids
-        self.pq.set_centroids(c)
+        self.pq.train(x, self.cp)
 
 
 # ---------------------------------------------------------------- scalar quantisation (faiss.IndexScalarQuantizer)
@@ -2668,10 +2777,157 @@ class IndexIVFScalarQuantizer(_IndexIVF):
         return index
 
 
+# ---------------------------------------------------------------- inverted lists over product-quantiser codes (faiss.IndexIVFPQ)
+def _ivfpq_args(quantizer=None, d=0, nlist=0, M=0, nbits=8, metric=METRIC_L2, by_residual=True):
+    """``IndexIVFPQ``'s constructor arguments, by position or by name."""
+    return quantizer, d, nlist, M, nbits, metric, by_residual
+
+
+class IndexIVFPQ(_IndexIVF):
+    """faiss.IndexIVFPQ(quantizer, d, nlist, M, nbits=8, metric=METRIC_L2, by_residual=False) with 8-bit sub-quantisers:
+    ``IndexIVFFlat``'s lists holding ``IndexPQ``'s code rows -- the reference's "cell-probe" index (backend/utils.py:311-325)
+    over codes of the rows themselves.  The codec is ``IndexPQ``'s: the same codebook ``[M][256][d / M]``, code bytes and
+    decoded rows for the same ``pq.centroids``.  ``add`` files row i under ``quantizer.search(x, 1)[1][i]``; ``search``
+    visits the ``nprobe`` lists nearest each query and returns the exact k best among their rows by the table-lookup
+    score: D has the bits ``IndexPQ.search`` reports for the same (query, row) pair and codebook, ties go by ascending id,
+    unfilled slots are -1 / +-FLT_MAX, a query with a NaN or inf entry gets padding only.  With ``nprobe == nlist`` the
+    result is ``IndexPQ.search`` itself.
+
+    ``by_residual=True`` -- Faiss's default, and this constructor's -- raises ``NotImplementedError`` before anything else
+    is looked at, and so does assigning it afterwards: a residual code makes the lookup tables differ per (query, list),
+    which needs a table builder and a scan of their own.  Pass ``by_residual=False``.  (The constructor
+    takes its arguments as ``*a, **kw``, the signature it had while the type was not provided; they are the ones above.)
+
+    ``cp`` holds the clustering parameters of the coarse quantiser (``niter`` 10), ``pq.cp`` those of the codebook
+    (``niter`` 25): the same rows, ``pq.cp`` and seed give ``IndexPQ.train``'s codebook bit for bit.
+
+    On the device (include/ise_knn.h, ise_ivfpq_*): ``add`` encodes into a pending buffer, the first search
+    after an ``add`` rebuilds the lists.  Not provided (they raise ``NotImplementedError``): ``nbits != 8``, residual
+    codes, ``range_search``, ``remove_ids``, ``params=``, ``add_with_ids`` and ``IndexIDMap`` over this type."""
+
+    _ABI = "ise_ivfpq"
+    _search_device = staticmethod(_n.lib.ise_ivfpq_search_device)
+    _search_host = staticmethod(_n.lib.ise_ivfpq_search_host)
+    _LIST_DTYPE = np.uint8
+    _ENCODES = True
+    ntotal = _ntotal_property(_n.lib.ise_ivfpq_info, 9, 6)
+
+    def __init__(self, *a, **kw):
+        quantizer, d, nlist, M, nbits, metric, by_residual = _ivfpq_args(*a, **kw)
+        if by_residual:
+            raise NotImplementedError("IndexIVFPQ with by_residual = True (Faiss's default) is not provided: pass "
+                                      "by_residual=False (codes of the rows themselves, not of their residuals)")
+        if int(nbits) != 8:
+            raise NotImplementedError(f"IndexIVFPQ with nbits = {nbits}: only 8-bit sub-quantisers are provided")
+        self.M = int(M)
+        assert 1 <= self.M <= _n.PQ_MAX_M and int(d) % self.M == 0, f"1 <= M <= {_n.PQ_MAX_M}, and M divides d"
+        self._init_ivf(quantizer, d, nlist, metric, list_width=self.M)
+        self.code_size = self.M
+        self._pq_trained = False
+        self._codec = None
+        _n.check(_n.lib.ise_ivfpq_create(ctypes.byref(self._h), self.d, self.M, 8, self.metric_type, self.nlist, self.device))
+        self.pq = ProductQuantizer(self)
+
+    @property
+    def by_residual(self) -> bool:
+        return False
+
+    @by_residual.setter
+    def by_residual(self, value) -> None:
+        if value:
+            raise NotImplementedError("IndexIVFPQ with by_residual = True is not provided (codes of the rows themselves only)")
+
+    @property
+    def is_trained(self) -> bool:
+        return self._pq_trained and self.quantizer.ntotal == self.nlist
+
+    def _codec_trained(self) -> bool:  # the index is trained with its quantiser only; the lists need the codec alone
+        return self._pq_trained
+
+    def _trained_set(self) -> None:  # ProductQuantizer.set_centroids has set the codebook
+        self._pq_trained = True
+        self._codec = None
+
+    # -- build side
+    def train(self, x) -> None:
+        """The quantiser's k-means as ``IndexIVFFlat.train`` (nothing when it holds ``nlist`` centroids), then the
+        codebook on the rows themselves as ``IndexPQ.train`` with ``pq.cp`` (nothing when the centroids are set)."""
+        self._train_quantizer(x)
+        if not self._pq_trained:
+            self.pq.train(x)
+
+    def _add_codes(self, codes: np.ndarray, lists: np.ndarray) -> None:
+        codes = _as_codes(codes, self.M)
+        lists = np.ascontiguousarray(lists, dtype=np.int64).reshape(-1)
+        assert lists.size == codes.shape[0], "one list number per code row"
+        _n.check(_n.lib.ise_ivfpq_add_codes_host(self._h, codes.ctypes.data, lists.ctypes.data, codes.shape[0]))
+
+    # -- the codec: an empty IndexPQ with the same centroids (ise_ivfpq_* has no encode / decode entry)
+    def _codec_index(self):
+        if not self._pq_trained:
+            raise RuntimeError("IndexIVFPQ's codec before train")
+        if self._codec is None:
+            codec = IndexPQ(self.d, self.M, 8, self.metric_type, self.device)
+            codec.pq.set_centroids(self.pq.centroids)
+            self._codec = codec
+        return self._codec
+
+    def sa_code_size(self) -> int:
+        return self.code_size
+
+    def sa_encode(self, x) -> np.ndarray:
+        """uint8 (n, M): the codes ``add`` would store."""
+        return self._codec_index().sa_encode(x)
+
+    def sa_decode(self, codes) -> np.ndarray:
+        return self._codec_index().sa_decode(codes)
+
+    def ivfpq_stats(self) -> dict:
+        """Search batches, scan passes (one per QT(M) queries and 32 results), 64-row tiles of list rows the passes
+        visited, table builds (one per 64 queries) (include/ise_knn.h, ise_ivfpq_stats).  Waits for the device."""
+        return _counters(_n.lib.ise_ivfpq_stats, self._h, ("batches", "passes", "tiles_loaded", "table_builds"))
+
+    # -- files
+    def _image(self) -> bytes:
+        self._require_trained("write_index")
+        qz = self.quantizer
+        lists = [self.get_list(l) for l in range(self.nlist)]
+        return serialize_ivfpq(self.d, self.metric_type, self.nlist, int(self.nprobe), qz.metric_type,
+                               qz.reconstruct_n(0, qz.ntotal), self.pq.centroids, lists, False)
+
+    def _add_lists(self, lists) -> None:
+        """The stored codes of a parsed image, added as they are, in the order of their ids, which have to be the
+        insertion numbers 0 .. ntotal - 1."""
+        ids = np.concatenate([ids for ids, _ in lists]) if lists else np.zeros(0, np.int64)
+        if ids.size:
+            order = np.argsort(ids, kind="stable")
+            if not np.array_equal(ids[order], np.arange(ids.size)):
+                raise RuntimeError("an IndexIVFPQ file whose ids are not the insertion numbers 0 .. ntotal - 1 is not readable")
+            codes = np.concatenate([codes for _, codes in lists])
+            list_no = np.repeat(np.arange(self.nlist, dtype=np.int64), [len(ids) for ids, _ in lists])
+            self._add_codes(codes[order], list_no[order])
+
+    @classmethod
+    def _from_parts(cls, parts, device, add_codes: bool = True):
+        """The index a parsed "IwPQ" image describes (``parse_ivfpq``)."""
+        if parts.by_residual:
+            raise NotImplementedError("read_index of an IndexIVFPQ file with by_residual = true is not provided")
+        quantizer = IndexFlat(parts.d, parts.qmetric, device)
+        if parts.centroids.shape[0]:
+            quantizer.add(parts.centroids)
+        index = cls(quantizer, parts.d, parts.nlist, parts.M, parts.nbits, parts.metric, by_residual=False)
+        index.nprobe = parts.nprobe
+        index.pq.set_centroids(parts.pq_centroids)
+        if add_codes:
+            index._add_lists(parts.lists)
+        return index
+
+
 # ---------------------------------------------------------------- exact re-ranking (faiss.IndexRefine / IndexRefineFlat)
 class IndexRefine:
     """faiss.IndexRefine(base_index, refine_index): ``search`` asks ``base_index`` -- an ``IndexFlat`` of either storage,
-    an ``IndexPQ``, an ``IndexScalarQuantizer``, an ``IndexIVFFlat`` or an ``IndexIVFScalarQuantizer`` -- for ``int(k * k_factor)`` labels and returns the k best of them by the exact
+    an ``IndexPQ``, an ``IndexScalarQuantizer``, an ``IndexIVFFlat``, an ``IndexIVFScalarQuantizer`` or an ``IndexIVFPQ`` -- for
+    ``int(k * k_factor)`` labels and returns the k best of them by the exact
     score ``refine_index`` (a float32 ``IndexFlat`` that holds the same rows) computes: D has the bits
     ``refine_index.search`` reports for the same (query, row) pair, ties go by ascending id, unfilled slots are
     -1 / +-FLT_MAX; -1 labels of the base are ignored.  With ``k * k_factor >= ntotal`` the result is
@@ -2683,8 +2939,8 @@ class IndexRefine:
 
     def __init__(self, base_index, refine_index):
         assert isinstance(base_index, (IndexFlat, IndexPQ, IndexScalarQuantizer, _IndexIVF, IndexPreTransform)), \
-            "the base index is an IndexFlat, an IndexPQ, an IndexScalarQuantizer, an IndexIVFFlat, an IndexIVFScalarQuantizer " \
-            "or an IndexPreTransform over one of them"
+            "the base index is an IndexFlat, an IndexPQ, an IndexScalarQuantizer, an IndexIVFFlat, an IndexIVFScalarQuantizer, " \
+            "an IndexIVFPQ or an IndexPreTransform over one of them"
         assert base_index.ntotal == 0, f"{type(self).__name__} wraps an empty index (Faiss: index is empty on input)"
         assert isinstance(refine_index, IndexFlat) and refine_index.storage == "f32", \
             "the refine index is a float32 IndexFlat"
@@ -2767,13 +3023,13 @@ class IndexRefine:
 
     def _image(self) -> bytes:
         base = self.base_index
-        if isinstance(base, _CodedIndex):
+        if isinstance(base, (_CodedIndex, IndexIVFPQ)):
             image = base._image()
         elif type(base) in (IndexFlat, IndexFlatL2, IndexFlatIP) and base.storage == "f32":
             image = _flat_image(base)
         else:
             raise NotImplementedError(f"write_index of an IndexRefine over {type(base).__name__} is not provided "
-                                      "(float32 IndexFlat, IndexPQ and IndexScalarQuantizer bases are)")
+                                      "(float32 IndexFlat, IndexPQ, IndexScalarQuantizer and IndexIVFPQ bases are)")
         rf = self.refine_index
         return serialize_refine(image, self.d, self.metric_type, rf.reconstruct_n(0, rf.ntotal), self.k_factor)
 
@@ -2798,12 +3054,14 @@ class IndexRefineFlat(IndexRefine):
         if kind == "flat":
             base = IndexFlat(parts.d, stored.metric, device)
         else:
-            base = {"pq": IndexPQ, "sq": IndexScalarQuantizer}[kind]._from_parts(stored, device, add_codes=False)
+            base = {"pq": IndexPQ, "sq": IndexScalarQuantizer, "ivfpq": IndexIVFPQ}[kind]._from_parts(stored, device, add_codes=False)
         index = cls(base)
         index.k_factor = parts.k_factor
         if parts.xb.shape[0]:
             if kind == "flat":
                 base.add(stored.xb)
+            elif kind == "ivfpq":
+                base._add_lists(stored.lists)
             else:
                 base._add_codes(stored.codes)
             index.refine_index.add(parts.xb)

@@ -75,7 +75,10 @@ def hashes_to_codes(hashes, nbits=64):
 def create_search_index(data_array, index_type="cosine"):
     """backend/utils.py:293-330.  'cosine' -> IndexFlatIP over rows normalised IN
     PLACE in the caller's array (quirk 5.9-6); 'l2' -> IndexFlatL2; then add.
-    'cell-probe' (IndexIVFPQ) is approximate and outside the scoped path; 'cell-probe-flat' is that branch
+    'cell-probe' is IndexIVFPQ with Faiss's default residual codes, which is not provided (NotImplementedError before any
+    device call); 'cell-probe-pq' is that branch (backend/utils.py:311-325) with by_residual=False: IndexIVFPQ over an L2
+    coarse quantiser with the reference's 8 centroids, m = 16 codes of 8 bits and nprobe = 5, trained on the data, then
+    add.  'cell-probe-flat' is that branch
     (backend/utils.py:311-325) without the product quantiser: IndexIVFFlat over an L2 coarse quantiser with the
     reference's 8 centroids and nprobe = 5, trained on the data, then add.  'pq' is that branch's product quantiser
     without the lists: IndexPQ with the reference's m = 16 codes of 8 bits, trained on the data, then add.
@@ -93,7 +96,8 @@ def create_search_index(data_array, index_type="cosine"):
     elif index_type == "l2":
         index = faiss.IndexFlatL2(num_features)
     elif index_type == "cell-probe":
-        raise NotImplementedError("'cell-probe' (IndexIVFPQ) is outside the exact brute-force hot path")
+        raise NotImplementedError("'cell-probe' is IndexIVFPQ with Faiss's default by_residual = True, which is not "
+                                  "provided: 'cell-probe-pq' is the same index over codes of the rows themselves")
     elif index_type == "cell-probe-flat":
         ncentroids = 8
         coarse_quantizer = faiss.IndexFlatL2(num_features)
@@ -111,6 +115,13 @@ def create_search_index(data_array, index_type="cosine"):
         index.train(data_array)
     elif index_type == "sq8":
         index = faiss.IndexScalarQuantizer(num_features, faiss.ScalarQuantizer.QT_8bit)
+        index.train(data_array)
+    elif index_type == "cell-probe-pq":
+        ncentroids = 8
+        code_size = 16
+        coarse_quantizer = faiss.IndexFlatL2(num_features)
+        index = faiss.IndexIVFPQ(coarse_quantizer, num_features, ncentroids, code_size, 8, by_residual=False)
+        index.nprobe = 5  # find n most similar clusters
         index.train(data_array)
     elif index_type == "cell-probe-sq8":
         ncentroids = 8

@@ -621,6 +621,53 @@ int ise_ivfsq_search_device(ise_ivfsq_t* h, const float* q_dev, int64_t nq, int 
                             float* D_dev, int64_t* I_dev, void* stream);
 int ise_ivfsq_stats(ise_ivfsq_t* h, uint64_t* out3);
 
+/* Inverted lists over product-quantiser codes: faiss.IndexIVFPQ with by_residual = false and 8-bit sub-quantisers
+ * (csrc/ise_ivfpq.hpp).  An ise_ivfpq_t is ise_ivf_t's lists holding ise_pq_t's code rows: nlist lists of M code bytes
+ * per row, NO coarse centroids (the coarse quantiser is the caller's; rows come with their list numbers, searches with
+ * their probe tables, as for ise_ivf_*), and the codec, codebook, code bytes and scores of ise_pq_* for the same
+ * centroids.  Calls, streams and workspaces as for ise_ivf_*.
+ *   create        d > 0, 1 <= M <= ISE_PQ_MAX_M, d % M == 0, nbits == 8, nlist >= 1, one of the two metrics; anything
+ *                 else is ISE_E_INVALID before the device is touched.  Untrained until the centroids are set; every
+ *                 entry point below except reset / info / list_sizes / stats is then ISE_E_INVALID
+ *   centroids     as ise_pq_set_centroids_host / ise_pq_get_centroids_host: [M][256][d / M] float32
+ *   add           list_no[i] in [0, nlist) is the list of row i; a number outside makes the call ISE_E_INVALID and
+ *                 nothing is added.  The rows are encoded at once (ise_pq_*'s encoder) into a pending buffer; a row with
+ *                 a NaN or inf entry makes the call ISE_E_INVALID ("NaN or inf" in the message) and NOTHING of that call
+ *                 is added.  All forms block.  add_codes takes ready-made codes (n x M bytes).  A row's id is its
+ *                 insertion number; fewer than 2^32 rows.  The first search or list_host after an add rebuilds the lists
+ *                 (64-row tiles; one rebuild moves the whole index)
+ *   list_sizes    rows per list, pending ones included
+ *   list          ids (ascending) and codes (m x M bytes) of one list, in list order; either may be NULL
+ *   search        probes: nq x nprobe list numbers; -1 and numbers outside [0, nlist) name nothing, a list named twice
+ *                 counts once.  The k best among the rows of a query's probed lists, scored as ise_pq_search_* scores
+ *                 the same (query, row) pair -- the same tables, summed from +0.0f over ascending m: the same bits --;
+ *                 ties by ascending id; unfilled slots are id -1 with +-FLT_MAX; a query with a NaN or inf entry gets
+ *                 padding only.  A pass serves QT queries and 32 results (QT as for ise_pq_*) and reads the 64-row tiles
+ *                 of the lists that at least one of its queries probes, and no others; a call makes ceil(nq / QT) x
+ *                 ceil(k / 32) passes and one table build per 64 queries, none of either on an empty index.
+ *                 search_device only enqueues, unless rows are pending or a workspace has to grow; search_host works
+ *                 through 4096 queries at a time
+ *   stats         out4[0] = search batches, out4[1] = scan passes, out4[2] = 64-row tiles the passes visited, out4[3] =
+ *                 table builds.  Waits for the device */
+typedef struct ise_ivfpq ise_ivfpq_t;
+int ise_ivfpq_create(ise_ivfpq_t** out, int d, int M, int nbits, int metric, int nlist, int device);
+int ise_ivfpq_destroy(ise_ivfpq_t* h); /* NULL is a no-op */
+int ise_ivfpq_reset(ise_ivfpq_t* h);   /* drop all rows, keep the centroids */
+int ise_ivfpq_info(const ise_ivfpq_t* h, int* d, int* M, int* nbits, int* metric, int* nlist, int64_t* ntotal, int* is_trained,
+                   int* device);
+int ise_ivfpq_set_centroids_host(ise_ivfpq_t* h, const float* c /* M * 256 * (d / M) floats */);
+int ise_ivfpq_get_centroids_host(ise_ivfpq_t* h, float* c);
+int ise_ivfpq_add_host(ise_ivfpq_t* h, const float* x, const int64_t* list_no, int64_t n);
+int ise_ivfpq_add_device(ise_ivfpq_t* h, const float* x_dev, const int64_t* list_no_dev, int64_t n, void* stream);
+int ise_ivfpq_add_codes_host(ise_ivfpq_t* h, const uint8_t* codes, const int64_t* list_no, int64_t n);
+int ise_ivfpq_list_sizes_host(ise_ivfpq_t* h, int64_t* sizes /* nlist */);
+int ise_ivfpq_list_host(ise_ivfpq_t* h, int list, int64_t* ids, uint8_t* codes);
+int ise_ivfpq_search_host(ise_ivfpq_t* h, const float* q, int64_t nq, int k, const int64_t* probes, int nprobe, float* D,
+                          int64_t* I);
+int ise_ivfpq_search_device(ise_ivfpq_t* h, const float* q_dev, int64_t nq, int k, const int64_t* probes_dev, int nprobe,
+                            float* D_dev, int64_t* I_dev, void* stream);
+int ise_ivfpq_stats(ise_ivfpq_t* h, uint64_t* out4);
+
 /* Inverted lists over bit codes: faiss.IndexBinaryIVF (csrc/ise_binary_ivf.hpp).  An ise_binary_ivf_t is ise_ivfsq_t's
  * lists holding ise_binary_index_t's codes: nlist lists of d_bits / 8 code bytes, NO centroids (the coarse quantiser is
  * the caller's; rows come with their list numbers, searches with their probe tables, as for ise_ivf_*), and the Hamming
